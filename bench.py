@@ -5,7 +5,12 @@ Workload (BASELINE.json configs[1], SURVEY.md section 8d "synthetic-10x-v1"): A=
 B=5000 cells x D=5000 genes, H=100, L=10, C=92, S=2, fp32, x_drop=0.5, in-kernel Philox noise, the batch
 already resident in HBM.  A "step" = one batch through mmvae_train_step (cpl_mixvae.py:434-463).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR then also writes what
+the last timed step computed (see dump_outputs).  Everything measured beside the headline -- the roofline of the dominant
+kernel, the bf16 configuration, the other workload configurations, the CPU baselines and the evaluation / augmenter /
+data-path rows -- runs only under --full (and there each part can still be switched off with its --no-* option).
 
 N > 1 either runs under a launcher (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE) or -- when those are
 absent -- starts its own N rank processes (one per GPU, before this process has touched any GPU; the reference does the
@@ -14,7 +19,7 @@ same with mp.spawn, train.py:286) and exits with their status.  Fewer than N vis
 N>1 is plain data parallelism: each rank trains on its own shard of cells, ONE RCCL all-reduce
 (average) of the flat gradient buffer per step, Adam on every rank ("weak" scaling: per-GPU batch fixed).
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  Under --full, besides the contract fields it carries
   "roofline":     dominant kernel (fc11 forward + loss + dZ11 + d(d10) in one launch: k_x3_fc11g under the default fp32x3
                   engine, k_fc11_zg under --gemm-dtype fp32_mfma): ALGORITHMIC FLOPs (A 4 B D H) and bytes (A 8 B D) per
                   launch / its average duration measured with HIP events on the launch stream.  `bound` / `achieved` /
@@ -159,8 +164,8 @@ def bf16_config(args, model_args, data, batches, nb, A, B, D, H, L, C, S, P, wor
             return DD.dp_train_step(m, xs, 1.0, opt, rehearse=args.rehearse_dp)
         return m.fused_train_step(xs, 1.0, opt, do_adam=True)
 
-    dt32, ev32, loss32 = timed(step32)
-    dt, ev, loss = timed(step16) if storage else (dt32, ev32, loss32)
+    dt32, ev32, loss32, _ = timed(step32)
+    dt, ev, loss, _ = timed(step16) if storage else (dt32, ev32, loss32, None)
     # the same K steps through a FIXED RANDOM permutation of the resident rows (drawn outside the timed region): what a shuffled
     # epoch asks of the 16-byte bf16 row reads; `value` above uses contiguous row sets
     shuffled = None
@@ -173,7 +178,7 @@ def bf16_config(args, model_args, data, batches, nb, A, B, D, H, L, C, S, P, wor
             if world > 1 or args.rehearse_dp:
                 return DD.dp_train_step(m, None, 1.0, opt, rehearse=args.rehearse_dp, rows=(data, prows[i % nb], data16))
             return m.fused_train_step_rows(data, prows[i % nb], 1.0, opt, do_adam=True, data16=data16)
-        dtp, evp, _ = timed(step16p)
+        dtp, evp, _, _ = timed(step16p)
         shuffled = {"ms_per_step": dtp / args.steps * 1e3, "value": world * B * args.steps / dtp, "ms_per_step_hip_events": evp,
                     "rows": "a fixed random permutation of the resident rows (torch.randperm, seeded), B per step"}
     cells = world * B * args.steps / dt
@@ -341,6 +346,11 @@ def main():
                     help="one rank, but through the data-parallel step (RCCL init, all-reduce(AVG) of the flat gradients, "
                          "separate Adam launch): exercises the N > 1 code path on a one-GPU box")
     ap.add_argument("--log-dir", default="", help="N > 1 without a launcher: directory for the ranks' rank<r>.err files")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline, bf16 configuration, other configurations, "
+                         "CPU baselines, evaluation / augmenter / data-path rows); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -458,9 +468,11 @@ def main():
         per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
         stats = {"median": per[len(per) // 2], "min": per[0], "max": per[-1], "p10": per[len(per) // 10],
                  "p90": per[(9 * len(per)) // 10], "n": len(per)}
-        return float(tmax), stats, float(buf_[0])
+        return float(tmax), stats, float(buf_[0]), buf_
 
-    dt, ev_stats, loss_last = timed(step)
+    dt, ev_stats, loss_last, last_buf = timed(step)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, last_buf)
 
     P = 0
     lay = N.param_layout(N.Dims(A, B, D, H, L, C, S))
@@ -471,7 +483,7 @@ def main():
     cells_per_s = world * B * args.steps / dt
 
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         try:
             roof = measure_stages(model, batches[0], A, B, D, H)
         except Exception as e:   # noqa: BLE001
@@ -514,14 +526,14 @@ def main():
         # the --share-gpu rehearsal, which is not an RCCL observation)
         out["collective_ranks"] = rccl_ranks
         out["collective_backend"] = "rccl (torch.distributed nccl)" if backend == "nccl" else backend
-    if args.gemm_dtype != "bf16" and not args.no_bf16:
+    if args.full and args.gemm_dtype != "bf16" and not args.no_bf16:
         # BASELINE.json configs[2] beside the headline: the same step with bf16 operands in the five D x H GEMMs
         try:
             out["bf16_config"] = bf16_config(args, model_args, data, batches, nb, A, B, D, H, L, C, S, P_count(N, A, B, D, H, L, C, S),
                                              world, rank, dev, timed, DD, FusedAdam, mixVAE_model)
         except Exception as e:   # noqa: BLE001
             out["bf16_config"] = {"error": f"{type(e).__name__}: {e}"}
-    if (rank == 0 and world == 1 and not args.no_other_configs and args.gemm_dtype != "bf16"
+    if (args.full and rank == 0 and world == 1 and not args.no_other_configs and args.gemm_dtype != "bf16"
             and (A, B, D) == (2, 5000, 5000)):
         try:
             out["other_configs"] = other_configs(args, dev, data, B, mixVAE_model, FusedAdam, N)
@@ -529,12 +541,12 @@ def main():
             out["other_configs"] = {"error": f"{type(e).__name__}: {e}"}
     if roof is not None:
         out["roofline"] = roof
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args, D, H, L, C, S, A, B)
         except Exception as e:   # noqa: BLE001
             out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_eval:
+    if args.full and rank == 0 and world == 1 and not args.no_eval:
         # the widened rows beside the headline metric; a failure here must not cost the JSON line
         for key, fn in (("eval_consensus", lambda: eval_consensus(args, model, batches, A, B, D, H, L, C, S, not args.no_cpu_baseline)),
                         ("augmenter", lambda: augmenter_forward(args, batches, A, B, D, not args.no_cpu_baseline)),
@@ -551,6 +563,40 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, buf):
+    """What the last timed step handed its caller, as float32 .npy files in ``out_dir``: ``loss`` (the step's loss
+    vector, include/mmvae.h MMVAE_LOSS_*), ``parameters`` (every parameter after the step's Adam update), ``gradients``
+    (the step's gradients) and ``running_stats`` (the BatchNorm running means / variances after the step); the last three
+    are concatenated in state_dict order.  The inputs are seeded, so the same arguments give the same inputs on every
+    run.  Should the files exceed 64 MB in all (large --genes / --arms), every large array is cut to a fixed, seeded
+    sample of its entries (the same positions on every run)."""
+    torch.cuda.synchronize()
+    model.bind_grads()
+    params = [p for _, p in model.named_parameters()]
+    arrays = {
+        "loss": buf.detach().float().cpu().numpy(),
+        "parameters": torch.cat([p.detach().reshape(-1) for p in params]).float().cpu().numpy(),
+        "gradients": torch.cat([p.grad.detach().reshape(-1) for p in params]).float().cpu().numpy(),
+        "running_stats": torch.cat([v.detach().reshape(-1) for k, v in model.state_dict().items()
+                                    if k.endswith(("running_mean", "running_var"))]).float().cpu().numpy(),
+    }
+    big = [name for name, a in arrays.items() if a.size > 4096]
+    small_bytes = sum(a.nbytes for name, a in arrays.items() if name not in big)
+    big_bytes = sum(arrays[name].nbytes for name in big)
+    if small_bytes + big_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - small_bytes) / big_bytes
+        for name in big:
+            a = arrays[name]
+            idx = np.sort(np.random.default_rng(546).choice(a.size, size=int(a.size * keep), replace=False))
+            arrays[name] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def eval_consensus(args, model, batches, A, B, D, H, L, C, S, with_cpu):

@@ -2,10 +2,10 @@
 
 This file reads ``/root/reference`` and therefore only works in the build
 container; nothing on the GPU box (``-m gpu`` tests, ``smoke()``, ``bench.py``)
-imports it.  It is used by ``oracle/gen_golden.py`` (to emit the committed
-fixtures under ``tests/golden/``) and by ``tests/test_oracle_vs_reference.py``
-(skipped when ``/root/reference`` is absent) to pin ``oracle/restatement.py``
-to the reference's own arithmetic.
+imports it.  It is used by the ``oracle/gen_golden*.py`` generators only, to
+emit the committed fixtures under ``tests/golden/`` (``gen_golden_ref.py``
+records the cases with which the tests pin ``oracle/restatement.py`` to the
+reference's own arithmetic); no test imports it.
 
 How the reference is loaded:
 ``/root/reference/mmidas/nn_model.py`` needs Python >= 3.12 only for two lines

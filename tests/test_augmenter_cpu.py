@@ -1,6 +1,6 @@
-"""CPU: the augmenter oracle (oracle/augmenter.py) against the reference-generated fixture (tests/golden/aug_small.npz,
-written by oracle/gen_golden_aug.py from the real reference class) and, in the build container, against the live
-reference class on fresh random cases."""
+"""CPU: the augmenter oracle (oracle/augmenter.py) against the reference-generated fixtures (tests/golden/aug_small.npz,
+written by oracle/gen_golden_aug.py, and tests/golden/ref_augmenter.npz, written by oracle/gen_golden_ref.py, both from
+the real reference class)."""
 import os
 
 import numpy as np
@@ -8,9 +8,11 @@ import pytest
 import torch
 
 from oracle import augmenter as OA
-from oracle import ref_loader as RL
+from oracle import packed as PK
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "aug_small.npz")
+REF = os.path.join(os.path.dirname(__file__), "golden", "ref_augmenter.npz")
+AUG_CASES = [(5, 2, 40, 20, 2, 9), (16, 10, 100, 60, 4, 33)]
 
 
 def _sd(g):
@@ -31,25 +33,24 @@ def test_oracle_matches_reference_fixture():
     assert float(xa.abs().max()) > 0.1 and float((xa > 0).float().mean()) > 0.05     # not a dead network
 
 
-@pytest.mark.skipif(not RL.reference_available(), reason="/root/reference not present")
-@pytest.mark.parametrize("cfg", [(5, 2, 40, 20, 2, 9), (16, 10, 100, 60, 4, 33)])
+@pytest.mark.parametrize("cfg", AUG_CASES)
 @pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-12), (torch.float32, 1e-5)])
 def test_oracle_equals_live_reference(cfg, dtype, tol):
+    """Fresh random cases (not those of aug_small.npz): the reference class's eval forward, recorded by
+    oracle/gen_golden_ref.py on x drawn from torch's generator seeded with 2, z0 and eps from it seeded with 1, as here."""
     NZ, Z, D, ND, A, B = cfg
-    cls = RL.load_reference_augmenter()
+    g = PK.Packed(REF)
+    pre = f"aug/{AUG_CASES.index(cfg)}/{'f64' if dtype == torch.float64 else 'f32'}"
     old = torch.get_default_dtype()
     torch.set_default_dtype(dtype)
     try:
         sd = OA.random_state_dict(NZ, Z, D, ND, seed=3, dtype=dtype)
-        m = cls(noise_dim=NZ, latent_dim=Z, input_dim=D, n_dim=ND)
-        m.load_state_dict(sd)
-        m.eval()
+        torch.manual_seed(2)
         x = torch.randn(B, D, dtype=dtype).abs()
+        assert g.matches(f"{pre}/x", x)               # the input the reference was run on
         torch.manual_seed(1)
         z0, eps = torch.randn(A, B, NZ, dtype=dtype), torch.randn(A, B, Z, dtype=dtype)
-        torch.manual_seed(1)
-        with torch.no_grad():
-            s_ref, x_ref = m(x.expand(A, -1, -1), True, 0.1)
+        s_ref, x_ref = torch.from_numpy(np.array(g[f"{pre}/s"])), torch.from_numpy(np.array(g[f"{pre}/x_aug"]))
         s, xa = OA.forward_eval(sd, x.expand(A, -1, -1), z0, eps, 0.1)
         assert float((s - s_ref).abs().max()) <= tol * max(1.0, float(s_ref.abs().max()))
         assert float((xa - x_ref).abs().max()) <= tol * max(1.0, float(x_ref.abs().max()))
@@ -58,8 +59,8 @@ def test_oracle_equals_live_reference(cfg, dtype, tol):
 
 
 def test_mirror_constructor_matches_reference_keys_and_init():
-    """Same sub-module names / shapes as the reference class, and (in the build container) bit-identical initial
-    parameters for the same torch seed."""
+    """Same sub-module names / shapes as the reference class, and bit-identical initial parameters for the same torch
+    seed (the reference constructor's, recorded in tests/golden/ref_augmenter.npz)."""
     import distributed_vae_amd  # noqa: F401
     from distributed_vae_amd.augmentation import Augmenter_smartseq
     torch.manual_seed(11)
@@ -68,11 +69,10 @@ def test_mirror_constructor_matches_reference_keys_and_init():
     assert list(m.state_dict().keys()) == list(sd.keys())
     for k, v in m.state_dict().items():
         assert v.shape == sd[k].shape, k
-    if RL.reference_available():
-        torch.manual_seed(11)
-        r = RL.load_reference_augmenter()(noise_dim=6, latent_dim=3, input_dim=52, n_dim=20)
-        for (k, v), (k2, v2) in zip(m.state_dict().items(), r.state_dict().items()):
-            assert k == k2 and torch.equal(v, v2), k
+    g = PK.Packed(REF)       # the reference's initial parameters, as digests
+    assert list(m.state_dict().keys()) == list(g.digests_under("mirror/sd"))
+    for k, v in m.state_dict().items():
+        assert g.matches(f"mirror/sd/{k}", v), k
 
 
 def test_forward_without_gpu_fails_loudly():

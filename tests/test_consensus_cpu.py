@@ -1,6 +1,6 @@
 """CPU: the consensus oracle (oracle/consensus.py) against the reference's own known-answer vectors
-(tests/golden/consensus_kat.json, restated from the reference's tests/test_utils.py:18-105) and, in the build
-container, against the reference's functions themselves on random cases."""
+(tests/golden/consensus_kat.json, restated from the reference's tests/test_utils.py:18-105) and against what the
+reference's functions themselves computed on random cases (tests/golden/ref_consensus.npz, oracle/gen_golden_ref.py)."""
 import json
 import os
 
@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 
 from oracle import consensus as OC
-from oracle import ref_loader as RL
+from oracle import packed as PK
 
 KAT = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "consensus_kat.json")))
+GOLD = os.path.join(os.path.dirname(__file__), "golden", "ref_consensus.npz")
 
 
 def test_compute_confmat_kat():
@@ -50,17 +51,16 @@ def test_edge_cases():
     assert vals[0] == OC.confmat_mean(OC.confmat_normalize(OC.compute_confmat(lab[0], lab[1], 3)))
 
 
-@pytest.mark.skipif(not RL.reference_available(), reason="/root/reference not present")
 def test_oracle_equals_reference_functions():
-    ref = RL.load_reference_consensus_utils()
+    g = PK.Packed(GOLD)      # the reference's matrices and labels as digests (exact equality), its means as values
     rng = np.random.default_rng(3)
     for K, n in [(4, 50), (92, 5000), (92, 300), (128, 20000), (7, 1)]:
         l1 = rng.integers(0, K, n).astype(np.int64)
         l2 = np.where(rng.random(n) < 0.7, l1, rng.integers(0, K, n)).astype(np.int64)
-        cm_ref = ref.compute_confmat(l1, l2, K)
+        pre = f"cons/{K}_{n}"
         cm = OC.compute_confmat(l1, l2, K)
-        assert np.array_equal(cm, cm_ref) and np.array_equal(cm_ref, ref.compute_confmat_naive(l1, l2, K))
-        assert np.array_equal(OC.confmat_normalize(cm), ref.confmat_normalize(cm_ref))
-        assert OC.confmat_mean(OC.confmat_normalize(cm)) == ref.confmat_mean(ref.confmat_normalize(cm_ref))
+        assert g.matches(f"{pre}/cm", cm) and g.matches(f"{pre}/cm_naive", cm)
+        assert g.matches(f"{pre}/norm", OC.confmat_normalize(cm))
+        assert OC.confmat_mean(OC.confmat_normalize(cm)) == float(g[f"{pre}/mean"])
     p = rng.random((40, 9))
-    assert np.array_equal(OC.classify(p), ref.classify(p))
+    assert g.matches("cons/classify", OC.classify(p))
