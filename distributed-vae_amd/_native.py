@@ -14,7 +14,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMVAE_LIB") or os.path.join(HERE, "libmmvae_hip.so")   # env override: A/B timing of builds
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 N_PARAM_TENSORS = 28
 N_BN = 6
 MAX_ARMS = 8
@@ -77,8 +77,8 @@ N_TUNE = 24
 # environment switch that sets each one: the LIBRARY reads
 # no environment variables, this module translates them (experiments and A/B timing only; none is needed in production)
 TUNE_ENV = {
-    "MMVAE_EVAL_CHAIN": (0, lambda v: int(int(v) == 0)), "MMVAE_AUG_TILE": (3, int), "MMVAE_ABLATE_C": (4, int), "MMVAE_ABLATE": (5, int),
-    "MMVAE_FC11_ZG": (8, lambda v: int(int(v) == 0)), "MMVAE_COUPLE_SIDE": (13, int), "MMVAE_ABLATE_L": (14, int), "MMVAE_ABLATE_B": (16, int),
+    "MMVAE_EVAL_CHAIN": (0, lambda v: int(int(v) == 0)), "MMVAE_AUG_TILE": (3, int),
+    "MMVAE_FC11_ZG": (8, lambda v: int(int(v) == 0)), "MMVAE_COUPLE_SIDE": (13, int),
     "MMVAE_BF16_NARROW_FP32": (18, int), "MMVAE_BN_PARTIALS": (19, int), "MMVAE_PRESPLIT_ALL": (20, int), "MMVAE_CHAIN_FP32": (21, int),
 }
 TUNE_ENGINE = 17    # MMVAE_TUNE_ENGINE: the GEMM engine the caller runs (the layout's split factors are chosen for it)
@@ -135,8 +135,6 @@ def lib():
     L.mmvae_workspace_bytes.restype = C.c_size_t
     L.mmvae_ws_offset.argtypes = [C.POINTER(Dims), ex, C.c_int]
     L.mmvae_ws_offset.restype = i64
-    L.mmvae_ws_debug_offset.argtypes = [C.POINTER(Dims), ex]
-    L.mmvae_ws_debug_offset.restype = i64
     L.mmvae_splits.argtypes = [C.POINTER(Dims), ex, C.POINTER(C.c_int32 * 6)]
     L.mmvae_forward.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, i64, vp, i32,
                                 vp, C.c_size_t, ex, vp]
@@ -324,10 +322,6 @@ class Engine:
 
     def ws_raw(self, name: str, numel: int) -> torch.Tensor:
         off = int(lib().mmvae_ws_offset(C.byref(self.dims), self._x(), WS_IDS[name]))
-        return self.ws[off: off + numel]
-
-    def ws_debug(self, numel: int = 1024) -> torch.Tensor:
-        off = int(lib().mmvae_ws_debug_offset(C.byref(self.dims), self._x()))
         return self.ws[off: off + numel]
 
     def forward(self, hyper: Hyper, noise: Noise, params, bn_running, nbt, x, x_arm_stride, x_rec, need_grad):

@@ -166,7 +166,7 @@ Layout make_layout(const mmvae_dims& d, const mmvae_exec* ex) {
     L.lat_part = take(A * nb * 2);
     L.fc1_slab = take((int64_t)L.sp.ks_fc1 * A * B * NP);
     L.n11 = (L.nblk64 + 2) * (max(L.sp.ns_fc11, L.sp.ks_gd10) + 1) + cdiv(d.D, 64);
-    L.fc11_part = take(A * (int64_t)L.n11 * 2 + 64);   // + diagnostic stamp counters
+    L.fc11_part = take(A * (int64_t)L.n11 * 2);
     L.acc = take((int64_t)ACC_NSETS * A * ACC_SET_FLOATS);   // directly behind fc11_part: one zero fill at the start of a forward pass
     L.acc_end = off;                                        // (the backward sets are the last ones: one zero fill at the start of a backward pass)
     L.GD10_slab = take((int64_t)max(L.sp.ns_fc11, L.sp.ks_gd10) * A * B * H);
@@ -194,7 +194,6 @@ Layout make_layout(const mmvae_dims& d, const mmvae_exec* ex) {
         L.pl_small = take(A * (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128 / 2);
     }
     L.rowmap = take(B + MAP_PAD);
-    L.loss_scratch = take(4096);
     L.total = off;
     return L;
 }
@@ -458,7 +457,7 @@ using namespace mmvae;
 
 extern "C" {
 
-int mmvae_abi_version(void) { return 4; }
+int mmvae_abi_version(void) { return 5; }
 const char* mmvae_last_error_string(void) { return g_err; }
 int mmvae_check_dims(const mmvae_dims* d) { return check_dims(d); }
 
@@ -524,11 +523,6 @@ int mmvae_splits(const mmvae_dims* d, const mmvae_exec* ex, int32_t out[6]) {
     const Splits s = default_splits(*d, ex);
     out[0] = s.ks_fc1; out[1] = s.ns_fc11; out[2] = s.ks_dw; out[3] = s.ks_small; out[4] = s.ks_gd10; out[5] = s.ks_dw11;
     return 0;
-}
-
-int64_t mmvae_ws_debug_offset(const mmvae_dims* d, const mmvae_exec* ex) {
-    if (check_dims(d)) return -1;
-    return make_layout(*d, ex).loss_scratch + 2048;
 }
 
 int mmvae_forward(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, const float* params,

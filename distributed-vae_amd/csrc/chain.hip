@@ -64,8 +64,6 @@ struct ChainFwdArgs {
     int rows;               // cells per workgroup (<= CHAIN_ROWS, multiple of 8): Layout::chain_rows_fwd
     int nblk;               // row blocks per arm (the launch's grid.x, unless the launch has other roles beside the chain)
     int64_t per_arm;
-    int ablate;   // timing experiments only (MMVAE_ABLATE_C)
-    int64_t dbg_off;   // >= 0: workspace offset of a diagnostic stamp-counter block (bit 3 of ablate)
 };
 
 // stage W [N][K] (global, row-major) into LDS rows [0, rows_pad) x cols [0, cols_pad), zero padded.
@@ -217,19 +215,6 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
     const int nvalid = min(a.rows, B - b0);
     const int Rlim = b0 + nvalid;            // rows of x beyond the block read as zero (the tile has CHAIN_ROWS rows)
     const float* P = params + (int64_t)arm * a.per_arm;
-    const bool stamps = (a.ablate & 8) != 0 && a.dbg_off >= 0;
-    unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-    auto stamp = [&](int i) {
-        if (stamps) {
-            __builtin_amdgcn_sched_barrier(0);
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            ph[i] += now - tprev;
-            tprev = now;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    if (stamps) { tprev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); }
 
     // ---- requested before anything waits: the first layer's weights and the workgroup's input rows (with the batch sums
     //      below: one memory round trip in front of the first GEMM instead of three)
@@ -262,24 +247,12 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         float mean = 0.f, rstd = 0.f;
         if (a.bn_part_off >= 0) {
             float m2 = 0.f;
-            unsigned long long st[5] = {0, 0, 0, 0, 0};
             if (a.acc_in_off >= 0) {
-                if (stamps) { st[0] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); }
                 if (tid < K0)
                     acc_mean_m2(reinterpret_cast<const long long*>(ws + a.acc_in_off) + (int64_t)arm * ACC_SET_I64, tid, B, mean, m2);
-                if (stamps) {
-                    asm volatile("" :: "v"(mean), "v"(m2));
-                    st[1] = st[2] = st[3] = st[0];
-                    st[4] = __builtin_amdgcn_s_memtime();
-                    __builtin_amdgcn_s_waitcnt(0xC07F);
-                }
             } else {
                 stats_from_partials<CH_NT>(ws + a.bn_part_off + (int64_t)arm * a.part_n * 2 * K0, a.part_n, B, a.part_rows, K0,
-                                           Ws, mean, m2, stamps ? st : nullptr);
-            }
-            if (stamps && lane == 0) {
-                unsigned long long* dbg = reinterpret_cast<unsigned long long*>(ws + a.dbg_off);
-                for (int i = 0; i < 4; ++i) atomicAdd(dbg + 8 + i, st[i + 1] - st[i]);
+                                           Ws, mean, m2);
             }
             rstd = 1.0f / sqrtf(m2 / (float)B + a.bn_eps);
             if (blk == 0 && tid < K0) {
@@ -344,7 +317,6 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         if (vec) stage_x(VecTag{});
         else stage_x(ScalarTag{});
     }
-    stamp(0);
     for (int l = 0; l < a.nlayers; ++l) {
         const FwdLayer Lr = a.L[l];
         const int K = Lr.K, N = Lr.N, KP = rup(K, 8), NPad = rup(N, 32);
@@ -357,9 +329,7 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         const bool obn = Lr.obn_mean_off >= 0;
         const float omean = (obn && active && col < N) ? ws[Lr.obn_mean_off + (int64_t)arm * N + col] : 0.f;
         const float orstd = (obn && active && col < N) ? ws[Lr.obn_rstd_off + (int64_t)arm * N + col] : 0.f;
-        stamp(1);
         lds_barrier();
-        stamp(2);
         wq_valid = false;
         if (l + 1 < a.nlayers) {   // next layer's weights travel while this layer computes
             const FwdLayer Ln = a.L[l + 1];
@@ -372,14 +342,11 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         }
         f32x16 acc = zero16();
         if constexpr (X3) {
-            if (active && !(a.ablate & 1)) mma_nt_x3(acc, Xp, xpl, Wp, wpl, ld, rt * 32, ct * 32, rup(K, 16) >> 4);
+            if (active) mma_nt_x3(acc, Xp, xpl, Wp, wpl, ld, rt * 32, ct * 32, rup(K, 16) >> 4);
         } else {
-            if (active && !(a.ablate & 1)) mma_nt(acc, Xs, ld, rt * 32, Ws, ld, ct * 32, KP / 8);
+            if (active) mma_nt(acc, Xs, ld, rt * 32, Ws, ld, ct * 32, KP / 8);
         }
-        if (stamps) asm volatile("" :: "v"(acc[0]));
-        stamp(3);
         lds_barrier();   // every wave has finished reading Xs / Ws
-        stamp(2);
         const bool last = (l + 1 == a.nlayers);
         const bool need_x = !last || a.planes_off >= 0;
         float vals[16];
@@ -392,7 +359,7 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
                 if (col < N && row < nvalid) {
                     v = acc[r] + bias;
                     if (Lr.act) v = relu_keep_nan(v);
-                    if (!(a.ablate & 4)) out[(int64_t)(b0 + row) * N + col] = v;
+                    out[(int64_t)(b0 + row) * N + col] = v;
                 }
                 vals[r] = v;
                 // next layer's input: zero beyond N (up to the next multiple of 8) and beyond nvalid
@@ -454,9 +421,7 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
                 }
             }
         }
-        stamp(4);
         lds_barrier();
-        stamp(2);
     }
     if (a.planes_off >= 0) {
         // slice planes of [d10 | 1]: Xs holds the last layer's output (zero beyond nvalid rows); pairs of columns, lanes
@@ -489,11 +454,6 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
 #pragma unroll
             for (int p = 0; p < 3; ++p) *reinterpret_cast<unsigned*>(pl + p * plane + (int64_t)(b0 + r) * 128 + c) = w[p];
         }
-    }
-    if (stamps && lane == 0) {
-        unsigned long long* dbg = reinterpret_cast<unsigned long long*>(ws + a.dbg_off);
-        for (int i = 0; i < 5; ++i) atomicAdd(dbg + i, ph[i]);
-        atomicAdd(dbg + 5, 1ull);
     }
 }
 template <bool X3>
@@ -1009,8 +969,6 @@ int launch_chain_fwd_enc(const Ctx& c, int layer, const float* params, float* bn
     a.ld = fwd_ld(max(d.H, N));
     a.wrows = max(rup(N, 32), cdiv(WS_SCRATCH, a.ld));   // Ws doubles as scratch (statistics prologue / epilogue)
     a.per_arm = c.po.per_arm;
-    a.ablate = c.tune(MMVAE_TUNE_ABLATE_C);
-    a.dbg_off = L.loss_scratch + 2048;
     a.L[0].pl_slot = layer - 2;
     return launch_fwd(c, a, max(d.H, N), params, bn_running, nbt, "k_chain_fwd<enc>");
 }
@@ -1039,8 +997,6 @@ int launch_chain_fwd_enc_eval(const Ctx& c, const float* params) {
     a.ld = fwd_ld(max(d.H, d.L));
     a.wrows = rup(max(d.H, d.L), 32);
     a.per_arm = c.po.per_arm;
-    a.ablate = 0;
-    a.dbg_off = -1;
     for (int i = 0; i < 4; ++i) a.L[i].pl_slot = i;
     return launch_fwd(c, a, max(d.H, d.L), params, nullptr, nullptr, "k_chain_fwd<enc eval>");
 }
@@ -1067,8 +1023,6 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
     a.ld = fwd_ld(max(max(d.H, d.L), d.C + d.S));
     a.wrows = rup(max(d.H, d.L), 32);
     a.per_arm = c.po.per_arm;
-    a.ablate = c.tune(MMVAE_TUNE_ABLATE_C);
-    a.dbg_off = L.loss_scratch + 2048;
     for (int i = 0; i < 5; ++i) a.L[i].pl_slot = 4 + i;
     if (with_couple) {
         // the coupling terms as a second role of this launch (k_chain_fwd_couple): fp32x3 form, accumulator sets, 2 .. 5 arms
@@ -1082,7 +1036,6 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
         cr.nchain = L.nblkf; cr.ncouple = L.nblk32; cr.B = d.B; cr.C = d.C; cr.eps = c.h.eps; cr.lam = c.h.lam;
         cr.cc_off = L.CC; cr.csmp_off = L.CSMP; cr.c_mean_off = L.c_mean; cr.c_iv_off = L.c_iv; cr.couple_part_off = L.couple_part;
         cr.c_acc_off = acc_set_off(L, d.A, ACC_C); cr.t_acc_off = acc_set_off(L, d.A, ACC_T);
-        if (c.tune(MMVAE_TUNE_COUPLE_SIDE) == 2) cr.ncouple = 0;   // timing experiment: the role's workgroups exit at once (results wrong)
         const dim3 grid(max(L.nblkf, cdiv(L.nblk32, 2)), d.A + 1);
         const size_t shm_c = (size_t)2 * (5 * d.A * CPL * 64 + 8) * sizeof(float);
         const size_t shm = max(chain_smem_x3(a.ld, a.wrows), shm_c);
@@ -1105,12 +1058,11 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
 // 1.479 / 1.489 -- the two bubbles it removes from the main stream show in a rocprofv3 trace (5 - 6 us each) but not in the
 // un-profiled step at two and three arms, where the combined launch is 3 us longer than the chain's own (its grid has a third
 // row of workgroups); at five arms the chain's 395 workgroups already run in two rounds and the role fills the second.  So: the
-// role from four arms up, the side stream below (MMVAE_TUNE_COUPLE_SIDE: 1 side stream always, 3 role always, 2 the role's
-// launch with its workgroups exiting at once -- a timing experiment, results wrong).
+// role from four arms up, the side stream below (MMVAE_TUNE_COUPLE_SIDE: 1 side stream always, 3 role always).
 bool dec_couple_ok(const Ctx& c) {
     const mmvae_dims& d = c.d;
     return c.h.training && c.use_acc() && c.small_planes && chain_x3_ok(c) && max(max(d.H, d.L), d.C + d.S) <= 128 && d.A >= 2 &&
-           d.A <= 5 && d.C <= CPL * 64 && c.tune(MMVAE_TUNE_COUPLE_SIDE) != 1 && (d.A >= 4 || c.tune(MMVAE_TUNE_COUPLE_SIDE) >= 2);
+           d.A <= 5 && d.C <= CPL * 64 && c.tune(MMVAE_TUNE_COUPLE_SIDE) != 1 && (d.A >= 4 || c.tune(MMVAE_TUNE_COUPLE_SIDE) == 3);
 }
 
 int launch_chain_bwd_dec(const Ctx& c, const float* params, int nslab) {

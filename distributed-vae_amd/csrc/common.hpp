@@ -86,7 +86,6 @@ struct Layout {
     int64_t acc;
     int64_t acc_end;               // end of the accumulator sets (the backward pass zeroes [ACC_BWD sets, acc_end))
     int64_t rowmap;                // uint32 [B + MAP_PAD]: element offsets of the batch's rows in the resident matrix (mmvae_train_step_rows)
-    int64_t loss_scratch;          // small
     int64_t total;
 };
 // accumulator set geometry (device side below)
@@ -336,17 +335,7 @@ static_assert(ACC_MIN_PRODUCER_ROWS <= LAT_ROWS_BWD && ACC_MIN_PRODUCER_ROWS <= 
 
 template <bool VEC, int NT>
 __device__ __forceinline__ void stats_from_partials_t(const float* __restrict__ part, int nblk, int B, int PR, int W,
-                                                      float* scratch, float& mean_out, float& m2_out,
-                                                      unsigned long long* st = nullptr) {
-    auto tick = [&](int i) {
-        if (st) {
-            __builtin_amdgcn_sched_barrier(0);
-            st[i] = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    tick(0);
+                                                      float* scratch, float& mean_out, float& m2_out) {
     constexpr int E = VEC ? 4 : 1;
     const int units = 2 * W / E;   // load units per partial: the first W/E hold means, the rest M2s
     const int G = max(1, min(min(NT / units, PART_MAXG), nblk));
@@ -361,7 +350,6 @@ __device__ __forceinline__ void stats_from_partials_t(const float* __restrict__ 
         // value of the first batch (a separate load for it would cost one more memory latency in front of the batch)
 #pragma unroll
         for (int e = 0; e < E; ++e) { sh[e] = 0.f; s1[e] = 0.f; s2[e] = 0.f; }
-        tick(1);
         // PART_BATCH loads in flight per pass, clamped and weighted instead of branched (a branch around
         // a load makes hipcc wait for every load separately: one memory latency per partial)
         for (int i0 = g; i0 < nblk; i0 += PART_BATCH * G) {
@@ -404,9 +392,7 @@ __device__ __forceinline__ void stats_from_partials_t(const float* __restrict__ 
             }
         }
     }
-    tick(2);
     lds_barrier();
-    tick(3);
     float n = 0.f, mean = 0.f, m2 = 0.f;
     if (t < W) {
         for (int k = 0; k < G; ++k) {   // Chan's pairwise update over the groups, fixed order
@@ -422,14 +408,12 @@ __device__ __forceinline__ void stats_from_partials_t(const float* __restrict__ 
     }
     mean_out = mean;
     m2_out = m2;
-    tick(4);
 }
 template <int NT>
 __device__ __forceinline__ void stats_from_partials(const float* __restrict__ part, int nblk, int B, int PR, int W,
-                                                    float* scratch, float& mean_out, float& m2_out,
-                                                    unsigned long long* st = nullptr) {
-    if ((W & 3) == 0) stats_from_partials_t<true, NT>(part, nblk, B, PR, W, scratch, mean_out, m2_out, st);
-    else stats_from_partials_t<false, NT>(part, nblk, B, PR, W, scratch, mean_out, m2_out, st);
+                                                    float* scratch, float& mean_out, float& m2_out) {
+    if ((W & 3) == 0) stats_from_partials_t<true, NT>(part, nblk, B, PR, W, scratch, mean_out, m2_out);
+    else stats_from_partials_t<false, NT>(part, nblk, B, PR, W, scratch, mean_out, m2_out);
 }
 
 // part: [nblk][n] plain partial sums -> thread t < n returns sum over blocks of part[.][t].

@@ -569,7 +569,6 @@ struct GemmArgs {
     int64_t fo_arm, fo_x_arm;    // arm strides of dz / x_rec and of x (0: the arms share x)
     int n11;
     int A;
-    long long* dbg;              // diagnostic phase counters (builds with -DX3_STAMPS only), else unused
 };
 
 // the MFMAs of one K tile: this wave's 64 x 64 of the block tile (NP = 3: six slice products per pair of fragments, the
@@ -933,9 +932,6 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
             if (n_mine > 1) first(std::integral_constant<int, DEPTH - 1>{}, kfirst + KSTEP);
         }
     }
-#ifdef X3_STAMPS
-    long long t_st = 0, t_mf = 0, t_bar = 0, t_ld = 0, t0 = __builtin_amdgcn_s_memtime(), t_begin = t0;
-#endif
     // phase p: group g is at step q = p - g of its own sequence stage(0), mfma(0), stage(1), mfma(1), ...
     for (int p = 0; p <= 2 * n; ++p) {
         const int q = p - grp;
@@ -945,15 +941,7 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
             unsigned* const Bd = Bs[SHARE == 2 ? (t & 1) : grp];
             if (q & 1) {
                 mfma_ktile<AMINOR, BMINOR, 3>(acc, Ad, Bd, wm, wn, lane);
-#ifdef X3_STAMPS
-                asm volatile("" :: "v"(acc[0][0]), "v"(acc[1][1]));
-                { const long long t1 = __builtin_amdgcn_s_memtime(); t_mf += t1 - t0; t0 = t1; }
-#endif
             } else {
-#ifdef X3_STAMPS
-                __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): how long the stage waits for its operands
-                { const long long t1 = __builtin_amdgcn_s_memtime(); t_ld += t1 - t0; t0 = t1; }
-#endif
                 // tile t + DEPTH / t + 1 exist: their requests go out with tile t's store
                 const bool more = t + DEPTH < n_mine, morep = t + 1 < n_mine;
                 const int kld = k0 + DEPTH * KSTEP, kpl = k0 + KSTEP;
@@ -964,24 +952,10 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
                 };
                 if (DEPTH == 1 || !(t & 1)) go(std::integral_constant<int, 0>{});
                 else go(std::integral_constant<int, DEPTH - 1>{});
-#ifdef X3_STAMPS
-                __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the LDS writes have been issued and accepted
-                { const long long t1 = __builtin_amdgcn_s_memtime(); t_st += t1 - t0; t0 = t1; }
-#endif
             }
         }
         __syncthreads();
-#ifdef X3_STAMPS
-        { const long long t1 = __builtin_amdgcn_s_memtime(); t_bar += t1 - t0; t0 = t1; }
-#endif
     }
-#ifdef X3_STAMPS
-    if (g.dbg && lane == 0 && wv == 0 && blockIdx.x == 3 && blockIdx.y == 2 && blockIdx.z == 0) {
-        g.dbg[grp * 8 + 0] = t_st; g.dbg[grp * 8 + 1] = t_mf; g.dbg[grp * 8 + 2] = t_bar; g.dbg[grp * 8 + 3] = n;
-        g.dbg[grp * 8 + 4] = __builtin_amdgcn_s_memtime() - t_begin;
-        g.dbg[grp * 8 + 5] = t_ld;
-    }
-#endif
     if constexpr (SHARE == 3) {
         // group 1's partial sums join group 0's through LDS (the operand images are dead: every wave is past the loop's last
         // barrier), one row-tile pair of accumulators at a time: 2 x 16 floats per lane = 32 KB
@@ -1136,9 +1110,6 @@ __global__ __launch_bounds__(256, 2) void k_bf16_fc11(const GemmArgs g_in) {
 // S16 (bf16 storage): x is read from its bf16 copy (g.fo.x addresses 2-byte elements; the loss and dZ11 then see the rounded
 // x) and dZ11 is WRITTEN as bf16 (g.fo.dz likewise) -- exactly the values the d(d10) product here and the dW11 GEMM take
 // anyway, so only the loss's view of x changes; the kernel moves 2 x 2 + 2 bytes per cell and gene instead of 2 x 4 + 4.
-#ifndef BF16FC_ABL
-#define BF16FC_ABL 0     // timing ablations of k_bf16_fc11g (diagnostic builds only; results wrong): 1 no W11 reloads, 2 no x loads, 4 no dZ11 stores
-#endif
 // W16: W11 is read from slice 0 of its planes ([D -> rup 128][128] bf16, launch_x3_planes) in sixteen-byte pieces of eight elements
 // that go to the LDS image as they are, instead of fp32 rounded by every block (half the bytes from L2, no conversion; the
 // timing ablation prices the fp32 tiles at 13 of the kernel's 84 us: profiles/r04_bf16_fc11g_ablation.txt; 84 -> 75 us.  Requesting
@@ -1219,7 +1190,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_fc11g(const GemmArgs g_in) {
         w_store(j0);
         if (tid < BT) bias_s[tid] = bnext;
         __syncthreads();
-        if (!(BF16FC_ABL & 1) && t + 1 < t1) {
+        if (t + 1 < t1) {
             w_request(j0 + BT);
             if (tid < BT) bnext = bias[min(j0 + BT + tid, D - 1)];
         }
@@ -1239,8 +1210,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_fc11g(const GemmArgs g_in) {
 #pragma unroll
                     for (int qp = 0; qp < 2; ++qp) {
                         const int gene = j0 + 32 * (2 * half + gl) + 8 * (2 * qp + hh);                   // D % 8 == 0
-                        if (BF16FC_ABL & 2) xraw[gl][qp] = u32x4v{0x3c003c00u, 0x3c003c00u, 0u, 0u};
-                        else xraw[gl][qp] = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const unsigned short*>(xa) + rowoff + min(gene, D - 8));
+                        xraw[gl][qp] = *reinterpret_cast<const u32x4v*>(reinterpret_cast<const unsigned short*>(xa) + rowoff + min(gene, D - 8));
                     }
                 } else {
 #pragma unroll
@@ -1311,8 +1281,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_fc11g(const GemmArgs g_in) {
                         u32x4v w;
                         w[0] = s0[0]; w[1] = s1[0]; w[2] = s0[1]; w[3] = s1[1];
                         const int gene = j0 + 32 * gi + 8 * (2 * qp + hh);
-                        if (!(BF16FC_ABL & 4) && cell < B && gene < D) *reinterpret_cast<u32x4v*>(reinterpret_cast<unsigned short*>(dza) + (int64_t)cell * D + gene) = w;
-                        if (BF16FC_ABL & 4) asm volatile("" :: "v"(w));
+                        if (cell < B && gene < D) *reinterpret_cast<u32x4v*>(reinterpret_cast<unsigned short*>(dza) + (int64_t)cell * D + gene) = w;
                     }
                 }
                 // d(d10) += dZ11 piece (registers) x W11 rows 32 gi .. + 31 (LDS): two K steps of sixteen genes
@@ -1393,9 +1362,6 @@ __global__ __launch_bounds__(256, 2) void k_bf16_fc11g(const GemmArgs g_in) {
 // and no row pitch serves both (60 dwords: transposing reads 2-way conflicts, 19 % of the kernel's busy cycles in the PMC
 // pass; 80: row reads 4-way).  The XOR below makes both conflict-free: rows r .. r + 3 differ in bits 2-3 of the block,
 // rows r, r + 4, r + 8, r + 12 in bits 0-1.
-#ifndef FC11_ABL
-#define FC11_ABL 0     // timing ablations of k_x3_fc11g (diagnostic builds only; results wrong): 1 no x loads, 2 no dZ11 stores,
-#endif                 // 4 no W11 DMA in the loop, 8 no epilogue, 16 / 32 no MFMAs in stage 1 / 2, 64 no mismatch count
 constexpr int FW_ROW = 64;                     // dwords per W11 image row
 constexpr int FW_PLANE = 64 * FW_ROW;          // dwords per slice image of a 64-gene tile
 constexpr int FW_TILE = 3 * FW_PLANE;
@@ -1488,11 +1454,6 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
         int off = gene < dlim ? (rowoff + gene) * 4 : -16;
         asm("" : "+v"(off));       // (a plain select: hipcc otherwise branches around two copies of the load, and a branch
                                    // ends the region in which MFMAs and VALU instructions can be interleaved)
-        if constexpr (FC11_ABL & 1) { X[q] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-        if constexpr (FC11_ABL & 128) {   // the same requests in whole 128-byte lines (eight lanes per row; wrong data)
-            const int cc = min(c0 + 32 * wv + (lane >> 3) + 8 * q, B - 1), gg = min(j0g + 4 * (lane & 7), D - 4);
-            off = (cc * D + gg) * 4;
-        }
         X[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
     };
     // six slice products of one K step
@@ -1573,12 +1534,6 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
         z_frags(W1, 0);
         z_frags(W1, 1);
     }
-#ifdef X3_STAMPS
-    long long t_s1 = 0, t_dma = 0, t_s2 = 0, tw = 0, tp = __builtin_amdgcn_s_memtime(), tbeg = tp;
-#define X3_ST(var) { const long long t1_ = __builtin_amdgcn_s_memtime(); var += t1_ - tp; tp = t1_; }
-#else
-#define X3_ST(var)
-#endif
     // piece p: epilogue reads `acc` / `xin`, the z product of piece p + 1 goes to `accn`, its x to `xnx`
     // (ONE z accumulator: the piece copies its z out of the accumulator registers at its head -- the epilogue's VALU
     // instructions cannot read those anyway -- and the next piece's product goes into the same registers.  With two
@@ -1602,10 +1557,6 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
         // unit (lane-mask population counts), outside the VALU's dependency chains.
         auto chunk = [&](int ch) __attribute__((always_inline)) {
             const int q = ch >> 1;
-            if constexpr (FC11_ABL & 8) {
-                if (ch & 1) for (int pl = 0; pl < 3; ++pl) { au[q >> 1][pl][2 * (q & 1)] = 0x3f803f80u; au[q >> 1][pl][2 * (q & 1) + 1] = 0x3f803f80u; }
-                return;
-            }
             if ((ch & 1) == 0) {
                 const int gene = j0g + 8 * q + 4 * hh;
                 const float xv[4] = {xin[q].x, xin[q].y, xin[q].z, xin[q].w};
@@ -1619,18 +1570,12 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
                     seq[q] = __builtin_fmaf(er, er, seq[q]);
                     const float d_ = g.fo.coef * er;
                     dzq[e] = a_ > 0.f ? d_ : 0.f;
-                    if constexpr (!(FC11_ABL & 64))
                     mism += __builtin_popcountll(__builtin_amdgcn_ballot_w64(xr > 0.1f) ^ __builtin_amdgcn_ballot_w64(xv[e] > 0.1f));
                 }
                 // (always issued -- the counted wait at the end of a tile relies on it; what must not be written gets an offset
                 // beyond the buffer's range, which the hardware drops)
                 int soff = gene < dlim ? dzoff + gene * 4 : -16;
                 asm("" : "+v"(soff));
-                if constexpr (FC11_ABL & 256) {
-                    const int cc = min(c0 + 32 * wv + (lane >> 3) + 8 * q, B - 1), gg = min(j0g + 4 * (lane & 7), D - 4);
-                    soff = (cc * D + gg) * 4;
-                }
-                if constexpr (!(FC11_ABL & 2))
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, make_float4(dzq[0], dzq[1], dzq[2], dzq[3])), rz, soff, 0, 0);
             } else {
                 unsigned w0[3], w1[3];
@@ -1650,21 +1595,13 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
             __builtin_amdgcn_sched_barrier(0);
             if (s + 2 < 7) z_frags(Wn, s + 2);
             if (s == 5) d_frags(Wt16, 0);           // (the first region of stage 2: its slot of the ring is free)
-            if constexpr (!(FC11_ABL & 16)) mfma6(accn, an[s % 3], s);
-            else { asm volatile("" :: "v"(an[s % 3][0]), "v"(an[s % 3][1]), "v"(an[s % 3][2])); }
+            mfma6(accn, an[s % 3], s);
             if (s < 5) chunk(s);
         }
         asm volatile("" : "+s"(mism));
         // the DMA of a later tile goes here, behind the last use of this piece's x: hipcc does not count the assembly's
         // instructions, so a wait it places for a register loaded BEFORE them also waits for them
-#ifdef X3_STAMPS
-        asm volatile("" :: "v"(accn), "v"(au[0][0][0]), "v"(au[1][2][3]));
-        X3_ST(t_s1)
-#endif
-        if (!(FC11_ABL & 4) && dma_tile >= 0) dma(dma_tile);
-#ifdef X3_STAMPS
-        X3_ST(t_dma)
-#endif
+        if (dma_tile >= 0) dma(dma_tile);
         // ---- stage 2: d(d10) += dZ11 piece (registers) x W11 rows of piece p (LDS, transposed)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1688,11 +1625,6 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
             }
             // product-major: consecutive MFMAs go to the two h tiles of the region (independent accumulators)
             const int n0 = 2 * (r & 1);
-            if constexpr (FC11_ABL & 32) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) asm volatile("" :: "v"(wq[r & 1][j][0]), "v"(wq[r & 1][j][1]), "v"(wq[r & 1][j][2]), "v"(af[0]), "v"(af[1]), "v"(af[2]));
-                continue;
-            }
 #pragma unroll
             for (int j = 0; j < 2; ++j) gd[n0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], wq[r & 1][j][0], gd[n0 + j], 0, 0, 0);
 #pragma unroll
@@ -1706,10 +1638,6 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) gd[n0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], wq[r & 1][j][0], gd[n0 + j], 0, 0, 0);
         }
-#ifdef X3_STAMPS
-        asm volatile("" :: "v"(gd[0]), "v"(gd[3]));
-        X3_ST(t_s2)
-#endif
         __builtin_amdgcn_sched_barrier(0);
     };
     for (int t = t0; t < t1; ++t) {
@@ -1724,14 +1652,7 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
         // landed, and the barrier that of the others.  The barrier also lets tile t's buffer be overwritten.
         __builtin_amdgcn_s_waitcnt(0x0F74);                // vmcnt(4)
         __syncthreads();
-        X3_ST(tw)
     }
-#ifdef X3_STAMPS
-    if (g.dbg && lane == 0 && (wv == 0 || wv == 3) && blockIdx.x == 3 && blockIdx.y == 2 && blockIdx.z == 0) {
-        long long* o = g.dbg + (wv ? 1 : 0) * 8;
-        o[0] = t_s1; o[1] = t_dma; o[2] = t_s2; o[3] = npieces; o[4] = __builtin_amdgcn_s_memtime() - tbeg; o[5] = tw; o[6] = 0;
-    }
-#endif
     // ---- d(d10) partial of this gene range: slab [NS][A][B][H]; gd[nt][r]: cell row acc_row(r), h = 32 nt + (lane & 31)
     {
         float* out = g.so.out + (int64_t)blockIdx.y * g.so.ks_stride + (int64_t)arm * g.so.arm_stride;
@@ -1954,7 +1875,6 @@ int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64
     g.b_arm = c.po.per_arm;
     g.M = d.B; g.N = d.H; g.K = d.D; g.KS = c.lay.sp.ks_fc1; g.A = d.A;
     g.so = SlabOut{c.ws + c.lay.fc1_slab, (int64_t)d.A * d.B * NP, (int64_t)d.B * NP, NP, d.B, d.H};
-    g.dbg = reinterpret_cast<long long*>(c.ws + c.lay.loss_scratch + 2048);
     if (c.x_rows) {   // the batch as rows of the resident matrix (mmvae_train_step_rows): x is read through the row map
         if (!c.rowmap_ready) { set_error("row-indexed batches need the fused step's head launch"); return MMVAE_E_UNSUPPORTED; }
         g.a.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); g.a.nrec = c.x_nrows * c.x_ld; g.a.map_n = d.B;
@@ -2008,7 +1928,6 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
         g.fo_arm = (int64_t)d.B * d.D;
         g.fo_x_arm = xs;
         g.so = SlabOut{c.ws + L.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
-        g.dbg = reinterpret_cast<long long*>(c.ws + c.lay.loss_scratch + 2048);
         launch_k(c, k_x3_fc11g, dim3(cdiv(d.B, 128), NS, d.A), dim3(256), 0, g);
         HIP_LAUNCH_CHECK("k_x3_fc11g");
         return 0;
@@ -2085,7 +2004,6 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
         g.b_arm = xs;
         if (use_mask) { g.b.bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits); g.b.wpr = cdiv(d.D, 32); g.b_bits_arm = (int64_t)d.B * g.b.wpr; }
         g.M = d.H; g.N = d.D; g.K = d.B; g.KS = L.sp.ks_dw; g.A = d.A;
-        g.dbg = reinterpret_cast<long long*>(c.ws + c.lay.loss_scratch + 2048);
         g.so = SlabOut{c.ws + L.dw1_slab, (int64_t)d.A * d.H * d.D, (int64_t)d.H * d.D, d.D, d.H, d.D};
         if (c.x_rows) {
             if (!c.rowmap_ready) { set_error("row-indexed batches need the fused step's head launch"); return MMVAE_E_UNSUPPORTED; }
@@ -2119,7 +2037,6 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
         g.b.ones_row = d.H;                                      // logical row H (not in memory) reads 1: the bias gradient
         g.b_arm = (int64_t)d.B * d.H;
         g.M = d.D; g.N = d.H + 1; g.K = d.B; g.KS = L.sp.ks_dw11; g.A = d.A;
-        g.dbg = reinterpret_cast<long long*>(c.ws + c.lay.loss_scratch + 2048);
         g.so = SlabOut{c.ws + L.dw11_slab, (int64_t)d.A * d.D * DW11_LD, (int64_t)d.D * DW11_LD, DW11_LD, d.D, d.H + 1};
         if (split3_gemms(c)) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
             use_planes(c, g.b, PL_D10);

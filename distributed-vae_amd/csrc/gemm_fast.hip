@@ -51,8 +51,7 @@ template <bool USE_MASK>
 __global__ __launch_bounds__(256) void k_fc1_fwd_v2(const float* __restrict__ x, int64_t x_arm_stride,
                                                     const float* __restrict__ params, int64_t per_arm, int64_t w_off,
                                                     const uint32_t* __restrict__ bits, int wpr,
-                                                    float* __restrict__ slab, int A, int B, int D, int H, int KS,
-                                                    int ablate) {
+                                                    float* __restrict__ slab, int A, int B, int D, int H, int KS) {
     __shared__ __attribute__((aligned(16))) float As[128 * V2_LD];
     __shared__ __attribute__((aligned(16))) float Bs[128 * V2_LD];
     const int arm = blockIdx.z, ks = blockIdx.y, b0 = blockIdx.x * 128;
@@ -112,10 +111,9 @@ __global__ __launch_bounds__(256) void k_fc1_fwd_v2(const float* __restrict__ x,
             *reinterpret_cast<float4*>(&Bs[(r0 + 32 * i) * V2_LD + c4 * 4]) = rb4[i];
         }
         __syncthreads();
-        if (kt + 1 < kt1 && !(ablate & 2)) load_tiles(kt + 1);
+        if (kt + 1 < kt1) load_tiles(kt + 1);
         const float* la = As + (wm * 64 + l31) * V2_LD + 4 * hh;
         const float* lb = Bs + (wn * 64 + l31) * V2_LD + 4 * hh;
-        if (!(ablate & 1))
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 a0 = *reinterpret_cast<const float4*>(la + 8 * g);
@@ -155,8 +153,7 @@ template <bool USE_MASK>
 __global__ __launch_bounds__(256, 2) void k_fc1_fwd_v3(const float* __restrict__ x, int64_t x_arm_stride,
                                                     const float* __restrict__ params, int64_t per_arm, int64_t w_off,
                                                     const uint32_t* __restrict__ bits, int wpr,
-                                                    float* __restrict__ slab, int A, int B, int D, int H, int KS,
-                                                    int ablate) {
+                                                    float* __restrict__ slab, int A, int B, int D, int H, int KS) {
     __shared__ __attribute__((aligned(16))) float As[128 * V2_LD];
     __shared__ __attribute__((aligned(16))) float Bs[128 * V2_LD];
     const int arm = blockIdx.z, ks = blockIdx.y, b0 = blockIdx.x * 128;
@@ -213,11 +210,10 @@ __global__ __launch_bounds__(256, 2) void k_fc1_fwd_v3(const float* __restrict__
             *reinterpret_cast<float4*>(&Bs[(r0 + 32 * i) * V2_LD + c4 * 4]) = rb4[i];
         }
         __syncthreads();
-        if (kt + 1 < kt1 && !(ablate & 2)) load_tiles(kt + 1);
+        if (kt + 1 < kt1) load_tiles(kt + 1);
         const float* la = As + (wv * 32 + l31) * V2_LD + 4 * hh;
         const float* lb = Bs + l31 * V2_LD + 4 * hh;
         const float* ll = Bs + 96 * V2_LD + 4 * hh;      // rows 96..99 of W1: the same address for a whole half wave
-        if (!(ablate & 1))
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 a = *reinterpret_cast<const float4*>(la + 8 * g);
@@ -573,15 +569,14 @@ __device__ __forceinline__ void quad_transpose4(float& v0, float& v1, float& v2,
 }
 
 // XREC: x_rec is written (forward / inference calls); the train step instantiates XREC = false, where dZ11 is
-// always written.  ABL: timing experiments only (1 no MFMA, 2 no x loads, 4 no dZ11 stores); 0 in production --
-// compile-time so that the step body stays one basic block.
-template <int FZ_KG, bool EXACT, bool BIASK, bool XREC, int ABL>
+// always written.
+template <int FZ_KG, bool EXACT, bool BIASK, bool XREC>
 __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d10, const float* __restrict__ params,
                                                     int64_t per_arm, int64_t w_off, int64_t b_off,
                                                     const float* __restrict__ x, int64_t x_arm_stride,
                                                     float* __restrict__ x_rec, float* __restrict__ dz11,
                                                     float* __restrict__ part, int n11, float coef, int need_grad,
-                                                    int A, int B, int D, int H, int ldk, unsigned long long* dbgc) {
+                                                    int A, int B, int D, int H, int ldk) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Wbuf = smem;                     // [2][64][ldk]
     float* red = smem + 2 * 64 * ldk;       // [16]
@@ -590,7 +585,7 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
     const int l31 = lane & 31, hh = lane >> 5;
     const bool lb0 = (lane & 1) != 0, lb1 = (lane & 2) != 0;
     const int KP = rup(H, 8), kg = KP / 8, nc4 = KP / 4, hc4 = H / 4;
-    const bool late = (ABL & 16) ? wv < 4 : wv >= 4;
+    const bool late = wv >= 4;
     const float* W = params + (int64_t)arm * per_arm + w_off;     // [D, H]
     const float* bias = params + (int64_t)arm * per_arm + b_off;
     const float* xa = x + (int64_t)arm * x_arm_stride;
@@ -656,7 +651,6 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
     // one 16-byte piece (gene half c, cell group q) of tile t's x
     auto load_x1 = [&](int t, int c, int q, float4& dst, auto edge_tag) __attribute__((always_inline)) {
         constexpr bool EDGE = decltype(edge_tag)::value;
-        if (ABL & 2) { dst = make_float4(0.f, 0.f, 0.f, 0.f); return; }
         if (!EDGE) {
             const float* xu = xa + ((int64_t)8 * q * D + t * 64 + 32 * c);      // wave-uniform
             dst = *reinterpret_cast<const float4*>(xu + lane_off);
@@ -677,7 +671,6 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
         const float* pb = Ws + l31 * ldk + 4 * hh;
         float4 q0 = *reinterpret_cast<const float4*>(pb);
         float4 q1 = *reinterpret_cast<const float4*>(pb + 32 * ldk);
-        if (!(ABL & 1))
 #pragma unroll
         for (int g = 0; g < FZ_KG; ++g) {
             if (EXACT || g < kg) {
@@ -726,8 +719,7 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
                     if (!EDGE) {
                         const int64_t uo = (int64_t)8 * q * D + t * 64 + 32 * c;      // wave-uniform
                         if (XREC) *reinterpret_cast<float4*>(xra + uo + lane_off) = make_float4(xr[0], xr[1], xr[2], xr[3]);
-                        if (do_grad && !(ABL & 4))
-                            *reinterpret_cast<float4*>(dza + uo + lane_off) = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
+                        if (do_grad) *reinterpret_cast<float4*>(dza + uo + lane_off) = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
                     } else {
                         const uint32_t off = (uint32_t)(cbase + 8 * q) * (uint32_t)D + (uint32_t)col;
                         if (XREC) *reinterpret_cast<float4*>(xra + off) = make_float4(xr[0], xr[1], xr[2], xr[3]);
@@ -750,20 +742,6 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
     }
     __syncthreads();
     int cur = 0;
-    // ABL bit 3: shader-clock stamps per phase, summed over waves (early waves: counters 0-5, late: 8-13)
-    constexpr bool STAMPS = (ABL & 8) != 0;
-    unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-    auto stamp = [&](int i) {
-        if (STAMPS) {
-            __builtin_amdgcn_sched_barrier(0);
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            ph[i] += now - tprev;
-            tprev = now;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    if (STAMPS) { tprev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); }
     // Every step body is straight-line per role: no condition around a load or a store (a conditional epilogue or
     // prefetch makes the compiler's vmcnt bookkeeping pessimistic at the join, and it then waits for the previous
     // step's dZ11 stores before touching the W tile).  The W prefetch of the last step re-reads a clamped row and
@@ -777,40 +755,28 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
         if (!late) {
             load_x(t, xv, edge_tag);
             __builtin_amdgcn_sched_barrier(0);
-            stamp(0);
             mfma_tile(Ws);
-            if (STAMPS) asm volatile("" :: "v"(z0[0]), "v"(z1[15]));
             __builtin_amdgcn_sched_barrier(0);
-            stamp(1);
             prefetch_w(t + 1);
             __builtin_amdgcn_sched_barrier(0);
-            stamp(2);
             epilogue(t, xv, edge_tag);
             __builtin_amdgcn_sched_barrier(0);
-            stamp(3);
         } else {
             // W loads before the epilogue's stores: vmcnt retires in order
             prefetch_w(t + 1);
             __builtin_amdgcn_sched_barrier(0);
-            stamp(2);
             if (!FIRST) epilogue(t - 1, xv, edge_tag);   // z still holds tile t-1
             __builtin_amdgcn_sched_barrier(0);
-            stamp(3);
             // x for this tile goes into the registers the epilogue has just drained; it is not needed before the
             // next step's epilogue, and issuing it here (not at the top of the step with waves 0-3's loads) spreads
             // the CU's outstanding misses over the step
             load_x(t, xv, edge_tag);
             __builtin_amdgcn_sched_barrier(0);
-            stamp(0);
             mfma_tile(Ws);
-            if (STAMPS) asm volatile("" :: "v"(z0[0]), "v"(z1[15]));
             __builtin_amdgcn_sched_barrier(0);
-            stamp(1);
         }
         store_w(Wbuf + (cur ^ 1) * 64 * ldk);
-        stamp(4);
         lds_barrier();      // LDS only: the dZ11 / x_rec stores stay in flight
-        stamp(5);
         cur ^= 1;
     };
     // first step (guarded body, valid for any tile), interior steps (all 256 cells and all 64 genes in range),
@@ -820,11 +786,6 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
     for (int t = t0 + 1; t < t_mid; ++t) step(t, ScalarTag{}, ScalarTag{});      // ::value == false: interior body
     for (int t = max(t_mid, t0 + 1); t < t1; ++t) step(t, VecTag{}, ScalarTag{});    // guarded body
     if (late && t1 > t0) epilogue(t1 - 1, xv, VecTag{});
-    if (STAMPS && lane == 0) {
-        unsigned long long* dbg = dbgc + (late ? 8 : 0);
-        for (int i = 0; i < 6; ++i) atomicAdd(dbg + i, ph[i]);
-        atomicAdd(dbg + 6, 1ull);
-    }
     se = wave_sum(se);
     const float mismf = wave_sum((float)mism);
     if (lane == 0) { red[wv * 2] = se; red[wv * 2 + 1] = mismf; }
@@ -858,7 +819,6 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zg(const float* __restrict__ d1
                                                     float* __restrict__ part, int n11, float coef, int need_grad,
                                                     int A, int B, int D, int H, int ldk, float* __restrict__ gd_slab) {
     constexpr bool XREC = false;
-    constexpr int ABL = 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Wbuf = smem;                               // [3][64][ldk]: tiles t-1 (late waves' d(d10)), t, t+1 (being staged)
     float* DZall = smem + 3 * 64 * ldk;               // [8 waves][32 cells][ZG_LD]: each wave's dZ11 tile
@@ -868,7 +828,7 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zg(const float* __restrict__ d1
     const int l31 = lane & 31, hh = lane >> 5;
     const bool lb0 = (lane & 1) != 0, lb1 = (lane & 2) != 0;
     const int KP = rup(H, 8), kg = KP / 8, nc4 = KP / 4, hc4 = H / 4;
-    const bool late = (ABL & 16) ? wv < 4 : wv >= 4;
+    const bool late = wv >= 4;
     const float* W = params + (int64_t)arm * per_arm + w_off;     // [D, H]
     const float* bias = params + (int64_t)arm * per_arm + b_off;
     const float* xa = x + (int64_t)arm * x_arm_stride;
@@ -940,7 +900,6 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zg(const float* __restrict__ d1
     // one 16-byte piece (gene half c, cell group q) of tile t's x
     auto load_x1 = [&](int t, int c, int q, float4& dst, auto edge_tag) __attribute__((always_inline)) {
         constexpr bool EDGE = decltype(edge_tag)::value;
-        if (ABL & 2) { dst = make_float4(0.f, 0.f, 0.f, 0.f); return; }
         if (!EDGE) {
             const uint32_t so = ((uint32_t)(8 * q) * (uint32_t)D + (uint32_t)(t * 64 + 32 * c)) * 4u;   // wave-uniform
             dst = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)lane_boff, (int)so, 0));
@@ -1372,26 +1331,24 @@ int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64
     const mmvae_dims& d = c.d;
     const bool use_mask = c.h.training && c.h.x_drop > 0.f;
     const int KS = c.lay.sp.ks_fc1;
-    const int ablate = c.tune(MMVAE_TUNE_ABLATE);   // timing experiments only
-    const int padlds = 0;
     dim3 grid(cdiv(d.B, 128), KS, d.A);
     const uint32_t* bits = reinterpret_cast<const uint32_t*>(c.ws + c.lay.xbits);
     if (d.H == 100) {
         if (use_mask)
-            hipLaunchKernelGGL((k_fc1_fwd_v3<true>), grid, dim3(256), padlds, c.stream, x, xs, params, c.po.per_arm,
-                               c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS, ablate);
+            hipLaunchKernelGGL((k_fc1_fwd_v3<true>), grid, dim3(256), 0, c.stream, x, xs, params, c.po.per_arm,
+                               c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS);
         else
             hipLaunchKernelGGL((k_fc1_fwd_v3<false>), grid, dim3(256), 0, c.stream, x, xs, params, c.po.per_arm,
-                               c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS, ablate);
+                               c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS);
         HIP_LAUNCH_CHECK("k_fc1_fwd_v3");
         return 0;
     }
     if (use_mask)
-        hipLaunchKernelGGL((k_fc1_fwd_v2<true>), grid, dim3(256), padlds, c.stream, x, xs, params, c.po.per_arm, c.po.o[0],
-                           bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS, ablate);
+        hipLaunchKernelGGL((k_fc1_fwd_v2<true>), grid, dim3(256), 0, c.stream, x, xs, params, c.po.per_arm, c.po.o[0],
+                           bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS);
     else
         hipLaunchKernelGGL((k_fc1_fwd_v2<false>), grid, dim3(256), 0, c.stream, x, xs, params, c.po.per_arm,
-                           c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS, ablate);
+                           c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS);
     HIP_LAUNCH_CHECK("k_fc1_fwd_v2");
     return 0;
 }
@@ -1440,21 +1397,20 @@ int launch_fc11_fast(const Ctx& c, const float* params, const float* x, int64_t 
             const size_t shm = (size_t)(2 * 64 * ldk + 16) * sizeof(float);
             dim3 grid(nb, nsz, d.A);
 #define FZT_ARGS c.ws + L.Dk[4], params, c.po.per_arm, c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + L.DZ11,        \
-                 c.ws + L.fc11_part, L.n11, coef, need_grad, d.A, d.B, d.D, d.H, ldk,                            \
-                 reinterpret_cast<unsigned long long*>(c.ws + L.loss_scratch + 2048)
-#define FZT_LAUNCH(KG, EX, BK, XR, AB) \
-    hipLaunchKernelGGL((k_fc11_zt<KG, EX, BK, XR, AB>), grid, dim3(512), shm, c.stream, FZT_ARGS)
+                 c.ws + L.fc11_part, L.n11, coef, need_grad, d.A, d.B, d.D, d.H, ldk
+#define FZT_LAUNCH(KG, EX, BK, XR) \
+    hipLaunchKernelGGL((k_fc11_zt<KG, EX, BK, XR>), grid, dim3(512), shm, c.stream, FZT_ARGS)
             const bool xr = x_rec != nullptr;
             // without x_rec the kernel always writes dZ11 (workspace), wanted or not: one variant fewer
             if (kgv == 13 && d.H == 100) {
-                if (xr) FZT_LAUNCH(13, true, true, true, 0);
-                else FZT_LAUNCH(13, true, true, false, 0);
+                if (xr) FZT_LAUNCH(13, true, true, true);
+                else FZT_LAUNCH(13, true, true, false);
             } else if (kgv == 16 && d.H == 128) {
-                if (xr) FZT_LAUNCH(16, true, false, true, 0);
-                else FZT_LAUNCH(16, true, false, false, 0);
+                if (xr) FZT_LAUNCH(16, true, false, true);
+                else FZT_LAUNCH(16, true, false, false);
             } else {
-                if (xr) FZT_LAUNCH(16, false, false, true, 0);
-                else FZT_LAUNCH(16, false, false, false, 0);
+                if (xr) FZT_LAUNCH(16, false, false, true);
+                else FZT_LAUNCH(16, false, false, false);
             }
 #undef FZT_LAUNCH
 #undef FZT_ARGS

@@ -53,9 +53,6 @@ struct PPArgs {
     int tiles_m, tiles_n;
 };
 
-#ifndef PP_ABL
-#define PP_ABL 0      // timing ablations (diagnostic builds only; results wrong): 1 no MFMAs, 2 no LDS-DMA in the loop, 4 no fragment reads
-#endif
 // s_waitcnt lgkmcnt(CNT) with the fragments it makes valid as operands
 template <int CNT, int NP>
 __device__ __forceinline__ void wait_lgkm_tie(bf16x8q (&a)[NP]) {
@@ -164,7 +161,6 @@ __global__ __launch_bounds__(512) void k_pp_gemm(const PPArgs g_in) {
         return __builtin_bit_cast(bf16x8q, *reinterpret_cast<const u32x4q*>(p));
     };
     auto mma = [&](f32x16& c, const bf16x8q (&a)[NP], const bf16x8q (&b)[NP]) __attribute__((always_inline)) {
-        if constexpr ((PP_ABL & 1) != 0) { asm volatile("" :: "v"(a[0]), "v"(b[0]), "v"(a[NP - 1]), "v"(b[NP - 1])); return; }
         if constexpr (NP == 3) {   // six of the nine slice products, the small ones first (gemm_bf16.hip Eng<3>)
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(512) void k_pp_gemm(const PPArgs g_in) {
         for (int it = 0; it < nk; ++it) {
             wait_behind(min(NSTAGE - 2, nk - 1 - it));
             barrier();     // every wave's share of stage `it` is in LDS; every wave is done reading stage it - 1
-            if (!(PP_ABL & 2) && it + NSTAGE - 1 < nk) dma(kt0 + it + NSTAGE - 1, st == 0 ? NSTAGE - 1 : st - 1);
+            if (it + NSTAGE - 1 < nk) dma(kt0 + it + NSTAGE - 1, st == 0 ? NSTAGE - 1 : st - 1);
             // The fragment reads are inline assembly with hand-counted waits: left to hipcc, each read sinks to its first use and is
             // waited for at once (nine exposed LDS latencies per step in the ISA), and with all eighteen requested up front its
             // wait-count pass emits lgkmcnt(0) before the first MFMA (the counter has four bits).  B and the first row tiles of A

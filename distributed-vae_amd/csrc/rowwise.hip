@@ -71,7 +71,6 @@ struct LatArgs {
     // backward only
     int64_t GZIN, GMS, GZC, G5, bnb_part5, T, c_mean, c_iv;
     float am1, beta, lam;
-    int64_t dbg_off;   // >= 0: diagnostic stamp counters (MMVAE_ABLATE_L=8)
     int32_t* labels;   // non-null (eval): labels[arm * B + b] = argmax_k c, the `classify` of the consensus path
     // forward, training: BN5's partials [A][nblk][2][L] are recombined by every row block
     int64_t bn_part5, run_mean_off, run_var_off, run_arm_stride;
@@ -138,20 +137,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
     const int64_t ab = (int64_t)arm * B;
     const float eps = a.eps;
 
-    const bool stamps = a.dbg_off >= 0;
-    unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-    auto stamp = [&](int i) {
-        if (stamps) {
-            __builtin_amdgcn_sched_barrier(0);
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            ph[i] += now - tprev;
-            tprev = now;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    if (stamps) { tprev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); }
-
     // this wave's cells; their fc5 outputs are requested first, so that this latency, the weight staging and the
     // statistics partials all overlap
     int bb[LAT_NR];
@@ -201,7 +186,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
     }
     const float mu5 = lane < L ? (a.bn_part5 >= 0 ? sh_bn5[0][lane] : ws[a.mean5 + arm * L + lane]) : 0.f;
     const float rs5 = lane < L ? (a.bn_part5 >= 0 ? sh_bn5[1][lane] : ws[a.rstd5 + arm * L + lane]) : 0.f;
-    stamp(0);   // weight staging + statistics loads
 
     // ---- x_low = BN5(R5)
     float xl[LAT_NR];
@@ -258,7 +242,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
         }
     };
     softmax_rows(z, cp);
-    stamp(1);   // x_low, fcc, first softmax
     // ---- c = softmax(c_prob / tau)
     const float inv_tau = 1.f / a.tau, inv_temp = 1.f / a.temp;
     float tmp[LAT_NR][CPL];
@@ -317,7 +300,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
 #pragma unroll
             for (int t = 0; t < CPL; ++t) cs[r][t] = ys[r][t];
     }
-    stamp(2);   // second softmax, Gumbel sample (noise)
     // ---- store; c goes to the workgroup tile for the block statistics (zero rows beyond the batch)
     float kl_acc = 0.f, ent_acc = 0.f;
 #pragma unroll
@@ -338,7 +320,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
             }
         }
     }
-    stamp(3);   // stores
     // ---- state head: [mu | sigma_pre] = y [Wmu; Wsigma]^T + b
     float mso[LAT_NR];
 #pragma unroll
@@ -383,7 +364,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
             kl_acc += 1.f + lv - mu * mu - expf(lv);
         }
     }
-    stamp(4);   // state head
     // ---- block partials: mean and M2 of c over the workgroup's cells, two passes over the LDS tile, 8 row groups
     kl_acc = wave_sum(kl_acc);
     ent_acc = wave_sum(ent_acc);
@@ -428,12 +408,6 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
         for (int w = 0; w < LAT_NW; ++w) { k0 += sh_red[w][0]; k1 += sh_red[w][1]; }
         p[0] = k0;
         p[1] = k1;
-    }
-    stamp(5);   // block reduction
-    if (stamps && lane == 0) {
-        unsigned long long* dbg = reinterpret_cast<unsigned long long*>(ws + a.dbg_off);
-        for (int i = 0; i < 6; ++i) atomicAdd(dbg + i, ph[i]);
-        atomicAdd(dbg + 6, 1ull);
     }
 }
 
@@ -1469,8 +1443,6 @@ static LatArgs make_lat_args(const Ctx& c) {
     a.acc_T = (c.h.training && c.use_acc()) ? acc_set_off(L, d.A, ACC_T) : -1;
     a.run_mean_off = c.po.bn_mean[4]; a.run_var_off = c.po.bn_var[4]; a.run_arm_stride = c.po.bn_per_arm;
     a.bn_momentum = c.h.bn_momentum;
-    const int abl = c.tune(MMVAE_TUNE_ABLATE_L);
-    a.dbg_off = (abl & 8) ? L.loss_scratch + 2048 : -1;
     return a;
 }
 
@@ -1500,8 +1472,7 @@ int launch_lat_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, flo
     a.labels = labels;
     NoiseDev nd = make_noise_dev(nz, c.h);
     const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
-    const int fullwave = 0;
-    if (!fullwave && a.dbg_off < 0 && c.d.C <= 32 * LH_CPL && c.d.L <= 32 && 2 * c.d.S <= 32) {
+    if (c.d.C <= 32 * LH_CPL && c.d.L <= 32 && 2 * c.d.S <= 32) {
         launch_k(c, k_lat_fwd_h, dim3(c.lay.nblkl, c.d.A), dim3(64 * LH_NW), shm, a, nd, params, c.ws, bn_running, nbt);
         HIP_LAUNCH_CHECK("k_lat_fwd_h");
         return 0;
@@ -1560,8 +1531,7 @@ int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params) {
     LatArgs a = make_lat_args(c);
     NoiseDev nd = make_noise_dev(nz, c.h);
     const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
-    const int fullwave = 0;
-    if (!fullwave && c.d.C <= 32 * LH_CPL && c.d.L <= 32 && 2 * c.d.S <= 32) {
+    if (c.d.C <= 32 * LH_CPL && c.d.L <= 32 && 2 * c.d.S <= 32) {
         hipLaunchKernelGGL(k_lat_bwd_h, dim3(cdiv(c.d.B, LAT_ROWS_BWD), c.d.A), dim3(64 * LBH_NW), shm, c.stream, a, nd, params, c.ws);
         HIP_LAUNCH_CHECK("k_lat_bwd_h");
         return 0;

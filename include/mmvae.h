@@ -130,7 +130,7 @@ typedef struct mmvae_noise {
 #define MMVAE_TUNE_ENGINE 17    /* the GEMM engine the caller is going to run (mmvae_hyper.gemm_bf16 & 0xFF; 0 = not stated).
                                    The split factors of the workspace layout are chosen for the workgroup shapes of that
                                    engine; any engine runs correctly on any layout */
-/* Every other index is an experiment switch of the implementation (A/B timing, ablations, test hooks), listed in the
+/* Every other index is an experiment switch of the implementation (A/B timing, test hooks), listed in the
  * library's private header distributed-vae_amd/csrc/tune.h; callers leave them 0. */
 typedef struct mmvae_exec {
     void *side_stream;
@@ -216,9 +216,6 @@ int64_t mmvae_ws_offset(const mmvae_dims *d, const mmvae_exec *ex, int ws_id);
  * splits, 2 dW1 batch splits, 3 small-layer dW batch splits, 4 d(d10) gene splits = slabs of MMVAE_WS_GD10_SLAB,
  * 5 dW11 batch splits) */
 int mmvae_splits(const mmvae_dims *d, const mmvae_exec *ex, int32_t out[6]);
-/* offset (in floats) of a 1024-float block inside the workspace that only diagnostic builds write
- * (in-kernel cycle stamps, enabled by environment switches; never read by any kernel) */
-int64_t mmvae_ws_debug_offset(const mmvae_dims *d, const mmvae_exec *ex);
 
 /* ---- compute (device pointers, asynchronous on stream) ----------------------------------- */
 

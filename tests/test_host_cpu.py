@@ -24,11 +24,24 @@ def test_library_exports_every_declared_symbol():
     L = N.lib()
     for n in names:
         assert hasattr(L, n), n
-    assert L.mmvae_abi_version() == N.ABI_VERSION == 4
+    assert L.mmvae_abi_version() == N.ABI_VERSION == 5
     # the library keeps no process-wide or per-thread knobs: no setters, and it reads no environment variables
     assert not [n for n in names if n.startswith("mmvae_set_")]
     blob = open(N.LIB_PATH, "rb").read()
     assert b"getenv" not in blob and b"MMVAE_" not in blob
+
+
+def test_tune_env_matches_tune_header():
+    # every environment switch sets an index that csrc/tune.h names, and every index there has its switch
+    # (MMVAE_TUNE_ENGINE is set by the binding itself, from the engine it runs)
+    src = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "distributed-vae_amd", "csrc", "tune.h")).read())
+    enum = {name: int(v) for name, v in re.findall(r"\b(MMVAE_TUNE_\w+)\s*=\s*(\d+)", src)}
+    assert len(enum) >= 8
+    env_idx = {idx for idx, _ in N.TUNE_ENV.values()}
+    assert len(env_idx) == len(N.TUNE_ENV)
+    assert env_idx <= set(enum.values()), sorted(env_idx - set(enum.values()))
+    assert {v for k, v in enum.items() if k != "MMVAE_TUNE_ENGINE"} <= env_idx
+    assert max(enum.values()) < N.N_TUNE and N.TUNE_ENGINE not in env_idx
 
 
 def test_param_layout_matches_state_dict_shapes():

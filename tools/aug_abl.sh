@@ -1,5 +1,6 @@
 #!/bin/bash
-# per-layer timeline of the augmenter forward for a list of library builds (diagnostic ablations): tools/aug_abl.sh fp32|bf16 lib1.so lib2.so ...
+# per-layer timeline of the augmenter forward for a list of library builds (A/B of builds, e.g. one with a patch from
+# tools/experiments/ applied): tools/aug_abl.sh fp32|bf16 lib1.so lib2.so ...
 # run on the GPU box from the repo root
 MODE=$1; shift
 cd /tmp && export TMPDIR=/tmp

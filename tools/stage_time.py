@@ -1,4 +1,4 @@
-"""GPU tuning aid: time given stages once (HIP events), honouring MMVAE_ABLATE / split env."""
+"""GPU tuning aid: time given stages once (HIP events), honouring the MMVAE_SPLIT* / MMVAE_LIB environment."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,4 +20,4 @@ for sid in [int(s) for s in sys.argv[1:]]:
     e0.record()
     for _ in range(10): eng.debug_stage(sid, hyper, noise, m._flat, x, 0, m._flat_grad)
     e1.record(); e1.synchronize()
-    print(f"ABLATE={os.environ.get('MMVAE_ABLATE','0')} splits={[os.environ.get(f'MMVAE_SPLIT{w}') for w in range(4)]} stage {sid}: {e0.elapsed_time(e1)/10*1e3:.1f} us", flush=True)
+    print(f"splits={[os.environ.get(f'MMVAE_SPLIT{w}') for w in range(4)]} stage {sid}: {e0.elapsed_time(e1)/10*1e3:.1f} us", flush=True)
