@@ -77,9 +77,7 @@ N_TUNE = 24
 # environment switch that sets each one: the LIBRARY reads
 # no environment variables, this module translates them (experiments and A/B timing only; none is needed in production)
 TUNE_ENV = {
-    "MMVAE_EVAL_CHAIN": (0, lambda v: int(int(v) == 0)), "MMVAE_AUG_TILE": (3, int),
-    "MMVAE_FC11_ZG": (8, lambda v: int(int(v) == 0)), "MMVAE_COUPLE_SIDE": (13, int),
-    "MMVAE_BF16_NARROW_FP32": (18, int), "MMVAE_BN_PARTIALS": (19, int), "MMVAE_PRESPLIT_ALL": (20, int), "MMVAE_CHAIN_FP32": (21, int),
+    "MMVAE_AUG_TILE": (3, int), "MMVAE_COUPLE_SIDE": (13, int), "MMVAE_BN_PARTIALS": (19, int), "MMVAE_CHAIN_FP32": (21, int),
 }
 TUNE_ENGINE = 17    # MMVAE_TUNE_ENGINE: the GEMM engine the caller runs (the layout's split factors are chosen for it)
 
@@ -93,9 +91,9 @@ class Exec(C.Structure):
 
 def exec_from_env(engine: int = 0) -> Exec:
     """An Exec with the split factors (MMVAE_SPLIT<i>) and experiment switches the environment asks for; ``engine`` is the
-    GEMM engine the caller is going to run (gemm_mode(...) & 0xFF)."""
+    GEMM engine the caller is going to run (gemm_mode(...))."""
     ex = Exec()
-    ex.tune[TUNE_ENGINE] = engine & 0xFF
+    ex.tune[TUNE_ENGINE] = engine
     for w in range(6):
         v = os.environ.get(f"MMVAE_SPLIT{w}")
         if v:
@@ -249,7 +247,7 @@ class Engine:
 
     def __init__(self, A, B, D, H, L, Cc, S, device, ex: Optional[Exec] = None, gemm_engine: int = 0):
         self.dims = Dims(A, B, D, H, L, Cc, S)
-        self.gemm_engine = gemm_engine & 0xFF      # which engine the layout's split factors are chosen for
+        self.gemm_engine = gemm_engine             # which engine the layout's split factors are chosen for
         check(lib().mmvae_check_dims(C.byref(self.dims)), "mmvae_check_dims")
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -493,7 +491,4 @@ def gemm_mode(dtype: str) -> int:
         dtype = FP32_ENGINE
     if dtype not in _GEMM_MODES:
         raise ValueError(f"gemm_dtype must be 'fp32', 'fp32_mfma', 'fp32x3' or 'bf16', got {dtype!r}")
-    mode = _GEMM_MODES[dtype]
-    if mode == 2:   # diagnostics: MMVAE_X3_OFF=<mask> keeps single products on the fp32 matrix instruction (1 fc1, 2 fc11, 4 dW1, 8 dW11)
-        mode |= (int(os.environ.get("MMVAE_X3_OFF", "0")) & 0xF) << 8
-    return mode
+    return _GEMM_MODES[dtype]

@@ -157,7 +157,7 @@ class Augmenter_smartseq(nn.Module):
     def planes_needed(self) -> int:
         """Slice planes per matrix element the row-indexed forward wants from ``DeviceLoader.data_planes`` for the current
         ``gemm_dtype``: 3 (fp32: the exact fp32x3 slices), 1 (bf16), 0 = not offered (the fp32 matrix-instruction engine)."""
-        mode = N.gemm_mode(self.gemm_dtype) & 0xFF
+        mode = N.gemm_mode(self.gemm_dtype)
         return 3 if mode == 2 else (1 if mode == 1 else 0)
 
     @torch.no_grad()

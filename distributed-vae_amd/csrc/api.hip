@@ -219,6 +219,7 @@ static int make_ctx(Ctx& c, const mmvae_dims* d, const mmvae_hyper* h, void* ws,
                     void* stream) {
     if (int rc = check_dims(d)) return rc;
     if (!h || !ws) { set_error("null hyper / workspace"); return MMVAE_E_BADARG; }
+    if (int rc = check_gemm_engine(h->gemm_bf16)) return rc;
     if (h->training && d->B < 2) {   // a one-cell batch has no batch statistics; eval mode (running statistics) takes it
         set_error("training mode needs B >= 2 for the batch statistics (got B=%d)", d->B);
         return MMVAE_E_BADARG;
@@ -323,7 +324,7 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
     // batch statistics are recombined by the kernel that consumes each BatchNorm (no finalize launches);
     // eval mode copies the running statistics into the workspace instead
     if ((rc = launch_bn_eval_stats(c, bn_running))) return rc;
-    if (!c.h.training && !c.tune(MMVAE_TUNE_EVAL_CHAIN_OFF)) {
+    if (!c.h.training) {
         if ((rc = launch_chain_fwd_enc_eval(c, params))) return rc;
     } else {
         for (int layer = 2; layer <= 5; ++layer)
@@ -360,7 +361,6 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
         *couple_done = true;
         c.couple_in_dec = true;
         if ((rc = launch_chain_fwd_dec(c, params, true))) return rc;
-        if (need_grad && (rc = launch_x3_planes(c, params, 2))) return rc;
         return fc11_with_fork();
     }
     if (couple_done && c.side()) {
@@ -372,8 +372,7 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
             if ((rc = record_on_side(c, EV_COUPLE))) return rc;
         }
     }
-    if ((rc = launch_chain_fwd_dec(c, params))) return rc;
-    if (fast && need_grad && (rc = launch_x3_planes(c, params, 2))) return rc;   // fp32x3: slice planes of [d10 | 1] (fc11, dW11)
+    if ((rc = launch_chain_fwd_dec(c, params))) return rc;   // (fp32x3: it writes the slice planes of [d10 | 1] for fc11, dW11)
     if (t_early) return fc11_with_fork();
     if (couple_done && *couple_done && (rc = record_on_side(c, EV_COUPLE))) return rc;
     if (fast) return launch_fc11_fast(c, params, x, xs, x_rec, need_grad);
@@ -619,9 +618,9 @@ int mmvae_train_step_rows(const mmvae_dims* d, const mmvae_hyper* h, const mmvae
         set_error("train_step_rows: needs ld %% 4 == 0, 16-byte aligned data and n_rows * ld < 2^30 floats");
         return MMVAE_E_UNSUPPORTED;
     }
-    const bool x3 = split3_gemms(c) && d->H + 1 <= 112, b16 = (h->gemm_bf16 & 0xFF) == 1 && bf16_gemms(c);
+    const bool x3 = split3_gemms(c) && d->H + 1 <= 112, b16 = h->gemm_bf16 == 1 && bf16_gemms(c);
     if (!h->training || !(h->x_drop > 0.f) || !(x3 || b16) || !prologue_merged(c) || !fast_path_ok(c, params, data, 0) ||
-        (int64_t)cdiv(d->B, 128) * c.lay.sp.ks_gd10 > c.lay.n11 || c.tune(MMVAE_TUNE_FC11_ZG_OFF) || ((h->gemm_bf16 >> 8) & 15)) {
+        (int64_t)cdiv(d->B, 128) * c.lay.sp.ks_gd10 > c.lay.n11) {
         set_error("train_step_rows: only the fused training step of the fp32x3 / bf16 engines reads the batch through a row map");
         return MMVAE_E_UNSUPPORTED;
     }

@@ -25,15 +25,6 @@
 
 namespace mmvae {
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 static inline int64_t pad4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
 
@@ -191,9 +182,7 @@ __global__ void k_aug_pack_affine(const float* __restrict__ bias, const float* _
 struct AugLayer {         // offsets in floats into the packed buffer
     int64_t w, sc, sh;
     int N, K, ldw;
-    int64_t pl;           // the weight's three bf16 slice planes [3][Np][Kp] (fp32x3 engine; gemm_bf16.hip), Np = N padded to
-    int Np, Kp;           // whole 128-row tiles, Kp = ldw padded to whole K tiles of 32
-    int64_t tp;           // the same three slices as TILED planes (gemm_pp.hip: [3][ceil(ldw / 16)][N rounded up to 256][16] bf16)
+    int64_t tp;           // the weight's three bf16 slice planes, tiled (gemm_pp.hip: [3][ceil(ldw / 16)][N rounded up to 256][16] bf16)
 };
 struct AugPacked {
     AugLayer g[10];          // fc1 fc2 fc3 fc4 fc5[:, :n]  fc7 fc8 fc9 fc10 fc11
@@ -220,9 +209,6 @@ static AugPacked aug_packed_layout(const mmvae_aug_dims& d) {
         g.w = take((int64_t)g.N * g.ldw);
         g.sc = take(g.N);
         g.sh = take(g.N);
-        g.Np = (g.N + 127) / 128 * 128;
-        g.Kp = (g.ldw + 31) / 32 * 32;
-        g.pl = take((int64_t)3 * g.Np * g.Kp / 2);     // bf16: two per float
         g.tp = take(3 * tp_plane_elems(g.N, g.ldw) / 2);
     }
     p.noise_w = take((int64_t)NZ * NZ); p.z_sc = take(NZ); p.z_sh = take(NZ);
@@ -420,15 +406,11 @@ static void aug_gemm_launch(hipStream_t s, bool relu, bool affine, const float* 
 }
 
 static int aug_gemm(hipStream_t s, int force_tile, bool relu, bool affine, const float* A, int lda, int M, const float* pk,
-                    const AugLayer& g, float* C, int ldc, float* scratch = nullptr, int64_t scratch_floats = 0) {
+                    const AugLayer& g, float* C, int ldc) {
     const int ncols = ldc < (int)pad4(g.N) ? ldc : (int)pad4(g.N);   // the K padding of the next layer is written too (zeros)
     const float* W = pk + g.w;
     const float* sc = pk + g.sc;
     const float* sh = pk + g.sh;
-    if (force_tile == 99 || force_tile == 98)   // bf16 operands (mmvae_augment's gemm_bf16 = 1) or fp32 operands split into
-        // three bf16 slices (gemm_bf16 = 2): the shared tile engine of gemm_bf16.hip, fp32 epilogue
-        return launch_bf16_affine(s, relu, affine, A, lda, M, W, g.ldw, g.N, g.ldw, sc, sh, C, ldc, ncols, force_tile == 98,
-                                  reinterpret_cast<const unsigned short*>(pk + g.pl), g.Np, g.Kp, scratch, scratch_floats);
     // the largest tile that still leaves two workgroups per CU (256 CUs); MMVAE_AUG_TILE=<BM><BN> code forces one
     const int force = force_tile;   // 11 12 21 22 (1 = 64, 2 = 128), 0 = automatic
     auto count = [&](int bm, int bn) { return (int64_t)cdiv(M, bm) * cdiv(ncols, bn); };
@@ -498,9 +480,7 @@ int mmvae_aug_pack(const mmvae_aug_dims* d, const mmvae_aug_tensors* t, float* p
         const int mi = mod_of_g[i];
         const int src_ld = (mi == 4) ? d->N3 + d->NZ : g.K;
         packw(t->w[mi], src_ld, 0, g.N, g.K, g.w, g.ldw);
-        // slice planes of the packed (zero-padded) weight for the fp32x3 engine
-        if (int rc = launch_presplit_one(s, packed + g.w, g.ldw, g.N, g.ldw, g.Np, g.Kp, reinterpret_cast<unsigned short*>(packed + g.pl)))
-            return rc;
+        // slice planes of the packed (zero-padded) weight for the planes x planes engine
         if (int rc = launch_tp_from_f32(s, packed + g.w, g.ldw, g.N, g.ldw, 3, tp_make(reinterpret_cast<unsigned short*>(packed + g.tp), g.N, g.ldw)))
             return rc;
         if (mi == 4) continue;                                  // fc5's affine is applied in the latent kernel
@@ -531,6 +511,7 @@ static int augment_impl(const mmvae_aug_dims* d, const float* packed, const floa
                         const float* eps_n, float scale, void* ws, size_t ws_bytes, float* s_out, float* x_aug,
                         int gemm_bf16, const mmvae_exec* ex, void* stream) {
     if (int rc = aug_check_dims(d)) return rc;
+    if (int rc = check_gemm_engine(gemm_bf16)) return rc;
     if (!packed || (!x && !xp) || !z0 || !eps_n || !ws || !s_out || !x_aug) { set_error("augment: null argument"); return MMVAE_E_BADARG; }
     const bool shared = x_arm_stride == 0;
     if (!shared && x_arm_stride != (int64_t)d->B * d->D) {
@@ -543,14 +524,13 @@ static int augment_impl(const mmvae_aug_dims* d, const float* packed, const floa
     const AugPacked L = aug_packed_layout(*d);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* w = reinterpret_cast<float*>(ws);
-    const int ft = gemm_bf16 == 2 ? 98 : gemm_bf16 ? 99 : (ex ? ex->tune[MMVAE_TUNE_AUG_TILE] : 0);
+    const int ft = ex ? ex->tune[MMVAE_TUNE_AUG_TILE] : 0;
     int rc;
-    const int tune_tile = ex ? ex->tune[MMVAE_TUNE_AUG_TILE] : 0;
-    if (xp && !(gemm_bf16 && tune_tile != 90)) { set_error("augment_rows: needs the planes engine (gemm_bf16 1 or 2)"); return MMVAE_E_UNSUPPORTED; }
-    if (gemm_bf16 && tune_tile != 90) {
+    if (xp && !gemm_bf16) { set_error("augment_rows: needs the planes engine (gemm_bf16 1 or 2)"); return MMVAE_E_UNSUPPORTED; }
+    if (gemm_bf16) {
         // planes x planes engine (gemm_pp.hip): every layer's epilogue writes the next layer's operand as tiled slice planes
-        // (three exact slices: fp32x3; one rounded plane: the bf16 configuration).  MMVAE_AUG_TILE=90: the tile engine of
-        // gemm_bf16.hip as before (A/B timing); 1..3 (+ 10 x workgroups): forced tile / grid for every layer.
+        // (three exact slices: fp32x3; one rounded plane: the bf16 configuration).  MMVAE_AUG_TILE 1..3 (+ 10 x workgroups):
+        // forced tile / grid for every layer.
         const int NP = gemm_bf16 == 2 ? 3 : 1;
         auto tpa = [&](int64_t off, int rows, int K) { return tp_make(reinterpret_cast<unsigned short*>(w + off), rows, K); };
         auto tpw = [&](int i) {
@@ -568,7 +548,7 @@ static int augment_impl(const mmvae_aug_dims* d, const float* packed, const floa
             TPlanes a = in;
             if (a.KT > b.KT) a.KT = b.KT; else b.KT = a.KT;     // (equal unless the producer's width was padded differently)
             return launch_pp_gemm(s, NP, a, b, M, L.g[i].N, packed + L.g[i].sc, packed + L.g[i].sh, affine, relu, out32, ld32, nc32, outp,
-                                  scr, W.scratch_floats, i, tune_tile, mapped ? rmap : nullptr, mapped ? W.rowmap_n : 0);
+                                  scr, W.scratch_floats, i, ft, mapped ? rmap : nullptr, mapped ? W.rowmap_n : 0);
         };
         // (the forward's first launch also zeroes the flag words of the K-split combines)
         if (xp) {
@@ -599,9 +579,8 @@ static int augment_impl(const mmvae_aug_dims* d, const float* packed, const floa
         if ((rc = layer(8, H9, R, true, true, nullptr, 0, 0, &H10))) return rc;
         return layer(9, H10, R, true, true, x_aug, d->D, d->D, nullptr);
     }
-    // trunk: once per cell when the arms share x
-    // (the first layer may split K into slabs: the buffers of the last two hidden layers, h9 and h10, are adjacent and not in use yet)
-    if ((rc = aug_gemm(s, ft, true, true, x, d->D, T, packed, L.g[0], w + W.h1, W.ld1, w + W.h9, W.total - W.h9))) return rc;
+    // fp32 matrix instruction (gemm_bf16 = 0); trunk: once per cell when the arms share x
+    if ((rc = aug_gemm(s, ft, true, true, x, d->D, T, packed, L.g[0], w + W.h1, W.ld1))) return rc;
     if ((rc = aug_gemm(s, ft, true, true, w + W.h1, W.ld1, T, packed, L.g[1], w + W.h2, W.ld1))) return rc;
     if ((rc = aug_gemm(s, ft, true, true, w + W.h2, W.ld1, T, packed, L.g[2], w + W.h3, W.ld3))) return rc;
     if ((rc = aug_gemm(s, ft, true, true, w + W.h3, W.ld3, T, packed, L.g[3], w + W.h4, W.ld3))) return rc;
@@ -647,6 +626,7 @@ int mmvae_augment_rows(const mmvae_aug_dims* d, const float* packed, const uint1
                        const int64_t* rows, const float* z0, const float* eps_n, float scale, void* ws, size_t ws_bytes,
                        float* s_out, float* x_aug, int gemm_bf16, const mmvae_exec* ex, void* stream) {
     if (int rc = aug_check_dims(d)) return rc;
+    if (int rc = check_gemm_engine(gemm_bf16)) return rc;
     if (!x_planes || !rows || !mmvae_tp_planes_bytes(n_rows, d->D, n_planes)) { set_error("augment_rows: bad planes argument"); return MMVAE_E_BADARG; }
     if (n_planes != (gemm_bf16 == 2 ? 3 : 1) || !gemm_bf16) {
         set_error("augment_rows: the planes must be the engine's (three for gemm_bf16 = 2, one for 1)");

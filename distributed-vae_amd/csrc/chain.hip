@@ -19,15 +19,6 @@
 
 namespace mmvae {
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 constexpr int CH_RT = CHAIN_ROWS / 32;     // 32-row tiles per workgroup
 constexpr int CH_NT = 256 * CH_RT;         // threads per workgroup
 
@@ -1016,8 +1007,8 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
     a.bn_mean_off = a.bn_rstd_off = a.bn_part_off = -1;
     a.stats_part_off = -1;
     a.acc_in_off = a.acc_out_off = -1;
-    // fp32x3 engine: the slice planes of [d10 | 1] (launch_x3_planes(.., 2) then has nothing to do)
-    a.planes_off = dec_chain_writes_planes(c) ? L.pl_d10 : -1;
+    // fp32x3 engine: the slice planes of [d10 | 1] for fc11 and dW11
+    a.planes_off = split3_gemms(c) ? L.pl_d10 : -1;
     a.planes_rows = rup(d.B, 256);
     a.B = d.B;
     a.ld = fwd_ld(max(max(d.H, d.L), d.C + d.S));

@@ -114,6 +114,21 @@ struct POff {
 POff make_poff(const mmvae_dims& d);
 
 void set_error(const char* fmt, ...);
+// the launch just made failed: record why and return MMVAE_E_LAUNCH from the calling launcher
+#define HIP_LAUNCH_CHECK(what)                                                        \
+    do {                                                                              \
+        hipError_t e_ = hipGetLastError();                                            \
+        if (e_ != hipSuccess) {                                                       \
+            set_error("%s: %s", what, hipGetErrorString(e_));                         \
+            return MMVAE_E_LAUNCH;                                                    \
+        }                                                                             \
+    } while (0)
+// mmvae_hyper.gemm_bf16 and mmvae_augment's gemm_bf16 name one of three engines (include/mmvae.h)
+inline int check_gemm_engine(int gemm_bf16) {
+    if (gemm_bf16 >= 0 && gemm_bf16 <= 2) return 0;
+    set_error("gemm_bf16 must be 0, 1 or 2 (got %d)", gemm_bf16);
+    return MMVAE_E_BADARG;
+}
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------------------------------
@@ -821,42 +836,26 @@ int launch_dw_big_fast(const Ctx& c, const float* x, int64_t xs, int which /*bit
 // bf16-operand variants of the five D x H GEMMs (gemm_bf16.hip; mmvae_hyper.gemm_bf16), same outputs / layouts
 // gemm_bf16 == 2: fp32 operands split exactly into three bf16 slices each (six slice products per product: fp32-grade
 // results on the bf16 matrix pipe); the same tile engine with three LDS planes per operand
-// bits 8.. of gemm_bf16 (diagnostics): products that stay on the fp32 matrix instruction although gemm_bf16 & 0xFF == 2
-// (1 fc1, 2 fc11 + d(d10), 4 dW1, 8 dW11)
-inline bool split3_gemms(const Ctx& c, int op = 0) { return (c.h.gemm_bf16 & 0xFF) == 2 && c.d.H <= 124 && !((c.h.gemm_bf16 >> 8) & op); }
-inline bool bf16_gemms(const Ctx& c, int op = 0) { return ((c.h.gemm_bf16 & 0xFF) == 1 || split3_gemms(c, op)) && c.d.H <= 124; }
-int launch_x3_planes(const Ctx& c, const float* params, int which /*bit0 W1 + [W11|b11] + small layers, bit1 [d10|1], bit2 dZ1, bit3 small layers only, bit4 + keep-mask and zero fill (head of a training step)*/,
+inline bool split3_gemms(const Ctx& c) { return c.h.gemm_bf16 == 2 && c.d.H <= 124; }
+inline bool bf16_gemms(const Ctx& c) { return (c.h.gemm_bf16 == 1 || c.h.gemm_bf16 == 2) && c.d.H <= 124; }
+int launch_x3_planes(const Ctx& c, const float* params, int which /*bit0 W1 + [W11|b11] + small layers, bit2 dZ1, bit3 small layers only, bit4 + keep-mask and zero fill (head of a training step)*/,
                      const mmvae_noise* nz = nullptr);
-// true when launch_x3_planes(.., 1 | 16, nz) takes over k_make_xbits' work (the engines that have a k_presplit launch at the head of the step)
-inline bool prologue_merged(const Ctx& c);
-// the kernels that produce dZ1 / d10 write their slice planes themselves (no k_presplit launch for them)
 // the chain kernels' own GEMMs on the fp32x3 engine: every layer within one 128 x 128 plane
 // (also in the bf16 configuration: only its five D x H products round their operands, everything else stays fp32-grade)
 inline bool chain_x3_ok(const Ctx& c) {
     return bf16_gemms(c) && c.d.C + c.d.S <= 128 && c.d.L <= 128 && !c.tune(MMVAE_TUNE_CHAIN_FP32);
 }
-inline bool prologue_merged(const Ctx& c) {
-    return c.h.training && c.h.x_drop > 0.f && (split3_gemms(c) || chain_x3_ok(c)) && !c.tune(MMVAE_TUNE_PRESPLIT_ALL);
-}
-inline bool dec_chain_writes_planes(const Ctx& c) { return split3_gemms(c) && !c.tune(MMVAE_TUNE_PRESPLIT_ALL); }
+// true when launch_x3_planes(.., 1 | 16, nz) takes over k_make_xbits' work (the engines that have a k_presplit launch at the head of the step)
+inline bool prologue_merged(const Ctx& c) { return c.h.training && c.h.x_drop > 0.f && (split3_gemms(c) || chain_x3_ok(c)); }
 // bf16 configuration on bf16 storage (mmvae_train_step_rows(data_bf16)): the NARROW operands of fc1 / dW1 (W1, dZ1) are read as
 // bf16 too -- slice 0 of the planes the fp32x3 engine uses -- instead of fp32 rounded by every block tile
-inline bool bf16_narrow_planes(const Ctx& c) {
-    return (c.h.gemm_bf16 & 0xFF) == 1 && c.x16 != nullptr && c.d.H <= 124 && (c.d.D & 7) == 0 && !c.tune(MMVAE_TUNE_PRESPLIT_ALL) &&
-           !c.tune(MMVAE_TUNE_BF16_NARROW_FP32);
-}
-inline bool bn_apply_writes_planes(const Ctx& c) {
-    return (split3_gemms(c, 4) || bf16_narrow_planes(c)) && (c.d.H & 1) == 0 && !c.tune(MMVAE_TUNE_PRESPLIT_ALL);
-}
+inline bool bf16_narrow_planes(const Ctx& c) { return c.h.gemm_bf16 == 1 && c.x16 != nullptr && c.d.H <= 124 && (c.d.D & 7) == 0; }
+// k_bn_bwd_apply writes the slice planes of dZ1 itself (no k_presplit job for them), as the decoder chain does those of
+// [d10 | 1] under split3_gemms
+inline bool bn_apply_writes_planes(const Ctx& c) { return (split3_gemms(c) || bf16_narrow_planes(c)) && (c.d.H & 1) == 0; }
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs);
 int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which);
 int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which);
-int launch_bf16_affine(hipStream_t s, bool relu, bool affine, const float* A, int lda, int M, const float* W, int ldw, int N,
-                       int Kpad, const float* sc, const float* sh, float* C, int ldc, int ncols, int split3 = 0,
-                       const unsigned short* w_planes = nullptr, int Np = 0, int Kp = 0,
-                       float* scratch = nullptr, int64_t scratch_floats = 0 /*room for split-K slabs of layers with few tiles and a long K*/);
-// fp32 [R][C] (row pitch ld) -> three bf16 slice planes [3][Rp][Cp], zero-padded (fp32x3 engine)
-int launch_presplit_one(hipStream_t s, const float* src, int64_t ld, int R, int C, int Rp, int Cp, unsigned short* dst);
 // planes x planes GEMM (gemm_pp.hip): tiled slice planes of a matrix X [R][K] -- NP planes (3 exact slices / 1 rounded), each
 // [KT = ceil(K / 16)][Rp = R rounded up to 256][16] bf16, zero for k >= K
 struct TPlanes { unsigned short* p; int64_t plane; int Rp, KT; };

@@ -12,15 +12,6 @@
 
 namespace mmvae {
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 // labels[a][b] = argmax_k c[a][b][k], first maximum on ties (np.argmax).  One wave per cell; grid-stride.
 __global__ __launch_bounds__(256) void k_classify(const float* __restrict__ cc, int64_t n_cells, int C,
                                                   int32_t* __restrict__ labels) {

@@ -9,15 +9,6 @@
 
 namespace mmvae {
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ data, int64_t ld, int64_t n_rows,
                                                      const int64_t* __restrict__ idx, int64_t n, int D,

@@ -3,7 +3,7 @@
 //   * mmvae_hyper.gemm_bf16 == 1 -- BASELINE.json configs[2] ("bf16, DP over 8 GPUs"): operands ROUNDED to bf16;
 //   * mmvae_hyper.gemm_bf16 == 2 -- "fp32x3", the library's fp32 engine: every fp32 operand split EXACTLY into three bf16
 //     slices, six slice products per product (see Eng<NP> below; k_presplit, k_x3_gemm, k_x3_small, k_x3_fc11g; DESIGN.md
-//     section 14).  It also serves the small-layer gradient products and the augmenter's layers.
+//     section 14).  It also serves the small-layer gradient products.
 //
 // What follows describes the shared tile engine in its one-plane (bf16) form.  Operands are rounded to bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32) on their way
 // into LDS, products accumulate in fp32 on v_mfma_f32_32x32x16_bf16 (2.5 PFLOP/s dense: 16 x the fp32 matrix rate), and
@@ -34,15 +34,6 @@
 #include "common.hpp"
 
 namespace mmvae {
-
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -250,20 +241,20 @@ __device__ __forceinline__ void ro_init(unsigned (&ro)[Eng<NP>::NQ], const Opera
     }
 }
 // the indexed operand's offsets for its first K tile (and, K-minor, the request for the second one's)
-template <bool KMINOR, int NP, int KSTEP>
+template <bool KMINOR, int NP>
 __device__ __forceinline__ void idx_begin(unsigned (&ro)[Eng<NP>::NQ], MapRegs<NP>& mr, const OperandDev& o, int r0, int kfirst) {
     if constexpr (KMINOR) {
         map_request<NP>(mr, o, kfirst);
         map_offsets<NP>(ro, mr);
-        map_request<NP>(mr, o, kfirst + KSTEP);
+        map_request<NP>(mr, o, kfirst + Eng<NP>::KT);
     } else ro_init<NP>(ro, o, r0);
 }
 // ... and for the K tile at kld, at the head of the staging phase that requests it
-template <bool KMINOR, int NP, int KSTEP>
+template <bool KMINOR, int NP>
 __device__ __forceinline__ void idx_next(unsigned (&ro)[Eng<NP>::NQ], MapRegs<NP>& mr, const OperandDev& o, int kld) {
     if constexpr (KMINOR) {
         map_offsets<NP>(ro, mr);
-        map_request<NP>(mr, o, kld + KSTEP);
+        map_request<NP>(mr, o, kld + Eng<NP>::KT);
     }
 }
 template <bool KMINOR, bool BITS = true, int NP = 1, bool BN = false>
@@ -550,12 +541,6 @@ struct Fc11Out {       // z tile -> + bias, dZ11, loss partials (nn_model.py:286
     int64_t x_nrec;
 };
 
-struct AffineOut {     // C tile -> out[m][n] = act(C * scale[n] + shift[n]) (the augmenter's Linear + folded BatchNorm + ReLU);
-    const float *scale, *shift;   // columns N .. ld - 1 (the next layer's K padding) are written as zeros
-    float* out;
-    int ld, M, N, relu, affine;
-};
-
 struct GemmArgs {
     Operand a, b;
     int64_t a_arm, b_arm;        // arm strides of the operands (floats); mask bits: a_bits_arm / b_bits_arm (words)
@@ -565,7 +550,6 @@ struct GemmArgs {
     int KS;                      // splits of the k range (grid.y) -- or of the n tiles when loop_n
     SlabOut so;
     Fc11Out fo;
-    AffineOut ao;
     int64_t fo_arm, fo_x_arm;    // arm strides of dz / x_rec and of x (0: the arms share x)
     int n11;
     int A;
@@ -614,33 +598,10 @@ __device__ __forceinline__ void mfma_ktile(f32x16 (&acc)[2][2], const unsigned* 
     }
 }
 
-// The tile epilogues: accumulator register r of tile (i, j) is row m0 + 64 wm + 32 i + acc_row(r), column
+// The tile epilogue: accumulator register r of tile (i, j) is row m0 + 64 wm + 32 i + acc_row(r), column
 // n0 + 64 wn + 32 j + (lane & 31).
-template <int EPI>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int lane, int arm) {
     const int l31 = lane & 31;
-    if (EPI == 1) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + 64 * wn + 32 * j + l31;
-            if (col >= g.ao.ld) continue;
-            const bool real = col < g.ao.N;
-            const float sc = (g.ao.affine && real) ? g.ao.scale[col] : 1.f;
-            const float sh = (g.ao.affine && real) ? g.ao.shift[col] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + 64 * wm + 32 * i + acc_row(r, lane);
-                    if (row < g.ao.M) {
-                        float v = acc[i][j][r] * sc + sh;
-                        if (g.ao.relu) v = fmaxf(v, 0.f);
-                        g.ao.out[(int64_t)row * g.ao.ld + col] = real ? v : 0.f;
-                    }
-                }
-        }
-        return;
-    }
     float* out = g.so.out + (int64_t)blockIdx.y * g.so.ks_stride + (int64_t)arm * g.so.arm_stride;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -659,7 +620,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
 // the second LDS buffer while tile t is multiplied (one barrier per K tile); a piece's registers request tile t + 2 as
 // soon as they have been written out for tile t + 1.
 // IDX: 1 / 2 = the A / B operand through its row map (see k_x3_gemm); S16: bit 0 / bit 1 = the A / B operand is bf16 in memory
-template <bool AMINOR, bool BMINOR, int EPI = 0, int IDX = 0, int S16 = 0>
+template <bool AMINOR, bool BMINOR, int IDX = 0, int S16 = 0>
 __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
     const GemmArgs g = g_in;
     __shared__ __attribute__((aligned(16))) unsigned As[2][BT * LDB];   // two K tiles in LDS: tile t is multiplied while tile
@@ -672,11 +633,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
     if (ob_h.bits) ob_h.bits += (int64_t)arm * g.b_bits_arm;
     const OperandDev oa = make_operand_dev<AMINOR>(oa_h), ob = make_operand_dev<BMINOR>(ob_h);
     const int tiles_n = cdiv(g.N, BT);
-    int wg = blockIdx.x;
-    if (EPI == 1) {   // XCD-aware tile order: workgroup i runs on XCD i % 8; give XCD x a contiguous range of tiles
-        const int nwg = gridDim.x;
-        if (nwg % 8 == 0) wg = (wg & 7) * (nwg >> 3) + (wg >> 3);
-    }
+    const int wg = blockIdx.x;
     const int m0 = (wg / tiles_n) * BT, n0 = (wg % tiles_n) * BT;
     const int nkt = cdiv(g.K, KT);
     const int kb = (int)(((int64_t)blockIdx.y * nkt) / g.KS) * KT;
@@ -695,11 +652,11 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
         constexpr bool LOAD = decltype(load_tag)::value;
         if constexpr (LOAD && IDX == 1 && AMINOR) {
             if constexpr (A16) { oct_map_offsets(ro, mr); map_request<1>(mr, oa, kld + KT); }
-            else idx_next<AMINOR, 1, KT>(ro, mr, oa, kld);
+            else idx_next<AMINOR, 1>(ro, mr, oa, kld);
         }
         if constexpr (LOAD && IDX == 2 && BMINOR) {
             if constexpr (B16) { oct_map_offsets(ro, mr); map_request<1>(mr, ob, kld + KT); }
-            else idx_next<BMINOR, 1, KT>(ro, mr, ob, kld);
+            else idx_next<BMINOR, 1>(ro, mr, ob, kld);
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -746,7 +703,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) oct_load<MINOR, IDXD>(t16, o, r0, kb, ke, q, ro);
         } else if constexpr (IDXD) {
-            idx_begin<MINOR, 1, KT>(ro, mr, o, r0, kb);
+            idx_begin<MINOR, 1>(ro, mr, o, r0, kb);
 #pragma unroll
             for (int q = 0; q < Eng<1>::NQ; ++q) quad_load_idx<MINOR, 1>(ISA ? ta : tb, o, r0, kb, ke, q, ro);
         } else tile_load<MINOR>(ISA ? ta : tb, o, r0, kb, ke);
@@ -768,7 +725,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
         __syncthreads();
         cur ^= 1;
     }
-    gemm_epilogue<EPI>(g, acc, m0, n0, wm, wn, lane, arm);
+    gemm_epilogue(g, acc, m0, n0, wm, wn, lane, arm);
 }
 
 // The split (NP = 3) engine: fp32 operands as three bf16 planes each, six MFMAs per pair of fragments.  With six times the
@@ -786,11 +743,8 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
 // in-kernel stamps: a stage phase lasts as long as its loads take to issue).  Group 0 stages the shared operand for both
 // (two LDS buffers, indexed by the K tile's parity; group 1 multiplies tile t while group 0 already stages tile t + 1), a
 // quarter less traffic per pair of tiles.  LDS: two private + two shared buffer sets of 30 KB = 120 KB.
-// SPL: the shared operand comes as slice planes (k_presplit) and is copied, not split again by every block.
-// SHARE = 3: BOTH groups work on the SAME block tile and take alternate K tiles (group g: tiles g, g + 2, ...); group 1's
-// accumulators are added to group 0's through LDS before the epilogue.  For GEMMs with fewer tiles than CUs (the augmenter's
-// 500- and 1000-wide trunk layers at M = 5000: 40 to 160 tiles): twice the workgroups, half the K loop each.  With SPL the B
-// operand comes from planes, copied by each group for its own K tiles.
+// The shared operand comes as slice planes (k_presplit, or the kernel that produced it) and is copied, not split again by
+// every block.
 // IDX: 1 / 2 = the A / B operand is read through its row map (Operand::rowmap: x of a batch that is never materialised)
 // K tiles of the fp32 operand a group keeps in flight.  2 (-DX3_DEPTH=2) was measured and lost: the kernels sit at 234 - 242 of
 // the 256 registers a thread of a 512-thread workgroup has, twenty more for the second tile spilled (2 - 40 registers) and
@@ -799,8 +753,9 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
 #define X3_DEPTH 1
 #endif
 static_assert(X3_DEPTH == 1 || X3_DEPTH == 2, "one or two K tiles in flight");
-template <bool AMINOR, bool BMINOR, int EPI = 0, int SHARE = 0, bool SPL = false, int IDX = 0>
+template <bool AMINOR, bool BMINOR, int SHARE, int IDX = 0>
 __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
+    static_assert(SHARE == 1 || SHARE == 2, "the two tiles of a block share one operand");
     typedef Eng<3> E;
     constexpr int KTv = E::KT;
     const GemmArgs g = g_in;
@@ -814,28 +769,18 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
     if (ob_h.bits) ob_h.bits += (int64_t)arm * g.b_bits_arm;
     const OperandDev oa = make_operand_dev<AMINOR>(oa_h), ob = make_operand_dev<BMINOR>(ob_h);
     // The two tiles of a block: neighbours along m for the same n tile when they share the B operand (SHARE = 2), along n
-    // for the same m tile when they share A (SHARE = 1), consecutive tiles of the (m, n) list otherwise.  An odd count
-    // leaves the last block's second group idle.  EPI = 1 (the augmenter's layers): XCD-aware block order -- workgroup i
-    // runs on XCD i % 8; give XCD x a contiguous range of blocks (neighbouring n tiles read the same activation rows).
+    // for the same m tile when they share A (SHARE = 1).  An odd count leaves the last block's second group idle.
     const int tiles_m = cdiv(g.M, BT), tiles_n = cdiv(g.N, BT);
-    int bi = blockIdx.x;
-    if (EPI == 1 && (gridDim.x & 7) == 0) bi = (bi & 7) * (gridDim.x >> 3) + (bi >> 3);
+    const int bi = blockIdx.x;
     int tm, tn;
     if (SHARE == 2) { tn = bi % tiles_n; tm = 2 * (bi / tiles_n) + grp; }
-    else if (SHARE == 1) { tm = bi % tiles_m; tn = 2 * (bi / tiles_m) + grp; }
-    else if (SHARE == 3) { tm = bi / tiles_n; tn = bi % tiles_n; }
-    else { const int wg = 2 * bi + grp; tm = wg / tiles_n; tn = wg % tiles_n; }
+    else { tm = bi % tiles_m; tn = 2 * (bi / tiles_m) + grp; }
     const bool active = tm < tiles_m && tn < tiles_n;
     const int m0 = tm * BT, n0 = tn * BT;
     const int nkt = cdiv(g.K, KTv);
     const int kb = (int)(((int64_t)blockIdx.y * nkt) / g.KS) * KTv;
     const int ke = min(g.K, (int)(((int64_t)(blockIdx.y + 1) * nkt) / g.KS) * KTv);
-    const int n_all = ke > kb ? cdiv(ke - kb, KTv) : 0;  // K tiles of this block
-    // SHARE = 3: this group's share of them (tiles grp, grp + 2, ...); the phase loop runs for the larger share
-    const int n = SHARE == 3 ? (n_all + 1) / 2 : n_all;
-    const int n_mine = SHARE == 3 ? (n_all + 1 - grp) / 2 : n_all;
-    constexpr int KSTEP = SHARE == 3 ? 2 * KTv : KTv;      // distance between consecutive K tiles of a group
-    const int kfirst = SHARE == 3 ? kb + grp * KTv : kb;
+    const int n = ke > kb ? cdiv(ke - kb, KTv) : 0;  // K tiles of this block
     f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
     // X3_DEPTH K tiles of a group's fp32 operand are in flight (register slot = tile index % X3_DEPTH).  With one, a CU keeps
     // about 30 KB in flight and takes in 26 GB/s -- the latency-bound part of the intake curve (tools/micro/intake_bench.hip,
@@ -848,8 +793,7 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
     unsigned ro[E::NQ] = {};           // IDX: element offsets of the indexed operand's memory rows (see quad_load_idx)
     MapRegs<3> mr = {};
     PlaneRegs ps;
-    constexpr bool APL = SPL && SHARE == 1, BPL = SPL && (SHARE == 2 || SHARE == 3);
-    static_assert(IDX == 0 || SHARE != 3, "row indirection: not with the K-alternating form");
+    constexpr bool APL = SHARE == 1, BPL = SHARE == 2;
     const PlaneDev dp = make_plane_dev(SHARE == 1 ? g.a : g.b, arm);
     const bool do_a = SHARE != 1 || grp == 0, do_b = SHARE != 2 || grp == 0;   // which operands this group stages
     // one piece of each operand in turn; a piece's registers request the next tile as soon as they have been written out
@@ -860,8 +804,8 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
         constexpr int SLOT = decltype(slot_tag)::value;
         TileRegsT<true, E::NQ>& ta = ta_[SLOT];
         TileRegsT<true, E::NQ>& tb = tb_[SLOT];
-        if constexpr (LOAD && IDX == 1) idx_next<AMINOR, 3, KSTEP>(ro, mr, oa, kld);
-        if constexpr (LOAD && IDX == 2) idx_next<BMINOR, 3, KSTEP>(ro, mr, ob, kld);
+        if constexpr (LOAD && IDX == 1) idx_next<AMINOR, 3>(ro, mr, oa, kld);
+        if constexpr (LOAD && IDX == 2) idx_next<BMINOR, 3>(ro, mr, ob, kld);
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             if constexpr (APL) {
@@ -906,8 +850,8 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
             }
         } else if (do_a) {
             if constexpr (IDX == 1) {
-                if constexpr (SLOT == 0) idx_begin<AMINOR, 3, KSTEP>(ro, mr, oa, m0, k);
-                else idx_next<AMINOR, 3, KSTEP>(ro, mr, oa, k);
+                if constexpr (SLOT == 0) idx_begin<AMINOR, 3>(ro, mr, oa, m0, k);
+                else idx_next<AMINOR, 3>(ro, mr, oa, k);
 #pragma unroll
                 for (int q = 0; q < E::NQ; ++q) quad_load_idx<AMINOR, 3>(ta, oa, m0, k, ke, q, ro);
             } else tile_load<AMINOR, true, 3>(ta, oa, m0, k, ke);
@@ -919,32 +863,32 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
             }
         } else if (do_b) {
             if constexpr (IDX == 2) {
-                if constexpr (SLOT == 0) idx_begin<BMINOR, 3, KSTEP>(ro, mr, ob, n0, k);
-                else idx_next<BMINOR, 3, KSTEP>(ro, mr, ob, k);
+                if constexpr (SLOT == 0) idx_begin<BMINOR, 3>(ro, mr, ob, n0, k);
+                else idx_next<BMINOR, 3>(ro, mr, ob, k);
 #pragma unroll
                 for (int q = 0; q < E::NQ; ++q) quad_load_idx<BMINOR, 3>(tb, ob, n0, k, ke, q, ro);
             } else tile_load<BMINOR, true, 3>(tb, ob, n0, k, ke);
         }
     };
-    if (active && n_mine > 0) {
-        first(std::integral_constant<int, 0>{}, kfirst);
+    if (active && n > 0) {
+        first(std::integral_constant<int, 0>{}, kb);
         if constexpr (DEPTH > 1) {
-            if (n_mine > 1) first(std::integral_constant<int, DEPTH - 1>{}, kfirst + KSTEP);
+            if (n > 1) first(std::integral_constant<int, DEPTH - 1>{}, kb + KTv);
         }
     }
     // phase p: group g is at step q = p - g of its own sequence stage(0), mfma(0), stage(1), mfma(1), ...
     for (int p = 0; p <= 2 * n; ++p) {
         const int q = p - grp;
-        if (active && q >= 0 && q < 2 * n_mine) {
-            const int t = q >> 1, k0 = kfirst + t * KSTEP;
+        if (active && q >= 0 && q < 2 * n) {
+            const int t = q >> 1, k0 = kb + t * KTv;
             unsigned* const Ad = As[SHARE == 1 ? (t & 1) : grp];
             unsigned* const Bd = Bs[SHARE == 2 ? (t & 1) : grp];
             if (q & 1) {
                 mfma_ktile<AMINOR, BMINOR, 3>(acc, Ad, Bd, wm, wn, lane);
             } else {
                 // tile t + DEPTH / t + 1 exist: their requests go out with tile t's store
-                const bool more = t + DEPTH < n_mine, morep = t + 1 < n_mine;
-                const int kld = k0 + DEPTH * KSTEP, kpl = k0 + KSTEP;
+                const bool more = t + DEPTH < n, morep = t + 1 < n;
+                const int kld = k0 + DEPTH * KTv, kpl = k0 + KTv;
                 auto go = [&](auto slot_tag) __attribute__((always_inline)) {
                     if (more) stage(Ad, Bd, k0, kld, kpl, VecTag{}, VecTag{}, slot_tag);
                     else if (morep) stage(Ad, Bd, k0, k0, kpl, ScalarTag{}, VecTag{}, slot_tag);
@@ -956,31 +900,7 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
         }
         __syncthreads();
     }
-    if constexpr (SHARE == 3) {
-        // group 1's partial sums join group 0's through LDS (the operand images are dead: every wave is past the loop's last
-        // barrier), one row-tile pair of accumulators at a time: 2 x 16 floats per lane = 32 KB
-        float* red = reinterpret_cast<float*>(&As[0][0]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (grp == 1) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) red[(j * 16 + r) * 256 + tid] = acc[i][j][r];
-            }
-            __syncthreads();
-            if (grp == 0) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] += red[(j * 16 + r) * 256 + tid];
-            }
-            __syncthreads();
-        }
-        if (active && grp == 0) gemm_epilogue<EPI>(g, acc, m0, n0, wm, wn, lane, arm);
-        return;
-    }
-    if (active) gemm_epilogue<EPI>(g, acc, m0, n0, wm, wn, lane, arm);
+    if (active) gemm_epilogue(g, acc, m0, n0, wm, wn, lane, arm);
 }
 
 // fc11 forward + bias + reconstruction loss + dZ11.  The product is computed TRANSPOSED, z^T = W11 d10^T: MFMA rows are
@@ -1766,9 +1686,10 @@ __global__ __launch_bounds__(512, 1) void k_x3_small(const TnDescs descs, int nd
 static Operand kmajor(const float* p, int64_t ld, int rows, int K) { return Operand{p, ld, rows, K, 0, nullptr, 0, -1, nullptr, 0, 0, 0, nullptr, 0, 0, 0}; }
 static Operand kminor(const float* p, int64_t ld, int rows, int K) { return Operand{p, ld, rows, K, 1, nullptr, 0, -1, nullptr, 0, 0, 0, nullptr, 0, 0, 0}; }
 
-// Slice planes of the four small operands (fp32x3 engine).  They are written by launch_x3_planes at fixed points of the
-// step -- W1 and [W11 | b11] at the start of the forward pass, [d10 | 1] behind the decoder chain, dZ1 behind the encoder's
-// backward chain -- and read by the GEMM launchers below, which only fill in the operand's plane fields.
+// Slice planes of the four small operands (fp32x3 engine).  They are written at fixed points of the step -- W1 and
+// [W11 | b11] at the start of the forward pass (launch_x3_planes), [d10 | 1] by the decoder chain, dZ1 by k_bn_bwd_apply or
+// launch_x3_planes behind the encoder's backward chain -- and read by the GEMM launchers below, which only fill in the
+// operand's plane fields.
 static inline int rup_i(int a, int b) { return cdiv(a, b) * b; }
 enum { PL_W1 = 0, PL_W11 = 1, PL_D10 = 2, PL_DZ1 = 3 };
 struct PlaneGeom { int R, C, Rp, Cp, ones_col; int64_t ws_off; };
@@ -1804,15 +1725,15 @@ static int launch_presplit(hipStream_t s, int A, const SplitJob* jobs, int n, co
     return 0;
 }
 
-// fp32x3: write the slice planes of the small operands (bit 0: W1 and [W11 | b11], from the parameters; bit 1: [d10 | 1];
-// bit 2: dZ1) -- one small launch each time, ahead of the GEMMs that copy them into LDS.  No-op for the other engines.
+// fp32x3: write the slice planes of the small operands (bit 0: W1 and [W11 | b11], from the parameters; bit 2: dZ1) -- one
+// small launch each time, ahead of the GEMMs that copy them into LDS.  No-op for the other engines.
 int launch_x3_planes(const Ctx& c, const float* params, int which, const mmvae_noise* nz) {
     const bool x3 = split3_gemms(c);
     if (!x3 && !chain_x3_ok(c)) return 0;
     // bit 4 (the head of a training step's forward pass, dropout on): this launch also makes the keep-mask and zeroes the
     // loss partial slots and the forward accumulator sets -- k_make_xbits' work (launch_forward_zero) without its launch
     XbitsJob xb{};
-    const bool head = (which & 16) && c.h.training && c.h.x_drop > 0.f && !c.tune(MMVAE_TUNE_PRESPLIT_ALL);
+    const bool head = (which & 16) && c.h.training && c.h.x_drop > 0.f;
     if (head) {
         const mmvae_dims& dd = c.d;
         xb.nz = make_noise_dev(nz, c.h);
@@ -1859,7 +1780,6 @@ int launch_x3_planes(const Ctx& c, const float* params, int which, const mmvae_n
             c.small_planes = true;
         }
     }
-    if ((which & 2) && !dec_chain_writes_planes(c)) jobs[n++] = plane_job(c, PL_D10, c.ws + c.lay.Dk[4], d.H, (int64_t)d.B * d.H);
     if ((which & 4) && !bn_apply_writes_planes(c)) jobs[n++] = plane_job(c, PL_DZ1, c.ws + c.lay.DZ[1], d.H, (int64_t)d.B * d.H);
     return (n || head) ? launch_presplit(c.stream, d.A, jobs, n, head ? &xb : nullptr) : 0;
 }
@@ -1880,21 +1800,21 @@ int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64
         g.a.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); g.a.nrec = c.x_nrows * c.x_ld; g.a.map_n = d.B;
         if (split3_gemms(c)) {
             use_planes(c, g.b, PL_W1);
-            hipLaunchKernelGGL((k_x3_gemm<false, false, 0, 2, true, 1>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+            hipLaunchKernelGGL((k_x3_gemm<false, false, 2, 1>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
         } else if (c.x16) {         // bf16 storage: x from its bf16 copy
             g.a.ptr = reinterpret_cast<const float*>(c.x16); g.a.src16 = 1;
             if (bf16_narrow_planes(c)) {   // ... and W1 from slice 0 of its planes (launch_x3_planes): [128][rup(D, 32)] bf16, zero rows beyond H
                 const PlaneGeom pg = plane_geom(c, PL_W1);
                 g.b.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.b.ld = pg.Cp; g.b.src16 = 1;
                 g.b_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;       // arm stride in FLOATS of the pointer arithmetic (planes: 2-byte elements)
-                hipLaunchKernelGGL((k_bf16_gemm<false, false, 0, 1, 3>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+                hipLaunchKernelGGL((k_bf16_gemm<false, false, 1, 3>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
             } else
-                hipLaunchKernelGGL((k_bf16_gemm<false, false, 0, 1, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+                hipLaunchKernelGGL((k_bf16_gemm<false, false, 1, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         } else
-            hipLaunchKernelGGL((k_bf16_gemm<false, false, 0, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+            hipLaunchKernelGGL((k_bf16_gemm<false, false, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
     } else if (split3_gemms(c)) {   // (fc_dim <= 124: one tile wide, the two tiles of a block share the W1 tile)
         use_planes(c, g.b, PL_W1);
-        hipLaunchKernelGGL((k_x3_gemm<false, false, 0, 2, true>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+        hipLaunchKernelGGL((k_x3_gemm<false, false, 2>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
     } else
         hipLaunchKernelGGL((k_bf16_gemm<false, false>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
     HIP_LAUNCH_CHECK("k_bf16_gemm<fc1>");
@@ -1906,8 +1826,8 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
     const Layout& L = c.lay;
     const int NS = L.sp.ks_gd10;
     // forward for gradients without x_rec (the train step, mmvae_forward(need_grad) for backward): one fused kernel, and
-    // the call for d(d10) (which & 2) has nothing left to do; with x_rec wanted (or MMVAE_TUNE_FC11_ZG_OFF) two kernels
-    const bool fused = need_grad && !x_rec && !c.tune(MMVAE_TUNE_FC11_ZG_OFF);
+    // the call for d(d10) (which & 2) has nothing left to do; with x_rec wanted two kernels
+    const bool fused = need_grad && !x_rec;
     if (split3_gemms(c)) {
         // fp32x3: only the fused train-step kernel exists in this engine (fc_dim + 1 <= 112, 128 cells per block fit the
         // loss-partial slots); everything else runs the fp32 matrix-instruction kernels (the caller falls through)
@@ -1982,11 +1902,7 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
         g.b_arm = c.po.per_arm;
         g.M = d.B; g.N = d.H; g.K = d.D; g.KS = NS; g.A = d.A;
         g.so = SlabOut{c.ws + L.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
-        if (split3_gemms(c)) {
-            use_planes(c, g.b, PL_W11);      // (its bias column is row fc_dim of the transposed operand: beyond N, never stored)
-            hipLaunchKernelGGL((k_x3_gemm<false, true, 0, 2, true>), dim3(cdiv(cdiv(d.B, BT), 2), NS, d.A), dim3(512), 0, c.stream, g);
-        } else
-            hipLaunchKernelGGL((k_bf16_gemm<false, true>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), NS, d.A), dim3(256), 0, c.stream, g);
+        hipLaunchKernelGGL((k_bf16_gemm<false, true>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), NS, d.A), dim3(256), 0, c.stream, g);
         HIP_LAUNCH_CHECK("k_bf16_gemm<gd10>");
     }
     return 0;
@@ -2010,21 +1926,21 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
             g.b.rowmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap); g.b.nrec = c.x_nrows * c.x_ld; g.b.map_n = d.B;
             if (split3_gemms(c)) {
                 use_planes(c, g.a, PL_DZ1);
-                hipLaunchKernelGGL((k_x3_gemm<true, true, 0, 1, true, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+                hipLaunchKernelGGL((k_x3_gemm<true, true, 1, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
             } else if (c.x16) {
                 g.b.ptr = reinterpret_cast<const float*>(c.x16); g.b.src16 = 1;
                 if (bf16_narrow_planes(c) && bn_apply_writes_planes(c)) {   // dZ1 from slice 0 of its planes (k_bn_bwd_apply): [rup(B, 256)][128] bf16
                     const PlaneGeom pg = plane_geom(c, PL_DZ1);
                     g.a.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.a.ld = pg.Cp; g.a.src16 = 1;
                     g.a_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;
-                    hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 2, 3>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+                    hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 3>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
                 } else
-                    hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 2, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+                    hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
             } else
-                hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+                hipLaunchKernelGGL((k_bf16_gemm<true, true, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         } else if (split3_gemms(c)) {   // one tile high: the two tiles of a block share the dZ1 tile
             use_planes(c, g.a, PL_DZ1);
-            hipLaunchKernelGGL((k_x3_gemm<true, true, 0, 1, true>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+            hipLaunchKernelGGL((k_x3_gemm<true, true, 1>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
         } else
             hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         HIP_LAUNCH_CHECK("k_bf16_gemm<dW1>");
@@ -2040,11 +1956,11 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
         g.so = SlabOut{c.ws + L.dw11_slab, (int64_t)d.A * d.D * DW11_LD, (int64_t)d.D * DW11_LD, DW11_LD, d.D, d.H + 1};
         if (split3_gemms(c)) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
             use_planes(c, g.b, PL_D10);
-            hipLaunchKernelGGL((k_x3_gemm<true, true, 0, 2, true>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+            hipLaunchKernelGGL((k_x3_gemm<true, true, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
         } else if (c.dz16) {        // bf16 storage: the fused fc11 kernel of this step wrote dZ11 as bf16
             g.a.src16 = 1;
             g.a_arm = (int64_t)d.B * d.D / 2;
-            hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 0, 1>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+            hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 1>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         } else
             hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         HIP_LAUNCH_CHECK("k_bf16_gemm<dW11>");
@@ -2056,114 +1972,6 @@ int launch_dw_small_x3(const Ctx& c, const TnDescs& ts, int nsel) {
     const int KS = c.lay.sp.ks_small;
     hipLaunchKernelGGL(k_x3_small, dim3(cdiv(nsel * c.d.A, 2), KS), dim3(512), 0, c.stream, ts, nsel, c.d.A, c.d.B, KS);
     HIP_LAUNCH_CHECK("k_x3_small");
-    return 0;
-}
-
-// C[M][ld] = act((A[M][K] . W[N][K]^T) * scale + shift): the augmenter's layers with bf16 operands (augment.hip)
-int launch_presplit_one(hipStream_t s, const float* src, int64_t ld, int R, int C, int Rp, int Cp, unsigned short* dst) {
-    const SplitJob j{src, ld, 0, R, C, Rp, Cp, -1, dst, 0, nullptr, 0};
-    return launch_presplit(s, 1, &j, 1);
-}
-
-// sum of the split-K slabs of an augmenter layer + its folded BatchNorm / ReLU epilogue: out[m][n] = act(sum_ks slab[ks][m][n] *
-// scale[n] + shift[n]) for n < N, zero for the padding columns N .. ncols - 1.  One float4 per thread (ld, ncols multiples of 4).
-__global__ __launch_bounds__(256) void k_aug_slab_epi(const float* __restrict__ slab, int64_t ks_stride, int KS, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, float* __restrict__ out, int ld, int M, int N,
-                                                      int ncols, int relu, int affine) {
-    const int c4n = ncols >> 2;
-    const int64_t n = (int64_t)M * c4n;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int m = (int)(i / c4n), c = (int)(i - (int64_t)m * c4n) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = 0; k < KS; ++k) {   // (KS <= 4: the loads of all slabs are independent and issue together)
-            const float4 t = *reinterpret_cast<const float4*>(slab + k * ks_stride + (int64_t)m * ld + c);
-            v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-        }
-        float r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int col = c + e;
-            const bool real = col < N;
-            float y = r[e] * ((affine && real) ? scale[col] : 1.f) + ((affine && real) ? shift[col] : 0.f);
-            if (relu) y = fmaxf(y, 0.f);
-            r[e] = real ? y : 0.f;
-        }
-        *reinterpret_cast<float4*>(out + (int64_t)m * ld + c) = make_float4(r[0], r[1], r[2], r[3]);
-    }
-}
-
-int launch_bf16_affine(hipStream_t s, bool relu, bool affine, const float* A, int lda, int M, const float* W, int ldw, int N,
-                       int Kpad, const float* sc, const float* sh, float* C, int ldc, int ncols, int split3,
-                       const unsigned short* w_planes, int Np, int Kp, float* scratch, int64_t scratch_floats) {
-    GemmArgs g{};
-    g.a = kmajor(A, lda, M, Kpad);        // rows are zero-padded to Kpad = pad4(K) floats on both sides
-    g.b = kmajor(W, ldw, N, Kpad);
-    g.M = M; g.N = ncols; g.K = Kpad; g.KS = 1; g.A = 1;
-    g.ao = AffineOut{sc, sh, C, ldc, M, N, relu ? 1 : 0, affine ? 1 : 0};
-    if (split3 && w_planes && Np >= cdiv(ncols, BT) * BT) {
-        // fp32x3 with the weight's slice planes (written at pack time): the two tiles of a block are m neighbours of one
-        // n tile and share its weight tile, copied from the planes; the activations are split on their way into LDS
-        g.b.pl = w_planes; g.b.pl_plane = (int64_t)Np * Kp; g.b.pl_arm = 0; g.b.pl_ld = Kp;
-        const int tiles = cdiv(M, BT) * cdiv(ncols, BT);
-        // A layer with fewer tile pairs than CUs and a long K (the first layer at the benchmark shape: 5000 x 1000 x 5000 = 160
-        // blocks on 256 CUs, 362 of the forward's 1 580 us): split K over KS blocks per pair -- the count in 2 .. 4 that needs
-        // the fewest rounds of the chip per unit of K -- into slabs in the caller's scratch, and a small pass sums them and
-        // applies the epilogue.
-        {
-            constexpr int N_CUS = 256;   // MI355X
-            const int pairs = cdiv(cdiv(M, BT), 2) * cdiv(ncols, BT);
-            int ks_best = 1;
-            double cost_best = (double)cdiv(pairs, N_CUS);
-            for (int ks = 2; ks <= 4; ++ks) {
-                const double cost = (double)cdiv(pairs * ks, N_CUS) / ks;
-                if (cost < 0.8 * cost_best && Kpad / ks >= 32 * Eng<3>::KT && (int64_t)ks * M * ldc <= scratch_floats) { ks_best = ks; cost_best = cost; }
-            }
-            if (scratch && ks_best > 1 && tiles > 192 && (ldc & 3) == 0 && (ncols & 3) == 0) {
-                g.KS = ks_best;
-                g.so = SlabOut{scratch, (int64_t)M * ldc, 0, ldc, M, N < ncols ? N : ncols};
-                hipLaunchKernelGGL((k_x3_gemm<false, false, 0, 2, true>), dim3(pairs, ks_best, 1), dim3(512), 0, s, g);
-                HIP_LAUNCH_CHECK("k_x3_gemm<affine, split K>");
-                const int64_t items = (int64_t)M * (ncols >> 2);
-                hipLaunchKernelGGL(k_aug_slab_epi, dim3((unsigned)imin64(4096, cdiv64(items, 256))), dim3(256), 0, s, scratch, (int64_t)M * ldc,
-                                   ks_best, sc, sh, C, ldc, M, N, ncols, relu ? 1 : 0, affine ? 1 : 0);
-                HIP_LAUNCH_CHECK("k_aug_slab_epi");
-                return 0;
-            }
-        }
-        // fewer tile pairs than half the CUs: one tile per block, the groups split K (trunk layers 1000 -> 500, 500 -> 500,
-        // 500 -> 100 at M = 5000: 77 -> 51, 45 -> 32, 44 -> 31 us; at 320 tiles the lost sharing of the weight tile costs more:
-        // 360 -> 385, 82 -> 92, 50 -> 62 us)
-        if (tiles <= 192 && Kpad >= 4 * Eng<3>::KT)
-            hipLaunchKernelGGL((k_x3_gemm<false, false, 1, 3, true>), dim3(tiles, 1, 1), dim3(512), 0, s, g);
-        else
-            hipLaunchKernelGGL((k_x3_gemm<false, false, 1, 2, true>), dim3(cdiv(cdiv(M, BT), 2) * cdiv(ncols, BT), 1, 1), dim3(512), 0, s, g);
-    } else if (split3)
-        hipLaunchKernelGGL((k_x3_gemm<false, false, 1, 0>), dim3(cdiv(cdiv(M, BT) * cdiv(ncols, BT), 2), 1, 1), dim3(512), 0, s, g);
-    else {
-        // bf16 operands: one tile per 256-thread block, two blocks per CU; the same split of a long K for layers that leave
-        // slots of the chip empty (the first layer: 320 tiles on 512 slots)
-        const int tiles = cdiv(M, BT) * cdiv(ncols, BT);
-        constexpr int SLOTS = 512;
-        int ks_best = 1;
-        double cost_best = (double)cdiv(tiles, SLOTS);
-        for (int ks = 2; ks <= 4; ++ks) {
-            const double cost = (double)cdiv(tiles * ks, SLOTS) / ks;
-            if (cost < 0.8 * cost_best && Kpad / ks >= 16 * KT && (int64_t)ks * M * ldc <= scratch_floats) { ks_best = ks; cost_best = cost; }
-        }
-        if (scratch && ks_best > 1 && (ldc & 3) == 0 && (ncols & 3) == 0) {
-            g.KS = ks_best;
-            g.so = SlabOut{scratch, (int64_t)M * ldc, 0, ldc, M, N < ncols ? N : ncols};
-            hipLaunchKernelGGL((k_bf16_gemm<false, false>), dim3(tiles, ks_best, 1), dim3(256), 0, s, g);
-            HIP_LAUNCH_CHECK("k_bf16_gemm<affine, split K>");
-            const int64_t items = (int64_t)M * (ncols >> 2);
-            hipLaunchKernelGGL(k_aug_slab_epi, dim3((unsigned)imin64(4096, cdiv64(items, 256))), dim3(256), 0, s, scratch, (int64_t)M * ldc,
-                               ks_best, sc, sh, C, ldc, M, N, ncols, relu ? 1 : 0, affine ? 1 : 0);
-            HIP_LAUNCH_CHECK("k_aug_slab_epi");
-            return 0;
-        }
-        hipLaunchKernelGGL((k_bf16_gemm<false, false, 1>), dim3(tiles, 1, 1), dim3(256), 0, s, g);
-    }
-    HIP_LAUNCH_CHECK("k_bf16_gemm<affine>");
     return 0;
 }
 

@@ -576,15 +576,6 @@ template __global__ void k_gemm_tn<128, 128>(const TnDescs, int, NoiseDev, int, 
 // ---------------------------------------------------------------------------------------------
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 int launch_fc1_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
     const int use_mask = (c.h.training && c.h.x_drop > 0.f) ? 1 : 0;

@@ -24,15 +24,6 @@
 
 namespace mmvae {
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 typedef __bf16 bf16x8q __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4q __attribute__((ext_vector_type(4)));
 

@@ -20,15 +20,6 @@
 
 namespace mmvae {
 
-#define HIP_LAUNCH_CHECK(what)                                                        \
-    do {                                                                              \
-        hipError_t e_ = hipGetLastError();                                            \
-        if (e_ != hipSuccess) {                                                       \
-            set_error("%s: %s", what, hipGetErrorString(e_));                         \
-            return MMVAE_E_LAUNCH;                                                    \
-        }                                                                             \
-    } while (0)
-
 
 NoiseDev make_noise_dev(const mmvae_noise* nz, const mmvae_hyper& h) {
     NoiseDev n{};

@@ -197,7 +197,7 @@ class mixVAE_model(nn.Module):
     def _ensure(self, B: int) -> N.Engine:
         if not self._is_packed():
             self._pack()
-        mode = N.gemm_mode(self.gemm_dtype) & 0xFF
+        mode = N.gemm_mode(self.gemm_dtype)
         if (self._engine is None or self._engine.dims.B != B or self._engine.device != self._flat.device
                 or self._engine.gemm_engine != mode):
             # a trainer alternates between a few batch sizes (training batch, evaluation chunks, their ragged tails):

@@ -67,7 +67,7 @@ typedef struct mmvae_hyper {
     int32_t hard;      /* straight-through one-hot sample, :486-493         */
     int32_t training;  /* module.training: batch-stat BN + dropout active   */
     int32_t eval_flag; /* forward(eval=True): no Gumbel noise, hard sample, :340-343 */
-    int32_t gemm_bf16; /* engine of the five D x H GEMMs (fc1, fc11, d(d10), dW1, dW11); low byte:
+    int32_t gemm_bf16; /* engine of the five D x H GEMMs (fc1, fc11, d(d10), dW1, dW11):
                           0  fp32 operands on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32: an exact fp32 FMA chain);
                           1  bf16 operands (rounded to nearest even on load), fp32 accumulation on the bf16 matrix pipe --
                              BASELINE.json's bf16 configuration;
@@ -77,8 +77,7 @@ typedef struct mmvae_hyper {
                              fp32-grade results at 6/64 of the matrix-pipe time of engine 0 (the Python binding's "fp32").
                           Every other computation and all parameters stay fp32 under all three.  Engines 1 and 2 need the
                           fast path (D % 4 == 0, fc_dim % 4 == 0, fc_dim <= 124; engine 2's fused fc11 kernel fc_dim <= 111),
-                          else engine 0 runs.  Bits 8..11 (diagnostics, engine 2 only): products that stay on engine 0
-                          (1 fc1, 2 fc11 + d(d10), 4 dW1, 8 dW11). */
+                          else engine 0 runs.  Any other value: MMVAE_E_BADARG. */
     uint32_t cat_mask[4]; /* category subset of forward(mask=...) (nn_model.py:332-335, the pruning-time forward; eval_model passes
                           the categories whose fcc bias is non-zero, cpl_mixvae.py:1476-1478): bit k of the 128-bit mask set =
                           category k is kept; c = softmax(c_prob[:, kept] / tau) on the kept categories and 0 elsewhere.
@@ -127,7 +126,7 @@ typedef struct mmvae_noise {
 #define MMVAE_N_EVENTS 8
 #define MMVAE_N_TUNE 24
 /* mmvae_exec.tune: 0 everywhere = production behaviour.  One entry is part of the interface: */
-#define MMVAE_TUNE_ENGINE 17    /* the GEMM engine the caller is going to run (mmvae_hyper.gemm_bf16 & 0xFF; 0 = not stated).
+#define MMVAE_TUNE_ENGINE 17    /* the GEMM engine the caller is going to run (mmvae_hyper.gemm_bf16; 0 = not stated).
                                    The split factors of the workspace layout are chosen for the workgroup shapes of that
                                    engine; any engine runs correctly on any layout */
 /* Every other index is an experiment switch of the implementation (A/B timing, test hooks), listed in the
@@ -264,7 +263,7 @@ int mmvae_train_step(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_nois
  * the per-step row gather of mmvae_gather_rows: fc1, the fused fc11 kernel and dW1 read x through a row map (B 32-bit
  * offsets the step's head launch derives from `rows`), so a shuffled batch costs what a resident one does.  Bit-identical to
  * mmvae_gather_rows + mmvae_train_step.  Offered where it is built -- the fused training step of the fp32x3 and bf16 engines
- * (gemm_bf16 & 0xFF == 2 with fc_dim <= 111, or == 1; x_drop > 0), ld % 4 == 0, 16-byte aligned data, n_rows * ld < 2^30 floats --; otherwise
+ * (gemm_bf16 == 2 with fc_dim <= 111, or == 1; x_drop > 0), ld % 4 == 0, 16-byte aligned data, n_rows * ld < 2^30 floats --; otherwise
  * MMVAE_E_UNSUPPORTED: gather the batch and call mmvae_train_step.
  *
  * data_bf16 (optional, NULL = none; the bf16 engine only, BASELINE.json configs[2]): a bf16 copy of `data` with the same

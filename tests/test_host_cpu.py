@@ -31,12 +31,12 @@ def test_library_exports_every_declared_symbol():
     assert b"getenv" not in blob and b"MMVAE_" not in blob
 
 
-def test_tune_env_matches_tune_header():
+def test_tune_env_names_exactly_the_live_switches():
     # every environment switch sets an index that csrc/tune.h names, and every index there has its switch
     # (MMVAE_TUNE_ENGINE is set by the binding itself, from the engine it runs)
     src = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "distributed-vae_amd", "csrc", "tune.h")).read())
     enum = {name: int(v) for name, v in re.findall(r"\b(MMVAE_TUNE_\w+)\s*=\s*(\d+)", src)}
-    assert len(enum) >= 8
+    assert enum == {"MMVAE_TUNE_AUG_TILE": 3, "MMVAE_TUNE_COUPLE_SIDE": 13, "MMVAE_TUNE_BN_PARTIALS": 19, "MMVAE_TUNE_CHAIN_FP32": 21}
     env_idx = {idx for idx, _ in N.TUNE_ENV.values()}
     assert len(env_idx) == len(N.TUNE_ENV)
     assert env_idx <= set(enum.values()), sorted(env_idx - set(enum.values()))
@@ -220,21 +220,34 @@ def test_bench_refuses_more_gpus_than_visible():
     assert r.returncode != 0 and "refusing" in r.stderr and r.stdout.strip() == ""
 
 
-def test_gemm_engine_names_map_to_the_abi_values(monkeypatch):
+def test_gemm_engines_are_the_three_abi_values(monkeypatch):
     """mmvae_hyper.gemm_bf16: 0 fp32 matrix instruction, 1 bf16 operands, 2 fp32x3 (include/mmvae.h); "fp32" is the
-    library's fp32 engine (fp32x3 unless MMVAE_FP32_ENGINE says otherwise); the diagnostic mask rides in bits 8.."""
+    library's fp32 engine (fp32x3 unless MMVAE_FP32_ENGINE says otherwise).  Any other value is refused on the host."""
     from distributed_vae_amd import _native as N
     assert N.gemm_mode("fp32_mfma") == 0 and N.gemm_mode("bf16") == 1 and N.gemm_mode("fp32x3") == 2
     monkeypatch.setattr(N, "FP32_ENGINE", "fp32x3")
     assert N.gemm_mode("fp32") == 2
     monkeypatch.setattr(N, "FP32_ENGINE", "fp32_mfma")
     assert N.gemm_mode("fp32") == 0
-    monkeypatch.setenv("MMVAE_X3_OFF", "5")
-    assert N.gemm_mode("fp32x3") == 2 | (5 << 8) and N.gemm_mode("bf16") == 1
     with pytest.raises(ValueError):
         N.gemm_mode("fp16")
     ex = N.exec_from_env(2)
     assert ex.tune[N.TUNE_ENGINE] == 2
+    # the engine value is checked before the workspace: an empty one gives MMVAE_E_WORKSPACE (-4) for the three engines and
+    # MMVAE_E_BADARG (-1) for anything else, and neither reaches the GPU
+    L = N.lib()
+    d = N.Dims(2, 32, 64, 16, 4, 6, 2)
+    ad = N.AugDims(2, 100, 5000, 1000, 500, 100, 10, 50)
+    buf = (C.c_float * 64)()
+    for eng, want in ((0, -4), (1, -4), (2, -4), (3, -1), (2 | (5 << 8), -1), (-1, -1)):
+        h = N.Hyper(0.005, 1.0, 1.0, 1.0, 1e-8, 0.01, 0.5, 0.0, 0, 1, 0, eng)
+        assert L.mmvae_forward(C.byref(d), C.byref(h), None, buf, buf, buf, buf, 0, None, 1, buf, 0, None, None) == want, eng
+        assert L.mmvae_train_step(C.byref(d), C.byref(h), None, buf, buf, buf, buf, 0, buf, 0, buf, buf, 0, None, None, 1,
+                                  1e-3, 0.9, 0.999, 1e-8, 0.0, 0, None, None) == want, eng
+        assert L.mmvae_augment(C.byref(ad), buf, buf, 0, buf, buf, 0.1, buf, 0, buf, buf, eng, None, None) == want, eng
+        if want == -1:
+            assert b"gemm_bf16" in L.mmvae_last_error_string()
+            assert L.mmvae_augment_rows(C.byref(ad), buf, buf, 100, 1, buf, buf, buf, 0.1, buf, 0, buf, buf, eng, None, None) == -1
 
 
 def test_split_factors_follow_the_engine_hint():
