@@ -40,7 +40,7 @@ Splits default_splits(const mmvae_dims& d, const mmvae_exec* ex) {
     };
     Splits s;
     const int nb128 = cdiv(d.B, 128), nb64 = cdiv(d.B, 64);
-    const bool fastdims = (d.D & 3) == 0 && (d.H & 3) == 0;
+    const bool fastdims = fast_dims(d);
     // fc1 forward: fast kernel 128-row blocks, 3 workgroups / CU; general kernel 64-row blocks
     // (fc_dim 100: k_fc1_fwd_v3, two workgroups / CU)
     s.ks_fc1 = g_split[0] > 0 ? g_split[0] : (fastdims ? fit(nb128 * d.A, (d.H == 100 ? 2 : 3) * CUS, 16) : fit(nb64 * d.A, 4 * CUS, 16));
@@ -79,7 +79,7 @@ Splits default_splits(const mmvae_dims& d, const mmvae_exec* ex) {
     // (fc1, dW1, dW11) or 128 cells (the fused fc11 kernel) -- so the splits fill 256 slots, not 512.  dW11 runs beside the
     // latency-bound backward chain, which needs CUs of its own (measured at A = 2: 873 us per step with the splits above,
     // 836 with these).
-    if (ex && ex->tune[MMVAE_TUNE_ENGINE] == 2 && fastdims && d.H + 1 <= 112) {
+    if (ex && ex->tune[MMVAE_TUNE_ENGINE] == 2 && fastdims && x3_fc11_fits(d)) {
         const int pairs_b = cdiv(nb128, 2), pairs_d = cdiv(cdiv(d.D, 128), 2);
         if (g_split[0] <= 0) s.ks_fc1 = min(fit(pairs_b * d.A, CUS, 16), max(1, cdiv(d.D, 32)));
         if (g_split[4] <= 0) s.ks_gd10 = min(fit(nb128 * d.A, CUS, 16), max(1, cdiv(d.D, 64)));
@@ -92,14 +92,14 @@ Splits default_splits(const mmvae_dims& d, const mmvae_exec* ex) {
         // 5: 722; A = 3: 2 splits 931, 3: 940; A = 5: 1 split 1527, 2: 1530)
         if (g_split[5] <= 0) {
             const int nwg = max(1, pairs_d * d.A);
-            const bool chain_x3 = d.C + d.S <= 128 && d.L <= 128 && !ex->tune[MMVAE_TUNE_CHAIN_FP32];
+            const bool chain_x3 = chain_planes_fit(d) && !ex->tune[MMVAE_TUNE_CHAIN_FP32];
             const int target = chain_x3 ? 140 : 3 * CUS / 8;
             s.ks_dw11 = min(max(1, (target + nwg / 2) / nwg), max(1, cdiv(d.B, 32)));
         }
         if (g_split[3] <= 0) s.ks_small = min(fit(cdiv(N_SMALL * d.A, 2), CUS, 32), max(1, cdiv(d.B, 32)));   // k_x3_small: a pair of products per block
     }
     // the bf16 configuration runs its small-layer gradient products on k_x3_small too
-    if (ex && ex->tune[MMVAE_TUNE_ENGINE] == 1 && fastdims && d.H <= 124) {
+    if (ex && ex->tune[MMVAE_TUNE_ENGINE] == 1 && fastdims && bf16_tiles_fit(d)) {
         if (g_split[3] <= 0) s.ks_small = min(fit(cdiv(N_SMALL * d.A, 2), CUS, 32), max(1, cdiv(d.B, 32)));
         // dW11 beside the backward chain: about 160 of its two-per-CU workgroups (A = 2: 5 splits 701 us per step, 3: 688, 2: 680)
         if (g_split[5] <= 0) {
@@ -276,10 +276,78 @@ static int check_noise(const Ctx& c, const mmvae_noise* nz) {
     return 0;
 }
 
-// Train step with a side stream (couple_done != null): the coupling kernel needs only the latent block's outputs
-// and the loss scalars only the coupling and fc11 partials, so both run on the side stream -- the coupling beside
-// the decoder chain and fc11, the finalisation (loss_out != null) beside the d(d10) GEMM.  *couple_done tells the
-// caller that the loss is on its way (event EV_COUPLE) and do_loss must not launch anything.
+static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The call's plan (common.hpp).  c.x_rows / c.x16 are set before; fc11_grad: fc11 runs for gradients without x_rec.
+static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x, int64_t xs, bool fc11_grad = true) {
+    const mmvae_dims& d = c.d;
+    const mmvae_hyper& h = c.h;
+    const Layout& L = c.lay;
+    Plan& p = c.plan;
+    p = Plan{};
+    p.kind = kind;
+    const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS, fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY;
+    const bool dropout = h.training && h.x_drop > 0.f, side = c.side() != nullptr;
+    p.fast = fast_dims(d) && al16(params) && al16(x) && (xs & 3) == 0 && d.H >= 4 && (int64_t)d.B * d.D < ((int64_t)1 << 30);
+    // engines of the five D x H products (mmvae_hyper.gemm_bf16: 1 bf16 operands, 2 fp32x3)
+    const bool bf16_tiles = (h.gemm_bf16 == 1 || h.gemm_bf16 == 2) && bf16_tiles_fit(d);
+    const bool x3 = h.gemm_bf16 == 2 && bf16_tiles_fit(d);
+    p.big = !p.fast ? GEMM_GENERAL : x3 ? GEMM_X3 : bf16_tiles ? GEMM_BF16 : GEMM_FP32;
+    p.small_x3 = bf16_tiles;   // (the bf16 configuration's small layers stay fp32-grade; on either path)
+    // fp32x3: the fused train-step form of fc11 has its own kernel, the other forms run the fp32 matrix-instruction kernels.
+    // At fc_dim 100 d(d10) is folded into the fc11 kernel (k_fc11_zg), whose gene split count equals the d(d10) kernel's so
+    // that the decoder backward sums the same number of slabs whichever forward ran
+    const bool slots = fc11_slots_fit(L, d.B);
+    if (!p.fast) p.fc11 = FC11_GENERAL;
+    else if (p.big == GEMM_X3 && fc11_grad && x3_fc11_fits(d) && slots) p.fc11 = FC11_X3;
+    else if (p.big == GEMM_BF16) p.fc11 = FC11_BF16;
+    else if (fc11_grad && d.H == 100 && (int64_t)cdiv(d.B, 256) * L.sp.ks_gd10 <= L.n11) p.fc11 = FC11_ZG;
+    else p.fc11 = FC11_ZT;
+    p.gd10_slabs = p.fast ? L.sp.ks_gd10 : L.sp.ns_fc11;
+    p.dw11_slabs = p.fast ? L.sp.ks_dw11 : L.sp.ks_dw;
+    // the chain kernels' own GEMMs on the fp32x3 engine (also in the bf16 configuration: only its five D x H products round
+    // their operands, everything else stays fp32-grade)
+    p.chain_planes = p.fast && bf16_tiles && chain_planes_fit(d) && !c.tune(MMVAE_TUNE_CHAIN_FP32);
+    p.lat_half = d.C <= 32 * LH_CPL && d.L <= 32 && 2 * d.S <= 32;
+    // bf16 configuration on bf16 storage (mmvae_train_step_rows(data_bf16)): the NARROW operands of fc1 / dW1 (W1, dZ1) are
+    // read as bf16 too -- slice 0 of the planes the fp32x3 engine uses -- instead of fp32 rounded by every block tile
+    p.narrow = h.gemm_bf16 == 1 && c.x16 != nullptr && bf16_tiles_fit(d) && (d.D & 7) == 0;
+    p.presplit = fwd && p.fast && (x3 || p.chain_planes);
+    p.bwd_small_planes = kind == CALL_BACKWARD && p.chain_planes;   // (the fused step's forward pass has left them in place)
+    p.d10_planes = x3;                                   // (these two also off the fast path, where no kernel reads them)
+    p.dz1_in_apply = (x3 || p.narrow) && (d.H & 1) == 0;
+    if (fwd && h.training) p.zero = p.presplit && dropout ? ZERO_PRESPLIT : p.fast && dropout ? ZERO_XBITS : ZERO_MEMSET;
+    // what the row-indexed kernels take: the head launch builds the row map, the fused fc11 kernel of the fp32x3 or bf16 engine
+    p.rowmap = kind == CALL_STEP_ROWS && p.zero == ZERO_PRESPLIT && slots && (p.fc11 == FC11_X3 || p.fc11 == FC11_BF16);
+    p.dz11_bf16 = p.rowmap && c.x16 != nullptr && p.fc11 == FC11_BF16;
+    // dW11 depends only on dZ11 and d10 (both final after forward): it runs on the side stream beside the backward chain, forked at
+    // the START of the backward pass -- the later it starts, the more of it lands on the MFMA-bound dW1 (measured again in round 4,
+    // profiles/r04_dw11_placement_sweep.txt: behind the decoder chain + 30 us per step, behind the latent backward + 15, not
+    // forked + 75; fewer or more workgroups than the default split + 5 .. 10).
+    p.dw11_side = (step || kind == CALL_BACKWARD) && p.fast && side;
+    // The fused step on the fast path: the coupling terms AND the T sums of the latent backward (which need nothing but the
+    // coupling kernel's output) run on the side stream beside the decoder chain and fc11; the loss scalars (which need
+    // fc11's partials) follow dW11 on the side stream -- no fork between fc11 and the backward pass.
+    p.loss_on_side = step && p.fast && side;
+    // The coupling terms as a role of the decoder chain's launch (k_chain_fwd_couple: fp32x3 form, accumulator sets, 2 .. 5
+    // arms; C <= 128 by check_dims).  Measured (A/B/A/B per arm count on one box, ms per step, role against side stream):
+    // A = 2 0.674 / 0.672, A = 3 0.901 / 0.896, A = 5 1.479 / 1.489 -- the two bubbles it removes from the main stream show
+    // in a rocprofv3 trace (5 - 6 us each) but not in the un-profiled step at two and three arms, where the combined launch
+    // is 3 us longer than the chain's own (its grid has a third row of workgroups); at five arms the chain's 395 workgroups
+    // already run in two rounds and the role fills the second.  So: the role from four arms up, the side stream below
+    // (MMVAE_TUNE_COUPLE_SIDE: 1 side stream always, 3 role always).
+    const int cs = c.tune(MMVAE_TUNE_COUPLE_SIDE);
+    const bool role = p.loss_on_side && c.use_acc() && p.chain_planes && d.A >= 2 && d.A <= 5 && cs != 1 && (d.A >= 4 || cs == 3);
+    p.couple = step && side ? (role ? COUPLE_IN_DEC : COUPLE_SIDE) : COUPLE_INLINE;
+    // fork events ride on the kernels in front of the forks (the latent forward, the fused fc11 kernel): a recorded event is
+    // a barrier packet of its own, 6 - 7 us of idle main stream (round 3: 686 -> 681 us per step)
+    p.lat_fork_rides = p.couple == COUPLE_SIDE && p.lat_half;
+    p.fc11_fork_rides = p.loss_on_side && (p.fc11 == FC11_X3 || p.fc11 == FC11_BF16);
+}
+
+// Train step with a side stream: the coupling kernel needs only the latent block's outputs and the loss scalars only the
+// coupling and fc11 partials, so both run on the side stream -- the coupling beside the decoder chain and fc11, the
+// finalisation beside the d(d10) GEMM or dW11 (Plan::couple, loss_on_side).
 static int fork_to_side(const Ctx& c, int ev) {
     if (hipEventRecord(c.ev(ev), c.stream) != hipSuccess || hipStreamWaitEvent(c.side(), c.ev(ev), 0) != hipSuccess) {
         set_error("stream fork failed");
@@ -301,21 +369,26 @@ static int join_from_side(const Ctx& c, int ev) {
     return 0;
 }
 
+// `launcher` with fork event `ev` riding on its kernel (launch_k) if the plan says so; it must have taken the event
+template <class F>
+static int launch_with_fork(const Ctx& c, bool rides, int ev, F launcher) {
+    if (rides) c.stop_ev = c.ev(ev);
+    int rc = launcher();
+    if (rides && !rc && !c.stop_used) { set_error("internal: the fork event did not ride on its kernel"); rc = MMVAE_E_LAUNCH; }
+    c.stop_ev = nullptr;
+    c.stop_used = false;
+    return rc;
+}
+
 static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
-                      const float* x, int64_t xs, float* x_rec, int need_grad, bool* couple_done = nullptr,
-                      float* loss_out = nullptr, bool latent_only = false, int32_t* labels = nullptr) {
+                      const float* x, int64_t xs, float* x_rec, int need_grad, float* loss_out = nullptr,
+                      int32_t* labels = nullptr) {
+    const Plan& p = c.plan;
     int rc;
-    const bool fast = fast_path_ok(c, params, x, xs);
-    // training: the loss partial slots and the forward accumulator sets start the pass at zero (inside k_make_xbits
-    // when that runs); eval mode has no batch sums and the fc11 launchers zero their slots themselves
-    const bool merged = fast && prologue_merged(c);   // keep-mask + zero fill inside the k_presplit launch below
-    if (c.h.training) {
-        if (!merged && (rc = launch_forward_zero(c, fast, nz))) return rc;
-    } else if (fast && (rc = launch_make_xbits(c, nz))) {
-        return rc;
-    }
-    if (fast) {
-        if ((rc = launch_x3_planes(c, params, merged ? 17 : 1, nz))) return rc;   // fp32x3: slice planes of W1, [W11 | b11], the small layers
+    if ((p.zero == ZERO_MEMSET || p.zero == ZERO_XBITS) && (rc = launch_forward_zero(c, nz))) return rc;
+    // fp32x3 / chain planes: slice planes of W1, [W11 | b11], the small layers (+ keep-mask, zero fill, row map: Plan::zero)
+    if (p.presplit && (rc = launch_x3_planes(c, params, true, nz))) return rc;
+    if (p.fast) {
         if ((rc = launch_fc1_fwd_fast(c, params, x, xs))) return rc;
         if ((rc = launch_fc1_epi(c, params))) return rc;
     } else if ((rc = launch_fc1_fwd(c, nz, params, x, xs))) {
@@ -330,53 +403,24 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
         for (int layer = 2; layer <= 5; ++layer)
             if ((rc = launch_chain_fwd_enc(c, layer, params, bn_running, nbt))) return rc;
     }
-    // fork events ride on the kernels in front of the forks (the latent forward here, the fused fc11 kernel below): a recorded
-    // event is a barrier packet of its own, 6 - 7 us of idle main stream (round 3: 686 -> 681 us per step)
-    const bool t_early = fast && couple_done && c.side() && loss_out && !latent_only && fc11_split_path(c, params, x, xs);
-    c.stop_used = false;
-    // the coupling terms as a role of the decoder chain's launch: no fork behind the latent forward at all
-    const bool couple_role = t_early && dec_couple_ok(c);
-    c.couple_in_dec = false;
-    if (couple_done && c.side() && !latent_only && !couple_role) c.stop_ev = c.ev(EV_LAT);
-    if ((rc = launch_lat_fwd(c, nz, params, bn_running, nbt, labels))) return rc;
-    c.stop_ev = nullptr;
-    const bool lat_rode = c.stop_used;
-    c.stop_used = false;
-    if (latent_only) return 0;   // evaluation labels need c only: no decoder, no fc11
+    if ((rc = launch_with_fork(c, p.lat_fork_rides, EV_LAT, [&] { return launch_lat_fwd(c, nz, params, bn_running, nbt, labels); })))
+        return rc;
+    if (p.kind == CALL_CLASSIFY) return 0;   // evaluation labels need c only: no decoder, no fc11
     Ctx cs = c;
     cs.stream = c.side();
-    // The fused step on the fast path (t_early): the coupling terms AND the T sums of the latent backward (which need nothing but
-    // the coupling kernel's output) run on the side stream from here, beside the decoder chain and fc11; the loss scalars
-    // (which need fc11's partials) follow dW11 on the side stream in do_backward -- no fork between fc11 and the backward
-    // pass, and dW11 starts as soon as fc11 has finished: EV_FORK rides on the fc11 kernel.
-    auto fc11_with_fork = [&]() -> int {
-        if (need_grad) c.stop_ev = c.ev(EV_FORK);
-        const int r = launch_fc11_fast(c, params, x, xs, x_rec, need_grad);
-        c.stop_ev = nullptr;
-        c.fork_on_fc11 = c.stop_used;
-        c.stop_used = false;
-        return r;
-    };
-    if (couple_role) {
-        *couple_done = true;
-        c.couple_in_dec = true;
-        if ((rc = launch_chain_fwd_dec(c, params, true))) return rc;
-        return fc11_with_fork();
-    }
-    if (couple_done && c.side()) {
-        if ((rc = lat_rode ? fork_wait_only(c, EV_LAT) : fork_to_side(c, EV_LAT))) return rc;
+    if (p.couple == COUPLE_SIDE) {
+        if ((rc = p.lat_fork_rides ? fork_wait_only(c, EV_LAT) : fork_to_side(c, EV_LAT))) return rc;
         if ((rc = launch_couple(cs))) return rc;
-        *couple_done = true;
-        if (t_early) {
+        if (p.loss_on_side) {
             if ((rc = launch_loss_finalize(cs, loss_out, 1))) return rc;
             if ((rc = record_on_side(c, EV_COUPLE))) return rc;
         }
     }
-    if ((rc = launch_chain_fwd_dec(c, params))) return rc;   // (fp32x3: it writes the slice planes of [d10 | 1] for fc11, dW11)
-    if (t_early) return fc11_with_fork();
-    if (couple_done && *couple_done && (rc = record_on_side(c, EV_COUPLE))) return rc;
-    if (fast) return launch_fc11_fast(c, params, x, xs, x_rec, need_grad);
-    return launch_fc11_fused(c, params, x, xs, x_rec, need_grad);
+    // (fp32x3: it writes the slice planes of [d10 | 1] for fc11, dW11; COUPLE_IN_DEC: the coupling terms too)
+    if ((rc = launch_chain_fwd_dec(c, params))) return rc;
+    if (p.couple == COUPLE_SIDE && !p.loss_on_side && (rc = record_on_side(c, EV_COUPLE))) return rc;
+    // loss_on_side: dW11 starts as soon as fc11 has finished -- EV_FORK rides on the fused fc11 kernel
+    return launch_with_fork(c, p.fc11_fork_rides, EV_FORK, [&] { return launch_fc11(c, params, x, xs, x_rec, need_grad); });
 }
 
 static int do_loss(const Ctx& c, float* loss_out) {
@@ -385,32 +429,25 @@ static int do_loss(const Ctx& c, float* loss_out) {
     return launch_loss_finalize(c, loss_out);
 }
 
-// scalars_out != null: the loss scalars are still to be computed (mmvae_train_step on the fast path; the T sums are
-// already on the side stream, EV_COUPLE) -- behind dW11 on the side stream, or at the end of the main stream
+// Plan::loss_on_side: the loss scalars (into loss_out) are still to be computed (the T sums are already on the side
+// stream, EV_COUPLE) -- behind dW11 on the side stream
 static int do_backward(const Ctx& c, const mmvae_noise* nz, const float* params, const float* x, int64_t xs,
-                       float grad_scale, float* grads, const AdamHost* adam = nullptr, bool wait_loss = false,
-                       float* scalars_out = nullptr) {
+                       float grad_scale, float* grads, const AdamHost* adam = nullptr, float* loss_out = nullptr) {
+    const Plan& p = c.plan;
     int rc;
-    const bool fast = fast_path_ok(c, params, x, xs);
-    // dW11 depends only on dZ11 and d10 (both final after forward): it runs on the side stream beside the backward chain, forked at
-    // the START of the backward pass -- the later it starts, the more of it lands on the MFMA-bound dW1 (measured again in round 4,
-    // profiles/r04_dw11_placement_sweep.txt: behind the decoder chain + 30 us per step, behind the latent backward + 15, not
-    // forked + 75; fewer or more workgroups than the default split + 5 .. 10).
-    bool forked = false;
-    const bool use_side = fast && c.side();
-    const bool early = use_side && !adam && c.ex.early_grad_event != nullptr;
-    const bool side_red = use_side && adam;
+    // dW11 on the side stream (Plan::dw11_side)
+    const bool early = p.dw11_side && !adam && c.ex.early_grad_event != nullptr;
+    const bool side_red = p.dw11_side && adam;
     if (c.ex_out) c.ex_out->early_recorded = 0;
     Ctx cs = c;
     cs.stream = c.side();
-    if (use_side) {
-        if ((rc = (c.fork_on_fc11 ? fork_wait_only(c, EV_FORK) : fork_to_side(c, EV_FORK)))) return rc;
-        c.fork_on_fc11 = false;
+    if (p.dw11_side) {
+        if ((rc = (p.fc11_fork_rides ? fork_wait_only(c, EV_FORK) : fork_to_side(c, EV_FORK)))) return rc;
         if ((rc = launch_dw_big_fast(cs, x, xs, 2))) return rc;
         if (early) {
             // data parallel: fc11.weight / fc11.bias (47 % of the parameters) are final here; reduce their slabs now
             // and tell the caller, who starts their all-reduce beside the rest of backward
-            if ((rc = launch_reduce_grads(cs, grads, grad_scale, nullptr, true, 1))) return rc;
+            if ((rc = launch_reduce_grads(cs, grads, grad_scale, nullptr, 1))) return rc;
             if (hipEventRecord(reinterpret_cast<hipEvent_t>(c.ex.early_grad_event), c.side()) != hipSuccess) {
                 set_error("event record failed");
                 return MMVAE_E_LAUNCH;
@@ -420,34 +457,23 @@ static int do_backward(const Ctx& c, const mmvae_noise* nz, const float* params,
         if (side_red) {
             // fused Adam: fc11.weight / fc11.bias (47 % of the parameters) are reduced and updated here, behind their GEMM on
             // the side stream -- nothing reads W11 again in this step, and the side stream is idle from here to the join
-            if ((rc = launch_reduce_grads(cs, grads, grad_scale, adam, true, 1))) return rc;
+            if ((rc = launch_reduce_grads(cs, grads, grad_scale, adam, 1))) return rc;
         }
-        if (scalars_out && (rc = launch_loss_finalize(cs, scalars_out, 2))) return rc;
+        if (p.loss_on_side && (rc = launch_loss_finalize(cs, loss_out, 2))) return rc;
         if ((rc = record_on_side(c, EV_JOIN))) return rc;
-        forked = true;
     }
-    // fp32x3 engine: a backward pass that is its own call writes the small layers' weight planes again (the fused step's
-    // forward pass has left them in place)
-    if (fast && !c.small_planes && (rc = launch_x3_planes(c, params, 8))) return rc;
-    const int nslab = fc11_split_path(c, params, x, xs) ? c.lay.sp.ks_gd10 : c.lay.sp.ns_fc11;
-    if ((rc = launch_chain_bwd_dec(c, params, nslab))) return rc;
+    if (p.bwd_small_planes && (rc = launch_x3_planes(c, params, false))) return rc;
+    if ((rc = launch_chain_bwd_dec(c, params))) return rc;
     // T (sum of G log c, from the loss finalisation) is first needed here
-    if (wait_loss && !c.couple_in_dec && (rc = join_from_side(c, EV_COUPLE))) return rc;
+    if (p.loss_on_side && p.couple == COUPLE_SIDE && (rc = join_from_side(c, EV_COUPLE))) return rc;
     if ((rc = launch_lat_bwd(c, nz, params))) return rc;
     for (int layer = 5; layer >= 2; --layer)
         if ((rc = launch_chain_bwd_enc(c, layer, params))) return rc;
     if ((rc = launch_bn_bwd_apply1(c))) return rc;
-    if (fast) {
-        if ((rc = launch_x3_planes(c, params, 4))) return rc;            // fp32x3: slice planes of dZ1 (dW1)
-        if ((rc = launch_dw_big_fast(c, x, xs, forked ? 1 : 3))) return rc;
-    } else if ((rc = launch_dw_big(c, nz, x, xs))) {
-        return rc;
-    }
+    if ((rc = p.fast ? launch_dw_big_fast(c, x, xs, p.dw11_side ? 1 : 3) : launch_dw_big(c, nz, x, xs))) return rc;
     if ((rc = launch_dw_small(c))) return rc;
-    const bool fc11_on_side = (early || side_red) && forked;
-    if (forked && (rc = join_from_side(c, EV_JOIN))) return rc;
-    if (scalars_out && !forked && (rc = launch_loss_finalize(c, scalars_out, 2))) return rc;
-    return launch_reduce_grads(c, grads, grad_scale, adam, fast, fc11_on_side ? 2 : 3);
+    if (p.dw11_side && (rc = join_from_side(c, EV_JOIN))) return rc;
+    return launch_reduce_grads(c, grads, grad_scale, adam, early || side_red ? 2 : 3);
 }
 
 }  // namespace mmvae
@@ -532,6 +558,7 @@ int mmvae_forward(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* 
     if (!params || !x) { set_error("null params / x"); return MMVAE_E_BADARG; }
     if (int rc = check_noise(c, nz)) return rc;
     if (need_grad && !h->training) { set_error("need_grad requires training mode (batch statistics)"); return MMVAE_E_UNSUPPORTED; }
+    make_plan(c, CALL_FORWARD, params, x, x_arm_stride, need_grad && !x_rec);
     return do_forward(c, nz, params, bn_running, nbt, x, x_arm_stride, x_rec, need_grad);
 }
 
@@ -540,6 +567,7 @@ int mmvae_loss(const mmvae_dims* d, const mmvae_hyper* h, void* ws, size_t ws_by
     Ctx c;
     if (int rc = make_ctx(c, d, h, ws, ws_bytes, ex, stream)) return rc;
     if (!loss_out) { set_error("loss_out is null"); return MMVAE_E_BADARG; }
+    make_plan(c, CALL_LOSS, nullptr, nullptr, 0);
     return do_loss(c, loss_out);
 }
 
@@ -551,6 +579,7 @@ int mmvae_backward(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise*
     if (!params || !x || !grads) { set_error("null params / x / grads"); return MMVAE_E_BADARG; }
     if (int rc = check_noise(c, nz)) return rc;
     if (!h->training) { set_error("backward requires training mode"); return MMVAE_E_UNSUPPORTED; }
+    make_plan(c, CALL_BACKWARD, params, x, x_arm_stride);
     return do_backward(c, nz, params, x, x_arm_stride, grad_scale, grads);
 }
 
@@ -572,14 +601,13 @@ static int train_step_impl(Ctx& c, const mmvae_hyper* h, const mmvae_noise* nz, 
     if (!params || !x || !grads || !loss_out) { set_error("null params / x / grads / loss_out"); return MMVAE_E_BADARG; }
     if (int rc = check_noise(c, nz)) return rc;
     if (!h->training) { set_error("train_step requires training mode"); return MMVAE_E_UNSUPPORTED; }
+    const Plan& p = c.plan;
     int rc;
-    bool side_loss = false;   // coupling (+ loss scalars on the fast path) already running on the side stream
-    if ((rc = do_forward(c, nz, params, bn_running, nbt, x, x_arm_stride, nullptr, 1, &side_loss, loss_out))) return rc;
-    const bool loss_on_side = side_loss && fc11_split_path(c, params, x, x_arm_stride);
-    if (side_loss && !loss_on_side) {   // general path: coupling done on the side, finalise here
+    if ((rc = do_forward(c, nz, params, bn_running, nbt, x, x_arm_stride, nullptr, 1, loss_out))) return rc;
+    if (p.couple == COUPLE_SIDE && !p.loss_on_side) {   // general path: coupling done on the side, finalise here
         if ((rc = join_from_side(c, EV_COUPLE))) return rc;
         if ((rc = launch_loss_finalize(c, loss_out))) return rc;
-    } else if (!side_loss && (rc = do_loss(c, loss_out))) {
+    } else if (p.couple == COUPLE_INLINE && (rc = do_loss(c, loss_out))) {
         return rc;
     }
     if (do_adam) {
@@ -587,9 +615,9 @@ static int train_step_impl(Ctx& c, const mmvae_hyper* h, const mmvae_noise* nz, 
         // need no update)
         if (!exp_avg || !exp_avg_sq || step < 1) { set_error("adam state missing"); return MMVAE_E_BADARG; }
         const AdamHost ah{params, exp_avg, exp_avg_sq, step, lr, beta1, beta2, adam_eps, weight_decay, decoupled};
-        return do_backward(c, nz, params, x, x_arm_stride, 1.f, grads, &ah, loss_on_side, loss_on_side ? loss_out : nullptr);
+        return do_backward(c, nz, params, x, x_arm_stride, 1.f, grads, &ah, loss_out);
     }
-    return do_backward(c, nz, params, x, x_arm_stride, 1.f, grads, nullptr, loss_on_side, loss_on_side ? loss_out : nullptr);
+    return do_backward(c, nz, params, x, x_arm_stride, 1.f, grads, nullptr, loss_out);
 }
 
 int mmvae_train_step(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, float* params,
@@ -599,6 +627,7 @@ int mmvae_train_step(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_nois
                      mmvae_exec* ex, void* stream) {
     Ctx c;
     if (int rc = make_ctx(c, d, h, ws, ws_bytes, ex, stream)) return rc;
+    make_plan(c, CALL_STEP, params, x, x_arm_stride);
     return train_step_impl(c, h, nz, params, bn_running, nbt, x, x_arm_stride, grads, loss_out, do_adam, exp_avg, exp_avg_sq, step,
                            lr, beta1, beta2, adam_eps, weight_decay, decoupled);
 }
@@ -618,22 +647,20 @@ int mmvae_train_step_rows(const mmvae_dims* d, const mmvae_hyper* h, const mmvae
         set_error("train_step_rows: needs ld %% 4 == 0, 16-byte aligned data and n_rows * ld < 2^30 floats");
         return MMVAE_E_UNSUPPORTED;
     }
-    const bool x3 = split3_gemms(c) && d->H + 1 <= 112, b16 = h->gemm_bf16 == 1 && bf16_gemms(c);
-    if (!h->training || !(h->x_drop > 0.f) || !(x3 || b16) || !prologue_merged(c) || !fast_path_ok(c, params, data, 0) ||
-        (int64_t)cdiv(d->B, 128) * c.lay.sp.ks_gd10 > c.lay.n11) {
-        set_error("train_step_rows: only the fused training step of the fp32x3 / bf16 engines reads the batch through a row map");
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (data_bf16) {   // bf16 storage: the bf16 engine reads x from the copy and keeps dZ11 as bf16
-        if (!b16 || (d->D & 7) || (ld & 7) || (reinterpret_cast<uintptr_t>(data_bf16) & 15)) {
-            set_error("train_step_rows: data_bf16 needs the bf16 engine, D %% 8 == 0, ld %% 8 == 0 and a 16-byte aligned copy");
-            return MMVAE_E_UNSUPPORTED;
-        }
-        c.x16 = data_bf16;
-    }
     c.x_rows = rows;
     c.x_ld = ld;
     c.x_nrows = n_rows;
+    c.x16 = data_bf16;
+    make_plan(c, CALL_STEP_ROWS, params, data, 0);
+    if (!c.plan.rowmap) {
+        set_error("train_step_rows: only the fused training step of the fp32x3 / bf16 engines reads the batch through a row map");
+        return MMVAE_E_UNSUPPORTED;
+    }
+    // bf16 storage: the bf16 engine reads x from the copy and keeps dZ11 as bf16
+    if (data_bf16 && (c.plan.big != GEMM_BF16 || (d->D & 7) || (ld & 7) || (reinterpret_cast<uintptr_t>(data_bf16) & 15))) {
+        set_error("train_step_rows: data_bf16 needs the bf16 engine, D %% 8 == 0, ld %% 8 == 0 and a 16-byte aligned copy");
+        return MMVAE_E_UNSUPPORTED;
+    }
     return train_step_impl(c, h, nz, params, bn_running, nbt, data, 0, grads, loss_out, do_adam, exp_avg, exp_avg_sq, step,
                            lr, beta1, beta2, adam_eps, weight_decay, decoupled);
 }
@@ -650,9 +677,9 @@ int mmvae_eval_classify(const mmvae_dims* d, const mmvae_hyper* h, const float* 
     // sample the latent kernel also produces does not enter c: it takes the Philox stream of seed 0
     mmvae_noise nzp{};
     nzp.mode = 1;
+    make_plan(c, CALL_CLASSIFY, params, x, x_arm_stride);
     // the latent kernel's hard-sample argmax IS classify(c) in eval mode: the labels come out of it directly
-    if ((rc = do_forward(c, &nzp, params, const_cast<float*>(bn_running), nullptr, x, x_arm_stride, nullptr, 0, nullptr,
-                         nullptr, true, labels)))
+    if ((rc = do_forward(c, &nzp, params, const_cast<float*>(bn_running), nullptr, x, x_arm_stride, nullptr, 0, nullptr, labels)))
         return rc;
     if (counts) return launch_confmat(labels, d->A, d->B, d->C, counts, c.stream);
     return 0;
@@ -685,38 +712,35 @@ int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noi
     if (!params || !x) { set_error("null params / x"); return MMVAE_E_BADARG; }
     if (int rc = check_noise(c, nz)) return rc;
     // a stage is replayed on the state a complete forward / backward pass of the same engine left behind: its slice planes
-    // (fp32x3 engine) are in place
-    c.small_planes = chain_x3_ok(c) && fast_path_ok(c, params, x, x_arm_stride);
+    // are in place, and no head launch of this call has zeroed anything
+    make_plan(c, CALL_REPLAY, params, x, x_arm_stride);
+    const bool fast = c.plan.fast;
     switch (stage) {
         case 0:
-            if (fast_path_ok(c, params, x, x_arm_stride)) {
+            if (fast) {
                 if (int rc = launch_fc1_fwd_fast(c, params, x, x_arm_stride)) return rc;
                 return launch_fc1_epi(c, params);
             }
             return launch_fc1_fwd(c, nz, params, x, x_arm_stride);
-        case 1:
-            if (fast_path_ok(c, params, x, x_arm_stride)) return launch_fc11_fast(c, params, x, x_arm_stride, nullptr, 1);
-            return launch_fc11_fused(c, params, x, x_arm_stride, nullptr, 1);
-        case 2:
-            if (fast_path_ok(c, params, x, x_arm_stride)) return launch_dw_big_fast(c, x, x_arm_stride, 3);
-            return launch_dw_big(c, nz, x, x_arm_stride);
+        case 1: return launch_fc11(c, params, x, x_arm_stride, nullptr, 1);
+        case 2: return fast ? launch_dw_big_fast(c, x, x_arm_stride, 3) : launch_dw_big(c, nz, x, x_arm_stride);
         case 9: return launch_make_xbits(c, nz);
         case 20: return launch_chain_fwd_enc(c, 3, params, nullptr, nullptr);   // one encoder layer (fc3)
         case 21: return launch_chain_bwd_enc(c, 3, params);
         // single kernels of the fast path (per-kernel roofline timing)
         case 10: case 11: case 12: case 13: case 14:
-            if (!fast_path_ok(c, params, x, x_arm_stride)) { set_error("stage %d needs the fast path", stage); return MMVAE_E_UNSUPPORTED; }
-            if (stage == 10) return launch_fc11_fast(c, params, x, x_arm_stride, nullptr, 1, 1);
-            if (stage == 11) return launch_fc11_fast(c, params, x, x_arm_stride, nullptr, 1, 2);
+            if (!fast) { set_error("stage %d needs the fast path", stage); return MMVAE_E_UNSUPPORTED; }
+            if (stage == 10) return launch_fc11(c, params, x, x_arm_stride, nullptr, 1, 1);
+            if (stage == 11) return launch_fc11(c, params, x, x_arm_stride, nullptr, 1, 2);
             if (stage == 12) return launch_dw_big_fast(c, x, x_arm_stride, 1);
             if (stage == 13) return launch_dw_big_fast(c, x, x_arm_stride, 2);
             return launch_fc1_fwd_fast(c, params, x, x_arm_stride);
         case 3: return launch_dw_small(c);
         case 4: return launch_chain_fwd_dec(c, params);
-        case 5: return launch_chain_bwd_dec(c, params, fc11_split_path(c, params, x, x_arm_stride) ? c.lay.sp.ks_gd10 : c.lay.sp.ns_fc11);
+        case 5: return launch_chain_bwd_dec(c, params);
         case 6: return launch_lat_fwd(c, nz, params, nullptr, nullptr);
         case 7: return launch_lat_bwd(c, nz, params);
-        case 8: if (!grads) { set_error("grads is null"); return MMVAE_E_BADARG; } return launch_reduce_grads(c, grads, 1.f, nullptr, fast_path_ok(c, params, x, x_arm_stride));
+        case 8: if (!grads) { set_error("grads is null"); return MMVAE_E_BADARG; } return launch_reduce_grads(c, grads, 1.f, nullptr);
         default: set_error("unknown stage %d", stage); return MMVAE_E_BADARG;
     }
 }

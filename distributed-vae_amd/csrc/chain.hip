@@ -896,7 +896,7 @@ static int launch_fwd(const Ctx& c, ChainFwdArgs& a, int maxdim, const float* pa
     a.rows = c.lay.chain_rows_fwd;
     a.nblk = c.lay.nblkf;
     const dim3 grid(c.lay.nblkf, c.d.A);
-    if (c.small_planes && chain_x3_ok(c) && maxdim <= 128) {
+    if (c.plan.chain_planes) {
         a.ld = x3_ld(maxdim);
         a.wrows = 128;
         a.wpl_off = c.lay.pl_small;
@@ -912,7 +912,7 @@ static int launch_fwd(const Ctx& c, ChainFwdArgs& a, int maxdim, const float* pa
 
 static int launch_bwd(const Ctx& c, ChainBwdArgs& a, int maxdim, const float* params, const char* what) {
     const dim3 grid(c.lay.nblkc, c.d.A);
-    if (c.small_planes && chain_x3_ok(c) && maxdim <= 128) {
+    if (c.plan.chain_planes) {
         a.ld = x3_ld(maxdim);
         a.wrows = 128;
         a.wpl_off = c.lay.pl_small;
@@ -992,7 +992,7 @@ int launch_chain_fwd_enc_eval(const Ctx& c, const float* params) {
     return launch_fwd(c, a, max(d.H, d.L), params, nullptr, nullptr, "k_chain_fwd<enc eval>");
 }
 
-int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
+int launch_chain_fwd_dec(const Ctx& c, const float* params) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     ChainFwdArgs a{};
@@ -1008,14 +1008,14 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
     a.stats_part_off = -1;
     a.acc_in_off = a.acc_out_off = -1;
     // fp32x3 engine: the slice planes of [d10 | 1] for fc11 and dW11
-    a.planes_off = split3_gemms(c) ? L.pl_d10 : -1;
+    a.planes_off = c.plan.d10_planes ? L.pl_d10 : -1;
     a.planes_rows = rup(d.B, 256);
     a.B = d.B;
     a.ld = fwd_ld(max(max(d.H, d.L), d.C + d.S));
     a.wrows = rup(max(d.H, d.L), 32);
     a.per_arm = c.po.per_arm;
     for (int i = 0; i < 5; ++i) a.L[i].pl_slot = 4 + i;
-    if (with_couple) {
+    if (c.plan.couple == COUPLE_IN_DEC) {
         // the coupling terms as a second role of this launch (k_chain_fwd_couple): fp32x3 form, accumulator sets, 2 .. 5 arms
         const int maxdim = max(max(d.H, d.L), d.C + d.S);
         a.rows = L.chain_rows_fwd;
@@ -1044,19 +1044,7 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple) {
     }
     return launch_fwd(c, a, max(max(d.H, d.L), d.C + d.S), params, nullptr, nullptr, "k_chain_fwd<dec>");
 }
-// the fused train step may run the coupling terms inside the decoder chain's launch (see k_chain_fwd_couple).  Measured
-// (A/B/A/B per arm count on one box, ms per step, role against side stream): A = 2 0.674 / 0.672, A = 3 0.901 / 0.896, A = 5
-// 1.479 / 1.489 -- the two bubbles it removes from the main stream show in a rocprofv3 trace (5 - 6 us each) but not in the
-// un-profiled step at two and three arms, where the combined launch is 3 us longer than the chain's own (its grid has a third
-// row of workgroups); at five arms the chain's 395 workgroups already run in two rounds and the role fills the second.  So: the
-// role from four arms up, the side stream below (MMVAE_TUNE_COUPLE_SIDE: 1 side stream always, 3 role always).
-bool dec_couple_ok(const Ctx& c) {
-    const mmvae_dims& d = c.d;
-    return c.h.training && c.use_acc() && c.small_planes && chain_x3_ok(c) && max(max(d.H, d.L), d.C + d.S) <= 128 && d.A >= 2 &&
-           d.A <= 5 && d.C <= CPL * 64 && c.tune(MMVAE_TUNE_COUPLE_SIDE) != 1 && (d.A >= 4 || c.tune(MMVAE_TUNE_COUPLE_SIDE) == 3);
-}
-
-int launch_chain_bwd_dec(const Ctx& c, const float* params, int nslab) {
+int launch_chain_bwd_dec(const Ctx& c, const float* params) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     ChainBwdArgs a{};
@@ -1067,7 +1055,7 @@ int launch_chain_bwd_dec(const Ctx& c, const float* params, int nslab) {
     a.L[3] = BwdLayer{c.po.o[18], L.DZ[7], L.Dk[1], d.L, d.H};           // fc7: K = L
     a.L[4] = BwdLayer{c.po.o[16], L.DZ[6], L.Dk[0], d.C + d.S, d.L};     // fc6: K = C+S
     a.g_off = L.GD10_slab;
-    a.nslab = nslab;
+    a.nslab = c.plan.gd10_slabs;
     a.slab_stride = (int64_t)d.A * d.B * d.H;
     a.bnb_part_off = -1;
     a.bn_mean_off = a.bn_rstd_off = -1;
@@ -1079,7 +1067,6 @@ int launch_chain_bwd_dec(const Ctx& c, const float* params, int nslab) {
     // their first producer)
     a.zero_off = acc_set_off(L, d.A, ACC_BWD);
     a.zero_n4 = c.use_acc() ? (int)(c.bwd_zero_floats() / 4) : 0;
-    c.bwd_zeroed = a.zero_n4 > 0;
     a.B = d.B;
     a.ld = bwd_ld(max(max(d.H, d.L), d.C + d.S));
     a.wrows = max(rup(max(d.H, d.L), 8), cdiv(WS_SCRATCH, a.ld));   // Ws doubles as scratch of the epilogue's sums
@@ -1125,8 +1112,8 @@ int launch_chain_bwd_enc(const Ctx& c, int layer, const float* params) {
 int launch_bn_bwd_apply1(const Ctx& c) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
-    // fp32x3 engine: this launch also writes the slice planes of dZ1 (launch_x3_planes(.., 4) then has nothing to do)
-    const bool planes = bn_apply_writes_planes(c);
+    // fp32x3 engine, bf16 storage: this launch also writes the slice planes of dZ1 (Plan::dz1_in_apply)
+    const bool planes = c.plan.dz1_in_apply;
     const int Rp = rup(d.B, 256);
     hipLaunchKernelGGL(k_bn_bwd_apply, dim3(planes ? Rp / 32 : L.nblk32, d.A), dim3(256), 0, c.stream, c.ws + L.G[1],
                        c.ws + L.R[0], c.ws + L.bn_mean[0], c.ws + L.bn_rstd[0], c.ws + L.bnb_part[1], L.nblkc,

@@ -329,6 +329,8 @@ constexpr int CHAIN_ROWS = MMVAE_CHAIN_ROWS;
 // VALU-bound, so what counts is cells per CU: 48 gives 105 workgroups per arm at B = 5000 -- one per CU, three cells
 // per wave -- where 32 gave 314 workgroups on 256 CUs, i.e. 58 CUs with two (four cells per wave slot).
 constexpr int LAT_ROWS = 48;
+// half-wave form of the latent kernels (rowwise.hip): a cell owns 32 lanes x LH_CPL registers (C <= 32 LH_CPL)
+constexpr int LH_CPL = 3;
 // The backward kernel runs beside the dW11 GEMM of the side stream, where smaller workgroups spread over all CUs
 // measured faster in the step (61 against 70 us) although slower alone (32 against 24 us); with dW11 on 160 CUs
 // (round 2, chain kernels on the split engine) 8 cells per workgroup again beat 16 (step 718 against 725 us; 32: 729).
@@ -720,6 +722,51 @@ __device__ __forceinline__ void make_xbits_range(const NoiseDev& nz, int A, int 
 }
 #endif  // __HIPCC__
 
+// shape rules shared by default_splits (which sees only the dims and the exec) and make_plan (api.hip)
+inline bool fast_dims(const mmvae_dims& d) { return (d.D & 3) == 0 && (d.H & 3) == 0; }
+inline bool bf16_tiles_fit(const mmvae_dims& d) { return d.H <= 124; }         // the bf16 engines' D x H tiles
+inline bool x3_fc11_fits(const mmvae_dims& d) { return d.H + 1 <= 112; }       // k_x3_fc11g: [d10 | 1] within 112 columns
+inline bool chain_planes_fit(const mmvae_dims& d) { return d.C + d.S <= 128 && d.L <= 128; }   // one 128 x 128 plane per layer
+// the fused fc11 kernels of the bf16 engines: the loss partials of their 128-cell blocks fit the slots
+inline bool fc11_slots_fit(const Layout& L, int B) { return (int64_t)cdiv(B, 128) * L.sp.ks_gd10 <= L.n11; }
+
+// Per-call plan: which kernels a call runs, on which stream, and which launch writes what for whom.  make_plan (api.hip)
+// builds it once per entry point; the launchers and drivers read it and decide nothing themselves.
+enum CallKind { CALL_STEP, CALL_STEP_ROWS, CALL_FORWARD, CALL_BACKWARD, CALL_LOSS, CALL_CLASSIFY, CALL_REPLAY /*debug stage*/ };
+// fc1, dW1, dW11: gemm_big.hip, fp32 matrix instruction (gemm_fast.hip), k_bf16_* / k_x3_* (gemm_bf16.hip)
+enum GemmFamily { GEMM_GENERAL, GEMM_FP32, GEMM_BF16, GEMM_X3 };
+// fc11 + d(d10): k_fc11_fused, k_fc11_zg (d(d10) folded in), k_fc11_zt + k_gd10_*, k_bf16_fc11* (+ k_bf16_gemm), k_x3_fc11g
+enum Fc11Family { FC11_GENERAL, FC11_ZG, FC11_ZT, FC11_BF16, FC11_X3 };
+// the launch that zeroes the loss partial slots and the forward accumulator sets at the start of a forward pass (none:
+// eval mode or a replayed stage -- the fc11 launchers then zero their slots themselves)
+enum FwdZero { ZERO_NONE, ZERO_MEMSET, ZERO_XBITS /*k_make_xbits*/, ZERO_PRESPLIT /*the head k_presplit launch*/ };
+// a fused step's coupling terms: main stream behind fc11 (do_loss), side stream, or a role of the decoder chain's launch
+enum CouplePlace { COUPLE_INLINE, COUPLE_SIDE, COUPLE_IN_DEC };
+struct Plan {
+    CallKind kind;
+    bool fast;              // 16-byte aligned params and x, shape within 32-bit offsets
+    GemmFamily big;         // (GEMM_GENERAL exactly off the fast path)
+    bool small_x3;          // the batched small-layer dW products on k_x3_small (when every product fits its tiles)
+    Fc11Family fc11;
+    int gd10_slabs;         // d(d10) slabs the decoder backward sums
+    int dw11_slabs;         // dW11 slabs the gradient reduction sums
+    bool chain_planes;      // the chain kernels' fp32x3 form (small-layer weight planes, Layout::pl_small)
+    bool lat_half;          // the latent kernels' half-wave form
+    bool narrow;            // bf16 storage: W1, [W11 | b11] and dZ1 are read as bf16, slice 0 of their planes
+    bool presplit;          // slice planes: k_presplit at the head of the forward pass (W1 and [W11 | b11], small layers),
+    bool bwd_small_planes;  //   k_presplit at the head of a backward call of its own (small layers),
+    bool d10_planes;        //   the decoder chain ([d10 | 1]),
+    bool dz1_in_apply;      //   k_bn_bwd_apply (dZ1)
+    FwdZero zero;
+    bool rowmap;            // the batch is read through the row map (mmvae_train_step_rows; the head launch builds it)
+    bool dz11_bf16;         // the fused fc11 kernel writes dZ11 as bf16 and dW11 reads it so (bf16 storage)
+    bool dw11_side;         // dW11 and the fc11 tensors' reduction on the side stream beside the backward chain
+    bool loss_on_side;      // the fused step's loss scalars follow dW11 on the side stream
+    CouplePlace couple;
+    bool lat_fork_rides;    // EV_LAT rides on the latent forward kernel
+    bool fc11_fork_rides;   // EV_FORK rides on the fused fc11 kernel: do_backward's dW11 fork only waits
+};
+
 // ------------------------------------------------------------------------------------------
 // Launch context handed to the stage launchers (host)
 // ------------------------------------------------------------------------------------------
@@ -737,34 +784,25 @@ struct Ctx {
     int tune(int i) const { return ex.tune[i]; }
     // training-mode batch sums through the fixed-point accumulators (production) or the per-workgroup partial arrays
     bool use_acc() const { return !ex.tune[MMVAE_TUNE_BN_PARTIALS]; }
-    // set by the launcher that zeroed [fc11_part, end of the forward accumulator sets) at the start of this call's forward
-    // pass; launchers that find it unset (a stage replayed on its own) zero what they need themselves
-    mutable bool fwd_zeroed = false;
-    // set by launch_x3_planes when this call has written the small-layer weight planes (Layout::pl_small): the chain
-    // launchers then take the fp32x3 form of their kernels
-    mutable bool small_planes = false;
+    // the range Plan::zero names a launch for: [fc11_part, end of the forward accumulator sets)
     // (through the coupling's T set: the fused step's coupling runs inside the decoder chain's launch and finds it zeroed; the
     // coupling's own launcher zeroes it again, it may run more than once per forward pass)
     int64_t fwd_zero_floats() const { return acc_set_off(lay, d.A, ACC_BWD) - lay.fc11_part; }
     int64_t bwd_zero_floats() const { return lay.acc_end - acc_set_off(lay, d.A, ACC_BWD); }
-    mutable bool bwd_zeroed = false;   // set by the launcher of the first kernel of a backward pass (it zeroes that range)
     // mmvae_train_step_rows: the batch is rows x_rows[0 .. B) (device, int64) of the resident matrix [x_nrows][x_ld] that the
-    // call's `x` points at; the head launch of the step turns them into the row map (Layout::rowmap) and sets rowmap_ready
+    // call's `x` points at; the head launch of the step turns them into the row map (Layout::rowmap)
     const int64_t* x_rows = nullptr;
     // ... and, optionally, its bf16 copy (same shape and leading dimension, in elements): the bf16 engine's large GEMMs and its
-    // fused fc11 kernel read x from it and dZ11 travels as bf16 (dz16: the fused kernel of this call wrote it that way)
+    // fused fc11 kernel read x from it and dZ11 travels as bf16 (Plan::dz11_bf16)
     const unsigned short* x16 = nullptr;
-    mutable bool dz16 = false;
     int64_t x_ld = 0, x_nrows = 0;
-    mutable bool rowmap_ready = false;
+    Plan plan{};            // make_plan (api.hip), once per entry point
     // Fork events that ride on a kernel (hipExtLaunchKernel's stop event: the dispatch packet's own completion signal) instead
     // of a hipEventRecord behind it -- a recorded event is a barrier packet of its own, 6 - 7 us of idle main stream at every
     // fork.  The step's driver names the event the NEXT launch of a launcher that knows launch_k carries (stop_ev); the
     // launcher consumes it and sets stop_used, and the fork then only makes the side stream wait.
     mutable hipEvent_t stop_ev = nullptr;
     mutable bool stop_used = false;
-    mutable bool couple_in_dec = false;  // the coupling ran as a role of the decoder chain's launch: main stream, nothing to wait for
-    mutable bool fork_on_fc11 = false;   // EV_FORK rode on this call's fused fc11 kernel (do_backward's dW11 fork only waits)
 };
 #ifdef __HIPCC__
 template <class K, class... Args>
@@ -792,13 +830,11 @@ int launch_chain_fwd_enc(const Ctx& c, int layer /*2..5*/, const float* params, 
 int launch_chain_fwd_enc_eval(const Ctx& c, const float* params);   // eval mode: fc2..fc5 in one launch
 int launch_lat_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
                    int32_t* labels = nullptr /*eval: argmax of c per cell and arm*/);
-int launch_chain_fwd_dec(const Ctx& c, const float* params, bool with_couple = false /*the coupling terms as a role of the launch*/);
-bool dec_couple_ok(const Ctx& c);
+int launch_chain_fwd_dec(const Ctx& c, const float* params);   // (with the coupling terms as a role: Plan::couple)
 int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
 int launch_couple(const Ctx& c);
 int launch_loss_finalize(const Ctx& c, float* loss_out, int mode = 0 /*1: the T sums only, 2: the scalars only*/);
-int launch_chain_bwd_dec(const Ctx& c, const float* params, int nslab);
-bool fc11_split_path(const Ctx& c, const float* params, const float* x, int64_t xs);
+int launch_chain_bwd_dec(const Ctx& c, const float* params);
 int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params);
 int launch_chain_bwd_enc(const Ctx& c, int layer /*5..2*/, const float* params);
 int launch_bn_bwd_apply1(const Ctx& c);
@@ -819,40 +855,24 @@ struct TnDescs { TnDesc d[N_SMALL]; };
 int launch_dw_small_x3(const Ctx& c, const TnDescs& ts, int nsel);
 struct AdamHost { float* p; float* m; float* v; int64_t step; float lr, b1, b2, eps, wd; int decoupled; };
 // slabs -> grads; with `adam` (p != null) the Adam update is fused into the same pass
-int launch_reduce_grads(const Ctx& c, float* grads, float grad_scale, const AdamHost* adam, bool dw11_fast,
+int launch_reduce_grads(const Ctx& c, float* grads, float grad_scale, const AdamHost* adam,
                         int which = 3 /*bit0 fc11 tensors, bit1 the rest*/);
 int launch_adam(int64_t n, float* p, const float* g, float* m, float* v, int64_t step, float lr, float b1,
                 float b2, float eps, float wd, int decoupled, hipStream_t s);
-bool fast_path_ok(const Ctx& c, const float* params, const float* x, int64_t xs);
 int launch_make_xbits(const Ctx& c, const mmvae_noise* nz);
-// first thing of a forward pass: zero the loss partial slots and the forward accumulator sets (folded into
-// k_make_xbits when that runs, a fill otherwise)
-int launch_forward_zero(const Ctx& c, bool with_xbits, const mmvae_noise* nz);
+// first thing of a forward pass whose Plan::zero is ZERO_MEMSET or ZERO_XBITS: zero the loss partial slots and the
+// forward accumulator sets (folded into k_make_xbits when that runs, a fill otherwise)
+int launch_forward_zero(const Ctx& c, const mmvae_noise* nz);
 int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64_t xs);
 int launch_fc1_epi(const Ctx& c, const float* params);
-int launch_fc11_fast(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad,
-                     int which = 3);
+// fc11 and d(d10), the family Plan::fc11 names (which: bit0 x_rec / loss / dZ11, bit1 d(d10))
+int launch_fc11(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which = 3);
 int launch_dw_big_fast(const Ctx& c, const float* x, int64_t xs, int which /*bit0 dW1, bit1 dW11*/);
 // bf16-operand variants of the five D x H GEMMs (gemm_bf16.hip; mmvae_hyper.gemm_bf16), same outputs / layouts
 // gemm_bf16 == 2: fp32 operands split exactly into three bf16 slices each (six slice products per product: fp32-grade
 // results on the bf16 matrix pipe); the same tile engine with three LDS planes per operand
-inline bool split3_gemms(const Ctx& c) { return c.h.gemm_bf16 == 2 && c.d.H <= 124; }
-inline bool bf16_gemms(const Ctx& c) { return (c.h.gemm_bf16 == 1 || c.h.gemm_bf16 == 2) && c.d.H <= 124; }
-int launch_x3_planes(const Ctx& c, const float* params, int which /*bit0 W1 + [W11|b11] + small layers, bit2 dZ1, bit3 small layers only, bit4 + keep-mask and zero fill (head of a training step)*/,
-                     const mmvae_noise* nz = nullptr);
-// the chain kernels' own GEMMs on the fp32x3 engine: every layer within one 128 x 128 plane
-// (also in the bf16 configuration: only its five D x H products round their operands, everything else stays fp32-grade)
-inline bool chain_x3_ok(const Ctx& c) {
-    return bf16_gemms(c) && c.d.C + c.d.S <= 128 && c.d.L <= 128 && !c.tune(MMVAE_TUNE_CHAIN_FP32);
-}
-// true when launch_x3_planes(.., 1 | 16, nz) takes over k_make_xbits' work (the engines that have a k_presplit launch at the head of the step)
-inline bool prologue_merged(const Ctx& c) { return c.h.training && c.h.x_drop > 0.f && (split3_gemms(c) || chain_x3_ok(c)); }
-// bf16 configuration on bf16 storage (mmvae_train_step_rows(data_bf16)): the NARROW operands of fc1 / dW1 (W1, dZ1) are read as
-// bf16 too -- slice 0 of the planes the fp32x3 engine uses -- instead of fp32 rounded by every block tile
-inline bool bf16_narrow_planes(const Ctx& c) { return c.h.gemm_bf16 == 1 && c.x16 != nullptr && c.d.H <= 124 && (c.d.D & 7) == 0; }
-// k_bn_bwd_apply writes the slice planes of dZ1 itself (no k_presplit job for them), as the decoder chain does those of
-// [d10 | 1] under split3_gemms
-inline bool bn_apply_writes_planes(const Ctx& c) { return (split3_gemms(c) || bf16_narrow_planes(c)) && (c.d.H & 1) == 0; }
+// the k_presplit launch of Plan::presplit (head = true) or Plan::bwd_small_planes
+int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_noise* nz = nullptr);
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs);
 int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which);
 int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which);

@@ -1687,8 +1687,8 @@ static Operand kmajor(const float* p, int64_t ld, int rows, int K) { return Oper
 static Operand kminor(const float* p, int64_t ld, int rows, int K) { return Operand{p, ld, rows, K, 1, nullptr, 0, -1, nullptr, 0, 0, 0, nullptr, 0, 0, 0}; }
 
 // Slice planes of the four small operands (fp32x3 engine).  They are written at fixed points of the step -- W1 and
-// [W11 | b11] at the start of the forward pass (launch_x3_planes), [d10 | 1] by the decoder chain, dZ1 by k_bn_bwd_apply or
-// launch_x3_planes behind the encoder's backward chain -- and read by the GEMM launchers below, which only fill in the
+// [W11 | b11] at the start of the forward pass (launch_x3_planes), [d10 | 1] by the decoder chain, dZ1 by k_bn_bwd_apply
+// behind the encoder's backward chain (Plan) -- and read by the GEMM launchers below, which only fill in the
 // operand's plane fields.
 static inline int rup_i(int a, int b) { return cdiv(a, b) * b; }
 enum { PL_W1 = 0, PL_W11 = 1, PL_D10 = 2, PL_DZ1 = 3 };
@@ -1725,16 +1725,16 @@ static int launch_presplit(hipStream_t s, int A, const SplitJob* jobs, int n, co
     return 0;
 }
 
-// fp32x3: write the slice planes of the small operands (bit 0: W1 and [W11 | b11], from the parameters; bit 2: dZ1) -- one
-// small launch each time, ahead of the GEMMs that copy them into LDS.  No-op for the other engines.
-int launch_x3_planes(const Ctx& c, const float* params, int which, const mmvae_noise* nz) {
-    const bool x3 = split3_gemms(c);
-    if (!x3 && !chain_x3_ok(c)) return 0;
-    // bit 4 (the head of a training step's forward pass, dropout on): this launch also makes the keep-mask and zeroes the
-    // loss partial slots and the forward accumulator sets -- k_make_xbits' work (launch_forward_zero) without its launch
+// Write slice planes from the parameters -- one small launch ahead of the kernels that copy them into LDS: at the head of a
+// forward pass W1 and [W11 | b11] (fp32x3 engine, bf16 storage) and the small layers' weights (Plan::chain_planes), at the
+// head of a backward pass that is its own call the small layers' weights alone.
+int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_noise* nz) {
+    const Plan& p = c.plan;
+    // ZERO_PRESPLIT (the head of a training step's forward pass, dropout on): this launch also makes the keep-mask and zeroes
+    // the loss partial slots and the forward accumulator sets -- k_make_xbits' work (launch_forward_zero) without its launch
     XbitsJob xb{};
-    const bool head = (which & 16) && c.h.training && c.h.x_drop > 0.f;
-    if (head) {
+    const bool xbits = head && p.zero == ZERO_PRESPLIT;
+    if (xbits) {
         const mmvae_dims& dd = c.d;
         xb.nz = make_noise_dev(nz, c.h);
         xb.A = dd.A; xb.B = dd.B; xb.D = dd.D; xb.wpr = cdiv(dd.D, 32);
@@ -1743,45 +1743,35 @@ int launch_x3_planes(const Ctx& c, const float* params, int which, const mmvae_n
         xb.blocks = (int)imin64(2048, cdiv64((int64_t)dd.B * cdiv(xb.wpr, wpt), 256));
         xb.zero_p = c.ws + c.lay.fc11_part;
         xb.zero_n4 = (int)(c.fwd_zero_floats() / 4);
-        c.fwd_zeroed = true;
-        if (c.x_rows) {
+        if (p.rowmap) {
             xb.rows = c.x_rows; xb.map = reinterpret_cast<unsigned*>(c.ws + c.lay.rowmap);
             xb.rows_ld = c.x_ld; xb.n_rows = c.x_nrows;
-            c.rowmap_ready = true;
         }
     }
-    if (!x3) which &= 9;   // bf16 configuration: only the chain kernels take planes
     const mmvae_dims& d = c.d;
     SplitJob jobs[24];
     int n = 0;
-    if (which & 1 && x3) {
+    // (narrow, the bf16 configuration on bf16 storage: slice 0 of W1's planes IS bf16(W1) -- fc1 reads its narrow operand from
+    // it in sixteen-byte pieces of eight elements, like x, instead of fp32 rounded by every block tile (half the bytes) -- and
+    // slice 0 of [W11 | b11]'s planes is bf16(W11) for the fused fc11 kernel (the bias column meets a zero of d10))
+    if (head && (p.big == GEMM_X3 || p.narrow)) {
         jobs[n++] = plane_job(c, PL_W1, params + c.po.o[0], d.D, c.po.per_arm);
         jobs[n++] = plane_job(c, PL_W11, params + c.po.o[26], d.H, c.po.per_arm, params + c.po.o[27], c.po.per_arm);   // bias: column fc_dim
-    } else if ((which & 1) && bf16_narrow_planes(c)) {
-        // bf16 configuration on bf16 storage: slice 0 of W1's planes IS bf16(W1) -- fc1 reads its narrow operand from it in
-        // sixteen-byte pieces of eight elements, like x, instead of fp32 rounded by every block tile (half the bytes)
-        jobs[n++] = plane_job(c, PL_W1, params + c.po.o[0], d.D, c.po.per_arm);
-        // ... and slice 0 of [W11 | b11]'s planes is bf16(W11) for the fused fc11 kernel (the bias column meets a zero of d10)
-        jobs[n++] = plane_job(c, PL_W11, params + c.po.o[26], d.H, c.po.per_arm, params + c.po.o[27], c.po.per_arm);
     }
-    if (which & 9) {   // bit 3: the small layers alone (a backward pass that is its own call)
-        if (chain_x3_ok(c) && !c.small_planes) {   // the small layers' weights for the chain kernels: slot s = [N][K] of fc2..fc5, fc6..fc10
-            const int H = d.H, L = d.L, CS = d.C + d.S;
-            const int ti[9] = {2, 4, 6, 8, 16, 18, 20, 22, 24};                    // parameter tensor index of the weight
-            const int nn[9] = {H, H, H, L, L, H, H, H, H}, kk[9] = {H, H, H, H, CS, L, H, H, H};
-            unsigned short* base = reinterpret_cast<unsigned short*>(c.ws + c.lay.pl_small);
-            for (int s = 0; s < 9; ++s) {
-                jobs[n++] = SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, nn[s], kk[s], 128, 128, -1,
-                                     base + (int64_t)s * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 0};
-                // and [K][N] for the backward chain (its contraction runs over N)
-                jobs[n++] = SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, kk[s], nn[s], 128, 128, -1,
-                                     base + (int64_t)(9 + s) * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 1};
-            }
-            c.small_planes = true;
+    if (p.chain_planes) {   // the small layers' weights for the chain kernels: slot s = [N][K] of fc2..fc5, fc6..fc10
+        const int H = d.H, L = d.L, CS = d.C + d.S;
+        const int ti[9] = {2, 4, 6, 8, 16, 18, 20, 22, 24};                    // parameter tensor index of the weight
+        const int nn[9] = {H, H, H, L, L, H, H, H, H}, kk[9] = {H, H, H, H, CS, L, H, H, H};
+        unsigned short* base = reinterpret_cast<unsigned short*>(c.ws + c.lay.pl_small);
+        for (int s = 0; s < 9; ++s) {
+            jobs[n++] = SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, nn[s], kk[s], 128, 128, -1,
+                                 base + (int64_t)s * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 0};
+            // and [K][N] for the backward chain (its contraction runs over N)
+            jobs[n++] = SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, kk[s], nn[s], 128, 128, -1,
+                                 base + (int64_t)(9 + s) * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 1};
         }
     }
-    if ((which & 4) && !bn_apply_writes_planes(c)) jobs[n++] = plane_job(c, PL_DZ1, c.ws + c.lay.DZ[1], d.H, (int64_t)d.B * d.H);
-    return (n || head) ? launch_presplit(c.stream, d.A, jobs, n, head ? &xb : nullptr) : 0;
+    return launch_presplit(c.stream, d.A, jobs, n, xbits ? &xb : nullptr);
 }
 
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs) {
@@ -1795,15 +1785,15 @@ int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64
     g.b_arm = c.po.per_arm;
     g.M = d.B; g.N = d.H; g.K = d.D; g.KS = c.lay.sp.ks_fc1; g.A = d.A;
     g.so = SlabOut{c.ws + c.lay.fc1_slab, (int64_t)d.A * d.B * NP, (int64_t)d.B * NP, NP, d.B, d.H};
-    if (c.x_rows) {   // the batch as rows of the resident matrix (mmvae_train_step_rows): x is read through the row map
-        if (!c.rowmap_ready) { set_error("row-indexed batches need the fused step's head launch"); return MMVAE_E_UNSUPPORTED; }
+    const bool x3 = c.plan.big == GEMM_X3;
+    if (c.plan.rowmap) {   // the batch as rows of the resident matrix (mmvae_train_step_rows): x is read through the row map
         g.a.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); g.a.nrec = c.x_nrows * c.x_ld; g.a.map_n = d.B;
-        if (split3_gemms(c)) {
+        if (x3) {
             use_planes(c, g.b, PL_W1);
             hipLaunchKernelGGL((k_x3_gemm<false, false, 2, 1>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
         } else if (c.x16) {         // bf16 storage: x from its bf16 copy
             g.a.ptr = reinterpret_cast<const float*>(c.x16); g.a.src16 = 1;
-            if (bf16_narrow_planes(c)) {   // ... and W1 from slice 0 of its planes (launch_x3_planes): [128][rup(D, 32)] bf16, zero rows beyond H
+            if (c.plan.narrow) {   // ... and W1 from slice 0 of its planes (launch_x3_planes): [128][rup(D, 32)] bf16, zero rows beyond H
                 const PlaneGeom pg = plane_geom(c, PL_W1);
                 g.b.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.b.ld = pg.Cp; g.b.src16 = 1;
                 g.b_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;       // arm stride in FLOATS of the pointer arithmetic (planes: 2-byte elements)
@@ -1812,7 +1802,7 @@ int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64
                 hipLaunchKernelGGL((k_bf16_gemm<false, false, 1, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         } else
             hipLaunchKernelGGL((k_bf16_gemm<false, false, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    } else if (split3_gemms(c)) {   // (fc_dim <= 124: one tile wide, the two tiles of a block share the W1 tile)
+    } else if (x3) {   // (fc_dim <= 124: one tile wide, the two tiles of a block share the W1 tile)
         use_planes(c, g.b, PL_W1);
         hipLaunchKernelGGL((k_x3_gemm<false, false, 2>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
     } else
@@ -1828,9 +1818,9 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
     // forward for gradients without x_rec (the train step, mmvae_forward(need_grad) for backward): one fused kernel, and
     // the call for d(d10) (which & 2) has nothing left to do; with x_rec wanted two kernels
     const bool fused = need_grad && !x_rec;
-    if (split3_gemms(c)) {
+    if (c.plan.fc11 == FC11_X3) {
         // fp32x3: only the fused train-step kernel exists in this engine (fc_dim + 1 <= 112, 128 cells per block fit the
-        // loss-partial slots); everything else runs the fp32 matrix-instruction kernels (the caller falls through)
+        // loss-partial slots); everything else runs the fp32 matrix-instruction kernels (Plan::fc11)
         if (!(which & 1)) return 0;
         GemmArgs g{};
         g.a = kmajor(c.ws + L.Dk[4], d.H, d.B, d.H);
@@ -1840,8 +1830,7 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
         g.M = d.B; g.N = d.D; g.K = d.H; g.KS = NS; g.A = d.A; g.n11 = L.n11;
         g.fo = Fc11Out{params + c.po.o[27], x, c.ws + L.DZ11, nullptr, c.ws + L.fc11_part,
                        (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B, d.B, d.D, nullptr, 0};
-        if (c.x_rows) {
-            if (!c.rowmap_ready) { set_error("row-indexed batches need the fp32x3 engine's fused step"); return MMVAE_E_UNSUPPORTED; }
+        if (c.plan.rowmap) {
             g.fo.xmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap);
             g.fo.x_nrec = c.x_nrows * c.x_ld;
         }
@@ -1853,9 +1842,9 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
         return 0;
     }
     if (which & 1) {
-        hipError_t e = c.fwd_zeroed ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
+        hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
         if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
-        if ((int64_t)cdiv(d.B, BT) * NS > L.n11) { set_error("fc11 bf16: loss partial slots"); return MMVAE_E_LAUNCH; }
+        if (!fc11_slots_fit(L, d.B)) { set_error("fc11 bf16: loss partial slots"); return MMVAE_E_LAUNCH; }
         GemmArgs g{};
         g.a = kmajor(c.ws + L.Dk[4], d.H, d.B, d.H);          // d10 [B][H]
         g.a_arm = (int64_t)d.B * d.H;
@@ -1865,8 +1854,7 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
         g.M = d.B; g.N = d.D; g.K = d.H; g.KS = NS; g.A = d.A; g.n11 = L.n11;
         g.fo = Fc11Out{params + c.po.o[27], x, c.ws + L.DZ11, x_rec, c.ws + L.fc11_part,
                        (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B, d.B, d.D, nullptr, 0};
-        if (c.x_rows) {
-            if (!fused || !c.rowmap_ready) { set_error("row-indexed batches need the fused fc11 kernel of a training step"); return MMVAE_E_UNSUPPORTED; }
+        if (c.plan.rowmap) {
             g.fo.xmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap);
             g.fo.x_nrec = c.x_nrows * c.x_ld;
         }
@@ -1874,11 +1862,10 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
         g.fo_x_arm = xs;
         if (fused) {   // train step: d(d10) comes out of the same launch (which & 2 is then a no-op)
             g.so = SlabOut{c.ws + L.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
-            if (c.x16) {   // bf16 storage: x from its bf16 copy, dZ11 written as bf16 (dW11 below reads it that way)
+            if (c.plan.dz11_bf16) {   // bf16 storage: x from its bf16 copy, dZ11 written as bf16 (dW11 below reads it that way)
                 g.fo.x = reinterpret_cast<const float*>(c.x16);
                 g.fo_arm = (int64_t)d.B * d.D / 2;          // (arm stride of dZ11 in floats: B * D two-byte elements)
-                c.dz16 = true;
-                if (bf16_narrow_planes(c) && KT == 64) {   // W11 from slice 0 of its planes (launch_x3_planes): [rup(D, 128)][128] bf16
+                if (c.plan.narrow && KT == 64) {   // W11 from slice 0 of its planes (launch_x3_planes): [rup(D, 128)][128] bf16
                     const PlaneGeom pg = plane_geom(c, PL_W11);
                     g.b = kmajor(reinterpret_cast<const float*>(c.ws + pg.ws_off), pg.Cp, pg.Rp, pg.Cp);
                     g.b.src16 = 1;
@@ -1912,6 +1899,7 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     const bool use_mask = c.h.training && c.h.x_drop > 0.f;
+    const bool x3 = c.plan.big == GEMM_X3;
     if (which & 1) {   // dW1[h][d] = sum_b dZ1[b][h] x~[b][d]
         GemmArgs g{};
         g.a = kminor(c.ws + L.DZ[1], d.H, d.H, d.B);
@@ -1921,15 +1909,14 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
         if (use_mask) { g.b.bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits); g.b.wpr = cdiv(d.D, 32); g.b_bits_arm = (int64_t)d.B * g.b.wpr; }
         g.M = d.H; g.N = d.D; g.K = d.B; g.KS = L.sp.ks_dw; g.A = d.A;
         g.so = SlabOut{c.ws + L.dw1_slab, (int64_t)d.A * d.H * d.D, (int64_t)d.H * d.D, d.D, d.H, d.D};
-        if (c.x_rows) {
-            if (!c.rowmap_ready) { set_error("row-indexed batches need the fused step's head launch"); return MMVAE_E_UNSUPPORTED; }
+        if (c.plan.rowmap) {
             g.b.rowmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap); g.b.nrec = c.x_nrows * c.x_ld; g.b.map_n = d.B;
-            if (split3_gemms(c)) {
+            if (x3) {
                 use_planes(c, g.a, PL_DZ1);
                 hipLaunchKernelGGL((k_x3_gemm<true, true, 1, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
             } else if (c.x16) {
                 g.b.ptr = reinterpret_cast<const float*>(c.x16); g.b.src16 = 1;
-                if (bf16_narrow_planes(c) && bn_apply_writes_planes(c)) {   // dZ1 from slice 0 of its planes (k_bn_bwd_apply): [rup(B, 256)][128] bf16
+                if (c.plan.narrow && c.plan.dz1_in_apply) {   // dZ1 from slice 0 of its planes (k_bn_bwd_apply): [rup(B, 256)][128] bf16
                     const PlaneGeom pg = plane_geom(c, PL_DZ1);
                     g.a.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.a.ld = pg.Cp; g.a.src16 = 1;
                     g.a_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;
@@ -1938,7 +1925,7 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
                     hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
             } else
                 hipLaunchKernelGGL((k_bf16_gemm<true, true, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        } else if (split3_gemms(c)) {   // one tile high: the two tiles of a block share the dZ1 tile
+        } else if (x3) {   // one tile high: the two tiles of a block share the dZ1 tile
             use_planes(c, g.a, PL_DZ1);
             hipLaunchKernelGGL((k_x3_gemm<true, true, 1>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
         } else
@@ -1954,10 +1941,10 @@ int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
         g.b_arm = (int64_t)d.B * d.H;
         g.M = d.D; g.N = d.H + 1; g.K = d.B; g.KS = L.sp.ks_dw11; g.A = d.A;
         g.so = SlabOut{c.ws + L.dw11_slab, (int64_t)d.A * d.D * DW11_LD, (int64_t)d.D * DW11_LD, DW11_LD, d.D, d.H + 1};
-        if (split3_gemms(c)) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
+        if (x3) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
             use_planes(c, g.b, PL_D10);
             hipLaunchKernelGGL((k_x3_gemm<true, true, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-        } else if (c.dz16) {        // bf16 storage: the fused fc11 kernel of this step wrote dZ11 as bf16
+        } else if (c.plan.dz11_bf16) {   // bf16 storage: the fused fc11 kernel of this step wrote dZ11 as bf16
             g.a.src16 = 1;
             g.a_arm = (int64_t)d.B * d.D / 2;
             hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 1>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);

@@ -618,7 +618,7 @@ int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t
     const float coef = am1 / (float)d.B;
     const int NS = c.lay.sp.ns_fc11;
     dim3 grid(c.lay.nblk64, NS, d.A);
-    hipError_t e = c.fwd_zeroed ? hipSuccess : hipMemsetAsync(c.ws + c.lay.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * c.lay.n11, c.stream);
+    hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + c.lay.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * c.lay.n11, c.stream);
     if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
     hipLaunchKernelGGL(k_fc11_fused, grid, dim3(256), shm, c.stream, c.ws + c.lay.Dk[4], params, c.po.per_arm,
                        c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + c.lay.DZ11, c.ws + c.lay.GD10_slab,
@@ -695,7 +695,7 @@ int launch_dw_small(const Ctx& c, int which) {
         tiles = max(tiles, cdiv(hd[i].Mv, 128) * cdiv(hd[i].Nv + 1, 128));
     }
     if (nsel == 0) return 0;
-    if (bf16_gemms(c)) {        // fp32x3 engine -- and the bf16 configuration, whose small layers stay fp32-grade: the same
+    if (c.plan.small_x3) {      // fp32x3 engine -- and the bf16 configuration, whose small layers stay fp32-grade: the same
                                 // products as pairs of 128 x 128 tiles of exact slice products on the bf16 matrix pipe
         bool fits = true;
         for (int i = 0; i < nsel; ++i) fits = fits && ts.d[i].Mv <= 128 && ts.d[i].Nv + ts.d[i].q_ones <= 128 && !ts.d[i].q_xmask;

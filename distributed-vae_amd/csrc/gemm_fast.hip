@@ -1278,27 +1278,10 @@ __global__ __launch_bounds__(256, 2) void k_gd10_v3(const float* __restrict__ dz
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool fast_path_ok(const Ctx& c, const float* params, const float* x, int64_t xs) {
-    const mmvae_dims& d = c.d;
-    return (d.D & 3) == 0 && (d.H & 3) == 0 && al16(params) && al16(x) && (xs & 3) == 0 && d.H >= 4 &&
-           (int64_t)d.B * d.D < ((int64_t)1 << 30);
-}
-
-// true when forward used the fast fc11 kernels (d(d10) slab count ks_gd10) rather than the general fused kernel (ns_fc11)
-bool fc11_split_path(const Ctx& c, const float* params, const float* x, int64_t xs) {
-    return fast_path_ok(c, params, x, xs);
-}
-
-int launch_forward_zero(const Ctx& c, bool with_xbits, const mmvae_noise* nz) {
-    if (with_xbits && c.h.training && c.h.x_drop > 0.f) {
-        c.fwd_zeroed = true;   // k_make_xbits does it
-        return launch_make_xbits(c, nz);
-    }
+int launch_forward_zero(const Ctx& c, const mmvae_noise* nz) {
+    if (c.plan.zero == ZERO_XBITS) return launch_make_xbits(c, nz);   // k_make_xbits does it
     hipError_t e = hipMemsetAsync(c.ws + c.lay.fc11_part, 0, sizeof(float) * (size_t)c.fwd_zero_floats(), c.stream);
     if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
-    c.fwd_zeroed = true;
     return 0;
 }
 
@@ -1312,13 +1295,13 @@ int launch_make_xbits(const Ctx& c, const mmvae_noise* nz) {
     const int blocks = (int)imin64(4096, cdiv64(n, 256));
     hipLaunchKernelGGL(k_make_xbits, dim3(blocks), dim3(256), 0, c.stream, nd, d.A, d.B, d.D, wpr,
                        reinterpret_cast<uint32_t*>(c.ws + c.lay.xbits), c.ws + c.lay.fc11_part,
-                       c.fwd_zeroed ? (int)(c.fwd_zero_floats() / 4) : 0);
+                       c.plan.zero == ZERO_XBITS ? (int)(c.fwd_zero_floats() / 4) : 0);
     HIP_LAUNCH_CHECK("k_make_xbits");
     return 0;
 }
 
 int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64_t xs) {
-    if (bf16_gemms(c)) return launch_fc1_fwd_bf16(c, params, x, xs);
+    if (c.plan.big == GEMM_BF16 || c.plan.big == GEMM_X3) return launch_fc1_fwd_bf16(c, params, x, xs);
     const mmvae_dims& d = c.d;
     const bool use_mask = c.h.training && c.h.x_drop > 0.f;
     const int KS = c.lay.sp.ks_fc1;
@@ -1344,23 +1327,18 @@ int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64
     return 0;
 }
 
-int launch_fc11_fast(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad,
-                     int which /*bit0: x_rec/loss/dZ11 kernel, bit1: d(d10) GEMM*/) {
-    // fp32x3: the fused train-step form (forward for gradients, no x_rec, fc_dim + 1 <= 112) has its own kernel; the other
-    // forms of fc11 (x_rec wanted, forward only) run the fp32 matrix-instruction kernels below
-    if (split3_gemms(c) && need_grad && !x_rec && c.d.H + 1 <= 112 && (int64_t)cdiv(c.d.B, 128) * c.lay.sp.ks_gd10 <= c.lay.n11)
-        return launch_fc11_bf16(c, params, x, xs, x_rec, need_grad, which);
-    if (c.h.gemm_bf16 == 1 && bf16_gemms(c)) return launch_fc11_bf16(c, params, x, xs, x_rec, need_grad, which);
+int launch_fc11(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad,
+                int which /*bit0: x_rec/loss/dZ11 kernel, bit1: d(d10) GEMM*/) {
+    if (c.plan.fc11 == FC11_GENERAL) return launch_fc11_fused(c, params, x, xs, x_rec, need_grad);
+    if (c.plan.fc11 == FC11_BF16 || c.plan.fc11 == FC11_X3) return launch_fc11_bf16(c, params, x, xs, x_rec, need_grad, which);
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     const int ldk = rup(d.H, 8) + 4;
     const float coef = (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B;
     const int NS = L.sp.ns_fc11;
-    // train step at fc_dim 100: d(d10) is folded into the fc11 kernel (k_fc11_zg), whose gene split count equals the
-    // d(d10) kernel's so that the decoder backward sums the same number of slabs whichever forward ran
-    const bool use_zg = need_grad && !x_rec && d.H == 100 && (int64_t)cdiv(d.B, 256) * L.sp.ks_gd10 <= L.n11;
+    const bool use_zg = c.plan.fc11 == FC11_ZG;
     if ((which & 1) && use_zg) {
-        hipError_t e = c.fwd_zeroed ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
+        hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
         if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
         const size_t shm = (size_t)(3 * 64 * ldk + 8 * 32 * ZG_LD + 16) * sizeof(float);
         // (152 KB of dynamic LDS: this runtime takes it without the hipFuncSetAttribute opt-in, and the library keeps no
@@ -1373,7 +1351,7 @@ int launch_fc11_fast(const Ctx& c, const float* params, const float* x, int64_t 
     if (use_zg) return 0;
     if (which & 1) {
         // loss partials: the launch below fills a subset of the reserved slots
-        hipError_t e = c.fwd_zeroed ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
+        hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
         if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
         const int ntall = cdiv(d.D, 64);
         const int kgv = rup(d.H, 8) / 8;
@@ -1418,7 +1396,7 @@ int launch_fc11_fast(const Ctx& c, const float* params, const float* x, int64_t 
 }
 
 int launch_dw_big_fast(const Ctx& c, const float* x, int64_t xs, int which) {
-    if (bf16_gemms(c)) return launch_dw_big_bf16(c, x, xs, which);
+    if (c.plan.big == GEMM_BF16 || c.plan.big == GEMM_X3) return launch_dw_big_bf16(c, x, xs, which);
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     const bool use_mask = c.h.training && c.h.x_drop > 0.f;

@@ -410,7 +410,7 @@ __global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const Nois
 // instead of two for one is a quarter less element-wise work, and a reduction step now counts for two cells.
 // 8 waves x 2 halves x 3 cells = the same LAT_ROWS cells per workgroup and the same partial layouts as k_lat_fwd.
 // ---------------------------------------------------------------------------------------------
-constexpr int LH_NW = 8, LH_CPL = 3, LH_NR = LAT_ROWS / (LH_NW * 2);
+constexpr int LH_NW = 8, LH_NR = LAT_ROWS / (LH_NW * 2);   // (LH_CPL: common.hpp)
 static_assert(LH_NR * LH_NW * 2 == LAT_ROWS, "LAT_ROWS must be a multiple of 16");
 template <typename Op>
 __device__ __forceinline__ float half_allreduce(float v, Op op) {   // wave_allreduce without the 32-lane swap
@@ -1463,7 +1463,7 @@ int launch_lat_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, flo
     a.labels = labels;
     NoiseDev nd = make_noise_dev(nz, c.h);
     const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
-    if (c.d.C <= 32 * LH_CPL && c.d.L <= 32 && 2 * c.d.S <= 32) {
+    if (c.plan.lat_half) {
         launch_k(c, k_lat_fwd_h, dim3(c.lay.nblkl, c.d.A), dim3(64 * LH_NW), shm, a, nd, params, c.ws, bn_running, nbt);
         HIP_LAUNCH_CHECK("k_lat_fwd_h");
         return 0;
@@ -1522,7 +1522,7 @@ int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params) {
     LatArgs a = make_lat_args(c);
     NoiseDev nd = make_noise_dev(nz, c.h);
     const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
-    if (c.d.C <= 32 * LH_CPL && c.d.L <= 32 && 2 * c.d.S <= 32) {
+    if (c.plan.lat_half) {
         hipLaunchKernelGGL(k_lat_bwd_h, dim3(cdiv(c.d.B, LAT_ROWS_BWD), c.d.A), dim3(64 * LBH_NW), shm, c.stream, a, nd, params, c.ws);
         HIP_LAUNCH_CHECK("k_lat_bwd_h");
         return 0;
@@ -1533,15 +1533,15 @@ int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params) {
 }
 
 // which: bit 0 = fc11.weight / fc11.bias (final as soon as the dW11 GEMM is), bit 1 = everything else
-int launch_reduce_grads(const Ctx& c, float* grads, float gscale, const AdamHost* ah, bool dw11_fast, int which) {
+int launch_reduce_grads(const Ctx& c, float* grads, float gscale, const AdamHost* ah, int which) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     const int A = d.A, H = d.H, D = d.D, Ld = d.L, C = d.C, S = d.S;
     RedDescs ds{};
     int n = 0;
     const float xscale = (c.h.training && c.h.x_drop > 0.f) ? 1.f / (1.f - c.h.x_drop) : 1.f;
-    // big: fc1.w, fc11.w, fc11.b (the general path's dW11 uses ks_dw slabs, the fast path's its own count)
-    const int ks11 = dw11_fast ? L.sp.ks_dw11 : L.sp.ks_dw;
+    // big: fc1.w, fc11.w, fc11.b
+    const int ks11 = c.plan.dw11_slabs;
     ds.d[n++] = RedDesc{c.ws + L.dw1_slab, (int64_t)A * H * D, (int64_t)H * D, D, 0, H, D, c.po.o[0], D, gscale * xscale, L.sp.ks_dw};
     ds.d[n++] = RedDesc{c.ws + L.dw11_slab, (int64_t)A * D * DW11_LD, (int64_t)D * DW11_LD, DW11_LD, 0, D, H, c.po.o[26], H, gscale, ks11};
     ds.d[n++] = RedDesc{c.ws + L.dw11_slab, (int64_t)A * D * DW11_LD, (int64_t)D * DW11_LD, DW11_LD, H, D, 1, c.po.o[27], 1, gscale, ks11};

@@ -12,7 +12,7 @@ enum {
     MMVAE_TUNE_AUG_TILE = 3,       // augmenter GEMMs: fp32 matrix instruction: tile 11 12 21 22 (1 = 64, 2 = 128); planes x planes engine:
                                    // 1 / 2 / 3 = 256 x 256 / 256 x 128 / 128 x 128 (+ 10 KS: K split)
     MMVAE_TUNE_COUPLE_SIDE = 13,   // fused step, where the coupling terms run: 0 = as a role of the decoder chain's launch from four arms up
-                                   // and on the side stream below (chain.hip dec_couple_ok), 1 = side stream always, 3 = role always
+                                   // and on the side stream below (api.hip make_plan), 1 = side stream always, 3 = role always
     // 17 MMVAE_TUNE_ENGINE: public (mmvae.h)
     MMVAE_TUNE_BN_PARTIALS = 19,   // BatchNorm batch sums through per-workgroup partial arrays instead of the accumulators
     MMVAE_TUNE_CHAIN_FP32 = 21,    // fp32x3 engine: the chain kernels' own GEMMs stay on the fp32 matrix instruction
