@@ -166,6 +166,15 @@ def lib():
     L.mmvae_tp_planes_bytes.restype = C.c_size_t
     L.mmvae_tp_planes.argtypes = [vp, i64, i64, i32, i32, vp, vp]
     L.mmvae_augment_rows.argtypes = [C.POINTER(AugDims), vp, vp, i64, i32, vp, vp, vp, f32, vp, C.c_size_t, vp, vp, i32, ex, vp]
+    L.mmvae_decode_workspace_bytes.argtypes = [C.POINTER(Dims), ex]
+    L.mmvae_decode_workspace_bytes.restype = C.c_size_t
+    L.mmvae_decode.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, i64, vp, i64, vp, vp, C.c_size_t, ex, vp]
+    L.mmvae_decode.restype = C.c_int
+    L.mmvae_state_changes_workspace_bytes.argtypes = [C.POINTER(Dims), i32, ex]
+    L.mmvae_state_changes_workspace_bytes.restype = C.c_size_t
+    L.mmvae_state_changes.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, i32, i32, vp, vp,
+                                      C.c_size_t, ex, vp]
+    L.mmvae_state_changes.restype = C.c_int
     for fn in ("mmvae_check_dims", "mmvae_param_layout", "mmvae_splits", "mmvae_forward", "mmvae_loss",
                "mmvae_backward", "mmvae_adam_step", "mmvae_train_step", "mmvae_dump_noise", "mmvae_debug_stage",
                "mmvae_eval_classify", "mmvae_classify", "mmvae_confmat_accumulate", "mmvae_consensus", "mmvae_aug_pack",
@@ -383,6 +392,55 @@ class Engine:
         check(lib().mmvae_dump_noise(C.byref(self.dims), C.byref(hyper), C.byref(noise), _ptr(xm), _ptr(ug), _ptr(us),
                                      _ptr(sm), self._s()), "mmvae_dump_noise")
         return {"x_mask": xm, "u_gumbel": ug, "u_state": us, "s_mask": sm}
+
+
+class DecodeEngine:
+    """Workspace and execution context of mmvae_decode (rows = dims.B) or, with ``n_samp``, of mmvae_state_changes
+    (dims.B cells, n_samp samples each).  No side stream: both calls run on torch's current stream of the device."""
+
+    def __init__(self, A, B, D, H, L, Cc, S, device, gemm_engine: int = 0, n_samp: Optional[int] = None,
+                 ex: Optional[Exec] = None):
+        self.dims = Dims(A, B, D, H, L, Cc, S)
+        self.gemm_engine = gemm_engine
+        self.n_samp = n_samp
+        check(lib().mmvae_check_dims(C.byref(self.dims)), "mmvae_check_dims")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NativeError("the HIP engine needs a GPU device (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.ex = exec_from_env(gemm_engine)
+        if ex is not None:
+            for i in range(6):
+                self.ex.split[i] = ex.split[i]
+            for i in range(N_TUNE):
+                self.ex.tune[i] = ex.tune[i]
+        if n_samp is None:
+            self.ws_bytes = int(lib().mmvae_decode_workspace_bytes(C.byref(self.dims), C.byref(self.ex)))
+        else:
+            self.ws_bytes = int(lib().mmvae_state_changes_workspace_bytes(C.byref(self.dims), int(n_samp), C.byref(self.ex)))
+        if self.ws_bytes == 0:
+            raise NativeError("decode workspace: unsupported dims / n_samp")
+        with torch.cuda.device(self.device):
+            self.ws = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=self.device)
+
+    def ws_view(self, name: str, width: int) -> torch.Tensor:
+        """A decode's region (mmvae_ws_offset of these dims): e.g. "zin", "d6" .. "d10" hold the decoder's activations."""
+        off = int(lib().mmvae_ws_offset(C.byref(self.dims), C.byref(self.ex), WS_IDS[name]))
+        d = self.dims
+        return self.ws[off: off + d.A * d.B * width].view(d.A, d.B, width)
+
+    def decode(self, hyper: Hyper, params, c, c_arm_stride, s, s_arm_stride, x_rec):
+        check(lib().mmvae_decode(C.byref(self.dims), C.byref(hyper), _ptr(params), _ptr(c), int(c_arm_stride), _ptr(s),
+                                 int(s_arm_stride), _ptr(x_rec), _ptr(self.ws), self.ws_bytes, C.byref(self.ex),
+                                 _stream(self.device)), "mmvae_decode")
+        return x_rec
+
+    def state_changes(self, hyper: Hyper, noise: Noise, params, bn_running, x, d_s, x_rec):
+        check(lib().mmvae_state_changes(C.byref(self.dims), C.byref(hyper), C.byref(noise), _ptr(params), _ptr(bn_running),
+                                        _ptr(x), int(d_s), int(self.n_samp), _ptr(x_rec), _ptr(self.ws), self.ws_bytes,
+                                        C.byref(self.ex), _stream(self.device)), "mmvae_state_changes")
+        return x_rec
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, decoupled=False):

@@ -286,7 +286,8 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
     Plan& p = c.plan;
     p = Plan{};
     p.kind = kind;
-    const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS, fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY;
+    const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS, fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY ||
+                                                                 kind == CALL_TRAVERSE;
     const bool dropout = h.training && h.x_drop > 0.f, side = c.side() != nullptr;
     p.fast = fast_dims(d) && al16(params) && al16(x) && (xs & 3) == 0 && d.H >= 4 && (int64_t)d.B * d.D < ((int64_t)1 << 30);
     // engines of the five D x H products (mmvae_hyper.gemm_bf16: 1 bf16 operands, 2 fp32x3)
@@ -343,6 +344,17 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
     // a barrier packet of its own, 6 - 7 us of idle main stream (round 3: 686 -> 681 us per step)
     p.lat_fork_rides = p.couple == COUPLE_SIDE && p.lat_half;
     p.fc11_fork_rides = p.loss_on_side && (p.fc11 == FC11_X3 || p.fc11 == FC11_BF16);
+    if (kind == CALL_DECODE) {
+        // decode (`x` is x_rec, which the fast kernels store sixteen bytes at a time): the decoder chain as in a forward pass,
+        // then fc11 for x_rec alone -- on the slice planes (fp32x3 within k_x3_fc11g's 112 columns, bf16), else on the fp32
+        // matrix-instruction kernels in their output-only form.  Its planes come from one k_presplit launch of their own.
+        if (!p.fast) p.fc11 = FC11_GENERAL;
+        else if (p.big == GEMM_X3 && x3_fc11_fits(d)) p.fc11 = FC11_OUT_X3;
+        else if (p.big == GEMM_BF16) p.fc11 = FC11_OUT_BF16;
+        else p.fc11 = FC11_ZT;
+        p.d10_planes = p.fc11 == FC11_OUT_X3 || p.fc11 == FC11_OUT_BF16;
+        p.dec_planes = p.d10_planes || p.chain_planes;
+    }
 }
 
 // Train step with a side stream: the coupling kernel needs only the latent block's outputs and the loss scalars only the
@@ -405,7 +417,7 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
     }
     if ((rc = launch_with_fork(c, p.lat_fork_rides, EV_LAT, [&] { return launch_lat_fwd(c, nz, params, bn_running, nbt, labels); })))
         return rc;
-    if (p.kind == CALL_CLASSIFY) return 0;   // evaluation labels need c only: no decoder, no fc11
+    if (p.kind == CALL_CLASSIFY || p.kind == CALL_TRAVERSE) return 0;   // labels / the traversal's encoder: no decoder, no fc11
     Ctx cs = c;
     cs.stream = c.side();
     if (p.couple == COUPLE_SIDE) {
@@ -421,6 +433,16 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
     if (p.couple == COUPLE_SIDE && !p.loss_on_side && (rc = record_on_side(c, EV_COUPLE))) return rc;
     // loss_on_side: dW11 starts as soon as fc11 has finished -- EV_FORK rides on the fused fc11 kernel
     return launch_with_fork(c, p.fc11_fork_rides, EV_FORK, [&] { return launch_fc11(c, params, x, xs, x_rec, need_grad); });
+}
+
+// decode and the traversal's decoder half: ZIN from `zb`, the decoder chain (eval mode: it has no BatchNorm), fc11 for x_rec
+static int do_decode(const Ctx& c, const float* params, ZinBuild zb, const mmvae_noise* nz, float* x_rec) {
+    int rc;
+    if (c.plan.dec_planes && (rc = launch_dec_planes(c, params))) return rc;
+    zb.zin = c.ws + c.lay.ZIN;
+    if ((rc = launch_zin_build(zb, nz, c.h, c.stream))) return rc;
+    if ((rc = launch_chain_fwd_dec(c, params))) return rc;
+    return launch_fc11_out(c, params, x_rec);
 }
 
 static int do_loss(const Ctx& c, float* loss_out) {
@@ -683,6 +705,89 @@ int mmvae_eval_classify(const mmvae_dims* d, const mmvae_hyper* h, const float* 
         return rc;
     if (counts) return launch_confmat(labels, d->A, d->B, d->C, counts, c.stream);
     return 0;
+}
+
+// ---- decode / state traversal: every argument is checked before the first launch
+static int check_decode_hyper(const mmvae_hyper* h) {
+    if (!h) { set_error("hyper is null"); return MMVAE_E_BADARG; }
+    if (int rc = check_gemm_engine(h->gemm_bf16)) return rc;
+    return 0;
+}
+
+size_t mmvae_decode_workspace_bytes(const mmvae_dims* d, const mmvae_exec* ex) { return mmvae_workspace_bytes(d, ex); }
+
+int mmvae_decode(const mmvae_dims* d, const mmvae_hyper* h, const float* params, const float* c, int64_t c_arm_stride,
+                 const float* s, int64_t s_arm_stride, float* x_rec, void* ws, size_t ws_bytes, mmvae_exec* ex, void* stream) {
+    if (int rc = check_dims(d)) return rc;
+    if (int rc = check_decode_hyper(h)) return rc;
+    if (!params || !c || !s || !x_rec) { set_error("decode: null params / c / s / x_rec"); return MMVAE_E_BADARG; }
+    if (c_arm_stride < 0 || s_arm_stride < 0) { set_error("decode: negative arm stride"); return MMVAE_E_BADARG; }
+    // the decoder has no BatchNorm: training mode differs from eval mode only by state dropout, which decode does not offer
+    if (h->training != 0 && !(h->training == 1 && h->s_drop == 0.f)) {
+        set_error("decode: state dropout (training mode with s_drop > 0) is not supported");
+        return MMVAE_E_UNSUPPORTED;
+    }
+    mmvae_hyper he = *h;
+    he.training = 0;
+    Ctx cx;
+    if (int rc = make_ctx(cx, d, &he, ws, ws_bytes, ex, stream)) return rc;
+    make_plan(cx, CALL_DECODE, params, x_rec, 0);
+    ZinBuild zb{};
+    zb.A = d->A; zb.R = d->B; zb.C = d->C; zb.S = d->S; zb.L = d->L;
+    zb.c = c; zb.c_arm = c_arm_stride; zb.s = s; zb.s_arm = s_arm_stride;
+    return do_decode(cx, params, zb, nullptr, x_rec);
+}
+
+size_t mmvae_state_changes_workspace_bytes(const mmvae_dims* d, int n_samp, const mmvae_exec* ex) {
+    if (check_dims(d) || n_samp < 1 || (int64_t)n_samp * d->B > INT32_MAX) return 0;
+    mmvae_dims dd = *d;
+    dd.B = n_samp * d->B;
+    return mmvae_workspace_bytes(d, ex) + mmvae_workspace_bytes(&dd, ex);
+}
+
+int mmvae_state_changes(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, const float* params,
+                        const float* bn_running, const float* x, int d_s, int n_samp, float* x_rec, void* ws, size_t ws_bytes,
+                        mmvae_exec* ex, void* stream) {
+    if (int rc = check_dims(d)) return rc;
+    if (int rc = check_decode_hyper(h)) return rc;
+    if (!nz || !params || !bn_running || !x || !x_rec) {
+        set_error("state_changes: null noise / params / bn_running / x / x_rec");
+        return MMVAE_E_BADARG;
+    }
+    if (d_s < 0 || d_s >= d->S) { set_error("state_changes: d_s = %d outside [0, %d)", d_s, d->S); return MMVAE_E_BADARG; }
+    if (n_samp < 1) { set_error("state_changes: n_samp = %d < 1", n_samp); return MMVAE_E_BADARG; }
+    if (nz->mode != 0 && nz->mode != 1) { set_error("noise mode must be 0 (explicit) or 1 (philox)"); return MMVAE_E_BADARG; }
+    if (nz->mode == 0 && !nz->u_state) { set_error("state_changes: explicit noise needs u_state [A, n_samp, B]"); return MMVAE_E_BADARG; }
+    if (h->training) { set_error("state_changes needs eval mode (training = 0): the encoder reads the running statistics"); return MMVAE_E_UNSUPPORTED; }
+    if ((int64_t)n_samp * d->B > INT32_MAX) { set_error("state_changes: n_samp * B beyond 2^31 rows"); return MMVAE_E_UNSUPPORTED; }
+    mmvae_dims dd = *d;
+    dd.B = n_samp * d->B;
+    const size_t enc_bytes = mmvae_workspace_bytes(d, ex), dec_bytes = mmvae_workspace_bytes(&dd, ex);
+    if (!ws) { set_error("null workspace"); return MMVAE_E_BADARG; }
+    if (ws_bytes < enc_bytes + dec_bytes) {
+        set_error("workspace too small: need %zu bytes, got %zu", enc_bytes + dec_bytes, ws_bytes);
+        return MMVAE_E_WORKSPACE;
+    }
+    // encoder + latent block of forward(eval=True): c_smp is the hard straight-through sample of softmax(c_prob / tau) (no
+    // category mask, no Gumbel noise: temp has no effect), mu and y = [x_low | c] stay in the first part of the workspace
+    mmvae_hyper he = *h;
+    he.training = 0; he.eval_flag = 1; he.hard = 1;
+    for (int i = 0; i < 4; ++i) he.cat_mask[i] = 0;
+    Ctx ce, cd;
+    if (int rc = make_ctx(ce, d, &he, ws, enc_bytes, ex, stream)) return rc;
+    if (int rc = make_ctx(cd, &dd, &he, reinterpret_cast<char*>(ws) + enc_bytes, dec_bytes, ex, stream)) return rc;
+    make_plan(ce, CALL_TRAVERSE, params, x, 0);
+    make_plan(cd, CALL_DECODE, params, x_rec, 0);
+    mmvae_noise nzp{};   // (the latent kernel's own state sample is not used: Philox stream of seed 0, as eval_classify)
+    nzp.mode = 1;
+    int rc;
+    if ((rc = do_forward(ce, &nzp, params, const_cast<float*>(bn_running), nullptr, x, 0, nullptr, 0))) return rc;
+    ZinBuild zb{};
+    zb.A = d->A; zb.R = dd.B; zb.C = d->C; zb.S = d->S; zb.L = d->L;
+    zb.enc_ws = ce.ws; zb.csmp = ce.lay.CSMP; zb.y = ce.lay.Y; zb.mu = ce.lay.MU; zb.B = d->B; zb.d_s = d_s;
+    zb.params = params; zb.per_arm = ce.po.per_arm; zb.o_wsig = ce.po.o[13]; zb.o_bsig = ce.po.o[15];
+    zb.u = nz->mode == 0 ? nz->u_state : nullptr;
+    return do_decode(cd, params, zb, nz, x_rec);
 }
 
 int mmvae_classify(const float* c_probs, int64_t n_cells, int C, int32_t* labels, void* stream) {

@@ -732,11 +732,13 @@ inline bool fc11_slots_fit(const Layout& L, int B) { return (int64_t)cdiv(B, 128
 
 // Per-call plan: which kernels a call runs, on which stream, and which launch writes what for whom.  make_plan (api.hip)
 // builds it once per entry point; the launchers and drivers read it and decide nothing themselves.
-enum CallKind { CALL_STEP, CALL_STEP_ROWS, CALL_FORWARD, CALL_BACKWARD, CALL_LOSS, CALL_CLASSIFY, CALL_REPLAY /*debug stage*/ };
+enum CallKind { CALL_STEP, CALL_STEP_ROWS, CALL_FORWARD, CALL_BACKWARD, CALL_LOSS, CALL_CLASSIFY, CALL_REPLAY /*debug stage*/,
+                CALL_DECODE /*mmvae_decode, and the decoder half of mmvae_state_changes*/, CALL_TRAVERSE /*its encoder half*/ };
 // fc1, dW1, dW11: gemm_big.hip, fp32 matrix instruction (gemm_fast.hip), k_bf16_* / k_x3_* (gemm_bf16.hip)
 enum GemmFamily { GEMM_GENERAL, GEMM_FP32, GEMM_BF16, GEMM_X3 };
-// fc11 + d(d10): k_fc11_fused, k_fc11_zg (d(d10) folded in), k_fc11_zt + k_gd10_*, k_bf16_fc11* (+ k_bf16_gemm), k_x3_fc11g
-enum Fc11Family { FC11_GENERAL, FC11_ZG, FC11_ZT, FC11_BF16, FC11_X3 };
+// fc11 + d(d10): k_fc11_fused, k_fc11_zg (d(d10) folded in), k_fc11_zt + k_gd10_*, k_bf16_fc11* (+ k_bf16_gemm), k_x3_fc11g;
+// decode (x_rec only: no x, no loss, no dZ11): k_fc11_fused_out (GENERAL), k_fc11_zt_out (ZT), k_fc11_out<1> / <3>
+enum Fc11Family { FC11_GENERAL, FC11_ZG, FC11_ZT, FC11_BF16, FC11_X3, FC11_OUT_BF16, FC11_OUT_X3 };
 // the launch that zeroes the loss partial slots and the forward accumulator sets at the start of a forward pass (none:
 // eval mode or a replayed stage -- the fc11 launchers then zero their slots themselves)
 enum FwdZero { ZERO_NONE, ZERO_MEMSET, ZERO_XBITS /*k_make_xbits*/, ZERO_PRESPLIT /*the head k_presplit launch*/ };
@@ -757,6 +759,7 @@ struct Plan {
     bool bwd_small_planes;  //   k_presplit at the head of a backward call of its own (small layers),
     bool d10_planes;        //   the decoder chain ([d10 | 1]),
     bool dz1_in_apply;      //   k_bn_bwd_apply (dZ1)
+    bool dec_planes;        //   decode: k_presplit with the decoder's weights only (fc6..fc10 slots, [W11 | b11])
     FwdZero zero;
     bool rowmap;            // the batch is read through the row map (mmvae_train_step_rows; the head launch builds it)
     bool dz11_bf16;         // the fused fc11 kernel writes dZ11 as bf16 and dW11 reads it so (bf16 storage)
@@ -876,6 +879,24 @@ int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_n
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs);
 int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which);
 int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which);
+// decode (Plan::fc11 of a CALL_DECODE plan): x_rec = relu([d10 | 1] [W11 | b11]^T) and nothing else -- no x, no loss, no dZ11
+int launch_fc11_out(const Ctx& c, const float* params, float* x_rec);            // (gemm_fast.hip: picks the family)
+int launch_fc11_fused_out(const Ctx& c, const float* params, float* x_rec);      // gemm_big.hip
+int launch_fc11_out_bf16(const Ctx& c, float* x_rec);                            // gemm_bf16.hip, from the slice planes
+int launch_dec_planes(const Ctx& c, const float* params);                        // Plan::dec_planes
+// the decoder input rows [c | s] (ZIN of the decoder's workspace): decode packs the caller's c and s; the traversal
+// (mmvae_state_changes) builds n_samp rows per cell from the encoder's workspace
+struct ZinBuild {
+    int A, R, C, S, L;            // arms, rows of the decoder, widths
+    // decode (enc_ws == nullptr): c + a * c_arm + r * C, s + a * s_arm + r * S
+    const float* c; int64_t c_arm; const float* s; int64_t s_arm;
+    // traversal: row r = samp * B + b; enc_ws holds the encoder's CSMP / Y / MU ([A][B][.])
+    const float* enc_ws; int64_t csmp, y, mu; int B, d_s;
+    const float* params; int64_t per_arm, o_wsig, o_bsig;   // fc_sigma.weight / .bias
+    const float* u;               // explicit U(0,1) [A][n_samp][B], or nullptr: Philox (seed, offset) of `nz`
+    float* zin;                   // [A][R][C + S]
+};
+int launch_zin_build(const ZinBuild& z, const mmvae_noise* nz, const mmvae_hyper& h, hipStream_t s);
 // planes x planes GEMM (gemm_pp.hip): tiled slice planes of a matrix X [R][K] -- NP planes (3 exact slices / 1 rounded), each
 // [KT = ceil(K / 16)][Rp = R rounded up to 256][16] bf16, zero for k >= K
 struct TPlanes { unsigned short* p; int64_t plane; int Rp, KT; };

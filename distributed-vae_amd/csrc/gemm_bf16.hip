@@ -1600,6 +1600,83 @@ __global__ __launch_bounds__(256, 1) void k_x3_fc11g(const GemmArgs g_in) {
         for (int i = (int)gridDim.x * g.KS * 2 + tid; i < 2 * g.n11; i += 256) g.fo.part[(int64_t)arm * g.n11 * 2 + i] = 0.f;
 }
 
+// fc11 of a decode (mmvae_decode, mmvae_state_changes): x_rec = relu([d10 | 1] [W11 | b11]^T) and nothing else -- no x, no
+// loss, no dZ11, no d(d10).  Both operands come as the slice planes the decoder already has: [W11 | b11] from
+// launch_dec_planes, [d10 | 1] from the decoder chain (the bias rides as k = fc_dim, so the accumulator holds z + b).
+// NP = 3 (fp32x3): six slice products per K step in k_x3_fc11g's order; NP = 1 (bf16): slice 0 of each plane, i.e. the
+// operands -- the bias among them -- rounded to bf16.  NK K steps of 16 cover fc_dim + 1 (7: <= 112, 8: <= 128).
+// A wave keeps the [d10 | 1] slices of its 32 cells in registers (MFMA B operand, cell on the lane) and walks the gene
+// range of its block in pieces of 32 genes, the W11 rows of the next piece requested while the current one multiplies;
+// a lane stores four consecutive genes of its cell per accumulator quarter.  grid (ceil(B / 128), gene splits, A).
+struct Fc11OutArgs {
+    const unsigned short* wpl; int64_t w_plane, w_arm;    // [A][3][rup(D, 128)][128]
+    const unsigned short* dpl; int64_t d_plane, d_arm;    // [A][3][rup(B, 256)][128]
+    float* out;                                          // [A][B][D]
+    int B, D, KS;
+};
+template <int NP, int NK>
+__global__ __launch_bounds__(256, 1) void k_fc11_out(const Fc11OutArgs g) {
+    const int arm = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int l31 = lane & 31, hh = lane >> 5;
+    const int B = g.B, D = g.D;
+    const int cell = blockIdx.x * 128 + 32 * wv + l31;
+    const unsigned short* Wp = g.wpl + (int64_t)arm * g.w_arm;
+    const unsigned short* Dp = g.dpl + (int64_t)arm * g.d_arm;
+    bf16x8 dfr[NK][NP];
+    {
+        const int cr = min(cell, (int)(g.d_plane / 128) - 1);
+#pragma unroll
+        for (int s = 0; s < NK; ++s)
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl)
+                dfr[s][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(Dp + (int64_t)pl * g.d_plane + (int64_t)cr * 128 + 16 * s + 8 * hh));
+    }
+    const int npc = cdiv(D, 32);
+    const int p0 = (int)(((int64_t)blockIdx.y * npc) / g.KS), p1 = (int)(((int64_t)(blockIdx.y + 1) * npc) / g.KS);
+    // W11 rows 32 p + (lane & 31) of piece p exist in the planes (rup(D, 128) rows, zero beyond D)
+    auto load_w = [&](int p, bf16x8 (&a)[NK][NP]) __attribute__((always_inline)) {
+        const unsigned short* r = Wp + (int64_t)(32 * p + l31) * 128 + 8 * hh;
+#pragma unroll
+        for (int s = 0; s < NK; ++s)
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl)
+                a[s][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(r + (int64_t)pl * g.w_plane + 16 * s));
+    };
+    float* orow = g.out + ((int64_t)arm * B + min(cell, B - 1)) * D;
+    const bool cell_ok = cell < B;
+    bf16x8 wa[NK][NP], wb[NK][NP];
+    auto piece = [&](int p, const bf16x8 (&a)[NK][NP]) __attribute__((always_inline)) {
+        f32x16 acc = zero16();
+#pragma unroll
+        for (int s = 0; s < NK; ++s) {
+            if constexpr (NP == 3) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][2], dfr[s][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][0], dfr[s][2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][1], dfr[s][1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][1], dfr[s][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][0], dfr[s][1], acc, 0, 0, 0);
+            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][0], dfr[s][0], acc, 0, 0, 0);
+        }
+        // acc[4 q + e]: gene 32 p + 8 q + 4 hh + e of cell `cell`; D % 4 == 0, so a group of four exists entirely or not at all
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int gene = 32 * p + 8 * q + 4 * hh;
+            if (cell_ok && gene < D)
+                *reinterpret_cast<float4*>(orow + gene) = make_float4(relu_keep_nan(acc[4 * q]), relu_keep_nan(acc[4 * q + 1]),
+                                                                      relu_keep_nan(acc[4 * q + 2]), relu_keep_nan(acc[4 * q + 3]));
+        }
+    };
+    if (p0 < p1) load_w(p0, wa);
+    for (int p = p0; p < p1; p += 2) {
+        if (p + 1 < p1) load_w(p + 1, wb);
+        piece(p, wa);
+        if (p + 1 >= p1) break;
+        if (p + 2 < p1) load_w(p + 2, wa);
+        piece(p + 1, wb);
+    }
+}
+
 // The small-layer weight / bias gradients (twelve products per arm, out[m][n] = sum_b P[b][m] Q'[b][n], m <= 128,
 // n + 1 <= 128, K = batch) on the split engine: the ping-pong kernel with ONE PRODUCT PER GROUP -- the two groups of a block
 // take products 2 b and 2 b + 1 of the (product, arm) list, each with its own operands (both batch-reduced, i.e. K-minor;
@@ -1772,6 +1849,56 @@ int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_n
         }
     }
     return launch_presplit(c.stream, d.A, jobs, n, xbits ? &xb : nullptr);
+}
+
+// Decode: the planes its kernels read and nothing else -- fc6..fc10 for the chain kernels' fp32x3 form (forward slots only)
+// and [W11 | b11] for k_fc11_out (no W1, no transposed slots, no keep-mask: launch_x3_planes' head launch makes all of those)
+int launch_dec_planes(const Ctx& c, const float* params) {
+    const Plan& p = c.plan;
+    const mmvae_dims& d = c.d;
+    SplitJob jobs[6];
+    int n = 0;
+    if (p.fc11 == FC11_OUT_X3 || p.fc11 == FC11_OUT_BF16)
+        jobs[n++] = plane_job(c, PL_W11, params + c.po.o[26], d.H, c.po.per_arm, params + c.po.o[27], c.po.per_arm);
+    if (p.chain_planes) {   // slots 4 .. 8 as launch_x3_planes writes them
+        const int H = d.H, L = d.L, CS = d.C + d.S;
+        const int ti[5] = {16, 18, 20, 22, 24}, nn[5] = {L, H, H, H, H}, kk[5] = {CS, L, H, H, H};
+        unsigned short* base = reinterpret_cast<unsigned short*>(c.ws + c.lay.pl_small);
+        for (int i = 0; i < 5; ++i)
+            jobs[n++] = SplitJob{params + c.po.o[ti[i]], kk[i], c.po.per_arm, nn[i], kk[i], 128, 128, -1,
+                                 base + (int64_t)(4 + i) * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 0};
+    }
+    return n ? launch_presplit(c.stream, d.A, jobs, n) : 0;
+}
+
+int launch_fc11_out_bf16(const Ctx& c, float* x_rec) {
+    const mmvae_dims& d = c.d;
+    const PlaneGeom gw = plane_geom(c, PL_W11), gd = plane_geom(c, PL_D10);
+    Fc11OutArgs a{};
+    a.wpl = reinterpret_cast<const unsigned short*>(c.ws + gw.ws_off);
+    a.w_plane = (int64_t)gw.Rp * gw.Cp; a.w_arm = 3 * a.w_plane;
+    a.dpl = reinterpret_cast<const unsigned short*>(c.ws + gd.ws_off);
+    a.d_plane = (int64_t)gd.Rp * gd.Cp; a.d_arm = 3 * a.d_plane;
+    a.out = x_rec;
+    a.B = d.B; a.D = d.D;
+    // gene splits: the smallest count whose grid fills whole rounds of the CUs to >= 90 % (one workgroup per CU at fp32x3's
+    // register use, two at bf16's), at most one piece of 32 genes per split
+    const bool x3 = c.plan.fc11 == FC11_OUT_X3;
+    const int blocks = cdiv(d.B, 128) * d.A, slots = (x3 ? 1 : 2) * 256, cap = min(64, cdiv(d.D, 32));
+    int ks = 1;
+    double best = 0.0;
+    for (int k = 1; k <= cap; ++k) {
+        const int nwg = blocks * k;
+        const double eff = (double)nwg / (double)(cdiv(nwg, slots) * slots);
+        if (nwg >= slots && eff >= 0.9) { ks = k; break; }
+        if (eff > best + 1e-9) { best = eff; ks = k; }
+    }
+    a.KS = ks;
+    const dim3 grid(cdiv(d.B, 128), ks, d.A);
+    if (x3) hipLaunchKernelGGL((k_fc11_out<3, 7>), grid, dim3(256), 0, c.stream, a);
+    else hipLaunchKernelGGL((k_fc11_out<1, 8>), grid, dim3(256), 0, c.stream, a);
+    HIP_LAUNCH_CHECK("k_fc11_out");
+    return 0;
 }
 
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs) {

@@ -377,6 +377,47 @@ __global__ __launch_bounds__(256) void k_fc11_fused(const float* __restrict__ d1
     }
 }
 
+// x_rec alone (decode off the fast path): k_fc11_fused's tiles, product (mma_nt) and bias epilogue without x, the loss
+// partials, dZ11 and d(d10).  LDS: d10 tile [64][LDK], W tile [64][LDK].  grid (ceil(B/64), NS, A).
+__global__ __launch_bounds__(256) void k_fc11_fused_out(const float* __restrict__ d10, const float* __restrict__ params,
+                                                        int64_t per_arm, int64_t w_off, int64_t b_off, float* __restrict__ x_rec,
+                                                        int A, int B, int D, int H, int NS, int ldk, int vec_ok) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Ds = smem;                       // [64][ldk]
+    float* Ws = Ds + F11_BM * ldk;          // [64][ldk]
+    const int arm = blockIdx.z, ns = blockIdx.y, b0 = blockIdx.x * F11_BM;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
+    const int KP = rup(H, 8);
+    const float* W = params + (int64_t)arm * per_arm + w_off;     // [D, H]
+    const float* bias = params + (int64_t)arm * per_arm + b_off;  // [D]
+    const float* d10a = d10 + (int64_t)arm * B * H;
+    const bool hvec = ((H & 3) == 0) && vec_ok;
+    for (int idx = tid; idx < F11_BM * (ldk / 4); idx += 256) {
+        const int row = idx / (ldk / 4), c4 = idx % (ldk / 4);
+        *reinterpret_cast<float4*>(&Ds[row * ldk + c4 * 4]) = load_m4(d10a, H, b0 + row, c4 * 4, B, H, hvec);
+    }
+    const int ntile = cdiv(D, F11_BN);
+    const int t0 = (int)(((int64_t)ns * ntile) / NS), t1 = (int)(((int64_t)(ns + 1) * ntile) / NS);
+    for (int t = t0; t < t1; ++t) {
+        const int j0 = t * F11_BN;
+        __syncthreads();   // previous tile's readers of Ws are done
+        for (int idx = tid; idx < F11_BN * (ldk / 4); idx += 256) {
+            const int row = idx / (ldk / 4), c4 = idx % (ldk / 4);
+            *reinterpret_cast<float4*>(&Ws[row * ldk + c4 * 4]) = load_m4(W, H, j0 + row, c4 * 4, D, H, hvec);
+        }
+        __syncthreads();
+        f32x16 z = zero16();
+        mma_nt(z, Ds, ldk, wm * 32, Ws, ldk, wn * 32, KP / 8);
+        const int col = j0 + wn * 32 + (lane & 31);
+        const float bj = (col < D) ? bias[col] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = b0 + wm * 32 + acc_row(r, lane);
+            if (row < B && col < D) x_rec[((int64_t)arm * B + row) * D + col] = fmaxf(z[r] + bj, 0.f);
+        }
+    }
+}
+
 // =============================================================================================
 // TN GEMM over the batch:  out[m][n] = sum_b P[b][m] * Q[b][n]      (m < Mv, n < Nv)
 // Block tile TA x TB (TA*TB = 8192 or 16384), K tile 32 batch rows, 4 waves 2 x 2.
@@ -625,6 +666,17 @@ int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t
                        c.ws + c.lay.fc11_part, coef, need_grad, d.A, d.B, d.D, d.H, NS, ldk,
                        (int)(aligned16(params)), c.lay.n11);
     HIP_LAUNCH_CHECK("k_fc11_fused");
+    return 0;
+}
+
+int launch_fc11_fused_out(const Ctx& c, const float* params, float* x_rec) {
+    const mmvae_dims& d = c.d;
+    const int ldk = rup(d.H, 8) + 4;
+    const size_t shm = (size_t)(F11_BM * ldk + F11_BN * ldk) * sizeof(float);
+    const int NS = c.lay.sp.ns_fc11;
+    hipLaunchKernelGGL(k_fc11_fused_out, dim3(c.lay.nblk64, NS, d.A), dim3(256), shm, c.stream, c.ws + c.lay.Dk[4], params,
+                       c.po.per_arm, c.po.o[26], c.po.o[27], x_rec, d.A, d.B, d.D, d.H, NS, ldk, (int)(aligned16(params)));
+    HIP_LAUNCH_CHECK("k_fc11_fused_out");
     return 0;
 }
 

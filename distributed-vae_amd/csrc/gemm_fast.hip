@@ -790,6 +790,102 @@ __global__ __launch_bounds__(512, 2) void k_fc11_zt(const float* __restrict__ d1
     }
 }
 
+// x_rec alone (decode, Plan::fc11 == FC11_ZT of a CALL_DECODE plan): k_fc11_zt's product and epilogue arithmetic -- the same d10
+// fragments, W tile image (bias in the K padding when BIASK), MFMA order and quad transposes, so a decode reproduces a
+// forward's x_rec bit for bit -- without x, the loss partials and dZ11.  One W tile in LDS, all eight waves in step.
+// grid (ceil(B/256), NS, A)
+template <int FZ_KG, bool EXACT, bool BIASK>
+__global__ __launch_bounds__(512, 2) void k_fc11_zt_out(const float* __restrict__ d10, const float* __restrict__ params,
+                                                        int64_t per_arm, int64_t w_off, int64_t b_off, float* __restrict__ x_rec,
+                                                        int A, int B, int D, int H, int ldk) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Ws = smem;                       // [64][ldk]
+    const int arm = blockIdx.z, ns = blockIdx.y, NS = gridDim.y, b0 = blockIdx.x * 256;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int l31 = lane & 31, hh = lane >> 5;
+    const bool lb0 = (lane & 1) != 0, lb1 = (lane & 2) != 0;
+    const int KP = rup(H, 8), kg = KP / 8, nc4 = KP / 4, hc4 = H / 4;
+    const float* W = params + (int64_t)arm * per_arm + w_off;     // [D, H]
+    const float* bias = params + (int64_t)arm * per_arm + b_off;
+    float* xra = x_rec + (int64_t)arm * B * D;
+    const int bw = b0 + 32 * wv;
+    float4 afr[FZ_KG];
+    {
+        const int row = bw + l31;
+        const float* p = d10 + ((int64_t)arm * B + min(row, B - 1)) * H + 4 * hh;
+#pragma unroll
+        for (int g = 0; g < FZ_KG; ++g) {
+            const int k0 = 8 * g + 4 * hh;
+            const bool ok = row < B && k0 < H;
+            const float4 v = *reinterpret_cast<const float4*>(p + (ok ? 8 * g : 0));
+            afr[g] = sel4(ok, v);
+            if (BIASK && k0 == H) afr[g].x = 1.f;
+        }
+    }
+    const int ntall = cdiv(D, 64);
+    const int t0 = (int)(((int64_t)ns * ntall) / NS), t1 = (int)(((int64_t)(ns + 1) * ntall) / NS);
+    const int srow = tid >> 3, spart = tid & 7;
+    const int cbase = bw + 4 * hh + (l31 & 3);
+    const int gcol = 4 * (l31 >> 2);
+    for (int t = t0; t < t1; ++t) {
+        {   // W tile rows t * 64 + srow (k_fc11_zt's prefetch_w + store_w)
+            const int wj = t * 64 + srow;
+            const float* p = W + (int64_t)min(wj, D - 1) * H;
+            const float wbias = BIASK ? bias[min(wj, D - 1)] : 0.f;
+            const bool jok = wj < D;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = spart + 8 * i;
+                float4 v = sel4(jok && c < hc4, *reinterpret_cast<const float4*>(p + (c < hc4 ? c * 4 : 0)));
+                if (BIASK && c == hc4) v.x = jok ? wbias : 0.f;
+                if (c < nc4) *reinterpret_cast<float4*>(&Ws[srow * ldk + c * 4]) = v;
+            }
+        }
+        __syncthreads();
+        f32x16 z0 = zero16(), z1 = zero16();
+        {
+            const float* pb = Ws + l31 * ldk + 4 * hh;
+            float4 q0 = *reinterpret_cast<const float4*>(pb);
+            float4 q1 = *reinterpret_cast<const float4*>(pb + 32 * ldk);
+#pragma unroll
+            for (int g = 0; g < FZ_KG; ++g) {
+                if (EXACT || g < kg) {
+                    const int gn = EXACT ? ((g + 1 < FZ_KG) ? g + 1 : g) : ((g + 1 < kg) ? g + 1 : g);
+                    const float4 n0 = *reinterpret_cast<const float4*>(pb + 8 * gn);
+                    const float4 n1 = *reinterpret_cast<const float4*>(pb + 32 * ldk + 8 * gn);
+                    const float4 a = afr[g];
+                    z0 = mfma32(a.x, q0.x, z0); z1 = mfma32(a.x, q1.x, z1);
+                    z0 = mfma32(a.y, q0.y, z0); z1 = mfma32(a.y, q1.y, z1);
+                    z0 = mfma32(a.z, q0.z, z0); z1 = mfma32(a.z, q1.z, z1);
+                    z0 = mfma32(a.w, q0.w, z0); z1 = mfma32(a.w, q1.w, z1);
+                    q0 = n0; q1 = n1;
+                }
+            }
+        }
+        __syncthreads();   // every wave has read the tile: the next one may overwrite it
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int col = t * 64 + 32 * c + gcol;
+            float bq[4] = {0.f, 0.f, 0.f, 0.f};
+            if (!BIASK) {
+                const float4 b4 = *reinterpret_cast<const float4*>(bias + min(col, D - 4));
+                bq[0] = b4.x; bq[1] = b4.y; bq[2] = b4.z; bq[3] = b4.w;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float zz[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zz[e] = (c == 0 ? z0[4 * q + e] : z1[4 * q + e]);
+                quad_transpose4(zz[0], zz[1], zz[2], zz[3], lb0, lb1);
+                if (cbase + 8 * q < B && col < D)
+                    *reinterpret_cast<float4*>(xra + (int64_t)(cbase + 8 * q) * D + col) =
+                        make_float4(fmaxf(zz[0] + bq[0], 0.f), fmaxf(zz[1] + bq[1], 0.f), fmaxf(zz[2] + bq[2], 0.f),
+                                    fmaxf(zz[3] + bq[3], 0.f));
+            }
+        }
+    }
+}
+
 // =============================================================================================
 // fc11 forward + reconstruction loss + dZ11 + d(d10), train step at fc_dim = 100.  k_fc11_zt with the d(d10) GEMM of
 // k_gd10_v3 folded in: each wave keeps the dZ11 tile it has just produced in LDS and multiplies it with the W11 tile
@@ -1324,6 +1420,29 @@ int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64
         hipLaunchKernelGGL((k_fc1_fwd_v2<false>), grid, dim3(256), 0, c.stream, x, xs, params, c.po.per_arm,
                            c.po.o[0], bits, cdiv(d.D, 32), c.ws + c.lay.fc1_slab, d.A, d.B, d.D, d.H, KS);
     HIP_LAUNCH_CHECK("k_fc1_fwd_v2");
+    return 0;
+}
+
+int launch_fc11_out(const Ctx& c, const float* params, float* x_rec) {
+    if (c.plan.fc11 == FC11_GENERAL) return launch_fc11_fused_out(c, params, x_rec);
+    if (c.plan.fc11 == FC11_OUT_BF16 || c.plan.fc11 == FC11_OUT_X3) return launch_fc11_out_bf16(c, x_rec);
+    if (c.plan.fc11 != FC11_ZT) { set_error("internal: decode plan names fc11 family %d", (int)c.plan.fc11); return MMVAE_E_LAUNCH; }
+    // k_fc11_zt's template arguments and gene split (without the loss slots' limit)
+    const mmvae_dims& d = c.d;
+    const int ldk = rup(d.H, 8) + 4;
+    const int ntall = cdiv(d.D, 64), kgv = rup(d.H, 8) / 8;
+    const int nb = cdiv(d.B, 256);
+    const int nsz = max(1, min(min(256 / max(nb * d.A, 1), 16), ntall));
+    const size_t shm = (size_t)(64 * ldk) * sizeof(float);
+    const dim3 grid(nb, nsz, d.A);
+#define FZO_LAUNCH(KG, EX, BK) \
+    hipLaunchKernelGGL((k_fc11_zt_out<KG, EX, BK>), grid, dim3(512), shm, c.stream, c.ws + c.lay.Dk[4], params, c.po.per_arm, \
+                       c.po.o[26], c.po.o[27], x_rec, d.A, d.B, d.D, d.H, ldk)
+    if (kgv == 13 && d.H == 100) FZO_LAUNCH(13, true, true);
+    else if (kgv == 16 && d.H == 128) FZO_LAUNCH(16, true, false);
+    else FZO_LAUNCH(16, false, false);
+#undef FZO_LAUNCH
+    HIP_LAUNCH_CHECK("k_fc11_zt_out");
     return 0;
 }
 

@@ -1608,4 +1608,56 @@ int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noi
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// decoder input rows [c | s] (ZinBuild, common.hpp), one element per thread.  Decode copies the caller's c and s.  The
+// traversal (mixVAE_model.state_changes, nn_model.py:370-411) writes row r = samp * B + b of arm a as the encoder's c_smp of
+// cell b and s = mu of cell b, except s[d_s] = u * sqrt(exp(log(v))) + mu[d_s] with v = sigmoid(fc_sigma(y))[d_s] recomputed
+// in fp32 from y = [x_low | c] (the latent kernel keeps log(v + eps), not v; the reference's reparameterize takes log(v)
+// without eps), the product and the sum rounded separately as torch's eps.mul(std).add(mu) does.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_zin_build(const ZinBuild z, const NoiseDev nd) {
+    const int W = z.C + z.S;
+    const int64_t n = (int64_t)z.A * z.R * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int col = (int)(i % W);
+        const int64_t ar = i / W;
+        const int r = (int)(ar % z.R), a = (int)(ar / z.R);
+        float v;
+        if (!z.enc_ws) {
+            v = col < z.C ? z.c[a * z.c_arm + (int64_t)r * z.C + col] : z.s[a * z.s_arm + (int64_t)r * z.S + (col - z.C)];
+        } else {
+            const int64_t ab = (int64_t)a * z.B + r % z.B;
+            if (col < z.C) {
+                v = z.enc_ws[z.csmp + ab * z.C + col];
+            } else {
+                const int j = col - z.C;
+                const float mu = z.enc_ws[z.mu + ab * z.S + j];
+                if (j != z.d_s) {
+                    v = mu;
+                } else {
+                    const int K = z.L + z.C;
+                    const float* y = z.enc_ws + z.y + ab * K;
+                    const float* w = z.params + a * z.per_arm + z.o_wsig + (int64_t)z.d_s * K;
+                    float acc = 0.f;
+                    for (int k = 0; k < K; ++k) acc = fmaf(y[k], w[k], acc);
+                    acc += z.params[a * z.per_arm + z.o_bsig + z.d_s];
+                    const float var = 1.f / (1.f + expf(-acc));
+                    const float sd = sqrtf(expf(logf(var)));
+                    const float u = z.u ? z.u[(int64_t)a * z.R + r] : noise_uniform(nd, a, STREAM_STATE, (uint64_t)r);
+                    v = __fadd_rn(__fmul_rn(u, sd), mu);
+                }
+            }
+        }
+        z.zin[i] = v;
+    }
+}
+
+int launch_zin_build(const ZinBuild& z, const mmvae_noise* nz, const mmvae_hyper& h, hipStream_t s) {
+    const int64_t n = (int64_t)z.A * z.R * (z.C + z.S);
+    const NoiseDev nd = make_noise_dev(nz, h);
+    hipLaunchKernelGGL(k_zin_build, dim3((unsigned)imin64(4096, cdiv64(n, 256))), dim3(256), 0, s, z, nd);
+    HIP_LAUNCH_CHECK("k_zin_build");
+    return 0;
+}
+
 }  // namespace mmvae

@@ -3,7 +3,7 @@
 Mirrors (names, argument meaning, return contract, error behaviour):
 
 * ``mixVAE_model``            mmidas/nn_model.py:89   (``__init__`` :112-261, ``forward`` :297-368,
-                              ``loss`` :495-598)
+                              ``loss`` :495-598, ``decoder`` :277-287, ``state_changes`` :370-411)
 * ``mk_vae``                  mmidas/nn_model.py:679-721
 * ``VAEConfig``               mmidas/nn_model.py:14-36
 
@@ -126,6 +126,8 @@ class mixVAE_model(nn.Module):
         self._explicit_noise = None
         self._noise_seed = None
         self._noise_offset = 0
+        self._explicit_state_noise = None
+        self._dec_engines = {}
         self._exec: Optional[N.Exec] = None   # None: split factors / experiment switches from the environment
         # operand type of the five D x H GEMMs: "fp32" (the parity configuration) or "bf16" (BASELINE.json's bf16
         # configuration: operands rounded to bf16, fp32 accumulation; everything else and all parameters stay fp32)
@@ -396,6 +398,90 @@ class mixVAE_model(nn.Module):
         eng.eval_classify(self._hyper(temp, True), self._flat, self._bn_flat, xt, xs, labels, counts)
         self._ctx = None
         return labels
+
+    # ------------------------------------------------------------------ decoding a chosen code, state traversal
+    def _dec_engine(self, A: int, rows: int, n_samp=None) -> N.DecodeEngine:
+        if not self._is_packed():
+            self._pack()
+        mode = N.gemm_mode(self.gemm_dtype)
+        key = (A, rows, n_samp, str(self._flat.device), mode)
+        eng = self._dec_engines.pop(key, None)
+        if eng is None:
+            eng = N.DecodeEngine(A, rows, self.input_dim, self.fc_dim, self.lowD_dim, self.n_categories, self.state_dim,
+                                 self._flat.device, mode, n_samp, self._exec)
+        self._dec_engines[key] = eng
+        while len(self._dec_engines) > 3:
+            self._dec_engines.pop(next(iter(self._dec_engines)))
+        return eng
+
+    @torch.no_grad()
+    def decoder(self, c, s, arm):
+        """nn_model.py:277-287: ``relu(fc11(relu(fc10(... relu(fc6([c | s]))))))`` of arm ``arm`` for c [N, C], s [N, S]
+        (device tensors); returns the device tensor [N, D].  State dropout is the identity in eval mode; in training mode
+        with s_drop > 0 this raises NotImplementedError (the library does not offer a decode with state dropout)."""
+        if self.training and self.s_dp.p > 0:
+            raise NotImplementedError("decoder(): state dropout (training mode, s_drop > 0) is not supported; call model.eval()")
+        if not (0 <= int(arm) < self.n_arm):
+            raise IndexError(f"arm {arm} outside [0, {self.n_arm})")
+        if c.device.type != "cuda" or s.device.type != "cuda":
+            raise N.NativeError("mixVAE_model.decoder needs GPU tensors: the model runs only on the HIP engine")
+        c = c.reshape(-1, self.n_categories).contiguous().float()
+        s = s.reshape(-1, self.state_dim).contiguous().float()
+        if c.shape[0] != s.shape[0]:
+            raise ValueError(f"decoder(): c has {c.shape[0]} rows, s has {s.shape[0]}")
+        n = c.shape[0]
+        eng = self._dec_engine(1, n)
+        x_rec = torch.empty(n, self.input_dim, dtype=torch.float32, device=c.device)
+        per_arm = int(self._layout.per_arm)
+        params = self._flat[int(arm) * per_arm:]                     # that arm's segment: a one-arm model
+        eng.decode(self._hyper(1.0, True), params, c, 0, s, 0, x_rec)
+        return x_rec
+
+    def set_explicit_state_noise(self, u):
+        """Test hook of ``state_changes`` (as ``set_explicit_noise`` is of ``forward``): u float32 [A, n_samp, B] on the
+        device, the U(0,1) draws of the reference's ``torch.rand_like`` (nn_model.py:427) in its order -- arm, sample,
+        cell -- used by every following call; None returns to the model's Philox stream."""
+        self._explicit_state_noise = u
+
+    @torch.no_grad()
+    def state_changes(self, x, d_s, temp, n_samp=100):
+        """nn_model.py:370-411, the continuous traversal of state dimension ``d_s``: returns (recon_x, state_smp_sorted)
+        as CPU float32 tensors, recon_x [A, n_samp, D] for one cell and state_smp_sorted all zeros [A, n_samp], with the
+        samples reordered by ``torch.zeros(n_samp).sort()``'s indices as the reference does.  ``temp`` has no effect
+        (the reference's noise-free hard sample).  Extension: a batch of B > 1 cells (the reference raises) gives
+        recon_x [A, n_samp, B, D].  Needs model.eval(), as the reference's BatchNorm does."""
+        if self.training:
+            raise RuntimeError("state_changes() needs model.eval(): the reference traverses in eval mode "
+                               "(BatchNorm with one cell)")
+        xt = x if x.dim() == 2 else x.reshape(-1, self.input_dim)
+        if xt.device.type != "cuda":
+            raise N.NativeError("mixVAE_model.state_changes needs GPU tensors: the model runs only on the HIP engine")
+        xt = xt.contiguous().float()
+        B, n_samp, d_s = xt.shape[0], int(n_samp), int(d_s)
+        if not (0 <= d_s < self.state_dim):
+            raise IndexError(f"d_s {d_s} outside [0, {self.state_dim})")
+        if n_samp < 1:
+            raise ValueError("n_samp must be >= 1")
+        eng = self._dec_engine(self.n_arm, B, n_samp)
+        if self._explicit_state_noise is not None:
+            u = self._explicit_state_noise.contiguous().float()
+            assert tuple(u.shape) == (self.n_arm, n_samp, B) and u.device == xt.device
+            noise = N.make_noise({"u_state": u})
+        else:
+            if self._noise_seed is None:
+                self._noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+            self._noise_offset += 1
+            noise = N.make_noise(None, self._noise_seed, self._noise_offset)
+        out = torch.empty(self.n_arm, n_samp, B, self.input_dim, dtype=torch.float32, device=xt.device)
+        eng.state_changes(self._hyper(temp, True), noise, self._flat, self._bn_flat, xt, d_s, out)
+        recon = out.cpu()
+        state_smp_sorted = torch.zeros(self.n_arm, n_samp)
+        for arm in range(self.n_arm):
+            # the reference's reordering (nn_model.py:408-409): the sort indices of a zero vector, not the identity for
+            # every n_samp
+            _, sort_idx = torch.zeros(n_samp).sort()
+            recon[arm] = recon[arm, sort_idx]
+        return (recon[:, :, 0, :].contiguous() if B == 1 else recon), state_smp_sorted
 
     # ------------------------------------------------------------------ fused step (trainer path)
     def fused_train_step(self, x, temp, opt=None, do_adam=True):

@@ -15,6 +15,8 @@
  *   mmvae_eval_classify / mmvae_confmat_accumulate / mmvae_consensus
  *                      the per-epoch consensus loop  mmidas/cpl_mixvae.py:563-657, _utils.py:79-129
  *   mmvae_augment      netA(x.expand(A,-1,-1), True, 0.1)  mmidas/cpl_mixvae.py:422-423, augmentation/udagan.py:281-329
+ *   mmvae_decode       mixVAE_model.decoder(c, s, arm)     mmidas/nn_model.py:277-287
+ *   mmvae_state_changes  mixVAE_model.state_changes(x, d_s, temp, n_samp)  mmidas/nn_model.py:370-411
  *
  * Conventions
  *   - plain pointers and sizes only; every buffer is caller-owned DEVICE memory (fp32 unless
@@ -384,6 +386,34 @@ int mmvae_dp_unique_id(uint8_t id[MMVAE_DP_ID_BYTES]);
 int mmvae_dp_init(const uint8_t id[MMVAE_DP_ID_BYTES], int rank, int world_size, void **comm);
 int mmvae_allreduce_grads(void *comm, float *grads, int64_t n, void *stream);
 int mmvae_dp_destroy(void *comm);
+
+/* ---- decoding a chosen latent code, continuous-state traversal ---------------------------------------------------
+ * mmvae_decode: the decoder of every arm on N = d->B rows of the caller's code: x_rec = relu(fc11(relu(fc10(...relu(fc6([c | s]))...))))
+ *   (mixVAE_model.decoder, nn_model.py:277-287).  c: [A,N,C], arm a at c + a * c_arm_stride (floats), rows contiguous;
+ *   s: [A,N,S] likewise; x_rec: [A,N,D].  One arm of the model: A = 1 and params + a * per_arm.  State dropout is the
+ *   identity: h->training == 0, or == 1 with s_drop == 0 (both compute the same: the decoder has no BatchNorm); anything else
+ *   MMVAE_E_UNSUPPORTED.  Any N from 1 up (no training-batch cap).  fc11 reads no x and computes no loss: on engine 2 (within
+ *   fc_dim + 1 <= 112) and engine 1 it runs from the decoder's bf16 slice planes (engine 1: W11, b11 and d10 rounded to bf16),
+ *   otherwise on the fp32 matrix instruction with the forward pass's arithmetic (engine 0: x_rec of a forward, bit for bit).
+ *   Workspace: mmvae_decode_workspace_bytes(d, ex) == mmvae_workspace_bytes(d, ex) with d->B = N; the regions of mmvae_ws_offset
+ *   for these dims hold the decoder's activations (MMVAE_WS_ZIN, MMVAE_WS_D6 .. D10) afterwards.
+ * mmvae_state_changes: the continuous traversal of mixVAE_model.state_changes (nn_model.py:370-411) for d->B cells, eval mode
+ *   only (h->training == 0, else MMVAE_E_UNSUPPORTED).  x: [B,D] shared by the arms; bn_running: the running statistics.
+ *   Per arm: the eval-mode encoder and latent block (c = the hard straight-through sample of softmax(c_prob / tau), no category
+ *   mask; temp has no effect), mu and v = sigmoid(fc_sigma(y)); for sample i < n_samp and cell b the decoder input is
+ *   [c_b | s] with s = mu_b except s[d_s] = u[a][i][b] * sqrt(exp(log(v[d_s]))) + mu_b[d_s].  u ~ U(0,1): nz->mode 0 reads
+ *   nz->u_state as [A, n_samp, B]; mode 1 draws it from Philox (seed, offset).  x_rec: [A, n_samp, B, D] in sample order
+ *   (the reference's reordering of the samples is the caller's).  Workspace: mmvae_state_changes_workspace_bytes =
+ *   mmvae_workspace_bytes(d) + mmvae_workspace_bytes(d with B = n_samp * B), the encoder's part first.
+ * Both check every argument before any device work: MMVAE_E_BADARG for null pointers, n_samp < 1, d_s outside [0, S), a
+ * gemm_bf16 outside {0, 1, 2} and dims mmvae_check_dims rejects as such; MMVAE_E_UNSUPPORTED for shapes outside its limits. */
+size_t mmvae_decode_workspace_bytes(const mmvae_dims *d, const mmvae_exec *ex);
+int mmvae_decode(const mmvae_dims *d, const mmvae_hyper *h, const float *params, const float *c, int64_t c_arm_stride,
+                 const float *s, int64_t s_arm_stride, float *x_rec, void *ws, size_t ws_bytes, mmvae_exec *ex, void *stream);
+size_t mmvae_state_changes_workspace_bytes(const mmvae_dims *d, int n_samp, const mmvae_exec *ex);
+int mmvae_state_changes(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noise *nz, const float *params,
+                        const float *bn_running, const float *x, int d_s, int n_samp, float *x_rec, void *ws, size_t ws_bytes,
+                        mmvae_exec *ex, void *stream);
 
 /* Writes the noise the Philox mode (nz->mode == 1) would use, in explicit-buffer form, so a test
  * can replay a Philox step through mode 0.  Any output pointer may be NULL. */
