@@ -109,6 +109,43 @@ class NativeError(RuntimeError):
     pass
 
 
+# mmvae_debug_plan (include/mmvae.h): the fields of csrc/common.hpp's Plan in declaration order, the call kinds and the
+# enumerators by value
+PLAN_FIELDS = 23
+PLAN_NAMES = ("kind", "fast", "big", "small_x3", "fc11", "gd10_slabs", "dw11_slabs", "chain_planes", "lat_half", "narrow",
+              "presplit", "bwd_small_planes", "d10_planes", "dz1_in_apply", "dec_planes", "zero", "rowmap", "dz11_bf16",
+              "dw11_side", "loss_on_side", "couple", "lat_fork_rides", "fc11_fork_rides")
+CALL_KINDS = {"STEP": 0, "STEP_ROWS": 1, "FORWARD": 2, "BACKWARD": 3, "LOSS": 4, "CLASSIFY": 5, "REPLAY": 6, "DECODE": 7,
+              "TRAVERSE": 8}
+PLAN_ENUMS = {
+    "big": ("GEMM_GENERAL", "GEMM_FP32", "GEMM_BF16", "GEMM_X3"),
+    "fc11": ("FC11_GENERAL", "FC11_ZG", "FC11_ZT", "FC11_BF16", "FC11_X3", "FC11_OUT_BF16", "FC11_OUT_X3"),
+    "zero": ("ZERO_NONE", "ZERO_MEMSET", "ZERO_XBITS", "ZERO_PRESPLIT"),
+    "couple": ("COUPLE_INLINE", "COUPLE_SIDE", "COUPLE_IN_DEC"),
+}
+
+
+def debug_plan(dims: "Dims", hyper: "Hyper", ex: Optional["Exec"], kind: str, params_align: int = 16, x_align: int = 16,
+               x_arm_stride: int = 0, has_x16: bool = False, fc11_grad: bool = True) -> Dict[str, object]:
+    """The plan a call of ``kind`` (a key of CALL_KINDS) with these arguments would take (mmvae_debug_plan: host only, no
+    device needed): {field: int, bool, or the enumerator's name}."""
+    out = (C.c_int32 * PLAN_FIELDS)()
+    check(lib().mmvae_debug_plan(C.byref(dims), C.byref(hyper), C.byref(ex) if ex is not None else None, CALL_KINDS[kind],
+                                 int(params_align), int(x_align), int(x_arm_stride), int(bool(has_x16)), int(bool(fc11_grad)),
+                                 C.byref(out)), "mmvae_debug_plan")
+    plan = {}
+    for name, v in zip(PLAN_NAMES, out):
+        if name in PLAN_ENUMS:
+            plan[name] = PLAN_ENUMS[name][v]
+        elif name == "kind":
+            plan[name] = next(k for k, i in CALL_KINDS.items() if i == v)
+        elif name in ("gd10_slabs", "dw11_slabs"):
+            plan[name] = int(v)
+        else:
+            plan[name] = bool(v)
+    return plan
+
+
 _lib = None
 
 
@@ -150,6 +187,9 @@ def lib():
     L.mmvae_debug_stage.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), i32, vp, vp, i64, vp,
                                     C.c_size_t, vp, ex, vp]
     L.mmvae_dump_noise.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, vp]
+    L.mmvae_debug_plan.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), ex, i32, i32, i32, i64, i32, i32,
+                                   C.POINTER(C.c_int32 * PLAN_FIELDS)]
+    L.mmvae_debug_plan.restype = C.c_int
     L.mmvae_eval_classify.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, vp, i64, vp, C.c_size_t, vp, vp, ex,
                                       vp]
     L.mmvae_classify.argtypes = [vp, i64, i32, vp, vp]

@@ -850,6 +850,42 @@ int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noi
     }
 }
 
+int mmvae_debug_plan(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_exec* ex, int call_kind, int params_align,
+                     int x_align, int64_t x_arm_stride, int has_x16, int fc11_grad, int32_t out[MMVAE_PLAN_FIELDS]) {
+    if (int rc = check_dims(d)) return rc;
+    if (!h || !out) { set_error("null hyper / out"); return MMVAE_E_BADARG; }
+    if (int rc = check_gemm_engine(h->gemm_bf16)) return rc;
+    static_assert(MMVAE_CALL_STEP == CALL_STEP && MMVAE_CALL_STEP_ROWS == CALL_STEP_ROWS && MMVAE_CALL_FORWARD == CALL_FORWARD &&
+                  MMVAE_CALL_BACKWARD == CALL_BACKWARD && MMVAE_CALL_LOSS == CALL_LOSS && MMVAE_CALL_CLASSIFY == CALL_CLASSIFY &&
+                  MMVAE_CALL_REPLAY == CALL_REPLAY && MMVAE_CALL_DECODE == CALL_DECODE && MMVAE_CALL_TRAVERSE == CALL_TRAVERSE,
+                  "MMVAE_CALL_* (include/mmvae.h) are the values of CallKind");
+    if (call_kind < CALL_STEP || call_kind > CALL_TRAVERSE) { set_error("unknown call kind %d", call_kind); return MMVAE_E_BADARG; }
+    if (params_align < 0 || x_align < 0) { set_error("negative alignment"); return MMVAE_E_BADARG; }
+    // what make_ctx gives make_plan to read -- dims, hyper, exec copy, layout -- without a workspace or a stream
+    Ctx c{};
+    c.d = *d;
+    c.h = *h;
+    // (as their entry points plan: decode and the traversal force eval mode, eval_classify accepts nothing else)
+    if (call_kind == CALL_DECODE || call_kind == CALL_TRAVERSE || call_kind == CALL_CLASSIFY) c.h.training = 0;
+    if (ex) c.ex = *ex; else memset(&c.ex, 0, sizeof(c.ex));
+    c.lay = make_layout(*d, &c.ex);
+    c.po = make_poff(*d);
+    // pointers that are never dereferenced: a 16-byte boundary plus the stated alignment's offset
+    const uintptr_t base = 1u << 20;
+    const float* params = reinterpret_cast<const float*>(base + (uintptr_t)(params_align & 15));
+    const float* x = reinterpret_cast<const float*>(2 * base + (uintptr_t)(x_align & 15));
+    if (has_x16 && call_kind == CALL_STEP_ROWS) c.x16 = reinterpret_cast<const unsigned short*>(3 * base);   // (no other call takes one)
+    make_plan(c, (CallKind)call_kind, params, x, x_arm_stride, fc11_grad != 0);
+    const Plan& p = c.plan;
+    const int32_t v[] = {(int32_t)p.kind, p.fast, (int32_t)p.big, p.small_x3, (int32_t)p.fc11, p.gd10_slabs, p.dw11_slabs, p.chain_planes,
+                         p.lat_half, p.narrow, p.presplit, p.bwd_small_planes, p.d10_planes, p.dz1_in_apply, p.dec_planes,
+                         (int32_t)p.zero, p.rowmap, p.dz11_bf16, p.dw11_side, p.loss_on_side, (int32_t)p.couple, p.lat_fork_rides,
+                         p.fc11_fork_rides};
+    static_assert(sizeof(v) / sizeof(v[0]) == MMVAE_PLAN_FIELDS, "one value per field of Plan, in declaration order");
+    for (int i = 0; i < MMVAE_PLAN_FIELDS; ++i) out[i] = v[i];
+    return 0;
+}
+
 int mmvae_dump_noise(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, uint8_t* x_mask,
                      float* u_gumbel, float* u_state, uint8_t* s_mask, void* stream) {
     if (int rc = check_dims(d)) return rc;

@@ -432,6 +432,35 @@ int mmvae_debug_stage(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noi
                       const float *params, const float *x, int64_t x_arm_stride, void *ws,
                       size_t ws_bytes, float *grads, mmvae_exec *ex, void *stream);
 
+/* Host only (no workspace, stream or device call): the per-call plan -- which kernel family, zero fill, stream
+ * placement and plane set a call with these arguments would take -- written as MMVAE_PLAN_FIELDS int32 values in the
+ * declaration order of `Plan` (csrc/common.hpp: kind, fast, big, small_x3, fc11, gd10_slabs, dw11_slabs, chain_planes,
+ * lat_half, narrow, presplit, bwd_small_planes, d10_planes, dz1_in_apply, dec_planes, zero, rowmap, dz11_bf16,
+ * dw11_side, loss_on_side, couple, lat_fork_rides, fc11_fork_rides; enumerators by value, bools 0 / 1).  It runs the
+ * library's own planner on the dims, the hyper-parameters and a copy of `ex` (null: zeros; a non-null side_stream
+ * counts as "has a side stream", its events are not looked at), for the tests that pin every switch point of it.
+ *   call_kind      MMVAE_CALL_*: the entry point (STEP mmvae_train_step, STEP_ROWS mmvae_train_step_rows, ...).  DECODE,
+ *                  TRAVERSE and CLASSIFY are planned in eval mode (h->training is ignored), as their entry points run.
+ *   params_align   alignment in bytes of the flat parameter pointer: 16 or more means 16-byte aligned, 4 or 8 a pointer
+ *                  that many bytes past a 16-byte boundary.
+ *   x_align        the same for x (for DECODE: x_rec).
+ *   x_arm_stride   as passed to the entry point (floats).
+ *   has_x16        STEP_ROWS only (ignored otherwise): a bf16 copy of the matrix is given.
+ *   fc11_grad      mmvae_forward: need_grad && !x_rec (every other entry point: 1). */
+#define MMVAE_PLAN_FIELDS 23
+#define MMVAE_CALL_STEP 0
+#define MMVAE_CALL_STEP_ROWS 1
+#define MMVAE_CALL_FORWARD 2
+#define MMVAE_CALL_BACKWARD 3
+#define MMVAE_CALL_LOSS 4
+#define MMVAE_CALL_CLASSIFY 5
+#define MMVAE_CALL_REPLAY 6
+#define MMVAE_CALL_DECODE 7
+#define MMVAE_CALL_TRAVERSE 8
+int mmvae_debug_plan(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_exec *ex, int call_kind,
+                     int params_align, int x_align, int64_t x_arm_stride, int has_x16, int fc11_grad,
+                     int32_t out[MMVAE_PLAN_FIELDS]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,3 +148,68 @@ def assert_gradients_tight(grads, fo, grad_tol=1e-3):
         assert float(e_gpu.max()) < 5 * grad_tol, (k, float(e_gpu.max()))
         thr = max(grad_tol / 4, 2.0 * float(e_cpu.max()))
         assert int((e_gpu > thr).sum()) <= max(3, e_gpu.numel() // 100), (k, thr, float(e_gpu.max()))
+
+
+def assert_loss_vector(buf, lt, A, loss_tol=1e-5, total_tol=None):
+    """The fused step's loss vector (include/mmvae.h MMVAE_LOSS_*) against an oracle loss tuple: loss_tol on the totals, the
+    coupling distance and the per-arm reconstruction / likelihood terms, 1e-4 on the entropy, L2 and KL terms.  total_tol:
+    another bound for the total alone."""
+    from distributed_vae_amd import _native as N
+    lt = [v.detach() if torch.is_tensor(v) else v for v in lt]
+    want = [float(lt[0]), float(lt[2]), float(lt[3]), float(lt[4]), float(lt[5])]
+    want += [float(v) for v in lt[1]] + [float(v) for v in lt[6]] + [float(v) for v in lt[8]]
+    got = buf.double().tolist()
+    tol = [loss_tol, loss_tol, 1e-4, loss_tol, 1e-4] + [loss_tol] * A + [1e-4] * A + [loss_tol] * A
+    if total_tol is not None:
+        tol[0] = total_tol
+    assert len(got) == N.LOSS_REC0 + 3 * A
+    for i, (g_, w_, t_) in enumerate(zip(got, want, tol)):
+        assert abs(g_ - w_) <= t_ * abs(w_) + 1e-7, (i, g_, w_)
+
+
+def bf16_round(t: torch.Tensor) -> torch.Tensor:
+    """fp32 -> bf16 (round to nearest even) -> fp64, on the host."""
+    return t.float().to(torch.bfloat16).double()
+
+
+def assert_five_bf16_products(eng, grads, sd, x, noise, h, tol):
+    """The bf16 engine's five D x H products of one fused step, each recomputed in fp64 from the operands the kernels read
+    (the workspace of `eng`, the parameters `sd`, the masked input), rounded to bf16 as the kernels round them: they may
+    differ by the fp32 accumulation order only.  grads: {name: gradient} of that step."""
+    A, B, D, H = h.n_arm, x.shape[0], h.input_dim, h.fc_dim
+
+    def rel(a, b):
+        return float((a - b).abs().max() / (b.abs().max() + 1e-300))
+    keep = 1.0 / (1.0 - h.x_drop)
+    ns = eng.splits()[4]
+    d10 = eng.ws_view("d10", H).cpu()
+    dz11 = eng.ws_view("dz11", D).cpu()
+    dz1 = eng.ws_view("dz1", H).cpu()
+    r1 = eng.ws_view("r1", H).cpu()
+    gd10 = eng.ws_raw("gd10_slab", ns * A * B * H).view(ns, A, B, H).cpu().double().sum(0)
+    grads = {k: v.double() for k, v in grads.items()}
+    coef = max(A - 1, 1) / B
+    for a in range(A):
+        xm = x * noise["x_mask"][a].float() if h.x_drop > 0 else x    # masked, unscaled: what the GEMMs read
+        w1, b1 = sd[f"fc1.{a}.weight"], sd[f"fc1.{a}.bias"]
+        w11, b11 = sd[f"fc11.{a}.weight"], sd[f"fc11.{a}.bias"]
+        # fc1 forward (+ the shared fp32 epilogue: scale, bias, ReLU)
+        want = torch.relu(keep * (bf16_round(xm) @ bf16_round(w1).t()) + b1.double())
+        assert rel(r1[a].double(), want) < tol, ("fc1", a)
+        # fc11 forward + loss epilogue: dZ11 = coef (relu(z) - x) where relu(z) > 0, z from bf16(d10), bf16(W11), fp32 bias
+        z = bf16_round(d10[a]) @ bf16_round(w11).t() + b11.double()
+        want = coef * (torch.relu(z) - x.double()) * (z > 0)
+        sure = z.abs() > 1e-4                                             # fp32 accumulation may flip a ReLU at |z| ~ 0
+        assert float(((dz11[a].double() - want).abs() * sure).max()) < tol * float(want.abs().max()), ("fc11", a)
+        assert float(sure.double().mean()) > 0.99
+        # d(d10) = dZ11 W11
+        want = bf16_round(dz11[a]) @ bf16_round(w11)
+        assert rel(gd10[a], want) < tol, ("gd10", a)
+        # dW1 = dZ1^T x~ (the 1 / (1 - p) of the dropout is applied by the reduction)
+        want = keep * (bf16_round(dz1[a]).t() @ bf16_round(xm))
+        assert rel(grads[f"fc1.{a}.weight"], want) < tol, ("dW1", a)
+        # [dW11 | db11] = dZ11^T [d10 | 1]
+        want = bf16_round(dz11[a]).t() @ bf16_round(d10[a])
+        assert rel(grads[f"fc11.{a}.weight"], want) < tol, ("dW11", a)
+        want = bf16_round(dz11[a]).sum(0)
+        assert rel(grads[f"fc11.{a}.bias"], want) < tol, ("db11", a)

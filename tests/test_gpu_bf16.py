@@ -24,8 +24,8 @@ LOSS_GATE = 5e-2
 
 
 def bf16_round(t: torch.Tensor) -> torch.Tensor:
-    """fp32 -> bf16 (round to nearest even) -> fp64, on the host."""
-    return t.float().to(torch.bfloat16).double()
+    from tests import gpu_util as U
+    return U.bf16_round(t)
 
 
 def _run(h, B, seed, dtype):
@@ -51,41 +51,10 @@ def test_the_five_gemms_reproduce_bf16_rounded_products(shape):
     A, B, D, H = shape
     h = R.Hyper(input_dim=D, fc_dim=H, n_categories=12, state_dim=2, lowD_dim=6, n_arm=A)
     m, sd, x, noise, _ = _run(h, B, 21, "bf16")
-    eng = m._engine
+    from tests import gpu_util as U
     assert m._hyper(1.0, False).gemm_bf16 == 1
-    keep = 1.0 / (1.0 - h.x_drop)
-    ns = eng.splits()[4]
-    d10 = eng.ws_view("d10", H).cpu()
-    dz11 = eng.ws_view("dz11", D).cpu()
-    dz1 = eng.ws_view("dz1", H).cpu()
-    r1 = eng.ws_view("r1", H).cpu()
-    gd10 = eng.ws_raw("gd10_slab", ns * A * B * H).view(ns, A, B, H).cpu().double().sum(0)
-    grads = {k: gv.detach().cpu().double() for (k, _), gv in zip(m.named_parameters(), m._grad_views)}
-    coef = max(A - 1, 1) / B
-    for a in range(A):
-        xm = x * noise["x_mask"][a].float()                               # masked, unscaled: what the GEMMs read
-        w1, b1 = sd[f"fc1.{a}.weight"], sd[f"fc1.{a}.bias"]
-        w11, b11 = sd[f"fc11.{a}.weight"], sd[f"fc11.{a}.bias"]
-        # fc1 forward (+ the shared fp32 epilogue: scale, bias, ReLU)
-        want = torch.relu(keep * (bf16_round(xm) @ bf16_round(w1).t()) + b1.double())
-        assert _rel(r1[a].double(), want) < ENGINE_TOL, ("fc1", a)
-        # fc11 forward + loss epilogue: dZ11 = coef (relu(z) - x) where relu(z) > 0, z from bf16(d10), bf16(W11), fp32 bias
-        z = bf16_round(d10[a]) @ bf16_round(w11).t() + b11.double()
-        want = coef * (torch.relu(z) - x.double()) * (z > 0)
-        sure = z.abs() > 1e-4                                             # fp32 accumulation may flip a ReLU at |z| ~ 0
-        assert float(((dz11[a].double() - want).abs() * sure).max()) < ENGINE_TOL * float(want.abs().max()), ("fc11", a)
-        assert float(sure.double().mean()) > 0.99
-        # d(d10) = dZ11 W11
-        want = bf16_round(dz11[a]) @ bf16_round(w11)
-        assert _rel(gd10[a], want) < ENGINE_TOL, ("gd10", a)
-        # dW1 = dZ1^T x~ (the 1 / (1 - p) of the dropout is applied by the reduction)
-        want = keep * (bf16_round(dz1[a]).t() @ bf16_round(xm))
-        assert _rel(grads[f"fc1.{a}.weight"], want) < ENGINE_TOL, ("dW1", a)
-        # [dW11 | db11] = dZ11^T [d10 | 1]
-        want = bf16_round(dz11[a]).t() @ bf16_round(d10[a])
-        assert _rel(grads[f"fc11.{a}.weight"], want) < ENGINE_TOL, ("dW11", a)
-        want = bf16_round(dz11[a]).sum(0)
-        assert _rel(grads[f"fc11.{a}.bias"], want) < ENGINE_TOL, ("db11", a)
+    grads = {k: gv.detach().cpu() for (k, _), gv in zip(m.named_parameters(), m._grad_views)}
+    U.assert_five_bf16_products(m._engine, grads, sd, x, noise, h, ENGINE_TOL)
 
 
 @pytest.mark.parametrize("name", ["tiny_a2", "tiny_a5_hard", "ragged_a2"])

@@ -116,16 +116,7 @@ def test_fused_step_against_oracle(case):
     c = case
     A = c["A"]
     U = _U()
-    from distributed_vae_amd import _native as N
-    lt = c["lt_64"]
-    lt = [v.detach() if torch.is_tensor(v) else v for v in lt]
-    want = [float(lt[0]), float(lt[2]), float(lt[3]), float(lt[4]), float(lt[5])]
-    want += [float(v) for v in lt[1]] + [float(v) for v in lt[6]] + [float(v) for v in lt[8]]
-    got = c["buf"].double().tolist()
-    tol = [LOSS_TOL, LOSS_TOL, 1e-4, LOSS_TOL, 1e-4] + [LOSS_TOL] * A + [1e-4] * A + [LOSS_TOL] * A
-    assert len(got) == N.LOSS_REC0 + 3 * A
-    for i, (g_, w_, t_) in enumerate(zip(got, want, tol)):
-        assert abs(g_ - w_) <= t_ * abs(w_) + 1e-7, (i, g_, w_)
+    U.assert_loss_vector(c["buf"], c["lt_64"], A, LOSS_TOL)
     # every tensor, bias gradients included, to the round-1 gate -- against the oracle evaluated on the decisions the
     # device took (at most a handful differ from the fp64 oracle's own, each at a pre-activation within rounding of zero:
     # asserted in the fixture)
