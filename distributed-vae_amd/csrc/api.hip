@@ -261,7 +261,7 @@ static int make_ctx(Ctx& c, const mmvae_dims* d, const mmvae_hyper* h, void* ws,
 static int check_noise(const Ctx& c, const mmvae_noise* nz) {
     if (!nz) { set_error("noise descriptor is null"); return MMVAE_E_BADARG; }
     if (nz->mode == 0) {
-        if (c.h.training && c.h.x_drop > 0.f && !nz->x_mask) { set_error("explicit noise: x_mask is null"); return MMVAE_E_BADARG; }
+        if (c.dropout() && !nz->x_mask) { set_error("explicit noise: x_mask is null"); return MMVAE_E_BADARG; }
         if (!c.h.eval_flag && !nz->u_gumbel) { set_error("explicit noise: u_gumbel is null"); return MMVAE_E_BADARG; }
         if (!nz->u_state) { set_error("explicit noise: u_state is null"); return MMVAE_E_BADARG; }
         if (c.h.training && c.h.s_drop > 0.f && !nz->s_mask) { set_error("explicit noise: s_mask is null"); return MMVAE_E_BADARG; }
@@ -288,7 +288,7 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
     p.kind = kind;
     const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS, fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY ||
                                                                  kind == CALL_TRAVERSE;
-    const bool dropout = h.training && h.x_drop > 0.f, side = c.side() != nullptr;
+    const bool dropout = c.dropout(), side = c.side() != nullptr;
     p.fast = fast_dims(d) && al16(params) && al16(x) && (xs & 3) == 0 && d.H >= 4 && (int64_t)d.B * d.D < ((int64_t)1 << 30);
     // engines of the five D x H products (mmvae_hyper.gemm_bf16: 1 bf16 operands, 2 fp32x3)
     const bool bf16_tiles = (h.gemm_bf16 == 1 || h.gemm_bf16 == 2) && bf16_tiles_fit(d);
@@ -360,16 +360,13 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
 // Train step with a side stream: the coupling kernel needs only the latent block's outputs and the loss scalars only the
 // coupling and fc11 partials, so both run on the side stream -- the coupling beside the decoder chain and fc11, the
 // finalisation beside the d(d10) GEMM or dW11 (Plan::couple, loss_on_side).
-static int fork_to_side(const Ctx& c, int ev) {
-    if (hipEventRecord(c.ev(ev), c.stream) != hipSuccess || hipStreamWaitEvent(c.side(), c.ev(ev), 0) != hipSuccess) {
+// rode: the event rode on the kernel in front of the fork (Plan::lat_fork_rides / fc11_fork_rides, launch_k) -- only the side
+// stream's wait is left
+static int fork_to_side(const Ctx& c, int ev, bool rode = false) {
+    if ((!rode && hipEventRecord(c.ev(ev), c.stream) != hipSuccess) || hipStreamWaitEvent(c.side(), c.ev(ev), 0) != hipSuccess) {
         set_error("stream fork failed");
         return MMVAE_E_LAUNCH;
     }
-    return 0;
-}
-// the fork's event rode on the kernel in front of it (Ctx::stop_ev, launch_k): only the side stream's wait is left
-static int fork_wait_only(const Ctx& c, int ev) {
-    if (hipStreamWaitEvent(c.side(), c.ev(ev), 0) != hipSuccess) { set_error("stream fork failed"); return MMVAE_E_LAUNCH; }
     return 0;
 }
 static int record_on_side(const Ctx& c, int ev) {
@@ -381,15 +378,40 @@ static int join_from_side(const Ctx& c, int ev) {
     return 0;
 }
 
-// `launcher` with fork event `ev` riding on its kernel (launch_k) if the plan says so; it must have taken the event
-template <class F>
-static int launch_with_fork(const Ctx& c, bool rides, int ev, F launcher) {
-    if (rides) c.stop_ev = c.ev(ev);
-    int rc = launcher();
-    if (rides && !rc && !c.stop_used) { set_error("internal: the fork event did not ride on its kernel"); rc = MMVAE_E_LAUNCH; }
-    c.stop_ev = nullptr;
-    c.stop_used = false;
-    return rc;
+// The one dispatch level: the drivers pick each product's kernel family from the plan, the launchers launch their own file's
+// kernels.  The three D x H GEMMs of the fast path (GEMM_FP32, GEMM_BF16 or GEMM_X3; GEMM_GENERAL: launch_fc1_fwd with its
+// epilogue, launch_dw_big for both gradients) -- fc1 writes slabs that launch_fc1_epi sums:
+static int fc1_gemm(const Ctx& c, const float* params, const float* x, int64_t xs) {
+    return c.plan.big == GEMM_FP32 ? launch_fc1_fwd_fp32(c, params, x, xs) : launch_fc1_fwd_bf16(c, params, x, xs);
+}
+static int dw1(const Ctx& c, const float* x, int64_t xs) {
+    return c.plan.big == GEMM_FP32 ? launch_dw1_fp32(c, x, xs) : launch_dw1_bf16(c, x, xs);
+}
+static int dw11(const Ctx& c) { return c.plan.big == GEMM_FP32 ? launch_dw11_fp32(c) : launch_dw11_bf16(c); }
+static int fc1_forward(const Ctx& c, const mmvae_noise* nz, const float* params, const float* x, int64_t xs) {
+    if (c.plan.big == GEMM_GENERAL) return launch_fc1_fwd(c, nz, params, x, xs);
+    if (int rc = fc1_gemm(c, params, x, xs)) return rc;
+    return launch_fc1_epi(c, params);
+}
+// fc11's main launch: x_rec / loss / dZ11 (where Plan::fc11_fork_rides, EV_FORK rides on it)
+static int fc11_main(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad) {
+    switch (c.plan.fc11) {
+        case FC11_GENERAL: return launch_fc11_fused(c, params, x, xs, x_rec, need_grad);
+        case FC11_ZG: return launch_fc11_zg(c, params, x, xs, x_rec, need_grad);
+        case FC11_ZT: return launch_fc11_zt(c, params, x, xs, x_rec, need_grad);
+        case FC11_BF16: return launch_fc11_bf16(c, params, x, xs, x_rec, need_grad);
+        case FC11_X3: return launch_fc11_x3(c, params, x, xs);
+        default: set_error("internal: plan names fc11 family %d", (int)c.plan.fc11); return MMVAE_E_LAUNCH;
+    }
+}
+// d(d10) = dZ11 W11 where it is a launch of its own
+static int fc11_gd10(const Ctx& c, const float* params, float* x_rec, int need_grad) {
+    if (!need_grad) return 0;
+    switch (c.plan.fc11) {
+        case FC11_ZT: return launch_gd10_fp32(c, params);
+        case FC11_BF16: return x_rec ? launch_gd10_bf16(c, params) : 0;   // (without x_rec k_bf16_fc11g has written it)
+        default: return 0;                                                // FC11_GENERAL, FC11_ZG, FC11_X3: out of the main launch
+    }
 }
 
 static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
@@ -400,12 +422,7 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
     if ((p.zero == ZERO_MEMSET || p.zero == ZERO_XBITS) && (rc = launch_forward_zero(c, nz))) return rc;
     // fp32x3 / chain planes: slice planes of W1, [W11 | b11], the small layers (+ keep-mask, zero fill, row map: Plan::zero)
     if (p.presplit && (rc = launch_x3_planes(c, params, true, nz))) return rc;
-    if (p.fast) {
-        if ((rc = launch_fc1_fwd_fast(c, params, x, xs))) return rc;
-        if ((rc = launch_fc1_epi(c, params))) return rc;
-    } else if ((rc = launch_fc1_fwd(c, nz, params, x, xs))) {
-        return rc;
-    }
+    if ((rc = fc1_forward(c, nz, params, x, xs))) return rc;
     // batch statistics are recombined by the kernel that consumes each BatchNorm (no finalize launches);
     // eval mode copies the running statistics into the workspace instead
     if ((rc = launch_bn_eval_stats(c, bn_running))) return rc;
@@ -415,13 +432,12 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
         for (int layer = 2; layer <= 5; ++layer)
             if ((rc = launch_chain_fwd_enc(c, layer, params, bn_running, nbt))) return rc;
     }
-    if ((rc = launch_with_fork(c, p.lat_fork_rides, EV_LAT, [&] { return launch_lat_fwd(c, nz, params, bn_running, nbt, labels); })))
-        return rc;
+    if ((rc = launch_lat_fwd(c, nz, params, bn_running, nbt, labels))) return rc;   // (Plan::lat_fork_rides: EV_LAT rides on it)
     if (p.kind == CALL_CLASSIFY || p.kind == CALL_TRAVERSE) return 0;   // labels / the traversal's encoder: no decoder, no fc11
     Ctx cs = c;
     cs.stream = c.side();
     if (p.couple == COUPLE_SIDE) {
-        if ((rc = p.lat_fork_rides ? fork_wait_only(c, EV_LAT) : fork_to_side(c, EV_LAT))) return rc;
+        if ((rc = fork_to_side(c, EV_LAT, p.lat_fork_rides))) return rc;
         if ((rc = launch_couple(cs))) return rc;
         if (p.loss_on_side) {
             if ((rc = launch_loss_finalize(cs, loss_out, 1))) return rc;
@@ -432,7 +448,8 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
     if ((rc = launch_chain_fwd_dec(c, params))) return rc;
     if (p.couple == COUPLE_SIDE && !p.loss_on_side && (rc = record_on_side(c, EV_COUPLE))) return rc;
     // loss_on_side: dW11 starts as soon as fc11 has finished -- EV_FORK rides on the fused fc11 kernel
-    return launch_with_fork(c, p.fc11_fork_rides, EV_FORK, [&] { return launch_fc11(c, params, x, xs, x_rec, need_grad); });
+    if ((rc = fc11_main(c, params, x, xs, x_rec, need_grad))) return rc;
+    return fc11_gd10(c, params, x_rec, need_grad);
 }
 
 // decode and the traversal's decoder half: ZIN from `zb`, the decoder chain (eval mode: it has no BatchNorm), fc11 for x_rec
@@ -442,7 +459,12 @@ static int do_decode(const Ctx& c, const float* params, ZinBuild zb, const mmvae
     zb.zin = c.ws + c.lay.ZIN;
     if ((rc = launch_zin_build(zb, nz, c.h, c.stream))) return rc;
     if ((rc = launch_chain_fwd_dec(c, params))) return rc;
-    return launch_fc11_out(c, params, x_rec);
+    switch (c.plan.fc11) {
+        case FC11_GENERAL: return launch_fc11_fused_out(c, params, x_rec);
+        case FC11_ZT: return launch_fc11_zt_out(c, params, x_rec);
+        case FC11_OUT_BF16: case FC11_OUT_X3: return launch_fc11_out_bf16(c, x_rec);
+        default: set_error("internal: decode plan names fc11 family %d", (int)c.plan.fc11); return MMVAE_E_LAUNCH;
+    }
 }
 
 static int do_loss(const Ctx& c, float* loss_out) {
@@ -464,8 +486,8 @@ static int do_backward(const Ctx& c, const mmvae_noise* nz, const float* params,
     Ctx cs = c;
     cs.stream = c.side();
     if (p.dw11_side) {
-        if ((rc = (p.fc11_fork_rides ? fork_wait_only(c, EV_FORK) : fork_to_side(c, EV_FORK)))) return rc;
-        if ((rc = launch_dw_big_fast(cs, x, xs, 2))) return rc;
+        if ((rc = fork_to_side(c, EV_FORK, p.fc11_fork_rides))) return rc;
+        if ((rc = dw11(cs))) return rc;
         if (early) {
             // data parallel: fc11.weight / fc11.bias (47 % of the parameters) are final here; reduce their slabs now
             // and tell the caller, who starts their all-reduce beside the rest of backward
@@ -492,7 +514,12 @@ static int do_backward(const Ctx& c, const mmvae_noise* nz, const float* params,
     for (int layer = 5; layer >= 2; --layer)
         if ((rc = launch_chain_bwd_enc(c, layer, params))) return rc;
     if ((rc = launch_bn_bwd_apply1(c))) return rc;
-    if ((rc = p.fast ? launch_dw_big_fast(c, x, xs, p.dw11_side ? 1 : 3) : launch_dw_big(c, nz, x, xs))) return rc;
+    if (p.big == GEMM_GENERAL) {
+        if ((rc = launch_dw_big(c, nz, x, xs))) return rc;
+    } else {
+        if ((rc = dw1(c, x, xs))) return rc;
+        if (!p.dw11_side && (rc = dw11(c))) return rc;
+    }
     if ((rc = launch_dw_small(c))) return rc;
     if (p.dw11_side && (rc = join_from_side(c, EV_JOIN))) return rc;
     return launch_reduce_grads(c, grads, grad_scale, adam, early || side_red ? 2 : 3);
@@ -821,25 +848,25 @@ int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noi
     make_plan(c, CALL_REPLAY, params, x, x_arm_stride);
     const bool fast = c.plan.fast;
     switch (stage) {
-        case 0:
-            if (fast) {
-                if (int rc = launch_fc1_fwd_fast(c, params, x, x_arm_stride)) return rc;
-                return launch_fc1_epi(c, params);
-            }
-            return launch_fc1_fwd(c, nz, params, x, x_arm_stride);
-        case 1: return launch_fc11(c, params, x, x_arm_stride, nullptr, 1);
-        case 2: return fast ? launch_dw_big_fast(c, x, x_arm_stride, 3) : launch_dw_big(c, nz, x, x_arm_stride);
+        case 0: return fc1_forward(c, nz, params, x, x_arm_stride);
+        case 1:
+            if (int rc = fc11_main(c, params, x, x_arm_stride, nullptr, 1)) return rc;
+            return fc11_gd10(c, params, nullptr, 1);
+        case 2:
+            if (!fast) return launch_dw_big(c, nz, x, x_arm_stride);
+            if (int rc = dw1(c, x, x_arm_stride)) return rc;
+            return dw11(c);
         case 9: return launch_make_xbits(c, nz);
         case 20: return launch_chain_fwd_enc(c, 3, params, nullptr, nullptr);   // one encoder layer (fc3)
         case 21: return launch_chain_bwd_enc(c, 3, params);
         // single kernels of the fast path (per-kernel roofline timing)
         case 10: case 11: case 12: case 13: case 14:
             if (!fast) { set_error("stage %d needs the fast path", stage); return MMVAE_E_UNSUPPORTED; }
-            if (stage == 10) return launch_fc11(c, params, x, x_arm_stride, nullptr, 1, 1);
-            if (stage == 11) return launch_fc11(c, params, x, x_arm_stride, nullptr, 1, 2);
-            if (stage == 12) return launch_dw_big_fast(c, x, x_arm_stride, 1);
-            if (stage == 13) return launch_dw_big_fast(c, x, x_arm_stride, 2);
-            return launch_fc1_fwd_fast(c, params, x, x_arm_stride);
+            if (stage == 10) return fc11_main(c, params, x, x_arm_stride, nullptr, 1);
+            if (stage == 11) return fc11_gd10(c, params, nullptr, 1);   // (a launch only where d(d10) has one of its own: FC11_ZT)
+            if (stage == 12) return dw1(c, x, x_arm_stride);
+            if (stage == 13) return dw11(c);
+            return fc1_gemm(c, params, x, x_arm_stride);
         case 3: return launch_dw_small(c);
         case 4: return launch_chain_fwd_dec(c, params);
         case 5: return launch_chain_bwd_dec(c, params);

@@ -905,8 +905,7 @@ static int launch_fwd(const Ctx& c, ChainFwdArgs& a, int maxdim, const float* pa
     } else {
         hipLaunchKernelGGL(k_chain_fwd<false>, grid, dim3(CH_NT), chain_smem(a.ld, a.wrows), c.stream, a, params, c.ws, bn_running, nbt);
     }
-    hipError_t e_ = hipGetLastError();
-    if (e_ != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e_)); return MMVAE_E_LAUNCH; }
+    HIP_LAUNCH_CHECK(what);
     return 0;
 }
 
@@ -921,8 +920,7 @@ static int launch_bwd(const Ctx& c, ChainBwdArgs& a, int maxdim, const float* pa
     } else {
         hipLaunchKernelGGL(k_chain_bwd<false>, grid, dim3(CH_NT), chain_smem(a.ld, a.wrows), c.stream, a, params, c.ws);
     }
-    hipError_t e_ = hipGetLastError();
-    if (e_ != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e_)); return MMVAE_E_LAUNCH; }
+    HIP_LAUNCH_CHECK(what);
     return 0;
 }
 
@@ -1014,7 +1012,7 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params) {
     a.ld = fwd_ld(max(max(d.H, d.L), d.C + d.S));
     a.wrows = rup(max(d.H, d.L), 32);
     a.per_arm = c.po.per_arm;
-    for (int i = 0; i < 5; ++i) a.L[i].pl_slot = 4 + i;
+    for (int i = 0; i < 5; ++i) a.L[i].pl_slot = PL_SMALL_DEC0 + i;
     if (c.plan.couple == COUPLE_IN_DEC) {
         // the coupling terms as a second role of this launch (k_chain_fwd_couple): fp32x3 form, accumulator sets, 2 .. 5 arms
         const int maxdim = max(max(d.H, d.L), d.C + d.S);
@@ -1038,8 +1036,7 @@ int launch_chain_fwd_dec(const Ctx& c, const float* params) {
             default: MMVAE_DEC_COUPLE(5); break;
         }
 #undef MMVAE_DEC_COUPLE
-        hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) { set_error("k_chain_fwd_couple: %s", hipGetErrorString(e_)); return MMVAE_E_LAUNCH; }
+        HIP_LAUNCH_CHECK("k_chain_fwd_couple");
         return 0;
     }
     return launch_fwd(c, a, max(max(d.H, d.L), d.C + d.S), params, nullptr, nullptr, "k_chain_fwd<dec>");
@@ -1071,7 +1068,7 @@ int launch_chain_bwd_dec(const Ctx& c, const float* params) {
     a.ld = bwd_ld(max(max(d.H, d.L), d.C + d.S));
     a.wrows = max(rup(max(d.H, d.L), 8), cdiv(WS_SCRATCH, a.ld));   // Ws doubles as scratch of the epilogue's sums
     a.per_arm = c.po.per_arm;
-    for (int i = 0; i < 5; ++i) a.L[i].pl_slot = 9 + 8 - i;   // fc10 .. fc6, transposed planes
+    for (int i = 0; i < 5; ++i) a.L[i].pl_slot = PL_SMALL_LAYERS + 8 - i;   // fc10 .. fc6, transposed planes
     return launch_bwd(c, a, max(max(d.H, d.L), d.C + d.S), params, "k_chain_bwd<dec>");
 }
 
@@ -1105,7 +1102,7 @@ int launch_chain_bwd_enc(const Ctx& c, int layer, const float* params) {
     a.ld = bwd_ld(max(d.H, N));
     a.wrows = max(rup(N, 8), cdiv(WS_SCRATCH, a.ld));   // Ws doubles as scratch (batch-sum prologue / epilogue)
     a.per_arm = c.po.per_arm;
-    a.L[0].pl_slot = 9 + layer - 2;
+    a.L[0].pl_slot = PL_SMALL_LAYERS + layer - 2;
     return launch_bwd(c, a, max(d.H, N), params, "k_chain_bwd<enc>");
 }
 

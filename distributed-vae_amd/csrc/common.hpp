@@ -89,7 +89,7 @@ struct Layout {
     int64_t total;
 };
 // accumulator set geometry (device side below)
-constexpr int PL_SMALL_SLOTS = 18;
+constexpr int PL_SMALL_LAYERS = 9, PL_SMALL_DEC0 = 4, PL_SMALL_SLOTS = 2 * PL_SMALL_LAYERS;   // (slot of fc6: the decoder's first)
 constexpr int ACC_W = 128;                             // columns per set
 constexpr int ACC_SET_I64 = 6 * ACC_W + 8;             // [6][ACC_W] slots + tail block, [0]: addends outside the window (-> NaN)
 constexpr int ACC_SET_FLOATS = 2 * ACC_SET_I64;
@@ -787,6 +787,8 @@ struct Ctx {
     int tune(int i) const { return ex.tune[i]; }
     // training-mode batch sums through the fixed-point accumulators (production) or the per-workgroup partial arrays
     bool use_acc() const { return !ex.tune[MMVAE_TUNE_BN_PARTIALS]; }
+    bool dropout() const { return h.training && h.x_drop > 0.f; }   // input dropout is on: the keep-mask exists and is applied
+    float fc11_coef() const { return (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B; }   // weight of fc11's loss term in dZ11
     // the range Plan::zero names a launch for: [fc11_part, end of the forward accumulator sets)
     // (through the coupling's T set: the fused step's coupling runs inside the decoder chain's launch and finds it zeroed; the
     // coupling's own launcher zeroes it again, it may run more than once per forward pass)
@@ -800,23 +802,24 @@ struct Ctx {
     const unsigned short* x16 = nullptr;
     int64_t x_ld = 0, x_nrows = 0;
     Plan plan{};            // make_plan (api.hip), once per entry point
-    // Fork events that ride on a kernel (hipExtLaunchKernel's stop event: the dispatch packet's own completion signal) instead
-    // of a hipEventRecord behind it -- a recorded event is a barrier packet of its own, 6 - 7 us of idle main stream at every
-    // fork.  The step's driver names the event the NEXT launch of a launcher that knows launch_k carries (stop_ev); the
-    // launcher consumes it and sets stop_used, and the fork then only makes the side stream wait.
-    mutable hipEvent_t stop_ev = nullptr;
-    mutable bool stop_used = false;
 };
+// ahead of an fc11 kernel that adds to the loss partial slots: no launch of this call has zeroed them (Plan::zero: eval mode,
+// a replayed stage), so fill them here
+inline int zero_fc11_part(const Ctx& c) {
+    if (c.plan.zero != ZERO_NONE) return 0;
+    hipError_t e = hipMemsetAsync(c.ws + c.lay.fc11_part, 0, sizeof(float) * 2 * (size_t)c.d.A * c.lay.n11, c.stream);
+    if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
+    return 0;
+}
 #ifdef __HIPCC__
+// Launch on the context's stream.  stop_ev != nullptr: a fork event rides on the kernel (hipExtLaunchKernel's stop event: the
+// dispatch packet's own completion signal) instead of a hipEventRecord behind it -- a recorded event is a barrier packet of
+// its own, 6 - 7 us of idle main stream at every fork; the fork then only makes the side stream wait.  The plan names the
+// launches that carry one (Plan::lat_fork_rides, fc11_fork_rides) and their launchers pass it.
 template <class K, class... Args>
-inline void launch_k(const Ctx& c, K kernel, dim3 grid, dim3 block, unsigned shm, Args... args) {
-    if (c.stop_ev) {
-        hipExtLaunchKernelGGL(kernel, grid, block, shm, c.stream, nullptr, c.stop_ev, 0, args...);
-        c.stop_ev = nullptr;
-        c.stop_used = true;
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, shm, c.stream, args...);
-    }
+inline void launch_k(const Ctx& c, hipEvent_t stop_ev, K kernel, dim3 grid, dim3 block, unsigned shm, Args... args) {
+    if (stop_ev) hipExtLaunchKernelGGL(kernel, grid, block, shm, c.stream, nullptr, stop_ev, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, shm, c.stream, args...);
 }
 #endif
 // events of mmvae_exec.ev by role
@@ -866,21 +869,28 @@ int launch_make_xbits(const Ctx& c, const mmvae_noise* nz);
 // first thing of a forward pass whose Plan::zero is ZERO_MEMSET or ZERO_XBITS: zero the loss partial slots and the
 // forward accumulator sets (folded into k_make_xbits when that runs, a fill otherwise)
 int launch_forward_zero(const Ctx& c, const mmvae_noise* nz);
-int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64_t xs);
 int launch_fc1_epi(const Ctx& c, const float* params);
-// fc11 and d(d10), the family Plan::fc11 names (which: bit0 x_rec / loss / dZ11, bit1 d(d10))
-int launch_fc11(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which = 3);
-int launch_dw_big_fast(const Ctx& c, const float* x, int64_t xs, int which /*bit0 dW1, bit1 dW11*/);
+// fp32 matrix-instruction family (gemm_fast.hip): GEMM_FP32, FC11_ZG (d(d10) folded in), FC11_ZT (+ launch_gd10_fp32)
+int launch_fc1_fwd_fp32(const Ctx& c, const float* params, const float* x, int64_t xs);
+int launch_fc11_zg(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
+int launch_fc11_zt(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
+int launch_gd10_fp32(const Ctx& c, const float* params);
+int launch_dw1_fp32(const Ctx& c, const float* x, int64_t xs);
+int launch_dw11_fp32(const Ctx& c);
 // bf16-operand variants of the five D x H GEMMs (gemm_bf16.hip; mmvae_hyper.gemm_bf16), same outputs / layouts
 // gemm_bf16 == 2: fp32 operands split exactly into three bf16 slices each (six slice products per product: fp32-grade
 // results on the bf16 matrix pipe); the same tile engine with three LDS planes per operand
 // the k_presplit launch of Plan::presplit (head = true) or Plan::bwd_small_planes
 int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_noise* nz = nullptr);
-int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs);
-int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which);
-int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which);
+int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs);           // GEMM_BF16 and GEMM_X3
+int launch_dw1_bf16(const Ctx& c, const float* x, int64_t xs);
+int launch_dw11_bf16(const Ctx& c);
+int launch_fc11_x3(const Ctx& c, const float* params, const float* x, int64_t xs);                // FC11_X3: loss, dZ11 and d(d10)
+// FC11_BF16: need_grad without x_rec the same in one fused kernel, else k_bf16_fc11 (and launch_gd10_bf16 for d(d10))
+int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
+int launch_gd10_bf16(const Ctx& c, const float* params);
 // decode (Plan::fc11 of a CALL_DECODE plan): x_rec = relu([d10 | 1] [W11 | b11]^T) and nothing else -- no x, no loss, no dZ11
-int launch_fc11_out(const Ctx& c, const float* params, float* x_rec);            // (gemm_fast.hip: picks the family)
+int launch_fc11_zt_out(const Ctx& c, const float* params, float* x_rec);         // gemm_fast.hip
 int launch_fc11_fused_out(const Ctx& c, const float* params, float* x_rec);      // gemm_big.hip
 int launch_fc11_out_bf16(const Ctx& c, float* x_rec);                            // gemm_bf16.hip, from the slice planes
 int launch_dec_planes(const Ctx& c, const float* params);                        // Plan::dec_planes

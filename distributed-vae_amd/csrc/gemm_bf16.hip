@@ -1802,22 +1802,34 @@ static int launch_presplit(hipStream_t s, int A, const SplitJob* jobs, int n, co
     return 0;
 }
 
+// The small layers' weight planes for the chain kernels (Layout::pl_small): slot s holds [N][K] of fc2..fc5 (0..3) and
+// fc6..fc10 (4..8), slot 9 + s the same layer as [K][N] for the backward chain (its contraction runs over N)
+static SplitJob small_plane_job(const Ctx& c, const float* params, int s, bool transposed) {
+    const int H = c.d.H, L = c.d.L, CS = c.d.C + c.d.S;
+    const int ti[PL_SMALL_LAYERS] = {2, 4, 6, 8, 16, 18, 20, 22, 24};                    // parameter tensor index of the weight
+    const int nn[PL_SMALL_LAYERS] = {H, H, H, L, L, H, H, H, H}, kk[PL_SMALL_LAYERS] = {H, H, H, H, CS, L, H, H, H};
+    unsigned short* base = reinterpret_cast<unsigned short*>(c.ws + c.lay.pl_small);
+    return SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, transposed ? kk[s] : nn[s], transposed ? nn[s] : kk[s], 128, 128, -1,
+                    base + (int64_t)(transposed ? PL_SMALL_LAYERS + s : s) * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128,
+                    nullptr, 0, transposed ? 1 : 0};
+}
+
 // Write slice planes from the parameters -- one small launch ahead of the kernels that copy them into LDS: at the head of a
 // forward pass W1 and [W11 | b11] (fp32x3 engine, bf16 storage) and the small layers' weights (Plan::chain_planes), at the
 // head of a backward pass that is its own call the small layers' weights alone.
 int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_noise* nz) {
     const Plan& p = c.plan;
+    const mmvae_dims& d = c.d;
     // ZERO_PRESPLIT (the head of a training step's forward pass, dropout on): this launch also makes the keep-mask and zeroes
     // the loss partial slots and the forward accumulator sets -- k_make_xbits' work (launch_forward_zero) without its launch
     XbitsJob xb{};
     const bool xbits = head && p.zero == ZERO_PRESPLIT;
     if (xbits) {
-        const mmvae_dims& dd = c.d;
         xb.nz = make_noise_dev(nz, c.h);
-        xb.A = dd.A; xb.B = dd.B; xb.D = dd.D; xb.wpr = cdiv(dd.D, 32);
+        xb.A = d.A; xb.B = d.B; xb.D = d.D; xb.wpr = cdiv(d.D, 32);
         xb.bits = reinterpret_cast<uint32_t*>(c.ws + c.lay.xbits);
         const int wpt = xb.nz.mode != 0 && xb.nz.x_mlog2 <= 2 ? (int)(4u >> xb.nz.x_mlog2) : 1;   // as in make_xbits_range
-        xb.blocks = (int)imin64(2048, cdiv64((int64_t)dd.B * cdiv(xb.wpr, wpt), 256));
+        xb.blocks = (int)imin64(2048, cdiv64((int64_t)d.B * cdiv(xb.wpr, wpt), 256));
         xb.zero_p = c.ws + c.lay.fc11_part;
         xb.zero_n4 = (int)(c.fwd_zero_floats() / 4);
         if (p.rowmap) {
@@ -1825,7 +1837,6 @@ int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_n
             xb.rows_ld = c.x_ld; xb.n_rows = c.x_nrows;
         }
     }
-    const mmvae_dims& d = c.d;
     SplitJob jobs[24];
     int n = 0;
     // (narrow, the bf16 configuration on bf16 storage: slice 0 of W1's planes IS bf16(W1) -- fc1 reads its narrow operand from
@@ -1835,19 +1846,11 @@ int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_n
         jobs[n++] = plane_job(c, PL_W1, params + c.po.o[0], d.D, c.po.per_arm);
         jobs[n++] = plane_job(c, PL_W11, params + c.po.o[26], d.H, c.po.per_arm, params + c.po.o[27], c.po.per_arm);   // bias: column fc_dim
     }
-    if (p.chain_planes) {   // the small layers' weights for the chain kernels: slot s = [N][K] of fc2..fc5, fc6..fc10
-        const int H = d.H, L = d.L, CS = d.C + d.S;
-        const int ti[9] = {2, 4, 6, 8, 16, 18, 20, 22, 24};                    // parameter tensor index of the weight
-        const int nn[9] = {H, H, H, L, L, H, H, H, H}, kk[9] = {H, H, H, H, CS, L, H, H, H};
-        unsigned short* base = reinterpret_cast<unsigned short*>(c.ws + c.lay.pl_small);
-        for (int s = 0; s < 9; ++s) {
-            jobs[n++] = SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, nn[s], kk[s], 128, 128, -1,
-                                 base + (int64_t)s * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 0};
-            // and [K][N] for the backward chain (its contraction runs over N)
-            jobs[n++] = SplitJob{params + c.po.o[ti[s]], kk[s], c.po.per_arm, kk[s], nn[s], 128, 128, -1,
-                                 base + (int64_t)(9 + s) * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 1};
+    if (p.chain_planes)
+        for (int s = 0; s < PL_SMALL_LAYERS; ++s) {
+            jobs[n++] = small_plane_job(c, params, s, false);
+            jobs[n++] = small_plane_job(c, params, s, true);
         }
-    }
     return launch_presplit(c.stream, d.A, jobs, n, xbits ? &xb : nullptr);
 }
 
@@ -1860,14 +1863,8 @@ int launch_dec_planes(const Ctx& c, const float* params) {
     int n = 0;
     if (p.fc11 == FC11_OUT_X3 || p.fc11 == FC11_OUT_BF16)
         jobs[n++] = plane_job(c, PL_W11, params + c.po.o[26], d.H, c.po.per_arm, params + c.po.o[27], c.po.per_arm);
-    if (p.chain_planes) {   // slots 4 .. 8 as launch_x3_planes writes them
-        const int H = d.H, L = d.L, CS = d.C + d.S;
-        const int ti[5] = {16, 18, 20, 22, 24}, nn[5] = {L, H, H, H, H}, kk[5] = {CS, L, H, H, H};
-        unsigned short* base = reinterpret_cast<unsigned short*>(c.ws + c.lay.pl_small);
-        for (int i = 0; i < 5; ++i)
-            jobs[n++] = SplitJob{params + c.po.o[ti[i]], kk[i], c.po.per_arm, nn[i], kk[i], 128, 128, -1,
-                                 base + (int64_t)(4 + i) * 3 * 128 * 128, (int64_t)PL_SMALL_SLOTS * 3 * 128 * 128, nullptr, 0, 0};
-    }
+    if (p.chain_planes)
+        for (int s = PL_SMALL_DEC0; s < PL_SMALL_LAYERS; ++s) jobs[n++] = small_plane_job(c, params, s, false);
     return n ? launch_presplit(c.stream, d.A, jobs, n) : 0;
 }
 
@@ -1901,20 +1898,24 @@ int launch_fc11_out_bf16(const Ctx& c, float* x_rec) {
     return 0;
 }
 
+// x (or dW1's x~) as rows of the resident matrix (mmvae_train_step_rows): the operand is read through the row map
+static void use_rowmap(const Ctx& c, Operand& o) {
+    o.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); o.nrec = c.x_nrows * c.x_ld; o.map_n = c.d.B;
+}
+
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
-    const bool use_mask = c.h.training && c.h.x_drop > 0.f;
     GemmArgs g{};
     g.a = kmajor(x, d.D, d.B, d.D);
     g.a_arm = xs;
-    if (use_mask) { g.a.bits = reinterpret_cast<const uint32_t*>(c.ws + c.lay.xbits); g.a.wpr = cdiv(d.D, 32); g.a_bits_arm = (int64_t)d.B * g.a.wpr; }
+    if (c.dropout()) { g.a.bits = reinterpret_cast<const uint32_t*>(c.ws + c.lay.xbits); g.a.wpr = cdiv(d.D, 32); g.a_bits_arm = (int64_t)d.B * g.a.wpr; }
     g.b = kmajor(params + c.po.o[0], d.D, d.H, d.D);
     g.b_arm = c.po.per_arm;
     g.M = d.B; g.N = d.H; g.K = d.D; g.KS = c.lay.sp.ks_fc1; g.A = d.A;
     g.so = SlabOut{c.ws + c.lay.fc1_slab, (int64_t)d.A * d.B * NP, (int64_t)d.B * NP, NP, d.B, d.H};
     const bool x3 = c.plan.big == GEMM_X3;
-    if (c.plan.rowmap) {   // the batch as rows of the resident matrix (mmvae_train_step_rows): x is read through the row map
-        g.a.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); g.a.nrec = c.x_nrows * c.x_ld; g.a.map_n = d.B;
+    if (c.plan.rowmap) {
+        use_rowmap(c, g.a);
         if (x3) {
             use_planes(c, g.b, PL_W1);
             hipLaunchKernelGGL((k_x3_gemm<false, false, 2, 1>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
@@ -1938,147 +1939,152 @@ int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64
     return 0;
 }
 
-int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad, int which) {
+// what the fc11 kernels of both engines share: [d10 | W11^T] operands, the gene split, loss / dZ11 / x_rec outputs
+static GemmArgs fc11_args(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
-    const int NS = L.sp.ks_gd10;
-    // forward for gradients without x_rec (the train step, mmvae_forward(need_grad) for backward): one fused kernel, and
-    // the call for d(d10) (which & 2) has nothing left to do; with x_rec wanted two kernels
-    const bool fused = need_grad && !x_rec;
-    if (c.plan.fc11 == FC11_X3) {
-        // fp32x3: only the fused train-step kernel exists in this engine (fc_dim + 1 <= 112, 128 cells per block fit the
-        // loss-partial slots); everything else runs the fp32 matrix-instruction kernels (Plan::fc11)
-        if (!(which & 1)) return 0;
-        GemmArgs g{};
-        g.a = kmajor(c.ws + L.Dk[4], d.H, d.B, d.H);
-        g.b = kmajor(params + c.po.o[26], d.H, d.D, d.H);
-        use_planes(c, g.b, PL_W11);
-        use_planes(c, g.a, PL_D10);
-        g.M = d.B; g.N = d.D; g.K = d.H; g.KS = NS; g.A = d.A; g.n11 = L.n11;
-        g.fo = Fc11Out{params + c.po.o[27], x, c.ws + L.DZ11, nullptr, c.ws + L.fc11_part,
-                       (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B, d.B, d.D, nullptr, 0};
-        if (c.plan.rowmap) {
-            g.fo.xmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap);
-            g.fo.x_nrec = c.x_nrows * c.x_ld;
-        }
-        g.fo_arm = (int64_t)d.B * d.D;
-        g.fo_x_arm = xs;
-        g.so = SlabOut{c.ws + L.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
-        launch_k(c, k_x3_fc11g, dim3(cdiv(d.B, 128), NS, d.A), dim3(256), 0, g);
-        HIP_LAUNCH_CHECK("k_x3_fc11g");
-        return 0;
+    GemmArgs g{};
+    g.a = kmajor(c.ws + L.Dk[4], d.H, d.B, d.H);          // d10 [B][H]
+    g.b = kmajor(params + c.po.o[26], d.H, d.D, d.H);      // W11 [D][H]
+    g.M = d.B; g.N = d.D; g.K = d.H; g.KS = L.sp.ks_gd10; g.A = d.A; g.n11 = L.n11;
+    g.fo = Fc11Out{params + c.po.o[27], x, c.ws + L.DZ11, x_rec, c.ws + L.fc11_part, c.fc11_coef(), d.B, d.D, nullptr, 0};
+    if (c.plan.rowmap) {
+        g.fo.xmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap);
+        g.fo.x_nrec = c.x_nrows * c.x_ld;
     }
-    if (which & 1) {
-        hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
-        if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
-        if (!fc11_slots_fit(L, d.B)) { set_error("fc11 bf16: loss partial slots"); return MMVAE_E_LAUNCH; }
-        GemmArgs g{};
-        g.a = kmajor(c.ws + L.Dk[4], d.H, d.B, d.H);          // d10 [B][H]
-        g.a_arm = (int64_t)d.B * d.H;
-        g.b = kmajor(params + c.po.o[26], d.H, d.D, d.H);      // W11 [D][H]
-        g.b_arm = c.po.per_arm;
-        g.bias_arm = c.po.per_arm;
-        g.M = d.B; g.N = d.D; g.K = d.H; g.KS = NS; g.A = d.A; g.n11 = L.n11;
-        g.fo = Fc11Out{params + c.po.o[27], x, c.ws + L.DZ11, x_rec, c.ws + L.fc11_part,
-                       (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B, d.B, d.D, nullptr, 0};
-        if (c.plan.rowmap) {
-            g.fo.xmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap);
-            g.fo.x_nrec = c.x_nrows * c.x_ld;
-        }
-        g.fo_arm = (int64_t)d.B * d.D;
-        g.fo_x_arm = xs;
-        if (fused) {   // train step: d(d10) comes out of the same launch (which & 2 is then a no-op)
-            g.so = SlabOut{c.ws + L.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
-            if (c.plan.dz11_bf16) {   // bf16 storage: x from its bf16 copy, dZ11 written as bf16 (dW11 below reads it that way)
-                g.fo.x = reinterpret_cast<const float*>(c.x16);
-                g.fo_arm = (int64_t)d.B * d.D / 2;          // (arm stride of dZ11 in floats: B * D two-byte elements)
-                if (c.plan.narrow && KT == 64) {   // W11 from slice 0 of its planes (launch_x3_planes): [rup(D, 128)][128] bf16
-                    const PlaneGeom pg = plane_geom(c, PL_W11);
-                    g.b = kmajor(reinterpret_cast<const float*>(c.ws + pg.ws_off), pg.Cp, pg.Rp, pg.Cp);
-                    g.b.src16 = 1;
-                    g.b_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;       // arm stride in FLOATS of the pointer arithmetic (planes: 2-byte elements)
-                    launch_k(c, k_bf16_fc11g<true, true>, dim3(cdiv(d.B, BT), NS, d.A), dim3(256), 0, g);
-                } else
-                    launch_k(c, k_bf16_fc11g<true>, dim3(cdiv(d.B, BT), NS, d.A), dim3(256), 0, g);
-            } else
-                launch_k(c, k_bf16_fc11g<false>, dim3(cdiv(d.B, BT), NS, d.A), dim3(256), 0, g);
-            HIP_LAUNCH_CHECK("k_bf16_fc11g");
-        } else {
-            hipLaunchKernelGGL(k_bf16_fc11, dim3(cdiv(d.B, BT), NS, d.A), dim3(256), 0, c.stream, g);
-            HIP_LAUNCH_CHECK("k_bf16_fc11");
-        }
-    }
-    if (need_grad && (which & 2) && !fused) {
-        GemmArgs g{};
-        g.a = kmajor(c.ws + L.DZ11, d.D, d.B, d.D);            // dZ11 [B][D], k = gene
-        g.a_arm = (int64_t)d.B * d.D;
-        g.b = kminor(params + c.po.o[26], d.H, d.H, d.D);      // W11 [D][H] read as B[n = h][k = j]
-        g.b_arm = c.po.per_arm;
-        g.M = d.B; g.N = d.H; g.K = d.D; g.KS = NS; g.A = d.A;
-        g.so = SlabOut{c.ws + L.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
-        hipLaunchKernelGGL((k_bf16_gemm<false, true>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), NS, d.A), dim3(256), 0, c.stream, g);
-        HIP_LAUNCH_CHECK("k_bf16_gemm<gd10>");
-    }
+    g.fo_arm = (int64_t)d.B * d.D;
+    g.fo_x_arm = xs;
+    return g;
+}
+static SlabOut gd10_slab(const Ctx& c) {
+    const mmvae_dims& d = c.d;
+    return SlabOut{c.ws + c.lay.GD10_slab, (int64_t)d.A * d.B * d.H, (int64_t)d.B * d.H, d.H, d.B, d.H};
+}
+
+// fp32x3: only the fused train-step kernel exists in this engine (fc_dim + 1 <= 112, 128 cells per block fit the
+// loss-partial slots, no x_rec); everything else runs the fp32 matrix-instruction kernels (Plan::fc11)
+int launch_fc11_x3(const Ctx& c, const float* params, const float* x, int64_t xs) {
+    const mmvae_dims& d = c.d;
+    GemmArgs g = fc11_args(c, params, x, xs, nullptr);
+    use_planes(c, g.b, PL_W11);
+    use_planes(c, g.a, PL_D10);
+    g.so = gd10_slab(c);
+    // (fc11_fork_rides implies FC11_X3 or FC11_BF16 with fc11_grad, i.e. this launch or k_bf16_fc11g below)
+    launch_k(c, c.plan.fc11_fork_rides ? c.ev(EV_FORK) : nullptr, k_x3_fc11g, dim3(cdiv(d.B, 128), g.KS, d.A), dim3(256), 0, g);
+    HIP_LAUNCH_CHECK("k_x3_fc11g");
     return 0;
 }
 
-int launch_dw_big_bf16(const Ctx& c, const float* x, int64_t xs, int which) {
+int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad) {
+    const mmvae_dims& d = c.d;
+    if (int rc = zero_fc11_part(c)) return rc;
+    if (!fc11_slots_fit(c.lay, d.B)) { set_error("fc11 bf16: loss partial slots"); return MMVAE_E_LAUNCH; }
+    GemmArgs g = fc11_args(c, params, x, xs, x_rec);
+    g.a_arm = (int64_t)d.B * d.H;
+    g.b_arm = c.po.per_arm;
+    g.bias_arm = c.po.per_arm;
+    const dim3 grid(cdiv(d.B, BT), g.KS, d.A);
+    // forward for gradients without x_rec (the train step, mmvae_forward(need_grad) for backward): one fused kernel that
+    // also writes d(d10); with x_rec wanted two kernels (launch_gd10_bf16)
+    if (!(need_grad && !x_rec)) {
+        hipLaunchKernelGGL(k_bf16_fc11, grid, dim3(256), 0, c.stream, g);
+        HIP_LAUNCH_CHECK("k_bf16_fc11");
+        return 0;
+    }
+    g.so = gd10_slab(c);
+    // (fc11_fork_rides implies FC11_BF16 with fc11_grad -- need_grad without x_rec --, i.e. one of these three launches)
+    const hipEvent_t fork = c.plan.fc11_fork_rides ? c.ev(EV_FORK) : nullptr;
+    if (c.plan.dz11_bf16) {   // bf16 storage: x from its bf16 copy, dZ11 written as bf16 (dW11 reads it that way)
+        g.fo.x = reinterpret_cast<const float*>(c.x16);
+        g.fo_arm = (int64_t)d.B * d.D / 2;          // (arm stride of dZ11 in floats: B * D two-byte elements)
+        if (c.plan.narrow && KT == 64) {   // W11 from slice 0 of its planes (launch_x3_planes): [rup(D, 128)][128] bf16
+            const PlaneGeom pg = plane_geom(c, PL_W11);
+            g.b = kmajor(reinterpret_cast<const float*>(c.ws + pg.ws_off), pg.Cp, pg.Rp, pg.Cp);
+            g.b.src16 = 1;
+            g.b_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;       // arm stride in FLOATS of the pointer arithmetic (planes: 2-byte elements)
+            launch_k(c, fork, k_bf16_fc11g<true, true>, grid, dim3(256), 0, g);
+        } else
+            launch_k(c, fork, k_bf16_fc11g<true>, grid, dim3(256), 0, g);
+    } else
+        launch_k(c, fork, k_bf16_fc11g<false>, grid, dim3(256), 0, g);
+    HIP_LAUNCH_CHECK("k_bf16_fc11g");
+    return 0;
+}
+
+int launch_gd10_bf16(const Ctx& c, const float* params) {
+    const mmvae_dims& d = c.d;
+    GemmArgs g{};
+    g.a = kmajor(c.ws + c.lay.DZ11, d.D, d.B, d.D);        // dZ11 [B][D], k = gene
+    g.a_arm = (int64_t)d.B * d.D;
+    g.b = kminor(params + c.po.o[26], d.H, d.H, d.D);      // W11 [D][H] read as B[n = h][k = j]
+    g.b_arm = c.po.per_arm;
+    g.M = d.B; g.N = d.H; g.K = d.D; g.KS = c.lay.sp.ks_gd10; g.A = d.A;
+    g.so = gd10_slab(c);
+    hipLaunchKernelGGL((k_bf16_gemm<false, true>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+    HIP_LAUNCH_CHECK("k_bf16_gemm<gd10>");
+    return 0;
+}
+
+// dW1[h][d] = sum_b dZ1[b][h] x~[b][d]
+int launch_dw1_bf16(const Ctx& c, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
-    const bool use_mask = c.h.training && c.h.x_drop > 0.f;
     const bool x3 = c.plan.big == GEMM_X3;
-    if (which & 1) {   // dW1[h][d] = sum_b dZ1[b][h] x~[b][d]
-        GemmArgs g{};
-        g.a = kminor(c.ws + L.DZ[1], d.H, d.H, d.B);
-        g.a_arm = (int64_t)d.B * d.H;
-        g.b = kminor(x, d.D, d.D, d.B);
-        g.b_arm = xs;
-        if (use_mask) { g.b.bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits); g.b.wpr = cdiv(d.D, 32); g.b_bits_arm = (int64_t)d.B * g.b.wpr; }
-        g.M = d.H; g.N = d.D; g.K = d.B; g.KS = L.sp.ks_dw; g.A = d.A;
-        g.so = SlabOut{c.ws + L.dw1_slab, (int64_t)d.A * d.H * d.D, (int64_t)d.H * d.D, d.D, d.H, d.D};
-        if (c.plan.rowmap) {
-            g.b.rowmap = reinterpret_cast<const unsigned*>(c.ws + L.rowmap); g.b.nrec = c.x_nrows * c.x_ld; g.b.map_n = d.B;
-            if (x3) {
-                use_planes(c, g.a, PL_DZ1);
-                hipLaunchKernelGGL((k_x3_gemm<true, true, 1, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-            } else if (c.x16) {
-                g.b.ptr = reinterpret_cast<const float*>(c.x16); g.b.src16 = 1;
-                if (c.plan.narrow && c.plan.dz1_in_apply) {   // dZ1 from slice 0 of its planes (k_bn_bwd_apply): [rup(B, 256)][128] bf16
-                    const PlaneGeom pg = plane_geom(c, PL_DZ1);
-                    g.a.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.a.ld = pg.Cp; g.a.src16 = 1;
-                    g.a_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;
-                    hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 3>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-                } else
-                    hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-            } else
-                hipLaunchKernelGGL((k_bf16_gemm<true, true, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        } else if (x3) {   // one tile high: the two tiles of a block share the dZ1 tile
+    GemmArgs g{};
+    g.a = kminor(c.ws + L.DZ[1], d.H, d.H, d.B);
+    g.a_arm = (int64_t)d.B * d.H;
+    g.b = kminor(x, d.D, d.D, d.B);
+    g.b_arm = xs;
+    if (c.dropout()) { g.b.bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits); g.b.wpr = cdiv(d.D, 32); g.b_bits_arm = (int64_t)d.B * g.b.wpr; }
+    g.M = d.H; g.N = d.D; g.K = d.B; g.KS = L.sp.ks_dw; g.A = d.A;
+    g.so = SlabOut{c.ws + L.dw1_slab, (int64_t)d.A * d.H * d.D, (int64_t)d.H * d.D, d.D, d.H, d.D};
+    if (c.plan.rowmap) {
+        use_rowmap(c, g.b);
+        if (x3) {
             use_planes(c, g.a, PL_DZ1);
-            hipLaunchKernelGGL((k_x3_gemm<true, true, 1>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+            hipLaunchKernelGGL((k_x3_gemm<true, true, 1, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+        } else if (c.x16) {
+            g.b.ptr = reinterpret_cast<const float*>(c.x16); g.b.src16 = 1;
+            if (c.plan.narrow && c.plan.dz1_in_apply) {   // dZ1 from slice 0 of its planes (k_bn_bwd_apply): [rup(B, 256)][128] bf16
+                const PlaneGeom pg = plane_geom(c, PL_DZ1);
+                g.a.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.a.ld = pg.Cp; g.a.src16 = 1;
+                g.a_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;
+                hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 3>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+            } else
+                hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
         } else
-            hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        HIP_LAUNCH_CHECK("k_bf16_gemm<dW1>");
-    }
-    if (which & 2) {   // [dW11 | db11][j][h] = sum_b dZ11[b][j] [d10 | 1][b][h]
-        GemmArgs g{};
-        g.a = kminor(c.ws + L.DZ11, d.D, d.D, d.B);
-        g.a_arm = (int64_t)d.B * d.D;
-        g.b = kminor(c.ws + L.Dk[4], d.H, d.H, d.B);
-        g.b.ones_row = d.H;                                      // logical row H (not in memory) reads 1: the bias gradient
-        g.b_arm = (int64_t)d.B * d.H;
-        g.M = d.D; g.N = d.H + 1; g.K = d.B; g.KS = L.sp.ks_dw11; g.A = d.A;
-        g.so = SlabOut{c.ws + L.dw11_slab, (int64_t)d.A * d.D * DW11_LD, (int64_t)d.D * DW11_LD, DW11_LD, d.D, d.H + 1};
-        if (x3) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
-            use_planes(c, g.b, PL_D10);
-            hipLaunchKernelGGL((k_x3_gemm<true, true, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-        } else if (c.plan.dz11_bf16) {   // bf16 storage: the fused fc11 kernel of this step wrote dZ11 as bf16
-            g.a.src16 = 1;
-            g.a_arm = (int64_t)d.B * d.D / 2;
-            hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 1>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        } else
-            hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        HIP_LAUNCH_CHECK("k_bf16_gemm<dW11>");
-    }
+            hipLaunchKernelGGL((k_bf16_gemm<true, true, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+    } else if (x3) {   // one tile high: the two tiles of a block share the dZ1 tile
+        use_planes(c, g.a, PL_DZ1);
+        hipLaunchKernelGGL((k_x3_gemm<true, true, 1>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+    } else
+        hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+    HIP_LAUNCH_CHECK("k_bf16_gemm<dW1>");
+    return 0;
+}
+
+// [dW11 | db11][j][h] = sum_b dZ11[b][j] [d10 | 1][b][h]
+int launch_dw11_bf16(const Ctx& c) {
+    const mmvae_dims& d = c.d;
+    const Layout& L = c.lay;
+    GemmArgs g{};
+    g.a = kminor(c.ws + L.DZ11, d.D, d.D, d.B);
+    g.a_arm = (int64_t)d.B * d.D;
+    g.b = kminor(c.ws + L.Dk[4], d.H, d.H, d.B);
+    g.b.ones_row = d.H;                                      // logical row H (not in memory) reads 1: the bias gradient
+    g.b_arm = (int64_t)d.B * d.H;
+    g.M = d.D; g.N = d.H + 1; g.K = d.B; g.KS = L.sp.ks_dw11; g.A = d.A;
+    g.so = SlabOut{c.ws + L.dw11_slab, (int64_t)d.A * d.D * DW11_LD, (int64_t)d.D * DW11_LD, DW11_LD, d.D, d.H + 1};
+    if (c.plan.big == GEMM_X3) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
+        use_planes(c, g.b, PL_D10);
+        hipLaunchKernelGGL((k_x3_gemm<true, true, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
+    } else if (c.plan.dz11_bf16) {   // bf16 storage: the fused fc11 kernel of this step wrote dZ11 as bf16
+        g.a.src16 = 1;
+        g.a_arm = (int64_t)d.B * d.D / 2;
+        hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 1>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+    } else
+        hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
+    HIP_LAUNCH_CHECK("k_bf16_gemm<dW11>");
     return 0;
 }
 

@@ -619,7 +619,7 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 int launch_fc1_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
-    const int use_mask = (c.h.training && c.h.x_drop > 0.f) ? 1 : 0;
+    const int use_mask = c.dropout() ? 1 : 0;
     NoiseDev nd = make_noise_dev(nz, c.h);
     const int vec_ok = ((d.D & 3) == 0) && aligned16(x) && aligned16(params) && ((xs & 3) == 0) &&
                        (nd.mode != 0 || !use_mask || ((reinterpret_cast<uintptr_t>(nd.x_mask) & 3) == 0));
@@ -634,7 +634,7 @@ int launch_fc1_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, con
 int launch_fc1_epi(const Ctx& c, const float* params) {
     const mmvae_dims& d = c.d;
     const int KS = c.lay.sp.ks_fc1;
-    const float scale = (c.h.training && c.h.x_drop > 0.f) ? 1.f / (1.f - c.h.x_drop) : 1.f;
+    const float scale = c.dropout() ? 1.f / (1.f - c.h.x_drop) : 1.f;
     long long* acc = c.h.training && c.use_acc() ? reinterpret_cast<long long*>(c.ws + acc_set_off(c.lay, d.A, 0)) : nullptr;
     const dim3 grid(c.lay.nblk32, d.A);
     // the smallest slab-load chunk (4 / 8 / 16 in flight per row) that covers the split count
@@ -655,15 +655,12 @@ int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t
     const mmvae_dims& d = c.d;
     const int ldk = rup(d.H, 8) + 4;
     const size_t shm = (size_t)(F11_BM * ldk + F11_BN * ldk + F11_BM * F11_LDZ + 8) * sizeof(float);
-    const float am1 = (float)(d.A > 1 ? d.A - 1 : 1);
-    const float coef = am1 / (float)d.B;
     const int NS = c.lay.sp.ns_fc11;
     dim3 grid(c.lay.nblk64, NS, d.A);
-    hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + c.lay.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * c.lay.n11, c.stream);
-    if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
+    if (int rc = zero_fc11_part(c)) return rc;
     hipLaunchKernelGGL(k_fc11_fused, grid, dim3(256), shm, c.stream, c.ws + c.lay.Dk[4], params, c.po.per_arm,
                        c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + c.lay.DZ11, c.ws + c.lay.GD10_slab,
-                       c.ws + c.lay.fc11_part, coef, need_grad, d.A, d.B, d.D, d.H, NS, ldk,
+                       c.ws + c.lay.fc11_part, c.fc11_coef(), need_grad, d.A, d.B, d.D, d.H, NS, ldk,
                        (int)(aligned16(params)), c.lay.n11);
     HIP_LAUNCH_CHECK("k_fc11_fused");
     return 0;
@@ -684,7 +681,7 @@ int launch_dw_big(const Ctx& c, const mmvae_noise* nz, const float* x, int64_t x
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     NoiseDev nd = make_noise_dev(nz, c.h);
-    const int use_mask = (c.h.training && c.h.x_drop > 0.f) ? 1 : 0;
+    const int use_mask = c.dropout() ? 1 : 0;
     const int KS = L.sp.ks_dw;
     // dW1[h][d] = sum_b dZ1[b][h] * x~[b][d]          -> slab [KS][A][H][D]
     TnDescs t1{}, t2{};

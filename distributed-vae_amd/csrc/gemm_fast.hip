@@ -1382,7 +1382,7 @@ int launch_forward_zero(const Ctx& c, const mmvae_noise* nz) {
 }
 
 int launch_make_xbits(const Ctx& c, const mmvae_noise* nz) {
-    if (!(c.h.training && c.h.x_drop > 0.f)) return 0;
+    if (!c.dropout()) return 0;
     const mmvae_dims& d = c.d;
     NoiseDev nd = make_noise_dev(nz, c.h);
     const int wpr = cdiv(d.D, 32);
@@ -1396,10 +1396,9 @@ int launch_make_xbits(const Ctx& c, const mmvae_noise* nz) {
     return 0;
 }
 
-int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64_t xs) {
-    if (c.plan.big == GEMM_BF16 || c.plan.big == GEMM_X3) return launch_fc1_fwd_bf16(c, params, x, xs);
+int launch_fc1_fwd_fp32(const Ctx& c, const float* params, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
-    const bool use_mask = c.h.training && c.h.x_drop > 0.f;
+    const bool use_mask = c.dropout();
     const int KS = c.lay.sp.ks_fc1;
     dim3 grid(cdiv(d.B, 128), KS, d.A);
     const uint32_t* bits = reinterpret_cast<const uint32_t*>(c.ws + c.lay.xbits);
@@ -1423,143 +1422,134 @@ int launch_fc1_fwd_fast(const Ctx& c, const float* params, const float* x, int64
     return 0;
 }
 
-int launch_fc11_out(const Ctx& c, const float* params, float* x_rec) {
-    if (c.plan.fc11 == FC11_GENERAL) return launch_fc11_fused_out(c, params, x_rec);
-    if (c.plan.fc11 == FC11_OUT_BF16 || c.plan.fc11 == FC11_OUT_X3) return launch_fc11_out_bf16(c, x_rec);
-    if (c.plan.fc11 != FC11_ZT) { set_error("internal: decode plan names fc11 family %d", (int)c.plan.fc11); return MMVAE_E_LAUNCH; }
-    // k_fc11_zt's template arguments and gene split (without the loss slots' limit)
-    const mmvae_dims& d = c.d;
-    const int ldk = rup(d.H, 8) + 4;
-    const int ntall = cdiv(d.D, 64), kgv = rup(d.H, 8) / 8;
+// k_fc11_zt and k_fc11_zt_out: the template variant (fc_dim 100 / 128 / any other) and the gene split -- one 512-thread
+// workgroup per CU, so the gene range is split until the grid fills the chip once
+struct ZtShape { int ldk, nb, nsz; bool h100, h128; };
+static ZtShape zt_shape(const mmvae_dims& d) {
     const int nb = cdiv(d.B, 256);
-    const int nsz = max(1, min(min(256 / max(nb * d.A, 1), 16), ntall));
-    const size_t shm = (size_t)(64 * ldk) * sizeof(float);
-    const dim3 grid(nb, nsz, d.A);
+    return ZtShape{rup(d.H, 8) + 4, nb, max(1, min(min(256 / max(nb * d.A, 1), 16), cdiv(d.D, 64))), d.H == 100, d.H == 128};
+}
+
+int launch_fc11_zt_out(const Ctx& c, const float* params, float* x_rec) {
+    const mmvae_dims& d = c.d;
+    const ZtShape z = zt_shape(d);
+    const size_t shm = (size_t)(64 * z.ldk) * sizeof(float);
+    const dim3 grid(z.nb, z.nsz, d.A);
 #define FZO_LAUNCH(KG, EX, BK) \
     hipLaunchKernelGGL((k_fc11_zt_out<KG, EX, BK>), grid, dim3(512), shm, c.stream, c.ws + c.lay.Dk[4], params, c.po.per_arm, \
-                       c.po.o[26], c.po.o[27], x_rec, d.A, d.B, d.D, d.H, ldk)
-    if (kgv == 13 && d.H == 100) FZO_LAUNCH(13, true, true);
-    else if (kgv == 16 && d.H == 128) FZO_LAUNCH(16, true, false);
+                       c.po.o[26], c.po.o[27], x_rec, d.A, d.B, d.D, d.H, z.ldk)
+    if (z.h100) FZO_LAUNCH(13, true, true);
+    else if (z.h128) FZO_LAUNCH(16, true, false);
     else FZO_LAUNCH(16, false, false);
 #undef FZO_LAUNCH
     HIP_LAUNCH_CHECK("k_fc11_zt_out");
     return 0;
 }
 
-int launch_fc11(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad,
-                int which /*bit0: x_rec/loss/dZ11 kernel, bit1: d(d10) GEMM*/) {
-    if (c.plan.fc11 == FC11_GENERAL) return launch_fc11_fused(c, params, x, xs, x_rec, need_grad);
-    if (c.plan.fc11 == FC11_BF16 || c.plan.fc11 == FC11_X3) return launch_fc11_bf16(c, params, x, xs, x_rec, need_grad, which);
+int launch_fc11_zg(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     const int ldk = rup(d.H, 8) + 4;
-    const float coef = (float)(d.A > 1 ? d.A - 1 : 1) / (float)d.B;
-    const int NS = L.sp.ns_fc11;
-    const bool use_zg = c.plan.fc11 == FC11_ZG;
-    if ((which & 1) && use_zg) {
-        hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
-        if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
-        const size_t shm = (size_t)(3 * 64 * ldk + 8 * 32 * ZG_LD + 16) * sizeof(float);
-        // (152 KB of dynamic LDS: this runtime takes it without the hipFuncSetAttribute opt-in, and the library keeps no
-        // per-process flag for having asked)
-        hipLaunchKernelGGL((k_fc11_zg<13, true, true>), dim3(cdiv(d.B, 256), L.sp.ks_gd10, d.A), dim3(512), shm, c.stream,
-                           c.ws + L.Dk[4], params, c.po.per_arm, c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + L.DZ11,
-                           c.ws + L.fc11_part, L.n11, coef, need_grad, d.A, d.B, d.D, d.H, ldk, c.ws + L.GD10_slab);
-        HIP_LAUNCH_CHECK("k_fc11_zg");
-    }
-    if (use_zg) return 0;
-    if (which & 1) {
-        // loss partials: the launch below fills a subset of the reserved slots
-        hipError_t e = c.plan.zero != ZERO_NONE ? hipSuccess : hipMemsetAsync(c.ws + L.fc11_part, 0, sizeof(float) * 2 * (size_t)d.A * L.n11, c.stream);
-        if (e != hipSuccess) { set_error("memset: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
-        const int ntall = cdiv(d.D, 64);
-        const int kgv = rup(d.H, 8) / 8;
-        {
-            // one 512-thread workgroup per CU: split the gene range so that the grid fills the chip once
-            const int nb = cdiv(d.B, 256);
-            int nsz = max(1, min(min(256 / max(nb * d.A, 1), 16), ntall));
-            while (nsz > 1 && (int64_t)nb * nsz > L.n11) --nsz;
-            const size_t shm = (size_t)(2 * 64 * ldk + 16) * sizeof(float);
-            dim3 grid(nb, nsz, d.A);
-#define FZT_ARGS c.ws + L.Dk[4], params, c.po.per_arm, c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + L.DZ11,        \
-                 c.ws + L.fc11_part, L.n11, coef, need_grad, d.A, d.B, d.D, d.H, ldk
-#define FZT_LAUNCH(KG, EX, BK, XR) \
-    hipLaunchKernelGGL((k_fc11_zt<KG, EX, BK, XR>), grid, dim3(512), shm, c.stream, FZT_ARGS)
-            const bool xr = x_rec != nullptr;
-            // without x_rec the kernel always writes dZ11 (workspace), wanted or not: one variant fewer
-            if (kgv == 13 && d.H == 100) {
-                if (xr) FZT_LAUNCH(13, true, true, true);
-                else FZT_LAUNCH(13, true, true, false);
-            } else if (kgv == 16 && d.H == 128) {
-                if (xr) FZT_LAUNCH(16, true, false, true);
-                else FZT_LAUNCH(16, true, false, false);
-            } else {
-                if (xr) FZT_LAUNCH(16, false, false, true);
-                else FZT_LAUNCH(16, false, false, false);
-            }
-#undef FZT_LAUNCH
-#undef FZT_ARGS
-            HIP_LAUNCH_CHECK("k_fc11_zt");
-        }
-    }
-    if (need_grad && (which & 2)) {
-        if (d.H == 100)
-            hipLaunchKernelGGL(k_gd10_v3, dim3(cdiv(d.B, 128), L.sp.ks_gd10, d.A), dim3(256), 0, c.stream, c.ws + L.DZ11,
-                               params, c.po.per_arm, c.po.o[26], c.ws + L.GD10_slab, d.A, d.B, d.D, d.H, L.sp.ks_gd10);
-        else
-        hipLaunchKernelGGL(k_gd10_v2, dim3(cdiv(d.B, 128), L.sp.ks_gd10, d.A), dim3(256), 0, c.stream, c.ws + L.DZ11,
-                           params, c.po.per_arm, c.po.o[26], c.ws + L.GD10_slab, d.A, d.B, d.D, d.H, L.sp.ks_gd10);
-        HIP_LAUNCH_CHECK("k_gd10_v2");
-    }
+    if (int rc = zero_fc11_part(c)) return rc;
+    const size_t shm = (size_t)(3 * 64 * ldk + 8 * 32 * ZG_LD + 16) * sizeof(float);
+    // (152 KB of dynamic LDS: this runtime takes it without the hipFuncSetAttribute opt-in, and the library keeps no
+    // per-process flag for having asked)
+    hipLaunchKernelGGL((k_fc11_zg<13, true, true>), dim3(cdiv(d.B, 256), L.sp.ks_gd10, d.A), dim3(512), shm, c.stream,
+                       c.ws + L.Dk[4], params, c.po.per_arm, c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + L.DZ11,
+                       c.ws + L.fc11_part, L.n11, c.fc11_coef(), need_grad, d.A, d.B, d.D, d.H, ldk, c.ws + L.GD10_slab);
+    HIP_LAUNCH_CHECK("k_fc11_zg");
     return 0;
 }
 
-int launch_dw_big_fast(const Ctx& c, const float* x, int64_t xs, int which) {
-    if (c.plan.big == GEMM_BF16 || c.plan.big == GEMM_X3) return launch_dw_big_bf16(c, x, xs, which);
+int launch_fc11_zt(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
-    const bool use_mask = c.h.training && c.h.x_drop > 0.f;
+    // loss partials: the launch below fills a subset of the reserved slots
+    if (int rc = zero_fc11_part(c)) return rc;
+    ZtShape z = zt_shape(d);
+    while (z.nsz > 1 && (int64_t)z.nb * z.nsz > L.n11) --z.nsz;
+    const size_t shm = (size_t)(2 * 64 * z.ldk + 16) * sizeof(float);
+    dim3 grid(z.nb, z.nsz, d.A);
+#define FZT_LAUNCH(KG, EX, BK, XR) \
+    hipLaunchKernelGGL((k_fc11_zt<KG, EX, BK, XR>), grid, dim3(512), shm, c.stream, c.ws + L.Dk[4], params, c.po.per_arm,    \
+                       c.po.o[26], c.po.o[27], x, xs, x_rec, c.ws + L.DZ11, c.ws + L.fc11_part, L.n11, c.fc11_coef(), need_grad, \
+                       d.A, d.B, d.D, d.H, z.ldk)
+    const bool xr = x_rec != nullptr;
+    // without x_rec the kernel always writes dZ11 (workspace), wanted or not: one variant fewer
+    if (z.h100) {
+        if (xr) FZT_LAUNCH(13, true, true, true);
+        else FZT_LAUNCH(13, true, true, false);
+    } else if (z.h128) {
+        if (xr) FZT_LAUNCH(16, true, false, true);
+        else FZT_LAUNCH(16, true, false, false);
+    } else {
+        if (xr) FZT_LAUNCH(16, false, false, true);
+        else FZT_LAUNCH(16, false, false, false);
+    }
+#undef FZT_LAUNCH
+    HIP_LAUNCH_CHECK("k_fc11_zt");
+    return 0;
+}
+
+int launch_gd10_fp32(const Ctx& c, const float* params) {
+    const mmvae_dims& d = c.d;
+    const Layout& L = c.lay;
+    const dim3 grid(cdiv(d.B, 128), L.sp.ks_gd10, d.A);
+    if (d.H == 100)
+        hipLaunchKernelGGL(k_gd10_v3, grid, dim3(256), 0, c.stream, c.ws + L.DZ11, params, c.po.per_arm, c.po.o[26],
+                           c.ws + L.GD10_slab, d.A, d.B, d.D, d.H, L.sp.ks_gd10);
+    else
+        hipLaunchKernelGGL(k_gd10_v2, grid, dim3(256), 0, c.stream, c.ws + L.DZ11, params, c.po.per_arm, c.po.o[26],
+                           c.ws + L.GD10_slab, d.A, d.B, d.D, d.H, L.sp.ks_gd10);
+    HIP_LAUNCH_CHECK("k_gd10_v2");
+    return 0;
+}
+
+// dW1[h][d] = sum_b dZ1[b][h] x~[b][d]   -> slab [KS][A][H][D]
+int launch_dw1_fp32(const Ctx& c, const float* x, int64_t xs) {
+    const mmvae_dims& d = c.d;
+    const Layout& L = c.lay;
+    const bool use_mask = c.dropout();
     const int KS = L.sp.ks_dw;
     const uint32_t* bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits);
     const int wpr = cdiv(d.D, 32);
-    if (which & 1) {   // dW1[h][d] = sum_b dZ1[b][h] x~[b][d]   -> slab [KS][A][H][D]
-        const int tiles_n = cdiv(d.D, 128);
-        dim3 grid(cdiv(d.H, 128) * tiles_n, KS, d.A);
-        if (d.H == 100) {
-            if (use_mask)
-                hipLaunchKernelGGL((k_tn_v3m<true>), grid, dim3(256), 0, c.stream, c.ws + L.DZ[1],
-                                   (int64_t)d.B * d.H, d.H, d.H, x, xs, d.D, d.D, bits, wpr, c.ws + L.dw1_slab,
-                                   (int64_t)d.H * d.D, (int64_t)d.A * d.H * d.D, d.D, d.B, KS, tiles_n);
-            else
-                hipLaunchKernelGGL((k_tn_v3m<false>), grid, dim3(256), 0, c.stream, c.ws + L.DZ[1],
-                                   (int64_t)d.B * d.H, d.H, d.H, x, xs, d.D, d.D, bits, wpr, c.ws + L.dw1_slab,
-                                   (int64_t)d.H * d.D, (int64_t)d.A * d.H * d.D, d.D, d.B, KS, tiles_n);
-            HIP_LAUNCH_CHECK("k_tn_v3m<dW1>");
-        } else
-        if (use_mask)
-            hipLaunchKernelGGL((k_tn_v2<true, false>), grid, dim3(256), 0, c.stream, c.ws + L.DZ[1],
-                               (int64_t)d.B * d.H, d.H, d.H, x, xs, d.D, d.D, bits, wpr, c.ws + L.dw1_slab,
-                               (int64_t)d.H * d.D, (int64_t)d.A * d.H * d.D, d.D, d.B, KS, tiles_n);
-        else
-            hipLaunchKernelGGL((k_tn_v2<false, false>), grid, dim3(256), 0, c.stream, c.ws + L.DZ[1],
-                               (int64_t)d.B * d.H, d.H, d.H, x, xs, d.D, d.D, bits, wpr, c.ws + L.dw1_slab,
-                               (int64_t)d.H * d.D, (int64_t)d.A * d.H * d.D, d.D, d.B, KS, tiles_n);
-        HIP_LAUNCH_CHECK("k_tn_v2<dW1>");
+    const int tiles_n = cdiv(d.D, 128);
+    dim3 grid(cdiv(d.H, 128) * tiles_n, KS, d.A);
+#define DW1_LAUNCH(K) \
+    hipLaunchKernelGGL(K, grid, dim3(256), 0, c.stream, c.ws + L.DZ[1], (int64_t)d.B * d.H, d.H, d.H, x, xs, d.D, d.D, bits, wpr, \
+                       c.ws + L.dw1_slab, (int64_t)d.H * d.D, (int64_t)d.A * d.H * d.D, d.D, d.B, KS, tiles_n)
+    if (d.H == 100) {
+        if (use_mask) DW1_LAUNCH((k_tn_v3m<true>));
+        else DW1_LAUNCH((k_tn_v3m<false>));
+        HIP_LAUNCH_CHECK("k_tn_v3m<dW1>");
+    } else if (use_mask) {
+        DW1_LAUNCH((k_tn_v2<true, false>));
+    } else {
+        DW1_LAUNCH((k_tn_v2<false, false>));
     }
-    if (which & 2) {   // [dW11 | db11][j][h] = sum_b dZ11[b][j] [d10 | 1][b][h]   -> slab [KS][A][D][DW11_LD]
-        const int tiles_n = cdiv(d.H + 1, 128);
-        const int KS11 = L.sp.ks_dw11;
-        dim3 grid(cdiv(d.D, 128) * tiles_n, KS11, d.A);
-        if (d.H == 100)
-            hipLaunchKernelGGL(k_tn_v3n, grid, dim3(256), 0, c.stream, c.ws + L.DZ11, (int64_t)d.B * d.D,
-                               d.D, d.D, c.ws + L.Dk[4], (int64_t)d.B * d.H, d.H, d.H, bits, wpr, c.ws + L.dw11_slab,
-                               (int64_t)d.D * DW11_LD, (int64_t)d.A * d.D * DW11_LD, DW11_LD, d.B, KS11, tiles_n);
-        else
+#undef DW1_LAUNCH
+    HIP_LAUNCH_CHECK("k_tn_v2<dW1>");
+    return 0;
+}
+
+// [dW11 | db11][j][h] = sum_b dZ11[b][j] [d10 | 1][b][h]   -> slab [KS][A][D][DW11_LD]
+int launch_dw11_fp32(const Ctx& c) {
+    const mmvae_dims& d = c.d;
+    const Layout& L = c.lay;
+    const uint32_t* bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits);
+    const int wpr = cdiv(d.D, 32);
+    const int tiles_n = cdiv(d.H + 1, 128);
+    const int KS11 = L.sp.ks_dw11;
+    dim3 grid(cdiv(d.D, 128) * tiles_n, KS11, d.A);
+    if (d.H == 100)
+        hipLaunchKernelGGL(k_tn_v3n, grid, dim3(256), 0, c.stream, c.ws + L.DZ11, (int64_t)d.B * d.D,
+                           d.D, d.D, c.ws + L.Dk[4], (int64_t)d.B * d.H, d.H, d.H, bits, wpr, c.ws + L.dw11_slab,
+                           (int64_t)d.D * DW11_LD, (int64_t)d.A * d.D * DW11_LD, DW11_LD, d.B, KS11, tiles_n);
+    else
         hipLaunchKernelGGL((k_tn_v2<false, true>), grid, dim3(256), 0, c.stream, c.ws + L.DZ11, (int64_t)d.B * d.D,
                            d.D, d.D, c.ws + L.Dk[4], (int64_t)d.B * d.H, d.H, d.H, bits, wpr, c.ws + L.dw11_slab,
                            (int64_t)d.D * DW11_LD, (int64_t)d.A * d.D * DW11_LD, DW11_LD, d.B, KS11, tiles_n);
-        HIP_LAUNCH_CHECK("k_tn_v2<dW11>");
-    }
+    HIP_LAUNCH_CHECK("k_tn_v2<dW11>");
     return 0;
 }
 

@@ -1464,7 +1464,8 @@ int launch_lat_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, flo
     NoiseDev nd = make_noise_dev(nz, c.h);
     const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
     if (c.plan.lat_half) {
-        launch_k(c, k_lat_fwd_h, dim3(c.lay.nblkl, c.d.A), dim3(64 * LH_NW), shm, a, nd, params, c.ws, bn_running, nbt);
+        // (lat_fork_rides implies lat_half, i.e. this launch)
+        launch_k(c, c.plan.lat_fork_rides ? c.ev(EV_LAT) : nullptr, k_lat_fwd_h, dim3(c.lay.nblkl, c.d.A), dim3(64 * LH_NW), shm, a, nd, params, c.ws, bn_running, nbt);
         HIP_LAUNCH_CHECK("k_lat_fwd_h");
         return 0;
     }
@@ -1539,7 +1540,7 @@ int launch_reduce_grads(const Ctx& c, float* grads, float gscale, const AdamHost
     const int A = d.A, H = d.H, D = d.D, Ld = d.L, C = d.C, S = d.S;
     RedDescs ds{};
     int n = 0;
-    const float xscale = (c.h.training && c.h.x_drop > 0.f) ? 1.f / (1.f - c.h.x_drop) : 1.f;
+    const float xscale = c.dropout() ? 1.f / (1.f - c.h.x_drop) : 1.f;
     // big: fc1.w, fc11.w, fc11.b
     const int ks11 = c.plan.dw11_slabs;
     ds.d[n++] = RedDesc{c.ws + L.dw1_slab, (int64_t)A * H * D, (int64_t)H * D, D, 0, H, D, c.po.o[0], D, gscale * xscale, L.sp.ks_dw};

@@ -455,3 +455,44 @@ def test_eval_forward_and_classify_labels_against_oracle(name, engine):
         print(f"   {nm}: {err:.2e}")
         assert err < tol, (nm, err)
     assert n_cls <= cap and n_fwd <= cap, (n_cls, n_fwd, cap)
+
+
+def _replay(eng, ws0, stages, hyper, nz, params, xd, xs, poison=()):
+    """The workspace after replaying `stages` on the state `ws0` (NaN in the `poison` views first: a replay must write them)."""
+    eng.ws.copy_(ws0)
+    for v in poison:
+        v.fill_(float("nan"))
+    for s in stages:
+        eng.debug_stage(s, hyper, nz, params, xd, xs)
+    torch.cuda.synchronize()
+    return eng.ws.clone()
+
+
+@pytest.mark.parametrize("engine", ENGINES)
+@pytest.mark.parametrize("name", ["h100", "h108"])
+def test_single_launch_stages_replay_the_combined_stages_bit_for_bit(name, engine):
+    """Debug stages 10 / 11 (fc11's main launch, d(d10)) and 12 / 13 (dW1, dW11) are the launches of stages 1 and 2, one at a
+    time: after a full step, replaying 10 then 11 leaves the workspace -- dZ11 and the d(d10) slabs in it -- bit-equal to
+    replaying 1, and 12 then 13 (the dW1 / dW11 slabs) bit-equal to replaying 2.  The same kernels on the same inputs: no
+    tolerance.  dZ11 and the slabs the decoder backward sums are NaN-filled before the fc11 replays and must come back finite.
+    (fc_dim 100 and 108: FC11_ZG / FC11_ZT on engine 0, the fused kernels of the other two, whose stage 11 launches nothing.)"""
+    from distributed_vae_amd import _native as N
+    row = P.BY_NAME[name]
+    U, h, sd, x, noise, m, eng = _env(row, engine)
+    noise_dev = U.noise_to_device(noise)
+    params, xd, xs = _place(m, x, None)
+    hyper, nz = m._hyper(1.0, False), N.make_noise(noise_dev)
+    plan = _assert_plan(row, engine, eng, hyper, params, xd, xs)
+    _fused(m, eng, noise_dev, params, xd, xs, (m._bn_flat.clone(), m._nbt.clone()))
+    ws0 = eng.ws.clone()
+    dz11 = eng.ws_view("dz11", row.D)
+    gd10 = eng.ws_raw("gd10_slab", plan["gd10_slabs"] * row.A * row.B * row.H)
+    bits = lambda t: t.view(torch.int32)
+    both = _replay(eng, ws0, (1,), hyper, nz, params, xd, xs, (dz11, gd10))
+    assert bool(torch.isfinite(dz11).all()) and bool(torch.isfinite(gd10).all())
+    apart = _replay(eng, ws0, (10, 11), hyper, nz, params, xd, xs, (dz11, gd10))
+    assert bool(torch.isfinite(dz11).all()) and bool(torch.isfinite(gd10).all())
+    assert torch.equal(bits(both), bits(apart)), "stage 1 vs 10 + 11"
+    both = _replay(eng, ws0, (2,), hyper, nz, params, xd, xs)
+    apart = _replay(eng, ws0, (12, 13), hyper, nz, params, xd, xs)
+    assert torch.equal(bits(both), bits(apart)), "stage 2 vs 12 + 13"
