@@ -304,6 +304,37 @@ def loss(out, xs: Sequence[Tensor], h: Hyper):
             sum(c_l2) / len(c_l2), kls, [], lls)
 
 
+TERMS = ("rec", "kl", "ent", "dist")
+
+
+def loss_terms(out, xs: Sequence[Tensor], h: Hyper):
+    """``loss()``'s total split into its four differentiable terms, each with the coefficient it carries there, and the
+    constant: ``rec`` = (A-1) sum_a rec_a, ``kl`` = (A-1) beta sum_a kl_a, ``ent`` = sum_pairs ent, ``dist`` = lam
+    sum_pairs c_dist, ``const`` = n_pairs (C/2 log 2 pi - 1/2 log 2 lam) (a float).  The same formulas, line for line
+    (nn_model.py:542-546, :565, :567-569, :592-596); ``sum(terms) + const == loss()[0]`` to rounding."""
+    x_recs, _, _, _, cs, _, _, s_means, s_logvars, _ = out
+    A, C, eps = h.n_arm, h.n_categories, h.eps
+    B = xs[0].shape[0]
+    if A < 2:
+        raise ZeroDivisionError("n_arm == 1: reference loss divides by len([]) (nn_model.py:592)")
+    logc = [torch.log(c + eps) for c in cs]
+    ivar = [torch.sqrt(1.0 / (c.var(0) + eps)) for c in cs]
+    recs, kls, ents, dists = [], [], [], []
+    for a in range(A):
+        x, xr = xs[a], x_recs[a]
+        se = ((xr - x) ** 2).sum()
+        mism = ((xr > 0.1) != (x > 0.1)).to(x.dtype).mean()
+        recs.append(0.5 * se / B + 0.5 * (100.0 * mism))
+        kls.append((-0.5 * torch.mean(1 + s_logvars[a] - s_means[a] ** 2 - torch.exp(s_logvars[a]), dim=0)).sum())
+        for b in range(a + 1, A):
+            ents.append((cs[a] * logc[a]).sum(-1).mean() + (cs[b] * logc[b]).sum(-1).mean())
+            dists.append(((logc[a] * ivar[a] - logc[b] * ivar[b]) ** 2).sum(-1).mean())
+    n_pairs = A * (A - 1) / 2
+    am1 = max(A - 1, 1)
+    return {"rec": am1 * sum(recs), "kl": am1 * h.beta * sum(kls), "ent": sum(ents), "dist": h.lam * sum(dists),
+            "const": n_pairs * ((C / 2) * math.log(2 * math.pi) - 0.5 * math.log(2 * h.lam))}
+
+
 # --------------------------------------------------------------------------- step
 
 def grads_autograd(sd, xs, h: Hyper, noise, **fw):
@@ -319,6 +350,22 @@ def grads_autograd(sd, xs, h: Hyper, noise, **fw):
         if k not in leaves:
             sd[k] = work[k]
     return out, lt, dict(zip(keys, gs))
+
+
+def term_grads(sd, xs, h: Hyper, noise, **fw):
+    """``{term: {param: grad}}`` for the terms of ``loss_terms``: one forward, one ``autograd.grad`` per term (a parameter
+    a term does not reach gets zeros).  ``sd`` is left unchanged (no running-statistics update)."""
+    keys = param_keys(h)
+    leaves = {k: sd[k].detach().clone().requires_grad_(True) for k in keys}
+    work = dict(sd)
+    work.update(leaves)
+    out = forward(work, xs, h, noise, **fw)
+    terms = loss_terms(out, xs, h)
+    res = {}
+    for t in TERMS:
+        gs = torch.autograd.grad(terms[t], [leaves[k] for k in keys], retain_graph=True, allow_unused=True)
+        res[t] = {k: (torch.zeros_like(leaves[k]) if g is None else g) for k, g in zip(keys, gs)}
+    return res
 
 
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, t: int, lr=1e-3, b1=0.9, b2=0.999,
