@@ -662,12 +662,18 @@ __device__ __forceinline__ bool xmask_keep(const NoiseDev& nz, int arm, int row,
     const u32x4 w = xmask_words(nz, arm, (uint32_t)row, (uint32_t)col >> epg_log2);
     return xmask_field_keep(nz, w, (uint32_t)col & ((1u << epg_log2) - 1u));
 }
+// Keep-mask words one work item of make_xbits_range writes: with m <= 4 bits per element one Philox call (128 bits) fills
+// 4 / m words; otherwise, and for an explicit mask, one word.  The launchers size their grids by it.
+__host__ __device__ __forceinline__ int xbits_words_per_thread(const NoiseDev& nz) {
+    const uint32_t mlog2 = nz.x_mlog2, m = 1u << mlog2;
+    return nz.mode != 0 && m <= 4 ? (int)(4u >> mlog2) : 1;
+}
 // The bit-packed dropout keep-mask of x (k_make_xbits, gemm_fast.hip; also a role of the step's prologue launch,
 // gemm_bf16.hip): threads first, first + stride, ... of the A * B * ceil(wpr / words-per-thread) work items.
 __device__ __forceinline__ void make_xbits_range(const NoiseDev& nz, int A, int B, int D, int wpr, uint32_t* __restrict__ bits,
                                                  int64_t first, int64_t stride) {
     const uint32_t mlog2 = nz.x_mlog2, m = 1u << mlog2;
-    const int wpt = nz.mode != 0 && m <= 4 ? (int)(4u >> mlog2) : 1;      // words per thread
+    const int wpt = xbits_words_per_thread(nz);
     const int tpr = (wpr + wpt - 1) / wpt;                // threads per row
     const int64_t n = (int64_t)A * B * tpr;
     for (int64_t i = first; i < n; i += stride) {

@@ -1034,6 +1034,7 @@ __global__ __launch_bounds__(256, 2) void k_bf16_fc11(const GemmArgs g_in) {
 // that go to the LDS image as they are, instead of fp32 rounded by every block (half the bytes from L2, no conversion; the
 // timing ablation prices the fp32 tiles at 13 of the kernel's 84 us: profiles/r04_bf16_fc11g_ablation.txt; 84 -> 75 us.  Requesting
 // x one half tile ahead in the registers this frees was measured too: 75.1 against 74.5 us, not kept)
+static_assert(KT == 64, "W16: a row of W11's planes (128 bf16) is exactly the two K tiles in LDS");
 template <bool S16, bool W16 = false>
 __global__ __launch_bounds__(256, 2) void k_bf16_fc11g(const GemmArgs g_in) {
     const GemmArgs g = g_in;
@@ -1760,29 +1761,41 @@ __global__ __launch_bounds__(512, 1) void k_x3_small(const TnDescs descs, int nd
 // ---------------------------------------------------------------------------------------------------------------
 // host launchers (same workspace layouts and split factors as the fp32 fast path)
 // ---------------------------------------------------------------------------------------------------------------
-static Operand kmajor(const float* p, int64_t ld, int rows, int K) { return Operand{p, ld, rows, K, 0, nullptr, 0, -1, nullptr, 0, 0, 0, nullptr, 0, 0, 0}; }
-static Operand kminor(const float* p, int64_t ld, int rows, int K) { return Operand{p, ld, rows, K, 1, nullptr, 0, -1, nullptr, 0, 0, 0, nullptr, 0, 0, 0}; }
+static Operand kmajor(const float* p, int64_t ld, int rows, int K) {
+    Operand o{};
+    o.ptr = p; o.ld = ld; o.rows = rows; o.K = K; o.ones_row = -1;
+    return o;
+}
+static Operand kminor(const float* p, int64_t ld, int rows, int K) { Operand o = kmajor(p, ld, rows, K); o.kminor = 1; return o; }
 
 // Slice planes of the four small operands (fp32x3 engine).  They are written at fixed points of the step -- W1 and
 // [W11 | b11] at the start of the forward pass (launch_x3_planes), [d10 | 1] by the decoder chain, dZ1 by k_bn_bwd_apply
 // behind the encoder's backward chain (Plan) -- and read by the GEMM launchers below, which only fill in the
 // operand's plane fields.
-static inline int rup_i(int a, int b) { return cdiv(a, b) * b; }
 enum { PL_W1 = 0, PL_W11 = 1, PL_D10 = 2, PL_DZ1 = 3 };
 struct PlaneGeom { int R, C, Rp, Cp, ones_col; int64_t ws_off; };
 static PlaneGeom plane_geom(const Ctx& c, int kind) {
     const mmvae_dims& d = c.d;
     switch (kind) {
-        case PL_W1:  return PlaneGeom{d.H, d.D, 128, rup_i(d.D, 32), -1, c.lay.pl_w1};                 // W1 [H][D]
-        case PL_W11: return PlaneGeom{d.D, d.H, rup_i(d.D, 128), 128, d.H, c.lay.pl_w11};              // [W11 | b11] [D][H + 1]
-        case PL_D10: return PlaneGeom{d.B, d.H, rup_i(d.B, 256), 128, d.H, c.lay.pl_d10};              // [d10 | 1] [B][H + 1]
-        default:     return PlaneGeom{d.B, d.H, rup_i(d.B, 256), 128, -1, c.lay.pl_dz1};               // dZ1 [B][H]
+        case PL_W1:  return PlaneGeom{d.H, d.D, 128, rup(d.D, 32), -1, c.lay.pl_w1};                 // W1 [H][D]
+        case PL_W11: return PlaneGeom{d.D, d.H, rup(d.D, 128), 128, d.H, c.lay.pl_w11};              // [W11 | b11] [D][H + 1]
+        case PL_D10: return PlaneGeom{d.B, d.H, rup(d.B, 256), 128, d.H, c.lay.pl_d10};              // [d10 | 1] [B][H + 1]
+        default:     return PlaneGeom{d.B, d.H, rup(d.B, 256), 128, -1, c.lay.pl_dz1};               // dZ1 [B][H]
     }
 }
 static void use_planes(const Ctx& c, Operand& o, int kind) {
     const PlaneGeom g = plane_geom(c, kind);
     o.pl = reinterpret_cast<const unsigned short*>(c.ws + g.ws_off);
     o.pl_plane = (int64_t)g.Rp * g.Cp; o.pl_arm = 3 * o.pl_plane; o.pl_ld = g.Cp;
+}
+// bf16 storage (Plan::narrow): slice 0 of a plane set IS the matrix rounded to bf16; the bf16 engine reads the operand from it in
+// sixteen-byte pieces, like x (half the bytes of fp32).  whole: rows and K become the planes' zero-padded extents (K-major).
+// Returns the arm stride in FLOATS of the kernels' pointer arithmetic (the planes' elements are two bytes).
+static int64_t read_slice0_bf16(const Ctx& c, Operand& o, int kind, bool whole = false) {
+    const PlaneGeom g = plane_geom(c, kind);
+    o.ptr = reinterpret_cast<const float*>(c.ws + g.ws_off); o.ld = g.Cp; o.src16 = 1;
+    if (whole) { o.rows = g.Rp; o.K = g.Cp; }
+    return 3 * (int64_t)g.Rp * g.Cp / 2;
 }
 static SplitJob plane_job(const Ctx& c, int kind, const float* src, int64_t ld, int64_t src_arm, const float* col_src = nullptr, int64_t col_arm = 0) {
     const PlaneGeom g = plane_geom(c, kind);
@@ -1828,8 +1841,7 @@ int launch_x3_planes(const Ctx& c, const float* params, bool head, const mmvae_n
         xb.nz = make_noise_dev(nz, c.h);
         xb.A = d.A; xb.B = d.B; xb.D = d.D; xb.wpr = cdiv(d.D, 32);
         xb.bits = reinterpret_cast<uint32_t*>(c.ws + c.lay.xbits);
-        const int wpt = xb.nz.mode != 0 && xb.nz.x_mlog2 <= 2 ? (int)(4u >> xb.nz.x_mlog2) : 1;   // as in make_xbits_range
-        xb.blocks = (int)imin64(2048, cdiv64((int64_t)d.B * cdiv(xb.wpr, wpt), 256));
+        xb.blocks = (int)imin64(2048, cdiv64((int64_t)d.B * cdiv(xb.wpr, xbits_words_per_thread(xb.nz)), 256));
         xb.zero_p = c.ws + c.lay.fc11_part;
         xb.zero_n4 = (int)(c.fwd_zero_floats() / 4);
         if (p.rowmap) {
@@ -1870,12 +1882,11 @@ int launch_dec_planes(const Ctx& c, const float* params) {
 
 int launch_fc11_out_bf16(const Ctx& c, float* x_rec) {
     const mmvae_dims& d = c.d;
-    const PlaneGeom gw = plane_geom(c, PL_W11), gd = plane_geom(c, PL_D10);
+    Operand w{}, dp{};
+    use_planes(c, w, PL_W11); use_planes(c, dp, PL_D10);
     Fc11OutArgs a{};
-    a.wpl = reinterpret_cast<const unsigned short*>(c.ws + gw.ws_off);
-    a.w_plane = (int64_t)gw.Rp * gw.Cp; a.w_arm = 3 * a.w_plane;
-    a.dpl = reinterpret_cast<const unsigned short*>(c.ws + gd.ws_off);
-    a.d_plane = (int64_t)gd.Rp * gd.Cp; a.d_arm = 3 * a.d_plane;
+    a.wpl = w.pl; a.w_plane = w.pl_plane; a.w_arm = w.pl_arm;
+    a.dpl = dp.pl; a.d_plane = dp.pl_plane; a.d_arm = dp.pl_arm;
     a.out = x_rec;
     a.B = d.B; a.D = d.D;
     // gene splits: the smallest count whose grid fills whole rounds of the CUs to >= 90 % (one workgroup per CU at fp32x3's
@@ -1898,45 +1909,69 @@ int launch_fc11_out_bf16(const Ctx& c, float* x_rec) {
     return 0;
 }
 
-// x (or dW1's x~) as rows of the resident matrix (mmvae_train_step_rows): the operand is read through the row map
-static void use_rowmap(const Ctx& c, Operand& o) {
-    o.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); o.nrec = c.x_nrows * c.x_ld; o.map_n = c.d.B;
+// x [cell][gene] as a GEMM operand, K-major for fc1 (k = gene) or K-minor for dW1 (x~, k = cell), with what the call attaches:
+// the keep-mask words under input dropout, the row map when the batch is rows of the resident matrix (mmvae_train_step_rows),
+// and under it the bf16 engine's bf16 copy (bf16 storage).  *arm, *bits_arm: arm strides of the matrix (floats) / the mask words.
+static Operand x_operand(const Ctx& c, const float* x, int64_t xs, bool minor, int64_t* arm, int64_t* bits_arm) {
+    const mmvae_dims& d = c.d;
+    Operand o = minor ? kminor(x, d.D, d.D, d.B) : kmajor(x, d.D, d.B, d.D);
+    if (c.dropout()) { o.bits = reinterpret_cast<const uint32_t*>(c.ws + c.lay.xbits); o.wpr = cdiv(d.D, 32); }
+    if (c.plan.rowmap) { o.rowmap = reinterpret_cast<const unsigned*>(c.ws + c.lay.rowmap); o.nrec = c.x_nrows * c.x_ld; o.map_n = d.B; }
+    if (c.plan.rowmap && c.plan.big != GEMM_X3 && c.x16) { o.ptr = reinterpret_cast<const float*>(c.x16); o.src16 = 1; }
+    *arm = xs; *bits_arm = (int64_t)d.B * o.wpr;
+    return o;
+}
+
+// The compiled instantiations of the two slab GEMM kernels by what their template arguments mean: engine, orientations, SHARE
+// (fp32x3: the two tiles of a block share 1 = A, 2 = B), IDX (1 / 2: A / B through its row map), S16 (bit 0 / 1: A / B is bf16 in memory)
+typedef void (*GemmKernel)(const GemmArgs);
+struct SlabVariant { bool x3, aminor, bminor; int share, idx, s16; GemmKernel kernel; };
+#define BF16_GEMM(AMINOR, BMINOR, IDX, S16) SlabVariant{false, AMINOR, BMINOR, 0, IDX, S16, k_bf16_gemm<AMINOR, BMINOR, IDX, S16>}
+#define X3_GEMM(AMINOR, BMINOR, SHARE, IDX) SlabVariant{true, AMINOR, BMINOR, SHARE, IDX, 0, k_x3_gemm<AMINOR, BMINOR, SHARE, IDX>}
+static const SlabVariant slab_variants[] = {
+    // fc1 -- x as it lies | through the row map | ... from its bf16 copy | ... and W1 from slice 0 of its planes
+    BF16_GEMM(false, false, 0, 0), BF16_GEMM(false, false, 1, 0), BF16_GEMM(false, false, 1, 1), BF16_GEMM(false, false, 1, 3),
+    X3_GEMM(false, false, 2, 0), X3_GEMM(false, false, 2, 1),   // (one tile wide: the two tiles of a block share the W1 tile)
+    BF16_GEMM(false, true, 0, 0),   // d(d10)
+    // dW1 -- x~ in the same four forms, the last with dZ1 from slice 0 of its planes; the first is dW11's too
+    BF16_GEMM(true, true, 0, 0), BF16_GEMM(true, true, 2, 0), BF16_GEMM(true, true, 2, 2), BF16_GEMM(true, true, 2, 3),
+    X3_GEMM(true, true, 1, 0), X3_GEMM(true, true, 1, 2),       // (one tile high: they share the dZ1 tile)
+    // dW11 -- on a bf16 dZ11 | fp32x3 (one tile wide: they share the [d10 | 1] tile)
+    BF16_GEMM(true, true, 0, 1), X3_GEMM(true, true, 2, 0),
+};
+#undef BF16_GEMM
+#undef X3_GEMM
+// Launch the slab GEMM g on the plan's engine.  The kernel follows from the operands as they were built -- orientation, row
+// map, bf16 source -- and from `share` (fp32x3 only); a combination that is not compiled is an error, not another kernel.
+static int launch_slab_gemm(const Ctx& c, const GemmArgs& g, int share, dim3 grid, const char* what) {
+    const bool x3 = c.plan.big == GEMM_X3, aminor = g.a.kminor != 0, bminor = g.b.kminor != 0;
+    const int idx = (g.a.rowmap ? 1 : 0) | (g.b.rowmap ? 2 : 0), s16 = (g.a.src16 ? 1 : 0) | (g.b.src16 ? 2 : 0);
+    if (!x3) share = 0;
+    for (const SlabVariant& v : slab_variants)
+        if (v.x3 == x3 && v.aminor == aminor && v.bminor == bminor && v.share == share && v.idx == idx && v.s16 == s16) {
+            hipLaunchKernelGGL(v.kernel, grid, dim3(x3 ? 512 : 256), 0, c.stream, g);
+            HIP_LAUNCH_CHECK(what);
+            return 0;
+        }
+    set_error("%s: no %s kernel for A k-%s, B k-%s, share %d, row map %d, bf16 source %d", what, x3 ? "k_x3_gemm" : "k_bf16_gemm",
+              aminor ? "minor" : "major", bminor ? "minor" : "major", share, idx, s16);
+    return MMVAE_E_LAUNCH;
+}
+// its grid.  fp32x3: a block carries two 128-row tiles of the GEMM's long side (`paired` rows); bf16: tiles_m x tiles_n
+static dim3 slab_grid(const Ctx& c, const GemmArgs& g, int paired) {
+    return dim3(c.plan.big == GEMM_X3 ? cdiv(cdiv(paired, BT), 2) : cdiv(g.M, BT) * cdiv(g.N, BT), g.KS, g.A);
 }
 
 int launch_fc1_fwd_bf16(const Ctx& c, const float* params, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
     GemmArgs g{};
-    g.a = kmajor(x, d.D, d.B, d.D);
-    g.a_arm = xs;
-    if (c.dropout()) { g.a.bits = reinterpret_cast<const uint32_t*>(c.ws + c.lay.xbits); g.a.wpr = cdiv(d.D, 32); g.a_bits_arm = (int64_t)d.B * g.a.wpr; }
-    g.b = kmajor(params + c.po.o[0], d.D, d.H, d.D);
-    g.b_arm = c.po.per_arm;
+    g.a = x_operand(c, x, xs, false, &g.a_arm, &g.a_bits_arm);
+    g.b = kmajor(params + c.po.o[0], d.D, d.H, d.D); g.b_arm = c.po.per_arm;
+    if (c.plan.big == GEMM_X3) use_planes(c, g.b, PL_W1);
+    else if (g.a.src16 && c.plan.narrow) g.b_arm = read_slice0_bf16(c, g.b, PL_W1);   // [128][rup(D, 32)] bf16, zero rows beyond H
     g.M = d.B; g.N = d.H; g.K = d.D; g.KS = c.lay.sp.ks_fc1; g.A = d.A;
     g.so = SlabOut{c.ws + c.lay.fc1_slab, (int64_t)d.A * d.B * NP, (int64_t)d.B * NP, NP, d.B, d.H};
-    const bool x3 = c.plan.big == GEMM_X3;
-    if (c.plan.rowmap) {
-        use_rowmap(c, g.a);
-        if (x3) {
-            use_planes(c, g.b, PL_W1);
-            hipLaunchKernelGGL((k_x3_gemm<false, false, 2, 1>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-        } else if (c.x16) {         // bf16 storage: x from its bf16 copy
-            g.a.ptr = reinterpret_cast<const float*>(c.x16); g.a.src16 = 1;
-            if (c.plan.narrow) {   // ... and W1 from slice 0 of its planes (launch_x3_planes): [128][rup(D, 32)] bf16, zero rows beyond H
-                const PlaneGeom pg = plane_geom(c, PL_W1);
-                g.b.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.b.ld = pg.Cp; g.b.src16 = 1;
-                g.b_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;       // arm stride in FLOATS of the pointer arithmetic (planes: 2-byte elements)
-                hipLaunchKernelGGL((k_bf16_gemm<false, false, 1, 3>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-            } else
-                hipLaunchKernelGGL((k_bf16_gemm<false, false, 1, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        } else
-            hipLaunchKernelGGL((k_bf16_gemm<false, false, 1>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    } else if (x3) {   // (fc_dim <= 124: one tile wide, the two tiles of a block share the W1 tile)
-        use_planes(c, g.b, PL_W1);
-        hipLaunchKernelGGL((k_x3_gemm<false, false, 2>), dim3(cdiv(cdiv(d.B, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-    } else
-        hipLaunchKernelGGL((k_bf16_gemm<false, false>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    HIP_LAUNCH_CHECK("k_bf16_gemm<fc1>");
-    return 0;
+    return launch_slab_gemm(c, g, 2, slab_grid(c, g, d.B), "k_bf16_gemm<fc1>");
 }
 
 // what the fc11 kernels of both engines share: [d10 | W11^T] operands, the gene split, loss / dZ11 / x_rec outputs
@@ -1994,19 +2029,19 @@ int launch_fc11_bf16(const Ctx& c, const float* params, const float* x, int64_t 
     g.so = gd10_slab(c);
     // (fc11_fork_rides implies FC11_BF16 with fc11_grad -- need_grad without x_rec --, i.e. one of these three launches)
     const hipEvent_t fork = c.plan.fc11_fork_rides ? c.ev(EV_FORK) : nullptr;
-    if (c.plan.dz11_bf16) {   // bf16 storage: x from its bf16 copy, dZ11 written as bf16 (dW11 reads it that way)
+    const bool s16 = c.plan.dz11_bf16;
+    if (s16) {   // bf16 storage: x from its bf16 copy, dZ11 written as bf16 (dW11 reads it that way)
         g.fo.x = reinterpret_cast<const float*>(c.x16);
         g.fo_arm = (int64_t)d.B * d.D / 2;          // (arm stride of dZ11 in floats: B * D two-byte elements)
-        if (c.plan.narrow && KT == 64) {   // W11 from slice 0 of its planes (launch_x3_planes): [rup(D, 128)][128] bf16
-            const PlaneGeom pg = plane_geom(c, PL_W11);
-            g.b = kmajor(reinterpret_cast<const float*>(c.ws + pg.ws_off), pg.Cp, pg.Rp, pg.Cp);
-            g.b.src16 = 1;
-            g.b_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;       // arm stride in FLOATS of the pointer arithmetic (planes: 2-byte elements)
-            launch_k(c, fork, k_bf16_fc11g<true, true>, grid, dim3(256), 0, g);
-        } else
-            launch_k(c, fork, k_bf16_fc11g<true>, grid, dim3(256), 0, g);
-    } else
-        launch_k(c, fork, k_bf16_fc11g<false>, grid, dim3(256), 0, g);
+        // W11 from slice 0 of its planes (launch_x3_planes): all of [rup(D, 128)][128] bf16
+        if (c.plan.narrow) g.b_arm = read_slice0_bf16(c, g.b, PL_W11, true);
+    }
+    // the compiled k_bf16_fc11g<S16, W16>, [S16: as above][W16: W11 is bf16 in memory]
+    static const GemmKernel variants[2][2] = {{k_bf16_fc11g<false, false>, nullptr},
+                                              {k_bf16_fc11g<true, false>, k_bf16_fc11g<true, true>}};
+    const GemmKernel kernel = variants[s16][g.b.src16 != 0];
+    if (!kernel) { set_error("k_bf16_fc11g: no kernel for a bf16 W11 beside an fp32 x"); return MMVAE_E_LAUNCH; }
+    launch_k(c, fork, kernel, grid, dim3(256), 0, g);
     HIP_LAUNCH_CHECK("k_bf16_fc11g");
     return 0;
 }
@@ -2020,47 +2055,22 @@ int launch_gd10_bf16(const Ctx& c, const float* params) {
     g.b_arm = c.po.per_arm;
     g.M = d.B; g.N = d.H; g.K = d.D; g.KS = c.lay.sp.ks_gd10; g.A = d.A;
     g.so = gd10_slab(c);
-    hipLaunchKernelGGL((k_bf16_gemm<false, true>), dim3(cdiv(d.B, BT) * cdiv(d.H, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    HIP_LAUNCH_CHECK("k_bf16_gemm<gd10>");
-    return 0;
+    // (FC11_BF16 implies GEMM_BF16: there is no fp32x3 form of this product, and on that engine the lookup would say so)
+    return launch_slab_gemm(c, g, 0, slab_grid(c, g, 0), "k_bf16_gemm<gd10>");
 }
 
 // dW1[h][d] = sum_b dZ1[b][h] x~[b][d]
 int launch_dw1_bf16(const Ctx& c, const float* x, int64_t xs) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
-    const bool x3 = c.plan.big == GEMM_X3;
     GemmArgs g{};
-    g.a = kminor(c.ws + L.DZ[1], d.H, d.H, d.B);
-    g.a_arm = (int64_t)d.B * d.H;
-    g.b = kminor(x, d.D, d.D, d.B);
-    g.b_arm = xs;
-    if (c.dropout()) { g.b.bits = reinterpret_cast<const uint32_t*>(c.ws + L.xbits); g.b.wpr = cdiv(d.D, 32); g.b_bits_arm = (int64_t)d.B * g.b.wpr; }
+    g.a = kminor(c.ws + L.DZ[1], d.H, d.H, d.B); g.a_arm = (int64_t)d.B * d.H;
+    g.b = x_operand(c, x, xs, true, &g.b_arm, &g.b_bits_arm);
+    if (c.plan.big == GEMM_X3) use_planes(c, g.a, PL_DZ1);
+    else if (g.b.src16 && c.plan.narrow && c.plan.dz1_in_apply) g.a_arm = read_slice0_bf16(c, g.a, PL_DZ1);   // (k_bn_bwd_apply wrote them)
     g.M = d.H; g.N = d.D; g.K = d.B; g.KS = L.sp.ks_dw; g.A = d.A;
     g.so = SlabOut{c.ws + L.dw1_slab, (int64_t)d.A * d.H * d.D, (int64_t)d.H * d.D, d.D, d.H, d.D};
-    if (c.plan.rowmap) {
-        use_rowmap(c, g.b);
-        if (x3) {
-            use_planes(c, g.a, PL_DZ1);
-            hipLaunchKernelGGL((k_x3_gemm<true, true, 1, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-        } else if (c.x16) {
-            g.b.ptr = reinterpret_cast<const float*>(c.x16); g.b.src16 = 1;
-            if (c.plan.narrow && c.plan.dz1_in_apply) {   // dZ1 from slice 0 of its planes (k_bn_bwd_apply): [rup(B, 256)][128] bf16
-                const PlaneGeom pg = plane_geom(c, PL_DZ1);
-                g.a.ptr = reinterpret_cast<const float*>(c.ws + pg.ws_off); g.a.ld = pg.Cp; g.a.src16 = 1;
-                g.a_arm = 3 * (int64_t)pg.Rp * pg.Cp / 2;
-                hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 3>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-            } else
-                hipLaunchKernelGGL((k_bf16_gemm<true, true, 2, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-        } else
-            hipLaunchKernelGGL((k_bf16_gemm<true, true, 2>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    } else if (x3) {   // one tile high: the two tiles of a block share the dZ1 tile
-        use_planes(c, g.a, PL_DZ1);
-        hipLaunchKernelGGL((k_x3_gemm<true, true, 1>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-    } else
-        hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.H, BT) * cdiv(d.D, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    HIP_LAUNCH_CHECK("k_bf16_gemm<dW1>");
-    return 0;
+    return launch_slab_gemm(c, g, 1, slab_grid(c, g, d.D), "k_bf16_gemm<dW1>");
 }
 
 // [dW11 | db11][j][h] = sum_b dZ11[b][j] [d10 | 1][b][h]
@@ -2068,24 +2078,14 @@ int launch_dw11_bf16(const Ctx& c) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     GemmArgs g{};
-    g.a = kminor(c.ws + L.DZ11, d.D, d.D, d.B);
-    g.a_arm = (int64_t)d.B * d.D;
-    g.b = kminor(c.ws + L.Dk[4], d.H, d.H, d.B);
+    g.a = kminor(c.ws + L.DZ11, d.D, d.D, d.B); g.a_arm = (int64_t)d.B * d.D;
+    g.b = kminor(c.ws + L.Dk[4], d.H, d.H, d.B); g.b_arm = (int64_t)d.B * d.H;
     g.b.ones_row = d.H;                                      // logical row H (not in memory) reads 1: the bias gradient
-    g.b_arm = (int64_t)d.B * d.H;
+    if (c.plan.big == GEMM_X3) use_planes(c, g.b, PL_D10);
+    else if (c.plan.dz11_bf16) { g.a.src16 = 1; g.a_arm /= 2; }   // bf16 storage: this step's fused fc11 kernel wrote dZ11 as bf16
     g.M = d.D; g.N = d.H + 1; g.K = d.B; g.KS = L.sp.ks_dw11; g.A = d.A;
     g.so = SlabOut{c.ws + L.dw11_slab, (int64_t)d.A * d.D * DW11_LD, (int64_t)d.D * DW11_LD, DW11_LD, d.D, d.H + 1};
-    if (c.plan.big == GEMM_X3) {   // one tile wide: the two tiles of a block share the [d10 | 1] tile
-        use_planes(c, g.b, PL_D10);
-        hipLaunchKernelGGL((k_x3_gemm<true, true, 2>), dim3(cdiv(cdiv(d.D, BT), 2), g.KS, d.A), dim3(512), 0, c.stream, g);
-    } else if (c.plan.dz11_bf16) {   // bf16 storage: the fused fc11 kernel of this step wrote dZ11 as bf16
-        g.a.src16 = 1;
-        g.a_arm = (int64_t)d.B * d.D / 2;
-        hipLaunchKernelGGL((k_bf16_gemm<true, true, 0, 1>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    } else
-        hipLaunchKernelGGL((k_bf16_gemm<true, true>), dim3(cdiv(d.D, BT) * cdiv(d.H + 1, BT), g.KS, d.A), dim3(256), 0, c.stream, g);
-    HIP_LAUNCH_CHECK("k_bf16_gemm<dW11>");
-    return 0;
+    return launch_slab_gemm(c, g, 2, slab_grid(c, g, d.D), "k_bf16_gemm<dW11>");
 }
 
 int launch_dw_small_x3(const Ctx& c, const TnDescs& ts, int nsel) {

@@ -1386,8 +1386,7 @@ int launch_make_xbits(const Ctx& c, const mmvae_noise* nz) {
     const mmvae_dims& d = c.d;
     NoiseDev nd = make_noise_dev(nz, c.h);
     const int wpr = cdiv(d.D, 32);
-    const int wpt = nd.mode != 0 && nd.x_mlog2 <= 2 ? (int)(4u >> nd.x_mlog2) : 1;   // as in the kernel
-    const int64_t n = (int64_t)d.A * d.B * cdiv(wpr, wpt);
+    const int64_t n = (int64_t)d.A * d.B * cdiv(wpr, xbits_words_per_thread(nd));
     const int blocks = (int)imin64(4096, cdiv64(n, 256));
     hipLaunchKernelGGL(k_make_xbits, dim3(blocks), dim3(256), 0, c.stream, nd, d.A, d.B, d.D, wpr,
                        reinterpret_cast<uint32_t*>(c.ws + c.lay.xbits), c.ws + c.lay.fc11_part,

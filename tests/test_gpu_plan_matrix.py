@@ -13,7 +13,8 @@ path fails here, whatever its numbers), then the numbers of that path:
     misaligned run to the fp32 gates, the aligned run's five products to 2e-5, their losses to 5e-2 of each other;
   * two Adam steps bit-reproducible run to run (engines bf16, fp32x3), the row-indexed step bit-identical to gather-then-step
     where the plan says `rowmap` and refused where it does not (the misaligned rows are left out here: this runs through the
-    model's own step, which cannot be handed a misaligned pointer, and aligned they are row h100);
+    model's own step, which cannot be handed a misaligned pointer, and aligned they are row h100); the same identity on
+    ragged tiles of a matrix whose pitch is not its width, fp32x3 and bf16, the latter also on the bf16 copy;
   * a NaN-filled workspace changes no bit on the plans with planes written and unread or not written at all;
   * decode / state_changes across the fc11 switch points (x_rec at the gates of tests/test_gpu_decode.py, decoder(forward's
     codes) bit-equal to the forward's x_rec on engine 0);
@@ -316,6 +317,44 @@ def test_two_adam_steps_reproduce_bit_for_bit_and_rows_equal_gather(name, engine
         # no row map in this plan (no input dropout, no head launch, a width past the fused fc11 kernels): refused, as today
         with pytest.raises(NotImplementedError):
             _two_adam_steps(row, engine, h, sd, data, rows, True)
+
+
+@pytest.mark.parametrize("config", ["fp32x3", "bf16", "bf16_data16"])
+def test_rows_equal_gather_on_ragged_tiles_of_a_pitched_matrix(config):
+    """The row-mapped loaders of fc1 and dW1 (and, with the bf16 copy, the bf16-source ones of fc1, fc11, dW1 and dW11) at the
+    smallest shape where they can go wrong: 129 cells (two 128-row tiles, the second ragged), 136 genes (two 128-gene tiles,
+    the second ragged; a multiple of 8, as bf16 storage needs), a resident matrix of 400 rows whose pitch (144) is not its
+    width.  The row-indexed step equals gather + step bit for bit: loss vector, gradients, BatchNorm statistics.  The matrix
+    holds bf16-representable values, so reading its bf16 copy moves other bytes and computes the same numbers."""
+    import distributed_vae_amd  # noqa: F401
+    from distributed_vae_amd import _native as N
+    from tests import gpu_util as U
+    A, B, D, H, n_rows, ld = 2, 129, 136, 100, 400, 144
+    h = R.Hyper(input_dim=D, fc_dim=H, n_categories=12, state_dim=2, lowD_dim=6, n_arm=A)
+    sd = R.init_state_dict(h, 31)
+    base = torch.zeros(n_rows, ld)
+    base[:, :D] = R.synthetic_batch(n_rows, D, seed=32).to(torch.bfloat16).float()
+    data = base.to(U.DEV)[:, :D]
+    data16 = N.to_bf16(data) if config == "bf16_data16" else None
+    rows = torch.randint(0, n_rows, (B,), generator=torch.Generator().manual_seed(33))
+    rows[:4] = torch.tensor([n_rows - 1, 0, 5, 5])                          # edges and a repeated row
+    rows = rows.to(U.DEV)
+    noise = U.noise_to_device(R.draw_noise(h, B, seed=34))
+    out = []
+    for indexed in (False, True):
+        m = U.build_model(h, sd)
+        m.train()
+        m.gemm_dtype = config.split("_")[0]
+        m.set_explicit_noise(noise)
+        if indexed:
+            buf = m.fused_train_step_rows(data, rows, 1.0, None, do_adam=False, data16=data16)
+        else:
+            buf = m.fused_train_step(data[rows].contiguous().expand(A, -1, -1), 1.0, None, do_adam=False)
+        torch.cuda.synchronize()
+        out.append([buf.cpu().clone(), m.flat_grad().detach().cpu().clone(), m._bn_flat.detach().cpu().clone()])
+    assert bool(torch.isfinite(out[0][0]).all()) and bool(torch.isfinite(out[0][1]).all()) and float(out[0][1].abs().max()) > 0
+    for u, v in zip(*out):
+        assert torch.equal(u.view(torch.int32), v.view(torch.int32)), "rows vs gather"
 
 
 @pytest.mark.parametrize("engine", ENGINES)
