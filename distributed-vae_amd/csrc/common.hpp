@@ -269,16 +269,18 @@ struct ScalarTag { static constexpr bool value = false; };
 // global store the wave has in flight; after an epilogue that is several microseconds per barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// Wave-wide all-reduce without LDS traffic: four DPP steps inside each row of 16 lanes (quad_perm xor 1,
-// quad_perm xor 2, row_half_mirror, row_mirror) and the gfx950 half-exchange instructions
-// v_permlane16_swap / v_permlane32_swap across rows.  (__shfl_xor lowers to ds_bpermute_b32, ~100 cycles
-// of dependent latency per step; the row-wise kernels chain ~15 reductions per cell.)
+// All-reduce over groups of W = 64 (the wave) or 32 (each half of it) lanes without LDS traffic: four DPP steps
+// inside each row of 16 lanes (quad_perm xor 1, quad_perm xor 2, row_half_mirror, row_mirror) and the gfx950
+// half-exchange instructions v_permlane16_swap / v_permlane32_swap across rows; the 32-lane group stops before
+// the last.  (__shfl_xor lowers to ds_bpermute_b32, ~100 cycles of dependent latency per step; the row-wise
+// kernels chain ~15 reductions per cell.)
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
-template <typename Op>
-__device__ __forceinline__ float wave_allreduce(float v, Op op) {
+template <int W, typename Op>
+__device__ __forceinline__ float group_allreduce(float v, Op op) {
+    static_assert(W == 64 || W == 32, "a group is the wave or half of it");
     v = op(v, dpp_f<0xB1>(v));    // quad_perm [1,0,3,2]
     v = op(v, dpp_f<0x4E>(v));    // quad_perm [2,3,0,1]
     v = op(v, dpp_f<0x141>(v));   // row_half_mirror
@@ -288,26 +290,32 @@ __device__ __forceinline__ float wave_allreduce(float v, Op op) {
         const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
         v = op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
     }
-    {
+    if constexpr (W == 64) {
         const unsigned u = __builtin_bit_cast(unsigned, v);
         const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
         v = op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
     }
     return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-    return wave_allreduce(v, [](float a, float b) { return a + b; });
+template <int W>
+__device__ __forceinline__ float group_sum(float v) {
+    return group_allreduce<W>(v, [](float a, float b) { return a + b; });
 }
-__device__ __forceinline__ float wave_max(float v) {
-    return wave_allreduce(v, [](float a, float b) { return fmaxf(a, b); });
+template <int W>
+__device__ __forceinline__ float group_max(float v) {
+    return group_allreduce<W>(v, [](float a, float b) { return fmaxf(a, b); });
 }
-__device__ __forceinline__ int wave_min_i(int v) {
-    const float f = wave_allreduce(__builtin_bit_cast(float, v), [](float a, float b) {
+template <int W>
+__device__ __forceinline__ int group_min_i(int v) {
+    const float f = group_allreduce<W>(__builtin_bit_cast(float, v), [](float a, float b) {
         const int x = __builtin_bit_cast(int, a), y = __builtin_bit_cast(int, b);
         return __builtin_bit_cast(float, x < y ? x : y);
     });
     return __builtin_bit_cast(int, f);
 }
+__device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
+__device__ __forceinline__ float wave_max(float v) { return group_max<64>(v); }
+__device__ __forceinline__ int wave_min_i(int v) { return group_min_i<64>(v); }
 
 // ---- consumer-side recombination of per-row-block partials ---------------------------------
 // Batch statistics cross every row block, so each BatchNorm used to cost a tiny finalize launch
@@ -325,9 +333,10 @@ constexpr int PART_BATCH = 16;
 #define MMVAE_CHAIN_ROWS 64
 #endif
 constexpr int CHAIN_ROWS = MMVAE_CHAIN_ROWS;
-// cells per workgroup of the latent-block kernels (16 waves, one cell per wave at a time).  These kernels are
-// VALU-bound, so what counts is cells per CU: 48 gives 105 workgroups per arm at B = 5000 -- one per CU, three cells
-// per wave -- where 32 gave 314 workgroups on 256 CUs, i.e. 58 CUs with two (four cells per wave slot).
+// cells per workgroup of the latent-block kernels (rowwise.hip, LatCell: their waves per workgroup, cells per wave and the
+// two cell geometries).  These kernels are VALU-bound, so what counts is cells per CU: 48 gives 105 workgroups per arm at
+// B = 5000 -- one per CU, three cells per wave slot (a wave, or half of one) -- where 32 gave 314 workgroups on 256 CUs,
+// i.e. 58 CUs with two (four cells per wave slot).
 constexpr int LAT_ROWS = 48;
 // half-wave form of the latent kernels (rowwise.hip): a cell owns 32 lanes x LH_CPL registers (C <= 32 LH_CPL)
 constexpr int LH_CPL = 3;
@@ -338,8 +347,6 @@ constexpr int LH_CPL = 3;
 #define MMVAE_LAT_ROWS_BWD 8
 #endif
 constexpr int LAT_ROWS_BWD = MMVAE_LAT_ROWS_BWD;
-constexpr int LATB_NW = 8;    // waves per workgroup of the latent backward kernel
-constexpr int LATB_NR = LAT_ROWS_BWD / LATB_NW;   // cells per wave, processed side by side
 // The exact batch-sum accumulators (acc_add below) hold ACC_MAX_ADDENDS addends of the largest magnitude per column without a
 // carry between their slots; a training batch may therefore have at most ACC_MAX_ADDENDS x (the fewest cells any producing
 // workgroup adds at once) cells per rank.  Producers: the fc1 epilogue and the coupling (32-cell blocks), the chain kernels

@@ -1,14 +1,15 @@
-// Row-wise (one wavefront per cell) kernels and the small reductions between them:
+// Row-wise (one wavefront or half of one per cell) kernels and the small reductions between them:
 //
 //   (batch statistics: every consumer recombines the producers' per-row-block (mean, M2) partials itself,
 //    common.hpp stats_from_partials -- BatchNorm1d incl. running statistics, nn_model.py:208-255, and
 //    inv_var, nn_model.py:75-77; eval mode: k_stats_from_running)
-//   k_lat_fwd         x_low = BN5(R5); c_prob = softmax(fcc x_low); c = softmax(c_prob/tau);
+//   k_lat_fwd[_h]     x_low = BN5(R5); c_prob = softmax(fcc x_low); c = softmax(c_prob/tau);
 //                     Gumbel-softmax sample; state head; reparameterise; decoder input
 //                     (nn_model.py:268-269, :337-351, :413-493)
 //   k_couple          pairwise coupling terms over arms (nn_model.py:558-569)
 //   k_loss_finalize   scalars of nn_model.py:542-598
-//   k_lat_bwd         autograd of k_lat_fwd + coupling / entropy / KL terms
+//   k_lat_bwd[_h]     autograd of k_lat_fwd + coupling / entropy / KL terms
+//                     (one body each, lat_fwd / lat_bwd<W, NW>; _h: a cell on W = 32 lanes, see LatCell)
 //   k_reduce          slabs -> flat gradient buffer;  k_adam: torch.optim.Adam(W) update
 //
 // Wave reductions only (no MFMA): these tensors are [B, <=128] and HBM/L2 resident.
@@ -91,8 +92,39 @@ __device__ __forceinline__ bool state_keep(const NoiseDev& nz, int arm, int B, i
     return noise_keep(nz, arm, STREAM_SMASK, (uint64_t)b * S + s, nz.s_keep_thr);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The latent block, forward (lat_fwd) and backward (lat_bwd): one body each, compiled for two cell geometries.  A cell
+// (one row of the batch) lives on W lanes of a wave, CP column registers in each; a wave instruction serves CPW = 64 / W
+// cells; a wave carries NR such cell groups side by side; NW waves per workgroup.  NW x CPW x NR = LAT_ROWS (forward) /
+// LAT_ROWS_BWD (backward, common.hpp) cells per workgroup in either geometry, so the partial layouts, the grids and the
+// workspace do not depend on it.
+//                                                  W    NW x CPW x NR
+constexpr int LAT_NW = 16, LAT_NR = LAT_ROWS / LAT_NW;             // k_lat_fwd     64   16 x 1 x 3
+constexpr int LH_NW = 8, LH_NR = LAT_ROWS / (LH_NW * 2);           // k_lat_fwd_h   32    8 x 2 x 3
+constexpr int LATB_NW = 8, LATB_NR = LAT_ROWS_BWD / LATB_NW;       // k_lat_bwd     64    8 x 1 x 1
+constexpr int LBH_NW = 4, LBH_NR = LAT_ROWS_BWD / (LBH_NW * 2);    // k_lat_bwd_h   32    4 x 2 x 1
+static_assert(LAT_NR * LAT_NW == LAT_ROWS && LH_NR * LH_NW * 2 == LAT_ROWS, "LAT_ROWS must be a multiple of 16");
+static_assert(LATB_NR * LATB_NW == LAT_ROWS_BWD && LBH_NR * LBH_NW * 2 == LAT_ROWS_BWD, "LAT_ROWS_BWD must be a multiple of 8");
+
+// Cell geometry.  W = 64, the wave form: the wave is one cell, 64 lanes x CPL = 128 column slots (C <= 128, L <= 64,
+// 2 S <= 64).  W = 32, the half-wave form (make_plan picks it for C <= 96, L <= 32, 2 S <= 32 -- the reference's 92 / 10 /
+// 2): 32 lanes x LH_CPL = 96 column slots for 92 categories.  These kernels are VALU-bound (a wave instruction occupies
+// its SIMD for four cycles): three registers for two cells instead of two for one is a quarter less element-wise work,
+// and a reduction is one step shorter (group_allreduce, common.hpp) and counts for two cells.
+template <int W>
+struct LatCell {
+    static_assert(W == 64 || W == 32, "a cell is the wave or half of it");
+    static constexpr int CPW = 64 / W;                    // cells served by one wave instruction
+    static constexpr int CP = W == 64 ? CPL : LH_CPL;     // column registers per lane: column sub + W t in register t
+    static __device__ __forceinline__ int sub(int lane) { return lane & (W - 1); }     // lane within the cell
+    static __device__ __forceinline__ int base(int lane) { return lane & (64 - W); }   // the cell's first lane (shuffle sources)
+    static __device__ __forceinline__ int cell(int lane) { return lane / W; }          // cell within the wave
+    static __device__ __forceinline__ float sum(float v) { return group_sum<W>(v); }   // over the cell's lanes
+    static __device__ __forceinline__ float max(float v) { return group_max<W>(v); }
+    static __device__ __forceinline__ int min_i(int v) { return group_min_i<W>(v); }
+};
+
 // Stages fcc (transposed to [L][C]) and the state-head weights in LDS once per workgroup.
-constexpr int LAT_NW = 16;   // waves per workgroup: LAT_ROWS / 16 cells each, one at a time
 __device__ __forceinline__ void lat_stage_weights(float* WcT, float* Wm, const float* __restrict__ Wc,
                                                   const float* __restrict__ Wms, int L, int C, int S) {
     for (int i = threadIdx.x; i < C * L; i += blockDim.x) {
@@ -103,348 +135,25 @@ __device__ __forceinline__ void lat_stage_weights(float* WcT, float* Wm, const f
     __syncthreads();
 }
 
-// grid (ceil(B/LAT_ROWS), A), 1024 threads; wave w handles cells b0 + w, b0 + w + 16, ... -- all LAT_NR of them side
-// by side: the per-cell work is one long dependency chain (three softmaxes = six wave reductions, the Gumbel
-// transform, four state-head dot products), and a wave that walks its cells one after the other spends most of its
-// time waiting on that chain (measured: 15 k cycles per cell with 4 waves per SIMD).
-constexpr int LAT_NR = LAT_ROWS / LAT_NW;
-static_assert(LAT_NR * LAT_NW == LAT_ROWS, "LAT_ROWS must be a multiple of the wave count");
-__global__ __launch_bounds__(1024) void k_lat_fwd(const LatArgs a_in, const NoiseDev nz_in,
-                                                  const float* __restrict__ params, float* __restrict__ ws,
-                                                  float* __restrict__ bn_running, int64_t* __restrict__ nbt) {
-    const LatArgs a = a_in;      // argument blocks into registers once (see k_chain_fwd)
-    const NoiseDev nz = nz_in;
-    extern __shared__ __attribute__((aligned(16))) float lat_smem[];
-    // statistics scratch of the prologue, then the workgroup's c tile [LAT_ROWS][128] for the block statistics
-    __shared__ __attribute__((aligned(16))) float sh_buf[LAT_ROWS * CPL * 64];
-    __shared__ float sh_ps[8][CPL * 64];
-    __shared__ float sh_red[LAT_NW][2], sh_bn5[2][64];
-    const int arm = blockIdx.y, blk = blockIdx.x, b0 = blk * LAT_ROWS;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int B = a.B, L = a.L, C = a.C, S = a.S;
-    const float* P = params + (int64_t)arm * a.per_arm;
-    float* WcT = lat_smem;            // [L][C]
-    float* Wms = lat_smem + C * L;    // [2S][L+C]
-    const int64_t ab = (int64_t)arm * B;
-    const float eps = a.eps;
-
-    // this wave's cells; their fc5 outputs are requested first, so that this latency, the weight staging and the
-    // statistics partials all overlap
-    int bb[LAT_NR];
-    bool okr[LAT_NR];
-    float r5[LAT_NR];
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r) {
-        bb[r] = b0 + wv + LAT_NW * r;
-        okr[r] = bb[r] < B;   // wave-uniform
-        r5[r] = lane < L ? ws[a.R5 + (ab + min(bb[r], B - 1)) * L + lane] : 0.f;
-    }
-    const bool vcol[CPL] = {lane < C, lane + 64 < C};
-    float bcv[CPL];
-#pragma unroll
-    for (int t = 0; t < CPL; ++t) bcv[t] = vcol[t] ? P[a.o_bc + lane + 64 * t] : 0.f;
-    lat_stage_weights(WcT, Wms, P + a.o_wc, P + a.o_wms, L, C, S);
-    const float* bms = P + a.o_bms;   // [2S]
-
-    if (a.bn_part5 >= 0) {   // training: BN5 batch statistics from fc5's per-row-block partials
-        float mean, m2;
-        if (a.acc_bn5 >= 0) {
-            mean = m2 = 0.f;
-            if ((int)threadIdx.x < L)
-                acc_mean_m2(reinterpret_cast<const long long*>(ws + a.acc_bn5) + (int64_t)arm * ACC_SET_I64, threadIdx.x, B, mean, m2);
-        } else {
-            stats_from_partials<64 * LAT_NW>(ws + a.bn_part5 + (int64_t)arm * a.bn5_n * 2 * L, a.bn5_n, B, CHAIN_ROWS, L,
-                                             sh_buf, mean, m2);
-        }
-        if (threadIdx.x < L) {
-            const int t = threadIdx.x;
-            const float rstd = 1.0f / sqrtf(m2 / (float)B + eps);
-            sh_bn5[0][t] = mean;
-            sh_bn5[1][t] = rstd;
-            if (blk == 0) {
-                ws[a.mean5 + arm * L + t] = mean;
-                ws[a.rstd5 + arm * L + t] = rstd;
-                if (bn_running) {
-                    float* rm = bn_running + a.run_mean_off + arm * a.run_arm_stride;
-                    float* rv = bn_running + a.run_var_off + arm * a.run_arm_stride;
-                    rm[t] = (1.f - a.bn_momentum) * rm[t] + a.bn_momentum * mean;
-                    rv[t] = (1.f - a.bn_momentum) * rv[t] + a.bn_momentum * (m2 / (float)max(B - 1, 1));
-                }
-                if (nbt && t == 0) nbt[arm * MMVAE_N_BN + 4] += 1;
-            }
-        }
-        lds_barrier();
-    }
-    const float mu5 = lane < L ? (a.bn_part5 >= 0 ? sh_bn5[0][lane] : ws[a.mean5 + arm * L + lane]) : 0.f;
-    const float rs5 = lane < L ? (a.bn_part5 >= 0 ? sh_bn5[1][lane] : ws[a.rstd5 + arm * L + lane]) : 0.f;
-
-    // ---- x_low = BN5(R5)
-    float xl[LAT_NR];
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r) {
-        xl[r] = lane < L ? (r5[r] - mu5) * rs5 : 0.f;
-        if (okr[r] && lane < L) {
-            ws[a.XLOW + (ab + bb[r]) * L + lane] = xl[r];
-            ws[a.Y + (ab + bb[r]) * (L + C) + lane] = xl[r];
-        }
-    }
-    // ---- zc = fcc(x_low); c_prob = softmax(zc)
-    float z[LAT_NR][CPL];
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r)
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) z[r][t] = bcv[t];
-    for (int k = 0; k < L; ++k) {
-        float w[CPL];
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) w[t] = vcol[t] ? WcT[k * C + lane + 64 * t] : 0.f;
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            const float xk = __shfl(xl[r], k, 64);
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) z[r][t] += xk * w[t];
-        }
-    }
-    float m[LAT_NR], ssum[LAT_NR], e[LAT_NR][CPL];
-    float cp[LAT_NR][CPL], cc[LAT_NR][CPL], lc[LAT_NR][CPL], ys[LAT_NR][CPL], cs[LAT_NR][CPL];
-    // softmax over the valid columns of v (in place in e, sum in ssum)
-    auto softmax_rows = [&](float (&v)[LAT_NR][CPL], float (&out)[LAT_NR][CPL]) {
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            m[r] = -INFINITY;
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) if (vcol[t]) m[r] = fmaxf(m[r], v[r][t]);
-        }
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) m[r] = wave_max(m[r]);
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            ssum[r] = 0.f;
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) { e[r][t] = vcol[t] ? expf(v[r][t] - m[r]) : 0.f; ssum[r] += e[r][t]; }
-        }
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) ssum[r] = wave_sum(ssum[r]);
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            const float inv = 1.f / ssum[r];   // one division per cell, not per element: the kernel is VALU-bound
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) out[r][t] = e[r][t] * inv;
-        }
-    };
-    softmax_rows(z, cp);
-    // ---- c = softmax(c_prob / tau)
-    const float inv_tau = 1.f / a.tau, inv_temp = 1.f / a.temp;
-    float tmp[LAT_NR][CPL];
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r)
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) tmp[r][t] = cat_kept(a, lane + 64 * t) ? cp[r][t] * inv_tau : -INFINITY;   // masked-out: exp(-inf) = 0
-    softmax_rows(tmp, cc);
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r)
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) lc[r][t] = logf(cc[r][t] + eps);
-    // ---- Gumbel-softmax sample
-    bool hard = a.hard != 0;
-    if (a.eval_flag) {
-        hard = true;
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r)
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) ys[r][t] = cc[r][t];
-    } else {
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r)
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) {
-                tmp[r][t] = 0.f;
-                if (vcol[t]) {
-                    const float U = gumbel_u(nz, arm, B, C, min(bb[r], B - 1), lane + 64 * t);
-                    const float g = -logf(-logf(U + eps) + eps);
-                    tmp[r][t] = (lc[r][t] + g) * inv_temp;
-                }
-            }
-        softmax_rows(tmp, ys);
-    }
-    if (hard) {
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            float mv = -INFINITY;
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) if (vcol[t]) mv = fmaxf(mv, ys[r][t]);
-            mv = wave_max(mv);
-            int cand = 1 << 30;
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) if (vcol[t] && ys[r][t] == mv) cand = min(cand, lane + 64 * t);
-            cand = wave_min_i(cand);
-            if (a.labels && a.eval_flag && okr[r] && lane == 0) a.labels[ab + bb[r]] = cand;   // eval: ys == c
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) {
-                const float hv = (lane + 64 * t == cand) ? 1.f : 0.f;
-                cs[r][t] = (hv - ys[r][t]) + ys[r][t];   // (y_hard - y).detach() + y, nn_model.py:492
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r)
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) cs[r][t] = ys[r][t];
-    }
-    // ---- store; c goes to the workgroup tile for the block statistics (zero rows beyond the batch)
-    float kl_acc = 0.f, ent_acc = 0.f;
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r) {
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) {
-            const int col = lane + 64 * t;
-            sh_buf[(wv + LAT_NW * r) * (CPL * 64) + col] = (okr[r] && vcol[t]) ? cc[r][t] : 0.f;
-            if (okr[r] && vcol[t]) {
-                const int64_t o = (ab + bb[r]) * C + col;
-                ws[a.CPROB + o] = cp[r][t];
-                ws[a.CC + o] = cc[r][t];
-                ws[a.YSOFT + o] = ys[r][t];
-                ws[a.CSMP + o] = cs[r][t];
-                ws[a.Y + (ab + bb[r]) * (L + C) + L + col] = cs[r][t];
-                ws[a.ZIN + (ab + bb[r]) * (C + S) + col] = cs[r][t];
-                ent_acc += cc[r][t] * lc[r][t];
-            }
-        }
-    }
-    // ---- state head: [mu | sigma_pre] = y [Wmu; Wsigma]^T + b
-    float mso[LAT_NR];
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r) mso[r] = 0.f;
-    for (int o = 0; o < 2 * S; ++o) {
-        const float* w = Wms + (int64_t)o * (L + C);
-        const float wl = lane < L ? w[lane] : 0.f;
-        float wc[CPL], pr[LAT_NR];
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) wc[t] = vcol[t] ? w[L + lane + 64 * t] : 0.f;
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            pr[r] = xl[r] * wl;
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) pr[r] += cs[r][t] * wc[t];
-        }
-        const float bo = bms[o];
-#pragma unroll
-        for (int r = 0; r < LAT_NR; ++r) {
-            const float pv = wave_sum(pr[r]) + bo;
-            if (lane == o) mso[r] = pv;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < LAT_NR; ++r) {
-        if (okr[r] && lane < 2 * S) ws[a.MS + (ab + bb[r]) * 2 * S + lane] = mso[r];
-        const float sg = __shfl(mso[r], (lane + S) & 63, 64);
-        if (okr[r] && lane < S) {
-            const int b = bb[r];
-            const float mu = mso[r];
-            const float var = 1.f / (1.f + expf(-sg));
-            const float lv = logf(var + eps);
-            const float sd = sqrtf(expf(lv));
-            const float U = state_u(nz, arm, B, S, b, lane);
-            const float sv = U * sd + mu;
-            float sin_ = sv;
-            if (a.training && a.s_drop > 0.f) sin_ = state_keep(nz, arm, B, S, b, lane) ? sv / (1.f - a.s_drop) : 0.f;
-            ws[a.MU + (ab + b) * S + lane] = mu;
-            ws[a.LV + (ab + b) * S + lane] = lv;
-            ws[a.SS + (ab + b) * S + lane] = sv;
-            ws[a.ZIN + (ab + b) * (C + S) + C + lane] = sin_;
-            kl_acc += 1.f + lv - mu * mu - expf(lv);
-        }
-    }
-    // ---- block partials: mean and M2 of c over the workgroup's cells, two passes over the LDS tile, 8 row groups
-    kl_acc = wave_sum(kl_acc);
-    ent_acc = wave_sum(ent_acc);
-    if (lane == 0) { sh_red[wv][0] = kl_acc; sh_red[wv][1] = ent_acc; }
-    lds_barrier();
-    {
-        const int col = threadIdx.x & (CPL * 64 - 1), g = threadIdx.x >> 7;   // 1024 threads = 8 groups x 128 columns
-        const int nv = min(LAT_ROWS, B - b0);
-        float v[LAT_ROWS / 8];
-        float s1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < LAT_ROWS / 8; ++i) { v[i] = sh_buf[(g + 8 * i) * (CPL * 64) + col]; s1 += v[i]; }   // rows beyond nv are 0
-        sh_ps[g][col] = s1;
-        lds_barrier();
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tot += sh_ps[k][col];
-        const float mean = tot / (float)nv;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < LAT_ROWS / 8; ++i) { const float d = v[i] - mean; q += (g + 8 * i < nv) ? d * d : 0.f; }
-        lds_barrier();   // every thread has read sh_ps
-        sh_ps[g][col] = q;
-        lds_barrier();
-        if (g == 0 && col < C) {
-            float m2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) m2 += sh_ps[k][col];
-            if (a.acc_c >= 0) {
-                acc_add_stats(reinterpret_cast<long long*>(ws + a.acc_c) + (int64_t)arm * ACC_SET_I64, col, (float)nv, mean, m2);
-            } else {
-                float* p = ws + a.c_part + (((int64_t)arm * gridDim.x + blk) * 2) * C;
-                p[col] = mean;
-                p[C + col] = m2;
-            }
-        }
-    }
-    if (threadIdx.x == 0) {
-        float* p = ws + a.lat_part + ((int64_t)arm * gridDim.x + blk) * 2;
-        float k0 = 0.f, k1 = 0.f;
-#pragma unroll
-        for (int w = 0; w < LAT_NW; ++w) { k0 += sh_red[w][0]; k1 += sh_red[w][1]; }
-        p[0] = k0;
-        p[1] = k1;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Half-wave layout of the latent forward (C <= 96, L <= 32, 2 S <= 32 -- the reference's 92 / 10 / 2):
-// a cell owns 32 lanes x 3 registers (96 column slots for 92 categories instead of 64 x 2 = 128), a wave instruction
-// therefore serves TWO cells, and the softmax reductions stop at 32 lanes (the last cross-half step is dropped).
-// The kernel is VALU-bound (a wave instruction occupies its SIMD for four cycles): three registers for two cells
-// instead of two for one is a quarter less element-wise work, and a reduction step now counts for two cells.
-// 8 waves x 2 halves x 3 cells = the same LAT_ROWS cells per workgroup and the same partial layouts as k_lat_fwd.
-// ---------------------------------------------------------------------------------------------
-constexpr int LH_NW = 8, LH_NR = LAT_ROWS / (LH_NW * 2);   // (LH_CPL: common.hpp)
-static_assert(LH_NR * LH_NW * 2 == LAT_ROWS, "LAT_ROWS must be a multiple of 16");
-template <typename Op>
-__device__ __forceinline__ float half_allreduce(float v, Op op) {   // wave_allreduce without the 32-lane swap
-    v = op(v, dpp_f<0xB1>(v));
-    v = op(v, dpp_f<0x4E>(v));
-    v = op(v, dpp_f<0x141>(v));
-    v = op(v, dpp_f<0x140>(v));
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-}
-__device__ __forceinline__ float half_sum(float v) { return half_allreduce(v, [](float a, float b) { return a + b; }); }
-__device__ __forceinline__ float half_max(float v) { return half_allreduce(v, [](float a, float b) { return fmaxf(a, b); }); }
-__device__ __forceinline__ int half_min_i(int v) {
-    const float f = half_allreduce(__builtin_bit_cast(float, v), [](float a, float b) {
-        const int x = __builtin_bit_cast(int, a), y = __builtin_bit_cast(int, b);
-        return __builtin_bit_cast(float, x < y ? x : y);
-    });
-    return __builtin_bit_cast(int, f);
-}
-
-__global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, const NoiseDev nz_in,
-                                                         const float* __restrict__ params, float* __restrict__ ws,
-                                                         float* __restrict__ bn_running, int64_t* __restrict__ nbt) {
-    constexpr int NR = LH_NR, CP = LH_CPL, NT = 64 * LH_NW;
+// Forward.  grid (ceil(B/LAT_ROWS), A), 64 NW threads; cell slot r (NW CPW) + wv CPW + cell of the workgroup is cell group
+// r of wave wv -- all NR of them side by side: the per-cell work is one long dependency chain (three softmaxes = six
+// reductions, the Gumbel transform, four state-head dot products), and a wave that walks its cells one after the other
+// spends most of its time waiting on that chain (measured: 15 k cycles per cell with 4 waves per SIMD).
+template <int W, int NW>
+__global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const NoiseDev nz_in, const float* __restrict__ params,
+                                                      float* __restrict__ ws, float* __restrict__ bn_running, int64_t* __restrict__ nbt) {
+    using Cell = LatCell<W>;
+    constexpr int CPW = Cell::CPW, CP = Cell::CP, NR = LAT_ROWS / (NW * CPW), NT = 64 * NW;
+    static_assert(NR * NW * CPW == LAT_ROWS && NT % 128 == 0 && LAT_ROWS % (NT / 128) == 0, "cells per workgroup");
     const LatArgs a = a_in;
     const NoiseDev nz = nz_in;
     extern __shared__ __attribute__((aligned(16))) float lat_smem[];
     __shared__ __attribute__((aligned(16))) float sh_buf[LAT_ROWS * 128];   // prologue scratch, then the c tile
     __shared__ float sh_ps[NT / 128][128];
-    __shared__ float sh_red[LH_NW][2], sh_bn5[2][64];
+    __shared__ float sh_red[NW][2], sh_bn5[2][64];
     const int arm = blockIdx.y, blk = blockIdx.x, b0 = blk * LAT_ROWS;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int sub = lane & 31, hb = lane & 32, half = lane >> 5;
+    const int sub = Cell::sub(lane), base = Cell::base(lane), cell = Cell::cell(lane);
     const int B = a.B, L = a.L, C = a.C, S = a.S;
     const float* P = params + (int64_t)arm * a.per_arm;
     float* WcT = lat_smem;            // [L][C]
@@ -457,15 +166,15 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
     float r5[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        slot[r] = r * (LH_NW * 2) + wv * 2 + half;
+        slot[r] = r * (NW * CPW) + wv * CPW + cell;
         bb[r] = b0 + slot[r];
-        okr[r] = bb[r] < B;                   // per half-wave
+        okr[r] = bb[r] < B;                   // per cell
         r5[r] = sub < L ? ws[a.R5 + (ab + min(bb[r], B - 1)) * L + sub] : 0.f;
     }
     bool vcol[CP];
     float bcv[CP];
 #pragma unroll
-    for (int t = 0; t < CP; ++t) { vcol[t] = sub + 32 * t < C; bcv[t] = vcol[t] ? P[a.o_bc + sub + 32 * t] : 0.f; }
+    for (int t = 0; t < CP; ++t) { vcol[t] = sub + W * t < C; bcv[t] = vcol[t] ? P[a.o_bc + sub + W * t] : 0.f; }
     lat_stage_weights(WcT, Wms, P + a.o_wc, P + a.o_wms, L, C, S);
     const float* bms = P + a.o_bms;
 
@@ -519,10 +228,10 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
     for (int k = 0; k < L; ++k) {
         float w[CP];
 #pragma unroll
-        for (int t = 0; t < CP; ++t) w[t] = vcol[t] ? WcT[k * C + sub + 32 * t] : 0.f;
+        for (int t = 0; t < CP; ++t) w[t] = vcol[t] ? WcT[k * C + sub + W * t] : 0.f;
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-            const float xk = __shfl(xl[r], hb + k, 64);   // this half's own cell
+            const float xk = __shfl(xl[r], base + k, 64);   // this lane's own cell
 #pragma unroll
             for (int t = 0; t < CP; ++t) z[r][t] += xk * w[t];
         }
@@ -537,7 +246,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
             for (int t = 0; t < CP; ++t) if (vcol[t]) m[r] = fmaxf(m[r], v[r][t]);
         }
 #pragma unroll
-        for (int r = 0; r < NR; ++r) m[r] = half_max(m[r]);
+        for (int r = 0; r < NR; ++r) m[r] = Cell::max(m[r]);
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             ssum[r] = 0.f;
@@ -545,7 +254,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
             for (int t = 0; t < CP; ++t) { e[r][t] = vcol[t] ? expf(v[r][t] - m[r]) : 0.f; ssum[r] += e[r][t]; }
         }
 #pragma unroll
-        for (int r = 0; r < NR; ++r) ssum[r] = half_sum(ssum[r]);
+        for (int r = 0; r < NR; ++r) ssum[r] = Cell::sum(ssum[r]);
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             const float inv = 1.f / ssum[r];
@@ -560,7 +269,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
 #pragma unroll
     for (int r = 0; r < NR; ++r)
 #pragma unroll
-        for (int t = 0; t < CP; ++t) tmp[r][t] = cat_kept(a, sub + 32 * t) ? cp[r][t] * inv_tau : -INFINITY;   // masked-out: exp(-inf) = 0
+        for (int t = 0; t < CP; ++t) tmp[r][t] = cat_kept(a, sub + W * t) ? cp[r][t] * inv_tau : -INFINITY;   // masked-out: exp(-inf) = 0
     softmax_rows(tmp, cc);
 #pragma unroll
     for (int r = 0; r < NR; ++r)
@@ -581,7 +290,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
             for (int t = 0; t < CP; ++t) {
                 tmp[r][t] = 0.f;
                 if (vcol[t]) {
-                    const float U = gumbel_u(nz, arm, B, C, min(bb[r], B - 1), sub + 32 * t);
+                    const float U = gumbel_u(nz, arm, B, C, min(bb[r], B - 1), sub + W * t);
                     const float g = -logf(-logf(U + eps) + eps);
                     tmp[r][t] = (lc[r][t] + g) * inv_temp;
                 }
@@ -594,15 +303,15 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
             float mv = -INFINITY;
 #pragma unroll
             for (int t = 0; t < CP; ++t) if (vcol[t]) mv = fmaxf(mv, ys[r][t]);
-            mv = half_max(mv);
+            mv = Cell::max(mv);
             int cand = 1 << 30;
 #pragma unroll
-            for (int t = 0; t < CP; ++t) if (vcol[t] && ys[r][t] == mv) cand = min(cand, sub + 32 * t);
-            cand = half_min_i(cand);
+            for (int t = 0; t < CP; ++t) if (vcol[t] && ys[r][t] == mv) cand = min(cand, sub + W * t);
+            cand = Cell::min_i(cand);
             if (a.labels && a.eval_flag && okr[r] && sub == 0) a.labels[ab + bb[r]] = cand;    // eval: ys == c
 #pragma unroll
             for (int t = 0; t < CP; ++t) {
-                const float hv = (sub + 32 * t == cand) ? 1.f : 0.f;
+                const float hv = (sub + W * t == cand) ? 1.f : 0.f;
                 cs[r][t] = (hv - ys[r][t]) + ys[r][t];   // (y_hard - y).detach() + y, nn_model.py:492
             }
         }
@@ -618,7 +327,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
     for (int r = 0; r < NR; ++r) {
 #pragma unroll
         for (int t = 0; t < CP; ++t) {
-            const int col = sub + 32 * t;
+            const int col = sub + W * t;
             sh_buf[slot[r] * 128 + col] = (okr[r] && vcol[t]) ? cc[r][t] : 0.f;
             if (okr[r] && vcol[t]) {
                 const int64_t o = (ab + bb[r]) * C + col;
@@ -641,7 +350,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
         const float wl = sub < L ? w[sub] : 0.f;
         float wc[CP], pr[NR];
 #pragma unroll
-        for (int t = 0; t < CP; ++t) wc[t] = vcol[t] ? w[L + sub + 32 * t] : 0.f;
+        for (int t = 0; t < CP; ++t) wc[t] = vcol[t] ? w[L + sub + W * t] : 0.f;
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             pr[r] = xl[r] * wl;
@@ -651,14 +360,14 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
         const float bo = bms[o];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-            const float pv = half_sum(pr[r]) + bo;
+            const float pv = Cell::sum(pr[r]) + bo;
             if (sub == o) mso[r] = pv;
         }
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         if (okr[r] && sub < 2 * S) ws[a.MS + (ab + bb[r]) * 2 * S + sub] = mso[r];
-        const float sg = __shfl(mso[r], hb + ((sub + S) & 31), 64);
+        const float sg = __shfl(mso[r], base + ((sub + S) & (W - 1)), 64);
         if (okr[r] && sub < S) {
             const int b = bb[r];
             const float mu = mso[r];
@@ -685,7 +394,7 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
         constexpr int G = NT / 128, RPG = LAT_ROWS / G;
         const int col = threadIdx.x & 127, g = threadIdx.x >> 7;
         const int nv = min(LAT_ROWS, B - b0);
-        const bool live = col < 32 * CP;              // columns the cells wrote
+        const bool live = col < W * CP;              // columns the cells wrote
         float v[RPG];
         float s1 = 0.f;
 #pragma unroll
@@ -719,11 +428,12 @@ __global__ __launch_bounds__(64 * LH_NW) void k_lat_fwd_h(const LatArgs a_in, co
         float* p = ws + a.lat_part + ((int64_t)arm * gridDim.x + blk) * 2;
         float k0 = 0.f, k1 = 0.f;
 #pragma unroll
-        for (int w = 0; w < LH_NW; ++w) { k0 += sh_red[w][0]; k1 += sh_red[w][1]; }
+        for (int w = 0; w < NW; ++w) { k0 += sh_red[w][0]; k1 += sh_red[w][1]; }
         p[0] = k0;
         p[1] = k1;
     }
 }
+constexpr auto k_lat_fwd = k_lat_fwd_g<64, LAT_NW>, k_lat_fwd_h = k_lat_fwd_g<32, LH_NW>;
 
 // ---------------------------------------------------------------------------------------------
 // coupling: for every cell, over all arms.  u_a = log(c_a + eps) * iv_a
@@ -833,214 +543,21 @@ __global__ __launch_bounds__(256) void k_loss_finalize(int A, int B, int D, int 
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward of the latent block.  grid (ceil(B/LAT_ROWS_BWD), A), 64 * LATB_NW threads, one wave per cell at a time.
+// backward of the latent block.  grid (ceil(B/LAT_ROWS_BWD), A), 64 NW threads, the geometries of the forward (LatCell).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * LATB_NW) void k_lat_bwd(const LatArgs a_in, const NoiseDev nz_in,
-                                                  const float* __restrict__ params, float* __restrict__ ws) {
+template <int W, int NW>
+__global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const NoiseDev nz_in, const float* __restrict__ params,
+                                                      float* __restrict__ ws) {
+    using Cell = LatCell<W>;
+    constexpr int CPW = Cell::CPW, CP = Cell::CP, NR = LAT_ROWS_BWD / (NW * CPW);
+    static_assert(NR * NW * CPW == LAT_ROWS_BWD, "cells per workgroup");
     const LatArgs a = a_in;
     const NoiseDev nz = nz_in;
     extern __shared__ __attribute__((aligned(16))) float lat_smem[];
-    __shared__ float sh_s[LATB_NW][2][64];
+    __shared__ float sh_s[NW][2][64];
     const int arm = blockIdx.y, blk = blockIdx.x, b0 = blk * LAT_ROWS_BWD;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int A = a.A, B = a.B, L = a.L, C = a.C, S = a.S;
-    const float* P = params + (int64_t)arm * a.per_arm;
-    float* WcT = lat_smem;            // [L][C]
-    float* Wms = lat_smem + C * L;    // [2S][L+C]
-    lat_stage_weights(WcT, Wms, P + a.o_wc, P + a.o_wms, L, C, S);
-    const int64_t ab = (int64_t)arm * B;
-    const float eps = a.eps, invB = 1.f / (float)B;
-    const float coefG = 2.f * a.lam * invB;
-
-    float Tk[CPL], cmean[CPL], ivm[CPL], ivall[MMVAE_MAX_ARMS][CPL];
-#pragma unroll
-    for (int t = 0; t < CPL; ++t) {
-        const int col = lane + 64 * t;
-        Tk[t] = col < C ? ws[a.T + arm * C + col] : 0.f;
-        if (a.acc_T >= 0 && col < C) {
-            double s1, s2;
-            acc_get(reinterpret_cast<const long long*>(ws + a.acc_T) + (int64_t)arm * ACC_SET_I64, col, s1, s2);
-            Tk[t] = (float)s1;
-        }
-        cmean[t] = col < C ? ws[a.c_mean + arm * C + col] : 0.f;
-        ivm[t] = col < C ? ws[a.c_iv + arm * C + col] : 0.f;
-#pragma unroll
-        for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa) ivall[aa][t] = (aa < A && col < C) ? ws[a.c_iv + aa * C + col] : 0.f;
-    }
-    float s1 = 0.f, s2 = 0.f;   // BN5 backward sums for column `lane` (< L)
-
-    // The wave's LATB_NR cells side by side, every global load of both issued before the first use: beside the dW11
-    // GEMM of the side stream this kernel's 4-byte loads queue behind the GEMM's in the CU's in-order memory pipe
-    // (82 us in the step against 28 us alone when each cell's loads were issued and awaited one after the other).
-    constexpr int NR = LATB_NR;
-    int bb[NR];
-    bool okr[NR];
-    float gs_l[NR], mu_l[NR], lv_l[NR], sg_l[NR], xlow_l[NR];
-    float cc[NR][CPL], ys[NR][CPL], gz[NR][CPL], cp[NR][CPL], call[NR][MMVAE_MAX_ARMS][CPL];
-    const bool vcol[CPL] = {lane < C, lane + 64 < C};
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        bb[r] = b0 + wv + LATB_NW * r;
-        okr[r] = bb[r] < B;                         // wave-uniform
-        const int64_t b = min(bb[r], B - 1);        // cells beyond the batch recompute the last cell; nothing is stored
-        gs_l[r] = lane < S ? ws[a.GZIN + (ab + b) * (C + S) + C + lane] : 0.f;
-        mu_l[r] = lane < S ? ws[a.MU + (ab + b) * S + lane] : 0.f;
-        lv_l[r] = lane < S ? ws[a.LV + (ab + b) * S + lane] : 0.f;
-        sg_l[r] = lane < S ? ws[a.MS + (ab + b) * 2 * S + S + lane] : 0.f;
-        xlow_l[r] = lane < L ? ws[a.XLOW + (ab + b) * L + lane] : 0.f;
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) {
-            const int col = lane + 64 * t;
-            const int64_t o = (ab + b) * C + col;
-            cc[r][t] = vcol[t] ? ws[a.CC + o] : 0.f;
-            ys[r][t] = vcol[t] ? ws[a.YSOFT + o] : 0.f;
-            cp[r][t] = vcol[t] ? ws[a.CPROB + o] : 0.f;
-            gz[r][t] = vcol[t] ? ws[a.GZIN + (ab + b) * (C + S) + col] : 0.f;
-#pragma unroll
-            for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa)
-                call[r][aa][t] = (aa < A && vcol[t]) ? ws[a.CC + ((int64_t)aa * B + b) * C + col] : 1.f;
-        }
-    }
-    const float inv_temp = 1.f / a.temp, inv_tau = 1.f / a.tau, inv_bm1 = 1.f / (float)(B - 1);
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int b = min(bb[r], B - 1);
-        // ---- state head backward (lanes < S)
-        float gms = 0.f;   // lane o < 2S: d loss / d MS[o]
-        {
-            float gmu = 0.f, gsig = 0.f;
-            if (lane < S) {
-                float gs = gs_l[r];
-                if (a.training && a.s_drop > 0.f)
-                    gs = state_keep(nz, arm, B, S, b, lane) ? gs / (1.f - a.s_drop) : 0.f;
-                const float mu = mu_l[r], lv = lv_l[r], sg = sg_l[r];
-                const float var = 1.f / (1.f + expf(-sg));
-                const float U = state_u(nz, arm, B, S, b, lane);
-                const float elv = expf(lv);
-                gmu = gs + a.am1 * a.beta * mu * invB;
-                const float glv = gs * U * 0.5f * sqrtf(elv) + a.am1 * a.beta * (-0.5f * invB) * (1.f - elv);
-                const float gvar = glv / (var + eps);
-                gsig = gvar * var * (1.f - var);
-            }
-            const float gsig_sh = __shfl(gsig, (lane - S) & 63, 64);   // lane S+s takes lane s's gsig
-            if (lane < S) gms = gmu;
-            else if (lane < 2 * S) gms = gsig_sh;
-            if (okr[r] && lane < 2 * S) ws[a.GMS + (ab + b) * 2 * S + lane] = gms;
-        }
-        // ---- gy = gms [Wmu; Wsigma]
-        float gxl = 0.f, gcs[CPL] = {0.f, 0.f};
-        for (int o = 0; o < 2 * S; ++o) {
-            const float go = __shfl(gms, o, 64);
-            const float* w = Wms + (int64_t)o * (L + C);
-            if (lane < L) gxl += go * w[lane];
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) if (vcol[t]) gcs[t] += go * w[L + lane + 64 * t];
-        }
-        // ---- gradient w.r.t. the sample, through the Gumbel softmax to c
-        float lc[CPL], gc[CPL], usum[CPL] = {0.f, 0.f}, rcc[CPL];
-        float dot = 0.f;
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) {
-            lc[t] = gc[t] = 0.f;
-            rcc[t] = 1.f / (cc[r][t] + eps);
-            if (vcol[t]) {
-                gcs[t] += gz[r][t];
-                dot += ys[r][t] * gcs[t];
-#pragma unroll
-                for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa)
-                    if (aa < A) {
-                        const float l_aa = logf(call[r][aa][t] + eps);
-                        usum[t] += l_aa * ivall[aa][t];
-                        if (aa == arm) lc[t] = l_aa;      // this arm's own log c: the same value, computed once
-                    }
-            }
-        }
-        if (a.eval_flag) {
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) gc[t] = gcs[t];
-        } else {
-            dot = wave_sum(dot);
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) gc[t] = (ys[r][t] * (gcs[t] - dot) * inv_temp) * rcc[t];
-        }
-        // ---- coupling / entropy terms on c (nn_model.py:558-569)
-        float dot2 = 0.f;
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) {
-            if (vcol[t]) {
-                const float G = coefG * ((float)A * lc[t] * ivm[t] - usum[t]);
-                gc[t] += (float)(A - 1) * (lc[t] + cc[r][t] * rcc[t]) * invB;
-                gc[t] += G * ivm[t] * rcc[t];
-                gc[t] += (Tk[t] * (-0.5f) * ivm[t] * ivm[t] * ivm[t]) * 2.f * (cc[r][t] - cmean[t]) * inv_bm1;
-                dot2 += cc[r][t] * gc[t];
-            } else {
-                gc[t] = 0.f;
-            }
-        }
-        dot2 = wave_sum(dot2);
-        // ---- double softmax backward
-        float gq[CPL], dot3 = 0.f;
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) {
-            gq[t] = cc[r][t] * (gc[t] - dot2) * inv_tau;
-            dot3 += cp[r][t] * gq[t];
-        }
-        dot3 = wave_sum(dot3);
-        float gzc[CPL];
-#pragma unroll
-        for (int t = 0; t < CPL; ++t) {
-            gzc[t] = cp[r][t] * (gq[t] - dot3);
-            if (okr[r] && vcol[t]) ws[a.GZC + (ab + b) * C + lane + 64 * t] = gzc[t];
-        }
-        // ---- g5 = gy[:, :L] + gzc Wc
-        float g5 = 0.f;
-        for (int k = 0; k < L; ++k) {
-            float p = 0.f;
-#pragma unroll
-            for (int t = 0; t < CPL; ++t) if (vcol[t]) p += gzc[t] * WcT[k * C + lane + 64 * t];
-            p = wave_sum(p);
-            if (lane == k) g5 = gxl + p;
-        }
-        if (okr[r] && lane < L) {
-            ws[a.G5 + (ab + b) * L + lane] = g5;
-            s1 += g5;
-            s2 += g5 * xlow_l[r];
-        }
-    }
-    sh_s[wv][0][lane] = s1;
-    sh_s[wv][1][lane] = s2;
-    lds_barrier();
-    if (threadIdx.x < L) {
-        const int k = threadIdx.x;
-        float* p = ws + a.bnb_part5 + (((int64_t)arm * gridDim.x + blk) * 2) * L;
-        float k0 = 0.f, k1 = 0.f;
-        for (int w = 0; w < LATB_NW; ++w) { k0 += sh_s[w][0][k]; k1 += sh_s[w][1][k]; }
-        if (a.acc_bnb5 >= 0) {
-            acc_add_sums(reinterpret_cast<long long*>(ws + a.acc_bnb5) + (int64_t)arm * ACC_SET_I64, k, k0, k1);
-        } else {
-            p[k] = k0;
-            p[L + k] = k1;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Half-wave layout of the latent backward (same limits and reasons as k_lat_fwd_h): a cell owns 32 lanes x 3
-// registers, a wave instruction serves two cells.  4 waves x 2 halves x 2 cells = LAT_ROWS_BWD cells per workgroup
-// (the partial layout of k_lat_bwd).
-// ---------------------------------------------------------------------------------------------
-constexpr int LBH_NW = 4, LBH_NR = LAT_ROWS_BWD / (LBH_NW * 2);
-static_assert(LBH_NR * LBH_NW * 2 == LAT_ROWS_BWD, "LAT_ROWS_BWD must be a multiple of 8");
-__global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, const NoiseDev nz_in,
-                                                          const float* __restrict__ params, float* __restrict__ ws) {
-    constexpr int NR = LBH_NR, CP = LH_CPL;
-    const LatArgs a = a_in;
-    const NoiseDev nz = nz_in;
-    extern __shared__ __attribute__((aligned(16))) float lat_smem[];
-    __shared__ float sh_s[LBH_NW][2][64];
-    const int arm = blockIdx.y, blk = blockIdx.x, b0 = blk * LAT_ROWS_BWD;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int sub = lane & 31, hb = lane & 32, half = lane >> 5;
+    const int sub = Cell::sub(lane), base = Cell::base(lane), cell = Cell::cell(lane);
     const int A = a.A, B = a.B, L = a.L, C = a.C, S = a.S;
     const float* P = params + (int64_t)arm * a.per_arm;
     float* WcT = lat_smem;            // [L][C]
@@ -1054,7 +571,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
     float Tk[CP], cmean[CP], ivm[CP], ivall[MMVAE_MAX_ARMS][CP];
 #pragma unroll
     for (int t = 0; t < CP; ++t) {
-        const int col = sub + 32 * t;
+        const int col = sub + W * t;
         vcol[t] = col < C;
         Tk[t] = vcol[t] ? ws[a.T + arm * C + col] : 0.f;
         if (a.acc_T >= 0 && vcol[t]) {
@@ -1067,7 +584,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
 #pragma unroll
         for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa) ivall[aa][t] = (aa < A && vcol[t]) ? ws[a.c_iv + aa * C + col] : 0.f;
     }
-    float s1 = 0.f, s2 = 0.f;   // BN5 backward sums for column `sub` (< L), this half's cells
+    float s1 = 0.f, s2 = 0.f;   // BN5 backward sums for column `sub` (< L), this lane group's cells
 
     int bb[NR];
     bool okr[NR];
@@ -1075,8 +592,8 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
     float cc[NR][CP], ys[NR][CP], gz[NR][CP], cp[NR][CP], call[NR][MMVAE_MAX_ARMS][CP];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        bb[r] = b0 + r * (LBH_NW * 2) + wv * 2 + half;
-        okr[r] = bb[r] < B;                         // per half-wave
+        bb[r] = b0 + r * (NW * CPW) + wv * CPW + cell;
+        okr[r] = bb[r] < B;                         // per cell
         const int64_t b = min(bb[r], B - 1);        // cells beyond the batch recompute the last cell; nothing is stored
         gs_l[r] = sub < S ? ws[a.GZIN + (ab + b) * (C + S) + C + sub] : 0.f;
         mu_l[r] = sub < S ? ws[a.MU + (ab + b) * S + sub] : 0.f;
@@ -1085,7 +602,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
         xlow_l[r] = sub < L ? ws[a.XLOW + (ab + b) * L + sub] : 0.f;
 #pragma unroll
         for (int t = 0; t < CP; ++t) {
-            const int col = sub + 32 * t;
+            const int col = sub + W * t;
             const int64_t o = (ab + b) * C + col;
             cc[r][t] = vcol[t] ? ws[a.CC + o] : 0.f;
             ys[r][t] = vcol[t] ? ws[a.YSOFT + o] : 0.f;
@@ -1100,7 +617,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const int b = min(bb[r], B - 1);
-        // ---- state head backward (lanes sub < S of each half)
+        // ---- state head backward (lanes sub < S of each cell)
         float gms = 0.f;   // sub = o < 2S: d loss / d MS[o]
         {
             float gmu = 0.f, gsig = 0.f;
@@ -1117,7 +634,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
                 const float gvar = glv / (var + eps);
                 gsig = gvar * var * (1.f - var);
             }
-            const float gsig_sh = __shfl(gsig, hb + ((sub - S) & 31), 64);   // sub S+s takes sub s's gsig
+            const float gsig_sh = __shfl(gsig, base + ((sub - S) & (W - 1)), 64);   // sub S+s takes sub s's gsig
             if (sub < S) gms = gmu;
             else if (sub < 2 * S) gms = gsig_sh;
             if (okr[r] && sub < 2 * S) ws[a.GMS + (ab + b) * 2 * S + sub] = gms;
@@ -1127,11 +644,11 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
 #pragma unroll
         for (int t = 0; t < CP; ++t) gcs[t] = 0.f;
         for (int o = 0; o < 2 * S; ++o) {
-            const float go = __shfl(gms, hb + o, 64);
+            const float go = __shfl(gms, base + o, 64);
             const float* w = Wms + (int64_t)o * (L + C);
             if (sub < L) gxl += go * w[sub];
 #pragma unroll
-            for (int t = 0; t < CP; ++t) if (vcol[t]) gcs[t] += go * w[L + sub + 32 * t];
+            for (int t = 0; t < CP; ++t) if (vcol[t]) gcs[t] += go * w[L + sub + W * t];
         }
         // ---- gradient w.r.t. the sample, through the Gumbel softmax to c
         float lc[CP], gc[CP], usum[CP], rcc[CP];
@@ -1156,7 +673,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
 #pragma unroll
             for (int t = 0; t < CP; ++t) gc[t] = gcs[t];
         } else {
-            dot = half_sum(dot);
+            dot = Cell::sum(dot);
 #pragma unroll
             for (int t = 0; t < CP; ++t) gc[t] = (ys[r][t] * (gcs[t] - dot) * inv_temp) * rcc[t];
         }
@@ -1174,7 +691,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
                 gc[t] = 0.f;
             }
         }
-        dot2 = half_sum(dot2);
+        dot2 = Cell::sum(dot2);
         // ---- double softmax backward
         float gq[CP], dot3 = 0.f;
 #pragma unroll
@@ -1182,20 +699,20 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
             gq[t] = cc[r][t] * (gc[t] - dot2) * inv_tau;
             dot3 += cp[r][t] * gq[t];
         }
-        dot3 = half_sum(dot3);
+        dot3 = Cell::sum(dot3);
         float gzc[CP];
 #pragma unroll
         for (int t = 0; t < CP; ++t) {
             gzc[t] = cp[r][t] * (gq[t] - dot3);
-            if (okr[r] && vcol[t]) ws[a.GZC + (ab + b) * C + sub + 32 * t] = gzc[t];
+            if (okr[r] && vcol[t]) ws[a.GZC + (ab + b) * C + sub + W * t] = gzc[t];
         }
         // ---- g5 = gy[:, :L] + gzc Wc
         float g5 = 0.f;
         for (int k = 0; k < L; ++k) {
             float p = 0.f;
 #pragma unroll
-            for (int t = 0; t < CP; ++t) if (vcol[t]) p += gzc[t] * WcT[k * C + sub + 32 * t];
-            p = half_sum(p);
+            for (int t = 0; t < CP; ++t) if (vcol[t]) p += gzc[t] * WcT[k * C + sub + W * t];
+            p = Cell::sum(p);
             if (sub == k) g5 = gxl + p;
         }
         if (okr[r] && sub < L) {
@@ -1212,9 +729,12 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
         float* p = ws + a.bnb_part5 + (((int64_t)arm * gridDim.x + blk) * 2) * L;
         float k0 = 0.f, k1 = 0.f;
 #pragma unroll
-        for (int w = 0; w < LBH_NW; ++w) {
-            k0 += sh_s[w][0][k] + sh_s[w][0][32 + k];      // the two halves hold different cells
-            k1 += sh_s[w][1][k] + sh_s[w][1][32 + k];
+        for (int w = 0; w < NW; ++w) {
+            float c0 = sh_s[w][0][k], c1 = sh_s[w][1][k];       // the CPW lane groups hold different cells: their sum
+#pragma unroll
+            for (int h = 1; h < CPW; ++h) { c0 += sh_s[w][0][W * h + k]; c1 += sh_s[w][1][W * h + k]; }   // first, then the wave's
+            k0 += c0;
+            k1 += c1;
         }
         if (a.acc_bnb5 >= 0) {
             acc_add_sums(reinterpret_cast<long long*>(ws + a.acc_bnb5) + (int64_t)arm * ACC_SET_I64, k, k0, k1);
@@ -1224,6 +744,7 @@ __global__ __launch_bounds__(64 * LBH_NW) void k_lat_bwd_h(const LatArgs a_in, c
         }
     }
 }
+constexpr auto k_lat_bwd = k_lat_bwd_g<64, LATB_NW>, k_lat_bwd_h = k_lat_bwd_g<32, LBH_NW>;
 
 // ---------------------------------------------------------------------------------------------
 // slabs -> flat gradient buffer
@@ -1457,12 +978,15 @@ int launch_bn_eval_stats(const Ctx& c, const float* bn_running) {
     return 0;
 }
 
+// dynamic LDS of the four latent kernels: what lat_stage_weights stages
+static size_t lat_smem_bytes(const mmvae_dims& d) { return (size_t)(d.C * d.L + 2 * d.S * (d.L + d.C)) * sizeof(float); }
+
 int launch_lat_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
                    int32_t* labels) {
     LatArgs a = make_lat_args(c);
     a.labels = labels;
     NoiseDev nd = make_noise_dev(nz, c.h);
-    const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
+    const size_t shm = lat_smem_bytes(c.d);
     if (c.plan.lat_half) {
         // (lat_fork_rides implies lat_half, i.e. this launch)
         launch_k(c, c.plan.lat_fork_rides ? c.ev(EV_LAT) : nullptr, k_lat_fwd_h, dim3(c.lay.nblkl, c.d.A), dim3(64 * LH_NW), shm, a, nd, params, c.ws, bn_running, nbt);
@@ -1522,7 +1046,7 @@ int launch_loss_finalize(const Ctx& c, float* loss_out, int mode) {
 int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params) {
     LatArgs a = make_lat_args(c);
     NoiseDev nd = make_noise_dev(nz, c.h);
-    const size_t shm = (size_t)(c.d.C * c.d.L + 2 * c.d.S * (c.d.L + c.d.C)) * sizeof(float);
+    const size_t shm = lat_smem_bytes(c.d);
     if (c.plan.lat_half) {
         hipLaunchKernelGGL(k_lat_bwd_h, dim3(cdiv(c.d.B, LAT_ROWS_BWD), c.d.A), dim3(64 * LBH_NW), shm, c.stream, a, nd, params, c.ws);
         HIP_LAUNCH_CHECK("k_lat_bwd_h");

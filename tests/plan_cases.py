@@ -40,6 +40,8 @@ ROWS = [
     _r("a4", 4, 200, 256, 100), _r("a6", 6, 200, 256, 100), _r("a8", 8, 200, 256, 100),
     _r("lat_c97", 2, 200, 256, 100, C=97), _r("lat_l33", 2, 200, 256, 100, L=33), _r("lat_s17", 2, 200, 256, 100, S=17),
     _r("cs129", 2, 200, 256, 100, C=125, S=4),
+    # the wave-form latent kernels on a ragged batch: 57 = 48 + 9 = 7 * 8 + 1 (LAT_ROWS / LAT_ROWS_BWD cells per workgroup)
+    _r("lat_c97_b57", 2, 57, 256, 100, C=97),
     _r("d_min_h100", 2, 70, 4, 100), _r("d_min_h64", 2, 70, 4, 64),
     _r("d36_h100", 2, 70, 36, 100), _r("d36_h64", 2, 70, 36, 64),
     _r("d132_h100", 2, 300, 132, 100), _r("d132_h64", 2, 300, 132, 64),
@@ -94,7 +96,10 @@ STEP = {
     # the coupling as a role of the decoder chain's launch from four arms (it needs the chain planes: not on engine 0), to five
     "a4": {"fp32_mfma": _E0, "bf16": dict(_E1, **_IN_DEC), "fp32x3": dict(_E2, **_IN_DEC)},
     "a6": _STD, "a8": _STD,
-    "lat_c97": _each(_STD, **_NO_HALF), "lat_l33": _each(_STD, **_NO_HALF), "lat_s17": _each(_STD, **_NO_HALF),
+    "lat_c97": _each(_STD, **_NO_HALF),
+    "lat_c97_b57": _each(_STD, **_NO_HALF),
+    "lat_l33": _each(_STD, **_NO_HALF),
+    "lat_s17": _each(_STD, **_NO_HALF),
     # C + S = 129: no chain planes (bf16: then no head launch either); C = 125 is also past the half-wave latent kernels
     "cs129": {"fp32_mfma": dict(_E0, **_NO_HALF),
               "bf16": dict(_E1, chain_planes=False, presplit=False, zero="ZERO_XBITS", **_NO_HALF),
