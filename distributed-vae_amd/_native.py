@@ -71,6 +71,11 @@ class AugTensors(C.Structure):
                 ("bnz_weight", C.c_void_p), ("bnz_bias", C.c_void_p), ("bnz_mean", C.c_void_p), ("bnz_var", C.c_void_p)]
 
 
+class EncodeOut(C.Structure):
+    """mmvae_encode_out: the arrays an encode is to write; each may be None."""
+    _fields_ = [(n, C.c_void_p) for n in ("x_low", "c_prob", "c", "c_smp", "s_mean", "s_logvar", "labels", "counts")]
+
+
 N_EVENTS = 8
 N_TUNE = 24
 # mmvae_exec.tune indices (private: csrc/tune.h; public: MMVAE_TUNE_ENGINE in include/mmvae.h) and the
@@ -116,7 +121,7 @@ PLAN_NAMES = ("kind", "fast", "big", "small_x3", "fc11", "gd10_slabs", "dw11_sla
               "presplit", "bwd_small_planes", "d10_planes", "dz1_in_apply", "dec_planes", "zero", "rowmap", "dz11_bf16",
               "dw11_side", "loss_on_side", "couple", "lat_fork_rides", "fc11_fork_rides")
 CALL_KINDS = {"STEP": 0, "STEP_ROWS": 1, "FORWARD": 2, "BACKWARD": 3, "LOSS": 4, "CLASSIFY": 5, "REPLAY": 6, "DECODE": 7,
-              "TRAVERSE": 8}
+              "TRAVERSE": 8, "ENCODE": 10}
 PLAN_ENUMS = {
     "big": ("GEMM_GENERAL", "GEMM_FP32", "GEMM_BF16", "GEMM_X3"),
     "fc11": ("FC11_GENERAL", "FC11_ZG", "FC11_ZT", "FC11_BF16", "FC11_X3", "FC11_OUT_BF16", "FC11_OUT_X3"),
@@ -215,6 +220,13 @@ def lib():
     L.mmvae_state_changes.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, i32, i32, vp, vp,
                                       C.c_size_t, ex, vp]
     L.mmvae_state_changes.restype = C.c_int
+    L.mmvae_encode_workspace_bytes.argtypes = [C.POINTER(Dims), ex]
+    L.mmvae_encode_workspace_bytes.restype = C.c_size_t
+    L.mmvae_encode.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, i64, C.POINTER(EncodeOut),
+                               i64, i64, vp, C.c_size_t, ex, vp]
+    L.mmvae_encode.restype = C.c_int
+    L.mmvae_intermed.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, i64, vp, vp, vp]
+    L.mmvae_intermed.restype = C.c_int
     for fn in ("mmvae_check_dims", "mmvae_param_layout", "mmvae_splits", "mmvae_forward", "mmvae_loss",
                "mmvae_backward", "mmvae_adam_step", "mmvae_train_step", "mmvae_dump_noise", "mmvae_debug_stage",
                "mmvae_eval_classify", "mmvae_classify", "mmvae_confmat_accumulate", "mmvae_consensus", "mmvae_aug_pack",
@@ -418,6 +430,30 @@ class Engine:
                                         self._x(), self._s()), "mmvae_eval_classify")
         return labels
 
+    def encode(self, hyper: Hyper, noise: Optional[Noise], params, bn_running, nbt, x, x_arm_stride, out: Dict[str, torch.Tensor],
+               row0: int = 0, rows: Optional[int] = None):
+        """mmvae_encode: the encoder (and, in eval mode, the latent block) without decoder or fc11.  ``out``: the arrays to
+        write by field name of mmvae_encode_out ([A, rows, .] each, contiguous); cell b of arm a lands at row row0 + b."""
+        d = self.dims
+        rows = d.B if rows is None else int(rows)
+        eo = EncodeOut()
+        widths = {"x_low": d.L, "c_prob": d.C, "c": d.C, "c_smp": d.C, "s_mean": d.S, "s_logvar": d.S}
+        for name, t in out.items():
+            if t is None:
+                continue
+            if name == "counts":
+                assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == max(d.A * (d.A - 1) // 2, 1) * d.C * d.C
+            elif name == "labels":
+                assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (d.A, rows)
+            else:
+                assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (d.A, rows, widths[name]), name
+            assert t.device == self.device
+            setattr(eo, name, t.data_ptr())
+        check(lib().mmvae_encode(C.byref(self.dims), C.byref(hyper), C.byref(noise) if noise is not None else None, _ptr(params),
+                                 _ptr(bn_running), _ptr(nbt), _ptr(x), int(x_arm_stride), C.byref(eo), int(row0), rows,
+                                 _ptr(self.ws), self.ws_bytes, self._x(), self._s()), "mmvae_encode")
+        return out
+
     def debug_stage(self, stage: int, hyper: Hyper, noise: Noise, params, x, x_arm_stride, grads=None):
         check(lib().mmvae_debug_stage(C.byref(self.dims), C.byref(hyper), C.byref(noise), int(stage), _ptr(params),
                                       _ptr(x), x_arm_stride, _ptr(self.ws), self.ws_bytes, _ptr(grads), self._x(),
@@ -481,6 +517,13 @@ class DecodeEngine:
                                         _ptr(x), int(d_s), int(self.n_samp), _ptr(x_rec), _ptr(self.ws), self.ws_bytes,
                                         C.byref(self.ex), _stream(self.device)), "mmvae_state_changes")
         return x_rec
+
+
+def intermed(dims: Dims, hyper: Hyper, params, y: torch.Tensor, y_arm_stride: int, mu: torch.Tensor, var: torch.Tensor):
+    """mmvae_intermed: mu = fc_mu(y), var = sigmoid(fc_sigma(y)) for dims.B rows of dims.A arms (no workspace)."""
+    check(lib().mmvae_intermed(C.byref(dims), C.byref(hyper), _ptr(params), _ptr(y), int(y_arm_stride), _ptr(mu), _ptr(var),
+                               _stream(y.device)), "mmvae_intermed")
+    return mu, var
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, decoupled=False):

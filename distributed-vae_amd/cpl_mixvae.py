@@ -608,3 +608,56 @@ class cpl_mixVAE:
             "prune_indx": prune_indx,
             "cnss": cnss,
         }
+
+    @torch.no_grad()
+    def encode_dataset(self, dl, c_p=0, c_onehot=0):
+        """``eval_model`` without everything that needs the decoder: the latents of every batch ``(x, index)`` of ``dl`` from
+        the encoder and the latent block alone (``mixVAE_model.encode``: no decoder chain, no fc11, no x_rec, no loss),
+        each batch written straight into its rows of [A, N, .] device buffers, one copy to the host at the end.  Returns
+        ``eval_model``'s keys ``state_mu``, ``state_var``, ``state_cat``, ``prob_cat``, ``predicted_label``, ``data_indx``,
+        ``z_prob``, ``z_sample``, ``x_low``, ``prune_indx`` and ``cnss`` with its shapes, dtypes and values; ``recon_c`` and
+        the loss means are not in it."""
+        if self.ref_prior:
+            raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
+        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
+        n_rows = len(dl.dataset)
+        B = dl.batch_size
+        if B is None:
+            raise ValueError("error: expected non-None value")            # unwrap(dl.batch_size), cpl_mixvae.py:104-107
+        dev = self.device
+        was_training = self.model.training
+        self.model.eval()
+        bias = self.model.fcc[0].bias.detach().cpu().numpy()
+        pruning_mask = np.where(bias != 0.0)[0]
+        prune_indx = np.where(bias == 0.0)[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
+               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
+               "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
+        data_indx = torch.zeros(n_rows, dtype=torch.float64, device=dev)
+        from ._utils import confmat_counts, consensus_from_counts
+        counts = confmat_counts(A, Cc, dev)
+        for i, (x, data_idx) in enumerate(dl):
+            n_fst, n_lst = i * B, min((i + 1) * B, n_rows)
+            x = x.to(dev)
+            self.model.encode(x.expand(A, -1, -1), self.temp, mask=pruning_mask, out=out, row0=n_fst,
+                              counts=counts if A > 1 else None)
+            data_indx[n_fst:n_lst] = torch.as_tensor(data_idx).to(dev).to(torch.int64).to(torch.float64)
+        prob = out["c"].max(dim=-1).values
+        cnss = float(np.mean(consensus_from_counts(counts).cpu().numpy())) if A > 1 and n_rows else float("nan")
+        self.model.train(was_training)
+        to64 = lambda t: t.double().cpu().numpy()
+        lab1 = to64(out["labels"]) + 1.0
+        return {
+            "state_mu": to64(out["s_mean"]),
+            "state_var": to64(out["s_logvar"]),
+            "state_cat": lab1.copy(),
+            "prob_cat": to64(prob),
+            "predicted_label": lab1,
+            "data_indx": data_indx.cpu().numpy(),
+            "z_prob": to64(out["c"]),
+            "z_sample": to64(out["c_smp"]),
+            "x_low": to64(out["x_low"]),
+            "prune_indx": prune_indx,
+            "cnss": cnss,
+        }

@@ -287,7 +287,7 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
     p = Plan{};
     p.kind = kind;
     const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS, fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY ||
-                                                                 kind == CALL_TRAVERSE;
+                                                                 kind == CALL_TRAVERSE || kind == CALL_ENCODE;
     const bool dropout = c.dropout(), side = c.side() != nullptr;
     p.fast = fast_dims(d) && al16(params) && al16(x) && (xs & 3) == 0 && d.H >= 4 && (int64_t)d.B * d.D < ((int64_t)1 << 30);
     // engines of the five D x H products (mmvae_hyper.gemm_bf16: 1 bf16 operands, 2 fp32x3)
@@ -416,7 +416,7 @@ static int fc11_gd10(const Ctx& c, const float* params, float* x_rec, int need_g
 
 static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
                       const float* x, int64_t xs, float* x_rec, int need_grad, float* loss_out = nullptr,
-                      int32_t* labels = nullptr) {
+                      int32_t* labels = nullptr, const EncOut* enc = nullptr) {
     const Plan& p = c.plan;
     int rc;
     if ((p.zero == ZERO_MEMSET || p.zero == ZERO_XBITS) && (rc = launch_forward_zero(c, nz))) return rc;
@@ -432,6 +432,7 @@ static int do_forward(const Ctx& c, const mmvae_noise* nz, const float* params, 
         for (int layer = 2; layer <= 5; ++layer)
             if ((rc = launch_chain_fwd_enc(c, layer, params, bn_running, nbt))) return rc;
     }
+    if (p.kind == CALL_ENCODE) return launch_lat_enc(c, nz, params, bn_running, nbt, *enc, labels);   // mmvae_encode ends here
     if ((rc = launch_lat_fwd(c, nz, params, bn_running, nbt, labels))) return rc;   // (Plan::lat_fork_rides: EV_LAT rides on it)
     if (p.kind == CALL_CLASSIFY || p.kind == CALL_TRAVERSE) return 0;   // labels / the traversal's encoder: no decoder, no fc11
     Ctx cs = c;
@@ -817,6 +818,62 @@ int mmvae_state_changes(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_n
     return do_decode(cd, params, zb, nz, x_rec);
 }
 
+// ---- encode / intermed: every argument is checked before the first launch
+size_t mmvae_encode_workspace_bytes(const mmvae_dims* d, const mmvae_exec* ex) { return mmvae_workspace_bytes(d, ex); }
+
+int mmvae_encode(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, const float* params, float* bn_running,
+                 int64_t* nbt, const float* x, int64_t x_arm_stride, const mmvae_encode_out* out, int64_t out_row0,
+                 int64_t out_rows, void* ws, size_t ws_bytes, mmvae_exec* ex, void* stream) {
+    if (int rc = check_dims(d)) return rc;
+    if (int rc = check_decode_hyper(h)) return rc;
+    if (!params || !bn_running || !x || !out) { set_error("encode: null params / bn_running / x / out"); return MMVAE_E_BADARG; }
+    if (x_arm_stride < 0) { set_error("encode: negative arm stride"); return MMVAE_E_BADARG; }
+    const bool latent = out->c || out->c_smp || out->s_mean || out->s_logvar || out->labels || out->counts;
+    if (!latent && !out->x_low && !out->c_prob) { set_error("encode: every output is null"); return MMVAE_E_BADARG; }
+    if (out_row0 < 0 || out_rows < out_row0 + d->B) {
+        set_error("encode: rows [%lld, %lld + %d) do not fit the %lld destination rows", (long long)out_row0, (long long)out_row0,
+                  d->B, (long long)out_rows);
+        return MMVAE_E_BADARG;
+    }
+    if (out->counts && d->A < 2) { set_error("encode: counts need at least two arms (got A=%d)", d->A); return MMVAE_E_BADARG; }
+    if (h->training != 0 && h->training != 1) { set_error("encode: training must be 0 or 1"); return MMVAE_E_UNSUPPORTED; }
+    if (h->training && latent) {
+        set_error("encode: training mode offers the encoder outputs only (x_low, c_prob); mmvae_forward computes the latent block");
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (!h->training && !h->eval_flag) { set_error("encode: eval mode needs eval_flag = 1 (the noise-free sample)"); return MMVAE_E_UNSUPPORTED; }
+    mmvae_noise nzp{};   // eval mode draws nothing that reaches the outputs (the kernel's own state sample: Philox of seed 0, as
+    nzp.mode = 1;        // eval_classify); training mode reads the dropout keep-mask only
+    if (h->training) {
+        if (!nz) { set_error("noise descriptor is null"); return MMVAE_E_BADARG; }
+        if (nz->mode != 0 && nz->mode != 1) { set_error("noise mode must be 0 (explicit) or 1 (philox)"); return MMVAE_E_BADARG; }
+        if (h->x_drop < 0.f || h->x_drop >= 1.f) { set_error("dropout probabilities must be in [0,1)"); return MMVAE_E_BADARG; }
+        if (nz->mode == 0 && h->x_drop > 0.f && !nz->x_mask) { set_error("explicit noise: x_mask is null"); return MMVAE_E_BADARG; }
+        nzp = *nz;
+    }
+    Ctx c;
+    if (int rc = make_ctx(c, d, h, ws, ws_bytes, ex, stream)) return rc;
+    make_plan(c, CALL_ENCODE, params, x, x_arm_stride);
+    EncOut eo{out->x_low, out->c_prob, out->c, out->c_smp, out->s_mean, out->s_logvar, out->labels, out_row0, out_rows, !latent};
+    // the confusion counts read compact [A, B] labels: the kernel leaves them in a region only a backward pass uses
+    static_assert(sizeof(int32_t) == sizeof(float), "labels fit GZC's [A, B, C] floats");
+    int32_t* labels_ab = out->counts ? reinterpret_cast<int32_t*>(c.ws + c.lay.GZC) : nullptr;
+    if (int rc = do_forward(c, &nzp, params, bn_running, h->training ? nbt : nullptr, x, x_arm_stride, nullptr, 0, nullptr,
+                            labels_ab, &eo))
+        return rc;
+    if (out->counts) return launch_confmat(labels_ab, d->A, d->B, d->C, out->counts, c.stream);
+    return 0;
+}
+
+int mmvae_intermed(const mmvae_dims* d, const mmvae_hyper* h, const float* params, const float* y, int64_t y_arm_stride,
+                   float* mu, float* var, void* stream) {
+    if (int rc = check_dims(d)) return rc;
+    if (int rc = check_decode_hyper(h)) return rc;
+    if (!params || !y || !mu || !var) { set_error("intermed: null params / y / mu / var"); return MMVAE_E_BADARG; }
+    if (y_arm_stride < 0) { set_error("intermed: negative arm stride"); return MMVAE_E_BADARG; }
+    return launch_intermed(*d, make_poff(*d), params, y, y_arm_stride, mu, var, reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_classify(const float* c_probs, int64_t n_cells, int C, int32_t* labels, void* stream) {
     if (!c_probs || !labels || n_cells <= 0 || C <= 0) { set_error("classify: bad argument"); return MMVAE_E_BADARG; }
     return launch_classify(c_probs, n_cells, C, labels, reinterpret_cast<hipStream_t>(stream));
@@ -884,9 +941,10 @@ int mmvae_debug_plan(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_exec
     if (int rc = check_gemm_engine(h->gemm_bf16)) return rc;
     static_assert(MMVAE_CALL_STEP == CALL_STEP && MMVAE_CALL_STEP_ROWS == CALL_STEP_ROWS && MMVAE_CALL_FORWARD == CALL_FORWARD &&
                   MMVAE_CALL_BACKWARD == CALL_BACKWARD && MMVAE_CALL_LOSS == CALL_LOSS && MMVAE_CALL_CLASSIFY == CALL_CLASSIFY &&
-                  MMVAE_CALL_REPLAY == CALL_REPLAY && MMVAE_CALL_DECODE == CALL_DECODE && MMVAE_CALL_TRAVERSE == CALL_TRAVERSE,
+                  MMVAE_CALL_REPLAY == CALL_REPLAY && MMVAE_CALL_DECODE == CALL_DECODE && MMVAE_CALL_TRAVERSE == CALL_TRAVERSE &&
+                  MMVAE_CALL_ENCODE == CALL_ENCODE,
                   "MMVAE_CALL_* (include/mmvae.h) are the values of CallKind");
-    if (call_kind < CALL_STEP || call_kind > CALL_TRAVERSE) { set_error("unknown call kind %d", call_kind); return MMVAE_E_BADARG; }
+    if (call_kind < CALL_STEP || (call_kind > CALL_TRAVERSE && call_kind != CALL_ENCODE)) { set_error("unknown call kind %d", call_kind); return MMVAE_E_BADARG; }
     if (params_align < 0 || x_align < 0) { set_error("negative alignment"); return MMVAE_E_BADARG; }
     // what make_ctx gives make_plan to read -- dims, hyper, exec copy, layout -- without a workspace or a stream
     Ctx c{};

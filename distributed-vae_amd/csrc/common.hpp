@@ -746,7 +746,8 @@ inline bool fc11_slots_fit(const Layout& L, int B) { return (int64_t)cdiv(B, 128
 // Per-call plan: which kernels a call runs, on which stream, and which launch writes what for whom.  make_plan (api.hip)
 // builds it once per entry point; the launchers and drivers read it and decide nothing themselves.
 enum CallKind { CALL_STEP, CALL_STEP_ROWS, CALL_FORWARD, CALL_BACKWARD, CALL_LOSS, CALL_CLASSIFY, CALL_REPLAY /*debug stage*/,
-                CALL_DECODE /*mmvae_decode, and the decoder half of mmvae_state_changes*/, CALL_TRAVERSE /*its encoder half*/ };
+                CALL_DECODE /*mmvae_decode, and the decoder half of mmvae_state_changes*/, CALL_TRAVERSE /*its encoder half*/,
+                CALL_ENCODE = 10 /*9 stays unknown to mmvae_debug_plan; mmvae_encode: the encoder and the latent block, or its head alone*/ };
 // fc1, dW1, dW11: gemm_big.hip, fp32 matrix instruction (gemm_fast.hip), k_bf16_* / k_x3_* (gemm_bf16.hip)
 enum GemmFamily { GEMM_GENERAL, GEMM_FP32, GEMM_BF16, GEMM_X3 };
 // fc11 + d(d10): k_fc11_fused, k_fc11_zg (d(d10) folded in), k_fc11_zt + k_gd10_*, k_bf16_fc11* (+ k_bf16_gemm), k_x3_fc11g;
@@ -849,6 +850,21 @@ int launch_chain_fwd_enc(const Ctx& c, int layer /*2..5*/, const float* params, 
 int launch_chain_fwd_enc_eval(const Ctx& c, const float* params);   // eval mode: fc2..fc5 in one launch
 int launch_lat_fwd(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
                    int32_t* labels = nullptr /*eval: argmax of c per cell and arm*/);
+// mmvae_encode: where the latent kernel stores the caller's outputs -- cell b of arm a is row a * rows + row0 + b of each
+// array that is not null.  head: only x_low / c_prob are wanted, the kernel returns behind the first softmax.
+struct EncOut {
+    float *x_low, *c_prob, *c, *c_smp, *s_mean, *s_logvar;
+    int32_t* labels;
+    int64_t row0, rows;
+    bool head;
+};
+// the latent forward of a CALL_ENCODE plan (k_lat_fwd_g<W, NW, ENC>: the forward's kernel body with EncOut's stores); labels_ab: compact
+// [A, B] labels for the confusion counts, or null
+int launch_lat_enc(const Ctx& c, const mmvae_noise* nz, const float* params, float* bn_running, int64_t* nbt,
+                   const EncOut& eo, int32_t* labels_ab);
+// mmvae_intermed: mu = fc_mu(y), var = sigmoid(fc_sigma(y)) for N rows of every arm (k_intermed)
+int launch_intermed(const mmvae_dims& d, const POff& po, const float* params, const float* y, int64_t y_arm_stride, float* mu,
+                    float* var, hipStream_t s);
 int launch_chain_fwd_dec(const Ctx& c, const float* params);   // (with the coupling terms as a role: Plan::couple)
 int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
 int launch_couple(const Ctx& c);

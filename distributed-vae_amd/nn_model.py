@@ -128,6 +128,7 @@ class mixVAE_model(nn.Module):
         self._noise_offset = 0
         self._explicit_state_noise = None
         self._dec_engines = {}
+        self._arm_engines = {}
         self._exec: Optional[N.Exec] = None   # None: split factors / experiment switches from the environment
         # operand type of the five D x H GEMMs: "fp32" (the parity configuration) or "bf16" (BASELINE.json's bf16
         # configuration: operands rounded to bf16, fp32 accumulation; everything else and all parameters stay fp32)
@@ -195,6 +196,7 @@ class mixVAE_model(nn.Module):
         self._flat, self._flat_grad, self._bn_flat, self._nbt, self._layout = flat, grad, bn, nbt, lay
         self._engine = None
         self._engines = {}
+        self._arm_engines = {}
 
     def _ensure(self, B: int) -> N.Engine:
         if not self._is_packed():
@@ -398,6 +400,151 @@ class mixVAE_model(nn.Module):
         eng.eval_classify(self._hyper(temp, True), self._flat, self._bn_flat, xt, xs, labels, counts)
         self._ctx = None
         return labels
+
+    # ------------------------------------------------------------------ the encoder alone, latents without the decoder
+    def _mask_words(self, mask):
+        """The category subset of ``forward(mask=...)`` as the four words of mmvae_hyper.cat_mask, validated as ``forward``
+        validates it; None: every category is kept."""
+        if mask is None:
+            return None
+        import numpy as _np
+        mk = _np.asarray(mask.detach().cpu() if isinstance(mask, torch.Tensor) else mask)
+        mk = _np.flatnonzero(mk) if mk.dtype == _np.bool_ else _np.unique(mk.astype(_np.int64))
+        if mk.size == 0 or mk[0] < 0 or mk[-1] >= self.n_categories:
+            raise IndexError(f"category mask {mk.tolist()} outside [0, {self.n_categories})")
+        if mk.size == self.n_categories:
+            return None
+        words = [0, 0, 0, 0]
+        for k in mk.tolist():
+            words[k >> 5] |= 1 << (k & 31)
+        return words
+
+    def _arm_engine(self, B: int) -> N.Engine:
+        """The engine of a ONE-arm call on B cells (``encoder``): its split factors are those of the model's A-arm engine
+        for this batch, so that fc1 sums its K pieces in the order ``forward`` does and the outputs agree bit for bit."""
+        full = self._ensure(B)
+        mode = N.gemm_mode(self.gemm_dtype)
+        key = (B, str(self._flat.device), id(self._exec), mode)
+        eng = self._arm_engines.pop(key, None)
+        if eng is None:
+            ex = N.Exec()
+            for i in range(N.N_TUNE):
+                ex.tune[i] = full.ex.tune[i]
+            for i, k in enumerate(full.splits()):
+                ex.split[i] = k
+            d = full.dims
+            eng = N.Engine(1, B, d.D, d.H, d.L, d.C, d.S, self._flat.device, ex, gemm_engine=mode)
+        self._arm_engines[key] = eng
+        while len(self._arm_engines) > 3:
+            self._arm_engines.pop(next(iter(self._arm_engines)))
+        return eng
+
+    @torch.no_grad()
+    def encoder(self, x, arm):
+        """nn_model.py:263-269: ``(x_low, softmax(fcc(x_low)))`` of arm ``arm`` for x [N, D] on the device; returns the
+        device tensors [N, L] and [N, C].  Eval mode: running statistics, any N.  Training mode, as in the reference: input
+        dropout (the mask a ``forward`` at this point of the model's noise source would draw for this arm; one entry /
+        offset is consumed), batch statistics, and ``batch_l1..5[arm]``'s running statistics and counters move."""
+        arm = int(arm)
+        if not (0 <= arm < self.n_arm):
+            raise IndexError(f"arm {arm} outside [0, {self.n_arm})")
+        if x.device.type != "cuda":
+            raise N.NativeError("mixVAE_model.encoder needs GPU tensors: the model runs only on the HIP engine")
+        xt = x.reshape(-1, x.shape[-1]).contiguous().float()
+        n = xt.shape[0]
+        assert xt.shape[1] == self.input_dim
+        eng = self._arm_engine(n)
+        hyper = self._hyper(1.0, True)
+        noise = None
+        if self.training:
+            if self.x_dp.p > 0:
+                if isinstance(self._explicit_noise, list):
+                    if not self._explicit_noise:
+                        raise RuntimeError("explicit noise schedule exhausted")
+                    mask = self._explicit_noise.pop(0)["x_mask"][arm]
+                elif self._explicit_noise is not None:
+                    mask = self._explicit_noise["x_mask"][arm]
+                else:
+                    # the mask the A-arm forward would draw at this offset, written out; this arm's slice is explicit noise
+                    full = self._ensure(n)
+                    mask = full.dump_noise(self._hyper(1.0, False), self._next_noise())["x_mask"][arm]
+                self._noise_keep = mask = mask.contiguous()
+                noise = N.make_noise({"x_mask": mask})
+            else:
+                self._next_noise()
+                noise = N.make_noise({})
+        lay = self._layout
+        params = self._flat[arm * int(lay.per_arm):]
+        bn = self._bn_flat[arm * int(lay.bn_per_arm):]
+        nbt = self._nbt[arm * N.N_BN:] if self.training else None
+        out = {"x_low": torch.empty(1, n, self.lowD_dim, dtype=torch.float32, device=xt.device),
+               "c_prob": torch.empty(1, n, self.n_categories, dtype=torch.float32, device=xt.device)}
+        eng.encode(hyper, noise, params, bn, nbt, xt, 0, out)
+        self._ctx = None
+        return out["x_low"][0], out["c_prob"][0]
+
+    @torch.no_grad()
+    def intermed(self, y, arm):
+        """nn_model.py:271-275: ``(fc_mu(y), sigmoid(fc_sigma(y)))`` of arm ``arm`` for y [N, L + C] on the device; returns
+        the device tensors [N, S] each (the log with eps is ``forward``'s)."""
+        assert self.varitional, "Non-variational not implemented"
+        arm = int(arm)
+        if not (0 <= arm < self.n_arm):
+            raise IndexError(f"arm {arm} outside [0, {self.n_arm})")
+        if y.device.type != "cuda":
+            raise N.NativeError("mixVAE_model.intermed needs GPU tensors: the model runs only on the HIP engine")
+        K = self.lowD_dim + self.n_categories
+        yt = y.reshape(-1, y.shape[-1]).contiguous().float()
+        assert yt.shape[1] == K
+        if not self._is_packed():
+            self._pack()
+        n = yt.shape[0]
+        mu = torch.empty(n, self.state_dim, dtype=torch.float32, device=yt.device)
+        var = torch.empty_like(mu)
+        d = N.Dims(1, n, self.input_dim, self.fc_dim, self.lowD_dim, self.n_categories, self.state_dim)
+        with torch.cuda.device(yt.device):
+            N.intermed(d, self._hyper(1.0, True), self._flat[arm * int(self._layout.per_arm):], yt, 0, mu, var)
+        return mu, var
+
+    @torch.no_grad()
+    def encode(self, x, temp=1.0, mask=None, out=None, row0=0, counts=None):
+        """The latents of ``self(x, temp, eval=True, mask=mask)`` for every arm without the decoder, fc11 or x_rec
+        (mmvae_encode): a dict of device tensors ``x_low`` [A,N,L], ``c_prob``, ``c``, ``c_smp`` [A,N,C], ``s_mean``,
+        ``s_logvar`` [A,N,S] and ``labels`` int32 [A,N] (argmax of c) -- the forward's values bit for bit.  x: as
+        ``forward`` takes it ([A,N,D] or a list of A [N,D] tensors).  ``out``: such a dict of [A, rows, .] arrays to write
+        at rows ``row0 .. row0 + N`` instead (how ``cpl_mixVAE.encode_dataset`` fills a data set's arrays chunk by chunk);
+        ``counts``: int64 [pairs, C, C] that also receives this batch's between-arm confusion counts.  The module must be
+        in eval mode."""
+        if self.training:
+            raise RuntimeError("encode() needs model.eval(): the reference classifies in eval mode "
+                               "(cpl_mixvae.py:563)")
+        words = self._mask_words(mask)
+        xt, xs = self._prep_x(x)
+        if xt.device.type != "cuda":
+            raise N.NativeError("mixVAE_model.encode needs GPU tensors: the model runs only on the HIP engine")
+        A, n = self.n_arm, xt.shape[-2]
+        assert xt.shape[-1] == self.input_dim
+        eng = self._ensure(n)
+        hyper = self._hyper(temp, True)
+        if words is not None:
+            for i in range(4):
+                hyper.cat_mask[i] = words[i]
+        rows = n
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=xt.device)
+            L, Cc, S = self.lowD_dim, self.n_categories, self.state_dim
+            out = {"x_low": torch.empty(A, n, L, **f32), "c_prob": torch.empty(A, n, Cc, **f32),
+                   "c": torch.empty(A, n, Cc, **f32), "c_smp": torch.empty(A, n, Cc, **f32),
+                   "s_mean": torch.empty(A, n, S, **f32), "s_logvar": torch.empty(A, n, S, **f32),
+                   "labels": torch.empty(A, n, dtype=torch.int32, device=xt.device)}
+        else:
+            rows = next(t for t in out.values() if t is not None).shape[1]
+        args = dict(out)
+        if counts is not None:
+            args["counts"] = counts
+        eng.encode(hyper, None, self._flat, self._bn_flat, None, xt, xs, args, row0, rows)
+        self._ctx = None
+        return out
 
     # ------------------------------------------------------------------ decoding a chosen code, state traversal
     def _dec_engine(self, A: int, rows: int, n_samp=None) -> N.DecodeEngine:

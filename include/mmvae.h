@@ -17,6 +17,8 @@
  *   mmvae_augment      netA(x.expand(A,-1,-1), True, 0.1)  mmidas/cpl_mixvae.py:422-423, augmentation/udagan.py:281-329
  *   mmvae_decode       mixVAE_model.decoder(c, s, arm)     mmidas/nn_model.py:277-287
  *   mmvae_state_changes  mixVAE_model.state_changes(x, d_s, temp, n_samp)  mmidas/nn_model.py:370-411
+ *   mmvae_encode       mixVAE_model.encoder(x, arm) and the latent block of forward(eval=True)  mmidas/nn_model.py:263-269, :330-351
+ *   mmvae_intermed     mixVAE_model.intermed(y, arm)       mmidas/nn_model.py:271-275
  *
  * Conventions
  *   - plain pointers and sizes only; every buffer is caller-owned DEVICE memory (fp32 unless
@@ -415,6 +417,46 @@ int mmvae_state_changes(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_n
                         const float *bn_running, const float *x, int d_s, int n_samp, float *x_rec, void *ws, size_t ws_bytes,
                         mmvae_exec *ex, void *stream);
 
+/* ---- the encoder and the latent block alone: latents of a data set without the decoder -------------------------------
+ * mmvae_encode: what a forward pass computes up to the latent block -- fc1 .. fc5 with their BatchNorms, fcc and the first
+ *   softmax, and in eval mode the second softmax, the noise-free hard sample and the state head -- for d->B cells of every arm,
+ *   with the kernels of mmvae_forward (its outputs, bit for bit); no decoder chain, no fc11, no x_rec.  x, x_arm_stride, params,
+ *   bn_running, num_batches_tracked: as mmvae_forward takes them.  `out` names the arrays wanted; each pointer may be NULL, not
+ *   all of them.  Cell b of arm a is written to row a * out_rows + out_row0 + b of every array, so the chunks of a data set
+ *   land in [A, out_rows, .] arrays directly (out_rows >= out_row0 + B; rows outside [out_row0, out_row0 + B) are not touched).
+ *   Eval mode (h->training == 0, h->eval_flag == 1; nz may be NULL): running statistics, no dropout, any B >= 1 (no training
+ *   batch cap), num_batches_tracked may be NULL, nothing is written to bn_running.  With only x_low / c_prob asked for the
+ *   latent kernel returns behind the first softmax.
+ *   Training mode (h->training == 1): the encoder half of a training mmvae_forward -- dropout from nz (only x_mask is read),
+ *   batch statistics, the momentum update of bn_running and the increment of num_batches_tracked for BatchNorm 1 .. 5 -- and
+ *   x_low / c_prob only: any other output MMVAE_E_UNSUPPORTED (mmvae_forward is the call for those); 2 <= B <= the batch cap.
+ *   One arm of the model: A = 1 with params + a * per_arm, bn_running + a * bn_per_arm, num_batches_tracked + a * MMVAE_N_BN.
+ *   Workspace: mmvae_encode_workspace_bytes(d, ex) == mmvae_workspace_bytes(d, ex), 256-byte aligned; afterwards the regions of
+ *   mmvae_ws_offset hold the encoder's activations (MMVAE_WS_R1 .. R5, X_LOW) and, unless only x_low / c_prob were asked
+ *   for, the latent block's (C_PROB, C, C_SMP, S_MEAN, S_LOGVAR); with counts, MMVAE_WS_GZC holds the [A, B] labels.
+ * mmvae_intermed: mu = fc_mu(y), var = sigmoid(fc_sigma(y)) (the log with eps is forward's, nn_model.py:350) for N = d->B
+ *   rows per arm.  y: [A,N,L+C], arm a at y + a * y_arm_stride (floats), rows contiguous; mu, var: [A,N,S].  Any N >= 1; reads
+ *   no BatchNorm (training and eval compute the same), needs no workspace.  One arm: A = 1 and params + a * per_arm.
+ * Both check every argument before any device work: MMVAE_E_BADARG for null required pointers, every output NULL,
+ * out_row0 < 0 or out_rows < out_row0 + B, counts with A < 2, a gemm_bf16 outside {0, 1, 2}, a negative arm stride and dims
+ * mmvae_check_dims rejects as such; MMVAE_E_UNSUPPORTED for shapes outside its limits. */
+typedef struct mmvae_encode_out {
+    float *x_low;     /* [A,out_rows,L]  low-dimensional representation, BatchNorm5's output                       */
+    float *c_prob;    /* [A,out_rows,C]  softmax(fcc(x_low)): the second value of mixVAE_model.encoder             */
+    float *c;         /* [A,out_rows,C]  softmax(c_prob / tau) on the categories h->cat_mask keeps, 0 elsewhere    */
+    float *c_smp;     /* [A,out_rows,C]  eval: the noise-free hard sample                                          */
+    float *s_mean;    /* [A,out_rows,S]                                                                            */
+    float *s_logvar;  /* [A,out_rows,S]  log(sigmoid(fc_sigma(y)) + eps)                                           */
+    int32_t *labels;  /* [A,out_rows]    argmax of c (first maximum on ties)                                       */
+    int64_t *counts;  /* [A(A-1)/2,C,C]  += this call's between-arm confusion counts, as mmvae_eval_classify       */
+} mmvae_encode_out;
+size_t mmvae_encode_workspace_bytes(const mmvae_dims *d, const mmvae_exec *ex);
+int mmvae_encode(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noise *nz, const float *params, float *bn_running,
+                 int64_t *num_batches_tracked, const float *x, int64_t x_arm_stride, const mmvae_encode_out *out,
+                 int64_t out_row0, int64_t out_rows, void *ws, size_t ws_bytes, mmvae_exec *ex, void *stream);
+int mmvae_intermed(const mmvae_dims *d, const mmvae_hyper *h, const float *params, const float *y, int64_t y_arm_stride,
+                   float *mu, float *var, void *stream);
+
 /* Writes the noise the Philox mode (nz->mode == 1) would use, in explicit-buffer form, so a test
  * can replay a Philox step through mode 0.  Any output pointer may be NULL. */
 int mmvae_dump_noise(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noise *nz,
@@ -440,7 +482,9 @@ int mmvae_debug_stage(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noi
  * library's own planner on the dims, the hyper-parameters and a copy of `ex` (null: zeros; a non-null side_stream
  * counts as "has a side stream", its events are not looked at), for the tests that pin every switch point of it.
  *   call_kind      MMVAE_CALL_*: the entry point (STEP mmvae_train_step, STEP_ROWS mmvae_train_step_rows, ...).  DECODE,
- *                  TRAVERSE and CLASSIFY are planned in eval mode (h->training is ignored), as their entry points run.
+ *                  TRAVERSE and CLASSIFY are planned in eval mode (h->training is ignored), as their entry points run;
+ *                  ENCODE (mmvae_encode) in the mode h->training states: CLASSIFY's choices in eval mode, the forward half
+ *                  of FORWARD's in training mode.
  *   params_align   alignment in bytes of the flat parameter pointer: 16 or more means 16-byte aligned, 4 or 8 a pointer
  *                  that many bytes past a 16-byte boundary.
  *   x_align        the same for x (for DECODE: x_rec).
@@ -457,6 +501,7 @@ int mmvae_debug_stage(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noi
 #define MMVAE_CALL_REPLAY 6
 #define MMVAE_CALL_DECODE 7
 #define MMVAE_CALL_TRAVERSE 8
+#define MMVAE_CALL_ENCODE 10   /* (9 is not a call kind: mmvae_debug_plan refuses it as unknown, as it always has) */
 int mmvae_debug_plan(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_exec *ex, int call_kind,
                      int params_align, int x_align, int64_t x_arm_stride, int has_x16, int fc11_grad,
                      int32_t out[MMVAE_PLAN_FIELDS]);
