@@ -227,6 +227,8 @@ def lib():
     L.mmvae_encode.restype = C.c_int
     L.mmvae_intermed.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, i64, vp, vp, vp]
     L.mmvae_intermed.restype = C.c_int
+    L.mmvae_prune_apply.argtypes = [C.POINTER(Dims), C.POINTER(C.c_uint32 * 4), vp, vp, vp, vp, vp]
+    L.mmvae_prune_apply.restype = C.c_int
     for fn in ("mmvae_check_dims", "mmvae_param_layout", "mmvae_splits", "mmvae_forward", "mmvae_loss",
                "mmvae_backward", "mmvae_adam_step", "mmvae_train_step", "mmvae_dump_noise", "mmvae_debug_stage",
                "mmvae_eval_classify", "mmvae_classify", "mmvae_confmat_accumulate", "mmvae_consensus", "mmvae_aug_pack",
@@ -524,6 +526,25 @@ def intermed(dims: Dims, hyper: Hyper, params, y: torch.Tensor, y_arm_stride: in
     check(lib().mmvae_intermed(C.byref(dims), C.byref(hyper), _ptr(params), _ptr(y), int(y_arm_stride), _ptr(mu), _ptr(var),
                                _stream(y.device)), "mmvae_intermed")
     return mu, var
+
+
+def prune_apply(dims: Dims, mask_words, params=None, grads=None, exp_avg=None, exp_avg_sq=None, n: Optional[int] = None):
+    """mmvae_prune_apply: +0.0 at the positions of the categories ``mask_words`` (the four words of mmvae_hyper.cat_mask: bit k
+    set = category k kept) does not keep -- fcc.weight[k, :], fcc.bias[k], fc_mu.weight[:, L + k], fc_sigma.weight[:, L + k],
+    fc6.weight[:, k] of every arm -- in each given flat buffer of the parameter layout; one launch on torch's current stream of
+    the buffers' device.  ``n``: the floats every buffer must hold, A * per_arm (None: asked of mmvae_param_layout; a caller
+    on a per-step path passes the number it already has)."""
+    bufs = [t for t in (params, grads, exp_avg, exp_avg_sq) if t is not None]
+    if n is None:
+        n = dims.A * int(param_layout(dims).per_arm)
+    for t in bufs:
+        if t.device.type != "cuda":
+            raise NativeError("prune_apply needs CUDA tensors (no CPU fallback)")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n and t.device == bufs[0].device
+    words = (C.c_uint32 * 4)(*[int(w) & 0xFFFFFFFF for w in mask_words])
+    stream = _stream(bufs[0].device) if bufs else None
+    check(lib().mmvae_prune_apply(C.byref(dims), C.byref(words), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                  stream), "mmvae_prune_apply")
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, decoupled=False):

@@ -3,8 +3,9 @@
 Mirrors ``__init__`` (:153-186), ``init_model`` (:193-286), ``load_model`` (:317-321) and the
 training loop of ``train`` (:323-492: per-batch driver :415-478, epoch reductions :480-492,
 checkpoints :777-788) on top of the fused HIP train step.  Out of the hot path and therefore not
-here: pruning phase, wandb/matplotlib reporting.  The augmenter in front of the step
-(:182-186, :422-423) is ``distributed_vae_amd.augmentation``.
+here: wandb/matplotlib reporting.  The augmenter in front of the step
+(:182-186, :422-423) is ``distributed_vae_amd.augmentation``.  The pruning phase (:996-1444), which upstream
+switches off inside ``train``, is the opt-in ``cpl_mixVAE.prune``.
 """
 from __future__ import annotations
 
@@ -114,6 +115,27 @@ def get_device(device=None) -> torch.device:
     return torch.device(device)
 
 
+def prune_start(bias):
+    """cpl_mixvae.py:998-1000: ``(kept, pruned)`` index arrays from the ``fcc`` bias of arm 0 -- a category is pruned iff its
+    bias is exactly zero, so a checkpoint of an already pruned model resumes where it stopped."""
+    bias = np.asarray(bias)
+    return np.where(bias != 0.0)[0], np.where(bias == 0.0)[0]
+
+
+def prune_decision(c_agreement, kept, min_con, pr, max_prun_it):
+    """cpl_mixvae.py:1108-1132: the category to prune next, or None to stop.  ``c_agreement``: float64 [C]
+    (``cpl_mixVAE.category_agreement``); ``kept``: the indices still in use, ascending.  While ``pr < max_prun_it`` and the
+    smallest agreement among the kept categories is at most ``min_con``, that category goes (``np.argmin``: the first on
+    ties).  The last kept category is never pruned (the reference would go on to a forward over an empty mask, which fails)."""
+    kept = np.asarray(kept, dtype=np.int64)
+    if kept.size <= 1 or not pr < max_prun_it:
+        return None
+    agreement = np.asarray(c_agreement, dtype=np.float64)[kept]
+    if not np.min(agreement) <= min_con:
+        return None
+    return int(kept[np.argmin(agreement)])
+
+
 class cpl_mixVAE:
     def __init__(self, saving_folder="", aug_file="", device=None, eps=1e-8, save_flag=True, load_weights=True):
         self.eps = eps
@@ -129,6 +151,7 @@ class cpl_mixVAE:
         # from MMVAE_BF16_STORAGE, on), recorded per run in ``used_bf16_storage`` and in train()'s history.
         self.bf16_storage = os.environ.get("MMVAE_BF16_STORAGE", "1") != "0"
         self.used_bf16_storage = False
+        self._prune_mask = None          # the kept categories while ``prune`` retrains (``_step`` / ``_step_rows`` pass it on)
         if aug_file:                                            # cpl_mixvae.py:182-186
             from .augmentation import mk_augmenter
             self.aug_model, self.aug_param, netA = mk_augmenter(aug_file, load_weights)
@@ -194,11 +217,14 @@ class cpl_mixVAE:
         parameter's ``.grad`` and steps itself."""
         if D.is_dist():
             return D.dp_train_step(self.model, xs, self.temp, self.optimizer)
+        mask = self._prune_mask
         if isinstance(self.optimizer, FusedAdam) and self.optimizer.model is self.model:
-            return self.model.fused_train_step(xs, self.temp, self.optimizer, do_adam=True)
-        buf = self.model.fused_train_step(xs, self.temp, None, do_adam=False)
+            return self.model.fused_train_step(xs, self.temp, self.optimizer, do_adam=True, mask=mask)
+        buf = self.model.fused_train_step(xs, self.temp, None, do_adam=False, mask=mask)
         self.model.bind_grads()
         self.optimizer.step()
+        if mask is not None:
+            self.model.prune_apply(mask, grads=False)            # weight_orig * mask behind a stock optimizer's step
         return buf
 
     def _step_rows(self, data: torch.Tensor, rows: torch.Tensor, data16=None):
@@ -206,11 +232,15 @@ class cpl_mixVAE:
         matrix's bf16 copy for the bf16 configuration (bf16 storage)."""
         if D.is_dist():
             return D.dp_train_step(self.model, None, self.temp, self.optimizer, rows=(data, rows, data16))
+        mask = self._prune_mask
         if isinstance(self.optimizer, FusedAdam) and self.optimizer.model is self.model:
-            return self.model.fused_train_step_rows(data, rows, self.temp, self.optimizer, do_adam=True, data16=data16)
-        buf = self.model.fused_train_step_rows(data, rows, self.temp, None, do_adam=False, data16=data16)
+            return self.model.fused_train_step_rows(data, rows, self.temp, self.optimizer, do_adam=True, data16=data16,
+                                                    mask=mask)
+        buf = self.model.fused_train_step_rows(data, rows, self.temp, None, do_adam=False, data16=data16, mask=mask)
         self.model.bind_grads()
         self.optimizer.step()
+        if mask is not None:
+            self.model.prune_apply(mask, grads=False)
         return buf
 
     def train_step(self, x: torch.Tensor):
@@ -451,8 +481,102 @@ class cpl_mixVAE:
         hist["bf16_storage"] = bool(self.used_bf16_storage)    # (not in the reference: which copy of x the run's losses were taken against)
         return hist
 
+    def prune(self, train_loader, test_loader, n_epoch_p, min_con=0.5, max_prun_it=0, c_p=0, c_onehot=0, rank=None,
+              run=None):
+        """The pruning phase of cpl_mixvae.py:996-1444 with its loop live (upstream forces ``stop_prune`` at :1007 and :1135,
+        which is why ``train(n_epoch_p > 0)`` does nothing; this method is the opt-in).  Repeats: assess the agreement of
+        the arms per category on the training set under the mask of the kept categories (``category_agreement``), prune the
+        kept category with the smallest agreement while that is at most ``min_con`` and fewer than ``max_prun_it`` rounds
+        have run (``prune_decision``; rounds count from ``self.n_pr``), retrain ``n_epoch_p`` epochs with that category
+        switched off (``epoch_steps`` under ``mask=``: the fused step with ``mmvae_hyper.cat_mask`` and ``prune_apply`` behind
+        it), write ``model/cpl_mixVAE_model_after_pruning_{round}_{time}.pth`` when ``self.folder`` is set.  Starts from
+        the categories whose ``fcc`` bias is non-zero, so a checkpoint of a pruned model resumes.
+
+        Effective weights are torch's ``weight_orig * mask`` after every step.  Deviation: with ``FusedAdam`` the Adam moments
+        of pruned entries are held at 0 where ``torch.nn.utils.prune`` leaves decaying remnants in the optimizer state;
+        they never reach an effective weight.  No plots.  Returns the history: ``pruned`` (every pruned category in the
+        order of the reference's ``ind``: those of the starting model first), ``kept``, ``agreement`` (one float64 [C] array
+        per assessment), ``rounds`` and the per-epoch lists of ``train`` (all retraining epochs in sequence)."""
+        if D.is_dist():
+            raise NotImplementedError("cpl_mixVAE.prune under data parallelism: the category mask is not plumbed through "
+                                      "dist.dp_train_step yet (issue 'Add the pruning phase: cpl_mixVAE.prune on a masked "
+                                      "fused train step', out of scope there)")
+        A, Dm, dev = self.n_arm, self.input_dim, self.device
+        hist = {"pruned": [], "kept": [], "agreement": [], "rounds": 0, "losses": [], "loss_joints": [],
+                "loss_recs": [[] for _ in range(A)], "c_ents": [], "c_l2_dists": [], "c_dists": [], "validation_loss": [],
+                "validation_rec_loss": [], "consensus_val": [], "epoch_times": []}
+        if n_epoch_p <= 0:
+            return hist
+        if A == 1:
+            raise ZeroDivisionError("division by zero")   # nn_model.py:592-594
+        kept, pruned = prune_start(self.model.fcc[0].bias.detach().cpu().numpy())       # :998-1000
+        hist["pruned"], hist["kept"] = [int(k) for k in pruned], [int(k) for k in kept]
+        pr = int(getattr(self, "n_pr", 0) or 0)                                          # :1005
+        if not getattr(self, "current_time", None):
+            self.current_time = time.strftime("%Y-%m-%d-%H-%M-%S")
+        fused = isinstance(self.optimizer, FusedAdam) and self.optimizer.model is self.model
+        # the row convention of train()'s consensus: the whole set in its base order unless the test loader has batches
+        whole_train = test_loader is not None and not ((getattr(test_loader, "batch_size", None) or 0) > 1)
+        while True:
+            agreement = self.category_agreement(train_loader, mask=kept, whole_set=whole_train)    # :1010-1107
+            hist["agreement"].append(agreement)
+            k = prune_decision(agreement, kept, min_con, pr, max_prun_it)                           # :1108-1132
+            if k is None:
+                print("No more pruning!")
+                break
+            kept = kept[kept != k]
+            hist["pruned"].append(k)
+            hist["kept"] = [int(i) for i in kept]
+            print("Continue training with pruning ...")
+            print(f"Pruned categories: {np.asarray(hist['pruned'])}")
+            # prune.custom_from_mask (:1153-1161): the effective weights are masked from here on
+            self.model.prune_apply(kept, self.optimizer if fused else None)
+            self._prune_mask = kept
+            try:
+                for _ in range(n_epoch_p):                                                          # :1163-1394
+                    t0 = time.time()
+                    self.model.train()
+                    acc = torch.zeros(5 + 3 * A, dtype=torch.float32, device=dev)
+                    nb = 0
+                    for buf in self.epoch_steps(train_loader):
+                        acc += buf
+                        nb += 1
+                    s = acc.cpu().numpy()                                     # the per-epoch means of train()
+                    n = np.float32(max(nb, 1))
+                    hist["losses"].append(s[N.LOSS_TOTAL] / n)
+                    hist["loss_joints"].append(s[N.LOSS_JOINT] / n)
+                    hist["c_ents"].append(s[N.LOSS_CENT] / n)
+                    hist["c_l2_dists"].append(s[N.LOSS_CL2] / n)
+                    hist["c_dists"].append(s[N.LOSS_CDIST] / n)
+                    for a in range(A):
+                        hist["loss_recs"][a].append(s[N.LOSS_REC0 + a] / Dm / n)
+                    if test_loader is not None:
+                        val_tot, val, val_cons = self.validate(test_loader, full=True, mask=kept)
+                    else:
+                        val_tot = val = val_cons = float("nan")
+                    hist["validation_loss"].append(val_tot)
+                    hist["validation_rec_loss"].append(val)
+                    hist["consensus_val"].append(val_cons)
+                    hist["epoch_times"].append(time.time() - t0)
+                    print(f"====> Pruning round {pr + 1} | loss: {hist['losses'][-1]:.2f} | rec: "
+                          f"{hist['loss_recs'][0][-1]:.2f} | val: {val:.2f}", flush=True)
+                    if run:
+                        run.log({"prune/total-loss": hist["losses"][-1], "prune/val-rec-loss": val, "prune/round": pr + 1})
+            finally:
+                self._prune_mask = None
+            # prune.remove (:1396-1401): the masked values become the parameters themselves
+            self.model.prune_apply(kept, self.optimizer if fused else None)
+            if self.folder:                                                                         # :1403-1417
+                os.makedirs(os.path.join(self.folder, "model"), exist_ok=True)
+                self.save_checkpoint(os.path.join(
+                    self.folder, "model", f"cpl_mixVAE_model_after_pruning_{pr + 1}_{self.current_time}.pth"))
+            pr += 1
+            hist["rounds"] += 1
+        self.n_pr = pr
+        return hist
+
     @torch.no_grad()
-    def consensus(self, loader, whole_set: Optional[bool] = None, chunk: Optional[int] = None) -> float:
+    def consensus(self, loader, whole_set: Optional[bool] = None, chunk: Optional[int] = None, mask=None) -> float:
         """Mean over arm pairs of ``confmat_mean(confmat_normalize(compute_confmat(labels_a, labels_b, C)))`` with
         ``labels = classify(c)`` of the eval-mode forward (cpl_mixvae.py:563-657).  ``whole_set``: classify every row
         of ``loader.dataset.tensors`` in its base order (what the reference does when the test loader's batch size is
@@ -461,8 +585,19 @@ class cpl_mixVAE:
         running statistics, so cells are independent and the whole set is processed in chunks of ``chunk`` rows
         (default: the loader's batch size) with identical labels.  Labels, counts and the normalisation stay on the
         device: one host read of A(A-1)/2 doubles per epoch.  Under data parallelism every rank counts its own shard and
-        the integer counts are summed (the reference, never run distributed, would report rank-local values)."""
-        from ._utils import confmat_counts, consensus_from_counts
+        the integer counts are summed (the reference, never run distributed, would report rank-local values).
+        ``mask``: the kept categories of a pruned model, as ``forward(mask=)`` takes them."""
+        from ._utils import consensus_from_counts
+        counts, seen = self._label_counts(loader, whole_set, chunk, mask)
+        if seen == 0:
+            return float("nan")
+        return float(np.mean(consensus_from_counts(counts).cpu().numpy()))   # np.mean(np.array(consensus)), :654
+
+    @torch.no_grad()
+    def _label_counts(self, loader, whole_set=None, chunk=None, mask=None):
+        """Between-arm confusion counts (int64 [pairs, C, C], on the device) of the eval-mode labels over ``loader``, and the
+        number of cells seen: the counting half of ``consensus`` and ``category_agreement``."""
+        from ._utils import confmat_counts
         was_training = self.model.training
         self.model.eval()
         counts = confmat_counts(self.n_arm, self.n_categories, self.device)
@@ -471,14 +606,24 @@ class cpl_mixVAE:
             x = x.to(self.device)
             if x.shape[0] < 1:
                 continue
-            self.model.eval_labels(x.expand(self.n_arm, -1, -1), self.temp, counts)
+            self.model.eval_labels(x.expand(self.n_arm, -1, -1), self.temp, counts, mask=mask)
             seen += x.shape[0]
         if D.is_dist():
             D.allreduce_sum_(counts)
         self.model.train(was_training)
-        if seen == 0:
-            return float("nan")
-        return float(np.mean(consensus_from_counts(counts).cpu().numpy()))   # np.mean(np.array(consensus)), :654
+        return counts, seen
+
+    @torch.no_grad()
+    def category_agreement(self, loader, mask=None, whole_set: Optional[bool] = None, chunk: Optional[int] = None) -> np.ndarray:
+        """The pruning phase's assessment (cpl_mixvae.py:1010-1107): per category, the mean over arm pairs of the diagonal of
+        the pair's confusion matrix of eval-mode labels under ``mask``, each column divided by max(its row sum, its column
+        sum) and 0 where that is 0 -- ``confmat_normalize``'s arithmetic, so the counts and the normalisation are
+        ``consensus``'s (on the device, ``_native.consensus(counts, want_norm=True)``); float64 [C], the mean over pairs
+        taken by numpy on the host.  A category no arm predicts has agreement 0."""
+        counts, _ = self._label_counts(loader, whole_set, chunk, mask)
+        _, norm = N.consensus(counts, want_norm=True)
+        diag = torch.diagonal(norm, dim1=1, dim2=2).contiguous().cpu().numpy()    # [pairs, C]: np.diag of every pair, :1080
+        return np.mean(diag, axis=0)                                                # :1107
 
     @staticmethod
     def _eval_batches(loader, whole_set: Optional[bool] = None, chunk: Optional[int] = None):
@@ -505,13 +650,14 @@ class cpl_mixVAE:
             yield batch[0] if isinstance(batch, (tuple, list)) else batch
 
     @torch.no_grad()
-    def validate(self, loader, full: bool = False):
+    def validate(self, loader, full: bool = False, mask=None):
         """The validation block of cpl_mixvae.py:665-775 in eval mode: ``validation_rec_loss = sum over batches and arms
         of loss_rec[a] / D, divided by len(loader) and n_arm`` (:742-763), ``validation_loss = sum of the total loss /
         len(loader)`` (:741, :764) and the between-arm consensus of the labels (:752-762, on the device).  Returns the
         rec loss, or the triple ``(validation_loss, validation_rec_loss, consensus_val)`` with ``full=True``.  With
         the reference's default test loader (batch_size 1) the whole set is one batch and ``len(loader)`` its row
-        count, as in the reference."""
+        count, as in the reference.  ``mask``: the kept categories of a pruned model, as ``forward(mask=)`` takes them (the
+        pruning phase validates under its mask, :1317-1323, :1362-1369)."""
         from ._utils import confmat_counts, consensus_from_counts
         was_training = self.model.training
         self.model.eval()
@@ -525,7 +671,7 @@ class cpl_mixVAE:
             if x.shape[0] < 2:     # a one-cell batch has no batch variance: the reference's loss is NaN there (nn_model.py:75)
                 continue
             xs = x.expand(A, -1, -1)
-            out = self.model(xs, self.temp, 0.0, eval=True)
+            out = self.model(xs, self.temp, 0.0, eval=True, mask=mask)
             lt = self.model.loss(out[0], [], [], xs, out[7], out[8], out[4], out[6], 0.0)
             tot += lt[0].double()                                             # :741 val_loss += loss.data.item()
             rec += lt[1].double().sum() / self.input_dim                      # :742-743 sum_a loss_rec[a] / D

@@ -874,6 +874,20 @@ int mmvae_intermed(const mmvae_dims* d, const mmvae_hyper* h, const float* param
     return launch_intermed(*d, make_poff(*d), params, y, y_arm_stride, mu, var, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- pruning: every argument is checked before the launch
+int mmvae_prune_apply(const mmvae_dims* d, const uint32_t cat_mask[4], float* params, float* grads, float* exp_avg,
+                      float* exp_avg_sq, void* stream) {
+    if (int rc = check_dims(d)) return rc;
+    if (!cat_mask) { set_error("prune_apply: cat_mask is null"); return MMVAE_E_BADARG; }
+    if (!params && !grads && !exp_avg && !exp_avg_sq) { set_error("prune_apply: every buffer is null"); return MMVAE_E_BADARG; }
+    if (!(cat_mask[0] | cat_mask[1] | cat_mask[2] | cat_mask[3])) return 0;   // no mask: every category kept (mmvae_hyper.cat_mask)
+    // bits beyond n_categories are ignored; at least one category must be kept (as make_ctx)
+    uint32_t any = 0;
+    for (int k = 0; k < d->C; ++k) any |= (cat_mask[k >> 5] >> (k & 31)) & 1u;
+    if (!any) { set_error("cat_mask keeps none of the %d categories", d->C); return MMVAE_E_BADARG; }
+    return launch_prune_apply(*d, make_poff(*d), cat_mask, params, grads, exp_avg, exp_avg_sq, reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_classify(const float* c_probs, int64_t n_cells, int C, int32_t* labels, void* stream) {
     if (!c_probs || !labels || n_cells <= 0 || C <= 0) { set_error("classify: bad argument"); return MMVAE_E_BADARG; }
     return launch_classify(c_probs, n_cells, C, labels, reinterpret_cast<hipStream_t>(stream));

@@ -865,6 +865,9 @@ int launch_lat_enc(const Ctx& c, const mmvae_noise* nz, const float* params, flo
 // mmvae_intermed: mu = fc_mu(y), var = sigmoid(fc_sigma(y)) for N rows of every arm (k_intermed)
 int launch_intermed(const mmvae_dims& d, const POff& po, const float* params, const float* y, int64_t y_arm_stride, float* mu,
                     float* var, hipStream_t s);
+// mmvae_prune_apply: +0.0f at the positions of the categories cat_mask does not keep, in each non-null buffer (k_prune_apply, prune.hip)
+int launch_prune_apply(const mmvae_dims& d, const POff& po, const uint32_t cat_mask[4], float* params, float* grads,
+                       float* exp_avg, float* exp_avg_sq, hipStream_t s);
 int launch_chain_fwd_dec(const Ctx& c, const float* params);   // (with the coupling terms as a role: Plan::couple)
 int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
 int launch_couple(const Ctx& c);

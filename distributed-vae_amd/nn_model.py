@@ -129,6 +129,7 @@ class mixVAE_model(nn.Module):
         self._explicit_state_noise = None
         self._dec_engines = {}
         self._arm_engines = {}
+        self._prune_dims = None
         self._exec: Optional[N.Exec] = None   # None: split factors / experiment switches from the environment
         # operand type of the five D x H GEMMs: "fp32" (the parity configuration) or "bf16" (BASELINE.json's bf16
         # configuration: operands rounded to bf16, fp32 accumulation; everything else and all parameters stay fp32)
@@ -384,11 +385,13 @@ class mixVAE_model(nn.Module):
 
     # ------------------------------------------------------------------ evaluation labels (consensus path)
     @torch.no_grad()
-    def eval_labels(self, x, temp=1.0, counts=None) -> torch.Tensor:
+    def eval_labels(self, x, temp=1.0, counts=None, mask=None) -> torch.Tensor:
         """``classify(cs[a])`` of ``self(x, temp, eval=True)`` for every arm without leaving the device
         (cpl_mixvae.py:596-611): int32 [n_arm, batch].  Runs the encoder and the latent block only (BatchNorm running
         statistics, no Gumbel noise); ``counts`` (int64 [pairs, C, C], see ``_utils.confmat_counts``) also receives
-        this batch's between-arm confusion counts.  The module must be in eval mode, as in the reference's loop."""
+        this batch's between-arm confusion counts.  ``mask``: the kept categories, as ``forward(mask=)`` takes them (the
+        pruning phase's assessment, cpl_mixvae.py:1040-1042).  The module must be in eval mode, as in the reference's loop."""
+        words = self._mask_words(mask)
         if self.training:
             raise RuntimeError("eval_labels() needs model.eval(): the reference classifies in eval mode "
                                "(cpl_mixvae.py:563)")
@@ -397,7 +400,11 @@ class mixVAE_model(nn.Module):
             raise N.NativeError("mixVAE_model.eval_labels needs GPU tensors: the model runs only on the HIP engine")
         eng = self._ensure(xt.shape[-2])
         labels = torch.empty(self.n_arm, xt.shape[-2], dtype=torch.int32, device=xt.device)
-        eng.eval_classify(self._hyper(temp, True), self._flat, self._bn_flat, xt, xs, labels, counts)
+        hyper = self._hyper(temp, True)
+        if words is not None:
+            for i in range(4):
+                hyper.cat_mask[i] = words[i]
+        eng.eval_classify(hyper, self._flat, self._bn_flat, xt, xs, labels, counts)
         self._ctx = None
         return labels
 
@@ -631,12 +638,47 @@ class mixVAE_model(nn.Module):
         return (recon[:, :, 0, :].contiguous() if B == 1 else recon), state_smp_sorted
 
     # ------------------------------------------------------------------ fused step (trainer path)
-    def fused_train_step(self, x, temp, opt=None, do_adam=True):
+    def prune_apply(self, mask, opt=None, params=True, grads=True):
+        """Exact zeros at the parameter positions of the categories ``mask`` (as ``forward(mask=)`` takes it: the KEPT
+        categories) does not keep, in every arm: ``fcc.weight[k, :]``, ``fcc.bias[k]``, ``fc_mu.weight[:, L + k]``,
+        ``fc_sigma.weight[:, L + k]``, ``fc6.weight[:, k]`` -- the five masks of the reference's pruning phase
+        (cpl_mixvae.py:1124-1128, applied by ``prune.custom_from_mask``, :1153-1161).  ``params`` / ``grads``: the flat
+        parameter / gradient buffer; ``opt`` (a ``FusedAdam`` of this model): its two moment buffers too.  One launch
+        (mmvae_prune_apply) on the current stream; a mask that keeps every category does nothing."""
+        self._prune_words(self._mask_words(mask), opt, params, grads)
+
+    def _prune_words(self, words, opt, params, grads):
+        if words is None:
+            return
+        if not self._is_packed():
+            self._pack()
+        m = v = None
+        if opt is not None:
+            opt._bind(self)
+            m, v = opt.exp_avg, opt.exp_avg_sq
+        if self._prune_dims is None:
+            self._prune_dims = self._dims(2)                  # (the call reads A, L, C, S; kept: this is on the per-step path)
+        with torch.cuda.device(self._flat.device):
+            N.prune_apply(self._prune_dims, words, self._flat if params else None, self._flat_grad if grads else None, m, v,
+                          n=self._flat.numel())
+
+    def fused_train_step(self, x, temp, opt=None, do_adam=True, mask=None):
         """forward + loss + backward (+ Adam) in one C-ABI call: cpl_mixvae.py:434-463.
-        Returns the device loss vector (see include/mmvae.h MMVAE_LOSS_*); no host sync."""
+        Returns the device loss vector (see include/mmvae.h MMVAE_LOSS_*); no host sync.
+
+        ``mask`` (the pruning phase, cpl_mixvae.py:1163-1394): the kept categories, as ``forward(mask=)`` takes them; the
+        step runs under ``mmvae_hyper.cat_mask`` and the parameters of the other categories are held at zero
+        (``prune_apply``).  With ``do_adam`` the parameters, gradients and both Adam moments are zeroed there behind the
+        step, so the effective weights are torch's ``weight_orig * mask`` after every step; the moments of pruned entries
+        are held at 0, where torch keeps decaying remnants that never reach an effective weight.  Without ``do_adam`` the
+        gradients are zeroed there; the caller steps its optimizer and then calls ``prune_apply(mask, grads=False)``."""
+        words = self._mask_words(mask)
         xt, xs = self._prep_x(x)
         eng = self._ensure(xt.shape[-2])
         hyper = self._hyper(temp, False)
+        if words is not None:
+            for i in range(4):
+                hyper.cat_mask[i] = words[i]
         noise = self._next_noise()
         self._step_id += 1
         self._ctx = None
@@ -644,24 +686,34 @@ class mixVAE_model(nn.Module):
             opt._bind(self)
             opt.step_count += 1
             g = opt.param_groups[0]
-            return eng.train_step(hyper, noise, self._flat, self._bn_flat, self._nbt, xt, xs, self._flat_grad, True,
-                                  opt.exp_avg, opt.exp_avg_sq, opt.step_count, g["lr"], g["betas"][0], g["betas"][1],
-                                  g["eps"], g["weight_decay"], opt.decoupled)
-        return eng.train_step(hyper, noise, self._flat, self._bn_flat, self._nbt, xt, xs, self._flat_grad, False,
-                              None, None, 1, 0.0)
+            buf = eng.train_step(hyper, noise, self._flat, self._bn_flat, self._nbt, xt, xs, self._flat_grad, True,
+                                 opt.exp_avg, opt.exp_avg_sq, opt.step_count, g["lr"], g["betas"][0], g["betas"][1],
+                                 g["eps"], g["weight_decay"], opt.decoupled)
+        else:
+            buf = eng.train_step(hyper, noise, self._flat, self._bn_flat, self._nbt, xt, xs, self._flat_grad, False,
+                                 None, None, 1, 0.0)
+        if words is not None:
+            # the step has joined its side stream (the fc11 reduction and update) before it returned: stream order suffices
+            self._prune_words(words, opt if do_adam else None, bool(do_adam), True)
+        return buf
 
 
-    def fused_train_step_rows(self, data, rows, temp, opt=None, do_adam=True, data16=None):
+    def fused_train_step_rows(self, data, rows, temp, opt=None, do_adam=True, data16=None, mask=None):
         """``fused_train_step`` on the batch ``data[rows]`` without materialising it (``x.expand`` over the arms): the step
         reads the cells x genes matrix through a row map (mmvae_train_step_rows; bit-identical to gather + step).  Raises
         ``NotImplementedError`` where the library does not offer it -- engines other than fp32x3, no input dropout, a
         matrix beyond 4 GB --: gather the batch and call ``fused_train_step`` then.  ``data16`` (``gemm_dtype == "bf16"``
-        only): the matrix's bf16 copy (``_native.to_bf16``, ``DeviceLoader.data_bf16()``): bf16 storage, see DESIGN.md section 13."""
+        only): the matrix's bf16 copy (``_native.to_bf16``, ``DeviceLoader.data_bf16()``): bf16 storage, see DESIGN.md section 13.
+        ``mask``: as ``fused_train_step`` takes it (the pruning phase), with the same zeroing behind the step."""
+        words = self._mask_words(mask)
         if data.device.type != "cuda" or data.dtype != torch.float32 or data.shape[1] != self.input_dim:
             raise N.NativeError("fused_train_step_rows needs the float32 cells x genes matrix on the GPU")
         rows = rows.to(device=data.device, dtype=torch.int64).contiguous()
         eng = self._ensure(int(rows.numel()))
         hyper = self._hyper(temp, False)
+        if words is not None:
+            for i in range(4):
+                hyper.cat_mask[i] = words[i]
         noise = self._next_noise()
         try:
             if do_adam:
@@ -682,6 +734,8 @@ class mixVAE_model(nn.Module):
             raise
         self._step_id += 1
         self._ctx = None
+        if words is not None:
+            self._prune_words(words, opt if do_adam else None, bool(do_adam), True)
         return buf
 
 

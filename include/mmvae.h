@@ -19,6 +19,7 @@
  *   mmvae_state_changes  mixVAE_model.state_changes(x, d_s, temp, n_samp)  mmidas/nn_model.py:370-411
  *   mmvae_encode       mixVAE_model.encoder(x, arm) and the latent block of forward(eval=True)  mmidas/nn_model.py:263-269, :330-351
  *   mmvae_intermed     mixVAE_model.intermed(y, arm)       mmidas/nn_model.py:271-275
+ *   mmvae_prune_apply  prune.custom_from_mask / prune.remove on fcc, fc_mu, fc_sigma, fc6  mmidas/cpl_mixvae.py:1124-1128, :1153-1161, :1396-1401
  *
  * Conventions
  *   - plain pointers and sizes only; every buffer is caller-owned DEVICE memory (fp32 unless
@@ -456,6 +457,22 @@ int mmvae_encode(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noise *n
                  int64_t out_row0, int64_t out_rows, void *ws, size_t ws_bytes, mmvae_exec *ex, void *stream);
 int mmvae_intermed(const mmvae_dims *d, const mmvae_hyper *h, const float *params, const float *y, int64_t y_arm_stride,
                    float *mu, float *var, void *stream);
+
+/* ---- the pruning phase: parameters of switched-off categories held at zero ------------------------------------------
+ * mmvae_prune_apply: for every arm and every category k < d->C whose bit of cat_mask is clear (bit k set = kept, as
+ *   mmvae_hyper.cat_mask; bits at or above C are ignored), writes +0.0f to fcc.weight[k, :], fcc.bias[k],
+ *   fc_mu.weight[:, L + k], fc_sigma.weight[:, L + k] and fc6.weight[:, k] of each given flat buffer of the parameter layout
+ *   (params, grads, exp_avg, exp_avg_sq: [A * per_arm] floats; any may be NULL and is skipped) -- the five masks of the
+ *   reference's pruning loop (mmidas/cpl_mixvae.py:1124-1128), which it applies through torch.nn.utils.prune.custom_from_mask
+ *   (:1153-1161).  No other element is written, alignment gaps included.  One launch for all arms and buffers, asynchronous
+ *   on `stream`.  Behind mmvae_train_step(do_adam = 1, the same cat_mask in the hyper-parameters) on the step's stream, with
+ *   all four buffers, the effective weights are torch's weight_orig * mask after every step; the Adam moments of pruned
+ *   entries are held at 0 (torch keeps decaying remnants there, which never reach an effective weight).  The step has joined
+ *   its side stream by the time it returns, so stream order is enough.
+ * All four words zero = nothing is pruned: returns 0 without a launch.  MMVAE_E_BADARG before any launch: null dims or
+ * cat_mask, all four buffers NULL, a mask that keeps none of the C categories. */
+int mmvae_prune_apply(const mmvae_dims *d, const uint32_t cat_mask[4], float *params, float *grads, float *exp_avg,
+                      float *exp_avg_sq, void *stream);
 
 /* Writes the noise the Philox mode (nz->mode == 1) would use, in explicit-buffer form, so a test
  * can replay a Philox step through mode 0.  Any output pointer may be NULL. */
