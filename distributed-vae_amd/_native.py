@@ -200,6 +200,11 @@ def lib():
     L.mmvae_classify.argtypes = [vp, i64, i32, vp, vp]
     L.mmvae_confmat_accumulate.argtypes = [vp, i32, i64, i32, vp, vp]
     L.mmvae_consensus.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.mmvae_pair_stats.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, vp, vp]
+    L.mmvae_debug_pair_stats.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]
+    L.mmvae_pair_stats_finish.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    for fn in ("mmvae_pair_stats", "mmvae_debug_pair_stats", "mmvae_pair_stats_finish"):
+        getattr(L, fn).restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -586,6 +591,67 @@ def consensus(counts: torch.Tensor, want_norm: bool = False):
     norm = torch.empty(P, Cc, Cc, dtype=torch.float64, device=cnt.device) if want_norm else None
     check(lib().mmvae_consensus(_ptr(cnt), P, Cc, _ptr(norm), _ptr(out), _stream(cnt.device)), "mmvae_consensus")
     return (out, norm) if want_norm else out
+
+
+PAIR_STATS_LDS_MAX_C = 116      # PS_LDS_MAX_C of csrc/common.hpp: the largest C whose histogram fits a workgroup's LDS
+PAIR_STATS_PATHS = {"auto": -1, "lds": 0, "wave": 1}
+
+
+def pair_stats(labels: torch.Tensor, probs: torch.Tensor, pairs, Cc: int, counts: Optional[torch.Tensor] = None,
+               dist_acc: Optional[torch.Tensor] = None, path: str = "auto"):
+    """mmvae_pair_stats: labels int32 [T, n], probs float32 [T, n, C] on the GPU, ``pairs`` a host table [n_pairs][4] of arm
+    indices (lab1, prob1, lab2, prob2) -> (counts int64 [n_pairs, C, C], dist_acc int64 [n_pairs, C, C, 2]), both ``+=`` when
+    given.  ``path``: "auto" (the launcher's rule), "lds" or "wave" (mmvae_debug_pair_stats: the same sums on a named path)."""
+    if labels.device.type != "cuda" or probs.device.type != "cuda":
+        raise NativeError("pair_stats needs CUDA tensors (no CPU fallback)")
+    import numpy as np
+    tab = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 4))
+    lab, pr = labels.contiguous(), probs.contiguous()
+    if lab.dtype != torch.int32 or pr.dtype != torch.float32:
+        raise TypeError("pair_stats: labels must be int32 and probs float32")
+    T, n = lab.shape
+    if tuple(pr.shape) != (T, n, Cc):
+        raise ValueError(f"pair_stats: probs {tuple(pr.shape)} is not [T, n, C] = {(T, n, Cc)}")
+    P = tab.shape[0]
+    if counts is None:
+        counts = torch.zeros(P, Cc, Cc, dtype=torch.int64, device=lab.device)
+    if dist_acc is None:
+        dist_acc = torch.zeros(P, Cc, Cc, 2, dtype=torch.int64, device=lab.device)
+    for t, shape in ((counts, (P, Cc, Cc)), (dist_acc, (P, Cc, Cc, 2))):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != lab.device:
+            raise ValueError(f"pair_stats: accumulator must be a contiguous int64 {shape} tensor on {lab.device}")
+    if n == 0 or P == 0:
+        return counts, dist_acc
+    tp = tab.ctypes.data_as(C.c_void_p)
+    if path == "auto":
+        rc = lib().mmvae_pair_stats(_ptr(lab), _ptr(pr), T, n, Cc, tp, P, _ptr(counts), _ptr(dist_acc), _stream(lab.device))
+    else:
+        rc = lib().mmvae_debug_pair_stats(_ptr(lab), _ptr(pr), T, n, Cc, tp, P, _ptr(counts), _ptr(dist_acc),
+                                          PAIR_STATS_PATHS[path], _stream(lab.device))
+    check(rc, "mmvae_pair_stats")
+    return counts, dist_acc
+
+
+def pair_stats_finish(counts: torch.Tensor, dist_acc: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """mmvae_pair_stats_finish on the accumulators of ``pair_stats``: float64 device tensors ``cm_norm``, ``emp``,
+    ``dist_norm`` [n_pairs, C, C], ``diag_mean``, ``diag_min`` [n_pairs].  They are views of one buffer, ``packed`` (in this
+    order), so that a caller can bring everything to the host with a single copy."""
+    if counts.device.type != "cuda" or dist_acc.device.type != "cuda":
+        raise NativeError("pair_stats_finish needs CUDA tensors (no CPU fallback)")
+    cnt, acc = counts.contiguous(), dist_acc.contiguous()
+    P, Cc, _ = cnt.shape
+    if cnt.dtype != torch.int64 or acc.dtype != torch.int64 or tuple(acc.shape) != (P, Cc, Cc, 2):
+        raise ValueError("pair_stats_finish: counts int64 [P, C, C] and dist_acc int64 [P, C, C, 2] expected")
+    m = P * Cc * Cc
+    packed = torch.empty(3 * m + 2 * P, dtype=torch.float64, device=cnt.device)
+    out = {"cm_norm": packed[0:m].view(P, Cc, Cc), "emp": packed[m:2 * m].view(P, Cc, Cc),
+           "dist_norm": packed[2 * m:3 * m].view(P, Cc, Cc), "diag_mean": packed[3 * m:3 * m + P],
+           "diag_min": packed[3 * m + P:], "packed": packed}
+    if P:
+        check(lib().mmvae_pair_stats_finish(_ptr(cnt), _ptr(acc), P, Cc, _ptr(out["cm_norm"]), _ptr(out["emp"]),
+                                            _ptr(out["dist_norm"]), _ptr(out["diag_mean"]), _ptr(out["diag_min"]),
+                                            _stream(cnt.device)), "mmvae_pair_stats_finish")
+    return out
 
 
 def to_bf16(data: torch.Tensor) -> torch.Tensor:

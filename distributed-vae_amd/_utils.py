@@ -1,11 +1,14 @@
-"""Consensus utilities of mmidas/_utils.py:79-129 on the device.
+"""Consensus utilities of mmidas/_utils.py:68-129 on the device.
 
 Same names and meaning as the reference; inputs and outputs are CUDA tensors instead of numpy arrays, the arithmetic
 runs in the HIP library (csrc/consensus.hip) and the values are bit-identical to the reference's numpy code
 (integer counts; fp64 division and numpy's summation order for the mean).  No CPU fallback.
+
+``reassign`` and ``mk_masks`` (_utils.py:68-75) are host functions on small numpy arrays, as in the reference.
 """
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -72,3 +75,78 @@ def _np_pairwise_sum(v: torch.Tensor) -> torch.Tensor:
 def consensus_from_counts(counts: torch.Tensor) -> torch.Tensor:
     """``confmat_mean(confmat_normalize(cm))`` for every arm pair in one launch: float64 [pairs]."""
     return N.consensus(counts)
+
+
+def mk_masks(bias):
+    """_utils.py:74-75: ``(pruning_mask, inds_prune)`` = the indices of the non-zero / zero entries of a bias vector
+    (the categories a pruned model keeps / has dropped), int64 numpy arrays."""
+    b = bias.detach().cpu().numpy() if isinstance(bias, torch.Tensor) else np.asarray(bias)
+    return np.where(b != 0)[0], np.where(b == 0)[0]
+
+
+def _assign_min(cost: np.ndarray) -> np.ndarray:
+    """Minimum-cost assignment of a square matrix by shortest augmenting paths with row / column potentials (the
+    Hungarian method in its O(K^3) form; the scan over the columns is vectorised): ``col[i]`` = the column of row i."""
+    n = cost.shape[0]
+    u, v = np.zeros(n + 1), np.zeros(n + 1)
+    p = np.zeros(n + 1, dtype=np.int64)             # p[j]: the row (1-based) matched to column j; column 0 is virtual
+    way = np.zeros(n + 1, dtype=np.int64)
+    for i in range(1, n + 1):
+        p[0] = i
+        j0 = 0
+        minv = np.full(n + 1, np.inf)
+        used = np.zeros(n + 1, dtype=bool)
+        while True:
+            used[j0] = True
+            i0 = p[j0]
+            cur = cost[i0 - 1] - u[i0] - v[1:]
+            upd = ~used[1:] & (cur < minv[1:])
+            minv[1:][upd] = cur[upd]
+            way[1:][upd] = j0
+            cand = np.where(used[1:], np.inf, minv[1:])
+            j1 = int(np.argmin(cand)) + 1
+            delta = cand[j1 - 1]
+            u[p[used]] += delta
+            v[used] -= delta
+            minv[~used] -= delta
+            j0 = j1
+            if p[j0] == 0:
+                break
+        while j0:
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+    col = np.zeros(n, dtype=np.int64)
+    col[p[1:] - 1] = np.arange(n)
+    return col
+
+
+def reassign(x):
+    """_utils.py:68-70: the columns of the square matrix x permuted by a maximum-weight assignment
+    (``linear_sum_assignment(-x)``), solved here in numpy (the package does not import scipy).  Which of several optimal
+    assignments is taken may differ from scipy's; ``np.mean(np.diag(reassign(x)))`` -- all any caller uses -- is the optimal
+    value over K either way."""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.shape[0] != x.shape[1]:
+        raise ValueError(f"reassign takes a square matrix, got {x.shape}")
+    n = x.shape[0]
+    if n == 0:
+        return x
+    w = x.astype(np.float64)
+    rows, cols = np.flatnonzero(w.any(axis=1)), np.flatnonzero(w.any(axis=0))
+    if (len(rows) == n and len(cols) == n) or (w < 0).any():
+        return x[:, _assign_min(-w)]
+    # A non-negative matrix with all-zero rows or columns (a confusion matrix of arms that use a few of K categories; the
+    # solver walks K^2 ties there: 99 ms at K = 92 with three labels): those rows and columns add nothing whichever way they
+    # are matched, so the assignment is solved on the rest, padded square with zeros (an unmatched row or column of the rest
+    # costs nothing either), and the remaining rows take the remaining columns in order.
+    m = max(len(rows), len(cols))
+    sub = np.zeros((m, m))
+    sub[:len(rows), :len(cols)] = w[np.ix_(rows, cols)]
+    col = np.full(n, -1, dtype=np.int64)
+    if m:
+        c = _assign_min(-sub)[:len(rows)]
+        real = c < len(cols)
+        col[rows[real]] = cols[c[real]]
+    col[col < 0] = np.setdiff1d(np.arange(n), col[col >= 0])
+    return x[:, col]

@@ -780,15 +780,10 @@ class cpl_mixVAE:
         out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
                "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
                "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
-        data_indx = torch.zeros(n_rows, dtype=torch.float64, device=dev)
         from ._utils import confmat_counts, consensus_from_counts
+        from .model import fill_latents
         counts = confmat_counts(A, Cc, dev)
-        for i, (x, data_idx) in enumerate(dl):
-            n_fst, n_lst = i * B, min((i + 1) * B, n_rows)
-            x = x.to(dev)
-            self.model.encode(x.expand(A, -1, -1), self.temp, mask=pruning_mask, out=out, row0=n_fst,
-                              counts=counts if A > 1 else None)
-            data_indx[n_fst:n_lst] = torch.as_tensor(data_idx).to(dev).to(torch.int64).to(torch.float64)
+        data_indx = fill_latents(dl, [(self.model, pruning_mask, out, counts if A > 1 else None)], self.temp)
         prob = out["c"].max(dim=-1).values
         cnss = float(np.mean(consensus_from_counts(counts).cpu().numpy())) if A > 1 and n_rows else float("nan")
         self.model.train(was_training)

@@ -907,6 +907,53 @@ int mmvae_consensus(const int64_t* counts, int npairs, int C, double* cm_norm, d
     return launch_consensus(counts, npairs, C, cm_norm, consensus, reinterpret_cast<hipStream_t>(stream));
 }
 
+// every argument of mmvae_pair_stats is checked here, on the host, before any device work
+static int pair_stats_args(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
+                           int n_pairs, const int64_t* counts, const int64_t* dist_acc) {
+    if (!labels || !probs || !pairs || !counts || !dist_acc) { set_error("pair_stats: null pointer"); return MMVAE_E_BADARG; }
+    if (C < 1 || C > 128) { set_error("pair_stats: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (n < 0 || n_pairs < 0) { set_error("pair_stats: negative n or n_pairs"); return MMVAE_E_BADARG; }
+    if (n > ((int64_t)1 << 31)) { set_error("pair_stats: more than 2^31 cells in one call"); return MMVAE_E_BADARG; }
+    if (n_arms_total < 1 || n_arms_total > 2 * MMVAE_MAX_ARMS) {
+        set_error("pair_stats: n_arms_total = %d outside [1, %d]", n_arms_total, 2 * MMVAE_MAX_ARMS);
+        return MMVAE_E_BADARG;
+    }
+    for (int64_t k = 0; k < 4 * (int64_t)n_pairs; ++k)
+        if (pairs[k] < 0 || pairs[k] >= n_arms_total) {
+            set_error("pair_stats: pairs[%lld][%d] = %d outside [0, %d)", (long long)(k / 4), (int)(k % 4), pairs[k], n_arms_total);
+            return MMVAE_E_BADARG;
+        }
+    return 0;
+}
+
+int mmvae_pair_stats(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
+                     int n_pairs, int64_t* counts, int64_t* dist_acc, void* stream) {
+    if (int rc = pair_stats_args(labels, probs, n_arms_total, n, C, pairs, n_pairs, counts, dist_acc)) return rc;
+    if (n == 0 || n_pairs == 0) return 0;
+    return launch_pair_stats(labels, probs, n, C, pairs, n_pairs, counts, dist_acc, -1, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_pair_stats(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
+                           int n_pairs, int64_t* counts, int64_t* dist_acc, int path, void* stream) {
+    if (int rc = pair_stats_args(labels, probs, n_arms_total, n, C, pairs, n_pairs, counts, dist_acc)) return rc;
+    if (path < -1 || path > 1) { set_error("debug_pair_stats: path %d outside {-1, 0, 1}", path); return MMVAE_E_BADARG; }
+    if (n == 0 || n_pairs == 0) return 0;
+    return launch_pair_stats(labels, probs, n, C, pairs, n_pairs, counts, dist_acc, path, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_pair_stats_finish(const int64_t* counts, const int64_t* dist_acc, int n_pairs, int C, double* cm_norm, double* emp,
+                            double* dist_norm, double* diag_mean, double* diag_min, void* stream) {
+    if (!counts || !dist_acc || !cm_norm || !emp || !dist_norm || !diag_mean || !diag_min) {
+        set_error("pair_stats_finish: null pointer");
+        return MMVAE_E_BADARG;
+    }
+    if (C < 1 || C > 128) { set_error("pair_stats_finish: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (n_pairs < 0) { set_error("pair_stats_finish: negative n_pairs"); return MMVAE_E_BADARG; }
+    if (n_pairs == 0) return 0;
+    return launch_pair_finish(counts, dist_acc, n_pairs, C, cm_norm, emp, dist_norm, diag_mean, diag_min,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

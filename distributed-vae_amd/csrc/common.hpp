@@ -962,6 +962,11 @@ int launch_pp_rowmap(hipStream_t s, const int64_t* rows, int n, int64_t n_rows, 
 int launch_classify(const float* cc, int64_t n_cells, int C, int32_t* labels, hipStream_t s);
 int launch_confmat(const int32_t* labels, int A, int64_t n, int C, int64_t* counts, hipStream_t s);
 int launch_consensus(const int64_t* counts, int npairs, int C, double* cm_norm, double* consensus, hipStream_t s);
+constexpr int PS_LDS_MAX_C = 116;   // largest C whose pair-statistics histogram fits a workgroup's LDS (consensus.hip)
+int launch_pair_stats(const int32_t* labels, const float* probs, int64_t n, int C, const int32_t* pairs, int n_pairs,
+                      int64_t* counts, int64_t* dist_acc, int path, hipStream_t s);
+int launch_pair_finish(const int64_t* counts, const int64_t* dist_acc, int n_pairs, int C, double* cm_norm, double* emp,
+                       double* dist_norm, double* diag_mean, double* diag_min, hipStream_t s);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

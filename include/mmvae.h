@@ -311,6 +311,41 @@ int mmvae_confmat_accumulate(const int32_t *labels, int A, int64_t n, int C, int
 int mmvae_consensus(const int64_t *counts, int npairs, int C, double *cm_norm, double *consensus,
                     void *stream);
 
+/* ---- cross-run evaluation (mmidas/_evals.py::evals2) ---------------------
+ * evals2 fills, for every arm pair of two trained runs, a confusion matrix pm and a matrix emp of summed
+ * probability distances with a host loop over the cells.  Here the labels and probabilities of both runs stay on
+ * the device: T = the arms of run a followed by the arms of run b, labels int32 [T, n] (mmvae_encode's labels),
+ * probs float [T, n, C] (mmvae_encode's c).
+ *
+ * mmvae_pair_stats: pairs is a HOST array int32 [n_pairs][4] = (lab1, prob1, lab2, prob2), arm indices into T (the
+ *   reference's within-run loops take the second probability row from another arm than the second label row, so
+ *   the four are separate).  For every pair p and cell i with i1 = labels[lab1][i], i2 = labels[lab2][i] both in
+ *   [0, C) (other cells are skipped):
+ *     counts[p][i1][i2] += 1                                                    int64 [n_pairs, C, C]
+ *     dist[p][i1][i2]   += |(double)probs[prob1][i][i1] - (double)probs[prob2][i][i2]|
+ *   dist_acc: int64 [n_pairs, C, C, 2], a fixed-point sum with resolution 2^-52 (slots hi, lo; value =
+ *   (hi 2^32 + lo) 2^-52): every term is truncated by at most 2^-52, the adds are integer atomics, so the result is
+ *   bit-identical from run to run and cannot overflow below 2^31 cells per call sequence.  A term outside [0, 2)
+ *   (not a difference of probabilities; NaN, Inf) marks its matrix cell, which then reads back as NaN.  Both arrays
+ *   are zeroed by the caller and a call ADDS to them, so a data set can be fed batch by batch.
+ * mmvae_pair_stats_finish, per pair in fp64: smp[j] = max(row sum j, column sum j) of counts;
+ *   cm_norm = counts / smp[j] along the last axis, 0 where smp[j] == 0 (mmvae_consensus's cm_norm, bit for bit);
+ *   emp = the distance sums; dist_norm = emp / smp[j] by the same rule (all double [n_pairs, C, C]);
+ *   diag_mean = mean of diag(cm_norm) in numpy's summation order, diag_min its minimum (double [n_pairs]).
+ * Both check every argument on the host before any device work: MMVAE_E_BADARG for a null pointer, C outside
+ *   [1, 128], n < 0 or n > 2^31, n_pairs < 0, n_arms_total outside [1, 2 MMVAE_MAX_ARMS], a pair index outside
+ *   [0, n_arms_total).  n == 0 or n_pairs == 0: returns 0 without a launch.
+ * mmvae_debug_pair_stats: mmvae_pair_stats with the kernel path named (-1 the launcher's rule, 0 the per-workgroup
+ *   LDS histogram -- C <= 116, else MMVAE_E_UNSUPPORTED --, 1 the wave-combined global atomics); same results. */
+int mmvae_pair_stats(const int32_t *labels, const float *probs, int n_arms_total, int64_t n, int C,
+                     const int32_t *pairs, int n_pairs, int64_t *counts, int64_t *dist_acc, void *stream);
+int mmvae_pair_stats_finish(const int64_t *counts, const int64_t *dist_acc, int n_pairs, int C,
+                            double *cm_norm, double *emp, double *dist_norm, double *diag_mean,
+                            double *diag_min, void *stream);
+int mmvae_debug_pair_stats(const int32_t *labels, const float *probs, int n_arms_total, int64_t n, int C,
+                           const int32_t *pairs, int n_pairs, int64_t *counts, int64_t *dist_acc, int path,
+                           void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
