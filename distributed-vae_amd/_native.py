@@ -205,6 +205,13 @@ def lib():
     L.mmvae_pair_stats_finish.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     for fn in ("mmvae_pair_stats", "mmvae_debug_pair_stats", "mmvae_pair_stats_finish"):
         getattr(L, fn).restype = C.c_int
+    L.mmvae_mutinfo_counts.argtypes = [vp, i32, i64, i32, vp, i32, i64, i32, vp, vp, vp, vp]
+    L.mmvae_debug_mutinfo_counts.argtypes = [vp, i32, i64, i32, vp, i32, i64, i32, vp, vp, vp, i32, vp]
+    L.mmvae_ami_binary_workspace_bytes.argtypes = [i64]
+    L.mmvae_ami_binary_workspace_bytes.restype = C.c_size_t
+    L.mmvae_ami_binary.argtypes = [vp, vp, vp, i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
+    for fn in ("mmvae_mutinfo_counts", "mmvae_debug_mutinfo_counts", "mmvae_ami_binary"):
+        getattr(L, fn).restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -651,6 +658,64 @@ def pair_stats_finish(counts: torch.Tensor, dist_acc: torch.Tensor) -> Dict[str,
         check(lib().mmvae_pair_stats_finish(_ptr(cnt), _ptr(acc), P, Cc, _ptr(out["cm_norm"]), _ptr(out["emp"]),
                                             _ptr(out["dist_norm"]), _ptr(out["diag_mean"]), _ptr(out["diag_min"]),
                                             _stream(cnt.device)), "mmvae_pair_stats_finish")
+    return out
+
+
+MUTINFO_LDS_MAX_WORDS = 16384   # MI_LDS_MAX_WORDS of csrc/common.hpp: F * C + C + F counts at most for the LDS histograms
+MUTINFO_PATHS = {"auto": -1, "lds": 0, "global": 1}
+
+
+def mutinfo_counts(labels: torch.Tensor, targets: torch.Tensor, Cc: int, F: Optional[int] = None, out=None, path: str = "auto"):
+    """mmvae_mutinfo_counts: labels int32 [A, n] and a 0/1 matrix ``targets`` [n, >= F] (uint8, bool or int32; rows may be
+    strided, columns not) on the GPU -> (counts int64 [A, F, C], t_sum int64 [F], p_sum int64 [A, C]); ``out``: the three
+    accumulators of an earlier call, which this one adds to.  ``F``: the leading columns used (default: all).  ``path``:
+    "auto" (the launcher's rule), "lds" or "global" (mmvae_debug_mutinfo_counts: the same counts on a named path)."""
+    if labels.device.type != "cuda" or targets.device.type != "cuda":
+        raise NativeError("mutinfo_counts needs CUDA tensors (no CPU fallback)")
+    lab = labels.contiguous()
+    tg = targets.view(torch.uint8) if targets.dtype == torch.bool else targets
+    if lab.dtype != torch.int32 or lab.dim() != 2 or tg.dtype not in (torch.uint8, torch.int32) or tg.dim() != 2:
+        raise TypeError("mutinfo_counts: labels must be int32 [A, n] and targets uint8 / bool / int32 [n, F]")
+    A, n = lab.shape
+    F = int(tg.shape[1] if F is None else F)
+    if tg.shape[0] != n or not 1 <= F <= tg.shape[1]:
+        raise ValueError(f"mutinfo_counts: targets {tuple(tg.shape)} do not give {n} cells x {F} columns")
+    if n > 1 and tg.stride(1) != 1:
+        tg = tg.contiguous()
+    ldt = int(tg.stride(0)) if n > 1 else max(int(tg.shape[1]), F)
+    shapes = ((A, F, Cc), (F,), (A, Cc))
+    if out is None:
+        out = tuple(torch.zeros(s, dtype=torch.int64, device=lab.device) for s in shapes)
+    for t, s in zip(out, shapes):
+        if t.dtype != torch.int64 or tuple(t.shape) != s or not t.is_contiguous() or t.device != lab.device:
+            raise ValueError(f"mutinfo_counts: accumulator must be a contiguous int64 {s} tensor on {lab.device}")
+    counts, t_sum, p_sum = out
+    args = (_ptr(lab), A, n, Cc, _ptr(tg), tg.element_size(), ldt, F, _ptr(counts), _ptr(t_sum), _ptr(p_sum))
+    if path == "auto":
+        rc = lib().mmvae_mutinfo_counts(*args, _stream(lab.device))
+    else:
+        rc = lib().mmvae_debug_mutinfo_counts(*args, MUTINFO_PATHS[path], _stream(lab.device))
+    check(rc, "mmvae_mutinfo_counts")
+    return counts, t_sum, p_sum
+
+
+def ami_binary(counts: torch.Tensor, t_sum: torch.Tensor, p_sum: torch.Tensor, n_cells: int, table: bool = True) -> torch.Tensor:
+    """mmvae_ami_binary on the counts of ``mutinfo_counts`` -> float64 [A, F, C] on the device: sklearn's adjusted mutual
+    information of every (cell-type column, cluster) pair of binary labelings of ``n_cells`` cells, NaN where p_sum == 0.
+    ``table``: log-gamma and log from a table in a workspace a first launch fills (the default), or evaluated per term."""
+    if counts.device.type != "cuda":
+        raise NativeError("ami_binary needs CUDA tensors (no CPU fallback)")
+    cnt, ts, ps = counts.contiguous(), t_sum.contiguous(), p_sum.contiguous()
+    A, F, Cc = cnt.shape
+    if any(t.dtype != torch.int64 for t in (cnt, ts, ps)) or tuple(ts.shape) != (F,) or tuple(ps.shape) != (A, Cc):
+        raise ValueError("ami_binary: counts int64 [A, F, C], t_sum int64 [F] and p_sum int64 [A, C] expected")
+    out = torch.empty(A, F, Cc, dtype=torch.float64, device=cnt.device)
+    ws, ws_bytes = None, 0
+    if table:
+        ws_bytes = int(lib().mmvae_ami_binary_workspace_bytes(int(n_cells)))
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=cnt.device)
+    check(lib().mmvae_ami_binary(_ptr(cnt), _ptr(ts), _ptr(ps), A, F, Cc, int(n_cells), _ptr(ws), ws_bytes, _ptr(out),
+                                 _stream(cnt.device)), "mmvae_ami_binary")
     return out
 
 

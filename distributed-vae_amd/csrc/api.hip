@@ -954,6 +954,61 @@ int mmvae_pair_stats_finish(const int64_t* counts, const int64_t* dist_acc, int 
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+// every argument of mmvae_mutinfo_counts is checked here, on the host, before any device work
+static int mutinfo_counts_args(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt,
+                               int F, const int64_t* counts, const int64_t* t_sum, const int64_t* p_sum) {
+    if (!labels || !targets || !counts || !t_sum || !p_sum) { set_error("mutinfo_counts: null pointer"); return MMVAE_E_BADARG; }
+    if (A < 1 || A > MMVAE_MAX_ARMS) { set_error("mutinfo_counts: A = %d outside [1, %d]", A, MMVAE_MAX_ARMS); return MMVAE_E_BADARG; }
+    if (C < 1 || C > 128) { set_error("mutinfo_counts: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (F < 1 || F > 4096) { set_error("mutinfo_counts: F = %d outside [1, 4096]", F); return MMVAE_E_BADARG; }
+    if (n < 0 || n > ((int64_t)1 << 31)) { set_error("mutinfo_counts: n outside [0, 2^31]"); return MMVAE_E_BADARG; }
+    if (ldt < F) { set_error("mutinfo_counts: ldt = %lld below F = %d", (long long)ldt, F); return MMVAE_E_BADARG; }
+    if (target_bytes != 1 && target_bytes != 4) {
+        set_error("mutinfo_counts: target_bytes = %d is neither 1 (uint8) nor 4 (int32)", target_bytes);
+        return MMVAE_E_BADARG;
+    }
+    return 0;
+}
+
+int mmvae_mutinfo_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt, int F,
+                         int64_t* counts, int64_t* t_sum, int64_t* p_sum, void* stream) {
+    if (int rc = mutinfo_counts_args(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum)) return rc;
+    if (n == 0) return 0;
+    return launch_mi_counts(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum, -1,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_mutinfo_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt,
+                               int F, int64_t* counts, int64_t* t_sum, int64_t* p_sum, int path, void* stream) {
+    if (int rc = mutinfo_counts_args(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum)) return rc;
+    if (path < -1 || path > 1) { set_error("debug_mutinfo_counts: path %d outside {-1, 0, 1}", path); return MMVAE_E_BADARG; }
+    if (n == 0) return 0;
+    return launch_mi_counts(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum, path,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mmvae_ami_binary_workspace_bytes(int64_t N) {
+    return N < 1 || N > ((int64_t)1 << 31) ? 0 : 2 * (size_t)(N + 1) * sizeof(double);
+}
+
+int mmvae_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_sum, int A, int F, int C, int64_t N, void* ws,
+                     size_t ws_bytes, double* ami, void* stream) {
+    if (!n11 || !t_sum || !p_sum || !ami) { set_error("ami_binary: null pointer"); return MMVAE_E_BADARG; }
+    if (A < 0 || A > MMVAE_MAX_ARMS) { set_error("ami_binary: A = %d outside [0, %d]", A, MMVAE_MAX_ARMS); return MMVAE_E_BADARG; }
+    if (C < 1 || C > 128) { set_error("ami_binary: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (F < 1 || F > 4096) { set_error("ami_binary: F = %d outside [1, 4096]", F); return MMVAE_E_BADARG; }
+    if (N < 1 || N > ((int64_t)1 << 31)) { set_error("ami_binary: N outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (ws) {
+        if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("ami_binary: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+        if (ws_bytes < mmvae_ami_binary_workspace_bytes(N)) {
+            set_error("ami_binary: workspace of %zu bytes below the %zu needed", ws_bytes, mmvae_ami_binary_workspace_bytes(N));
+            return MMVAE_E_WORKSPACE;
+        }
+    }
+    if (A == 0) return 0;
+    return launch_ami_binary(n11, t_sum, p_sum, A, F, C, N, static_cast<double*>(ws), ami, reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

@@ -967,6 +967,12 @@ int launch_pair_stats(const int32_t* labels, const float* probs, int64_t n, int 
                       int64_t* counts, int64_t* dist_acc, int path, hipStream_t s);
 int launch_pair_finish(const int64_t* counts, const int64_t* dist_acc, int n_pairs, int C, double* cm_norm, double* emp,
                        double* dist_norm, double* diag_mean, double* diag_min, hipStream_t s);
+// mutual-information evaluation (mutinfo.hip)
+constexpr int MI_LDS_MAX_WORDS = 16384;   // F * C + C + F 32-bit counts at most for the LDS histograms of k_mi_counts (64 KiB)
+int launch_mi_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int tsize, int64_t ldt, int F,
+                     int64_t* counts, int64_t* t_sum, int64_t* p_sum, int path, hipStream_t s);
+int launch_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_sum, int A, int F, int C, int64_t N, double* ws,
+                      double* ami, hipStream_t s);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

@@ -346,6 +346,45 @@ int mmvae_debug_pair_stats(const int32_t *labels, const float *probs, int n_arms
                            const int32_t *pairs, int n_pairs, int64_t *counts, int64_t *dist_acc, int path,
                            void *stream);
 
+/* ---- mutual-information evaluation (evaluation.py::mutinfo) ---------------
+ * mutinfo scores a model by sklearn's adjusted_mutual_info_score between every cell-type column f of the one-hot
+ * targets and every cluster c, two binary labelings of the n cells per call.  Here one launch counts the
+ * contingency of all (arm, f, c) and one launch evaluates all 2 x 2 adjusted-MI values from the counts.
+ *
+ * mmvae_mutinfo_counts: labels int32 [A, n] (mmvae_classify's argmax); targets a row-major 0/1 matrix [n, ldt] of
+ *   which columns 0..F-1 are used, elements of target_bytes = 1 (uint8) or 4 (int32) bytes, non-zero = set.
+ *   For every cell i and arm a with l = labels[a][i] in [0, C) (other labels are skipped):
+ *     counts[a][f][l] += 1 for each f < F with targets[i][f] != 0        int64 [A, F, C]
+ *     p_sum[a][l]     += 1                                                int64 [A, C]
+ *   and t_sum[f] += 1 once per cell per set column, whatever the labels   int64 [F].
+ *   Integer atomics: bit-identical from run to run.  The caller zeroes the three arrays and a call ADDS to them, so
+ *   a data set can be fed batch by batch.  MMVAE_E_BADARG, before any device work, for a null pointer, A outside
+ *   [1, MMVAE_MAX_ARMS], C outside [1, 128], F outside [1, 4096], n < 0 or n > 2^31, ldt < F, target_bytes not 1
+ *   or 4.  n == 0: returns 0 without a launch.
+ * mmvae_debug_mutinfo_counts: the same with the kernel path named: -1 the launcher's rule, 0 per-workgroup LDS
+ *   histograms (F C + C + F <= 16384 counts, else MMVAE_E_UNSUPPORTED), 1 global atomics; same results.
+ * mmvae_ami_binary: ami[a][f][c] (double [A, F, C]) = adjusted_mutual_info_score(u, v), average_method
+ *   "arithmetic", of binary labelings u with t = t_sum[f] ones and v with p = p_sum[a][c] ones of N cells that share
+ *   n11[a][f][c] ones, restated from the counts in fp64: contingency [[N-t-p+n11, p-n11], [t-n11, n11]]; both
+ *   labelings single-valued 1.0, exactly one 0.0, else (MI - EMI) / (mean(H(u), H(v)) - EMI) with sklearn's clamps
+ *   (numerator and denominator away from zero by 2^-52 keeping their sign, MI terms below 2^-52 dropped, MI clipped
+ *   at 0) and EMI the sum of sklearn's _expected_mutual_info_fast.pyx.  p == 0 (c is no cluster) gives NaN, and so
+ *   do counts that are no contingency table of N cells.  One wave per table with a fixed-order reduction:
+ *   bit-identical from run to run.  ws: mmvae_ami_binary_workspace_bytes(N) = 2 (N + 1) doubles of device memory
+ *   (0 for an N outside [1, 2^31]) for a table of lgamma(k + 1) and log(k) that a first small launch fills, or
+ *   NULL: log-gamma and log are then evaluated per term (slower; no memory).  MMVAE_E_BADARG, before any device
+ *   work, for a null n11 / t_sum / p_sum / ami, A outside [0, MMVAE_MAX_ARMS], C outside [1, 128], F outside
+ *   [1, 4096], N outside [1, 2^31], a misaligned ws; MMVAE_E_WORKSPACE for a ws below the size.  A == 0 (no
+ *   tables): returns 0 without a launch. */
+int mmvae_mutinfo_counts(const int32_t *labels, int A, int64_t n, int C, const void *targets, int target_bytes,
+                         int64_t ldt, int F, int64_t *counts, int64_t *t_sum, int64_t *p_sum, void *stream);
+int mmvae_debug_mutinfo_counts(const int32_t *labels, int A, int64_t n, int C, const void *targets,
+                               int target_bytes, int64_t ldt, int F, int64_t *counts, int64_t *t_sum,
+                               int64_t *p_sum, int path, void *stream);
+size_t mmvae_ami_binary_workspace_bytes(int64_t N);
+int mmvae_ami_binary(const int64_t *n11, const int64_t *t_sum, const int64_t *p_sum, int A, int F, int C,
+                     int64_t N, void *ws, size_t ws_bytes, double *ami, void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
