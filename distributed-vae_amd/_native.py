@@ -212,6 +212,10 @@ def lib():
     L.mmvae_ami_binary.argtypes = [vp, vp, vp, i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
     for fn in ("mmvae_mutinfo_counts", "mmvae_debug_mutinfo_counts", "mmvae_ami_binary"):
         getattr(L, fn).restype = C.c_int
+    L.mmvae_silhouette_workspace_bytes.argtypes = [i64, i32]
+    L.mmvae_silhouette_workspace_bytes.restype = C.c_size_t
+    L.mmvae_silhouette.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp]
+    L.mmvae_silhouette.restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -716,6 +720,50 @@ def ami_binary(counts: torch.Tensor, t_sum: torch.Tensor, p_sum: torch.Tensor, n
         ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=cnt.device)
     check(lib().mmvae_ami_binary(_ptr(cnt), _ptr(ts), _ptr(ps), A, F, Cc, int(n_cells), _ptr(ws), ws_bytes, _ptr(out),
                                  _stream(cnt.device)), "mmvae_ami_binary")
+    return out
+
+
+# launch_silhouette (csrc/silhouette.hip; the constants are those of csrc/common.hpp)
+SILHOUETTE_SEG_COLS = 512       # SIL_SEG_COLS: a cluster of more columns is cut into segments of this many
+SILHOUETTE_ROW_TILE = 256       # SIL_ROW_TILE: rows per workgroup, one thread each
+SILHOUETTE_LDS_FLOATS = 4096    # SIL_LDS_FLOATS: a pass stages SILHOUETTE_LDS_FLOATS // (4 * dv) columns
+SILHOUETTE_DV = (1, 2, 3, 4, 6, 8, 12, 16, 24, 32)   # SIL_DV: float4 pieces per point the kernel is built for
+SILHOUETTE_MAX_D = 128
+
+
+def silhouette_dv(d: int) -> int:
+    """The instance of the row kernel that runs dimension ``d``: the smallest entry of SILHOUETTE_DV with 4 * dv >= d."""
+    return next(v for v in SILHOUETTE_DV if 4 * v >= d)
+
+
+def silhouette(x_sorted: torch.Tensor, offsets: torch.Tensor, perm: Optional[torch.Tensor] = None, out=None,
+               path: str = "auto") -> torch.Tensor:
+    """mmvae_silhouette: float32 points [n, d] on the GPU (rows may be strided, columns not) ordered by cluster, int64
+    ``offsets`` [K + 1] (cluster k is the rows offsets[k] .. offsets[k + 1] - 1) and, optionally, the int64 permutation
+    ``perm`` [n] that sorted them (sorted row r is the caller's row perm[r]) -> sklearn's silhouette samples, float64 [n] on
+    the device, in the caller's order.  ``path``: the launcher has one path, "auto"."""
+    if x_sorted.device.type != "cuda" or offsets.device.type != "cuda" or (perm is not None and perm.device.type != "cuda"):
+        raise NativeError("silhouette needs CUDA tensors (no CPU fallback)")
+    if path != "auto":
+        raise ValueError(f"silhouette: the launcher has one path, 'auto'; got {path!r}")
+    if x_sorted.dtype != torch.float32 or x_sorted.dim() != 2 or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise TypeError("silhouette: x_sorted must be float32 [n, d] and offsets int64 [K + 1]")
+    n, d = (int(v) for v in x_sorted.shape)
+    x = x_sorted if x_sorted.stride(1) == 1 and x_sorted.stride(0) >= d else x_sorted.contiguous()
+    off = offsets.contiguous()
+    K = int(off.numel()) - 1
+    if perm is not None:
+        if perm.dtype != torch.int64 or tuple(perm.shape) != (n,):
+            raise TypeError(f"silhouette: perm must be int64 [{n}]")
+        perm = perm.contiguous()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=x.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"silhouette: out must be a contiguous float64 [{n}] tensor on {x.device}")
+    ws_bytes = int(lib().mmvae_silhouette_workspace_bytes(n, K))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    check(lib().mmvae_silhouette(_ptr(x), int(x.stride(0)), n, d, _ptr(off), K, _ptr(perm), _ptr(ws), ws_bytes, _ptr(out),
+                                 _stream(x.device)), "mmvae_silhouette")
     return out
 
 

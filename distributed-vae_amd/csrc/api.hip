@@ -1009,6 +1009,35 @@ int mmvae_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_
     return launch_ami_binary(n11, t_sum, p_sum, A, F, C, N, static_cast<double*>(ws), ami, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t mmvae_silhouette_workspace_bytes(int64_t n, int K) {
+    if (n < 3 || n > ((int64_t)1 << 31) || K < 2 || K > n - 1) return 0;
+    const unsigned __int128 nseg = (unsigned __int128)sil_nseg_max(n, K);
+    const unsigned __int128 bytes = 8 * (nseg * (unsigned __int128)n + nseg + 1) + 4 * (((unsigned __int128)K + 2) / 2 * 2);
+    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
+}
+
+// every argument is checked here, on the host, before any device work
+int mmvae_silhouette(const float* x_sorted, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
+                     size_t ws_bytes, double* s, void* stream) {
+    if (!x_sorted || !offsets || !ws || !s) { set_error("silhouette: null pointer"); return MMVAE_E_BADARG; }
+    if (n < 3 || n > ((int64_t)1 << 31)) { set_error("silhouette: n outside [3, 2^31]"); return MMVAE_E_BADARG; }
+    if (K < 2 || K > n - 1) { set_error("silhouette: K = %d outside [2, n - 1 = %lld]", K, (long long)(n - 1)); return MMVAE_E_BADARG; }
+    if (d < 1) { set_error("silhouette: d = %d below 1", d); return MMVAE_E_BADARG; }
+    if (ld < d) { set_error("silhouette: ld = %lld below d = %d", (long long)ld, d); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("silhouette: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+    if (d > SIL_MAX_D) { set_error("silhouette: d = %d above %d", d, SIL_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_silhouette_workspace_bytes(n, K);
+    if (sil_nseg_max(n, K) > SIL_MAX_SEGMENTS || need == 0) {
+        set_error("silhouette: K + n / %d = %lld segments above %lld", SIL_SEG_COLS, (long long)sil_nseg_max(n, K), (long long)SIL_MAX_SEGMENTS);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (ws_bytes < need) {
+        set_error("silhouette: workspace of %zu bytes below the %zu needed", ws_bytes, need);
+        return MMVAE_E_WORKSPACE;
+    }
+    return launch_silhouette(x_sorted, ld, n, d, offsets, K, perm, ws, s, reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

@@ -973,6 +973,18 @@ int launch_mi_counts(const int32_t* labels, int A, int64_t n, int C, const void*
                      int64_t* counts, int64_t* t_sum, int64_t* p_sum, int path, hipStream_t s);
 int launch_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_sum, int A, int F, int C, int64_t N, double* ws,
                       double* ami, hipStream_t s);
+// silhouette samples (silhouette.hip)
+constexpr int SIL_SEG_COLS = 512;      // columns per segment at most: a longer cluster is cut into pieces of this many
+constexpr int SIL_ROW_TILE = 256;      // rows per workgroup of k_sil_partial, one thread each
+constexpr int SIL_LDS_FLOATS = 4096;   // floats of staged columns per pass (16 KiB)
+constexpr int SIL_MAX_D = 128;
+constexpr int SIL_N_DV = 10;
+constexpr int SIL_DV[SIL_N_DV] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};   // float4 pieces per point k_sil_partial is built for
+constexpr int64_t SIL_MAX_SEGMENTS = (int64_t)1 << 23;                 // a grid's x extent times 256 threads stays below 2^32
+int64_t sil_nseg_max(int64_t n, int K);
+int sil_dv(int d);
+int launch_silhouette(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
+                      double* s, hipStream_t st);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

@@ -385,6 +385,39 @@ size_t mmvae_ami_binary_workspace_bytes(int64_t N);
 int mmvae_ami_binary(const int64_t *n11, const int64_t *t_sum, const int64_t *p_sum, int A, int F, int C,
                      int64_t N, void *ws, size_t ws_bytes, double *ami, void *stream);
 
+/* ---- silhouette samples (mmidas/utils/cluster_analysis.py: get_SilhScore, cluster_compare) ----
+ * sklearn's silhouette_samples(X, labels, metric="euclidean") of n cells with points x_i in R^d and encoded labels
+ * l_i in [0, K), cluster sizes f_k:
+ *   S(i, k) = sum over the cells j with l_j = k of |x_i - x_j|_2
+ *   a_i = S(i, l_i) / (f_{l_i} - 1)          (the cell itself adds an exact 0)
+ *   b_i = min over k != l_i of S(i, k) / f_k
+ *   s_i = (b_i - a_i) / max(a_i, b_i);  s_i = 0 when f_{l_i} = 1;  s_i = 0 when max(a_i, b_i) = 0
+ * (sklearn reaches both zero rules through 0 / 0 and nan_to_num).
+ *
+ * mmvae_silhouette: x_sorted float32 row-major [n, ld], columns 0..d-1 used, the cells ordered by label, so that cluster
+ *   k is the rows offsets[k] .. offsets[k + 1] - 1; offsets int64 [K + 1] on the device; perm int64 [n] on the device,
+ *   perm[r] the caller's index of sorted row r, or NULL for the identity; s double [n] on the device, s[perm[r]] the
+ *   value of sorted row r.  The host cannot read device memory without a synchronisation, so offsets that are not
+ *   non-decreasing from offsets[0] = 0 to offsets[K] = n, and a perm that is no permutation of 0..n-1, are the CALLER'S
+ *   CONTRACT: they give wrong values (no access outside the arrays).  An empty cluster is skipped.
+ *   Arithmetic: every distance in fp32 in difference form (x_i - x_j per coordinate, the squares added by fma in
+ *   coordinate order, a square root good to 1 ulp; no Gram expansion, hence no cancellation): relative error at most
+ *   (d / 2 + 2) 2^-24 for finite inputs without overflow or denormal differences.  The sums S, the divisions, the minimum
+ *   and s are fp64.  Nothing of size n x n exists: the sorted columns are cut into segments (whole clusters, a cluster of
+ *   more than 512 columns into pieces of 512), a first launch builds that table, a second one adds every (row, segment)
+ *   sum in column order and a third adds each cluster's segments in order and forms s.  No atomics, every sum in an order
+ *   fixed by the inputs: bit-identical from run to run, and a row's value does not depend on the rows beside it.
+ *   ws: mmvae_silhouette_workspace_bytes(n, K) bytes of device memory, 8-byte aligned: with m = K + n / 512 (the most
+ *   segments there can be) m n doubles of partial sums, m + 1 int64 and K + 1 int32 of tables; 0 for an n or K that
+ *   mmvae_silhouette refuses as a bad argument, or a size that size_t cannot hold.
+ *   MMVAE_E_BADARG, before any device work, for a null x_sorted / offsets / ws / s, n < 3 or n > 2^31, K outside
+ *   [2, n - 1], d < 1, ld < d, a misaligned ws; MMVAE_E_UNSUPPORTED for d > 128 or more than 2^23 possible segments;
+ *   MMVAE_E_WORKSPACE for a ws below the size.  The launcher has one path (the d dispatch picks among instances of one
+ *   kernel that give the same bits), so there is no debug entry. */
+size_t mmvae_silhouette_workspace_bytes(int64_t n, int K);
+int mmvae_silhouette(const float *x_sorted, int64_t ld, int64_t n, int d, const int64_t *offsets, int K,
+                     const int64_t *perm /* NULL = identity */, void *ws, size_t ws_bytes, double *s, void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
