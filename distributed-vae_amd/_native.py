@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -216,6 +216,11 @@ def lib():
     L.mmvae_silhouette_workspace_bytes.restype = C.c_size_t
     L.mmvae_silhouette.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp]
     L.mmvae_silhouette.restype = C.c_int
+    L.mmvae_state_corr_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.mmvae_state_corr_workspace_bytes.restype = C.c_size_t
+    L.mmvae_state_corr.argtypes = [vp, i64, i64, i32, vp, vp, i64, i64, i32, vp, i32, vp, C.c_size_t, vp, vp, vp]
+    L.mmvae_debug_state_corr.argtypes = [vp, i64, i64, i32, vp, vp, i64, i64, i32, vp, i32, vp, C.c_size_t, vp, vp, i32, vp]
+    L.mmvae_state_corr.restype = L.mmvae_debug_state_corr.restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -765,6 +770,57 @@ def silhouette(x_sorted: torch.Tensor, offsets: torch.Tensor, perm: Optional[tor
     check(lib().mmvae_silhouette(_ptr(x), int(x.stride(0)), n, d, _ptr(off), K, _ptr(perm), _ptr(ws), ws_bytes, _ptr(out),
                                  _stream(x.device)), "mmvae_silhouette")
     return out
+
+
+# launch_state_corr (csrc/statecorr.hip; the constants are those of csrc/common.hpp)
+STATECORR_SEG_ROWS = 256        # SC_SEG_ROWS: a group of more rows is cut into segments of this many
+STATECORR_TILE = 256            # SC_TILE: genes per wave of k_sc_partial, four consecutive genes a lane
+STATECORR_MAX_S = 32            # SC_MAX_S
+STATECORR_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
+
+
+def state_corr_wide(data: torch.Tensor) -> bool:
+    """The launcher's rule: the 16-byte loads where the matrix's base is 16-byte aligned and its row pitch a multiple of 4."""
+    return data.data_ptr() % 16 == 0 and data.stride(0) % 4 == 0
+
+
+def state_corr(data: torch.Tensor, state: torch.Tensor, rows: Optional[torch.Tensor] = None,
+               offsets: Optional[torch.Tensor] = None, path: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """mmvae_state_corr: float32 ``data`` [n_total, D] on the GPU (rows may be strided, columns not; read where it lies),
+    float32 ``state`` [n, S], optionally the int64 row map ``rows`` [n] (state row r belongs to ``data[rows[r]]``; None:
+    rows 0..n-1) and the int64 ``offsets`` [G + 1] that cut the n cells, ordered by group, into G groups (None: one group)
+    -> (r float64 [G, S, D], count int64 [G, D]) on the device: the Pearson correlation of every state with every gene over
+    the group's cells with x > 0, exactly 0 where there are at most four of them, NaN where x or the state is constant over
+    them.  Inputs must be finite.  ``path``: "auto" (the launcher's rule), "narrow", "wide" -- the load forms, equal bits."""
+    tensors = [t for t in (data, state, rows, offsets) if t is not None]
+    if any(t.device.type != "cuda" for t in tensors):
+        raise NativeError("state_corr needs CUDA tensors (no CPU fallback)")
+    if path not in STATECORR_PATHS:
+        raise ValueError(f"state_corr: path must be one of {sorted(STATECORR_PATHS)}; got {path!r}")
+    if data.dtype != torch.float32 or data.dim() != 2 or state.dtype != torch.float32 or state.dim() != 2:
+        raise TypeError("state_corr: data must be float32 [n_total, D] and state float32 [n, S]")
+    n_total, Dm = (int(v) for v in data.shape)
+    n, S = (int(v) for v in state.shape)
+    x = data if Dm == 0 or (data.stride(1) == 1 and data.stride(0) >= Dm) else data.contiguous()
+    st = state if S == 0 or (state.stride(1) == 1 and state.stride(0) >= S) else state.contiguous()
+    if rows is not None:
+        if rows.dtype != torch.int64 or tuple(rows.shape) != (n,):
+            raise TypeError(f"state_corr: rows must be int64 [{n}]")
+        rows = rows.contiguous()
+    G = 1
+    if offsets is not None:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2:
+            raise TypeError("state_corr: offsets must be int64 [G + 1]")
+        offsets = offsets.contiguous()
+        G = int(offsets.numel()) - 1
+    r = torch.empty(G, S, Dm, dtype=torch.float64, device=x.device)
+    count = torch.empty(G, Dm, dtype=torch.int64, device=x.device)
+    ws_bytes = int(lib().mmvae_state_corr_workspace_bytes(n, Dm, S, G))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    check(lib().mmvae_debug_state_corr(_ptr(x), int(x.stride(0)), n_total, Dm, _ptr(rows), _ptr(st), int(st.stride(0)), n, S,
+                                       _ptr(offsets), G, _ptr(ws), ws_bytes, _ptr(r), _ptr(count), STATECORR_PATHS[path],
+                                       _stream(x.device)), "mmvae_state_corr")
+    return r, count
 
 
 def to_bf16(data: torch.Tensor) -> torch.Tensor:

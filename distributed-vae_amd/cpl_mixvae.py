@@ -802,3 +802,70 @@ class cpl_mixVAE:
             "prune_indx": prune_indx,
             "cnss": cnss,
         }
+
+    @torch.no_grad()
+    def state_gene_corr(self, dl, arm: int = 0, by_category: bool = True):
+        """Which genes follow the state variable: the reference's ``corr_analysis`` (mmidas/utils/tree_based_analysis.py:7-59)
+        of arm ``arm``'s ``s_mean`` with the expression of the cells of ``dl``, for every category of that arm at once ("S
+        conditioning on Z = k"; ``by_category=False``: over all cells).  ``dl`` is encoded through the device encode path
+        (``fill_latents``, as ``encode_dataset``); ``s_mean`` and the arm's labels stay on the device, and
+        ``mmvae_state_corr`` reads the expression where it lies: a ``DeviceLoader``'s resident matrix through the batches'
+        row indices, or, for a plain loader, the concatenation of its batches on the device.  Neither the matrix nor the
+        latents are copied to the host.  Returns ``{"corr": float64 [G, S, D], "n": int64 [G, D], "categories": int64 [G]}``:
+        the signed Pearson r over the category's cells that express the gene (0 where at most four do, NaN where the
+        expression or the state is constant over them), their number, and the 0-based categories (all ``n_categories`` of
+        them; a category with no cell gives a row of zeros); G = 1 and category -1 with ``by_category=False``.  The loader
+        must serve every row once (no ``drop_last``)."""
+        if D.is_dist():
+            raise NotImplementedError("state_gene_corr is not data-parallel: run it on one rank, outside the process group")
+        if self.ref_prior:
+            raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
+        if not 0 <= int(arm) < self.n_arm:
+            raise ValueError(f"arm = {arm} outside [0, {self.n_arm})")
+        from .model import fill_latents
+        from .utils.dataloader import DeviceLoader
+        from .utils.tree_based_analysis import grouped_state_corr
+        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
+        dev = self.device
+        resident = isinstance(dl, DeviceLoader)
+        if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
+            raise ValueError("state_gene_corr needs a loader that serves every row once (no drop_last, no sharding)")
+        if not resident:
+            dl = _Replay(dl, dev)                                         # one walk of the loader: the same batches twice
+        n_rows = len(dl.dataset)
+        was_training = self.model.training
+        self.model.eval()
+        bias = self.model.fcc[0].bias.detach().cpu().numpy()
+        pruning_mask = np.where(bias != 0.0)[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
+               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
+               "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
+        inds = fill_latents(dl, [(self.model, pruning_mask, out, None)], self.temp)
+        self.model.train(was_training)
+        if resident:
+            data, rows = dl.data, inds.to(torch.int64)                     # the batches' indices are rows of the matrix
+        else:
+            data, rows = dl.matrix(), None
+        codes = out["labels"][int(arm)].to(torch.int64) if by_category else None
+        r, cnt = grouped_state_corr(out["s_mean"][int(arm)], data, rows, codes, Cc if by_category else 1)
+        cats = np.arange(Cc, dtype=np.int64) if by_category else np.array([-1], dtype=np.int64)
+        return {"corr": r.cpu().numpy(), "n": cnt.cpu().numpy(), "categories": cats}
+
+
+class _Replay:
+    """The batches ``(x, index)`` of one walk of a loader, kept on the device: ``fill_latents`` and the matrix they form see the
+    same cells in the same order whatever the loader's shuffling."""
+
+    def __init__(self, loader, device):
+        if loader.batch_size is None:
+            raise ValueError("the loader needs a batch size")
+        self.batch_size = loader.batch_size
+        self._batches = [(x.to(device=device, dtype=torch.float32), i_x) for x, i_x in loader]
+        self.dataset = range(sum(int(x.shape[0]) for x, _ in self._batches))
+
+    def __iter__(self):
+        return iter(self._batches)
+
+    def matrix(self) -> torch.Tensor:
+        return torch.cat([x for x, _ in self._batches])

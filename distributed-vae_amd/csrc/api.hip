@@ -1038,6 +1038,66 @@ int mmvae_silhouette(const float* x_sorted, int64_t ld, int64_t n, int d, const 
     return launch_silhouette(x_sorted, ld, n, d, offsets, K, perm, ws, s, reinterpret_cast<hipStream_t>(stream));
 }
 
+// the most segments and the most workgroups of one grid that mmvae_state_corr launches; false where it refuses the shape
+static bool sc_shape_ok(int64_t n, int D, int S, int G) {
+    if (S > SC_MAX_S) return false;
+    const unsigned __int128 tiles = (unsigned __int128)cdiv64(D, SC_TILE);
+    return (unsigned __int128)sc_nseg_max(n, G) * tiles <= (unsigned __int128)SC_MAX_BLOCKS &&
+           (unsigned __int128)G * (unsigned __int128)cdiv64(D, 256) <= (unsigned __int128)SC_MAX_BLOCKS;
+}
+
+size_t mmvae_state_corr_workspace_bytes(int64_t n, int D, int S, int G) {
+    if (n < 1 || n > ((int64_t)1 << 31) || D < 1 || S < 1 || G < 1 || !sc_shape_ok(n, D, S, G)) return 0;
+    const unsigned __int128 nseg = (unsigned __int128)sc_nseg_max(n, G);
+    const unsigned __int128 bytes = 8 * (nseg * (unsigned __int128)(5 + 5 * S) * (unsigned __int128)D + nseg + 1) +
+                                    4 * (((unsigned __int128)G + 2) / 2 * 2);
+    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
+}
+
+// every argument is checked here, on the host, before any device work.  path: -1 the launcher's rule (the 16-byte loads where
+// the base and the row pitch allow them), 0 the narrow loads, 1 the 16-byte loads
+static int state_corr_checked(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state,
+                              int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
+                              int64_t* count, int path, void* stream) {
+    if (!data || !state || !ws || !r || !count) { set_error("state_corr: null pointer"); return MMVAE_E_BADARG; }
+    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("state_corr: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (n_total < 1) { set_error("state_corr: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
+    if (!rows && n > n_total) { set_error("state_corr: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
+    if (D < 1 || S < 1 || G < 1) { set_error("state_corr: D = %d, S = %d, G = %d: each must be at least 1", D, S, G); return MMVAE_E_BADARG; }
+    if (ld < D) { set_error("state_corr: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
+    if (lds < S) { set_error("state_corr: lds = %lld below S = %d", (long long)lds, S); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("state_corr: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+    if (S > SC_MAX_S) { set_error("state_corr: S = %d above %d", S, SC_MAX_S); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_state_corr_workspace_bytes(n, D, S, G);
+    if (!sc_shape_ok(n, D, S, G) || need == 0) {
+        set_error("state_corr: n = %lld, D = %d, G = %d need a grid of more than %lld workgroups", (long long)n, D, G, (long long)SC_MAX_BLOCKS);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (ws_bytes < need) {
+        set_error("state_corr: workspace of %zu bytes below the %zu needed", ws_bytes, need);
+        return MMVAE_E_WORKSPACE;
+    }
+    if (path < -1 || path > 1) { set_error("state_corr: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
+    if (path == 1 && !sc_wide(data, ld)) {
+        set_error("state_corr: 16-byte loads need a 16-byte aligned base and ld a multiple of 4 (ld = %lld)", (long long)ld);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_state_corr(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, r, count,
+                             path < 0 ? sc_wide(data, ld) : path == 1, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
+                     int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r, int64_t* count,
+                     void* stream) {
+    return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, -1, stream);
+}
+
+int mmvae_debug_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state,
+                           int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
+                           int64_t* count, int path, void* stream) {
+    return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, path, stream);
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

@@ -985,6 +985,15 @@ int64_t sil_nseg_max(int64_t n, int K);
 int sil_dv(int d);
 int launch_silhouette(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
                       double* s, hipStream_t st);
+// state-gene correlation (statecorr.hip)
+constexpr int SC_SEG_ROWS = 256;       // rows per segment at most: a longer group is cut into pieces of this many
+constexpr int SC_TILE = 256;           // genes per workgroup of k_sc_partial: one wave, four consecutive genes a lane
+constexpr int SC_MAX_S = 32;           // the model's limit on state_dim; more passes of 4, 2 or 1 states, not more registers
+constexpr int64_t SC_MAX_BLOCKS = ((int64_t)1 << 31) - 1;              // segments x gene tiles, and groups x gene tiles, one grid each
+int64_t sc_nseg_max(int64_t n, int G);
+bool sc_wide(const float* data, int64_t ld);
+int launch_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
+                      int64_t n, int S, const int64_t* offsets, int G, void* ws, double* r, int64_t* count, bool wide, hipStream_t st);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

@@ -418,6 +418,49 @@ size_t mmvae_silhouette_workspace_bytes(int64_t n, int K);
 int mmvae_silhouette(const float *x_sorted, int64_t ld, int64_t n, int d, const int64_t *offsets, int K,
                      const int64_t *perm /* NULL = identity */, void *ws, size_t ws_bytes, double *s, void *stream);
 
+/* ---- state-gene correlation (mmidas/utils/tree_based_analysis.py: corr_analysis) ----
+ * For every group g of cells, state dimension s and gene d, over the cells i of the group with x_id > 0, c of them:
+ *   r = (sum x s - sum x sum s / c) / sqrt((sum x^2 - (sum x)^2 / c) (sum s^2 - (sum s)^2 / c)), clipped to [-1, 1]
+ *   r = 0 exactly when c <= 4 (the reference's rule; a gene that is zero or negative in every cell has c = 0)
+ *   r = NaN when x or s takes one value over those cells (min == max: scipy.stats.pearsonr's constant-input result)
+ * which is scipy.stats.pearsonr(state[mask, s], cell[mask, d])[0] under the reference's mask and its `> 4` rule.
+ *
+ * mmvae_state_corr: data float32 row-major [n_total, ld], columns 0..D-1 used, read where it lies; rows int64 [n] on the
+ *   device, the row of data of cell r, or NULL for the rows 0..n-1 (then n <= n_total); state float32 [n, lds], columns
+ *   0..S-1 used, row r the state of cell rows[r]; offsets int64 [G + 1] on the device, group g the cells
+ *   offsets[g] .. offsets[g + 1] - 1 (the cells ordered by group), or NULL for one group of all n cells (G = 1).
+ *   r double [G, S, D] and count int64 [G, D] (the c above) on the device.
+ *   The host cannot read device memory without a synchronisation, so offsets that are not non-decreasing from
+ *   offsets[0] = 0 to offsets[G] = n and row indices outside [0, n_total) are the CALLER'S CONTRACT: every index derived
+ *   from them is clamped, so they give wrong values and no access outside the arrays.  An empty group gives r = 0, c = 0.
+ *   INPUTS MUST BE FINITE: a NaN or an infinity in data or state gives NaNs or wrong values (the mask x > 0 drops a NaN
+ *   x, not a NaN state).
+ *   Arithmetic: one pass over the matrix.  Counts are exact.  The five sums are fp64 sums of exact terms (a product of
+ *   two fp32 values is exact in fp64) in row order within a segment, the segments of a group in order; with
+ *   kappa = max over x and s of 1 + mean^2 / variance over the mask, |r - exact r on the same float32 values| <=
+ *   8 (c + 1) kappa 2^-53 as long as that is small against 1 (DESIGN.md section 9e for the derivation).  Minima and
+ *   maxima are exact, so the two special values are exact.
+ *   The rows are cut into segments of at most 256 that never cross a group boundary; a wave owns one segment and 256
+ *   consecutive genes (16-byte loads where data is 16-byte aligned and ld a multiple of 4, else one float at a time: the
+ *   same lane-to-gene map and row order, hence the same bits), S states in passes of 4, 2 or 1; a last launch adds each
+ *   group's segments in order.  No atomics: bit-identical from run to run, and group g's values are bit for bit those
+ *   of a call on its cells alone.
+ *   ws: mmvae_state_corr_workspace_bytes(n, D, S, G) bytes of device memory, 8-byte aligned: with m = G + n / 256 (the
+ *   most segments there can be) m (5 + 5 S) D doubles of partial moments, m + 1 int64 and G + 1 int32 of tables; 0 for
+ *   arguments that mmvae_state_corr refuses, or a size that size_t cannot hold.
+ *   MMVAE_E_BADARG, before any device work, for a null data / state / ws / r / count, n < 1 or n > 2^31, n_total < 1,
+ *   rows NULL with n > n_total, D < 1, S < 1, G < 1, ld < D, lds < S, a misaligned ws; MMVAE_E_UNSUPPORTED for S > 32 or a
+ *   grid (m ceil(D / 256) or G ceil(D / 256) workgroups) of 2^31 or more; MMVAE_E_WORKSPACE for a ws below the size.
+ * mmvae_debug_state_corr: the same with the load form named: path -1 the launcher's rule, 0 the narrow loads (any
+ *   matrix), 1 the 16-byte loads (MMVAE_E_UNSUPPORTED where the base or ld does not allow them); same bits. */
+size_t mmvae_state_corr_workspace_bytes(int64_t n, int D, int S, int G);
+int mmvae_state_corr(const float *data, int64_t ld, int64_t n_total, int D, const int64_t *rows /* NULL = 0..n-1 */,
+                     const float *state, int64_t lds, int64_t n, int S, const int64_t *offsets /* NULL = one group */,
+                     int G, void *ws, size_t ws_bytes, double *r, int64_t *count, void *stream);
+int mmvae_debug_state_corr(const float *data, int64_t ld, int64_t n_total, int D, const int64_t *rows,
+                           const float *state, int64_t lds, int64_t n, int S, const int64_t *offsets, int G, void *ws,
+                           size_t ws_bytes, double *r, int64_t *count, int path, void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
