@@ -83,6 +83,27 @@ struct LatCell {
     static __device__ __forceinline__ int min_i(int v) { return group_min_i<W>(v); }
 };
 
+// Addressing of the latent kernels' per-cell arrays ([A, B, width] floats in the workspace): one wave-uniform base per
+// array AT THE WORKGROUP'S FIRST CELL (a buffer descriptor for loads, a pointer for stores; both from kernel arguments and
+// blockIdx alone, so they are computed on the scalar unit and live in SGPRs) and a 32-bit byte offset per lane -- no 64-bit
+// multiply-add per access.  A workgroup owns at most LAT_ROWS cells of at most 256 floats (check_dims: C + S, L + C <= 255,
+// 2 S <= 64), so a byte offset stays below LAT_BLOCK_BYTES whatever B is and never reaches LAT_OOB, the offset a lane
+// without an element asks for: beyond the descriptor's range, where a buffer load returns 0 and touches no memory.
+// Loads only; stores stay guarded by their predicate.
+constexpr uint32_t LAT_BLOCK_BYTES = (uint32_t)LAT_ROWS * 256u * 4u, LAT_OOB = 0x80000000u;
+static_assert(LAT_ROWS_BWD <= LAT_ROWS && LAT_BLOCK_BYTES < LAT_OOB && (uint64_t)LAT_BLOCK_BYTES + LAT_OOB <= 0xFFFFFFFFull,
+              "32-bit byte offsets within a workgroup's cells");
+// rows x width floats at p
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lat_rsrc(const float* p, int rows, int width) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, rows * width * 4, 0x00020000);
+}
+__device__ __forceinline__ float lat_ld(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off) {
+    return __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)byte_off, 0, 0));
+}
+__device__ __forceinline__ void lat_st(float* base, uint32_t byte_off, float v) {
+    *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
+}
+
 // Stages fcc (transposed to [L][C]) and the state-head weights in LDS once per workgroup.
 __device__ __forceinline__ void lat_stage_weights(float* WcT, float* Wm, const float* __restrict__ Wc,
                                                   const float* __restrict__ Wms, int L, int C, int S) {
@@ -131,22 +152,38 @@ __global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const
     float* WcT = lat_smem;            // [L][C]
     float* Wms = lat_smem + C * L;    // [2S][L+C]
     const int64_t ab = (int64_t)arm * B;
+    const int64_t ab0 = ab + b0;                 // the workgroup's first cell (lat_ld / lat_st above)
+    const int nrows = min(LAT_ROWS, B - b0);     // its cells within the batch
     const float eps = a.eps;
 
     int slot[NR], bb[NR];
     bool okr[NR];
     float r5[NR];
+    {
+        const auto rR5 = lat_rsrc(ws + a.R5 + ab0 * L, nrows, L);
+        const uint32_t lob = sub < L ? (uint32_t)sub * 4u : LAT_OOB;
 #pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        slot[r] = r * (NW * CPW) + wv * CPW + cell;
-        bb[r] = b0 + slot[r];
-        okr[r] = bb[r] < B;                   // per cell
-        r5[r] = sub < L ? ws[a.R5 + (ab + min(bb[r], B - 1)) * L + sub] : 0.f;
+        for (int r = 0; r < NR; ++r) {
+            slot[r] = r * (NW * CPW) + wv * CPW + cell;
+            bb[r] = b0 + slot[r];
+            okr[r] = bb[r] < B;                   // per cell
+            r5[r] = lat_ld(rR5, (uint32_t)min(slot[r], nrows - 1) * (uint32_t)L * 4u + lob);   // beyond the batch: the last cell's
+        }
     }
     bool vcol[CP];
     float bcv[CP];
+    {
+        const auto rBC = lat_rsrc(P + a.o_bc, 1, C);
 #pragma unroll
-    for (int t = 0; t < CP; ++t) { vcol[t] = sub + W * t < C; bcv[t] = vcol[t] ? P[a.o_bc + sub + W * t] : 0.f; }
+        for (int t = 0; t < CP; ++t) {
+            vcol[t] = sub + W * t < C;
+            bcv[t] = lat_ld(rBC, vcol[t] ? (uint32_t)(sub + W * t) * 4u : LAT_OOB);
+        }
+    }
+    // stores: the workgroup's first row of every array + a 32-bit byte offset
+    float* const pXLOW = ws + a.XLOW + ab0 * L;
+    float* const pY = ws + a.Y + ab0 * (L + C);
+    float* const pZIN = ws + a.ZIN + ab0 * (C + S);
     lat_stage_weights(WcT, Wms, P + a.o_wc, P + a.o_wms, L, C, S);
     const float* bms = P + a.o_bms;
 
@@ -187,8 +224,8 @@ __global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const
     for (int r = 0; r < NR; ++r) {
         xl[r] = sub < L ? (r5[r] - mu5) * rs5 : 0.f;
         if (okr[r] && sub < L) {
-            ws[a.XLOW + (ab + bb[r]) * L + sub] = xl[r];
-            ws[a.Y + (ab + bb[r]) * (L + C) + sub] = xl[r];
+            lat_st(pXLOW, ((uint32_t)slot[r] * (uint32_t)L + (uint32_t)sub) * 4u, xl[r]);
+            lat_st(pY, ((uint32_t)slot[r] * (uint32_t)(L + C) + (uint32_t)sub) * 4u, xl[r]);
             if constexpr (ENC != 0)
                 if (eo.x_low) eo.x_low[((int64_t)arm * eo.rows + eo.row0 + bb[r]) * L + sub] = xl[r];
         }
@@ -309,6 +346,10 @@ __global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const
     }
     // ---- store; c goes to the workgroup tile for the block statistics (zero rows beyond the batch)
     float kl_acc = 0.f, ent_acc = 0.f;
+    float* const pCPROB = ws + a.CPROB + ab0 * C;
+    float* const pCC = ws + a.CC + ab0 * C;
+    float* const pYSOFT = ws + a.YSOFT + ab0 * C;
+    float* const pCSMP = ws + a.CSMP + ab0 * C;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
 #pragma unroll
@@ -316,13 +357,13 @@ __global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const
             const int col = sub + W * t;
             sh_buf[slot[r] * 128 + col] = (okr[r] && vcol[t]) ? cc[r][t] : 0.f;
             if (okr[r] && vcol[t]) {
-                const int64_t o = (ab + bb[r]) * C + col;
-                ws[a.CPROB + o] = cp[r][t];
-                ws[a.CC + o] = cc[r][t];
-                ws[a.YSOFT + o] = ys[r][t];
-                ws[a.CSMP + o] = cs[r][t];
-                ws[a.Y + (ab + bb[r]) * (L + C) + L + col] = cs[r][t];
-                ws[a.ZIN + (ab + bb[r]) * (C + S) + col] = cs[r][t];
+                const uint32_t o = ((uint32_t)slot[r] * (uint32_t)C + (uint32_t)col) * 4u;
+                lat_st(pCPROB, o, cp[r][t]);
+                lat_st(pCC, o, cc[r][t]);
+                lat_st(pYSOFT, o, ys[r][t]);
+                lat_st(pCSMP, o, cs[r][t]);
+                lat_st(pY, ((uint32_t)slot[r] * (uint32_t)(L + C) + (uint32_t)(L + col)) * 4u, cs[r][t]);
+                lat_st(pZIN, ((uint32_t)slot[r] * (uint32_t)(C + S) + (uint32_t)col) * 4u, cs[r][t]);
                 if constexpr (ENC == 1) {
                     const int64_t eo_o = ((int64_t)arm * eo.rows + eo.row0 + bb[r]) * C + col;
                     if (eo.c_prob) eo.c_prob[eo_o] = cp[r][t];
@@ -356,9 +397,13 @@ __global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const
             if (sub == o) mso[r] = pv;
         }
     }
+    float* const pMS = ws + a.MS + ab0 * 2 * S;
+    float* const pMU = ws + a.MU + ab0 * S;
+    float* const pLV = ws + a.LV + ab0 * S;
+    float* const pSS = ws + a.SS + ab0 * S;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        if (okr[r] && sub < 2 * S) ws[a.MS + (ab + bb[r]) * 2 * S + sub] = mso[r];
+        if (okr[r] && sub < 2 * S) lat_st(pMS, ((uint32_t)slot[r] * (uint32_t)(2 * S) + (uint32_t)sub) * 4u, mso[r]);
         const float sg = __shfl(mso[r], base + ((sub + S) & (W - 1)), 64);
         if (okr[r] && sub < S) {
             const int b = bb[r];
@@ -370,10 +415,11 @@ __global__ __launch_bounds__(64 * NW) void k_lat_fwd_g(const LatArgs a_in, const
             const float sv = U * sd + mu;
             float sin_ = sv;
             if (a.training && a.s_drop > 0.f) sin_ = state_keep(nz, arm, B, S, b, sub) ? sv / (1.f - a.s_drop) : 0.f;
-            ws[a.MU + (ab + b) * S + sub] = mu;
-            ws[a.LV + (ab + b) * S + sub] = lv;
-            ws[a.SS + (ab + b) * S + sub] = sv;
-            ws[a.ZIN + (ab + b) * (C + S) + C + sub] = sin_;
+            const uint32_t so = ((uint32_t)slot[r] * (uint32_t)S + (uint32_t)sub) * 4u;
+            lat_st(pMU, so, mu);
+            lat_st(pLV, so, lv);
+            lat_st(pSS, so, sv);
+            lat_st(pZIN, ((uint32_t)slot[r] * (uint32_t)(C + S) + (uint32_t)(C + sub)) * 4u, sin_);
             if constexpr (ENC == 1) {
                 const int64_t eo_o = ((int64_t)arm * eo.rows + eo.row0 + b) * S + sub;
                 if (eo.s_mean) eo.s_mean[eo_o] = mu;

@@ -167,12 +167,16 @@ __global__ __launch_bounds__(256) void k_loss_finalize(int A, int B, int D, int 
 // ---------------------------------------------------------------------------------------------
 // backward of the latent block.  grid (ceil(B/LAT_ROWS_BWD), A), 64 NW threads, the geometries of the forward (LatCell).
 // ---------------------------------------------------------------------------------------------
-template <int W, int NW>
+// AT: the number of arms, a template parameter as k_couple's: the per-arm registers (call, ivall) are AT deep, not
+// MMVAE_MAX_ARMS, and no arm loop is predicated.  Every per-cell load goes through lat_ld (lat_fwd.hpp): a lane without an
+// element (column >= C, sub >= S / L) reads 0 without a branch.
+template <int W, int NW, int AT>
 __global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const NoiseDev nz_in, const float* __restrict__ params,
                                                       float* __restrict__ ws) {
     using Cell = LatCell<W>;
     constexpr int CPW = Cell::CPW, CP = Cell::CP, NR = LAT_ROWS_BWD / (NW * CPW);
     static_assert(NR * NW * CPW == LAT_ROWS_BWD, "cells per workgroup");
+    static_assert(AT >= 1 && AT <= MMVAE_MAX_ARMS, "arms");
     const LatArgs a = a_in;
     const NoiseDev nz = nz_in;
     extern __shared__ __attribute__((aligned(16))) float lat_smem[];
@@ -180,65 +184,88 @@ __global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const
     const int arm = blockIdx.y, blk = blockIdx.x, b0 = blk * LAT_ROWS_BWD;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int sub = Cell::sub(lane), base = Cell::base(lane), cell = Cell::cell(lane);
-    const int A = a.A, B = a.B, L = a.L, C = a.C, S = a.S;
+    constexpr int A = AT;
+    const int B = a.B, L = a.L, C = a.C, S = a.S;
     const float* P = params + (int64_t)arm * a.per_arm;
     float* WcT = lat_smem;            // [L][C]
     float* Wms = lat_smem + C * L;    // [2S][L+C]
     lat_stage_weights(WcT, Wms, P + a.o_wc, P + a.o_wms, L, C, S);
-    const int64_t ab = (int64_t)arm * B;
+    const int64_t ab0 = (int64_t)arm * B + b0;       // the workgroup's first cell
+    const int nrows = min(LAT_ROWS_BWD, B - b0);     // its cells within the batch
     const float eps = a.eps, invB = 1.f / (float)B;
     const float coefG = 2.f * a.lam * invB;
 
     bool vcol[CP];
-    float Tk[CP], cmean[CP], ivm[CP], ivall[MMVAE_MAX_ARMS][CP];
+    uint32_t cob[CP];   // byte offset of column `sub + W t` within a row; LAT_OOB beyond C
+    int colw[CP];       // the column whose staged weights the lane reads: its own, or column 0 beyond C (a finite weight
+                        // that meets an exact 0 there, or feeds a value nothing reads) -- no branch around the LDS reads
+    float Tk[CP], cmean[CP], ivm[CP], ivall[AT][CP];
+    {
+        const auto rT = lat_rsrc(ws + a.T, A, C), rM = lat_rsrc(ws + a.c_mean, A, C), rV = lat_rsrc(ws + a.c_iv, A, C);
 #pragma unroll
-    for (int t = 0; t < CP; ++t) {
-        const int col = sub + W * t;
-        vcol[t] = col < C;
-        Tk[t] = vcol[t] ? ws[a.T + arm * C + col] : 0.f;
-        if (a.acc_T >= 0 && vcol[t]) {
-            double s1, s2;
-            acc_get(reinterpret_cast<const long long*>(ws + a.acc_T) + (int64_t)arm * ACC_SET_I64, col, s1, s2);
-            Tk[t] = (float)s1;
+        for (int t = 0; t < CP; ++t) {
+            const int col = sub + W * t;
+            vcol[t] = col < C;
+            cob[t] = vcol[t] ? (uint32_t)col * 4u : LAT_OOB;
+            colw[t] = vcol[t] ? col : 0;
+            Tk[t] = lat_ld(rT, (uint32_t)(arm * C) * 4u + cob[t]);
+            if (a.acc_T >= 0 && vcol[t]) {
+                double s1, s2;
+                acc_get(reinterpret_cast<const long long*>(ws + a.acc_T) + (int64_t)arm * ACC_SET_I64, col, s1, s2);
+                Tk[t] = (float)s1;
+            }
+            cmean[t] = lat_ld(rM, (uint32_t)(arm * C) * 4u + cob[t]);
+            ivm[t] = lat_ld(rV, (uint32_t)(arm * C) * 4u + cob[t]);
+#pragma unroll
+            for (int aa = 0; aa < AT; ++aa) ivall[aa][t] = lat_ld(rV, (uint32_t)(aa * C) * 4u + cob[t]);
         }
-        cmean[t] = vcol[t] ? ws[a.c_mean + arm * C + col] : 0.f;
-        ivm[t] = vcol[t] ? ws[a.c_iv + arm * C + col] : 0.f;
-#pragma unroll
-        for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa) ivall[aa][t] = (aa < A && vcol[t]) ? ws[a.c_iv + aa * C + col] : 0.f;
     }
     float s1 = 0.f, s2 = 0.f;   // BN5 backward sums for column `sub` (< L), this lane group's cells
 
     int bb[NR];
     bool okr[NR];
     float gs_l[NR], mu_l[NR], lv_l[NR], sg_l[NR], xlow_l[NR];
-    float cc[NR][CP], ys[NR][CP], gz[NR][CP], cp[NR][CP], call[NR][MMVAE_MAX_ARMS][CP];
+    float cc[NR][CP], ys[NR][CP], gz[NR][CP], cp[NR][CP], call[NR][AT][CP];
+    {
+        const auto rGZ = lat_rsrc(ws + a.GZIN + ab0 * (C + S), nrows, C + S), rMU = lat_rsrc(ws + a.MU + ab0 * S, nrows, S),
+                   rLV = lat_rsrc(ws + a.LV + ab0 * S, nrows, S), rMS = lat_rsrc(ws + a.MS + ab0 * 2 * S, nrows, 2 * S),
+                   rXL = lat_rsrc(ws + a.XLOW + ab0 * L, nrows, L), rYS = lat_rsrc(ws + a.YSOFT + ab0 * C, nrows, C),
+                   rCP = lat_rsrc(ws + a.CPROB + ab0 * C, nrows, C), rCC = lat_rsrc(ws + a.CC + ab0 * C, nrows, C);
+        const uint32_t sob = sub < S ? (uint32_t)sub * 4u : LAT_OOB, lob = sub < L ? (uint32_t)sub * 4u : LAT_OOB;
 #pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        bb[r] = b0 + r * (NW * CPW) + wv * CPW + cell;
-        okr[r] = bb[r] < B;                         // per cell
-        const int64_t b = min(bb[r], B - 1);        // cells beyond the batch recompute the last cell; nothing is stored
-        gs_l[r] = sub < S ? ws[a.GZIN + (ab + b) * (C + S) + C + sub] : 0.f;
-        mu_l[r] = sub < S ? ws[a.MU + (ab + b) * S + sub] : 0.f;
-        lv_l[r] = sub < S ? ws[a.LV + (ab + b) * S + sub] : 0.f;
-        sg_l[r] = sub < S ? ws[a.MS + (ab + b) * 2 * S + S + sub] : 0.f;
-        xlow_l[r] = sub < L ? ws[a.XLOW + (ab + b) * L + sub] : 0.f;
+        for (int r = 0; r < NR; ++r) {
+            bb[r] = b0 + r * (NW * CPW) + wv * CPW + cell;
+            okr[r] = bb[r] < B;                                     // per cell
+            const uint32_t rl = (uint32_t)(min(bb[r], B - 1) - b0);   // cells beyond the batch recompute the last cell; nothing is stored
+            gs_l[r] = lat_ld(rGZ, (rl * (uint32_t)(C + S) + (uint32_t)C) * 4u + sob);
+            mu_l[r] = lat_ld(rMU, rl * (uint32_t)S * 4u + sob);
+            lv_l[r] = lat_ld(rLV, rl * (uint32_t)S * 4u + sob);
+            sg_l[r] = lat_ld(rMS, (rl * (uint32_t)(2 * S) + (uint32_t)S) * 4u + sob);
+            xlow_l[r] = lat_ld(rXL, rl * (uint32_t)L * 4u + lob);
 #pragma unroll
-        for (int t = 0; t < CP; ++t) {
-            const int col = sub + W * t;
-            const int64_t o = (ab + b) * C + col;
-            cc[r][t] = vcol[t] ? ws[a.CC + o] : 0.f;
-            ys[r][t] = vcol[t] ? ws[a.YSOFT + o] : 0.f;
-            cp[r][t] = vcol[t] ? ws[a.CPROB + o] : 0.f;
-            gz[r][t] = vcol[t] ? ws[a.GZIN + (ab + b) * (C + S) + col] : 0.f;
+            for (int t = 0; t < CP; ++t) {
+                const uint32_t o = rl * (uint32_t)C * 4u + cob[t];
+                cc[r][t] = lat_ld(rCC, o);
+                ys[r][t] = lat_ld(rYS, o);
+                cp[r][t] = lat_ld(rCP, o);
+                gz[r][t] = lat_ld(rGZ, rl * (uint32_t)(C + S) * 4u + cob[t]);
+            }
 #pragma unroll
-            for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa)
-                call[r][aa][t] = (aa < A && vcol[t]) ? ws[a.CC + ((int64_t)aa * B + b) * C + col] : 1.f;
+            for (int aa = 0; aa < AT; ++aa) {   // c of every arm at this cell
+                const auto rCa = lat_rsrc(ws + a.CC + ((int64_t)aa * B + b0) * C, nrows, C);
+#pragma unroll
+                for (int t = 0; t < CP; ++t) call[r][aa][t] = lat_ld(rCa, rl * (uint32_t)C * 4u + cob[t]);
+            }
         }
     }
     const float inv_temp = 1.f / a.temp, inv_tau = 1.f / a.tau, inv_bm1 = 1.f / (float)(B - 1);
+    float* const pGMS = ws + a.GMS + ab0 * 2 * S;   // stores: the workgroup's first row + a 32-bit byte offset
+    float* const pGZC = ws + a.GZC + ab0 * C;
+    float* const pG5 = ws + a.G5 + ab0 * L;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const int b = min(bb[r], B - 1);
+        const uint32_t rl = (uint32_t)(b - b0);
         // ---- state head backward (lanes sub < S of each cell)
         float gms = 0.f;   // sub = o < 2S: d loss / d MS[o]
         {
@@ -259,18 +286,19 @@ __global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const
             const float gsig_sh = __shfl(gsig, base + ((sub - S) & (W - 1)), 64);   // sub S+s takes sub s's gsig
             if (sub < S) gms = gmu;
             else if (sub < 2 * S) gms = gsig_sh;
-            if (okr[r] && sub < 2 * S) ws[a.GMS + (ab + b) * 2 * S + sub] = gms;
+            if (okr[r] && sub < 2 * S) lat_st(pGMS, (rl * (uint32_t)(2 * S) + (uint32_t)sub) * 4u, gms);
         }
         // ---- gy = gms [Wmu; Wsigma]
         float gxl = 0.f, gcs[CP];
+        const int subl = sub < L ? sub : 0;
 #pragma unroll
         for (int t = 0; t < CP; ++t) gcs[t] = 0.f;
         for (int o = 0; o < 2 * S; ++o) {
             const float go = __shfl(gms, base + o, 64);
             const float* w = Wms + (int64_t)o * (L + C);
-            if (sub < L) gxl += go * w[sub];
+            gxl += go * w[subl];                                               // (lanes sub >= L: read by nothing)
 #pragma unroll
-            for (int t = 0; t < CP; ++t) if (vcol[t]) gcs[t] += go * w[L + sub + W * t];
+            for (int t = 0; t < CP; ++t) gcs[t] += go * w[L + colw[t]];       // (columns >= C: dropped below)
         }
         // ---- gradient w.r.t. the sample, through the Gumbel softmax to c
         float lc[CP], gc[CP], usum[CP], rcc[CP];
@@ -283,12 +311,13 @@ __global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const
                 gcs[t] += gz[r][t];
                 dot += ys[r][t] * gcs[t];
 #pragma unroll
-                for (int aa = 0; aa < MMVAE_MAX_ARMS; ++aa)
-                    if (aa < A) {
-                        const float l_aa = logf(call[r][aa][t] + eps);
-                        usum[t] += l_aa * ivall[aa][t];
-                        if (aa == arm) lc[t] = l_aa;
-                    }
+                for (int aa = 0; aa < AT; ++aa) {
+                    const float l_aa = logf(call[r][aa][t] + eps);
+                    usum[t] = __builtin_fmaf(l_aa, ivall[aa][t], usum[t]);   // fused, as the per-arm blocks of the run-time arm
+                                                                              // count compiled (packed across arms the products
+                                                                              // would round on their own)
+                    if (aa == arm) lc[t] = l_aa;
+                }
             }
         }
         if (a.eval_flag) {
@@ -326,19 +355,19 @@ __global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const
 #pragma unroll
         for (int t = 0; t < CP; ++t) {
             gzc[t] = cp[r][t] * (gq[t] - dot3);
-            if (okr[r] && vcol[t]) ws[a.GZC + (ab + b) * C + sub + W * t] = gzc[t];
+            if (okr[r] && vcol[t]) lat_st(pGZC, (rl * (uint32_t)C + (uint32_t)(sub + W * t)) * 4u, gzc[t]);
         }
         // ---- g5 = gy[:, :L] + gzc Wc
         float g5 = 0.f;
         for (int k = 0; k < L; ++k) {
             float p = 0.f;
 #pragma unroll
-            for (int t = 0; t < CP; ++t) if (vcol[t]) p += gzc[t] * WcT[k * C + sub + W * t];
+            for (int t = 0; t < CP; ++t) p = __builtin_fmaf(gzc[t], WcT[k * C + colw[t]], p);   // columns >= C: gzc = cp (..) = 0 exactly
             p = Cell::sum(p);
             if (sub == k) g5 = gxl + p;
         }
         if (okr[r] && sub < L) {
-            ws[a.G5 + (ab + b) * L + sub] = g5;
+            lat_st(pG5, (rl * (uint32_t)L + (uint32_t)sub) * 4u, g5);
             s1 += g5;
             s2 += g5 * xlow_l[r];
         }
@@ -366,7 +395,6 @@ __global__ __launch_bounds__(64 * NW) void k_lat_bwd_g(const LatArgs a_in, const
         }
     }
 }
-constexpr auto k_lat_bwd = k_lat_bwd_g<64, LATB_NW>, k_lat_bwd_h = k_lat_bwd_g<32, LBH_NW>;
 
 // ---------------------------------------------------------------------------------------------
 // slabs -> flat gradient buffer
@@ -639,13 +667,27 @@ int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params) {
     LatArgs a = make_lat_args(c);
     NoiseDev nd = make_noise_dev(nz, c.h);
     const size_t shm = lat_smem_bytes(c.d);
-    if (c.plan.lat_half) {
-        hipLaunchKernelGGL(k_lat_bwd_h, dim3(cdiv(c.d.B, LAT_ROWS_BWD), c.d.A), dim3(64 * LBH_NW), shm, c.stream, a, nd, params, c.ws);
-        HIP_LAUNCH_CHECK("k_lat_bwd_h");
-        return 0;
+    const dim3 grid(cdiv(c.d.B, LAT_ROWS_BWD), c.d.A);
+    // k_lat_bwd_h: the half-wave form, k_lat_bwd: the wave form; the arm count is a template parameter (check_dims: 1 .. 8)
+#define MMVAE_LAT_BWD(AT)                                                                                                  \
+    if (c.plan.lat_half)                                                                                                   \
+        hipLaunchKernelGGL((k_lat_bwd_g<32, LBH_NW, AT>), grid, dim3(64 * LBH_NW), shm, c.stream, a, nd, params, c.ws);    \
+    else                                                                                                                   \
+        hipLaunchKernelGGL((k_lat_bwd_g<64, LATB_NW, AT>), grid, dim3(64 * LATB_NW), shm, c.stream, a, nd, params, c.ws)
+    static_assert(MMVAE_MAX_ARMS == 8, "one case per arm count");
+    switch (c.d.A) {
+        case 1: MMVAE_LAT_BWD(1); break;
+        case 2: MMVAE_LAT_BWD(2); break;
+        case 3: MMVAE_LAT_BWD(3); break;
+        case 4: MMVAE_LAT_BWD(4); break;
+        case 5: MMVAE_LAT_BWD(5); break;
+        case 6: MMVAE_LAT_BWD(6); break;
+        case 7: MMVAE_LAT_BWD(7); break;
+        case 8: MMVAE_LAT_BWD(8); break;
+        default: set_error("k_lat_bwd: A = %d outside [1, %d]", c.d.A, MMVAE_MAX_ARMS); return MMVAE_E_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(k_lat_bwd, dim3(cdiv(c.d.B, LAT_ROWS_BWD), c.d.A), dim3(64 * LATB_NW), shm, c.stream, a, nd, params, c.ws);
-    HIP_LAUNCH_CHECK("k_lat_bwd");
+#undef MMVAE_LAT_BWD
+    HIP_LAUNCH_CHECK(c.plan.lat_half ? "k_lat_bwd_h" : "k_lat_bwd");
     return 0;
 }
 
