@@ -57,6 +57,57 @@ struct ChainFwdArgs {
     int64_t per_arm;
 };
 
+// Addressing of the chains' per-cell arrays ([A, B, width] floats in the workspace), as in the latent kernels (lat_fwd.hpp):
+// one buffer descriptor per array AT THE WORKGROUP'S FIRST ROW, built from kernel arguments and blockIdx alone (scalar unit,
+// SGPRs), covering the workgroup's valid rows only, and a 32-bit byte offset per lane -- no 64-bit multiply-add per access.
+// A workgroup owns at most CHAIN_ROWS rows of at most 256 floats (check_dims: every chain width <= 255), so the offset of an
+// element stays below CH_BLOCK_BYTES whatever B is; a row past the block's valid rows lies beyond the descriptor's range by
+// itself, and a lane without a column asks for CH_OOB (+ its row term, still out of range): the load returns 0 and
+// touches no memory, the store is dropped.  No branch, no zeroing move, no select on the value.  The whole offset is
+// the per-lane one: the range check does not see a scalar offset.
+typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4c __attribute__((ext_vector_type(4)));
+constexpr uint32_t CH_BLOCK_BYTES = (uint32_t)CHAIN_ROWS * 256u * 4u, CH_OOB = 0x80000000u;
+static_assert(CH_BLOCK_BYTES < CH_OOB && (uint64_t)CH_BLOCK_BYTES + CH_OOB <= 0xFFFFFFFFull,
+              "32-bit byte offsets within a workgroup's rows");
+// rows x width floats at p (no rows: every access is out of range)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ch_rsrc(const float* p, int rows, int width) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, max(rows, 0) * width * 4, 0x00020000);
+}
+__device__ __forceinline__ float ch_ld(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off) {
+    return __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)byte_off, 0, 0));
+}
+__device__ __forceinline__ void ch_st(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), rs, (int)byte_off, 0, 0);
+}
+// [1 x 4] of a row-major array behind a descriptor: columns col .. col + 3 of the row at byte offset row_off, zero outside
+// the descriptor's rows and beyond Cn columns (ldg4_t's values, without its clamps and selects).  VEC: Cn % 4 == 0,
+// col % 4 == 0, rows 16-byte aligned.
+template <bool VEC>
+__device__ __forceinline__ float4 ch_ld4(__amdgpu_buffer_rsrc_t rs, uint32_t row_off, int col, int Cn) {
+    const uint32_t o = row_off + (uint32_t)col * 4u;
+    if (VEC) return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(col < Cn ? o : CH_OOB), 0, 0));
+    float4 v;
+    v.x = ch_ld(rs, col < Cn ? o : CH_OOB);
+    v.y = ch_ld(rs, col + 1 < Cn ? o + 4u : CH_OOB);
+    v.z = ch_ld(rs, col + 2 < Cn ? o + 8u : CH_OOB);
+    v.w = ch_ld(rs, col + 3 < Cn ? o + 12u : CH_OOB);
+    return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void ch_st4(__amdgpu_buffer_rsrc_t rs, uint32_t row_off, int col, int Cn, float4 v) {
+    const uint32_t o = row_off + (uint32_t)col * 4u;
+    if (VEC) {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4c, v), rs, (int)(col < Cn ? o : CH_OOB), 0, 0);
+        return;
+    }
+    ch_st(rs, col < Cn ? o : CH_OOB, v.x);
+    ch_st(rs, col + 1 < Cn ? o + 4u : CH_OOB, v.y);
+    ch_st(rs, col + 2 < Cn ? o + 8u : CH_OOB, v.z);
+    ch_st(rs, col + 3 < Cn ? o + 12u : CH_OOB, v.w);
+}
+
 // stage W [N][K] (global, row-major) into LDS rows [0, rows_pad) x cols [0, cols_pad), zero padded.
 // 8 threads per row (128-B segments), 128 rows per pass, four chunks in flight per thread, no per-element
 // branches: all loads of a pass issue before the first LDS store waits.
@@ -86,7 +137,7 @@ __device__ __forceinline__ void stage_w(float* Ws, int ld, const float* __restri
 }
 
 // Split form of stage_w for weights with K % 4 == 0 and a padded tile of at most 128 x 128: w_load only REQUESTS
-// the tile (raw clamped loads, nothing touches the values), w_store masks it and writes it to LDS later.  The
+// the tile (buffer loads that return 0 outside [N][K], nothing touches the values), w_store writes it to LDS later.  The
 // request for layer l+1 is issued before layer l's GEMM and lands under the GEMM and the epilogue, so a chain
 // pays the weight latency once instead of once per layer.
 constexpr int WQ_N = 4 * (128 / (CH_NT / 8));   // float4 per thread: 128 rows / (threads / 8 per row) passes x 4 chunks
@@ -95,14 +146,12 @@ __device__ __forceinline__ bool w_split_ok(const float* W, int K, int rows_pad, 
 }
 __device__ __forceinline__ void w_load(float4 (&wq)[WQ_N], const float* __restrict__ W, int N, int K) {
     const int part = threadIdx.x & 7, r0 = threadIdx.x >> 3;
+    const auto rW = ch_rsrc(W, N, K);      // at most 128 x 128 floats (w_split_ok); a row past N is out of range by itself
 #pragma unroll
     for (int p = 0; p < WQ_N / 4; ++p)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = r0 + (CH_NT / 8) * p, col = (part + 8 * j) * 4;
-            const bool ok = row < N && col < K;
-            wq[p * 4 + j] = *reinterpret_cast<const float4*>(W + (int64_t)(ok ? row : 0) * K + (ok ? col : 0));
-        }
+        for (int j = 0; j < 4; ++j)
+            wq[p * 4 + j] = ch_ld4<true>(rW, (uint32_t)((r0 + (CH_NT / 8) * p) * K) * 4u, (part + 8 * j) * 4, K);
 }
 __device__ __forceinline__ void w_store(float* Ws, int ld, const float4 (&wq)[WQ_N], int N, int K, int rows_pad, int cols_pad) {
     const int part = threadIdx.x & 7, r0 = threadIdx.x >> 3, c4n = cols_pad >> 2;
@@ -111,10 +160,7 @@ __device__ __forceinline__ void w_store(float* Ws, int ld, const float4 (&wq)[WQ
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int row = r0 + (CH_NT / 8) * p, c = part + 8 * j;
-            const bool ok = row < N && c * 4 < K;
-            const float4 q = wq[p * 4 + j];
-            const float4 v = make_float4(ok ? q.x : 0.f, ok ? q.y : 0.f, ok ? q.z : 0.f, ok ? q.w : 0.f);
-            if (c < c4n && row < rows_pad) *reinterpret_cast<float4*>(&Ws[row * ld + c * 4]) = v;
+            if (c < c4n && row < rows_pad) *reinterpret_cast<float4*>(&Ws[row * ld + c * 4]) = wq[p * 4 + j];   // (zero outside [N][K])
         }
 }
 
@@ -125,20 +171,22 @@ __device__ __forceinline__ void w_store(float* Ws, int ld, const float4 (&wq)[WQ
 // v_mfma_f32_32x32x16_bf16 per 16 k -- 42 matrix instructions of 32 cycles instead of 52 of 64, with fp32-grade results.
 // The weights come as planes from the step's k_presplit launch (Layout::pl_small: [A][slot][3][128][128] bf16, zero
 // outside [N][K]); the activations are split where they are written to LDS (input tile, epilogue).
-typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4c __attribute__((ext_vector_type(4)));
 constexpr int PLS = 128 * 128;                     // bf16 elements of one global weight plane
 constexpr int WP_N = 3 * ((128 * 16) / CH_NT);     // uint4 per thread: 3 planes x 128 rows x 16 sixteen-byte slots
+// Thread t takes the sixteen-byte slots t, t + CH_NT, .. of each plane (row = slot >> 4, k chunk = slot & 15).  One descriptor
+// over the three planes, the plane and the pass in the scalar offset, and per pass one lane offset: the slot's, or CH_OOB for a
+// slot outside [N][K], which fetches nothing (wp_store does not write it either) -- a launch takes in N x K of the 128 x 128.
 __device__ __forceinline__ void wp_load(u32x4c (&wq)[WP_N], const unsigned short* __restrict__ Wg, int N, int K) {
+    const auto rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Wg), 0, 3 * PLS * 2, 0x00020000);
     const int kc_n = rup(K, 16) >> 3;
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
+    for (int i = 0; i < WP_N / 3; ++i) {
+        const int idx = threadIdx.x + CH_NT * i, row = idx >> 4, kc = idx & 15;
+        const uint32_t off = (row < N && kc < kc_n) ? threadIdx.x * 16u : CH_OOB;
 #pragma unroll
-        for (int i = 0; i < WP_N / 3; ++i) {
-            const int idx = threadIdx.x + CH_NT * i, row = idx >> 4, kc = idx & 15;
-            const bool ok = row < N && kc < kc_n;
-            wq[pl * (WP_N / 3) + i] = *reinterpret_cast<const u32x4c*>(Wg + pl * PLS + (ok ? row : 0) * 128 + (ok ? kc : 0) * 8);
-        }
+        for (int pl = 0; pl < 3; ++pl)
+            wq[pl * (WP_N / 3) + i] = __builtin_bit_cast(u32x4c, __builtin_amdgcn_raw_buffer_load_b128(rW, (int)off, (pl * PLS + CH_NT * i * 8) * 2, 0));
+    }
 }
 __device__ __forceinline__ void wp_store(unsigned* Wp, int wpl, int ldp, const u32x4c (&wq)[WP_N], int N, int K) {
     const int kc_n = rup(K, 16) >> 3;
@@ -151,35 +199,40 @@ __device__ __forceinline__ void wp_store(unsigned* Wp, int wpl, int ldp, const u
         }
 }
 // acc[32 x 32] += A[a_row0 + .][k] * B[b_row0 + .][k] over ksteps x 16 k, operands as three planes each (plane strides
-// xpl / wpl dwords); the fragments of step s + 1 are requested before the MFMAs of step s
+// xpl / wpl dwords); the fragments of step s + 1 are requested before the MFMAs of step s.  Two steps per trip through the
+// loop, on two sets of fragment registers: one set handed to the next trip costs 24 register moves per step, issued
+// between the MFMAs of a loop whose trip count the compiler does not know.
+struct FragX3 { bf16x8c a[3], b[3]; };
+__device__ __forceinline__ void frag_x3(FragX3& f, const unsigned* pa, int xpl, const unsigned* pb, int wpl, int st) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        f.a[pl] = __builtin_bit_cast(bf16x8c, *reinterpret_cast<const u32x4c*>(pa + pl * xpl + 8 * st));
+        f.b[pl] = __builtin_bit_cast(bf16x8c, *reinterpret_cast<const u32x4c*>(pb + pl * wpl + 8 * st));
+    }
+}
+__device__ __forceinline__ void mfma6_x3(f32x16& acc, const FragX3& f) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[2], f.b[0], acc, 0, 0, 0);   // smallest terms first
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0], f.b[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1], f.b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1], f.b[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0], f.b[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0], f.b[0], acc, 0, 0, 0);
+}
 __device__ __forceinline__ void mma_nt_x3(f32x16& acc, const unsigned* Xp, int xpl, const unsigned* Wp, int wpl, int ldp,
                                           int a_row0, int b_row0, int ksteps) {
     const int lane = lane_id();
     const unsigned* pa = Xp + (a_row0 + (lane & 31)) * ldp + 4 * (lane >> 5);
     const unsigned* pb = Wp + (b_row0 + (lane & 31)) * ldp + 4 * (lane >> 5);
-    bf16x8c a[3], b[3];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-        a[pl] = __builtin_bit_cast(bf16x8c, *reinterpret_cast<const u32x4c*>(pa + pl * xpl));
-        b[pl] = __builtin_bit_cast(bf16x8c, *reinterpret_cast<const u32x4c*>(pb + pl * wpl));
+    FragX3 f0, f1;
+    frag_x3(f0, pa, xpl, pb, wpl, 0);
+    int st = 0;
+    for (; st + 1 < ksteps; st += 2) {
+        frag_x3(f1, pa, xpl, pb, wpl, st + 1);
+        mfma6_x3(acc, f0);
+        frag_x3(f0, pa, xpl, pb, wpl, min(st + 2, ksteps - 1));
+        mfma6_x3(acc, f1);
     }
-    for (int st = 0; st < ksteps; ++st) {
-        const int sn = (st + 1 < ksteps) ? st + 1 : st;
-        bf16x8c an[3], bn[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            an[pl] = __builtin_bit_cast(bf16x8c, *reinterpret_cast<const u32x4c*>(pa + pl * xpl + 8 * sn));
-            bn[pl] = __builtin_bit_cast(bf16x8c, *reinterpret_cast<const u32x4c*>(pb + pl * wpl + 8 * sn));
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);   // smallest terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) { a[pl] = an[pl]; b[pl] = bn[pl]; }
-    }
+    if (st < ksteps) mfma6_x3(acc, f0);     // odd step count: f0 holds the last step
 }
 
 template <bool X3>
@@ -205,6 +258,7 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
     const int B = a.B, ld = a.ld;
     const int nvalid = min(a.rows, B - b0);
     const int Rlim = b0 + nvalid;            // rows of x beyond the block read as zero (the tile has CHAIN_ROWS rows)
+    const uint32_t row_l = (uint32_t)(rt * 32 + 4 * (lane >> 5));   // the lane's part of its accumulator rows (acc_row)
     const float* P = params + (int64_t)arm * a.per_arm;
 
     // ---- requested before anything waits: the first layer's weights and the workgroup's input rows (with the batch sums
@@ -223,13 +277,14 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
             if (wq_valid) w_load(wq, P + L0.w_off, L0.N, L0.K);
         }
     }
-    const float* X = ws + a.x_off + (int64_t)arm * B * a.K0;
+    const auto rX = ch_rsrc(ws + a.x_off + ((int64_t)arm * B + b0) * a.K0, nvalid, a.K0);
+    const uint32_t x_row = (uint32_t)((tid >> 3) * a.K0) * 4u;     // 64 rows x 8 sixteen-byte parts
     const int xc4n = rup(a.K0, X3 ? 16 : 8) >> 2;
     const bool x_early = (a.K0 & 3) == 0 && xc4n <= 32;   // one pass of 16-byte loads covers the tile
     float4 xq[4];
     if (x_early) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) xq[j] = ldg4_t<true>(X, a.K0, b0 + (tid >> 3), ((tid & 7) + 8 * j) * 4, Rlim, a.K0);
+        for (int j = 0; j < 4; ++j) xq[j] = ch_ld4<true>(rX, x_row, ((tid & 7) + 8 * j) * 4, a.K0);
     }
     // ---- statistics of the input's BatchNorm: recombined from the producer's partials (training) or
     //      the running buffers' values left in the workspace (eval); zero beyond K0
@@ -275,7 +330,7 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
             for (int cb = 0; cb < c4n; cb += 32) {
                 float4 v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = (V && x_early) ? xq[j] : ldg4_t<V>(X, a.K0, b0 + row, (cb + part + 8 * j) * 4, Rlim, a.K0);
+                for (int j = 0; j < 4; ++j) v[j] = (V && x_early) ? xq[j] : ch_ld4<V>(rX, x_row, (cb + part + 8 * j) * 4, a.K0);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int c = cb + part + 8 * j;
@@ -316,10 +371,11 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         else stage_w(Ws, ld, P + Lr.w_off, N, K, NPad, KP);
         const int col = ct * 32 + (lane & 31);
         const bool active = ct * 32 < NPad;
-        const float bias = (active && col < N) ? P[Lr.b_off + col] : 0.f;   // requested before the barrier
+        const uint32_t c_off = (active && col < N) ? (uint32_t)col * 4u : CH_OOB;
+        const float bias = ch_ld(ch_rsrc(P + Lr.b_off, 1, N), c_off);   // requested before the barrier
         const bool obn = Lr.obn_mean_off >= 0;
-        const float omean = (obn && active && col < N) ? ws[Lr.obn_mean_off + (int64_t)arm * N + col] : 0.f;
-        const float orstd = (obn && active && col < N) ? ws[Lr.obn_rstd_off + (int64_t)arm * N + col] : 0.f;
+        const float omean = ch_ld(ch_rsrc(ws + Lr.obn_mean_off + (int64_t)arm * N, obn ? 1 : 0, N), c_off);
+        const float orstd = ch_ld(ch_rsrc(ws + Lr.obn_rstd_off + (int64_t)arm * N, obn ? 1 : 0, N), c_off);
         lds_barrier();
         wq_valid = false;
         if (l + 1 < a.nlayers) {   // next layer's weights travel while this layer computes
@@ -342,16 +398,15 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         const bool need_x = !last || a.planes_off >= 0;
         float vals[16];
         if (active) {
-            float* out = ws + Lr.out_off + (int64_t)arm * B * N;
+            const auto rO = ch_rsrc(ws + Lr.out_off + ((int64_t)arm * B + b0) * N, nvalid, N);
+            const uint32_t o_lane = col < N ? (row_l * (uint32_t)N + (uint32_t)col) * 4u : CH_OOB;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = rt * 32 + acc_row(r, lane);
-                float v = 0.f;
-                if (col < N && row < nvalid) {
-                    v = acc[r] + bias;
-                    if (Lr.act) v = relu_keep_nan(v);
-                    out[(int64_t)(b0 + row) * N + col] = v;
-                }
+                float v = acc[r] + bias;
+                if (Lr.act) v = relu_keep_nan(v);
+                v = (col < N && row < nvalid) ? v : 0.f;
+                ch_st(rO, o_lane + (uint32_t)(acc_row(r, 0) * N) * 4u, v);     // (dropped beyond nvalid rows and N columns)
                 vals[r] = v;
                 // next layer's input: zero beyond N (up to the next multiple of 8) and beyond nvalid
                 const float xin = obn ? ((col < N && row < nvalid) ? (v - omean) * orstd : 0.f) : v;
@@ -419,7 +474,8 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
         // along a row -> 256-byte store segments.  The last row block also writes the zero rows up to planes_rows.
         const int N = a.L[a.nlayers - 1].N;
         const int64_t plane = (int64_t)a.planes_rows * 128;
-        unsigned short* pl = reinterpret_cast<unsigned short*>(ws + a.planes_off) + (int64_t)arm * 3 * plane;
+        // (scalar base at the workgroup's first row, 32-bit offset per lane: at most 320 rows of 256 bytes)
+        char* const pl = reinterpret_cast<char*>(reinterpret_cast<unsigned short*>(ws + a.planes_off) + (int64_t)arm * 3 * plane + (int64_t)b0 * 128);
         const int rows_here = blk == a.nblk - 1 ? a.planes_rows - b0 : a.rows;
         for (int i = tid; i < rows_here * 64; i += CH_NT) {
             const int r = i >> 6, c = (i & 63) * 2;
@@ -443,7 +499,7 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdArgs& a_in, const f
                 split3(v0, v1, w);
             }
 #pragma unroll
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<unsigned*>(pl + p * plane + (int64_t)(b0 + r) * 128 + c) = w[p];
+            for (int p = 0; p < 3; ++p) *reinterpret_cast<unsigned*>(pl + p * plane * 2 + (uint32_t)(r * 128 + c) * 2u) = w[p];
         }
     }
 }
@@ -556,6 +612,7 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, rt = wv >> 2, ct = wv & 3;
     const int B = a.B, ld = a.ld;
     const int nvalid = min(CHAIN_ROWS, B - b0);
+    const uint32_t row_l = (uint32_t)(rt * 32 + 4 * (lane >> 5));   // the lane's part of its accumulator rows (acc_row)
     const float* P = params + (int64_t)arm * a.per_arm;
 
     if (a.zero_n4 > 0) grid_zero(ws + a.zero_off, a.zero_n4);
@@ -583,15 +640,18 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
         const BwdLayer L0 = a.L[0];
         const int N = L0.N, c4n = rup(N, X3 ? 16 : 8) >> 2;
         const bool has_act = L0.act_off >= 0, bnb = a.bnb_part_off >= 0;
-        const float* G = ws + a.g_off + (int64_t)arm * B * N;
-        const float* act = has_act ? ws + L0.act_off + (int64_t)arm * B * N : G;
-        float* dz = ws + L0.dz_off + (int64_t)arm * B * N;
-        const float* mu = bnb ? ws + a.bn_mean_off + (int64_t)arm * N : G;
-        const float* rs = bnb ? ws + a.bn_rstd_off + (int64_t)arm * N : G;
+        const int64_t blk_off = ((int64_t)arm * B + b0) * N;     // the workgroup's first row
+        const float* G = ws + a.g_off + blk_off;
+        const auto rG = ch_rsrc(G, nvalid, N);
+        const auto rAct = has_act ? ch_rsrc(ws + L0.act_off + blk_off, nvalid, N) : rG;
+        const auto rDz = ch_rsrc(ws + L0.dz_off + blk_off, nvalid, N);
+        const auto rMu = ch_rsrc(ws + a.bn_mean_off + (int64_t)arm * N, bnb ? 1 : 0, N);
+        const auto rRs = ch_rsrc(ws + a.bn_rstd_off + (int64_t)arm * N, bnb ? 1 : 0, N);
         const float invB = 1.f / (float)B;
         const bool vec = (N & 3) == 0;
-        const int part = tid & 7, row = tid >> 3;      // 128 rows x 8 sixteen-byte parts
+        const int part = tid & 7, row = tid >> 3;      // 64 rows x 8 sixteen-byte parts
         const bool rok = row < nvalid;
+        const uint32_t g_row = (uint32_t)(row * N) * 4u;
         auto stage_g = [&](auto tag) __attribute__((always_inline)) {
             constexpr bool V = decltype(tag)::value;
             for (int cb = 0; cb < c4n; cb += 32) {
@@ -609,22 +669,20 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
                         for (int s0 = 0; s0 < a.nslab; s0 += CHK) {
                             float4 t[CHK];
 #pragma unroll
-                            for (int sl = 0; sl < CHK; ++sl)
-                                t[sl] = ldg4_t<V>(G + (int64_t)min(s0 + sl, a.nslab - 1) * a.slab_stride, N, b0 + row, col, B, N);
+                            for (int sl = 0; sl < CHK; ++sl)      // (a slab past the last: no rows, reads 0, adds 0)
+                                t[sl] = ch_ld4<V>(ch_rsrc(G + (int64_t)min(s0 + sl, a.nslab - 1) * a.slab_stride,
+                                                          s0 + sl < a.nslab ? nvalid : 0, N), g_row, col, N);
 #pragma unroll
-                            for (int sl = 0; sl < CHK; ++sl) {
-                                const bool on = s0 + sl < a.nslab;
-                                g.x += on ? t[sl].x : 0.f; g.y += on ? t[sl].y : 0.f; g.z += on ? t[sl].z : 0.f; g.w += on ? t[sl].w : 0.f;
-                            }
+                            for (int sl = 0; sl < CHK; ++sl) { g.x += t[sl].x; g.y += t[sl].y; g.z += t[sl].z; g.w += t[sl].w; }
                         }
                     };
-                    if (a.nslab == 1) g = ldg4_t<V>(G, N, b0 + row, col, B, N);
+                    if (a.nslab == 1) g = ch_ld4<V>(rG, g_row, col, N);
                     else if (a.nslab <= 4) add_slabs(std::integral_constant<int, 4>{});
                     else add_slabs(std::integral_constant<int, 16>{});
                     gq[j] = g;
-                    avq[j] = ldg4_t<V>(act, N, b0 + row, col, B, N);
-                    mmq[j] = ldg4_t<V>(mu, 0, 0, col, 1, N);
-                    rrq[j] = ldg4_t<V>(rs, 0, 0, col, 1, N);
+                    avq[j] = ch_ld4<V>(rAct, g_row, col, N);
+                    mmq[j] = ch_ld4<V>(rMu, 0u, col, N);
+                    rrq[j] = ch_ld4<V>(rRs, 0u, col, N);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -657,17 +715,8 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
                         } else {
                             *reinterpret_cast<float4*>(&Gs[row * ld + col]) = v;
                         }
-                        if (rok) {
-                            float* o = dz + (int64_t)(b0 + row) * N + col;
-                            if (V && col + 3 < N) *reinterpret_cast<float4*>(o) = v;
-                            else {
-                                if (col < N) o[0] = v.x;
-                                if (col + 1 < N) o[1] = v.y;
-                                if (col + 2 < N) o[2] = v.z;
-                                if (col + 3 < N) o[3] = v.w;
-                            }
-                        }
                     }
+                    ch_st4<V>(rDz, g_row, col, N, v);     // (dropped beyond nvalid rows and N columns; N <= 4 c4n)
                 }
             }
         };
@@ -701,24 +750,21 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
         // layer (five per decoder launch)
         const bool last = (l + 1 == a.nlayers);
         constexpr int NTI = X3 ? 1 : 2;   // X3: every width <= 128, one column tile per wave
+        // (a lane without an element, or a layer without such an operand, reads 0; `gated` says whether ReLU' applies)
         float pre[NTI][16];
+        const int64_t blk_off = ((int64_t)arm * B + b0) * K;     // the workgroup's first row of a [A,B,K] array
+        const int64_t pre_off = last ? a.rprev_off : a.L[last ? l : l + 1].act_off;
+        const bool gated = !last && pre_off >= 0;
+        uint32_t o_lane[NTI];
         {
-            const float* src = nullptr;
-            if (!last) {
-                const BwdLayer Ln = a.L[l + 1];
-                src = Ln.act_off >= 0 ? ws + Ln.act_off + (int64_t)arm * B * K : nullptr;
-            } else if (a.part_off >= 0) {
-                src = ws + a.rprev_off + (int64_t)arm * B * K;
-            }
+            const bool has_src = last ? a.part_off >= 0 : pre_off >= 0;
+            const auto rPre = ch_rsrc(ws + pre_off + blk_off, has_src ? nvalid : 0, K);
 #pragma unroll
             for (int ti = 0; ti < NTI; ++ti) {
                 const int col = (ct + 4 * ti) * 32 + (lane & 31);
+                o_lane[ti] = ((ct + 4 * ti) * 32 < KPad && col < K) ? (row_l * (uint32_t)K + (uint32_t)col) * 4u : CH_OOB;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rt * 32 + acc_row(r, lane);
-                    const bool ok = src && (ct + 4 * ti) * 32 < KPad && col < K && row < nvalid;
-                    pre[ti][r] = ok ? src[(int64_t)(b0 + row) * K + col] : (last ? 0.f : 1.f);
-                }
+                for (int r = 0; r < 16; ++r) pre[ti][r] = ch_ld(rPre, o_lane[ti] + (uint32_t)(acc_row(r, 0) * K) * 4u);
             }
         }
         // input width K may reach 255 (fc6: K = C + S): up to 8 column tiles, two per wave
@@ -743,14 +789,13 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
             const f32x16 acc = accs[ti];
             const int col = cti * 32 + (lane & 31);
             if (!last) {
-                const BwdLayer Ln = a.L[l + 1];   // its N == this K
-                float* dz = ws + Ln.dz_off + (int64_t)arm * B * K;
+                const auto rDz = ch_rsrc(ws + a.L[l + 1].dz_off + blk_off, nvalid, K);   // the next layer's N == this K
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = rt * 32 + acc_row(r, lane);
                     const bool ok = col < K && row < nvalid;
-                    const float v = (ok && pre[ti][r] > 0.f) ? acc[r] : 0.f;
-                    if (ok) dz[(int64_t)(b0 + row) * K + col] = v;
+                    const float v = (ok && (!gated || pre[ti][r] > 0.f)) ? acc[r] : 0.f;
+                    ch_st(rDz, o_lane[ti] + (uint32_t)(acc_row(r, 0) * K) * 4u, v);
                     if constexpr (X3) {   // pairs of columns through the even lane (see k_chain_fwd)
                         const float nbv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xF5, 0xF, 0xF, false));
                         if (!(lane & 1) && col < rup(K, 16)) {
@@ -764,19 +809,17 @@ __global__ __launch_bounds__(CH_NT) void k_chain_bwd(const ChainBwdArgs a_in, co
                     }
                 }
             } else {
-                float* go = ws + a.gout_off + (int64_t)arm * B * K;
+                const auto rGo = ch_rsrc(ws + a.gout_off + blk_off, nvalid, K);
                 float s1 = 0.f, s2 = 0.f;
                 const bool want = a.part_off >= 0;
-                float mu = 0.f, rs = 0.f;
-                if (want && col < K) {
-                    mu = ws[a.rprev_mean_off + (int64_t)arm * K + col];
-                    rs = ws[a.rprev_rstd_off + (int64_t)arm * K + col];
-                }
+                const uint32_t c_off = col < K ? (uint32_t)col * 4u : CH_OOB;
+                const float mu = ch_ld(ch_rsrc(ws + a.rprev_mean_off + (int64_t)arm * K, want ? 1 : 0, K), c_off);
+                const float rs = ch_ld(ch_rsrc(ws + a.rprev_rstd_off + (int64_t)arm * K, want ? 1 : 0, K), c_off);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = rt * 32 + acc_row(r, lane);
+                    ch_st(rGo, o_lane[ti] + (uint32_t)(acc_row(r, 0) * K) * 4u, acc[r]);
                     if (col < K && row < nvalid) {
-                        go[(int64_t)(b0 + row) * K + col] = acc[r];
                         s1 += acc[r];
                         s2 = bn_bwd_xhat_acc(acc[r], pre[ti][r], mu, rs, s2);
                     }
