@@ -221,6 +221,15 @@ def lib():
     L.mmvae_state_corr.argtypes = [vp, i64, i64, i32, vp, vp, i64, i64, i32, vp, i32, vp, C.c_size_t, vp, vp, vp]
     L.mmvae_debug_state_corr.argtypes = [vp, i64, i64, i32, vp, vp, i64, i64, i32, vp, i32, vp, C.c_size_t, vp, vp, i32, vp]
     L.mmvae_state_corr.restype = L.mmvae_debug_state_corr.restype = C.c_int
+    L.mmvae_group_moments_workspace_bytes.argtypes = [i64, i32, i32]
+    L.mmvae_group_moments_workspace_bytes.restype = C.c_size_t
+    L.mmvae_group_moments.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp, vp]
+    L.mmvae_debug_group_moments.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp, i32, vp]
+    L.mmvae_group_moments.restype = L.mmvae_debug_group_moments.restype = C.c_int
+    L.mmvae_gauss_scores_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.mmvae_gauss_scores_workspace_bytes.restype = C.c_size_t
+    L.mmvae_gauss_scores.argtypes = [vp, i64, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.mmvae_gauss_scores.restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -821,6 +830,86 @@ def state_corr(data: torch.Tensor, state: torch.Tensor, rows: Optional[torch.Ten
                                        _ptr(offsets), G, _ptr(ws), ws_bytes, _ptr(r), _ptr(count), STATECORR_PATHS[path],
                                        _stream(x.device)), "mmvae_state_corr")
     return r, count
+
+
+# launch_group_moments / launch_gauss_scores (csrc/gaussclf.hip; the constants are those of csrc/common.hpp)
+GAUSSCLF_SEG_ROWS = 256         # GC_SEG_ROWS: a group of more rows is cut into segments of this many
+GAUSSCLF_ROW_CHUNK = 32         # GC_ROW_CHUNK: rows of a segment staged in LDS at a time
+GAUSSCLF_DC = (16, 32, 64, 128)  # GC_DC: the largest d of each instance of the segment kernel
+GAUSSCLF_ROW_TILE = 64          # GC_ROW_TILE: cells per workgroup of the score kernel, one a lane
+GAUSSCLF_SCORE_WAVES = 16       # GC_SCORE_WAVES: its waves at most, min(K, 16) of them; wave w scores the w-th run of classes
+GAUSSCLF_COL_BLOCK = 8          # GC_COL_BLOCK: columns of W carried at once; the d % 8 last ones go one by one
+GAUSSCLF_MAX_D, GAUSSCLF_MAX_K, GAUSSCLF_MAX_F = 128, 4096, 64
+GAUSSCLF_PATHS = {"auto": -1, "d16": 0, "d32": 1, "d64": 2, "d128": 3}
+
+
+def gaussclf_dclass(d: int) -> str:
+    """The instance of the segment kernel that the launcher runs dimension ``d`` on: a key of GAUSSCLF_PATHS."""
+    return next(f"d{v}" for v in GAUSSCLF_DC if d <= v)
+
+
+def group_moments(x_sorted: torch.Tensor, offsets: torch.Tensor, pivot: torch.Tensor,
+                  path: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """mmvae_group_moments: float32 points [n, d] on the GPU (rows may be strided, columns not) ordered by group, int64
+    ``offsets`` [G + 1] and the float32 ``pivot`` [d] -> (s float64 [G, d], M float64 [G, d (d + 1) / 2]) on the device: per
+    group the sum of x - pivot and the packed upper triangle of the sum of (x - pivot)(x - pivot)^T, the differences formed
+    in fp64.  Inputs must be finite.  ``path``: "auto" (the launcher's rule) or "d16" / "d32" / "d64" / "d128", the
+    instances of the segment kernel -- equal bits."""
+    if any(t.device.type != "cuda" for t in (x_sorted, offsets, pivot)):
+        raise NativeError("group_moments needs CUDA tensors (no CPU fallback)")
+    if path not in GAUSSCLF_PATHS:
+        raise ValueError(f"group_moments: path must be one of {sorted(GAUSSCLF_PATHS)}; got {path!r}")
+    if x_sorted.dtype != torch.float32 or x_sorted.dim() != 2 or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise TypeError("group_moments: x_sorted must be float32 [n, d] and offsets int64 [G + 1]")
+    n, d = (int(v) for v in x_sorted.shape)
+    if pivot.dtype != torch.float32 or tuple(pivot.shape) != (d,):
+        raise TypeError(f"group_moments: pivot must be float32 [{d}]")
+    x = x_sorted if x_sorted.stride(1) == 1 and x_sorted.stride(0) >= d else x_sorted.contiguous()
+    off, piv = offsets.contiguous(), pivot.contiguous()
+    G = int(off.numel()) - 1
+    s = torch.empty(max(G, 0), d, dtype=torch.float64, device=x.device)
+    M = torch.empty(max(G, 0), d * (d + 1) // 2, dtype=torch.float64, device=x.device)
+    ws_bytes = int(lib().mmvae_group_moments_workspace_bytes(n, d, G))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    check(lib().mmvae_debug_group_moments(_ptr(x), int(x.stride(0)), n, d, _ptr(off), G, _ptr(piv), _ptr(ws), ws_bytes, _ptr(s),
+                                          _ptr(M), GAUSSCLF_PATHS[path], _stream(x.device)), "mmvae_group_moments")
+    return s, M
+
+
+def gauss_scores(x: torch.Tensor, model: torch.Tensor, mu: torch.Tensor, W: torch.Tensor, c0: torch.Tensor,
+                 perm: Optional[torch.Tensor] = None, return_scores: bool = False):
+    """mmvae_gauss_scores: float32 points [n, d] on the GPU (rows may be strided, columns not), the int32 ``model`` [n] of
+    every row (sort the rows by it), float64 ``mu`` [F, K, d], ``W`` [F, K, d, d] and ``c0`` [F, K] and, optionally, the
+    int64 permutation ``perm`` [n] (row r is the caller's row perm[r]) -> (label int32 [n], best float64 [n], second
+    float64 [n], scores float64 [n, K] or None) on the device, in the caller's order:
+    score = c0 - |W^T (x - mu)|^2 / 2 under the row's own model, label its arg-max (the lowest index on ties)."""
+    tensors = [t for t in (x, model, mu, W, c0, perm) if t is not None]
+    if any(t.device.type != "cuda" for t in tensors):
+        raise NativeError("gauss_scores needs CUDA tensors (no CPU fallback)")
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise TypeError("gauss_scores: x must be float32 [n, d]")
+    n, d = (int(v) for v in x.shape)
+    if c0.dtype != torch.float64 or c0.dim() != 2:
+        raise TypeError("gauss_scores: c0 must be float64 [F, K]")
+    F, K = (int(v) for v in c0.shape)
+    if mu.dtype != torch.float64 or tuple(mu.shape) != (F, K, d) or W.dtype != torch.float64 or tuple(W.shape) != (F, K, d, d):
+        raise TypeError(f"gauss_scores: mu must be float64 [{F}, {K}, {d}] and W float64 [{F}, {K}, {d}, {d}]")
+    if model.dtype != torch.int32 or tuple(model.shape) != (n,):
+        raise TypeError(f"gauss_scores: model must be int32 [{n}]")
+    if perm is not None:
+        if perm.dtype != torch.int64 or tuple(perm.shape) != (n,):
+            raise TypeError(f"gauss_scores: perm must be int64 [{n}]")
+        perm = perm.contiguous()
+    xs = x if x.stride(1) == 1 and x.stride(0) >= d else x.contiguous()
+    mu, W, c0, model = mu.contiguous(), W.contiguous(), c0.contiguous(), model.contiguous()
+    label = torch.empty(n, dtype=torch.int32, device=xs.device)
+    best = torch.empty(n, dtype=torch.float64, device=xs.device)
+    second = torch.empty(n, dtype=torch.float64, device=xs.device)
+    scores = torch.empty(n, K, dtype=torch.float64, device=xs.device) if return_scores else None
+    check(lib().mmvae_gauss_scores(_ptr(xs), int(xs.stride(0)), n, d, _ptr(model), F, K, _ptr(mu), _ptr(W), _ptr(c0), _ptr(perm),
+                                   None, 0, _ptr(label), _ptr(best), _ptr(second), _ptr(scores), _stream(xs.device)),
+          "mmvae_gauss_scores")
+    return label, best, second, scores
 
 
 def to_bf16(data: torch.Tensor) -> torch.Tensor:

@@ -852,6 +852,54 @@ class cpl_mixVAE:
         cats = np.arange(Cc, dtype=np.int64) if by_category else np.array([-1], dtype=np.int64)
         return {"corr": r.cpu().numpy(), "n": cnt.cpu().numpy(), "categories": cats}
 
+    @torch.no_grad()
+    def classify_latents(self, dl, labels, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", kind: str = "qda"):
+        """How well a Gaussian classifier recovers ``labels`` from arm ``arm``'s latents under k-fold cross-validation: the
+        reference's ``QDA_classifier`` / ``LDA_classifier`` (mmidas/utils/cluster_analysis.py:38-83; ``kind`` "qda" or
+        "lda") on ``on`` = "x_low" (the low-dimensional representation), "state_mu" (the state's mean) or "z_prob" (the
+        categorical probabilities: points on the simplex, for which use "lda" or expect QDA to lean on its regulariser).
+        ``dl`` is encoded through the device encode path (``fill_latents``, as ``encode_dataset``) and the latents never
+        leave the device.  ``labels``: 1-D, one label per row of the data set; the label of a cell is ``labels[index]`` for
+        the index its batch carries, so the cells are classified in the order the loader serves them.  Returns
+        ``{"acc", "ref_labels", "pred_labels"}`` (lists over the folds, as the reference's dict entries for one label set),
+        ``"margin"`` float64 [n] (best minus second-best score of every cell, in the loader's order; +inf where only one
+        class is known), ``"fold"`` int64 [n] and ``"data_indx"``.  The loader must serve every row once (no ``drop_last``)."""
+        if D.is_dist():
+            raise NotImplementedError("classify_latents is not data-parallel: run it on one rank, outside the process group")
+        if self.ref_prior:
+            raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
+        if not 0 <= int(arm) < self.n_arm:
+            raise ValueError(f"arm = {arm} outside [0, {self.n_arm})")
+        names = {"x_low": "x_low", "state_mu": "s_mean", "z_prob": "c"}
+        if on not in names:
+            raise ValueError(f"on = {on!r}: one of {sorted(names)}")
+        from .model import fill_latents
+        from .utils.dataloader import DeviceLoader
+        from .utils import cluster_analysis as CA
+        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
+        dev = self.device
+        resident = isinstance(dl, DeviceLoader)
+        if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
+            raise ValueError("classify_latents needs a loader that serves every row once (no drop_last, no sharding)")
+        if not resident:
+            dl = _Replay(dl, dev)
+        n_rows = len(dl.dataset)
+        was_training = self.model.training
+        self.model.eval()
+        bias = self.model.fcc[0].bias.detach().cpu().numpy()
+        pruning_mask = np.where(bias != 0.0)[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
+               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
+               "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
+        inds = fill_latents(dl, [(self.model, pruning_mask, out, None)], self.temp)
+        self.model.train(was_training)
+        data_indx = inds.cpu().numpy()
+        y = np.asarray(labels)[data_indx.astype(np.int64)]
+        acc, ref, pred, res = CA.classify_points(out[names[on]][int(arm)], y, kfold, seed, kind)
+        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
+                "data_indx": data_indx}
+
 
 class _Replay:
     """The batches ``(x, index)`` of one walk of a loader, kept on the device: ``fill_latents`` and the matrix they form see the

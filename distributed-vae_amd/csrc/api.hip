@@ -1098,6 +1098,72 @@ int mmvae_debug_state_corr(const float* data, int64_t ld, int64_t n_total, int D
     return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, path, stream);
 }
 
+size_t mmvae_group_moments_workspace_bytes(int64_t n, int d, int G) {
+    if (n < 1 || n > ((int64_t)1 << 31) || d < 1 || d > GC_MAX_D || G < 1 || G > GC_MAX_G) return 0;
+    const unsigned __int128 nseg = (unsigned __int128)gc_nseg_max(n, G);
+    const unsigned __int128 bytes = 8 * (nseg * (unsigned __int128)(d * (d + 3) / 2) + nseg + 1) + 4 * (((unsigned __int128)G + 2) / 2 * 2);
+    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
+}
+
+// every argument is checked here, on the host, before any device work.  dclass: -1 the launcher's rule (the first instance
+// of GC_DC that holds d), 0 .. GC_N_DC - 1 that instance
+static int group_moments_checked(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot,
+                                 void* ws, size_t ws_bytes, double* s, double* M, int dclass, void* stream) {
+    if (!x || !offsets || !pivot || !ws || !s || !M) { set_error("group_moments: null pointer"); return MMVAE_E_BADARG; }
+    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("group_moments: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (d < 1 || G < 1) { set_error("group_moments: d = %d, G = %d: each must be at least 1", d, G); return MMVAE_E_BADARG; }
+    if (ld < d) { set_error("group_moments: ld = %lld below d = %d", (long long)ld, d); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("group_moments: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+    if (dclass < -1 || dclass >= GC_N_DC) { set_error("group_moments: dclass = %d outside [-1, %d]", dclass, GC_N_DC - 1); return MMVAE_E_BADARG; }
+    if (d > GC_MAX_D) { set_error("group_moments: d = %d above %d", d, GC_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    if (G > GC_MAX_G) { set_error("group_moments: G = %d above %d", G, GC_MAX_G); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_group_moments_workspace_bytes(n, d, G);
+    if (need == 0) { set_error("group_moments: a workspace size_t cannot hold"); return MMVAE_E_UNSUPPORTED; }
+    if (ws_bytes < need) {
+        set_error("group_moments: workspace of %zu bytes below the %zu needed", ws_bytes, need);
+        return MMVAE_E_WORKSPACE;
+    }
+    if (dclass >= 0 && d > GC_DC[dclass]) {
+        set_error("group_moments: the instance for d <= %d cannot run d = %d", GC_DC[dclass], d);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_group_moments(x, ld, n, d, offsets, G, pivot, ws, s, M, dclass < 0 ? gc_dclass(d) : dclass,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot, void* ws,
+                        size_t ws_bytes, double* s, double* M, void* stream) {
+    return group_moments_checked(x, ld, n, d, offsets, G, pivot, ws, ws_bytes, s, M, -1, stream);
+}
+
+int mmvae_debug_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot,
+                              void* ws, size_t ws_bytes, double* s, double* M, int dclass, void* stream) {
+    return group_moments_checked(x, ld, n, d, offsets, G, pivot, ws, ws_bytes, s, M, dclass, stream);
+}
+
+// the kernel keeps nothing between launches
+size_t mmvae_gauss_scores_workspace_bytes(int64_t n, int d, int F, int K) {
+    (void)n; (void)d; (void)F; (void)K;
+    return 0;
+}
+
+int mmvae_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int32_t* model, int F, int K, const double* mu,
+                       const double* W, const double* c0, const int64_t* perm, void* ws, size_t ws_bytes, int32_t* label,
+                       double* best, double* second, double* scores, void* stream) {
+    (void)ws_bytes;
+    if (!x || !model || !mu || !W || !c0 || !label || !best || !second) { set_error("gauss_scores: null pointer"); return MMVAE_E_BADARG; }
+    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("gauss_scores: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (d < 1 || F < 1 || K < 1) { set_error("gauss_scores: d = %d, F = %d, K = %d: each must be at least 1", d, F, K); return MMVAE_E_BADARG; }
+    if (ld < d) { set_error("gauss_scores: ld = %lld below d = %d", (long long)ld, d); return MMVAE_E_BADARG; }
+    if (ws && reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("gauss_scores: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+    if (d > GC_MAX_D || K > GC_MAX_K || F > GC_MAX_F) {
+        set_error("gauss_scores: d = %d, K = %d, F = %d above %d, %d, %d", d, K, F, GC_MAX_D, GC_MAX_K, GC_MAX_F);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_gauss_scores(x, ld, n, d, model, F, K, mu, W, c0, perm, label, best, second, scores,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

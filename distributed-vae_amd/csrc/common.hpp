@@ -994,6 +994,25 @@ int64_t sc_nseg_max(int64_t n, int G);
 bool sc_wide(const float* data, int64_t ld);
 int launch_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
                       int64_t n, int S, const int64_t* offsets, int G, void* ws, double* r, int64_t* count, bool wide, hipStream_t st);
+// Gaussian classifiers: group moments and class scores (gaussclf.hip)
+constexpr int GC_SEG_ROWS = 256;       // rows per segment at most: a longer group is cut into pieces of this many
+constexpr int GC_ROW_CHUNK = 32;       // rows of a segment staged in LDS at a time by k_gc_partial
+constexpr int GC_N_DC = 4;
+constexpr int GC_DC[GC_N_DC] = {16, 32, 64, 128};   // the largest d of each instance of k_gc_partial (1, 3, 9, 33 sums a thread)
+constexpr int GC_ROW_TILE = 64;        // cells per workgroup of k_gc_scores: one cell a lane of every wave
+constexpr int GC_SCORE_WAVES = 16;     // waves per workgroup of k_gc_scores at most: they share the cells and split the classes
+constexpr int GC_COL_BLOCK = 8;        // columns of W whose inner products k_gc_scores carries at once
+constexpr int GC_MAX_D = 128;
+constexpr int GC_MAX_K = 4096;
+constexpr int GC_MAX_F = 64;
+constexpr int GC_MAX_G = 1 << 20;      // groups of one mmvae_group_moments call (GC_MAX_K x GC_MAX_F fits four times)
+int64_t gc_nseg_max(int64_t n, int G);
+int gc_dclass(int d);
+int launch_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot, void* ws,
+                         double* s, double* M, int dclass, hipStream_t st);
+int launch_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int* model, int F, int K, const double* mu,
+                        const double* W, const double* c0, const int64_t* perm, int* label, double* best, double* second,
+                        double* scores, hipStream_t st);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

@@ -1,11 +1,22 @@
-"""The clusterability scores of the reference's ``mmidas/utils/cluster_analysis.py``: ``get_SilhScore`` and the silhouette
-half of ``cluster_compare``, on the device, without sklearn.
+"""The clusterability analysis of the reference's ``mmidas/utils/cluster_analysis.py``: ``get_SilhScore``, the silhouette
+half of ``cluster_compare`` and the two Gaussian classifiers ``QDA_classifier`` / ``LDA_classifier``, on the device, without
+sklearn.
 
 The reference calls ``sklearn.metrics.silhouette_samples`` / ``silhouette_score`` (euclidean) on the latents: n^2 distances,
 which sklearn computes on the host in float64 through the Gram expansion.  Here the cells are sorted by label on the host,
 uploaded once, and ``mmvae_silhouette`` (csrc/silhouette.hip) forms every distance in fp32 in difference
 form and everything after it in fp64; the per-cell scores come back as float64 and the means are numpy's, over the classes
-in ``np.unique`` order.  ``K_selection`` and the RF / LDA / QDA classifiers of that module are not part of this package."""
+in ``np.unique`` order.
+
+The classifiers answer how well the cell types are recovered from the latents under k-fold cross-validation.  One pass of
+``mmvae_group_moments`` (csrc/gaussclf.hip) gives the moments of every (class, fold) group of cells
+about one pivot; moments about one pivot add, so every fold's training set is a sum of groups.  The models are sklearn's,
+built on the host in fp64 (F K eigen-decompositions of d x d matrices, plumbing), and ``mmvae_gauss_scores`` scores every
+cell under every class of its own fold's model and takes the arg-max.  ``gaussian_cv_predict`` is the one function under
+both; it also returns the two best scores of every cell, whose difference is a confidence the reference does not offer.
+
+``RF_classifier`` and ``K_selection`` of that module are not part of this package (a random forest is not a dense, regular
+computation), and neither are ``custom_QDA`` and ``predict_leaf_gmm`` of ``analysis_tree_helpers.py``."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -155,3 +166,225 @@ def cluster_compare(data, labels, num_pc=0, saving_path=''):
         c_size.append(sizes[ascending])
         curves.append((key, means[ascending]))
     return _figure(curves, num_pc), silh_smp_score, sil_score, c_size
+
+
+# ---- the Gaussian classifiers ---------------------------------------------------------------------------------------------
+QDA_REG_PARAM = 1e-2            # the reference's QuadraticDiscriminantAnalysis(reg_param=1e-2)
+LDA_TOL = 1e-4                  # sklearn's LinearDiscriminantAnalysis(tol=1e-4): singular values at or below it are dropped
+
+
+def kfold_of(n: int, kfold: int, seed) -> np.ndarray:
+    """The fold whose test set holds every cell under sklearn's ``KFold(n_splits=kfold, shuffle=True, random_state=seed)``,
+    int64 [n]: ``np.random.RandomState(seed).shuffle`` of ``arange(n)``, cut into ``kfold`` consecutive pieces of which the
+    first ``n % kfold`` are one longer.  sklearn yields every test set in ascending order of the index."""
+    idx = np.arange(n)
+    np.random.RandomState(seed).shuffle(idx)
+    sizes = np.full(kfold, n // kfold, dtype=np.int64)
+    sizes[:n % kfold] += 1
+    fold = np.empty(n, dtype=np.int64)
+    fold[idx] = np.repeat(np.arange(kfold), sizes)
+    return fold
+
+
+def _qda_models(counts, scatter, reg):
+    """(W [K, d, d], c0 [K]) of sklearn's QDA from per-class training counts [K] and scatter matrices [K, d, d]."""
+    K, d = scatter.shape[:2]
+    N = float(counts.sum())
+    W, c0 = np.zeros((K, d, d)), np.full(K, -np.inf)
+    have = counts > 0
+    cov = scatter[have] / (counts[have] - 1.0)[:, None, None]
+    lam, V = np.linalg.eigh(cov)
+    S2 = (1.0 - reg) * lam + reg
+    W[have] = V * (S2 ** -0.5)[:, None, :]
+    c0[have] = -0.5 * np.sum(np.log(S2), axis=1) + np.log(counts[have] / N)
+    return W, c0
+
+
+def _lda_models(counts, scatter):
+    """(W [K, d, d], c0 [K]) of sklearn's LDA (solver "svd"): one factor of the pooled within-class covariance for all."""
+    K, d = scatter.shape[:2]
+    have = counts > 0
+    N = float(counts.sum())
+    Sw = np.sum(scatter[have], axis=0)
+    std = np.sqrt(np.diag(Sw) / N)
+    std[std == 0] = 1.0
+    Cm = Sw / np.outer(std, std) / (N - int(have.sum()))
+    lam, V = np.linalg.eigh(Cm)
+    lam, V = lam[::-1], V[:, ::-1]
+    S = np.sqrt(np.maximum(lam, 0.0))
+    rank = int(np.sum(S > LDA_TOL))
+    Wone = np.zeros((d, d))
+    Wone[:, :rank] = (V[:, :rank] / std[:, None]) / S[:rank]
+    c0 = np.full(K, -np.inf)
+    c0[have] = np.log(counts[have] / N)
+    return np.broadcast_to(Wone, (K, d, d)), c0
+
+
+def models_from_moments(s, M, counts, pivot, kind, reg_param=QDA_REG_PARAM):
+    """The F models of a k-fold cross-validation from the moments of the K x F (class, fold) groups about ``pivot``:
+    ``s`` [K, F, d], ``M`` [K, F, d (d + 1) / 2] (``mmvae_group_moments``), ``counts`` [K, F] -> (mu [F, K, d],
+    W [F, K, d, d], c0 [F, K]) in fp64.  The training set of fold f is the sum of the groups of the other folds, added in
+    fold order with no subtraction; mean = pivot + s / N, scatter = M - s s^T / N."""
+    K, F, d = s.shape
+    iu = np.triu_indices(d)
+    pivot = np.asarray(pivot, dtype=np.float64)
+    mu, W, c0 = np.zeros((F, K, d)), np.zeros((F, K, d, d)), np.zeros((F, K))
+    for f in range(F):
+        cnt, s_tr, M_tr = np.zeros(K), np.zeros((K, d)), np.zeros((K, M.shape[2]))
+        for g in range(F):
+            if g != f:
+                cnt += counts[:, g]
+                s_tr += s[:, g]
+                M_tr += M[:, g]
+        Nk = np.maximum(cnt, 1.0)[:, None]
+        mu[f] = pivot[None] + s_tr / Nk
+        full = np.zeros((K, d, d))
+        full[:, iu[0], iu[1]] = M_tr
+        full[:, iu[1], iu[0]] = M_tr
+        scatter = full - s_tr[:, :, None] * s_tr[:, None, :] / Nk[:, :, None]
+        if kind == "qda":
+            W[f], c0[f] = _qda_models(cnt, scatter, reg_param)
+        else:
+            W[f], c0[f] = _lda_models(cnt, scatter)
+    return mu, W, c0
+
+
+def _cv_on_device(x_dev, codes, classes, fold, kfold, kind, reg_param, return_scores):
+    """The two launches and the host factorisations between them, for points already on the device."""
+    n, d = (int(v) for v in x_dev.shape)
+    K, dev = len(classes), x_dev.device
+    group = codes * kfold + fold                                                    # class-major: [K, F]
+    order = np.argsort(group, kind="stable")
+    counts = np.bincount(group, minlength=K * kfold).astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    pivot = x_dev.mean(dim=0)                               # any pivot gives the same moments in exact arithmetic; the data's
+    perm = torch.from_numpy(order.astype(np.int64)).to(dev)  # mean keeps kappa = 1 + (mean - pivot)^2 / var as small as one pivot can
+    s, M = N.group_moments(x_dev.index_select(0, perm), torch.from_numpy(offsets).to(dev), pivot)
+    mu, W, c0 = models_from_moments(s.cpu().numpy().reshape(K, kfold, d), M.cpu().numpy().reshape(K, kfold, -1),
+                                    counts.reshape(K, kfold).astype(np.float64), pivot.cpu().numpy(), kind, reg_param)
+    by_fold = np.argsort(fold, kind="stable")
+    perm2 = torch.from_numpy(by_fold.astype(np.int64)).to(dev)
+    model = torch.from_numpy(fold[by_fold].astype(np.int32)).to(dev)
+    label, best, second, scores = N.gauss_scores(x_dev.index_select(0, perm2), model, torch.from_numpy(mu).to(dev),
+                                                 torch.from_numpy(np.ascontiguousarray(W)).to(dev), torch.from_numpy(c0).to(dev),
+                                                 perm2, return_scores)
+    out = {"pred": label.cpu().numpy().astype(np.int64), "fold": fold, "best": best.cpu().numpy(),
+           "second": second.cpu().numpy(), "classes": classes}
+    if return_scores:
+        out["scores"] = scores.cpu().numpy()
+    return out
+
+
+def _cv_refusals(labels, n, kfold, seed, kind):
+    """(classes, codes, fold) after every refusal that needs no device."""
+    if kind not in ("qda", "lda"):
+        raise ValueError(f"kind = {kind!r}: one of 'qda', 'lda'")
+    y = np.asarray(labels)
+    if y.ndim != 1:
+        raise ValueError(f"labels of shape {y.shape} are not 1-D")
+    if y.shape[0] != n:
+        raise ValueError(f"{y.shape[0]} labels for {n} samples")
+    if int(kfold) != kfold or not 2 <= kfold <= n:
+        raise ValueError(f"kfold = {kfold} outside [2, n = {n}]")
+    classes, codes = np.unique(y, return_inverse=True)
+    codes = codes.reshape(-1)
+    if len(classes) < 2:
+        raise ValueError(f"The number of classes has to be greater than one; got {len(classes)} class")
+    if len(classes) > N.GAUSSCLF_MAX_K or kfold > N.GAUSSCLF_MAX_F:
+        raise NotImplementedError(f"{len(classes)} classes and {kfold} folds: at most {N.GAUSSCLF_MAX_K} and {N.GAUSSCLF_MAX_F}")
+    fold = kfold_of(n, int(kfold), seed)
+    if kind == "qda":
+        per = np.bincount(codes * int(kfold) + fold, minlength=len(classes) * int(kfold)).reshape(len(classes), int(kfold))
+        train = per.sum(axis=1, keepdims=True) - per
+        bad = np.argwhere(train == 1)
+        if len(bad):
+            raise ValueError("y has only 1 sample in class %s, covariance is ill defined." % str(classes[bad[0][0]]))
+    return classes, codes, fold
+
+
+def _shape_of(x):
+    if not hasattr(x, "shape"):
+        x = np.asarray(x)
+    if len(x.shape) != 2:
+        raise ValueError(f"x of shape {tuple(x.shape)} is not [n, d]")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= d <= N.GAUSSCLF_MAX_D:
+        raise NotImplementedError(f"d = {d} outside [1, {N.GAUSSCLF_MAX_D}]")
+    return n
+
+
+def gaussian_cv_predict(x, labels, kfold, seed, kind="qda", reg_param=QDA_REG_PARAM, return_scores=False, device=None):
+    """k-fold cross-validated prediction of ``labels`` from the points ``x`` by a Gaussian classifier, every cell scored
+    under the model fitted to the folds it is not in.
+
+    ``kind="qda"``: sklearn's ``QuadraticDiscriminantAnalysis(reg_param)`` -- per class the eigen-pairs lam, V of the
+    unbiased covariance, S2 = (1 - reg) lam + reg, score = -|S2^(-1/2) V^T (x - mu)|^2 / 2 - sum(log S2) / 2 + log(N_k / N);
+    a class with exactly one training cell in some fold raises sklearn's ValueError.  DEPARTURE: for a class with at most
+    d training cells sklearn keeps only min(N_k, d) singular directions of the centred rows, the last of them an arbitrary
+    vector of the null space, so the reference's own prediction there is not reproducible; this function uses all d
+    eigen-directions of the regularised covariance (S2 = reg in the null space).  ``kind="lda"``: sklearn's
+    ``LinearDiscriminantAnalysis()`` (solver "svd") -- the pooled within-class covariance over N - K_present, scaled by
+    the within-class standard deviations, directions with a singular value <= 1e-4 dropped (which is what makes
+    probabilities on the simplex work), score = -|W^T (x - mu)|^2 / 2 + log(N_k / N).  sklearn's second SVD over the class
+    means only drops directions in which all classes score alike; it is not restated, so these scores differ from its
+    ``decision_function`` by a term that is the same for every class of a cell.
+
+    ``x``: array-like or tensor [n, d], d <= 128; a float32 tensor on the GPU is used where it lies, anything else is
+    ROUNDED to float32 and uploaded.  ``labels``: 1-D, ints or hashables, encoded by ``np.unique``.  The folds are those
+    of ``KFold(n_splits=kfold, shuffle=True, random_state=seed)`` (``kfold_of``).  Returns a dict: ``pred`` int64 [n] the
+    predicted code (``classes[pred]`` the label), ``fold`` int64 [n], ``best`` and ``second`` float64 [n] the largest
+    and second largest score (``best - second`` is the margin), ``classes``, and with ``return_scores`` the float64
+    ``scores`` [n, K] (-inf for a class that the cell's fold never saw in training).  Everything on the device is fp64 on
+    the float32 points, in an order fixed by the inputs: the same bits on every run.
+
+    ValueError for fewer than two classes, ``kfold`` outside [2, n], a label length mismatch, non-finite ``x``;
+    NotImplementedError under a process group and past d = 128, 4096 classes or 64 folds."""
+    if D.is_dist():
+        raise NotImplementedError("gaussian_cv_predict is not data-parallel: run it on one rank, outside the process group")
+    n = _shape_of(x)
+    classes, codes, fold = _cv_refusals(labels, n, kfold, seed, kind)
+    return _cv_on_device(_points_on_device(x, device), codes, classes, fold, int(kfold), kind, float(reg_param), return_scores)
+
+
+def classify_points(x_dev, y, kfold, seed, kind, checked=None):
+    """One label set on points already on the device: (acc, ref_labels, pred_labels, the ``gaussian_cv_predict`` dict), the
+    first three lists over the folds with every test set in ascending order of the cell index."""
+    y = np.asarray(y)
+    classes, codes, fold = checked if checked is not None else _cv_refusals(y, int(x_dev.shape[0]), kfold, seed, kind)
+    res = _cv_on_device(x_dev, codes, classes, fold, int(kfold), kind, QDA_REG_PARAM, False)
+    acc, ref_labels, pred_labels = [], [], []
+    for f in range(int(kfold)):
+        test = np.flatnonzero(fold == f)
+        pred = classes[res["pred"][test]]
+        acc.append(float(np.average(y[test] == pred)))                             # sklearn's accuracy_score
+        pred_labels.append(pred)
+        ref_labels.append(y[test])
+    return acc, ref_labels, pred_labels, res
+
+
+def _classifier(data, labels, kfold, seed, kind):
+    if D.is_dist():
+        raise NotImplementedError(f"{kind.upper()}_classifier is not data-parallel: run it on one rank, outside the process group")
+    n = _shape_of(data)
+    checked = {key: _cv_refusals(labels[key], n, kfold, seed, kind) for key in labels}      # every refusal before any device work
+    x_dev = _points_on_device(data, None)
+    acc, ref_labels, pred_labels = {}, {}, {}
+    for key in checked:
+        acc[key], ref_labels[key], pred_labels[key], _ = classify_points(x_dev, labels[key], kfold, seed, kind, checked[key])
+    return acc, ref_labels, pred_labels
+
+
+def QDA_classifier(data, labels, kfold, seed):
+    """The reference's ``QDA_classifier`` (cluster_analysis.py:62-83): ``(acc, ref_labels, pred_labels)``, dicts over the
+    keys of the dict ``labels``, each a list over the folds of ``KFold(n_splits=kfold, random_state=seed, shuffle=True)``:
+    the accuracy (a Python float), the held-out cells' labels and their predictions, in the caller's label values and in
+    ascending order of the cell index.  ``data`` is uploaded once for all keys (a float32 device tensor is used where it
+    lies; anything else is rounded to float32).  The model, its one departure from sklearn (classes of at most d
+    training cells) and the refusals are those of ``gaussian_cv_predict(kind="qda")``."""
+    return _classifier(data, labels, kfold, seed, "qda")
+
+
+def LDA_classifier(data, labels, kfold, seed):
+    """The reference's ``LDA_classifier`` (cluster_analysis.py:38-59): as ``QDA_classifier`` with
+    ``gaussian_cv_predict(kind="lda")``."""
+    return _classifier(data, labels, kfold, seed, "lda")

@@ -461,6 +461,76 @@ int mmvae_debug_state_corr(const float *data, int64_t ld, int64_t n_total, int D
                            const float *state, int64_t lds, int64_t n, int S, const int64_t *offsets, int G, void *ws,
                            size_t ws_bytes, double *r, int64_t *count, int path, void *stream);
 
+/* ---- Gaussian classifiers (mmidas/utils/cluster_analysis.py: QDA_classifier, LDA_classifier) ----
+ * A Gaussian classifier under k-fold cross-validation scores a held-out cell x under class k of the model m fitted to the
+ * other folds as
+ *   score(x, k) = c0[m, k] - |W_mk^T (x - mu_mk)|^2 / 2,   label = the arg-max over k (the lowest index on ties)
+ * with mu the class mean, W a factor of the inverse (regularised, or pooled) covariance and c0 the log prior minus half the
+ * log determinant.  The host builds mu, W and c0 in fp64 from per-group moments; the two entries below are the dense part.
+ *
+ * mmvae_group_moments: x float32 row-major [n, ld], columns 0..d-1 used, the rows ordered by group; offsets int64 [G + 1]
+ *   on the device, group g the rows offsets[g] .. offsets[g + 1] - 1; pivot float32 [d] on the device.  Per group, with
+ *   t = (double)x - (double)pivot (one fp64 rounding, exact where the two exponents are close):
+ *     s [G, d]               sum t
+ *     M [G, d (d + 1) / 2]   sum t t^T, the upper triangle packed row by row: entry (i, j), i <= j, at
+ *                            i d - i (i - 1) / 2 + j - i
+ *   both double on the device; the counts are the offsets' differences.  All moments are about ONE pivot, so they add
+ *   over groups: for a union of groups with N rows, mean = pivot + s / N and covariance = (M - s s^T / N) / (N - ddof).
+ *   The host cannot read device memory without a synchronisation, so offsets that are not non-decreasing from
+ *   offsets[0] = 0 to offsets[G] = n are the CALLER'S CONTRACT: every index derived from them is clamped, so they give
+ *   wrong values and no access outside the arrays.  An empty group gives zeros.  INPUTS MUST BE FINITE.
+ *   Arithmetic: each sum is one fp64 fma chain over the rows of a segment in row order (a product of two doubles is exact
+ *   inside the fma), the segments of a group added in order.  Error of a covariance entry (u = 2^-53): every t carries
+ *   one rounding, a chain of N terms at most N u times the sum of the terms' magnitudes, and by Cauchy-Schwarz
+ *   sum |t_i t_j| <= N sqrt(m_i m_j) with m_i = var_i + (mean_i - pivot_i)^2 = kappa_i var_i; M_ij is then off by at most
+ *   (N + 2) u N sqrt(m_i m_j), s_i s_j / N by at most (2 N + 5) u N sqrt(m_i m_j), and
+ *     |cov_ij - exact cov_ij on the same float32 values| <= 4 (N + 2) kappa u sqrt(var_i var_j) N / (N - ddof),
+ *     kappa = sqrt(kappa_i kappa_j),  kappa_i = 1 + (mean_i - pivot_i)^2 / var_i
+ *   as long as that is small against 1; a pivot near the data's mean keeps kappa near 1.
+ *   The rows are cut into segments of at most 256 that never cross a group boundary; a workgroup owns one segment and
+ *   all d (d + 3) / 2 of its sums, staging 32 rows at a time in LDS as doubles; a last launch adds each group's segments in
+ *   order.  No atomics: bit-identical from run to run, and group g's values are bit for bit those of a call on its rows
+ *   alone.  Four instances of the segment kernel, for d <= 16, 32, 64, 128 (1, 3, 9, 33 sums a thread): the same chains,
+ *   hence the same bits.
+ *   ws: mmvae_group_moments_workspace_bytes(n, d, G) bytes of device memory, 8-byte aligned: with m = G + n / 256 (the
+ *   most segments there can be) m d (d + 3) / 2 doubles of partial sums, m + 1 int64 and G + 1 int32 of tables; 0 for
+ *   arguments that mmvae_group_moments refuses, or a size that size_t cannot hold.
+ *   MMVAE_E_BADARG, before any device work, for a null x / offsets / pivot / ws / s / M, n < 1 or n > 2^31, d < 1, G < 1,
+ *   ld < d, a misaligned ws; MMVAE_E_UNSUPPORTED for d > 128 or G > 2^20; MMVAE_E_WORKSPACE for a ws below the size.
+ * mmvae_debug_group_moments: the same with the instance named: dclass -1 the launcher's rule (the first of 16, 32, 64,
+ *   128 that holds d), 0..3 that instance (MMVAE_E_UNSUPPORTED where d is above it); same bits.
+ *
+ * mmvae_gauss_scores: x float32 row-major [n, ld], columns 0..d-1 used; model int32 [n] on the device, the model (fold)
+ *   that scores cell r, in [0, F); mu double [F, K, d]; W double [F, K, d, d], W[m, k, j, c] the weight of coordinate j
+ *   in column c; c0 double [F, K], -inf for a class that model m does not have; perm int64 [n] on the device, perm[r] the
+ *   caller's index of row r, or NULL for the identity.  label int32 [n], best and second double [n] (the largest and the
+ *   second largest score, -inf where there is none), scores double [n, K] or NULL: all on the device, entry perm[r] the
+ *   value of row r.  The caller sorts the rows by model: a workgroup owns 64 consecutive cells (its waves, 16 at most,
+ *   share them and split the classes into runs, merged in class order) and walks every model that one of its cells
+ *   names, so sorted rows cost one walk a tile (two where a tile straddles two folds) and unsorted rows are slower, not
+ *   wrong.  model values are clamped to [0, F - 1] and perm values to [0, n - 1]: a bad
+ *   table gives wrong values and no access outside the arrays.
+ *   Arithmetic: t_j = (double)x_j - mu_j; each inner product sum_j W[j, c] t_j one fp64 fma chain in coordinate order;
+ *   the squares added by fma in column order; score = c0 - q / 2.  A column of W that is zero adds an exact 0, so a model of
+ *   lower rank is its factor padded with zero columns.  A class with c0 = -inf scores exactly -inf (its mu and W are not
+ *   read) and is never the label unless every class is -inf (label 0, as np.argmax).  Against the same formula summed in
+ *   another order: |score - score'| <= (3 d + 4) u (sum_c (sum_j |W[j, c] t_j|)^2 + |c0|).  A cell's values do not depend
+ *   on the cells beside it; bit-identical from run to run.  One kernel, no debug entry.
+ *   ws: mmvae_gauss_scores_workspace_bytes(n, d, F, K) = 0 bytes: ws may be NULL.
+ *   MMVAE_E_BADARG, before any device work, for a null x / model / mu / W / c0 / label / best / second, n < 1 or
+ *   n > 2^31, d < 1, F < 1, K < 1, ld < d, a misaligned ws; MMVAE_E_UNSUPPORTED for d > 128, K > 4096 or F > 64. */
+size_t mmvae_group_moments_workspace_bytes(int64_t n, int d, int G);
+int mmvae_group_moments(const float *x, int64_t ld, int64_t n, int d, const int64_t *offsets, int G,
+                        const float *pivot, void *ws, size_t ws_bytes, double *s, double *M, void *stream);
+int mmvae_debug_group_moments(const float *x, int64_t ld, int64_t n, int d, const int64_t *offsets, int G,
+                              const float *pivot, void *ws, size_t ws_bytes, double *s, double *M, int dclass,
+                              void *stream);
+size_t mmvae_gauss_scores_workspace_bytes(int64_t n, int d, int F, int K);
+int mmvae_gauss_scores(const float *x, int64_t ld, int64_t n, int d, const int32_t *model, int F, int K,
+                       const double *mu, const double *W, const double *c0, const int64_t *perm /* NULL = identity */,
+                       void *ws /* may be NULL */, size_t ws_bytes, int32_t *label, double *best, double *second,
+                       double *scores /* NULL = not wanted */, void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
