@@ -601,7 +601,8 @@ __host__ __device__ inline u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
     return u32x4{c0, c1, c2, c3};
 }
 
-// Noise streams of the Philox mode.  Counter = (element group, stream id, step); key = seed.
+// Noise streams of the Philox mode.  Counter = (element group, stream id, step); key = seed.  (The contract is stated in
+// DESIGN.md section 20 and restated on the host in tests/noise_restatement.py, to which tests/test_gpu_noise.py holds the kernels.)
 enum { STREAM_XMASK = 0, STREAM_GUMBEL = 1, STREAM_STATE = 2, STREAM_SMASK = 3 };
 
 struct NoiseDev {
@@ -654,7 +655,7 @@ __device__ __forceinline__ bool noise_keep(const NoiseDev& nz, int arm, int kind
 // generator to cost time (25 M elements per arm per step: 21 us of Philox at 16 bits per element), so an element takes
 // only as many random bits as the keep probability needs: m = 1, 2, 4, 8 or 16, the smallest with round((1-p) 2^16)
 // a multiple of 2^(16-m) (p = 0.5: one bit per element; resolution of p: 2^-16).  One Philox call serves the 128/m
-// consecutive genes [cg * 128/m, ...) of one row: counter (cg, row, stream ^ step_hi, step_lo); element i of the
+// consecutive genes [cg * 128/m, ...) of one row: counter (cg, row, stream ^ (step_hi << 8), step_lo); element i of the
 // group owns bits [i m, (i+1) m) of the 128-bit output (word i m / 32), and is kept iff that field < x_thr.
 __device__ __forceinline__ u32x4 xmask_words(const NoiseDev& nz, int arm, uint32_t row, uint32_t cg) {
     return philox4x32(cg, row, (uint32_t)(arm * 4 + STREAM_XMASK) ^ (nz.step_hi << 8), nz.step_lo, nz.k0, nz.k1);

@@ -99,22 +99,27 @@ def _assert_plan(row, engine, eng, hyper, params, xd, xs, kind="STEP", fields=No
     return got
 
 
-def _fused(m, eng, noise_dev, params, xd, xs, state0):
+def _noise(noise_dev):
+    """The call's mmvae_noise: explicit buffers (a dict of device tensors), or a ready one (the Philox mode of
+    tests/test_gpu_noise.py)."""
     from distributed_vae_amd import _native as N
+    return noise_dev if isinstance(noise_dev, N.Noise) else N.make_noise(noise_dev)
+
+
+def _fused(m, eng, noise_dev, params, xd, xs, state0):
     m._bn_flat.copy_(state0[0])
     m._nbt.copy_(state0[1])
     g = torch.zeros_like(m._flat_grad)
-    buf = eng.train_step(m._hyper(1.0, False), N.make_noise(noise_dev), params, m._bn_flat, m._nbt, xd, xs, g, False, None, None, 1,
+    buf = eng.train_step(m._hyper(1.0, False), _noise(noise_dev), params, m._bn_flat, m._nbt, xd, xs, g, False, None, None, 1,
                          0.0).clone()
     torch.cuda.synchronize()
     return buf, g
 
 
 def _api(m, eng, noise_dev, params, xd, xs, state0):
-    from distributed_vae_amd import _native as N
     m._bn_flat.copy_(state0[0])
     m._nbt.copy_(state0[1])
-    hyper, nz = m._hyper(1.0, False), N.make_noise(noise_dev)
+    hyper, nz = m._hyper(1.0, False), _noise(noise_dev)
     g = torch.zeros_like(m._flat_grad)
     eng.forward(hyper, nz, params, m._bn_flat, m._nbt, xd, xs, None, True)
     buf = eng.loss(hyper).clone()
