@@ -230,6 +230,19 @@ def lib():
     L.mmvae_gauss_scores_workspace_bytes.restype = C.c_size_t
     L.mmvae_gauss_scores.argtypes = [vp, i64, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.mmvae_gauss_scores.restype = C.c_int
+    L.mmvae_gram_workspace_bytes.argtypes = [i64, i32]
+    L.mmvae_gram_workspace_bytes.restype = C.c_size_t
+    L.mmvae_gram_segments.argtypes = [i64, i32, C.POINTER(C.c_int64)]
+    L.mmvae_gram.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, C.c_size_t, vp, vp, i32, vp]
+    L.mmvae_debug_gram.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, C.c_size_t, vp, vp, i32, i32, vp]
+    L.mmvae_symm_mul_workspace_bytes.argtypes = [i32, i32]
+    L.mmvae_symm_mul_workspace_bytes.restype = C.c_size_t
+    L.mmvae_symm_mul.argtypes = [vp, i64, i32, vp, i32, vp, vp]
+    L.mmvae_pca_project_workspace_bytes.argtypes = [i64, i32, i32]
+    L.mmvae_pca_project_workspace_bytes.restype = C.c_size_t
+    L.mmvae_pca_project.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, i32, vp, vp]
+    for fn in ("mmvae_gram_segments", "mmvae_gram", "mmvae_debug_gram", "mmvae_symm_mul", "mmvae_pca_project"):
+        getattr(L, fn).restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -910,6 +923,105 @@ def gauss_scores(x: torch.Tensor, model: torch.Tensor, mu: torch.Tensor, W: torc
                                    None, 0, _ptr(label), _ptr(best), _ptr(second), _ptr(scores), _stream(xs.device)),
           "mmvae_gauss_scores")
     return label, best, second, scores
+
+
+# launch_gram / launch_symm_mul / launch_pca_project (csrc/pca.hip; the constants are those of csrc/common.hpp)
+GRAM_TILE = 64                  # GRAM_TILE: rows and columns of G per workgroup
+GRAM_KC = 32                    # GRAM_KC: rows staged in LDS at a time
+GRAM_SEG_ROWS = 256             # GRAM_SEG_ROWS: rows per segment where the rows are cut, until GRAM_MAX_SEGS are in use
+GRAM_MAX_SEGS = 3               # GRAM_MAX_SEGS: segments at most
+GRAM_FILL_TILES = 256           # GRAM_FILL_TILES: upper-triangle tiles from which the rows are not cut
+GRAM_MAX_D = 32768
+PCA_MAX_BLOCK = 64              # RM_CHUNK: the most columns of Q (mmvae_symm_mul) and of V (mmvae_pca_project)
+GRAM_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
+
+
+def gram_segments(n: int, D: int) -> Tuple[int, int]:
+    """(number of segments, rows per segment) that mmvae_gram cuts ``n`` rows of ``D`` columns into; (0, 0) where it refuses."""
+    rows = C.c_int64(0)
+    nseg = int(lib().mmvae_gram_segments(n, D, C.byref(rows)))
+    return nseg, int(rows.value) if nseg else 0
+
+
+def gram_wide(data: torch.Tensor) -> bool:
+    """The launcher's rule: the 16-byte loads where the matrix's base is 16-byte aligned and its row pitch a multiple of 4."""
+    return data.data_ptr() % 16 == 0 and data.stride(0) % 4 == 0
+
+
+def _rows_of(what: str, data: torch.Tensor, rows: Optional[torch.Tensor]):
+    """(the matrix as the kernels read it, the row map or None, n) after the checks the three entries share."""
+    if data.dtype != torch.float32 or data.dim() != 2:
+        raise TypeError(f"{what}: data must be float32 [n_total, D]")
+    Dm = int(data.shape[1])
+    x = data if Dm == 0 or (data.stride(1) == 1 and data.stride(0) >= Dm) else data.contiguous()
+    n = int(data.shape[0])
+    if rows is not None:
+        if rows.dtype != torch.int64 or rows.dim() != 1:
+            raise TypeError(f"{what}: rows must be int64 [n]")
+        rows = rows.contiguous()
+        n = int(rows.numel())
+    return x, rows, n
+
+
+def gram(data: torch.Tensor, pivot: torch.Tensor, rows: Optional[torch.Tensor] = None, cov: bool = False,
+         path: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """mmvae_gram: float32 ``data`` [n_total, D] on the GPU (rows may be strided, columns not; read where it lies), the
+    float32 ``pivot`` [D] and optionally the int64 row map ``rows`` [n] (None: every row) -> (s float64 [D], G float64
+    [D, D]) on the device: with t = (double)x - (double)pivot, s = sum t and G = sum t t^T over the n rows, G exactly
+    symmetric; with ``cov`` G is the unbiased covariance (G - s s^T / n) / (n - 1) instead.  Inputs must be finite.
+    ``path``: "auto" (the launcher's rule), "narrow", "wide" -- the load forms, equal bits."""
+    if any(t.device.type != "cuda" for t in (data, pivot, rows) if t is not None):
+        raise NativeError("gram needs CUDA tensors (no CPU fallback)")
+    if path not in GRAM_PATHS:
+        raise ValueError(f"gram: path must be one of {sorted(GRAM_PATHS)}; got {path!r}")
+    x, rows, n = _rows_of("gram", data, rows)
+    n_total, Dm = (int(v) for v in x.shape)
+    if pivot.dtype != torch.float32 or tuple(pivot.shape) != (Dm,):
+        raise TypeError(f"gram: pivot must be float32 [{Dm}]")
+    piv = pivot.contiguous()
+    s = torch.empty(Dm, dtype=torch.float64, device=x.device)
+    G = torch.empty(Dm, Dm, dtype=torch.float64, device=x.device)
+    ws_bytes = int(lib().mmvae_gram_workspace_bytes(n, Dm))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    check(lib().mmvae_debug_gram(_ptr(x), int(x.stride(0)), n_total, _ptr(rows), n, Dm, _ptr(piv), _ptr(ws), ws_bytes, _ptr(s),
+                                 _ptr(G), int(bool(cov)), GRAM_PATHS[path], _stream(x.device)), "mmvae_gram")
+    return s, G
+
+
+def symm_mul(Cm: torch.Tensor, Q: torch.Tensor) -> torch.Tensor:
+    """mmvae_symm_mul: float64 ``Cm`` [D, D] (rows may be strided, columns not) times float64 ``Q`` [D, b], b <= 64, on the
+    GPU -> Y float64 [D, b] on the device, every entry one fma chain in coordinate order."""
+    if Cm.device.type != "cuda" or Q.device.type != "cuda":
+        raise NativeError("symm_mul needs CUDA tensors (no CPU fallback)")
+    if Cm.dtype != torch.float64 or Cm.dim() != 2 or Cm.shape[0] != Cm.shape[1]:
+        raise TypeError("symm_mul: C must be float64 [D, D]")
+    Dm = int(Cm.shape[0])
+    if Q.dtype != torch.float64 or Q.dim() != 2 or int(Q.shape[0]) != Dm:
+        raise TypeError(f"symm_mul: Q must be float64 [{Dm}, b]")
+    Cc = Cm if Dm == 0 or (Cm.stride(1) == 1 and Cm.stride(0) >= Dm) else Cm.contiguous()
+    Qc = Q.contiguous()
+    b = int(Q.shape[1])
+    Y = torch.empty(Dm, b, dtype=torch.float64, device=Cc.device)
+    check(lib().mmvae_symm_mul(_ptr(Cc), int(Cc.stride(0)), Dm, _ptr(Qc), b, _ptr(Y), _stream(Cc.device)), "mmvae_symm_mul")
+    return Y
+
+
+def pca_project(data: torch.Tensor, mean: torch.Tensor, V: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mmvae_pca_project: float32 ``data`` [n_total, D] on the GPU (read where it lies), float64 ``mean`` [D] and ``V``
+    [D, k], k <= 64, optionally the int64 row map ``rows`` [n] -> Z float64 [n, k] on the device: ((double)x - mean) V, row r
+    of Z the sample rows[r], every entry one fma chain in coordinate order."""
+    if any(t.device.type != "cuda" for t in (data, mean, V, rows) if t is not None):
+        raise NativeError("pca_project needs CUDA tensors (no CPU fallback)")
+    x, rows, n = _rows_of("pca_project", data, rows)
+    n_total, Dm = (int(v) for v in x.shape)
+    if mean.dtype != torch.float64 or tuple(mean.shape) != (Dm,) or V.dtype != torch.float64 or V.dim() != 2 or int(V.shape[0]) != Dm:
+        raise TypeError(f"pca_project: mean must be float64 [{Dm}] and V float64 [{Dm}, k]")
+    mean, V = mean.contiguous(), V.contiguous()
+    k = int(V.shape[1])
+    Z = torch.empty(n, k, dtype=torch.float64, device=x.device)
+    check(lib().mmvae_pca_project(_ptr(x), int(x.stride(0)), n_total, _ptr(rows), n, Dm, _ptr(mean), _ptr(V), k, _ptr(Z),
+                                  _stream(x.device)), "mmvae_pca_project")
+    return Z
 
 
 def to_bf16(data: torch.Tensor) -> torch.Tensor:

@@ -900,6 +900,40 @@ class cpl_mixVAE:
         return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
                 "data_indx": data_indx}
 
+    @torch.no_grad()
+    def classify_pcs(self, dl, labels, num_pc: int = 10, kfold: int = 10, seed=0, kind: str = "qda"):
+        """The linear baseline beside ``classify_latents``: how well the same Gaussian classifier recovers ``labels`` from
+        the top ``num_pc`` principal components of the expression of the cells of ``dl`` ("Linear vs Non-linear embedding" of
+        the reference's clusterability notebook).  The components are those of the cells the loader serves
+        (``utils.pca.pca_fit``: covariance, subspace iteration and projection on the device in fp64), read from a
+        ``DeviceLoader``'s resident matrix through the epoch's row indices, in the loader's order, without a host copy; a
+        plain loader's batches are concatenated on the device.  The model is not used: the answer depends on the data and
+        the labels alone.  ``labels``, the folds, ``kind`` and the returned dict (``"acc"``, ``"ref_labels"``,
+        ``"pred_labels"``, ``"margin"``, ``"fold"``, ``"data_indx"``) are those of ``classify_latents``, and so are the
+        loaders it refuses (``drop_last`` with a remainder, sharding)."""
+        if D.is_dist():
+            raise NotImplementedError("classify_pcs is not data-parallel: run it on one rank, outside the process group")
+        from .utils.dataloader import DeviceLoader
+        from .utils import cluster_analysis as CA
+        from .utils.pca import pca_project
+        resident = isinstance(dl, DeviceLoader)
+        if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
+            raise ValueError("classify_pcs needs a loader that serves every row once (no drop_last, no sharding)")
+        if resident:
+            rows = torch.cat(list(dl.iter_rows()))                         # the epoch's rows of the matrix, in visiting order
+            data, inds = dl.data, rows
+        else:
+            dl = _Replay(dl, self.device)
+            data, rows = dl.matrix(), None
+            inds = torch.cat([torch.as_tensor(i_x).reshape(-1) for _, i_x in dl])
+        data_indx = inds.cpu().numpy()
+        y = np.asarray(labels)[data_indx.astype(np.int64)]
+        checked = CA._cv_refusals(y, int(data_indx.shape[0]), kfold, seed, kind)       # every refusal before any device work
+        z = pca_project(data, num_pc, rows=rows, out="device")
+        acc, ref, pred, res = CA.classify_points(z, y, kfold, seed, kind, checked)
+        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
+                "data_indx": data_indx}
+
 
 class _Replay:
     """The batches ``(x, index)`` of one walk of a loader, kept on the device: ``fill_latents`` and the matrix they form see the

@@ -1164,6 +1164,85 @@ int mmvae_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int32
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+int mmvae_gram_segments(int64_t n, int D, int64_t* seg_rows) {
+    if (n < 2 || n > ((int64_t)1 << 31) || D < 1 || D > GRAM_MAX_D) return 0;
+    return gram_segments(n, D, seg_rows);
+}
+
+size_t mmvae_gram_workspace_bytes(int64_t n, int D) {
+    const int nseg = mmvae_gram_segments(n, D, nullptr);
+    if (nseg == 0) return 0;
+    return sizeof(double) * ((size_t)(nseg - 1) * (size_t)D * (size_t)D + (size_t)nseg * (size_t)D);
+}
+
+// every argument is checked here, on the host, before any device work.  path: -1 the launcher's rule, 0 the narrow loads,
+// 1 the 16-byte loads
+static int gram_checked(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot,
+                        void* ws, size_t ws_bytes, double* s, double* G, int cov, int path, void* stream) {
+    if (!data || !pivot || !ws || !s || !G) { set_error("gram: null pointer"); return MMVAE_E_BADARG; }
+    if (n < 2 || n > ((int64_t)1 << 31)) { set_error("gram: n outside [2, 2^31]"); return MMVAE_E_BADARG; }
+    if (n_total < 1) { set_error("gram: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
+    if (!rows && n > n_total) { set_error("gram: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
+    if (D < 1) { set_error("gram: D = %d below 1", D); return MMVAE_E_BADARG; }
+    if (ld < D) { set_error("gram: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("gram: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+    if (cov < 0 || cov > 1) { set_error("gram: cov = %d outside [0, 1]", cov); return MMVAE_E_BADARG; }
+    if (path < -1 || path > 1) { set_error("gram: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
+    if (D > GRAM_MAX_D) { set_error("gram: D = %d above %d", D, GRAM_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_gram_workspace_bytes(n, D);
+    if (ws_bytes < need) {
+        set_error("gram: workspace of %zu bytes below the %zu needed", ws_bytes, need);
+        return MMVAE_E_WORKSPACE;
+    }
+    if (path == 1 && !gram_wide(data, ld)) {
+        set_error("gram: 16-byte loads need a 16-byte aligned base and ld a multiple of 4 (ld = %lld)", (long long)ld);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_gram(data, ld, n_total, rows, n, D, pivot, ws, s, G, cov, path < 0 ? gram_wide(data, ld) : path == 1,
+                       reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot, void* ws,
+               size_t ws_bytes, double* s, double* G, int cov, void* stream) {
+    return gram_checked(data, ld, n_total, rows, n, D, pivot, ws, ws_bytes, s, G, cov, -1, stream);
+}
+
+int mmvae_debug_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot,
+                     void* ws, size_t ws_bytes, double* s, double* G, int cov, int path, void* stream) {
+    return gram_checked(data, ld, n_total, rows, n, D, pivot, ws, ws_bytes, s, G, cov, path, stream);
+}
+
+// the kernel keeps nothing between launches
+size_t mmvae_symm_mul_workspace_bytes(int D, int b) {
+    (void)D; (void)b;
+    return 0;
+}
+
+int mmvae_symm_mul(const double* C, int64_t ldc, int D, const double* Q, int b, double* Y, void* stream) {
+    if (!C || !Q || !Y) { set_error("symm_mul: null pointer"); return MMVAE_E_BADARG; }
+    if (D < 1 || b < 1) { set_error("symm_mul: D = %d, b = %d: each must be at least 1", D, b); return MMVAE_E_BADARG; }
+    if (ldc < D) { set_error("symm_mul: ldc = %lld below D = %d", (long long)ldc, D); return MMVAE_E_BADARG; }
+    if (D > GRAM_MAX_D || b > RM_CHUNK) { set_error("symm_mul: D = %d, b = %d above %d, %d", D, b, GRAM_MAX_D, RM_CHUNK); return MMVAE_E_UNSUPPORTED; }
+    return launch_symm_mul(C, ldc, D, Q, b, Y, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mmvae_pca_project_workspace_bytes(int64_t n, int D, int k) {
+    (void)n; (void)D; (void)k;
+    return 0;
+}
+
+int mmvae_pca_project(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const double* mean,
+                      const double* V, int k, double* Z, void* stream) {
+    if (!data || !mean || !V || !Z) { set_error("pca_project: null pointer"); return MMVAE_E_BADARG; }
+    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("pca_project: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (n_total < 1) { set_error("pca_project: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
+    if (!rows && n > n_total) { set_error("pca_project: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
+    if (D < 1 || k < 1) { set_error("pca_project: D = %d, k = %d: each must be at least 1", D, k); return MMVAE_E_BADARG; }
+    if (ld < D) { set_error("pca_project: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
+    if (k > RM_CHUNK) { set_error("pca_project: k = %d above %d", k, RM_CHUNK); return MMVAE_E_UNSUPPORTED; }
+    return launch_pca_project(data, ld, n_total, rows, n, D, mean, V, k, Z, reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

@@ -1014,6 +1014,23 @@ int launch_group_moments(const float* x, int64_t ld, int64_t n, int d, const int
 int launch_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int* model, int F, int K, const double* mu,
                         const double* W, const double* c0, const int64_t* perm, int* label, double* best, double* second,
                         double* scores, hipStream_t st);
+// principal components: Gram matrix on the fp64 MFMA, block product, projection (pca.hip)
+constexpr int GRAM_TILE = 64;          // rows and columns of G per workgroup of k_gram_partial: four waves of 32 x 32
+constexpr int GRAM_KC = 32;            // rows of the data staged in LDS at a time: eight MFMA steps of four
+constexpr int GRAM_PITCH = 80;         // doubles per staged row: the four rows an MFMA operand reads fall on disjoint banks
+constexpr int GRAM_SEG_ROWS = 256;     // rows per segment, where the rows are cut at all and until GRAM_MAX_SEGS are in use
+constexpr int GRAM_MAX_SEGS = 3;       // segments at most: the first lands in G, the others in the workspace (2 G at most)
+constexpr int GRAM_FILL_TILES = 256;   // upper-triangle tiles from which the rows are not cut: one workgroup a compute unit
+constexpr int GRAM_MAX_D = 32768;
+constexpr int RM_ROWS = 16;            // rows per workgroup of k_rows_mul: four a wave
+constexpr int RM_CHUNK = 64;           // coordinates staged at a time, and the most columns of the block (b, k <= 64)
+int gram_segments(int64_t n, int D, int64_t* seg_rows);
+bool gram_wide(const float* data, int64_t ld);
+int launch_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot, void* ws,
+                double* s, double* G, int cov, bool wide, hipStream_t st);
+int launch_symm_mul(const double* C, int64_t ldc, int D, const double* Q, int b, double* Y, hipStream_t st);
+int launch_pca_project(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const double* mean,
+                       const double* V, int k, double* Z, hipStream_t st);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

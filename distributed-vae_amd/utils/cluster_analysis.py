@@ -1,6 +1,9 @@
-"""The clusterability analysis of the reference's ``mmidas/utils/cluster_analysis.py``: ``get_SilhScore``, the silhouette
-half of ``cluster_compare`` and the two Gaussian classifiers ``QDA_classifier`` / ``LDA_classifier``, on the device, without
-sklearn.
+"""The clusterability analysis of the reference's ``mmidas/utils/cluster_analysis.py``: ``get_SilhScore``,
+``cluster_compare`` and the two Gaussian classifiers ``QDA_classifier`` / ``LDA_classifier``, on the device, without
+sklearn.  The principal components that ``cluster_compare`` scores on are the one O(N D^2) step of the analysis: at the data
+set's size a minute of host SVD in front of a silhouette of milliseconds.  ``cluster_compare(pca="device")`` takes them from
+``utils/pca.py`` (``mmvae_gram`` on the fp64 MFMA, subspace iteration, ``mmvae_pca_project``); the
+default ``pca="host"`` is numpy's exact SVD, kept as it was.
 
 The reference calls ``sklearn.metrics.silhouette_samples`` / ``silhouette_score`` (euclidean) on the latents: n^2 distances,
 which sklearn computes on the host in float64 through the Gram expansion.  Here the cells are sorted by label on the host,
@@ -137,25 +140,39 @@ def _figure(curves, num_pc):
     return fig
 
 
-def cluster_compare(data, labels, num_pc=0, saving_path=''):
+def cluster_compare(data, labels, num_pc=0, saving_path='', pca="host"):
     """The reference's ``cluster_compare`` (cluster_analysis.py:87-120): ``(fig, silh_smp_score, sil_score, c_size)`` for the
     dict ``labels`` of label arrays -- per entry the per-class mean silhouette samples (classes in ``np.unique`` order), the
     overall score, and the class sizes ordered by ascending mean score -- all on the projection of ``data`` onto its top
     ``num_pc`` principal components.
 
-    The projection is plumbing, not a hot path: numpy's exact SVD of the centred data in fp64 on the host, which is what
-    sklearn's ``PCA(svd_solver="full")`` computes (the silhouette does not see the components' signs).  sklearn's default
-    solver is a randomised one at large sizes, so at those sizes the reference's own numbers are not reproducible either.
-    The projected points are rounded to float32, uploaded once and scored for every entry of ``labels``.  ``fig`` shows what
-    the reference's figure shows, or is None when matplotlib is not installed.  Departure: ``num_pc == 0`` raises ValueError
-    (the reference fails there with an unbound local).  ``saving_path`` is unused, as in the reference."""
+    ``pca="host"`` (the default): numpy's exact SVD of the centred data in fp64 on the host, which is what sklearn's
+    ``PCA(svd_solver="full")`` computes (the silhouette does not see the components' signs); O(N D^2) on the host, about a
+    minute at the data set's size.  ``pca="device"``: ``utils.pca.pca_project`` -- the covariance, the subspace iteration's
+    products and the projection on the device in fp64 on the float32 values of ``data`` (FLOAT64 INPUT IS ROUNDED to
+    float32), the projected points handed to the silhouette without leaving the device; ``num_pc`` <= 32 there (the
+    iteration's block holds at most 64 vectors).  sklearn's default solver is a randomised one at large sizes, so at those
+    sizes the reference's own numbers are not reproducible either.  The projected points are rounded to float32 and scored
+    for every entry of ``labels``.  ``fig`` shows what the reference's figure shows, or is None when matplotlib is not
+    installed.  Departure: ``num_pc == 0`` raises ValueError (the reference fails there with an unbound local).
+    ``saving_path`` is unused, as in the reference."""
     if num_pc <= 0:
         raise ValueError("cluster_compare: num_pc must be positive (the reference computes nothing for num_pc = 0)")
+    if pca not in ("host", "device"):
+        raise ValueError(f"cluster_compare: pca = {pca!r}: one of 'host', 'device'")
     if D.is_dist():
         raise NotImplementedError("cluster_compare is not data-parallel: run it on one rank, outside the process group")
-    z = _project(data, num_pc)
-    encoded = {key: _encode(labels[key], z.shape[0]) for key in labels}           # every refusal before any device work
-    z_dev = _points_on_device(z, None)
+    if pca == "device":
+        shape = tuple(data.shape) if hasattr(data, "shape") else np.asarray(data).shape
+        if len(shape) != 2 or not 0 < num_pc <= min(shape):
+            raise ValueError(f"cluster_compare: num_pc = {num_pc} components of data of shape {shape}")
+        encoded = {key: _encode(labels[key], shape[0]) for key in labels}         # every refusal before any device work
+        from .pca import pca_project
+        z_dev = pca_project(data, num_pc, out="device")
+    else:
+        z = _project(data, num_pc)
+        encoded = {key: _encode(labels[key], z.shape[0]) for key in labels}       # every refusal before any device work
+        z_dev = _points_on_device(z, None)
     silh_smp_score, sil_score, c_size, curves = [], [], [], []
     for key, (classes, codes) in encoded.items():
         s = _samples(z_dev, codes, len(classes))

@@ -531,6 +531,69 @@ int mmvae_gauss_scores(const float *x, int64_t ld, int64_t n, int d, const int32
                        void *ws /* may be NULL */, size_t ws_bytes, int32_t *label, double *best, double *second,
                        double *scores /* NULL = not wanted */, void *stream);
 
+/* ---- principal components (mmidas/utils/cluster_analysis.py: cluster_compare's PCA) ----
+ * The top-k principal subspace of an fp32 matrix needs three dense products: the covariance (once), the covariance times a
+ * block of at most 64 vectors (once per step of a subspace iteration, which the host drives), and the centred data times the
+ * components.  Everything is fp64 on the fp32 values; u = 2^-53.
+ *
+ * mmvae_gram: data float32 row-major [n_total, ld], columns 0..D-1 used, read where it lies; rows int64 [n] on the device,
+ *   the row of data of sample r, or NULL for the rows 0..n-1 (then n <= n_total); pivot float32 [D] on the device.  With
+ *   t = (double)x - (double)pivot (one fp64 rounding):
+ *     s [D]      sum t over the n rows
+ *     G [D, D]   sum t t^T, the full matrix, row pitch D; G[i, j] and G[j, i] are the same bits
+ *   both double on the device.  cov = 0 leaves the raw moments about the pivot; cov = 1 turns G in place into the unbiased
+ *   covariance (G - s s^T / n) / (n - 1); s is the same either way, and mean = pivot + s / n.  Any pivot is valid: it moves
+ *   only kappa below.  Row indices outside [0, n_total) are the CALLER'S CONTRACT: they are clamped, so they give wrong
+ *   values and no access outside the matrix.  INPUTS MUST BE FINITE.
+ *   Arithmetic: only the 64 x 64 tiles with tile_i <= tile_j are computed, on v_mfma_f64_16x16x4_f64: the rows are staged
+ *   32 at a time in LDS as the doubles t and every entry is a chain of MFMA steps of four rows in row order, each product
+ *   exact before it is added.  Against the exact sum of the same t: |G_ij - exact| <= (n + 2) u sum_r |t_ri t_rj|, and for
+ *   cov = 1 the bound derived for mmvae_group_moments above holds with N = n:
+ *     |cov_ij - exact cov_ij on the same float32 values| <= 4 (n + 2) kappa u sqrt(var_i var_j) n / (n - 1).
+ *   Where the upper-triangle tiles alone do not fill the chip (fewer than 256 of them: D <= 1408) and n > 256, the rows are
+ *   cut into at most 3 segments -- of 256 rows while n <= 768, of ceil(n / 3) rounded up to a multiple of 32 beyond
+ *   (mmvae_gram_segments returns their number and writes their length; 0 for arguments mmvae_gram refuses) -- a workgroup
+ *   owns one tile of one segment, and a last launch adds the segments' tiles in segment order, mirrors the upper triangle
+ *   into the lower and applies cov.  No atomics: bit-identical from run to run.  Launches: grid (T, T, segments), T =
+ *   ceil(D / 64), 256 threads, 40 KiB of LDS (workgroups with tile_i > tile_j leave at once); then grid (ceil(D / 256), D).
+ *   ws: mmvae_gram_workspace_bytes(n, D) bytes of device memory, 8-byte aligned: (segments - 1) D^2 doubles of partial
+ *   matrices (the first segment's lands in G) and segments x D doubles of partial s: never more than twice the size of G
+ *   plus 3 D doubles; 0 for arguments that mmvae_gram refuses.
+ *   MMVAE_E_BADARG, before any device work, for a null data / pivot / ws / s / G, n < 2 or n > 2^31, n_total < 1, rows NULL
+ *   with n > n_total, D < 1, ld < D, a misaligned ws, cov outside {0, 1}; MMVAE_E_UNSUPPORTED for D > 32768;
+ *   MMVAE_E_WORKSPACE for a ws below the size.
+ * mmvae_debug_gram: the same with the load form named: path -1 the launcher's rule, 0 one float at a time (any matrix),
+ *   1 the 16-byte loads (MMVAE_E_UNSUPPORTED unless data is 16-byte aligned and ld a multiple of 4); same bits.
+ *
+ * mmvae_symm_mul: Y = C Q.  C double [D, ldc], columns 0..D-1 used (symmetric in its use here; the kernel reads every
+ *   entry and does not rely on it); Q double [D, b] and Y double [D, b], row-major without padding, 1 <= b <= 64; all on the
+ *   device.  Memory-bound: C is read once a call.  Y[i, c] is one fma chain over j = 0..D-1 in that order:
+ *   |Y_ic - exact| <= (D + 1) u sum_j |C_ij Q_jc|; bit-identical from run to run.  A workgroup of 256 threads owns 16
+ *   rows of C and stages 64 coordinates of them and of Q at a time (41 KiB of LDS); grid ceil(D / 16).
+ *   ws: none; mmvae_symm_mul_workspace_bytes is 0.
+ *   MMVAE_E_BADARG, before any device work, for a null C / Q / Y, D < 1, b < 1, ldc < D; MMVAE_E_UNSUPPORTED for
+ *   D > 32768 or b > 64.
+ *
+ * mmvae_pca_project: Z = ((double)x - mean) V.  data, ld, n_total, rows, n, D as for mmvae_gram (n >= 1 here); mean double
+ *   [D], V double [D, k] and Z double [n, k], row-major without padding, 1 <= k <= 64; all on the device.  Row r of Z is
+ *   the sample rows[r].  t_j = (double)x_j - mean_j carries one rounding and Z[r, c] is one fma chain over j = 0..D-1 in
+ *   that order: |Z_rc - exact on the same t| <= (D + 2) u sum_j |t_j V_jc|.  A row's values do not depend on the rows
+ *   beside it; bit-identical from run to run.  The same kernel as mmvae_symm_mul: 16 rows a workgroup, grid ceil(n / 16).
+ *   ws: none; mmvae_pca_project_workspace_bytes is 0.
+ *   MMVAE_E_BADARG, before any device work, for a null data / mean / V / Z, n < 1 or n > 2^31, n_total < 1, rows NULL with
+ *   n > n_total, D < 1, k < 1, ld < D; MMVAE_E_UNSUPPORTED for k > 64. */
+size_t mmvae_gram_workspace_bytes(int64_t n, int D);
+int mmvae_gram_segments(int64_t n, int D, int64_t *seg_rows /* may be NULL */);
+int mmvae_gram(const float *data, int64_t ld, int64_t n_total, const int64_t *rows /* NULL = 0..n-1 */, int64_t n, int D,
+               const float *pivot, void *ws, size_t ws_bytes, double *s, double *G, int cov, void *stream);
+int mmvae_debug_gram(const float *data, int64_t ld, int64_t n_total, const int64_t *rows, int64_t n, int D,
+                     const float *pivot, void *ws, size_t ws_bytes, double *s, double *G, int cov, int path, void *stream);
+size_t mmvae_symm_mul_workspace_bytes(int D, int b);
+int mmvae_symm_mul(const double *C, int64_t ldc, int D, const double *Q, int b, double *Y, void *stream);
+size_t mmvae_pca_project_workspace_bytes(int64_t n, int D, int k);
+int mmvae_pca_project(const float *data, int64_t ld, int64_t n_total, const int64_t *rows /* NULL = 0..n-1 */, int64_t n,
+                      int D, const double *mean, const double *V, int k, double *Z, void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
