@@ -115,16 +115,21 @@ struct TileRegsT {
     uint32_t wd[BITS ? NQ : 1];   // keep-mask words (only operands that carry a mask hold them)
 };
 
-// Loads go through buffer instructions: the operand's base sits in an SGPR descriptor and a piece is addressed by ONE
-// 32-bit per-lane byte offset computed where it is used (two integer ops), so no 64-bit pointers stay live across the
-// pipeline (sixteen of them per thread cost 32 VGPRs and pushed the kernel into scratch).  Offsets are clamped into the
-// matrix; what must read as zero is selected at the LDS store.  Every operand has ld % 4 == 0 and < 4 GB per arm.
+// Loads go through buffer instructions: the operand's base sits in an SGPR descriptor and a piece is addressed by a
+// 32-bit per-lane byte offset that is computed ONCE per block tile (PieceCtx) plus a uniform term for what is the same for
+// every lane: the K tile and the piece's own step (one addition per request).  No 64-bit pointers stay live across the pipeline (sixteen of them
+// per thread cost 32 VGPRs and pushed the kernel into scratch) and nothing is clamped: a piece that does not exist -- a row
+// beyond the operand, a k beyond the K range -- asks for the lane offset PIECE_OOB, which lies past every descriptor's
+// range, so the load returns 0 and touches no memory.
+// Every operand has ld % 4 == 0, K % 4 == 0 and < 4 GB per arm.
+constexpr unsigned PIECE_OOB = 0xFFFFFFF0u;
 struct OperandDev {
-    __amdgpu_buffer_rsrc_t rs, rb;   // matrix, mask words
+    __amdgpu_buffer_rsrc_t rs, rb;   // matrix, mask words (no mask: a range of 0 bytes)
     __amdgpu_buffer_rsrc_t rm;       // row map (row indirection; see Operand::rowmap)
     const unsigned* mp;              // the same map as a pointer: K-minor operands read it with scalar loads (map_request)
     int ld, rows, K, wpr, ones_row;
     bool bits;
+    unsigned nomask;                 // ORed onto a mask word: 0, or all ones for an operand without a mask (whose words read 0)
     float4 bn_sub, bn_mul;           // BN = true (k_x3_small): this thread's four rows read (v - bn_sub) * bn_mul
 };
 template <bool KMINOR>
@@ -136,9 +141,10 @@ __device__ __forceinline__ OperandDev make_operand_dev(const Operand& o) {
                                              (int)((o.rowmap ? o.map_n : 1) * 4), 0x00020000);
     d.mp = o.rowmap;
     d.bits = o.bits != nullptr;
+    d.nomask = d.bits ? 0u : 0xFFFFFFFFu;
     const int64_t nb = (KMINOR ? (int64_t)o.K : (int64_t)o.rows) * o.wpr;
     d.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.bits ? o.bits : reinterpret_cast<const uint32_t*>(o.ptr)), 0,
-                                             (int)((d.bits ? nb : 1) * 4), 0x00020000);
+                                             (int)((d.bits ? nb : 0) * 4), 0x00020000);
     d.ld = (int)o.ld; d.rows = o.rows; d.K = o.K; d.wpr = o.wpr; d.ones_row = o.ones_row;
     return d;
 }
@@ -151,58 +157,19 @@ __device__ __forceinline__ void piece_ph(int q, int& p, int& h) {
     if (!KMINOR && NP != 1) { p = q; h = 0; }
     else { p = q >> 1; h = q & 1; }
 }
-template <bool KMINOR, bool BITS = true, int NP = 1>
-__device__ __forceinline__ void quad_load(TileRegsT<BITS, Eng<NP>::NQ>& t, const OperandDev& o, int r0, int k0, int kend, int q) {
-    const int tid = threadIdx.x & 255;     // (the ping-pong kernel runs two 256-thread groups per workgroup)
-    int p, h;
-    piece_ph<KMINOR, NP>(q, p, h);
-    int off, woff;
-    if (!KMINOR) {
-        const int row = r0 + (tid >> 3) + 32 * p;
-        const int rc = min(row, o.rows - 1);
-        const int k = k0 + ((tid & 7) + 8 * h) * 4;
-        const bool ok = row < o.rows && k + 3 < kend && k + 3 < o.K;     // K % 4 == 0, k0 % 4 == 0
-        off = rc * o.ld + (ok ? k : 0);
-        woff = rc * o.wpr + ((ok ? k : 0) >> 5);
-    } else {
-        // row % 4 == 0 and ld % 4 == 0: the four floats stay inside the memory row whenever row < ld
-        const int k = k0 + 2 * ((tid >> 5) + 8 * p) + h;
-        const int kc = min(k, o.K - 1);
-        const int row = r0 + (tid & 31) * 4;
-        off = kc * o.ld + (row < o.ld ? row : 0);
-        woff = kc * o.wpr + (min(row, o.rows - 1) >> 5);
-    }
-    t.v[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(o.rs, off * 4, 0, 0));
-    if constexpr (BITS) t.wd[q] = o.bits ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(o.rb, woff * 4, 0, 0) : 0xFFFFFFFFu;
-}
-
-// The same request through a row map (Operand::rowmap).  ro[q]: the element offset of piece q's memory row, i.e. of the logical
-// row r0 + (tid >> 3) + 32 p (KMAJOR: the same for every K tile, requested once by ro_init) or of k (KMINOR: a new set per K
-// tile, from map_request / map_offsets below).
-template <bool KMINOR, int NP>
-__device__ __forceinline__ void quad_load_idx(TileRegsT<true, Eng<NP>::NQ>& t, const OperandDev& o, int r0, int k0, int kend, int q,
-                                              const unsigned (&ro)[Eng<NP>::NQ]) {
-    const int tid = threadIdx.x & 255;
-    int p, h;
-    piece_ph<KMINOR, NP>(q, p, h);
-    int off, woff;
-    if (!KMINOR) {
-        const int row = r0 + (tid >> 3) + 32 * p;
-        const int rc = min(row, o.rows - 1);
-        const int k = k0 + ((tid & 7) + 8 * h) * 4;
-        const bool ok = row < o.rows && k + 3 < kend && k + 3 < o.K;
-        off = (int)ro[q] + (ok ? k : 0);
-        woff = rc * o.wpr + ((ok ? k : 0) >> 5);
-    } else {
-        const int k = k0 + 2 * ((tid >> 5) + 8 * p) + h;
-        const int kc = min(k, o.K - 1);
-        const int row = r0 + (tid & 31) * 4;
-        off = (int)ro[q] + (row < o.ld ? row : 0);
-        woff = kc * o.wpr + (min(row, o.rows - 1) >> 5);
-    }
-    t.v[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(o.rs, off * 4, 0, 0));
-    t.wd[q] = o.bits ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(o.rb, woff * 4, 0, 0) : 0xFFFFFFFFu;
-}
+// What a thread needs of an operand's block tile at r0 and does not depend on the K tile, computed once per block tile.  Per K
+// tile and piece only uniform terms are added (quad_load: one scalar operand; quad_store: immediate LDS offsets).
+struct PieceCtx {
+    unsigned vb;       // lane byte offset of the thread's pieces: piece 0 of the K tile at k = 0 (K-minor through a row map: its rows only)
+    unsigned vr[4];    // K-major through a row map: one lane offset per row pass instead (the map's entries, requested here)
+    unsigned wb;       // ... of its mask words
+    int lim;           // K-major: rows from the thread's first one to the operand's end (row pass p exists iff 32 p < lim);
+                       // K-minor: one bit per row of the piece that exists
+    int sh;            // bit of a mask word that belongs to the piece's first element
+    int kl;            // K-major: last k of piece 0 inside the K tile; K-minor: its k
+    int one;           // K-minor: bit e set iff the piece's row e is the ones row
+    int li;            // dword index of piece 0 inside an LDS plane
+};
 // K-minor operand through its row map: piece q of a thread lies in memory row k = k0 + 2 ((tid >> 5) + 8 p) + h with p = q >> 1,
 // h = q & 1, i.e. k0 + 4 wave + 16 p + {0, 1} for the lower half of a wave and + {2, 3} for the upper one: the map entries a
 // wave needs for one K tile are KT / 16 aligned groups of four consecutive words, the same for all its lanes.  They are
@@ -230,24 +197,74 @@ __device__ __forceinline__ void map_offsets(unsigned (&ro)[Eng<NP>::NQ], const M
         ro[q] = hi ? mr.s[p][2 + h] : mr.s[p][h];
     }
 }
-template <int NP>     // K-major operand: the offsets of this thread's rows, once per block tile
-__device__ __forceinline__ void ro_init(unsigned (&ro)[Eng<NP>::NQ], const OperandDev& o, int r0) {
-    const int tid = threadIdx.x & 255;
+// IDX: the operand is read through its row map (Operand::rowmap).  K-major: the map entries of the thread's four row passes are
+// requested here, once per block tile; K-minor: a new set ro[] per K tile, from map_request / map_offsets above.
+template <bool KMINOR, int NP, bool IDX = false>
+__device__ __forceinline__ PieceCtx piece_ctx(const OperandDev& o, int r0) {
+    const int tid = threadIdx.x & 255;     // (the ping-pong kernels run two 256-thread groups per workgroup)
+    PieceCtx c = {};
+    if (!KMINOR) {
+        const int kq = tid & 7, rr = tid >> 3, row = r0 + rr;
+        c.vb = ((unsigned)row * (unsigned)o.ld + kq * 4u) * 4u;
+        if constexpr (IDX) {
 #pragma unroll
-    for (int q = 0; q < Eng<NP>::NQ; ++q) {
-        int p, h;
-        piece_ph<false, NP>(q, p, h);
-        ro[q] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(o.rm, min(r0 + (tid >> 3) + 32 * p, o.rows - 1) * 4, 0, 0);
+            for (int p = 0; p < 4; ++p)
+                c.vr[p] = ((unsigned)__builtin_amdgcn_raw_buffer_load_b32(o.rm, min(row + 32 * p, o.rows - 1) * 4, 0, 0) + kq * 4u) * 4u;
+        }
+        c.wb = (unsigned)row * (unsigned)o.wpr * 4u;
+        c.lim = o.rows - row;
+        c.sh = kq * 4;
+        c.kl = kq * 4 + 3;
+        c.li = rr * Eng<NP>::LDB + kq * 2;
+    } else {
+        // row % 4 == 0 and ld % 4 == 0: the four floats stay inside the memory row whenever row < rows <= ld
+        const int r4 = (tid & 31) * 4, kp = tid >> 5, row = r0 + r4;
+        c.vb = IDX ? row * 4u : (2u * kp * (unsigned)o.ld + row) * 4u;
+        c.wb = (2u * kp * (unsigned)o.wpr + (row >> 5)) * 4u;
+        c.lim = (1 << min(max(o.rows - row, 0), 4)) - 1;
+        c.sh = row & 31;
+        c.kl = 2 * kp;
+        const int e = o.ones_row - row;
+        c.one = (o.ones_row >= 0 && e >= 0 && e < 4) ? 1 << e : 0;
+        c.li = (2 * kp * Eng<NP>::LDK + r4) >> 1;     // LDK and r4 are multiples of 4 bf16
     }
+    return c;
+}
+// Request piece q of the K tile at k0 (k0 % 32 == 0; kend <= K, kend % 4 == 0).  No branch and no condition around a load: a
+// piece either exists entirely or asks for PIECE_OOB.  ro: K-minor through a row map, the element offsets of the pieces' memory rows.
+template <bool KMINOR, bool BITS = true, int NP = 1, bool IDX = false>
+__device__ __forceinline__ void quad_load(TileRegsT<BITS, Eng<NP>::NQ>& t, const OperandDev& o, const PieceCtx& c, int k0, int kend, int q,
+                                          const unsigned* ro = nullptr) {
+    int p, h;
+    piece_ph<KMINOR, NP>(q, p, h);
+    bool ok;
+    unsigned vo, so, swo;     // lane offset of the values; uniform terms of the values' and of the mask word's offset
+    if (!KMINOR) {
+        ok = 32 * p < c.lim && k0 + 32 * h + c.kl < kend;
+        vo = IDX ? c.vr[p] : c.vb;
+        so = IDX ? (unsigned)(k0 + 32 * h) * 4u : (32u * p * (unsigned)o.ld + k0 + 32 * h) * 4u;
+        swo = (32u * p * (unsigned)o.wpr + (k0 >> 5) + h) * 4u;
+    } else {
+        const int ks = k0 + 16 * p + h;
+        ok = c.lim != 0 && ks + c.kl < kend;
+        vo = IDX ? ro[q] * 4u + c.vb : c.vb;
+        so = IDX ? 0u : (unsigned)ks * (unsigned)o.ld * 4u;
+        swo = (unsigned)ks * (unsigned)o.wpr * 4u;
+    }
+    // (the uniform terms are added to the lane offset and the scalar offset stays 0, as in k_x3_fc11g's request_x: whether the
+    // range check adds a scalar offset to the lane offset has not been established for these descriptors, and if it does,
+    // PIECE_OOB plus the term wraps back into the range.  This form is right under either rule.)
+    t.v[q] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(o.rs, (int)(ok ? vo + so : PIECE_OOB), 0, 0));
+    if constexpr (BITS) t.wd[q] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(o.rb, (int)(ok ? c.wb + swo : PIECE_OOB), 0, 0);
 }
 // the indexed operand's offsets for its first K tile (and, K-minor, the request for the second one's)
 template <bool KMINOR, int NP>
-__device__ __forceinline__ void idx_begin(unsigned (&ro)[Eng<NP>::NQ], MapRegs<NP>& mr, const OperandDev& o, int r0, int kfirst) {
+__device__ __forceinline__ void idx_begin(unsigned (&ro)[Eng<NP>::NQ], MapRegs<NP>& mr, const OperandDev& o, int kfirst) {
     if constexpr (KMINOR) {
         map_request<NP>(mr, o, kfirst);
         map_offsets<NP>(ro, mr);
         map_request<NP>(mr, o, kfirst + Eng<NP>::KT);
-    } else ro_init<NP>(ro, o, r0);
+    }
 }
 // ... and for the K tile at kld, at the head of the staging phase that requests it
 template <bool KMINOR, int NP>
@@ -257,51 +274,52 @@ __device__ __forceinline__ void idx_next(unsigned (&ro)[Eng<NP>::NQ], MapRegs<NP
         map_request<NP>(mr, o, kld + Eng<NP>::KT);
     }
 }
-template <bool KMINOR, bool BITS = true, int NP = 1, bool BN = false>
-__device__ __forceinline__ void quad_store(unsigned* __restrict__ T, const TileRegsT<BITS, Eng<NP>::NQ>& t, const OperandDev& o, int r0,
+// Write piece q of the K tile at k0 to the LDS image.  What does not exist arrived as 0 (quad_load), so only the keep-mask and
+// the rows of a K-minor piece beyond the operand are masked here.  BN / ONES (K-minor): the BatchNorm-normalised form and the ones
+// row, compiled only where the operand can carry them: k_x3_small's Q (both) and the B operand of the bf16 engine's dW11 forms
+// (the fp32x3 GEMMs take their ones column from the slice planes)
+template <bool KMINOR, bool BITS = true, int NP = 1, bool BN = false, bool ONES = BN>
+__device__ __forceinline__ void quad_store(unsigned* __restrict__ T, const TileRegsT<BITS, Eng<NP>::NQ>& t, const OperandDev& o, const PieceCtx& c,
                                            int k0, int kend, int q) {
-    constexpr int LDBv = Eng<NP>::LDB, PLANE = Eng<NP>::PLANE;
-    const int tid = threadIdx.x & 255;
+    constexpr int PLANE = Eng<NP>::PLANE;
     int p, h;
     piece_ph<KMINOR, NP>(q, p, h);
-    float x[4];
+    const float4 v = t.v[q];
+    float x[4] = {v.x, v.y, v.z, v.w};
     int idx;        // dword index of the 8-byte LDS store inside a plane
     if (!KMINOR) {
-        const int kq = tid & 7, rr = tid >> 3;
-        const int row = r0 + rr + 32 * p;
-        const int k = k0 + (kq + 8 * h) * 4;
-        const bool ok = row < o.rows && k + 3 < kend && k + 3 < o.K;
         // keep bit e of nib -> an all-ones / all-zeros word (v_bfe_i32) ANDed onto the value: two VALU instructions per
         // element and no compare -> SGPR -> select chains
-        const int nib = ok ? (BITS ? (int)(t.wd[q] >> (k & 31)) : 0xF) : 0;
-        const float4 v = t.v[q];
-        const float vv[4] = {v.x, v.y, v.z, v.w};
+        if constexpr (BITS) {
+            const int nib = (int)((t.wd[q] | o.nomask) >> c.sh);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(__float_as_uint(vv[e]) & (unsigned)__builtin_amdgcn_sbfe(nib, e, 1));
-        idx = (rr + 32 * p) * LDBv + (kq + 8 * h) * 2;
+            for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(__float_as_uint(x[e]) & (unsigned)__builtin_amdgcn_sbfe(nib, e, 1));
+        }
+        idx = c.li + 32 * p * Eng<NP>::LDB + 16 * h;
     } else {
         // natural layout [k][row] (rows contiguous, Eng<NP>::LDK bf16 per k): one 8-byte store per (k, four rows); the MFMA
         // fragments come out of it through the transposing LDS read (ds_read_b64_tr_b16, see frag8)
-        const int r4 = (tid & 31) * 4, kp = tid >> 5;
-        const int kl = 2 * (kp + 8 * p) + h, k = k0 + kl;
-        const bool kok = k < kend && k < o.K;
-        const int nrow = min(max(o.rows - (r0 + r4), 0), 4);          // rows of this piece that exist
-        const int nib = kok ? ((BITS ? (int)(t.wd[q] >> ((r0 + r4) & 31)) : 0xF) & ((1 << nrow) - 1)) : 0;
-        const float4 v = t.v[q];
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(__float_as_uint(vv[e]) & (unsigned)__builtin_amdgcn_sbfe(nib, e, 1));
-        if constexpr (BN) {     // BatchNorm-normalised input, as k_gemm_tn: (v - mean) * rstd; rows / k that do not exist stay 0
-            const float sb[4] = {o.bn_sub.x, o.bn_sub.y, o.bn_sub.z, o.bn_sub.w}, ml[4] = {o.bn_mul.x, o.bn_mul.y, o.bn_mul.z, o.bn_mul.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = ((nib >> e) & 1) ? (x[e] - sb[e]) * ml[e] : 0.f;
+        const int kt = 16 * p + h;
+        int nib = BITS ? (int)((t.wd[q] | o.nomask) >> c.sh) & c.lim : c.lim;      // rows of this piece that exist (and are kept)
+        int one = c.one;
+        if constexpr (ONES) {       // a k that does not exist stays 0 under these forms too
+            const bool kok = k0 + kt + c.kl < kend;
+            nib = kok ? nib : 0;
+            one = kok ? one : 0;
         }
-        if (o.ones_row >= 0) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (kok && r0 + r4 + e == o.ones_row) x[e] = 1.f;
+        for (int e = 0; e < 4; ++e) {
+            const unsigned m = (unsigned)__builtin_amdgcn_sbfe(nib, e, 1);
+            if constexpr (BN) {     // BatchNorm-normalised input, as k_gemm_tn: (v - mean) * rstd; rows / k that do not exist stay 0
+                const float sb[4] = {o.bn_sub.x, o.bn_sub.y, o.bn_sub.z, o.bn_sub.w}, ml[4] = {o.bn_mul.x, o.bn_mul.y, o.bn_mul.z, o.bn_mul.w};
+                x[e] = __uint_as_float(__float_as_uint((x[e] - sb[e]) * ml[e]) & m);
+            } else x[e] = __uint_as_float(__float_as_uint(x[e]) & m);
+            if constexpr (ONES) {
+                const unsigned m1 = (unsigned)__builtin_amdgcn_sbfe(one, e, 1);
+                x[e] = __uint_as_float((__float_as_uint(x[e]) & ~m1) | (__float_as_uint(1.f) & m1));
+            }
         }
-        idx = (kl * Eng<NP>::LDK + r4) >> 1;     // LDK and r4 are multiples of 4 bf16
+        idx = c.li + ((kt * Eng<NP>::LDK) >> 1);
     }
     if constexpr (NP == 1) {
         uint2 w;
@@ -389,14 +407,16 @@ __device__ __forceinline__ void oct_map_offsets(unsigned (&ro)[8], const MapRegs
 
 template <bool KMINOR, bool BITS = true, int NP = 1>
 __device__ __forceinline__ void tile_load(TileRegsT<BITS, Eng<NP>::NQ>& t, const OperandDev& o, int r0, int k0, int kend) {
+    const PieceCtx c = piece_ctx<KMINOR, NP>(o, r0);
 #pragma unroll
-    for (int q = 0; q < Eng<NP>::NQ; ++q) quad_load<KMINOR, BITS, NP>(t, o, r0, k0, kend, q);
+    for (int q = 0; q < Eng<NP>::NQ; ++q) quad_load<KMINOR, BITS, NP>(t, o, c, k0, kend, q);
 }
 template <bool KMINOR, bool BITS = true, int NP = 1>
 __device__ __forceinline__ void tile_store(unsigned* __restrict__ T, const TileRegsT<BITS, Eng<NP>::NQ>& t, const OperandDev& o, int r0,
                                            int k0, int kend) {
+    const PieceCtx c = piece_ctx<KMINOR, NP>(o, r0);
 #pragma unroll
-    for (int q = 0; q < Eng<NP>::NQ; ++q) quad_store<KMINOR, BITS, NP>(T, t, o, r0, k0, kend, q);
+    for (int q = 0; q < Eng<NP>::NQ; ++q) quad_store<KMINOR, BITS, NP>(T, t, o, c, k0, kend, q);
 }
 
 // MFMA fragment of a 32-row tile (rows rb .. rb + 31 of the block tile), K step s (16 k's): lane l holds row l % 32,
@@ -435,11 +455,13 @@ __device__ __forceinline__ PlaneDev make_plane_dev(const Operand& o, int arm) {
 }
 template <bool KMINOR>
 __device__ __forceinline__ void plane_load(PlaneRegs& t, const PlaneDev& o, int r0, int k0, int j) {
-    const int tid = threadIdx.x & 255, pl = j >> 1, id = tid + 256 * (j & 1);
-    int off;   // elements
-    if (!KMINOR) off = pl * o.plane + (r0 + (id >> 2)) * o.ld + k0 + 8 * (id & 3);      // row id >> 2, k octet id & 3
-    else off = pl * o.plane + (k0 + (id >> 4)) * o.ld + r0 + 8 * (id & 15);              // k id >> 4, row octet id & 15
-    t.v[j] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(o.rs, off * 2, 0, 0));
+    // piece id = tid + 256 (j & 1) of plane j >> 1.  The lane offset is the thread's own (the same for every piece and K tile);
+    // plane, tile origin, K tile and the piece's half ride in the scalar offset (the planes are padded: no bounds)
+    const int tid = threadIdx.x & 255, pl = j >> 1, hi = j & 1;
+    int vo, so;   // elements
+    if (!KMINOR) { vo = (tid >> 2) * o.ld + 8 * (tid & 3); so = pl * o.plane + (r0 + 64 * hi) * o.ld + k0; }      // row id >> 2, k octet id & 3
+    else { vo = (tid >> 4) * o.ld + 8 * (tid & 15); so = pl * o.plane + (k0 + 16 * hi) * o.ld + r0; }             // k id >> 4, row octet id & 15
+    t.v[j] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(o.rs, vo * 2, so * 2, 0));
 }
 template <bool KMINOR>
 __device__ __forceinline__ void plane_store(unsigned* __restrict__ T, const PlaneRegs& t, int j) {
@@ -599,28 +621,41 @@ __device__ __forceinline__ void mfma_ktile(f32x16 (&acc)[2][2], const unsigned* 
 }
 
 // The tile epilogue: accumulator register r of tile (i, j) is row m0 + 64 wm + 32 i + acc_row(r), column
-// n0 + 64 wn + 32 j + (lane & 31).
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int lane, int arm) {
-    const int l31 = lane & 31;
-    float* out = g.so.out + (int64_t)blockIdx.y * g.so.ks_stride + (int64_t)arm * g.so.arm_stride;
+// n0 + 64 wn + 32 j + (lane & 31) of out[M][N] (row pitch ld).  One buffer descriptor per block: it starts at the tile's first
+// row and its range ends with the last row that exists, so rows beyond M are dropped by the hardware, and a lane whose column
+// lies beyond N asks for an offset past every range -- no branch and no 64-bit address per element.  The whole offset is the
+// per-lane one and the scalar offset is 0, so the range check sees all of it.  128 ld floats stay far below TILE_OOB.
+constexpr unsigned TILE_OOB = 0x80000000u;
+__device__ __forceinline__ void tile_out(float* out, int ld, int M, int N, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int lane) {
+    // (uniform, but hipcc forms the clamp on the vector unit: a descriptor in VGPRs would cost every store a waterfall loop)
+    const int rows = __builtin_amdgcn_readfirstlane(min(max(M - m0, 0), BT));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out + (int64_t)m0 * ld, 0, rows * ld * 4, 0x00020000);
+    const unsigned ldb = (unsigned)ld * 4u;
+    const unsigned row_l = (unsigned)(64 * wm + 4 * (lane >> 5)) * ldb;      // the lane's part of its accumulator rows (acc_row)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + 64 * wn + 32 * j + (lane & 31);
+        const unsigned o_lane = col < N ? row_l + (unsigned)col * 4u : TILE_OOB;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + 64 * wn + 32 * j + l31;
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 64 * wm + 32 * i + acc_row(r, lane);
-                if (row < g.so.M && col < g.so.N) out[(int64_t)row * g.so.ld + col] = acc[i][j][r];
+                const float v = acc[i][j][r];      // (a copy: __builtin_bit_cast of the vector ELEMENT reads element 0)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, (int)(o_lane + (unsigned)(32 * i + acc_row(r, 0)) * ldb), 0, 0);
             }
-        }
+    }
+}
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int lane, int arm) {
+    tile_out(g.so.out + (int64_t)blockIdx.y * g.so.ks_stride + (int64_t)arm * g.so.arm_stride, g.so.ld, g.so.M, g.so.N, acc, m0, n0, wm, wn, lane);
 }
 
 // C tile -> slab.  grid (tiles_m * tiles_n, KS, A): block (m tile, n tile) x k range ks x arm.  Tile t + 1 is written to
 // the second LDS buffer while tile t is multiplied (one barrier per K tile); a piece's registers request tile t + 2 as
 // soon as they have been written out for tile t + 1.
 // IDX: 1 / 2 = the A / B operand through its row map (see k_x3_gemm); S16: bit 0 / bit 1 = the A / B operand is bf16 in memory
-template <bool AMINOR, bool BMINOR, int IDX = 0, int S16 = 0>
+// XMASK: x~ -- fc1's A, dW1's B -- may carry its keep-mask (a null mask then reads as all ones: OperandDev::nomask); the forms
+// without it request no mask words at all (as out-of-range requests they cost dW11 on a bf16 dZ11 10 us of 105)
+template <bool AMINOR, bool BMINOR, int IDX = 0, int S16 = 0, bool XMASK = true>
 __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
     const GemmArgs g = g_in;
     __shared__ __attribute__((aligned(16))) unsigned As[2][BT * LDB];   // two K tiles in LDS: tile t is multiplied while tile
@@ -639,12 +674,17 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
     const int kb = (int)(((int64_t)blockIdx.y * nkt) / g.KS) * KT;
     const int ke = min(g.K, (int)(((int64_t)(blockIdx.y + 1) * nkt) / g.KS) * KT);
     f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
-    TileRegsT<true> ta, tb;
+    constexpr bool ABITS = XMASK && !AMINOR && !BMINOR, BBITS = XMASK && AMINOR && BMINOR;
+    TileRegsT<ABITS> ta;
+    TileRegsT<BBITS> tb;
     OctRegs t16a, t16b;                // S16 (bit 0: A, bit 1: B): a bf16-source operand's pieces (ta / tb of that operand stay unused)
-    unsigned ro[Eng<1>::NQ] = {};      // IDX: element offsets of the indexed operand's memory rows (see quad_load_idx)
+    unsigned ro[Eng<1>::NQ] = {};      // IDX: element offsets of the indexed operand's memory rows (K-minor fp32 pieces: quad_load; bf16 pieces: oct_load)
     MapRegs<1> mr = {};
     static_assert(IDX == 0 || S16 == 0 || (S16 & IDX) != 0, "row map and bf16 storage: the indexed operand (x) is a bf16 one");
     constexpr bool A16 = (S16 & 1) != 0, B16 = (S16 & 2) != 0;
+    constexpr bool AIDX = IDX == 1 && !A16, BIDX = IDX == 2 && !B16;     // through the row map as fp32 pieces
+    constexpr bool BONES = AMINOR && BMINOR && IDX == 0;                  // B may carry a ones row: the dW11 forms (launch_slab_gemm checks)
+    const PieceCtx ca = piece_ctx<AMINOR, 1, AIDX>(oa, m0), cb = piece_ctx<BMINOR, 1, BIDX>(ob, n0);
     // Software pipeline at the granularity of one 16-byte piece: a piece of tile t + 1 is rounded and written to LDS
     // and the SAME registers immediately request the piece of tile t + 2, so sixteen loads per thread are in flight
     // all the time and every load has a whole iteration (the other fifteen pieces, the MFMAs, the barrier) to land.
@@ -667,11 +707,8 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
                     if constexpr (LOAD) oct_load<AMINOR, IDX == 1>(t16a, oa, m0, kld, ke, q, ro);
                 }
             } else {
-                quad_store<AMINOR>(Ad, ta, oa, m0, kst, ke, q);
-                if constexpr (LOAD) {
-                    if constexpr (IDX == 1) quad_load_idx<AMINOR, 1>(ta, oa, m0, kld, ke, q, ro);
-                    else quad_load<AMINOR>(ta, oa, m0, kld, ke, q);
-                }
+                quad_store<AMINOR, ABITS>(Ad, ta, oa, ca, kst, ke, q);
+                if constexpr (LOAD) quad_load<AMINOR, ABITS, 1, AIDX>(ta, oa, ca, kld, ke, q, ro);
             }
             if constexpr (B16) {
                 if (q < 4) {
@@ -679,11 +716,8 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
                     if constexpr (LOAD) oct_load<BMINOR, IDX == 2>(t16b, ob, n0, kld, ke, q, ro);
                 }
             } else {
-                quad_store<BMINOR>(Bd, tb, ob, n0, kst, ke, q);
-                if constexpr (LOAD) {
-                    if constexpr (IDX == 2) quad_load_idx<BMINOR, 1>(tb, ob, n0, kld, ke, q, ro);
-                    else quad_load<BMINOR>(tb, ob, n0, kld, ke, q);
-                }
+                quad_store<BMINOR, BBITS, 1, false, BONES>(Bd, tb, ob, cb, kst, ke, q);
+                if constexpr (LOAD) quad_load<BMINOR, BBITS, 1, BIDX>(tb, ob, cb, kld, ke, q, ro);
             }
         }
     };
@@ -702,11 +736,14 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) oct_load<MINOR, IDXD>(t16, o, r0, kb, ke, q, ro);
-        } else if constexpr (IDXD) {
-            idx_begin<MINOR, 1>(ro, mr, o, r0, kb);
+        } else {
+            if constexpr (IDXD) idx_begin<MINOR, 1>(ro, mr, o, kb);
 #pragma unroll
-            for (int q = 0; q < Eng<1>::NQ; ++q) quad_load_idx<MINOR, 1>(ISA ? ta : tb, o, r0, kb, ke, q, ro);
-        } else tile_load<MINOR>(ISA ? ta : tb, o, r0, kb, ke);
+            for (int q = 0; q < Eng<1>::NQ; ++q) {
+                if constexpr (ISA) quad_load<MINOR, ABITS, 1, IDXD>(ta, o, ca, kb, ke, q, ro);
+                else quad_load<MINOR, BBITS, 1, IDXD>(tb, o, cb, kb, ke, q, ro);
+            }
+        }
     };
     if (kb < ke) {
         first(VecTag{});
@@ -753,21 +790,26 @@ __global__ __launch_bounds__(256, 2) void k_bf16_gemm(const GemmArgs g_in) {
 #define X3_DEPTH 1
 #endif
 static_assert(X3_DEPTH == 1 || X3_DEPTH == 2, "one or two K tiles in flight");
-template <bool AMINOR, bool BMINOR, int SHARE, int IDX = 0>
+// MASK: the fp32 operand carries a keep-mask (known at launch: a kernel without it requests no mask words at all)
+template <bool AMINOR, bool BMINOR, int SHARE, int IDX = 0, bool MASK = true>
 __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
     static_assert(SHARE == 1 || SHARE == 2, "the two tiles of a block share one operand");
+    static_assert(IDX == 0 || IDX == (SHARE == 2 ? 1 : 2), "the row map belongs to the operand that is read as fp32");
     typedef Eng<3> E;
     constexpr int KTv = E::KT;
+    // F: the operand a group reads as fp32 and splits itself; P: the one both tiles share, copied from its slice planes
+    constexpr bool FMINOR = SHARE == 2 ? AMINOR : BMINOR, PMINOR = SHARE == 2 ? BMINOR : AMINOR, IDXD = IDX != 0;
     const GemmArgs g = g_in;
     __shared__ __attribute__((aligned(16))) unsigned As[2][3 * E::PLANE];
     __shared__ __attribute__((aligned(16))) unsigned Bs[2][3 * E::PLANE];
-    const int arm = blockIdx.z, grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
-    Operand oa_h = g.a, ob_h = g.b;
-    oa_h.ptr += (int64_t)arm * g.a_arm;
-    ob_h.ptr += (int64_t)arm * g.b_arm;
-    if (oa_h.bits) oa_h.bits += (int64_t)arm * g.a_bits_arm;
-    if (ob_h.bits) ob_h.bits += (int64_t)arm * g.b_bits_arm;
-    const OperandDev oa = make_operand_dev<AMINOR>(oa_h), ob = make_operand_dev<BMINOR>(ob_h);
+    // the group index as a SCALAR: what follows from it -- the tile, whether it exists, which operands the group stages, the LDS
+    // buffers -- is then decided by scalar branches, and no load or LDS store of the steps sits in an exec-masked region
+    const int grp = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+    const int arm = blockIdx.z, tid = threadIdx.x & 255, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
+    Operand of_h = SHARE == 2 ? g.a : g.b;
+    of_h.ptr += (int64_t)arm * (SHARE == 2 ? g.a_arm : g.b_arm);
+    if (of_h.bits) of_h.bits += (int64_t)arm * (SHARE == 2 ? g.a_bits_arm : g.b_bits_arm);
+    const OperandDev of = make_operand_dev<FMINOR>(of_h);
     // The two tiles of a block: neighbours along m for the same n tile when they share the B operand (SHARE = 2), along n
     // for the same m tile when they share A (SHARE = 1).  An odd count leaves the last block's second group idle.
     const int tiles_m = cdiv(g.M, BT), tiles_n = cdiv(g.N, BT);
@@ -777,6 +819,7 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
     else { tm = bi % tiles_m; tn = 2 * (bi / tiles_m) + grp; }
     const bool active = tm < tiles_m && tn < tiles_n;
     const int m0 = tm * BT, n0 = tn * BT;
+    const int rf = SHARE == 2 ? m0 : n0, rp = SHARE == 2 ? n0 : m0;      // tile origins of F and P
     const int nkt = cdiv(g.K, KTv);
     const int kb = (int)(((int64_t)blockIdx.y * nkt) / g.KS) * KTv;
     const int ke = min(g.K, (int)(((int64_t)(blockIdx.y + 1) * nkt) / g.KS) * KTv);
@@ -789,86 +832,51 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
     constexpr int DEPTH = X3_DEPTH;
     // (only the fp32 operand -- the one that comes from HBM -- goes two deep: twenty registers; with the slice planes two deep
     // as well the kernel spilled 48 - 64 registers)
-    TileRegsT<true, E::NQ> ta_[DEPTH], tb_[DEPTH];
-    unsigned ro[E::NQ] = {};           // IDX: element offsets of the indexed operand's memory rows (see quad_load_idx)
+    TileRegsT<MASK, E::NQ> tf_[DEPTH];
+    unsigned ro[E::NQ] = {};           // K-minor through the row map: element offsets of the pieces' memory rows (see quad_load)
     MapRegs<3> mr = {};
     PlaneRegs ps;
-    constexpr bool APL = SHARE == 1, BPL = SHARE == 2;
     const PlaneDev dp = make_plane_dev(SHARE == 1 ? g.a : g.b, arm);
-    const bool do_a = SHARE != 1 || grp == 0, do_b = SHARE != 2 || grp == 0;   // which operands this group stages
+    const PieceCtx cf = piece_ctx<FMINOR, 3, IDXD>(of, rf);
     // one piece of each operand in turn; a piece's registers request the next tile as soon as they have been written out
     // kst: the tile whose registers (slot SLOT) are written out; kld: the tile they then request (DEPTH tiles on, LOAD); kpl:
-    // the tile the plane registers request (one tile on, LOADP)
-    auto stage = [&](unsigned* Ad, unsigned* Bd, int kst, int kld, int kpl, auto load_tag, auto loadp_tag, auto slot_tag) __attribute__((always_inline)) {
+    // the tile the plane registers request (one tile on, LOADP).  Group 0 stages the shared operand, for both groups: a scalar
+    // branch around its pieces, since the group index is a scalar
+    auto stage = [&](unsigned* Fd, unsigned* Pd, int kst, int kld, int kpl, auto load_tag, auto loadp_tag, auto slot_tag) __attribute__((always_inline)) {
         constexpr bool LOAD = decltype(load_tag)::value, LOADP = decltype(loadp_tag)::value;
         constexpr int SLOT = decltype(slot_tag)::value;
-        TileRegsT<true, E::NQ>& ta = ta_[SLOT];
-        TileRegsT<true, E::NQ>& tb = tb_[SLOT];
-        if constexpr (LOAD && IDX == 1) idx_next<AMINOR, 3>(ro, mr, oa, kld);
-        if constexpr (LOAD && IDX == 2) idx_next<BMINOR, 3>(ro, mr, ob, kld);
+        TileRegsT<MASK, E::NQ>& tf = tf_[SLOT];
+        if constexpr (LOAD && IDXD) idx_next<FMINOR, 3>(ro, mr, of, kld);
+        auto planes = [&](int i) __attribute__((always_inline)) {
+            if (grp == 0) {
+                plane_store<PMINOR>(Pd, ps, i);
+                if constexpr (LOADP) plane_load<PMINOR>(ps, dp, rp, kpl, i);
+            }
+        };
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            if constexpr (APL) {
-                if (do_a) {
-                    plane_store<AMINOR>(Ad, ps, i);
-                    if constexpr (LOADP) plane_load<AMINOR>(ps, dp, m0, kpl, i);
-                }
-            } else if (i < E::NQ) {
-                if (do_a) {
-                    quad_store<AMINOR, true, 3>(Ad, ta, oa, m0, kst, ke, i);
-                    if constexpr (LOAD) {
-                        if constexpr (IDX == 1) quad_load_idx<AMINOR, 3>(ta, oa, m0, kld, ke, i, ro);
-                        else quad_load<AMINOR, true, 3>(ta, oa, m0, kld, ke, i);
-                    }
-                }
+            if constexpr (SHARE == 1) planes(i);      // (A before B)
+            if (i < E::NQ) {
+                quad_store<FMINOR, MASK, 3>(Fd, tf, of, cf, kst, ke, i);
+                if constexpr (LOAD) quad_load<FMINOR, MASK, 3, IDXD>(tf, of, cf, kld, ke, i, ro);
             }
-            if constexpr (BPL) {
-                if (do_b) {
-                    plane_store<BMINOR>(Bd, ps, i);
-                    if constexpr (LOADP) plane_load<BMINOR>(ps, dp, n0, kpl, i);
-                }
-            } else if (i < E::NQ) {
-                if (do_b) {
-                    quad_store<BMINOR, true, 3>(Bd, tb, ob, n0, kst, ke, i);
-                    if constexpr (LOAD) {
-                        if constexpr (IDX == 2) quad_load_idx<BMINOR, 3>(tb, ob, n0, kld, ke, i, ro);
-                        else quad_load<BMINOR, true, 3>(tb, ob, n0, kld, ke, i);
-                    }
-                }
-            }
+            if constexpr (SHARE == 2) planes(i);
         }
     };
     // the first DEPTH tiles' requests (tile d into slot d)
     auto first = [&](auto slot_tag, int k) __attribute__((always_inline)) {
         constexpr int SLOT = decltype(slot_tag)::value;
-        TileRegsT<true, E::NQ>& ta = ta_[SLOT];
-        TileRegsT<true, E::NQ>& tb = tb_[SLOT];
-        if constexpr (APL) {
-            if (SLOT == 0 && do_a) {
+        TileRegsT<MASK, E::NQ>& tf = tf_[SLOT];
+        if (SLOT == 0 && grp == 0) {
 #pragma unroll
-                for (int i = 0; i < 6; ++i) plane_load<AMINOR>(ps, dp, m0, k, i);
-            }
-        } else if (do_a) {
-            if constexpr (IDX == 1) {
-                if constexpr (SLOT == 0) idx_begin<AMINOR, 3>(ro, mr, oa, m0, k);
-                else idx_next<AMINOR, 3>(ro, mr, oa, k);
-#pragma unroll
-                for (int q = 0; q < E::NQ; ++q) quad_load_idx<AMINOR, 3>(ta, oa, m0, k, ke, q, ro);
-            } else tile_load<AMINOR, true, 3>(ta, oa, m0, k, ke);
+            for (int i = 0; i < 6; ++i) plane_load<PMINOR>(ps, dp, rp, k, i);
         }
-        if constexpr (BPL) {
-            if (SLOT == 0 && do_b) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) plane_load<BMINOR>(ps, dp, n0, k, i);
-            }
-        } else if (do_b) {
-            if constexpr (IDX == 2) {
-                if constexpr (SLOT == 0) idx_begin<BMINOR, 3>(ro, mr, ob, n0, k);
-                else idx_next<BMINOR, 3>(ro, mr, ob, k);
-#pragma unroll
-                for (int q = 0; q < E::NQ; ++q) quad_load_idx<BMINOR, 3>(tb, ob, n0, k, ke, q, ro);
-            } else tile_load<BMINOR, true, 3>(tb, ob, n0, k, ke);
+        if constexpr (IDXD) {
+            if constexpr (SLOT == 0) idx_begin<FMINOR, 3>(ro, mr, of, k);
+            else idx_next<FMINOR, 3>(ro, mr, of, k);
         }
+#pragma unroll
+        for (int q = 0; q < E::NQ; ++q) quad_load<FMINOR, MASK, 3, IDXD>(tf, of, cf, k, ke, q, ro);
     };
     if (active && n > 0) {
         first(std::integral_constant<int, 0>{}, kb);
@@ -876,31 +884,40 @@ __global__ __launch_bounds__(512, 1) void k_x3_gemm(const GemmArgs g_in) {
             if (n > 1) first(std::integral_constant<int, DEPTH - 1>{}, kb + KTv);
         }
     }
-    // phase p: group g is at step q = p - g of its own sequence stage(0), mfma(0), stage(1), mfma(1), ...
-    for (int p = 0; p <= 2 * n; ++p) {
-        const int q = p - grp;
-        if (active && q >= 0 && q < 2 * n) {
-            const int t = q >> 1, k0 = kb + t * KTv;
-            unsigned* const Ad = As[SHARE == 1 ? (t & 1) : grp];
-            unsigned* const Bd = Bs[SHARE == 2 ? (t & 1) : grp];
-            if (q & 1) {
-                mfma_ktile<AMINOR, BMINOR, 3>(acc, Ad, Bd, wm, wn, lane);
-            } else {
-                // tile t + DEPTH / t + 1 exist: their requests go out with tile t's store
-                const bool more = t + DEPTH < n, morep = t + 1 < n;
-                const int kld = k0 + DEPTH * KTv, kpl = k0 + KTv;
-                auto go = [&](auto slot_tag) __attribute__((always_inline)) {
-                    if (more) stage(Ad, Bd, k0, kld, kpl, VecTag{}, VecTag{}, slot_tag);
-                    else if (morep) stage(Ad, Bd, k0, k0, kpl, ScalarTag{}, VecTag{}, slot_tag);
-                    else stage(Ad, Bd, k0, k0, k0, ScalarTag{}, ScalarTag{}, slot_tag);
-                };
-                if (DEPTH == 1 || !(t & 1)) go(std::integral_constant<int, 0>{});
-                else go(std::integral_constant<int, DEPTH - 1>{});
-            }
-        }
+    // A group's sequence is stage(0), mfma(0), stage(1), mfma(1), ... with a workgroup barrier behind every step; group 1 runs one
+    // step behind group 0, so every group passes 2 n + 1 barriers: group 1 one before its sequence, group 0 one behind it, a group
+    // without a tile all of them.  (One loop over the 2 n + 1 phases with the step chosen inside joins the two steps' registers at
+    // every phase: hipcc then keeps a second set of accumulators and copies the tile registers behind a wait for their loads.)
+    if (!active) {
+        for (int p = 0; p <= 2 * n; ++p) __syncthreads();
+        return;
+    }
+    if (grp == 1) __syncthreads();
+    for (int t = 0; t < n; ++t) {
+        const int k0 = kb + t * KTv;
+        unsigned* const Ad = As[SHARE == 1 ? (t & 1) : grp];
+        unsigned* const Bd = Bs[SHARE == 2 ? (t & 1) : grp];
+        unsigned* const Fd = SHARE == 2 ? Ad : Bd;
+        unsigned* const Pd = SHARE == 2 ? Bd : Ad;
+        // tile t + DEPTH / t + 1 exist: their requests go out with tile t's store
+        const bool more = t + DEPTH < n, morep = t + 1 < n;
+        const int kld = k0 + DEPTH * KTv, kpl = k0 + KTv;
+        auto go = [&](auto slot_tag) __attribute__((always_inline)) {
+            if (more) stage(Fd, Pd, k0, kld, kpl, VecTag{}, VecTag{}, slot_tag);
+            else if (morep) stage(Fd, Pd, k0, k0, kpl, ScalarTag{}, VecTag{}, slot_tag);
+            else stage(Fd, Pd, k0, k0, k0, ScalarTag{}, ScalarTag{}, slot_tag);
+        };
+        if (DEPTH == 1 || !(t & 1)) go(std::integral_constant<int, 0>{});
+        else go(std::integral_constant<int, DEPTH - 1>{});
+        __syncthreads();
+        mfma_ktile<AMINOR, BMINOR, 3>(acc, Ad, Bd, wm, wn, lane);
+        // (the MFMAs touch registers only, and hipcc moves the barrier up to where the fragment reads end: the step would then run
+        // beside the other group's matrix step instead of its staging step.  The fence keeps the barrier behind the step.)
+        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
     }
-    if (active) gemm_epilogue(g, acc, m0, n0, wm, wn, lane, arm);
+    if (grp == 0) __syncthreads();
+    gemm_epilogue(g, acc, m0, n0, wm, wn, lane, arm);
 }
 
 // fc11 forward + bias + reconstruction loss + dZ11.  The product is computed TRANSPOSED, z^T = W11 d10^T: MFMA rows are
@@ -1688,7 +1705,9 @@ __global__ __launch_bounds__(512, 1) void k_x3_small(const TnDescs descs, int nd
     constexpr int KTv = E::KT;
     __shared__ __attribute__((aligned(16))) unsigned As[2][3 * E::PLANE];
     __shared__ __attribute__((aligned(16))) unsigned Bs[2][3 * E::PLANE];
-    const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
+    // (the group index as a scalar, as in k_x3_gemm: the group's product, its operands and whether it exists are then uniform)
+    const int grp = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+    const int tid = threadIdx.x & 255, lane = tid & 63, wv = tid >> 6, wm = wv >> 1, wn = wv & 1;
     const int unit = 2 * blockIdx.x + grp;
     const bool active = unit < ndesc * A;
     const int di = active ? unit % ndesc : 0, arm = active ? unit / ndesc : 0;
@@ -1716,46 +1735,43 @@ __global__ __launch_bounds__(512, 1) void k_x3_small(const TnDescs descs, int nd
     const int n = ke > kb ? cdiv(ke - kb, KTv) : 0;
     f32x16 acc[2][2] = {{zero16(), zero16()}, {zero16(), zero16()}};
     TileRegsT<false, E::NQ> ta, tb;
+    const PieceCtx ca = piece_ctx<true, 3>(oa, 0), cb = piece_ctx<true, 3>(ob, 0);
     unsigned* const Ad = As[grp];
     unsigned* const Bd = Bs[grp];
     auto stage = [&](int kst, int kld, auto load_tag) __attribute__((always_inline)) {
         constexpr bool LOAD = decltype(load_tag)::value;
 #pragma unroll
         for (int i = 0; i < E::NQ; ++i) {
-            quad_store<true, false, 3>(Ad, ta, oa, 0, kst, ke, i);
-            if constexpr (LOAD) quad_load<true, false, 3>(ta, oa, 0, kld, ke, i);
-            quad_store<true, false, 3, true>(Bd, tb, ob, 0, kst, ke, i);
-            if constexpr (LOAD) quad_load<true, false, 3>(tb, ob, 0, kld, ke, i);
+            quad_store<true, false, 3>(Ad, ta, oa, ca, kst, ke, i);
+            if constexpr (LOAD) quad_load<true, false, 3>(ta, oa, ca, kld, ke, i);
+            quad_store<true, false, 3, true>(Bd, tb, ob, cb, kst, ke, i);
+            if constexpr (LOAD) quad_load<true, false, 3>(tb, ob, cb, kld, ke, i);
         }
     };
     if (active && n > 0) {
-        tile_load<true, false, 3>(ta, oa, 0, kb, ke);
-        tile_load<true, false, 3>(tb, ob, 0, kb, ke);
-    }
-    for (int p = 0; p <= 2 * n; ++p) {
-        const int q = p - grp;
-        if (active && q >= 0 && q < 2 * n) {
-            const int k0 = kb + (q >> 1) * KTv;
-            if (q & 1) mfma_ktile<true, true, 3>(acc, Ad, Bd, wm, wn, lane);
-            else if (k0 + KTv < ke) stage(k0, k0 + KTv, VecTag{});
-            else stage(k0, k0, ScalarTag{});
+#pragma unroll
+        for (int i = 0; i < E::NQ; ++i) {
+            quad_load<true, false, 3>(ta, oa, ca, kb, ke, i);
+            quad_load<true, false, 3>(tb, ob, cb, kb, ke, i);
         }
+    }
+    // (the sequence and its 2 n + 1 barriers as in k_x3_gemm; both groups have the same role here)
+    if (!active) {
+        for (int p = 0; p <= 2 * n; ++p) __syncthreads();
+        return;
+    }
+    if (grp == 1) __syncthreads();
+    for (int t = 0; t < n; ++t) {
+        const int k0 = kb + t * KTv;
+        if (k0 + KTv < ke) stage(k0, k0 + KTv, VecTag{});
+        else stage(k0, k0, ScalarTag{});
+        __syncthreads();
+        mfma_ktile<true, true, 3>(acc, Ad, Bd, wm, wn, lane);
+        __builtin_amdgcn_sched_barrier(0);      // (keeps the barrier behind the MFMAs: see k_x3_gemm)
         __syncthreads();
     }
-    if (!active) return;
-    float* out = d.out + (int64_t)blockIdx.y * d.out_ks_stride + (int64_t)arm * d.out_arm_stride;
-    const int ncols = d.Nv + d.q_ones, l31 = lane & 31;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = 64 * wn + 32 * j + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = 64 * wm + 32 * i + acc_row(r, lane);
-                if (row < d.Mv && col < ncols) out[(int64_t)row * d.ldo + col] = acc[i][j][r];
-            }
-        }
+    if (grp == 0) __syncthreads();
+    tile_out(d.out + (int64_t)blockIdx.y * d.out_ks_stride + (int64_t)arm * d.out_arm_stride, d.ldo, d.Mv, d.Nv + d.q_ones, acc, 0, 0, wm, wn, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1923,21 +1939,26 @@ static Operand x_operand(const Ctx& c, const float* x, int64_t xs, bool minor, i
 }
 
 // The compiled instantiations of the two slab GEMM kernels by what their template arguments mean: engine, orientations, SHARE
-// (fp32x3: the two tiles of a block share 1 = A, 2 = B), IDX (1 / 2: A / B through its row map), S16 (bit 0 / 1: A / B is bf16 in memory)
+// (fp32x3: the two tiles of a block share 1 = A, 2 = B), IDX (1 / 2: A / B through its row map), S16 (bit 0 / 1: A / B is bf16 in memory),
+// MASK (the kernel requests x~'s keep-mask words: fp32x3 exactly when the operand has a mask; the bf16 engine's masked forms also
+// take an x without one)
 typedef void (*GemmKernel)(const GemmArgs);
-struct SlabVariant { bool x3, aminor, bminor; int share, idx, s16; GemmKernel kernel; };
-#define BF16_GEMM(AMINOR, BMINOR, IDX, S16) SlabVariant{false, AMINOR, BMINOR, 0, IDX, S16, k_bf16_gemm<AMINOR, BMINOR, IDX, S16>}
-#define X3_GEMM(AMINOR, BMINOR, SHARE, IDX) SlabVariant{true, AMINOR, BMINOR, SHARE, IDX, 0, k_x3_gemm<AMINOR, BMINOR, SHARE, IDX>}
+struct SlabVariant { bool x3, aminor, bminor; int share, idx, s16, mask; GemmKernel kernel; };
+#define BF16_GEMM(AMINOR, BMINOR, IDX, S16, MASK) SlabVariant{false, AMINOR, BMINOR, 0, IDX, S16, MASK, k_bf16_gemm<AMINOR, BMINOR, IDX, S16, MASK != 0>}
+#define X3_GEMM(AMINOR, BMINOR, SHARE, IDX, MASK) SlabVariant{true, AMINOR, BMINOR, SHARE, IDX, 0, MASK, k_x3_gemm<AMINOR, BMINOR, SHARE, IDX, MASK != 0>}
 static const SlabVariant slab_variants[] = {
     // fc1 -- x as it lies | through the row map | ... from its bf16 copy | ... and W1 from slice 0 of its planes
-    BF16_GEMM(false, false, 0, 0), BF16_GEMM(false, false, 1, 0), BF16_GEMM(false, false, 1, 1), BF16_GEMM(false, false, 1, 3),
-    X3_GEMM(false, false, 2, 0), X3_GEMM(false, false, 2, 1),   // (one tile wide: the two tiles of a block share the W1 tile)
-    BF16_GEMM(false, true, 0, 0),   // d(d10)
-    // dW1 -- x~ in the same four forms, the last with dZ1 from slice 0 of its planes; the first is dW11's too
-    BF16_GEMM(true, true, 0, 0), BF16_GEMM(true, true, 2, 0), BF16_GEMM(true, true, 2, 2), BF16_GEMM(true, true, 2, 3),
-    X3_GEMM(true, true, 1, 0), X3_GEMM(true, true, 1, 2),       // (one tile high: they share the dZ1 tile)
-    // dW11 -- on a bf16 dZ11 | fp32x3 (one tile wide: they share the [d10 | 1] tile)
-    BF16_GEMM(true, true, 0, 1), X3_GEMM(true, true, 2, 0),
+    BF16_GEMM(false, false, 0, 0, 1), BF16_GEMM(false, false, 1, 0, 1), BF16_GEMM(false, false, 1, 1, 1), BF16_GEMM(false, false, 1, 3, 1),
+    // fp32x3 (one tile wide: the two tiles of a block share the W1 tile), x~ under its keep-mask | x without input dropout
+    // (the row map exists only under input dropout -- Plan::rowmap --, so its form always carries the mask)
+    X3_GEMM(false, false, 2, 0, 1), X3_GEMM(false, false, 2, 1, 1), X3_GEMM(false, false, 2, 0, 0),
+    BF16_GEMM(false, true, 0, 0, 0),   // d(d10)
+    // dW1 -- x~ in the same four forms, the last with dZ1 from slice 0 of its planes
+    BF16_GEMM(true, true, 0, 0, 1), BF16_GEMM(true, true, 2, 0, 1), BF16_GEMM(true, true, 2, 2, 1), BF16_GEMM(true, true, 2, 3, 1),
+    // fp32x3 (one tile high: they share the dZ1 tile), with and without the mask
+    X3_GEMM(true, true, 1, 0, 1), X3_GEMM(true, true, 1, 2, 1), X3_GEMM(true, true, 1, 0, 0),
+    // dW11 -- fp32 operands | on a bf16 dZ11 | fp32x3 (one tile wide: they share the [d10 | 1] tile)
+    BF16_GEMM(true, true, 0, 0, 0), BF16_GEMM(true, true, 0, 1, 0), X3_GEMM(true, true, 2, 0, 0),
 };
 #undef BF16_GEMM
 #undef X3_GEMM
@@ -1947,14 +1968,34 @@ static int launch_slab_gemm(const Ctx& c, const GemmArgs& g, int share, dim3 gri
     const bool x3 = c.plan.big == GEMM_X3, aminor = g.a.kminor != 0, bminor = g.b.kminor != 0;
     const int idx = (g.a.rowmap ? 1 : 0) | (g.b.rowmap ? 2 : 0), s16 = (g.a.src16 ? 1 : 0) | (g.b.src16 ? 2 : 0);
     if (!x3) share = 0;
-    for (const SlabVariant& v : slab_variants)
-        if (v.x3 == x3 && v.aminor == aminor && v.bminor == bminor && v.share == share && v.idx == idx && v.s16 == s16) {
-            hipLaunchKernelGGL(v.kernel, grid, dim3(x3 ? 512 : 256), 0, c.stream, g);
-            HIP_LAUNCH_CHECK(what);
-            return 0;
-        }
-    set_error("%s: no %s kernel for A k-%s, B k-%s, share %d, row map %d, bf16 source %d", what, x3 ? "k_x3_gemm" : "k_bf16_gemm",
-              aminor ? "minor" : "major", bminor ? "minor" : "major", share, idx, s16);
+    // fp32x3: the shared operand comes from its slice planes (ones column included); only the other one is read as fp32
+    const Operand& f = share == 1 ? g.b : g.a;
+    if (x3 && (!(share == 1 ? g.a : g.b).pl || (share == 1 ? g.a : g.b).bits || f.ones_row >= 0)) {
+        set_error("%s: k_x3_gemm takes the shared operand as slice planes and masks / extends neither it nor the other by a ones row", what);
+        return MMVAE_E_LAUNCH;
+    }
+    // bf16 engine: only B of the K-minor x K-minor forms without a row map compiles the ones row (k_bf16_gemm: BONES)
+    if (!x3 && (g.a.ones_row >= 0 || (g.b.ones_row >= 0 && !(aminor && bminor && idx == 0)))) {
+        set_error("%s: k_bf16_gemm extends only the B operand of a k-minor x k-minor product without a row map by a ones row", what);
+        return MMVAE_E_LAUNCH;
+    }
+    // bf16 engine: the mask belongs to x~, which is A of the k-major x k-major product (fc1) or B of a k-minor x k-minor one (dW1)
+    if (!x3 && ((g.a.bits && (aminor || bminor)) || (g.b.bits && !(aminor && bminor)))) {
+        set_error("%s: k_bf16_gemm takes a keep-mask on A of a k-major x k-major or on B of a k-minor x k-minor product only", what);
+        return MMVAE_E_LAUNCH;
+    }
+    const int mask = (x3 ? f.bits != nullptr : g.a.bits || g.b.bits) ? 1 : 0;
+    // the exact form first; an unmasked x of the bf16 engine (x_drop = 0) also runs on the masked form of its product
+    for (int pass = 0; pass < (x3 ? 1 : 2); ++pass)
+        for (const SlabVariant& v : slab_variants)
+            if (v.x3 == x3 && v.aminor == aminor && v.bminor == bminor && v.share == share && v.idx == idx && v.s16 == s16 &&
+                (pass == 0 ? v.mask == mask : v.mask >= mask)) {
+                hipLaunchKernelGGL(v.kernel, grid, dim3(x3 ? 512 : 256), 0, c.stream, g);
+                HIP_LAUNCH_CHECK(what);
+                return 0;
+            }
+    set_error("%s: no %s kernel for A k-%s, B k-%s, share %d, row map %d, bf16 source %d, mask %d", what, x3 ? "k_x3_gemm" : "k_bf16_gemm",
+              aminor ? "minor" : "major", bminor ? "minor" : "major", share, idx, s16, mask);
     return MMVAE_E_LAUNCH;
 }
 // its grid.  fp32x3: a block carries two 128-row tiles of the GEMM's long side (`paired` rows); bf16: tiles_m x tiles_n

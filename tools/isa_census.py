@@ -28,26 +28,29 @@ def demangle(names):
 
 
 def census(path):
-    kernels, cur, body = {}, None, None
+    kernels, cur, body, done = {}, None, None, None
     meta = collections.defaultdict(dict)
     for line in open(path):
         s = line.strip()
         m = re.match(r"^(_Z\w+):", line)
         if m and cur is None:
-            cur, body = m.group(1), collections.Counter()
+            cur, body, done = m.group(1), collections.Counter(), collections.Counter()
             continue
         if cur is not None:
-            if s.startswith((";", ".", "//")) or not s or s.endswith(":"):
-                continue
-            op = s.split()[0]
-            if op.endswith("_dpp"):
-                body["(dpp)"] += 1
-            op = re.sub(r"_(e32|e64|sdwa|dpp|e64_dpp)$", "", op)     # the encoding suffixes of the listing
-            body[op] += 1
-            if op == "s_endpgm":
-                kernels[cur] = body
+            if s.startswith(".amdhsa_kernel"):  # the body ends at its descriptor, not at the first s_endpgm: blocks are laid out
+                kernels[cur] = done             # behind it.  The s_nop / s_code_end padding at the end is not counted.
                 cur = None
-            continue
+            elif s.startswith((";", ".", "//")) or not s or s.endswith(":"):
+                continue
+            else:
+                op = s.split()[0]
+                if op.endswith("_dpp"):
+                    body["(dpp)"] += 1
+                op = re.sub(r"_(e32|e64|sdwa|dpp|e64_dpp)$", "", op)     # the encoding suffixes of the listing
+                body[op] += 1
+                if op not in ("s_nop", "s_code_end"):
+                    done = body.copy()
+                continue
         m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line)
         if m:
             mk = m.group(1)
