@@ -243,6 +243,16 @@ def lib():
     L.mmvae_pca_project.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, i32, vp, vp]
     for fn in ("mmvae_gram_segments", "mmvae_gram", "mmvae_debug_gram", "mmvae_symm_mul", "mmvae_pca_project"):
         getattr(L, fn).restype = C.c_int
+    f64 = C.c_double
+    L.mmvae_cpm_dense.argtypes = [vp, i32, i64, i64, i32, vp, i64, vp, i32, f64, i32, vp, i32, vp, vp]
+    L.mmvae_debug_cpm_dense.argtypes = [vp, i32, i64, i64, i32, vp, i64, vp, i32, f64, i32, vp, i32, vp, i32, vp]
+    L.mmvae_cpm_csr.argtypes = [vp, vp, vp, i32, i64, i64, i32, vp, i64, vp, i32, f64, i32, vp, i32, vp, vp]
+    L.mmvae_gene_stats_workspace_bytes.argtypes = [i64, i32]
+    L.mmvae_gene_stats_workspace_bytes.restype = C.c_size_t
+    L.mmvae_gene_stats.argtypes = [vp, i32, i64, i64, i32, vp, i64, f64, vp, C.c_size_t, vp, vp, vp, vp]
+    L.mmvae_debug_gene_stats.argtypes = [vp, i32, i64, i64, i32, vp, i64, f64, vp, C.c_size_t, vp, vp, vp, i32, vp]
+    for fn in ("mmvae_cpm_dense", "mmvae_debug_cpm_dense", "mmvae_cpm_csr", "mmvae_gene_stats", "mmvae_debug_gene_stats"):
+        getattr(L, fn).restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -1022,6 +1032,117 @@ def pca_project(data: torch.Tensor, mean: torch.Tensor, V: torch.Tensor, rows: O
     check(lib().mmvae_pca_project(_ptr(x), int(x.stride(0)), n_total, _ptr(rows), n, Dm, _ptr(mean), _ptr(V), k, _ptr(Z),
                                   _stream(x.device)), "mmvae_pca_project")
     return Z
+
+
+# launch_cpm_dense / launch_cpm_csr / launch_gene_stats (csrc/dataprep.hip; the constants are those of csrc/common.hpp)
+CPM_THREADS = 256               # CPM_THREADS: threads of the workgroup that owns a selected row
+CPM_WINDOW = 4096               # CPM_WINDOW: columns of the dense row that the CSR kernel rebuilds in LDS at a time
+CPM_MAX_G = 1 << 20             # CPM_MAX_G: genes at most
+GENESTATS_SEG_ROWS = 256        # GS_SEG_ROWS: rows per segment
+GENESTATS_TILE = 256            # GS_TILE: genes per wave, four consecutive genes a lane
+CPM_VTYPES = {torch.int32: 0, torch.float32: 1, torch.float64: 2}
+CPM_OTYPES = {torch.float32: 0, torch.float64: 1}
+CPM_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
+GENESTATS_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
+
+
+def cpm_wide(x: torch.Tensor) -> bool:
+    """The launcher's rule of mmvae_cpm_dense and mmvae_gene_stats: the 16-byte loads where the matrix's base is 16-byte
+    aligned and its row pitch a whole number of 16 bytes."""
+    return x.data_ptr() % 16 == 0 and (x.stride(0) * x.element_size()) % 16 == 0
+
+
+def _cpm_rows(what: str, rows: Optional[torch.Tensor], n_total: int) -> Tuple[Optional[torch.Tensor], int]:
+    if rows is None:
+        return None, n_total
+    if rows.dtype != torch.int64 or rows.dim() != 1:
+        raise TypeError(f"{what}: rows must be int64 [n]")
+    return rows.contiguous(), int(rows.numel())
+
+
+def cpm_dense(x: torch.Tensor, rows: Optional[torch.Tensor] = None, genes: Optional[torch.Tensor] = None, scaler: float = 1.0,
+              log: bool = False, out_dtype: torch.dtype = torch.float64, path: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+    """mmvae_cpm_dense: ``x`` [n_total, G] int32, float32 or float64 on the GPU (rows may be strided, columns not; read where
+    it lies), optionally the int64 row map ``rows`` [n] and the int32 gene list ``genes`` [ng] -> (out [n, ng] of
+    ``out_dtype`` float32 or float64, norms float64 [n]) on the device: out = x / norm * scaler, or log1p of that with
+    ``log``, norm the row's sum |x| over all G genes (1 where that is 0), norms the sums themselves.  ``path``: "auto" (the
+    launcher's rule), "narrow", "wide" -- the load forms, equal bits."""
+    if any(t.device.type != "cuda" for t in (x, rows, genes) if t is not None):
+        raise NativeError("cpm_dense needs CUDA tensors (no CPU fallback)")
+    if path not in CPM_PATHS:
+        raise ValueError(f"cpm_dense: path must be one of {sorted(CPM_PATHS)}; got {path!r}")
+    if x.dtype not in CPM_VTYPES or x.dim() != 2 or out_dtype not in CPM_OTYPES:
+        raise TypeError("cpm_dense: x must be int32, float32 or float64 [n_total, G] and out_dtype float32 or float64")
+    n_total, G = (int(v) for v in x.shape)
+    xm = x if G == 0 or (x.stride(1) == 1 and x.stride(0) >= G) else x.contiguous()
+    rows, n = _cpm_rows("cpm_dense", rows, n_total)
+    ng = G
+    if genes is not None:
+        if genes.dtype != torch.int32 or genes.dim() != 1:
+            raise TypeError("cpm_dense: genes must be int32 [ng]")
+        genes = genes.contiguous()
+        ng = int(genes.numel())
+    out = torch.empty(n, ng, dtype=out_dtype, device=xm.device)
+    norms = torch.empty(n, dtype=torch.float64, device=xm.device)
+    check(lib().mmvae_debug_cpm_dense(_ptr(xm), CPM_VTYPES[xm.dtype], int(xm.stride(0)), n_total, G, _ptr(rows), n, _ptr(genes), ng,
+                                      float(scaler), int(bool(log)), _ptr(out), CPM_OTYPES[out_dtype], _ptr(norms), CPM_PATHS[path],
+                                      _stream(xm.device)), "mmvae_cpm_dense")
+    return out, norms
+
+
+def cpm_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, shape: Tuple[int, int], inv: torch.Tensor, ng: int,
+            rows: Optional[torch.Tensor] = None, scaler: float = 1.0, log: bool = False,
+            out_dtype: torch.dtype = torch.float64) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mmvae_cpm_csr: the canonical CSR matrix (``indptr`` int64 [n_total + 1], ``indices`` int32 [nnz], ``data`` int32,
+    float32 or float64 [nnz]) of ``shape`` (n_total, G) on the GPU, the inverse gene map ``inv`` int32 [G] (the output column
+    of a gene, -1: not selected) onto ``ng`` columns, optionally the int64 row map ``rows`` [n] -> (out [n, ng], norms
+    float64 [n]) as ``cpm_dense`` on the dense matrix, bit for bit."""
+    if any(t.device.type != "cuda" for t in (indptr, indices, data, inv, rows) if t is not None):
+        raise NativeError("cpm_csr needs CUDA tensors (no CPU fallback)")
+    n_total, G = int(shape[0]), int(shape[1])
+    if indptr.dtype != torch.int64 or tuple(indptr.shape) != (n_total + 1,):
+        raise TypeError(f"cpm_csr: indptr must be int64 [{n_total + 1}]")
+    if indices.dtype != torch.int32 or indices.dim() != 1 or data.dim() != 1 or indices.numel() != data.numel():
+        raise TypeError("cpm_csr: indices must be int32 [nnz] and data [nnz]")
+    if data.dtype not in CPM_VTYPES or out_dtype not in CPM_OTYPES:
+        raise TypeError("cpm_csr: data must be int32, float32 or float64 and out_dtype float32 or float64")
+    if inv.dtype != torch.int32 or tuple(inv.shape) != (G,):
+        raise TypeError(f"cpm_csr: inv must be int32 [{G}]")
+    indptr, indices, data, inv = indptr.contiguous(), indices.contiguous(), data.contiguous(), inv.contiguous()
+    rows, n = _cpm_rows("cpm_csr", rows, n_total)
+    out = torch.empty(n, int(ng), dtype=out_dtype, device=data.device)
+    norms = torch.empty(n, dtype=torch.float64, device=data.device)
+    nnz = int(data.numel())
+    check(lib().mmvae_cpm_csr(_ptr(indptr), _ptr(indices) if nnz else None, _ptr(data) if nnz else None, CPM_VTYPES[data.dtype],
+                              nnz, n_total, G, _ptr(rows), n, _ptr(inv), int(ng), float(scaler), int(bool(log)), _ptr(out),
+                              CPM_OTYPES[out_dtype], _ptr(norms), _stream(data.device)), "mmvae_cpm_csr")
+    return out, norms
+
+
+def gene_stats(x: torch.Tensor, eps: float, rows: Optional[torch.Tensor] = None,
+               path: str = "auto") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """mmvae_gene_stats: ``x`` [n_total, D] float32 or float64 on the GPU (rows may be strided, columns not; read where it
+    lies), optionally the int64 row map ``rows`` [n] -> (n_above int64 [D], mean float64 [D], std float64 [D]) on the
+    device: per gene the number of selected rows with x > eps (eps rounded to x's dtype), the mean and the population
+    standard deviation.  Inputs must be finite.  ``path``: "auto", "narrow", "wide" -- the load forms, equal bits."""
+    if any(t.device.type != "cuda" for t in (x, rows) if t is not None):
+        raise NativeError("gene_stats needs CUDA tensors (no CPU fallback)")
+    if path not in GENESTATS_PATHS:
+        raise ValueError(f"gene_stats: path must be one of {sorted(GENESTATS_PATHS)}; got {path!r}")
+    if x.dtype not in (torch.float32, torch.float64) or x.dim() != 2:
+        raise TypeError("gene_stats: x must be float32 or float64 [n_total, D]")
+    n_total, Dm = (int(v) for v in x.shape)
+    xm = x if Dm == 0 or (x.stride(1) == 1 and x.stride(0) >= Dm) else x.contiguous()
+    rows, n = _cpm_rows("gene_stats", rows, n_total)
+    n_above = torch.empty(Dm, dtype=torch.int64, device=xm.device)
+    mean = torch.empty(Dm, dtype=torch.float64, device=xm.device)
+    sd = torch.empty(Dm, dtype=torch.float64, device=xm.device)
+    ws_bytes = int(lib().mmvae_gene_stats_workspace_bytes(n, Dm))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=xm.device)
+    check(lib().mmvae_debug_gene_stats(_ptr(xm), CPM_VTYPES[xm.dtype], int(xm.stride(0)), n_total, Dm, _ptr(rows), n, float(eps),
+                                       _ptr(ws), ws_bytes, _ptr(n_above), _ptr(mean), _ptr(sd), GENESTATS_PATHS[path],
+                                       _stream(xm.device)), "mmvae_gene_stats")
+    return n_above, mean, sd
 
 
 def to_bf16(data: torch.Tensor) -> torch.Tensor:

@@ -1243,6 +1243,117 @@ int mmvae_pca_project(const float* data, int64_t ld, int64_t n_total, const int6
     return launch_pca_project(data, ld, n_total, rows, n, D, mean, V, k, Z, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- data preparation (dataprep.hip): every argument is checked here, on the host, before any device work ----
+static int cpm_vsize(int vtype) { return vtype == 2 ? 8 : 4; }
+
+static int cpm_common_checked(const char* who, int vtype, int64_t n_total, int G, const int64_t* rows, int64_t n, int ng,
+                              double scaler, int mode, const void* out, int otype, const double* norms) {
+    if (!out || !norms) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (vtype < 0 || vtype > 2) { set_error("%s: value type %d outside [0, 2] (int32, float, double)", who, vtype); return MMVAE_E_BADARG; }
+    if (otype < 0 || otype > 1) { set_error("%s: output type %d outside [0, 1] (float, double)", who, otype); return MMVAE_E_BADARG; }
+    if (mode < 0 || mode > 1) { set_error("%s: mode %d outside [0, 1] (normalise, log1p)", who, mode); return MMVAE_E_BADARG; }
+    if (n < 1 || n >= ((int64_t)1 << 31)) { set_error("%s: n outside [1, 2^31)", who); return MMVAE_E_BADARG; }
+    if (n_total < 1) { set_error("%s: n_total = %lld below 1", who, (long long)n_total); return MMVAE_E_BADARG; }
+    if (!rows && n > n_total) { set_error("%s: n = %lld rows of a matrix of %lld without a row map", who, (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
+    if (G < 1 || ng < 1) { set_error("%s: G = %d, ng = %d: each must be at least 1", who, G, ng); return MMVAE_E_BADARG; }
+    if (!(scaler == scaler) || scaler - scaler != 0.0) { set_error("%s: scaler is not finite", who); return MMVAE_E_BADARG; }
+    if (G > CPM_MAX_G || ng > CPM_MAX_G) { set_error("%s: G = %d, ng = %d above %d", who, G, ng, CPM_MAX_G); return MMVAE_E_UNSUPPORTED; }
+    return 0;
+}
+
+static int cpm_dense_checked(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n,
+                             const int32_t* genes, int ng, double scaler, int mode, void* out, int otype, double* norms, int path,
+                             void* stream) {
+    if (!x) { set_error("cpm_dense: null pointer"); return MMVAE_E_BADARG; }
+    if (int rc = cpm_common_checked("cpm_dense", vtype, n_total, G, rows, n, ng, scaler, mode, out, otype, norms)) return rc;
+    if (ld < G) { set_error("cpm_dense: ld = %lld below G = %d", (long long)ld, G); return MMVAE_E_BADARG; }
+    if (!genes && ng != G) { set_error("cpm_dense: ng = %d without a gene list must be G = %d", ng, G); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(x) % cpm_vsize(vtype)) { set_error("cpm_dense: x not aligned to its value type"); return MMVAE_E_BADARG; }
+    if (path < -1 || path > 1) { set_error("cpm_dense: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
+    const bool can = cpm_wide(x, ld, cpm_vsize(vtype));
+    if (path == 1 && !can) {
+        set_error("cpm_dense: 16-byte loads need a 16-byte aligned base and a row pitch of whole 16 bytes (ld = %lld)", (long long)ld);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_cpm_dense(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, path < 0 ? can : path == 1,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n, const int32_t* genes,
+                    int ng, double scaler, int mode, void* out, int otype, double* norms, void* stream) {
+    return cpm_dense_checked(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, -1, stream);
+}
+
+int mmvae_debug_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n,
+                          const int32_t* genes, int ng, double scaler, int mode, void* out, int otype, double* norms, int path,
+                          void* stream) {
+    return cpm_dense_checked(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, path, stream);
+}
+
+int mmvae_cpm_csr(const int64_t* indptr, const int32_t* indices, const void* data, int vtype, int64_t nnz, int64_t n_total, int G,
+                  const int64_t* rows, int64_t n, const int32_t* inv, int ng, double scaler, int mode, void* out, int otype,
+                  double* norms, void* stream) {
+    if (!indptr || !inv) { set_error("cpm_csr: null pointer"); return MMVAE_E_BADARG; }
+    if (nnz < 0) { set_error("cpm_csr: nnz = %lld below 0", (long long)nnz); return MMVAE_E_BADARG; }
+    if (nnz > 0 && (!indices || !data)) { set_error("cpm_csr: null indices / data with nnz = %lld", (long long)nnz); return MMVAE_E_BADARG; }
+    if (int rc = cpm_common_checked("cpm_csr", vtype, n_total, G, rows, n, ng, scaler, mode, out, otype, norms)) return rc;
+    if (ng > G) { set_error("cpm_csr: ng = %d above G = %d", ng, G); return MMVAE_E_BADARG; }
+    return launch_cpm_csr(indptr, indices, data, vtype, nnz, n_total, G, rows, n, inv, ng, scaler, mode, out, otype, norms,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+static bool gs_shape_ok(int64_t n, int D) {
+    return (unsigned __int128)gs_nseg(n) * (unsigned __int128)cdiv64(D, GS_TILE) <= (unsigned __int128)GS_MAX_BLOCKS;
+}
+
+size_t mmvae_gene_stats_workspace_bytes(int64_t n, int D) {
+    if (n < 1 || n > ((int64_t)1 << 31) || D < 1 || !gs_shape_ok(n, D)) return 0;
+    const unsigned __int128 bytes = (unsigned __int128)8 * 3 * (unsigned __int128)gs_nseg(n) * (unsigned __int128)D;
+    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
+}
+
+static int gene_stats_checked(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n,
+                              double eps, void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, int path,
+                              void* stream) {
+    if (!data || !ws || !n_above || !mean || !sd) { set_error("gene_stats: null pointer"); return MMVAE_E_BADARG; }
+    if (vtype < 1 || vtype > 2) { set_error("gene_stats: value type %d outside [1, 2] (float, double)", vtype); return MMVAE_E_BADARG; }
+    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("gene_stats: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (n_total < 1) { set_error("gene_stats: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
+    if (!rows && n > n_total) { set_error("gene_stats: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
+    if (D < 1) { set_error("gene_stats: D = %d below 1", D); return MMVAE_E_BADARG; }
+    if (ld < D) { set_error("gene_stats: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
+    if (!(eps == eps)) { set_error("gene_stats: eps is NaN"); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("gene_stats: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+    if (reinterpret_cast<uintptr_t>(data) % cpm_vsize(vtype)) { set_error("gene_stats: data not aligned to its value type"); return MMVAE_E_BADARG; }
+    if (path < -1 || path > 1) { set_error("gene_stats: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
+    const size_t need = mmvae_gene_stats_workspace_bytes(n, D);
+    if (need == 0) {
+        set_error("gene_stats: n = %lld, D = %d need a grid of more than %lld workgroups", (long long)n, D, (long long)GS_MAX_BLOCKS);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (ws_bytes < need) {
+        set_error("gene_stats: workspace of %zu bytes below the %zu needed", ws_bytes, need);
+        return MMVAE_E_WORKSPACE;
+    }
+    const bool can = gs_wide(data, ld, cpm_vsize(vtype));
+    if (path == 1 && !can) {
+        set_error("gene_stats: 16-byte loads need a 16-byte aligned base and a row pitch of whole 16 bytes (ld = %lld)", (long long)ld);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_gene_stats(data, vtype, ld, n_total, D, rows, n, eps, ws, n_above, mean, sd, path < 0 ? can : path == 1,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
+                     void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, void* stream) {
+    return gene_stats_checked(data, vtype, ld, n_total, D, rows, n, eps, ws, ws_bytes, n_above, mean, sd, -1, stream);
+}
+
+int mmvae_debug_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
+                           void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, int path, void* stream) {
+    return gene_stats_checked(data, vtype, ld, n_total, D, rows, n, eps, ws, ws_bytes, n_above, mean, sd, path, stream);
+}
+
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

@@ -1031,6 +1031,23 @@ int launch_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* r
 int launch_symm_mul(const double* C, int64_t ldc, int D, const double* Q, int b, double* Y, hipStream_t st);
 int launch_pca_project(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const double* mean,
                        const double* V, int k, double* Z, hipStream_t st);
+// data preparation: normalise / log-CPM from dense or CSR counts, per-gene statistics (dataprep.hip)
+constexpr int CPM_THREADS = 256;       // threads of a workgroup of k_cpm_dense / k_cpm_csr: one workgroup a selected row
+constexpr int CPM_WINDOW = 4096;       // columns of the dense row that k_cpm_csr rebuilds in LDS at a time (32 KiB)
+constexpr int CPM_MAX_G = 1 << 20;     // genes at most: an int32 row sums to below 2^51, exact in a double
+constexpr int GS_SEG_ROWS = 256;       // rows per segment of k_gs_partial
+constexpr int GS_TILE = 256;           // genes per workgroup of k_gs_partial: one wave, four consecutive genes a lane
+constexpr int64_t GS_MAX_BLOCKS = ((int64_t)1 << 31) - 1;              // segments x gene tiles of one grid
+bool cpm_wide(const void* x, int64_t ld, int vsize);
+int launch_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n, const int* genes,
+                     int ng, double scaler, int log_mode, void* out, int otype, double* norms, bool wide, hipStream_t st);
+int launch_cpm_csr(const int64_t* indptr, const int* indices, const void* data, int vtype, int64_t nnz, int64_t n_total, int G,
+                   const int64_t* rows, int64_t n, const int* inv, int ng, double scaler, int log_mode, void* out, int otype,
+                   double* norms, hipStream_t st);
+int64_t gs_nseg(int64_t n);
+bool gs_wide(const void* data, int64_t ld, int vsize);
+int launch_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
+                      void* ws, int64_t* n_above, double* mean, double* sd, bool wide, hipStream_t st);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,
                       float* u_gumbel, float* u_state, uint8_t* s_mask, hipStream_t s);
 

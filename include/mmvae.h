@@ -594,6 +594,77 @@ size_t mmvae_pca_project_workspace_bytes(int64_t n, int D, int k);
 int mmvae_pca_project(const float *data, int64_t ld, int64_t n_total, const int64_t *rows /* NULL = 0..n-1 */, int64_t n,
                       int D, const double *mean, const double *V, int k, double *Z, void *stream);
 
+/* ---- data preparation (mmidas/utils/tools.py: normalize_cellxgene, logcpm, reorder_genes) ----
+ * The reference normalises a cell x gene count matrix with sklearn's normalize(x, axis=1, norm="l1") and takes
+ * np.log1p(. * scaler).  For the selected row r' (row rows[r'] of the matrix) and the selected gene j (column genes[j]):
+ *   norm = sum |x| over ALL G genes of the row, 1 where that is 0
+ *   out[r', j] = x / norm * scaler             (mode 0; scaler 1 gives the normalised matrix)
+ *   out[r', j] = log1p(x / norm * scaler)      (mode 1)
+ * the division, the product and log1p one IEEE double operation each, nothing contracted; x = 0 gives exactly 0; a float
+ * output is that double rounded once.  norms[r'] is the sum itself (0 for a zero row).  Value types (vtype): 0 int32,
+ * 1 float, 2 double; output types (otype): 0 float, 1 double.  An int32 row is summed in int64, exactly; a float or double
+ * row in fp64 in an order that depends on G alone: the row as 16-byte pieces, piece p to thread p mod 256 of the row's
+ * workgroup, a piece's values added in column order, a thread's pieces in order, the 256 sums by a fixed tree.  No atomics:
+ * bit-identical from run to run.  A NaN or an infinity in a row shows in its norm, which the caller can test; the rows'
+ * other values are then meaningless.
+ *
+ * mmvae_cpm_dense: x row-major [n_total, ld] of the value type, columns 0..G-1 used, read where it lies; rows int64 [n] on
+ *   the device or NULL for the rows 0..n-1 (then n <= n_total); genes int32 [ng] on the device or NULL for all G columns
+ *   in order (then ng = G).  out [n, ng] of the output type, row pitch ng, and norms double [n], on the device.  Only the
+ *   selected rows are read and only the selected columns are written.  Row indices outside [0, n_total) and gene indices
+ *   outside [0, G) are the CALLER'S CONTRACT: they are clamped, so they give wrong values and no access outside the
+ *   arrays.  All element offsets are 64-bit.  16-byte loads where x is 16-byte aligned and the row pitch a whole number of
+ *   16 bytes, else one value at a time: the same map and order, hence the same bits.
+ *   MMVAE_E_BADARG, before any device work, for a null x / out / norms, a vtype, otype or mode outside its range, n < 1 or
+ *   n >= 2^31, n_total < 1, rows NULL with n > n_total, G < 1, ng < 1, ld < G, genes NULL with ng != G, a scaler that is
+ *   not finite, a misaligned x; MMVAE_E_UNSUPPORTED for G or ng above 2^20.
+ * mmvae_debug_cpm_dense: the same with the load form named: path -1 the launcher's rule, 0 the narrow loads (any matrix),
+ *   1 the 16-byte loads (MMVAE_E_UNSUPPORTED where the base or ld does not allow them); same bits.
+ * mmvae_cpm_csr: the same matrix as CSR: indptr int64 [n_total + 1], indices int32 [nnz] and data [nnz] of the value
+ *   type, on the device; the indices of every row strictly increasing (canonical CSR: the CALLER'S CONTRACT).  inv int32
+ *   [G] on the device: the output column of gene g, or -1 for a gene that is not selected (ng <= G).  The library writes
+ *   the zeros of out itself.  The row's norm is summed in mmvae_cpm_dense's order (windows of 4096 columns of the dense
+ *   row are rebuilt in LDS), so out and norms are bit for bit those of mmvae_cpm_dense on the dense matrix.  Every position
+ *   read from indptr is clamped to [0, nnz]; an entry whose column is outside [0, G) is never used or written; an inv
+ *   value outside [0, ng) is not written: a table that breaks the contract gives wrong values and no access outside the
+ *   arrays.  An empty row gives a zero row.  MMVAE_E_BADARG as above, and for a null indptr / inv, nnz < 0, null indices
+ *   or data with nnz > 0, ng > G.
+ *
+ * mmvae_gene_stats: data float (vtype 1) or double (vtype 2) row-major [n_total, ld], columns 0..D-1 used, read where it
+ *   lies; rows as above.  Per gene d over the n selected rows: n_above int64 [D], the number of rows with x > eps, eps
+ *   rounded to the value type first (numpy's comparison of a float32 array with a Python float), exact; mean and sd double
+ *   [D], the mean and the population standard deviation from fp64 moments about the pivot p_d = x[rows[0], d]:
+ *   mean = p + s1 / n, sd = sqrt(max(0, (s2 - s1 s1 / n) / n)) with s1 = sum (x - p), s2 = sum (x - p)^2.  The rows are
+ *   cut into segments of 256; a wave owns one segment and 256 consecutive genes (16-byte loads where data is 16-byte
+ *   aligned and the row pitch a whole number of 16 bytes, else one value at a time: same bits) and adds its rows in
+ *   order; a last launch adds the segments in order.  No atomics: bit-identical from run to run, and a call with a row map
+ *   gives the bits of a call on those rows alone.  With kappa = 1 + (mean - p)^2 / var, mean and sd are within
+ *   (n + 2) kappa 2^-53 sd of the exact values on the same inputs, and the rounding of the value's own representation
+ *   (DESIGN.md section 9h).  INPUTS MUST BE FINITE.
+ *   ws: mmvae_gene_stats_workspace_bytes(n, D) = 8 * 3 * ceil(n / 256) * D bytes of device memory, 8-byte aligned; 0 for
+ *   arguments that mmvae_gene_stats refuses, or a size that size_t cannot hold.
+ *   MMVAE_E_BADARG, before any device work, for a null data / ws / n_above / mean / sd, a vtype outside [1, 2], n < 1 or
+ *   n > 2^31, n_total < 1, rows NULL with n > n_total, D < 1, ld < D, a NaN eps, a misaligned ws or data;
+ *   MMVAE_E_UNSUPPORTED for a grid (ceil(n / 256) ceil(D / 256) workgroups) of 2^31 or more; MMVAE_E_WORKSPACE for a ws
+ *   below the size.
+ * mmvae_debug_gene_stats: the same with the load form named, as mmvae_debug_cpm_dense. */
+int mmvae_cpm_dense(const void *x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t *rows /* NULL = 0..n-1 */,
+                    int64_t n, const int32_t *genes /* NULL = 0..G-1 */, int ng, double scaler, int mode, void *out,
+                    int otype, double *norms, void *stream);
+int mmvae_debug_cpm_dense(const void *x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t *rows, int64_t n,
+                          const int32_t *genes, int ng, double scaler, int mode, void *out, int otype, double *norms,
+                          int path, void *stream);
+int mmvae_cpm_csr(const int64_t *indptr, const int32_t *indices, const void *data, int vtype, int64_t nnz, int64_t n_total,
+                  int G, const int64_t *rows /* NULL = 0..n-1 */, int64_t n, const int32_t *inv, int ng, double scaler,
+                  int mode, void *out, int otype, double *norms, void *stream);
+size_t mmvae_gene_stats_workspace_bytes(int64_t n, int D);
+int mmvae_gene_stats(const void *data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t *rows /* NULL = 0..n-1 */,
+                     int64_t n, double eps, void *ws, size_t ws_bytes, int64_t *n_above, double *mean, double *sd,
+                     void *stream);
+int mmvae_debug_gene_stats(const void *data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t *rows, int64_t n,
+                           double eps, void *ws, size_t ws_bytes, int64_t *n_above, double *mean, double *sd, int path,
+                           void *stream);
+
 /* ---- augmenter forward in the training loop ----------------------
  * Replaces `self.netA(x.expand(A,-1,-1), True, 0.1)[1]` (mmidas/cpl_mixvae.py:422-423; netA.eval(), :184), i.e.
  * Augmenter_smartseq.forward in eval mode (mmidas/augmentation/udagan.py:281-329, reparam_trick
