@@ -166,7 +166,7 @@ def lib():
             "There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     vp, i64, f32, i32 = C.c_void_p, C.c_int64, C.c_float, C.c_int
-    L.mmvae_abi_version.restype = C.c_int
+    # (restype is set only where it is not int, ctypes' default)
     L.mmvae_last_error_string.restype = C.c_char_p
     L.mmvae_check_dims.argtypes = [C.POINTER(Dims)]
     L.mmvae_param_layout.argtypes = [C.POINTER(Dims), C.POINTER(ParamLayout)]
@@ -186,15 +186,12 @@ def lib():
                                    C.c_size_t, vp, vp, i32, vp, vp, i64, f32, f32, f32, f32, f32, i32, ex, vp]
     L.mmvae_train_step_rows.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, vp, i64, i64, vp, vp,
                                         C.c_size_t, vp, vp, i32, vp, vp, i64, f32, f32, f32, f32, f32, i32, ex, vp]
-    L.mmvae_train_step_rows.restype = C.c_int
     L.mmvae_to_bf16.argtypes = [vp, i64, i64, i32, vp, vp]
-    L.mmvae_to_bf16.restype = C.c_int
     L.mmvae_debug_stage.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), i32, vp, vp, i64, vp,
                                     C.c_size_t, vp, ex, vp]
     L.mmvae_dump_noise.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, vp]
     L.mmvae_debug_plan.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), ex, i32, i32, i32, i64, i32, i32,
                                    C.POINTER(C.c_int32 * PLAN_FIELDS)]
-    L.mmvae_debug_plan.restype = C.c_int
     L.mmvae_eval_classify.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, vp, i64, vp, C.c_size_t, vp, vp, ex,
                                       vp]
     L.mmvae_classify.argtypes = [vp, i64, i32, vp, vp]
@@ -203,33 +200,25 @@ def lib():
     L.mmvae_pair_stats.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, vp, vp]
     L.mmvae_debug_pair_stats.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, vp, i32, vp]
     L.mmvae_pair_stats_finish.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    for fn in ("mmvae_pair_stats", "mmvae_debug_pair_stats", "mmvae_pair_stats_finish"):
-        getattr(L, fn).restype = C.c_int
     L.mmvae_mutinfo_counts.argtypes = [vp, i32, i64, i32, vp, i32, i64, i32, vp, vp, vp, vp]
     L.mmvae_debug_mutinfo_counts.argtypes = [vp, i32, i64, i32, vp, i32, i64, i32, vp, vp, vp, i32, vp]
     L.mmvae_ami_binary_workspace_bytes.argtypes = [i64]
     L.mmvae_ami_binary_workspace_bytes.restype = C.c_size_t
     L.mmvae_ami_binary.argtypes = [vp, vp, vp, i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
-    for fn in ("mmvae_mutinfo_counts", "mmvae_debug_mutinfo_counts", "mmvae_ami_binary"):
-        getattr(L, fn).restype = C.c_int
     L.mmvae_silhouette_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_silhouette_workspace_bytes.restype = C.c_size_t
     L.mmvae_silhouette.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp]
-    L.mmvae_silhouette.restype = C.c_int
     L.mmvae_state_corr_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_state_corr_workspace_bytes.restype = C.c_size_t
     L.mmvae_state_corr.argtypes = [vp, i64, i64, i32, vp, vp, i64, i64, i32, vp, i32, vp, C.c_size_t, vp, vp, vp]
     L.mmvae_debug_state_corr.argtypes = [vp, i64, i64, i32, vp, vp, i64, i64, i32, vp, i32, vp, C.c_size_t, vp, vp, i32, vp]
-    L.mmvae_state_corr.restype = L.mmvae_debug_state_corr.restype = C.c_int
     L.mmvae_group_moments_workspace_bytes.argtypes = [i64, i32, i32]
     L.mmvae_group_moments_workspace_bytes.restype = C.c_size_t
     L.mmvae_group_moments.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp, vp]
     L.mmvae_debug_group_moments.argtypes = [vp, i64, i64, i32, vp, i32, vp, vp, C.c_size_t, vp, vp, i32, vp]
-    L.mmvae_group_moments.restype = L.mmvae_debug_group_moments.restype = C.c_int
     L.mmvae_gauss_scores_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_gauss_scores_workspace_bytes.restype = C.c_size_t
     L.mmvae_gauss_scores.argtypes = [vp, i64, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    L.mmvae_gauss_scores.restype = C.c_int
     L.mmvae_gram_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_gram_workspace_bytes.restype = C.c_size_t
     L.mmvae_gram_segments.argtypes = [i64, i32, C.POINTER(C.c_int64)]
@@ -241,8 +230,6 @@ def lib():
     L.mmvae_pca_project_workspace_bytes.argtypes = [i64, i32, i32]
     L.mmvae_pca_project_workspace_bytes.restype = C.c_size_t
     L.mmvae_pca_project.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp, i32, vp, vp]
-    for fn in ("mmvae_gram_segments", "mmvae_gram", "mmvae_debug_gram", "mmvae_symm_mul", "mmvae_pca_project"):
-        getattr(L, fn).restype = C.c_int
     f64 = C.c_double
     L.mmvae_cpm_dense.argtypes = [vp, i32, i64, i64, i32, vp, i64, vp, i32, f64, i32, vp, i32, vp, vp]
     L.mmvae_debug_cpm_dense.argtypes = [vp, i32, i64, i64, i32, vp, i64, vp, i32, f64, i32, vp, i32, vp, i32, vp]
@@ -251,8 +238,6 @@ def lib():
     L.mmvae_gene_stats_workspace_bytes.restype = C.c_size_t
     L.mmvae_gene_stats.argtypes = [vp, i32, i64, i64, i32, vp, i64, f64, vp, C.c_size_t, vp, vp, vp, vp]
     L.mmvae_debug_gene_stats.argtypes = [vp, i32, i64, i64, i32, vp, i64, f64, vp, C.c_size_t, vp, vp, vp, i32, vp]
-    for fn in ("mmvae_cpm_dense", "mmvae_debug_cpm_dense", "mmvae_cpm_csr", "mmvae_gene_stats", "mmvae_debug_gene_stats"):
-        getattr(L, fn).restype = C.c_int
     L.mmvae_aug_packed_floats.argtypes = [C.POINTER(AugDims)]
     L.mmvae_aug_packed_floats.restype = C.c_size_t
     L.mmvae_aug_workspace_bytes.argtypes = [C.POINTER(AugDims), i32]
@@ -267,32 +252,20 @@ def lib():
     L.mmvae_decode_workspace_bytes.argtypes = [C.POINTER(Dims), ex]
     L.mmvae_decode_workspace_bytes.restype = C.c_size_t
     L.mmvae_decode.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, i64, vp, i64, vp, vp, C.c_size_t, ex, vp]
-    L.mmvae_decode.restype = C.c_int
     L.mmvae_state_changes_workspace_bytes.argtypes = [C.POINTER(Dims), i32, ex]
     L.mmvae_state_changes_workspace_bytes.restype = C.c_size_t
     L.mmvae_state_changes.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, i32, i32, vp, vp,
                                       C.c_size_t, ex, vp]
-    L.mmvae_state_changes.restype = C.c_int
     L.mmvae_encode_workspace_bytes.argtypes = [C.POINTER(Dims), ex]
     L.mmvae_encode_workspace_bytes.restype = C.c_size_t
     L.mmvae_encode.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, i64, C.POINTER(EncodeOut),
                                i64, i64, vp, C.c_size_t, ex, vp]
-    L.mmvae_encode.restype = C.c_int
     L.mmvae_intermed.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, i64, vp, vp, vp]
-    L.mmvae_intermed.restype = C.c_int
     L.mmvae_prune_apply.argtypes = [C.POINTER(Dims), C.POINTER(C.c_uint32 * 4), vp, vp, vp, vp, vp]
-    L.mmvae_prune_apply.restype = C.c_int
-    for fn in ("mmvae_check_dims", "mmvae_param_layout", "mmvae_splits", "mmvae_forward", "mmvae_loss",
-               "mmvae_backward", "mmvae_adam_step", "mmvae_train_step", "mmvae_dump_noise", "mmvae_debug_stage",
-               "mmvae_eval_classify", "mmvae_classify", "mmvae_confmat_accumulate", "mmvae_consensus", "mmvae_aug_pack",
-               "mmvae_augment", "mmvae_gather_rows", "mmvae_tp_planes", "mmvae_augment_rows"):
-        getattr(L, fn).restype = C.c_int
     L.mmvae_dp_unique_id.argtypes = [vp]
     L.mmvae_dp_init.argtypes = [vp, i32, i32, C.POINTER(C.c_void_p)]
     L.mmvae_allreduce_grads.argtypes = [vp, vp, i64, vp]
     L.mmvae_dp_destroy.argtypes = [vp]
-    for fn in ("mmvae_dp_unique_id", "mmvae_dp_init", "mmvae_allreduce_grads", "mmvae_dp_destroy"):
-        getattr(L, fn).restype = C.c_int
     if L.mmvae_abi_version() != ABI_VERSION:
         raise NativeError("libmmvae_hip.so ABI version mismatch (rebuild: python distributed-vae_amd/build.py)")
     _lib = L
@@ -319,6 +292,47 @@ def _ptr(t: Optional[torch.Tensor]):
 
 def _stream(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# ---- what the wrappers of the evaluation and analysis entry points share ----
+LOAD_PATHS = {"auto": -1, "narrow": 0, "wide": 1}     # the load forms of a kernel that reads a matrix where it lies
+
+
+def _need_cuda(what: str, *tensors):
+    if any(t is not None and t.device.type != "cuda" for t in tensors):
+        raise NativeError(f"{what} needs CUDA tensors (no CPU fallback)")
+
+
+def _row_major(t: torch.Tensor) -> torch.Tensor:
+    """``t`` [n, D] as the kernels read it: rows may be strided, columns not -- ``t`` itself where it is that, else a copy."""
+    D = int(t.shape[1])
+    return t if D == 0 or (t.stride(1) == 1 and t.stride(0) >= D) else t.contiguous()
+
+
+def _row_map(what: str, rows: Optional[torch.Tensor], n_total: int) -> Tuple[Optional[torch.Tensor], int]:
+    """(the int64 row map or None, the number of selected rows)"""
+    if rows is None:
+        return None, n_total
+    if rows.dtype != torch.int64 or rows.dim() != 1:
+        raise TypeError(f"{what}: rows must be int64 [n]")
+    return rows.contiguous(), int(rows.numel())
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """An 8-byte aligned workspace of ``nbytes`` (never empty, so that it has an address)."""
+    return torch.empty(max(int(nbytes) // 8, 1), dtype=torch.float64, device=device)
+
+
+def _path(what: str, table: Dict[str, int], path: str) -> int:
+    if path not in table:
+        raise ValueError(f"{what}: path must be one of {sorted(table)}; got {path!r}")
+    return table[path]
+
+
+def _wide16(t: torch.Tensor) -> bool:
+    """The launcher's rule (wide16, csrc/common.hpp): the 16-byte loads where the matrix's base is 16-byte aligned and its
+    row pitch a whole number of 16 bytes (float32: a multiple of 4)."""
+    return t.data_ptr() % 16 == 0 and (t.stride(0) * t.element_size()) % 16 == 0
 
 
 def make_noise(explicit: Optional[Dict[str, torch.Tensor]] = None, seed: int = 0, offset: int = 0) -> Noise:
@@ -618,8 +632,7 @@ def classify(probs: torch.Tensor) -> torch.Tensor:
 
 def confmat_accumulate(labels: torch.Tensor, Cc: int, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
     """labels int32 [A, n] on the GPU -> counts int64 [A(A-1)/2, C, C] (+= when given)."""
-    if labels.device.type != "cuda":
-        raise NativeError("confmat_accumulate needs CUDA tensors (no CPU fallback)")
+    _need_cuda("confmat_accumulate", labels)
     lab = labels.contiguous().to(torch.int32)
     A, n = lab.shape
     if counts is None:
@@ -631,8 +644,7 @@ def confmat_accumulate(labels: torch.Tensor, Cc: int, counts: Optional[torch.Ten
 
 def consensus(counts: torch.Tensor, want_norm: bool = False):
     """counts int64 [pairs, C, C] -> consensus float64 [pairs] (and the normalised matrices when want_norm)."""
-    if counts.device.type != "cuda":
-        raise NativeError("consensus needs CUDA tensors (no CPU fallback)")
+    _need_cuda("consensus", counts)
     cnt = counts.contiguous()
     P, Cc, _ = cnt.shape
     out = torch.empty(P, dtype=torch.float64, device=cnt.device)
@@ -650,8 +662,7 @@ def pair_stats(labels: torch.Tensor, probs: torch.Tensor, pairs, Cc: int, counts
     """mmvae_pair_stats: labels int32 [T, n], probs float32 [T, n, C] on the GPU, ``pairs`` a host table [n_pairs][4] of arm
     indices (lab1, prob1, lab2, prob2) -> (counts int64 [n_pairs, C, C], dist_acc int64 [n_pairs, C, C, 2]), both ``+=`` when
     given.  ``path``: "auto" (the launcher's rule), "lds" or "wave" (mmvae_debug_pair_stats: the same sums on a named path)."""
-    if labels.device.type != "cuda" or probs.device.type != "cuda":
-        raise NativeError("pair_stats needs CUDA tensors (no CPU fallback)")
+    _need_cuda("pair_stats", labels, probs)
     import numpy as np
     tab = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 4))
     lab, pr = labels.contiguous(), probs.contiguous()
@@ -684,8 +695,7 @@ def pair_stats_finish(counts: torch.Tensor, dist_acc: torch.Tensor) -> Dict[str,
     """mmvae_pair_stats_finish on the accumulators of ``pair_stats``: float64 device tensors ``cm_norm``, ``emp``,
     ``dist_norm`` [n_pairs, C, C], ``diag_mean``, ``diag_min`` [n_pairs].  They are views of one buffer, ``packed`` (in this
     order), so that a caller can bring everything to the host with a single copy."""
-    if counts.device.type != "cuda" or dist_acc.device.type != "cuda":
-        raise NativeError("pair_stats_finish needs CUDA tensors (no CPU fallback)")
+    _need_cuda("pair_stats_finish", counts, dist_acc)
     cnt, acc = counts.contiguous(), dist_acc.contiguous()
     P, Cc, _ = cnt.shape
     if cnt.dtype != torch.int64 or acc.dtype != torch.int64 or tuple(acc.shape) != (P, Cc, Cc, 2):
@@ -711,8 +721,7 @@ def mutinfo_counts(labels: torch.Tensor, targets: torch.Tensor, Cc: int, F: Opti
     strided, columns not) on the GPU -> (counts int64 [A, F, C], t_sum int64 [F], p_sum int64 [A, C]); ``out``: the three
     accumulators of an earlier call, which this one adds to.  ``F``: the leading columns used (default: all).  ``path``:
     "auto" (the launcher's rule), "lds" or "global" (mmvae_debug_mutinfo_counts: the same counts on a named path)."""
-    if labels.device.type != "cuda" or targets.device.type != "cuda":
-        raise NativeError("mutinfo_counts needs CUDA tensors (no CPU fallback)")
+    _need_cuda("mutinfo_counts", labels, targets)
     lab = labels.contiguous()
     tg = targets.view(torch.uint8) if targets.dtype == torch.bool else targets
     if lab.dtype != torch.int32 or lab.dim() != 2 or tg.dtype not in (torch.uint8, torch.int32) or tg.dim() != 2:
@@ -744,8 +753,7 @@ def ami_binary(counts: torch.Tensor, t_sum: torch.Tensor, p_sum: torch.Tensor, n
     """mmvae_ami_binary on the counts of ``mutinfo_counts`` -> float64 [A, F, C] on the device: sklearn's adjusted mutual
     information of every (cell-type column, cluster) pair of binary labelings of ``n_cells`` cells, NaN where p_sum == 0.
     ``table``: log-gamma and log from a table in a workspace a first launch fills (the default), or evaluated per term."""
-    if counts.device.type != "cuda":
-        raise NativeError("ami_binary needs CUDA tensors (no CPU fallback)")
+    _need_cuda("ami_binary", counts)
     cnt, ts, ps = counts.contiguous(), t_sum.contiguous(), p_sum.contiguous()
     A, F, Cc = cnt.shape
     if any(t.dtype != torch.int64 for t in (cnt, ts, ps)) or tuple(ts.shape) != (F,) or tuple(ps.shape) != (A, Cc):
@@ -754,7 +762,7 @@ def ami_binary(counts: torch.Tensor, t_sum: torch.Tensor, p_sum: torch.Tensor, n
     ws, ws_bytes = None, 0
     if table:
         ws_bytes = int(lib().mmvae_ami_binary_workspace_bytes(int(n_cells)))
-        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=cnt.device)
+        ws = _workspace(ws_bytes, cnt.device)
     check(lib().mmvae_ami_binary(_ptr(cnt), _ptr(ts), _ptr(ps), A, F, Cc, int(n_cells), _ptr(ws), ws_bytes, _ptr(out),
                                  _stream(cnt.device)), "mmvae_ami_binary")
     return out
@@ -779,14 +787,13 @@ def silhouette(x_sorted: torch.Tensor, offsets: torch.Tensor, perm: Optional[tor
     ``offsets`` [K + 1] (cluster k is the rows offsets[k] .. offsets[k + 1] - 1) and, optionally, the int64 permutation
     ``perm`` [n] that sorted them (sorted row r is the caller's row perm[r]) -> sklearn's silhouette samples, float64 [n] on
     the device, in the caller's order.  ``path``: the launcher has one path, "auto"."""
-    if x_sorted.device.type != "cuda" or offsets.device.type != "cuda" or (perm is not None and perm.device.type != "cuda"):
-        raise NativeError("silhouette needs CUDA tensors (no CPU fallback)")
+    _need_cuda("silhouette", x_sorted, offsets, perm)
     if path != "auto":
         raise ValueError(f"silhouette: the launcher has one path, 'auto'; got {path!r}")
     if x_sorted.dtype != torch.float32 or x_sorted.dim() != 2 or offsets.dtype != torch.int64 or offsets.dim() != 1:
         raise TypeError("silhouette: x_sorted must be float32 [n, d] and offsets int64 [K + 1]")
     n, d = (int(v) for v in x_sorted.shape)
-    x = x_sorted if x_sorted.stride(1) == 1 and x_sorted.stride(0) >= d else x_sorted.contiguous()
+    x = _row_major(x_sorted)
     off = offsets.contiguous()
     K = int(off.numel()) - 1
     if perm is not None:
@@ -798,7 +805,7 @@ def silhouette(x_sorted: torch.Tensor, offsets: torch.Tensor, perm: Optional[tor
     elif out.dtype != torch.float64 or tuple(out.shape) != (n,) or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"silhouette: out must be a contiguous float64 [{n}] tensor on {x.device}")
     ws_bytes = int(lib().mmvae_silhouette_workspace_bytes(n, K))
-    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     check(lib().mmvae_silhouette(_ptr(x), int(x.stride(0)), n, d, _ptr(off), K, _ptr(perm), _ptr(ws), ws_bytes, _ptr(out),
                                  _stream(x.device)), "mmvae_silhouette")
     return out
@@ -808,12 +815,8 @@ def silhouette(x_sorted: torch.Tensor, offsets: torch.Tensor, perm: Optional[tor
 STATECORR_SEG_ROWS = 256        # SC_SEG_ROWS: a group of more rows is cut into segments of this many
 STATECORR_TILE = 256            # SC_TILE: genes per wave of k_sc_partial, four consecutive genes a lane
 STATECORR_MAX_S = 32            # SC_MAX_S
-STATECORR_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
-
-
-def state_corr_wide(data: torch.Tensor) -> bool:
-    """The launcher's rule: the 16-byte loads where the matrix's base is 16-byte aligned and its row pitch a multiple of 4."""
-    return data.data_ptr() % 16 == 0 and data.stride(0) % 4 == 0
+STATECORR_PATHS = LOAD_PATHS
+state_corr_wide = _wide16
 
 
 def state_corr(data: torch.Tensor, state: torch.Tensor, rows: Optional[torch.Tensor] = None,
@@ -824,17 +827,13 @@ def state_corr(data: torch.Tensor, state: torch.Tensor, rows: Optional[torch.Ten
     -> (r float64 [G, S, D], count int64 [G, D]) on the device: the Pearson correlation of every state with every gene over
     the group's cells with x > 0, exactly 0 where there are at most four of them, NaN where x or the state is constant over
     them.  Inputs must be finite.  ``path``: "auto" (the launcher's rule), "narrow", "wide" -- the load forms, equal bits."""
-    tensors = [t for t in (data, state, rows, offsets) if t is not None]
-    if any(t.device.type != "cuda" for t in tensors):
-        raise NativeError("state_corr needs CUDA tensors (no CPU fallback)")
-    if path not in STATECORR_PATHS:
-        raise ValueError(f"state_corr: path must be one of {sorted(STATECORR_PATHS)}; got {path!r}")
+    _need_cuda("state_corr", data, state, rows, offsets)
+    path = _path("state_corr", STATECORR_PATHS, path)
     if data.dtype != torch.float32 or data.dim() != 2 or state.dtype != torch.float32 or state.dim() != 2:
         raise TypeError("state_corr: data must be float32 [n_total, D] and state float32 [n, S]")
     n_total, Dm = (int(v) for v in data.shape)
     n, S = (int(v) for v in state.shape)
-    x = data if Dm == 0 or (data.stride(1) == 1 and data.stride(0) >= Dm) else data.contiguous()
-    st = state if S == 0 or (state.stride(1) == 1 and state.stride(0) >= S) else state.contiguous()
+    x, st = _row_major(data), _row_major(state)
     if rows is not None:
         if rows.dtype != torch.int64 or tuple(rows.shape) != (n,):
             raise TypeError(f"state_corr: rows must be int64 [{n}]")
@@ -848,9 +847,9 @@ def state_corr(data: torch.Tensor, state: torch.Tensor, rows: Optional[torch.Ten
     r = torch.empty(G, S, Dm, dtype=torch.float64, device=x.device)
     count = torch.empty(G, Dm, dtype=torch.int64, device=x.device)
     ws_bytes = int(lib().mmvae_state_corr_workspace_bytes(n, Dm, S, G))
-    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     check(lib().mmvae_debug_state_corr(_ptr(x), int(x.stride(0)), n_total, Dm, _ptr(rows), _ptr(st), int(st.stride(0)), n, S,
-                                       _ptr(offsets), G, _ptr(ws), ws_bytes, _ptr(r), _ptr(count), STATECORR_PATHS[path],
+                                       _ptr(offsets), G, _ptr(ws), ws_bytes, _ptr(r), _ptr(count), path,
                                        _stream(x.device)), "mmvae_state_corr")
     return r, count
 
@@ -878,24 +877,22 @@ def group_moments(x_sorted: torch.Tensor, offsets: torch.Tensor, pivot: torch.Te
     group the sum of x - pivot and the packed upper triangle of the sum of (x - pivot)(x - pivot)^T, the differences formed
     in fp64.  Inputs must be finite.  ``path``: "auto" (the launcher's rule) or "d16" / "d32" / "d64" / "d128", the
     instances of the segment kernel -- equal bits."""
-    if any(t.device.type != "cuda" for t in (x_sorted, offsets, pivot)):
-        raise NativeError("group_moments needs CUDA tensors (no CPU fallback)")
-    if path not in GAUSSCLF_PATHS:
-        raise ValueError(f"group_moments: path must be one of {sorted(GAUSSCLF_PATHS)}; got {path!r}")
+    _need_cuda("group_moments", x_sorted, offsets, pivot)
+    path = _path("group_moments", GAUSSCLF_PATHS, path)
     if x_sorted.dtype != torch.float32 or x_sorted.dim() != 2 or offsets.dtype != torch.int64 or offsets.dim() != 1:
         raise TypeError("group_moments: x_sorted must be float32 [n, d] and offsets int64 [G + 1]")
     n, d = (int(v) for v in x_sorted.shape)
     if pivot.dtype != torch.float32 or tuple(pivot.shape) != (d,):
         raise TypeError(f"group_moments: pivot must be float32 [{d}]")
-    x = x_sorted if x_sorted.stride(1) == 1 and x_sorted.stride(0) >= d else x_sorted.contiguous()
+    x = _row_major(x_sorted)
     off, piv = offsets.contiguous(), pivot.contiguous()
     G = int(off.numel()) - 1
     s = torch.empty(max(G, 0), d, dtype=torch.float64, device=x.device)
     M = torch.empty(max(G, 0), d * (d + 1) // 2, dtype=torch.float64, device=x.device)
     ws_bytes = int(lib().mmvae_group_moments_workspace_bytes(n, d, G))
-    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     check(lib().mmvae_debug_group_moments(_ptr(x), int(x.stride(0)), n, d, _ptr(off), G, _ptr(piv), _ptr(ws), ws_bytes, _ptr(s),
-                                          _ptr(M), GAUSSCLF_PATHS[path], _stream(x.device)), "mmvae_group_moments")
+                                          _ptr(M), path, _stream(x.device)), "mmvae_group_moments")
     return s, M
 
 
@@ -906,9 +903,7 @@ def gauss_scores(x: torch.Tensor, model: torch.Tensor, mu: torch.Tensor, W: torc
     int64 permutation ``perm`` [n] (row r is the caller's row perm[r]) -> (label int32 [n], best float64 [n], second
     float64 [n], scores float64 [n, K] or None) on the device, in the caller's order:
     score = c0 - |W^T (x - mu)|^2 / 2 under the row's own model, label its arg-max (the lowest index on ties)."""
-    tensors = [t for t in (x, model, mu, W, c0, perm) if t is not None]
-    if any(t.device.type != "cuda" for t in tensors):
-        raise NativeError("gauss_scores needs CUDA tensors (no CPU fallback)")
+    _need_cuda("gauss_scores", x, model, mu, W, c0, perm)
     if x.dtype != torch.float32 or x.dim() != 2:
         raise TypeError("gauss_scores: x must be float32 [n, d]")
     n, d = (int(v) for v in x.shape)
@@ -923,7 +918,7 @@ def gauss_scores(x: torch.Tensor, model: torch.Tensor, mu: torch.Tensor, W: torc
         if perm.dtype != torch.int64 or tuple(perm.shape) != (n,):
             raise TypeError(f"gauss_scores: perm must be int64 [{n}]")
         perm = perm.contiguous()
-    xs = x if x.stride(1) == 1 and x.stride(0) >= d else x.contiguous()
+    xs = _row_major(x)
     mu, W, c0, model = mu.contiguous(), W.contiguous(), c0.contiguous(), model.contiguous()
     label = torch.empty(n, dtype=torch.int32, device=xs.device)
     best = torch.empty(n, dtype=torch.float64, device=xs.device)
@@ -943,7 +938,8 @@ GRAM_MAX_SEGS = 3               # GRAM_MAX_SEGS: segments at most
 GRAM_FILL_TILES = 256           # GRAM_FILL_TILES: upper-triangle tiles from which the rows are not cut
 GRAM_MAX_D = 32768
 PCA_MAX_BLOCK = 64              # RM_CHUNK: the most columns of Q (mmvae_symm_mul) and of V (mmvae_pca_project)
-GRAM_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
+GRAM_PATHS = LOAD_PATHS
+gram_wide = _wide16
 
 
 def gram_segments(n: int, D: int) -> Tuple[int, int]:
@@ -953,24 +949,11 @@ def gram_segments(n: int, D: int) -> Tuple[int, int]:
     return nseg, int(rows.value) if nseg else 0
 
 
-def gram_wide(data: torch.Tensor) -> bool:
-    """The launcher's rule: the 16-byte loads where the matrix's base is 16-byte aligned and its row pitch a multiple of 4."""
-    return data.data_ptr() % 16 == 0 and data.stride(0) % 4 == 0
-
-
 def _rows_of(what: str, data: torch.Tensor, rows: Optional[torch.Tensor]):
-    """(the matrix as the kernels read it, the row map or None, n) after the checks the three entries share."""
+    """(the matrix as the kernels read it, the row map or None, n) after the checks mmvae_gram and mmvae_pca_project share."""
     if data.dtype != torch.float32 or data.dim() != 2:
         raise TypeError(f"{what}: data must be float32 [n_total, D]")
-    Dm = int(data.shape[1])
-    x = data if Dm == 0 or (data.stride(1) == 1 and data.stride(0) >= Dm) else data.contiguous()
-    n = int(data.shape[0])
-    if rows is not None:
-        if rows.dtype != torch.int64 or rows.dim() != 1:
-            raise TypeError(f"{what}: rows must be int64 [n]")
-        rows = rows.contiguous()
-        n = int(rows.numel())
-    return x, rows, n
+    return (_row_major(data),) + _row_map(what, rows, int(data.shape[0]))
 
 
 def gram(data: torch.Tensor, pivot: torch.Tensor, rows: Optional[torch.Tensor] = None, cov: bool = False,
@@ -980,10 +963,8 @@ def gram(data: torch.Tensor, pivot: torch.Tensor, rows: Optional[torch.Tensor] =
     [D, D]) on the device: with t = (double)x - (double)pivot, s = sum t and G = sum t t^T over the n rows, G exactly
     symmetric; with ``cov`` G is the unbiased covariance (G - s s^T / n) / (n - 1) instead.  Inputs must be finite.
     ``path``: "auto" (the launcher's rule), "narrow", "wide" -- the load forms, equal bits."""
-    if any(t.device.type != "cuda" for t in (data, pivot, rows) if t is not None):
-        raise NativeError("gram needs CUDA tensors (no CPU fallback)")
-    if path not in GRAM_PATHS:
-        raise ValueError(f"gram: path must be one of {sorted(GRAM_PATHS)}; got {path!r}")
+    _need_cuda("gram", data, pivot, rows)
+    path = _path("gram", GRAM_PATHS, path)
     x, rows, n = _rows_of("gram", data, rows)
     n_total, Dm = (int(v) for v in x.shape)
     if pivot.dtype != torch.float32 or tuple(pivot.shape) != (Dm,):
@@ -992,23 +973,22 @@ def gram(data: torch.Tensor, pivot: torch.Tensor, rows: Optional[torch.Tensor] =
     s = torch.empty(Dm, dtype=torch.float64, device=x.device)
     G = torch.empty(Dm, Dm, dtype=torch.float64, device=x.device)
     ws_bytes = int(lib().mmvae_gram_workspace_bytes(n, Dm))
-    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     check(lib().mmvae_debug_gram(_ptr(x), int(x.stride(0)), n_total, _ptr(rows), n, Dm, _ptr(piv), _ptr(ws), ws_bytes, _ptr(s),
-                                 _ptr(G), int(bool(cov)), GRAM_PATHS[path], _stream(x.device)), "mmvae_gram")
+                                 _ptr(G), int(bool(cov)), path, _stream(x.device)), "mmvae_gram")
     return s, G
 
 
 def symm_mul(Cm: torch.Tensor, Q: torch.Tensor) -> torch.Tensor:
     """mmvae_symm_mul: float64 ``Cm`` [D, D] (rows may be strided, columns not) times float64 ``Q`` [D, b], b <= 64, on the
     GPU -> Y float64 [D, b] on the device, every entry one fma chain in coordinate order."""
-    if Cm.device.type != "cuda" or Q.device.type != "cuda":
-        raise NativeError("symm_mul needs CUDA tensors (no CPU fallback)")
+    _need_cuda("symm_mul", Cm, Q)
     if Cm.dtype != torch.float64 or Cm.dim() != 2 or Cm.shape[0] != Cm.shape[1]:
         raise TypeError("symm_mul: C must be float64 [D, D]")
     Dm = int(Cm.shape[0])
     if Q.dtype != torch.float64 or Q.dim() != 2 or int(Q.shape[0]) != Dm:
         raise TypeError(f"symm_mul: Q must be float64 [{Dm}, b]")
-    Cc = Cm if Dm == 0 or (Cm.stride(1) == 1 and Cm.stride(0) >= Dm) else Cm.contiguous()
+    Cc = _row_major(Cm)
     Qc = Q.contiguous()
     b = int(Q.shape[1])
     Y = torch.empty(Dm, b, dtype=torch.float64, device=Cc.device)
@@ -1020,8 +1000,7 @@ def pca_project(data: torch.Tensor, mean: torch.Tensor, V: torch.Tensor, rows: O
     """mmvae_pca_project: float32 ``data`` [n_total, D] on the GPU (read where it lies), float64 ``mean`` [D] and ``V``
     [D, k], k <= 64, optionally the int64 row map ``rows`` [n] -> Z float64 [n, k] on the device: ((double)x - mean) V, row r
     of Z the sample rows[r], every entry one fma chain in coordinate order."""
-    if any(t.device.type != "cuda" for t in (data, mean, V, rows) if t is not None):
-        raise NativeError("pca_project needs CUDA tensors (no CPU fallback)")
+    _need_cuda("pca_project", data, mean, V, rows)
     x, rows, n = _rows_of("pca_project", data, rows)
     n_total, Dm = (int(v) for v in x.shape)
     if mean.dtype != torch.float64 or tuple(mean.shape) != (Dm,) or V.dtype != torch.float64 or V.dim() != 2 or int(V.shape[0]) != Dm:
@@ -1042,22 +1021,8 @@ GENESTATS_SEG_ROWS = 256        # GS_SEG_ROWS: rows per segment
 GENESTATS_TILE = 256            # GS_TILE: genes per wave, four consecutive genes a lane
 CPM_VTYPES = {torch.int32: 0, torch.float32: 1, torch.float64: 2}
 CPM_OTYPES = {torch.float32: 0, torch.float64: 1}
-CPM_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
-GENESTATS_PATHS = {"auto": -1, "narrow": 0, "wide": 1}
-
-
-def cpm_wide(x: torch.Tensor) -> bool:
-    """The launcher's rule of mmvae_cpm_dense and mmvae_gene_stats: the 16-byte loads where the matrix's base is 16-byte
-    aligned and its row pitch a whole number of 16 bytes."""
-    return x.data_ptr() % 16 == 0 and (x.stride(0) * x.element_size()) % 16 == 0
-
-
-def _cpm_rows(what: str, rows: Optional[torch.Tensor], n_total: int) -> Tuple[Optional[torch.Tensor], int]:
-    if rows is None:
-        return None, n_total
-    if rows.dtype != torch.int64 or rows.dim() != 1:
-        raise TypeError(f"{what}: rows must be int64 [n]")
-    return rows.contiguous(), int(rows.numel())
+CPM_PATHS = GENESTATS_PATHS = LOAD_PATHS
+cpm_wide = _wide16              # (the rule of mmvae_cpm_dense and of mmvae_gene_stats)
 
 
 def cpm_dense(x: torch.Tensor, rows: Optional[torch.Tensor] = None, genes: Optional[torch.Tensor] = None, scaler: float = 1.0,
@@ -1067,15 +1032,13 @@ def cpm_dense(x: torch.Tensor, rows: Optional[torch.Tensor] = None, genes: Optio
     ``out_dtype`` float32 or float64, norms float64 [n]) on the device: out = x / norm * scaler, or log1p of that with
     ``log``, norm the row's sum |x| over all G genes (1 where that is 0), norms the sums themselves.  ``path``: "auto" (the
     launcher's rule), "narrow", "wide" -- the load forms, equal bits."""
-    if any(t.device.type != "cuda" for t in (x, rows, genes) if t is not None):
-        raise NativeError("cpm_dense needs CUDA tensors (no CPU fallback)")
-    if path not in CPM_PATHS:
-        raise ValueError(f"cpm_dense: path must be one of {sorted(CPM_PATHS)}; got {path!r}")
+    _need_cuda("cpm_dense", x, rows, genes)
+    path = _path("cpm_dense", CPM_PATHS, path)
     if x.dtype not in CPM_VTYPES or x.dim() != 2 or out_dtype not in CPM_OTYPES:
         raise TypeError("cpm_dense: x must be int32, float32 or float64 [n_total, G] and out_dtype float32 or float64")
     n_total, G = (int(v) for v in x.shape)
-    xm = x if G == 0 or (x.stride(1) == 1 and x.stride(0) >= G) else x.contiguous()
-    rows, n = _cpm_rows("cpm_dense", rows, n_total)
+    xm = _row_major(x)
+    rows, n = _row_map("cpm_dense", rows, n_total)
     ng = G
     if genes is not None:
         if genes.dtype != torch.int32 or genes.dim() != 1:
@@ -1085,7 +1048,7 @@ def cpm_dense(x: torch.Tensor, rows: Optional[torch.Tensor] = None, genes: Optio
     out = torch.empty(n, ng, dtype=out_dtype, device=xm.device)
     norms = torch.empty(n, dtype=torch.float64, device=xm.device)
     check(lib().mmvae_debug_cpm_dense(_ptr(xm), CPM_VTYPES[xm.dtype], int(xm.stride(0)), n_total, G, _ptr(rows), n, _ptr(genes), ng,
-                                      float(scaler), int(bool(log)), _ptr(out), CPM_OTYPES[out_dtype], _ptr(norms), CPM_PATHS[path],
+                                      float(scaler), int(bool(log)), _ptr(out), CPM_OTYPES[out_dtype], _ptr(norms), path,
                                       _stream(xm.device)), "mmvae_cpm_dense")
     return out, norms
 
@@ -1097,8 +1060,7 @@ def cpm_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, sha
     float32 or float64 [nnz]) of ``shape`` (n_total, G) on the GPU, the inverse gene map ``inv`` int32 [G] (the output column
     of a gene, -1: not selected) onto ``ng`` columns, optionally the int64 row map ``rows`` [n] -> (out [n, ng], norms
     float64 [n]) as ``cpm_dense`` on the dense matrix, bit for bit."""
-    if any(t.device.type != "cuda" for t in (indptr, indices, data, inv, rows) if t is not None):
-        raise NativeError("cpm_csr needs CUDA tensors (no CPU fallback)")
+    _need_cuda("cpm_csr", indptr, indices, data, inv, rows)
     n_total, G = int(shape[0]), int(shape[1])
     if indptr.dtype != torch.int64 or tuple(indptr.shape) != (n_total + 1,):
         raise TypeError(f"cpm_csr: indptr must be int64 [{n_total + 1}]")
@@ -1109,7 +1071,7 @@ def cpm_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, sha
     if inv.dtype != torch.int32 or tuple(inv.shape) != (G,):
         raise TypeError(f"cpm_csr: inv must be int32 [{G}]")
     indptr, indices, data, inv = indptr.contiguous(), indices.contiguous(), data.contiguous(), inv.contiguous()
-    rows, n = _cpm_rows("cpm_csr", rows, n_total)
+    rows, n = _row_map("cpm_csr", rows, n_total)
     out = torch.empty(n, int(ng), dtype=out_dtype, device=data.device)
     norms = torch.empty(n, dtype=torch.float64, device=data.device)
     nnz = int(data.numel())
@@ -1125,22 +1087,20 @@ def gene_stats(x: torch.Tensor, eps: float, rows: Optional[torch.Tensor] = None,
     lies), optionally the int64 row map ``rows`` [n] -> (n_above int64 [D], mean float64 [D], std float64 [D]) on the
     device: per gene the number of selected rows with x > eps (eps rounded to x's dtype), the mean and the population
     standard deviation.  Inputs must be finite.  ``path``: "auto", "narrow", "wide" -- the load forms, equal bits."""
-    if any(t.device.type != "cuda" for t in (x, rows) if t is not None):
-        raise NativeError("gene_stats needs CUDA tensors (no CPU fallback)")
-    if path not in GENESTATS_PATHS:
-        raise ValueError(f"gene_stats: path must be one of {sorted(GENESTATS_PATHS)}; got {path!r}")
+    _need_cuda("gene_stats", x, rows)
+    path = _path("gene_stats", GENESTATS_PATHS, path)
     if x.dtype not in (torch.float32, torch.float64) or x.dim() != 2:
         raise TypeError("gene_stats: x must be float32 or float64 [n_total, D]")
     n_total, Dm = (int(v) for v in x.shape)
-    xm = x if Dm == 0 or (x.stride(1) == 1 and x.stride(0) >= Dm) else x.contiguous()
-    rows, n = _cpm_rows("gene_stats", rows, n_total)
+    xm = _row_major(x)
+    rows, n = _row_map("gene_stats", rows, n_total)
     n_above = torch.empty(Dm, dtype=torch.int64, device=xm.device)
     mean = torch.empty(Dm, dtype=torch.float64, device=xm.device)
     sd = torch.empty(Dm, dtype=torch.float64, device=xm.device)
     ws_bytes = int(lib().mmvae_gene_stats_workspace_bytes(n, Dm))
-    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=xm.device)
+    ws = _workspace(ws_bytes, xm.device)
     check(lib().mmvae_debug_gene_stats(_ptr(xm), CPM_VTYPES[xm.dtype], int(xm.stride(0)), n_total, Dm, _ptr(rows), n, float(eps),
-                                       _ptr(ws), ws_bytes, _ptr(n_above), _ptr(mean), _ptr(sd), GENESTATS_PATHS[path],
+                                       _ptr(ws), ws_bytes, _ptr(n_above), _ptr(mean), _ptr(sd), path,
                                        _stream(xm.device)), "mmvae_gene_stats")
     return n_above, mean, sd
 
@@ -1178,8 +1138,7 @@ def tp_planes(data: torch.Tensor, n_planes: int) -> Optional[torch.Tensor]:
 
 def gather_rows(data: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[i] = data[idx[i]] for a 2-D float32 CUDA matrix (rows may be strided) and int64 CUDA indices."""
-    if data.device.type != "cuda" or idx.device.type != "cuda":
-        raise NativeError("gather_rows needs CUDA tensors (no CPU fallback)")
+    _need_cuda("gather_rows", data, idx)
     assert data.dim() == 2 and data.dtype == torch.float32 and data.stride(1) == 1
     idx = idx.to(torch.int64).contiguous()
     n, Dm = idx.numel(), data.shape[1]

@@ -77,6 +77,28 @@ def consensus_from_counts(counts: torch.Tensor) -> torch.Tensor:
     return N.consensus(counts)
 
 
+def float32_on_device(a, device, what: str, shape_words: str, check_device_finite: bool = False) -> torch.Tensor:
+    """``a`` as float32 [., .] on ``device`` for the analysis routines of ``utils/``: a float32 device tensor as it is (with
+    its stride), anything else rounded to float32 and uploaded (a read-only array through a copy).  ``what`` and
+    ``shape_words`` name the argument and its shape in the messages.  Host input is always checked for NaN and infinity; a
+    device tensor only with ``check_device_finite`` (otherwise finite values are the caller's side of the kernel's contract)."""
+    if isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.device.type == "cuda":
+        if a.dim() != 2:
+            raise ValueError(f"{what} of shape {tuple(a.shape)} is not {shape_words}")
+        if check_device_finite and not bool(torch.isfinite(a).all()):
+            raise ValueError(f"{what} holds NaN or infinity")
+        return a
+    from .cpl_mixvae import get_device          # (cpl_mixvae imports this module, inside its functions)
+    h = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if h.ndim != 2:
+        raise ValueError(f"{what} of shape {h.shape} is not {shape_words}")
+    with np.errstate(over="ignore"):
+        h = np.ascontiguousarray(h, dtype=np.float32)
+    if not np.isfinite(h).all():
+        raise ValueError(f"{what} holds NaN or infinity (or a value float32 cannot hold)")
+    return torch.from_numpy(h if h.flags.writeable else h.copy()).to(get_device(device))
+
+
 def mk_masks(bias):
     """_utils.py:74-75: ``(pruning_mask, inds_prune)`` = the indices of the non-zero / zero entries of a bias vector
     (the categories a pruned model keeps / has dropped), int64 numpy arrays."""

@@ -888,472 +888,6 @@ int mmvae_prune_apply(const mmvae_dims* d, const uint32_t cat_mask[4], float* pa
     return launch_prune_apply(*d, make_poff(*d), cat_mask, params, grads, exp_avg, exp_avg_sq, reinterpret_cast<hipStream_t>(stream));
 }
 
-int mmvae_classify(const float* c_probs, int64_t n_cells, int C, int32_t* labels, void* stream) {
-    if (!c_probs || !labels || n_cells <= 0 || C <= 0) { set_error("classify: bad argument"); return MMVAE_E_BADARG; }
-    return launch_classify(c_probs, n_cells, C, labels, reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_confmat_accumulate(const int32_t* labels, int A, int64_t n, int C, int64_t* counts, void* stream) {
-    if (!labels || !counts || A < 1 || A > MMVAE_MAX_ARMS || n <= 0 || C <= 0) {
-        set_error("confmat_accumulate: bad argument");
-        return MMVAE_E_BADARG;
-    }
-    return launch_confmat(labels, A, n, C, counts, reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_consensus(const int64_t* counts, int npairs, int C, double* cm_norm, double* consensus, void* stream) {
-    if (!counts || !consensus || npairs < 1 || C < 1) { set_error("consensus: bad argument"); return MMVAE_E_BADARG; }
-    if (C > 128) { set_error("consensus: C > 128 unsupported"); return MMVAE_E_UNSUPPORTED; }
-    return launch_consensus(counts, npairs, C, cm_norm, consensus, reinterpret_cast<hipStream_t>(stream));
-}
-
-// every argument of mmvae_pair_stats is checked here, on the host, before any device work
-static int pair_stats_args(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
-                           int n_pairs, const int64_t* counts, const int64_t* dist_acc) {
-    if (!labels || !probs || !pairs || !counts || !dist_acc) { set_error("pair_stats: null pointer"); return MMVAE_E_BADARG; }
-    if (C < 1 || C > 128) { set_error("pair_stats: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
-    if (n < 0 || n_pairs < 0) { set_error("pair_stats: negative n or n_pairs"); return MMVAE_E_BADARG; }
-    if (n > ((int64_t)1 << 31)) { set_error("pair_stats: more than 2^31 cells in one call"); return MMVAE_E_BADARG; }
-    if (n_arms_total < 1 || n_arms_total > 2 * MMVAE_MAX_ARMS) {
-        set_error("pair_stats: n_arms_total = %d outside [1, %d]", n_arms_total, 2 * MMVAE_MAX_ARMS);
-        return MMVAE_E_BADARG;
-    }
-    for (int64_t k = 0; k < 4 * (int64_t)n_pairs; ++k)
-        if (pairs[k] < 0 || pairs[k] >= n_arms_total) {
-            set_error("pair_stats: pairs[%lld][%d] = %d outside [0, %d)", (long long)(k / 4), (int)(k % 4), pairs[k], n_arms_total);
-            return MMVAE_E_BADARG;
-        }
-    return 0;
-}
-
-int mmvae_pair_stats(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
-                     int n_pairs, int64_t* counts, int64_t* dist_acc, void* stream) {
-    if (int rc = pair_stats_args(labels, probs, n_arms_total, n, C, pairs, n_pairs, counts, dist_acc)) return rc;
-    if (n == 0 || n_pairs == 0) return 0;
-    return launch_pair_stats(labels, probs, n, C, pairs, n_pairs, counts, dist_acc, -1, reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_debug_pair_stats(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
-                           int n_pairs, int64_t* counts, int64_t* dist_acc, int path, void* stream) {
-    if (int rc = pair_stats_args(labels, probs, n_arms_total, n, C, pairs, n_pairs, counts, dist_acc)) return rc;
-    if (path < -1 || path > 1) { set_error("debug_pair_stats: path %d outside {-1, 0, 1}", path); return MMVAE_E_BADARG; }
-    if (n == 0 || n_pairs == 0) return 0;
-    return launch_pair_stats(labels, probs, n, C, pairs, n_pairs, counts, dist_acc, path, reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_pair_stats_finish(const int64_t* counts, const int64_t* dist_acc, int n_pairs, int C, double* cm_norm, double* emp,
-                            double* dist_norm, double* diag_mean, double* diag_min, void* stream) {
-    if (!counts || !dist_acc || !cm_norm || !emp || !dist_norm || !diag_mean || !diag_min) {
-        set_error("pair_stats_finish: null pointer");
-        return MMVAE_E_BADARG;
-    }
-    if (C < 1 || C > 128) { set_error("pair_stats_finish: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
-    if (n_pairs < 0) { set_error("pair_stats_finish: negative n_pairs"); return MMVAE_E_BADARG; }
-    if (n_pairs == 0) return 0;
-    return launch_pair_finish(counts, dist_acc, n_pairs, C, cm_norm, emp, dist_norm, diag_mean, diag_min,
-                              reinterpret_cast<hipStream_t>(stream));
-}
-
-// every argument of mmvae_mutinfo_counts is checked here, on the host, before any device work
-static int mutinfo_counts_args(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt,
-                               int F, const int64_t* counts, const int64_t* t_sum, const int64_t* p_sum) {
-    if (!labels || !targets || !counts || !t_sum || !p_sum) { set_error("mutinfo_counts: null pointer"); return MMVAE_E_BADARG; }
-    if (A < 1 || A > MMVAE_MAX_ARMS) { set_error("mutinfo_counts: A = %d outside [1, %d]", A, MMVAE_MAX_ARMS); return MMVAE_E_BADARG; }
-    if (C < 1 || C > 128) { set_error("mutinfo_counts: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
-    if (F < 1 || F > 4096) { set_error("mutinfo_counts: F = %d outside [1, 4096]", F); return MMVAE_E_BADARG; }
-    if (n < 0 || n > ((int64_t)1 << 31)) { set_error("mutinfo_counts: n outside [0, 2^31]"); return MMVAE_E_BADARG; }
-    if (ldt < F) { set_error("mutinfo_counts: ldt = %lld below F = %d", (long long)ldt, F); return MMVAE_E_BADARG; }
-    if (target_bytes != 1 && target_bytes != 4) {
-        set_error("mutinfo_counts: target_bytes = %d is neither 1 (uint8) nor 4 (int32)", target_bytes);
-        return MMVAE_E_BADARG;
-    }
-    return 0;
-}
-
-int mmvae_mutinfo_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt, int F,
-                         int64_t* counts, int64_t* t_sum, int64_t* p_sum, void* stream) {
-    if (int rc = mutinfo_counts_args(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum)) return rc;
-    if (n == 0) return 0;
-    return launch_mi_counts(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum, -1,
-                            reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_debug_mutinfo_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt,
-                               int F, int64_t* counts, int64_t* t_sum, int64_t* p_sum, int path, void* stream) {
-    if (int rc = mutinfo_counts_args(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum)) return rc;
-    if (path < -1 || path > 1) { set_error("debug_mutinfo_counts: path %d outside {-1, 0, 1}", path); return MMVAE_E_BADARG; }
-    if (n == 0) return 0;
-    return launch_mi_counts(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum, path,
-                            reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t mmvae_ami_binary_workspace_bytes(int64_t N) {
-    return N < 1 || N > ((int64_t)1 << 31) ? 0 : 2 * (size_t)(N + 1) * sizeof(double);
-}
-
-int mmvae_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_sum, int A, int F, int C, int64_t N, void* ws,
-                     size_t ws_bytes, double* ami, void* stream) {
-    if (!n11 || !t_sum || !p_sum || !ami) { set_error("ami_binary: null pointer"); return MMVAE_E_BADARG; }
-    if (A < 0 || A > MMVAE_MAX_ARMS) { set_error("ami_binary: A = %d outside [0, %d]", A, MMVAE_MAX_ARMS); return MMVAE_E_BADARG; }
-    if (C < 1 || C > 128) { set_error("ami_binary: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
-    if (F < 1 || F > 4096) { set_error("ami_binary: F = %d outside [1, 4096]", F); return MMVAE_E_BADARG; }
-    if (N < 1 || N > ((int64_t)1 << 31)) { set_error("ami_binary: N outside [1, 2^31]"); return MMVAE_E_BADARG; }
-    if (ws) {
-        if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("ami_binary: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-        if (ws_bytes < mmvae_ami_binary_workspace_bytes(N)) {
-            set_error("ami_binary: workspace of %zu bytes below the %zu needed", ws_bytes, mmvae_ami_binary_workspace_bytes(N));
-            return MMVAE_E_WORKSPACE;
-        }
-    }
-    if (A == 0) return 0;
-    return launch_ami_binary(n11, t_sum, p_sum, A, F, C, N, static_cast<double*>(ws), ami, reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t mmvae_silhouette_workspace_bytes(int64_t n, int K) {
-    if (n < 3 || n > ((int64_t)1 << 31) || K < 2 || K > n - 1) return 0;
-    const unsigned __int128 nseg = (unsigned __int128)sil_nseg_max(n, K);
-    const unsigned __int128 bytes = 8 * (nseg * (unsigned __int128)n + nseg + 1) + 4 * (((unsigned __int128)K + 2) / 2 * 2);
-    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
-}
-
-// every argument is checked here, on the host, before any device work
-int mmvae_silhouette(const float* x_sorted, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
-                     size_t ws_bytes, double* s, void* stream) {
-    if (!x_sorted || !offsets || !ws || !s) { set_error("silhouette: null pointer"); return MMVAE_E_BADARG; }
-    if (n < 3 || n > ((int64_t)1 << 31)) { set_error("silhouette: n outside [3, 2^31]"); return MMVAE_E_BADARG; }
-    if (K < 2 || K > n - 1) { set_error("silhouette: K = %d outside [2, n - 1 = %lld]", K, (long long)(n - 1)); return MMVAE_E_BADARG; }
-    if (d < 1) { set_error("silhouette: d = %d below 1", d); return MMVAE_E_BADARG; }
-    if (ld < d) { set_error("silhouette: ld = %lld below d = %d", (long long)ld, d); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("silhouette: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-    if (d > SIL_MAX_D) { set_error("silhouette: d = %d above %d", d, SIL_MAX_D); return MMVAE_E_UNSUPPORTED; }
-    const size_t need = mmvae_silhouette_workspace_bytes(n, K);
-    if (sil_nseg_max(n, K) > SIL_MAX_SEGMENTS || need == 0) {
-        set_error("silhouette: K + n / %d = %lld segments above %lld", SIL_SEG_COLS, (long long)sil_nseg_max(n, K), (long long)SIL_MAX_SEGMENTS);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (ws_bytes < need) {
-        set_error("silhouette: workspace of %zu bytes below the %zu needed", ws_bytes, need);
-        return MMVAE_E_WORKSPACE;
-    }
-    return launch_silhouette(x_sorted, ld, n, d, offsets, K, perm, ws, s, reinterpret_cast<hipStream_t>(stream));
-}
-
-// the most segments and the most workgroups of one grid that mmvae_state_corr launches; false where it refuses the shape
-static bool sc_shape_ok(int64_t n, int D, int S, int G) {
-    if (S > SC_MAX_S) return false;
-    const unsigned __int128 tiles = (unsigned __int128)cdiv64(D, SC_TILE);
-    return (unsigned __int128)sc_nseg_max(n, G) * tiles <= (unsigned __int128)SC_MAX_BLOCKS &&
-           (unsigned __int128)G * (unsigned __int128)cdiv64(D, 256) <= (unsigned __int128)SC_MAX_BLOCKS;
-}
-
-size_t mmvae_state_corr_workspace_bytes(int64_t n, int D, int S, int G) {
-    if (n < 1 || n > ((int64_t)1 << 31) || D < 1 || S < 1 || G < 1 || !sc_shape_ok(n, D, S, G)) return 0;
-    const unsigned __int128 nseg = (unsigned __int128)sc_nseg_max(n, G);
-    const unsigned __int128 bytes = 8 * (nseg * (unsigned __int128)(5 + 5 * S) * (unsigned __int128)D + nseg + 1) +
-                                    4 * (((unsigned __int128)G + 2) / 2 * 2);
-    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
-}
-
-// every argument is checked here, on the host, before any device work.  path: -1 the launcher's rule (the 16-byte loads where
-// the base and the row pitch allow them), 0 the narrow loads, 1 the 16-byte loads
-static int state_corr_checked(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state,
-                              int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
-                              int64_t* count, int path, void* stream) {
-    if (!data || !state || !ws || !r || !count) { set_error("state_corr: null pointer"); return MMVAE_E_BADARG; }
-    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("state_corr: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
-    if (n_total < 1) { set_error("state_corr: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
-    if (!rows && n > n_total) { set_error("state_corr: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
-    if (D < 1 || S < 1 || G < 1) { set_error("state_corr: D = %d, S = %d, G = %d: each must be at least 1", D, S, G); return MMVAE_E_BADARG; }
-    if (ld < D) { set_error("state_corr: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
-    if (lds < S) { set_error("state_corr: lds = %lld below S = %d", (long long)lds, S); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("state_corr: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-    if (S > SC_MAX_S) { set_error("state_corr: S = %d above %d", S, SC_MAX_S); return MMVAE_E_UNSUPPORTED; }
-    const size_t need = mmvae_state_corr_workspace_bytes(n, D, S, G);
-    if (!sc_shape_ok(n, D, S, G) || need == 0) {
-        set_error("state_corr: n = %lld, D = %d, G = %d need a grid of more than %lld workgroups", (long long)n, D, G, (long long)SC_MAX_BLOCKS);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (ws_bytes < need) {
-        set_error("state_corr: workspace of %zu bytes below the %zu needed", ws_bytes, need);
-        return MMVAE_E_WORKSPACE;
-    }
-    if (path < -1 || path > 1) { set_error("state_corr: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
-    if (path == 1 && !sc_wide(data, ld)) {
-        set_error("state_corr: 16-byte loads need a 16-byte aligned base and ld a multiple of 4 (ld = %lld)", (long long)ld);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    return launch_state_corr(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, r, count,
-                             path < 0 ? sc_wide(data, ld) : path == 1, reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
-                     int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r, int64_t* count,
-                     void* stream) {
-    return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, -1, stream);
-}
-
-int mmvae_debug_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state,
-                           int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
-                           int64_t* count, int path, void* stream) {
-    return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, path, stream);
-}
-
-size_t mmvae_group_moments_workspace_bytes(int64_t n, int d, int G) {
-    if (n < 1 || n > ((int64_t)1 << 31) || d < 1 || d > GC_MAX_D || G < 1 || G > GC_MAX_G) return 0;
-    const unsigned __int128 nseg = (unsigned __int128)gc_nseg_max(n, G);
-    const unsigned __int128 bytes = 8 * (nseg * (unsigned __int128)(d * (d + 3) / 2) + nseg + 1) + 4 * (((unsigned __int128)G + 2) / 2 * 2);
-    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
-}
-
-// every argument is checked here, on the host, before any device work.  dclass: -1 the launcher's rule (the first instance
-// of GC_DC that holds d), 0 .. GC_N_DC - 1 that instance
-static int group_moments_checked(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot,
-                                 void* ws, size_t ws_bytes, double* s, double* M, int dclass, void* stream) {
-    if (!x || !offsets || !pivot || !ws || !s || !M) { set_error("group_moments: null pointer"); return MMVAE_E_BADARG; }
-    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("group_moments: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
-    if (d < 1 || G < 1) { set_error("group_moments: d = %d, G = %d: each must be at least 1", d, G); return MMVAE_E_BADARG; }
-    if (ld < d) { set_error("group_moments: ld = %lld below d = %d", (long long)ld, d); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("group_moments: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-    if (dclass < -1 || dclass >= GC_N_DC) { set_error("group_moments: dclass = %d outside [-1, %d]", dclass, GC_N_DC - 1); return MMVAE_E_BADARG; }
-    if (d > GC_MAX_D) { set_error("group_moments: d = %d above %d", d, GC_MAX_D); return MMVAE_E_UNSUPPORTED; }
-    if (G > GC_MAX_G) { set_error("group_moments: G = %d above %d", G, GC_MAX_G); return MMVAE_E_UNSUPPORTED; }
-    const size_t need = mmvae_group_moments_workspace_bytes(n, d, G);
-    if (need == 0) { set_error("group_moments: a workspace size_t cannot hold"); return MMVAE_E_UNSUPPORTED; }
-    if (ws_bytes < need) {
-        set_error("group_moments: workspace of %zu bytes below the %zu needed", ws_bytes, need);
-        return MMVAE_E_WORKSPACE;
-    }
-    if (dclass >= 0 && d > GC_DC[dclass]) {
-        set_error("group_moments: the instance for d <= %d cannot run d = %d", GC_DC[dclass], d);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    return launch_group_moments(x, ld, n, d, offsets, G, pivot, ws, s, M, dclass < 0 ? gc_dclass(d) : dclass,
-                                reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot, void* ws,
-                        size_t ws_bytes, double* s, double* M, void* stream) {
-    return group_moments_checked(x, ld, n, d, offsets, G, pivot, ws, ws_bytes, s, M, -1, stream);
-}
-
-int mmvae_debug_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot,
-                              void* ws, size_t ws_bytes, double* s, double* M, int dclass, void* stream) {
-    return group_moments_checked(x, ld, n, d, offsets, G, pivot, ws, ws_bytes, s, M, dclass, stream);
-}
-
-// the kernel keeps nothing between launches
-size_t mmvae_gauss_scores_workspace_bytes(int64_t n, int d, int F, int K) {
-    (void)n; (void)d; (void)F; (void)K;
-    return 0;
-}
-
-int mmvae_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int32_t* model, int F, int K, const double* mu,
-                       const double* W, const double* c0, const int64_t* perm, void* ws, size_t ws_bytes, int32_t* label,
-                       double* best, double* second, double* scores, void* stream) {
-    (void)ws_bytes;
-    if (!x || !model || !mu || !W || !c0 || !label || !best || !second) { set_error("gauss_scores: null pointer"); return MMVAE_E_BADARG; }
-    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("gauss_scores: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
-    if (d < 1 || F < 1 || K < 1) { set_error("gauss_scores: d = %d, F = %d, K = %d: each must be at least 1", d, F, K); return MMVAE_E_BADARG; }
-    if (ld < d) { set_error("gauss_scores: ld = %lld below d = %d", (long long)ld, d); return MMVAE_E_BADARG; }
-    if (ws && reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("gauss_scores: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-    if (d > GC_MAX_D || K > GC_MAX_K || F > GC_MAX_F) {
-        set_error("gauss_scores: d = %d, K = %d, F = %d above %d, %d, %d", d, K, F, GC_MAX_D, GC_MAX_K, GC_MAX_F);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    return launch_gauss_scores(x, ld, n, d, model, F, K, mu, W, c0, perm, label, best, second, scores,
-                               reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_gram_segments(int64_t n, int D, int64_t* seg_rows) {
-    if (n < 2 || n > ((int64_t)1 << 31) || D < 1 || D > GRAM_MAX_D) return 0;
-    return gram_segments(n, D, seg_rows);
-}
-
-size_t mmvae_gram_workspace_bytes(int64_t n, int D) {
-    const int nseg = mmvae_gram_segments(n, D, nullptr);
-    if (nseg == 0) return 0;
-    return sizeof(double) * ((size_t)(nseg - 1) * (size_t)D * (size_t)D + (size_t)nseg * (size_t)D);
-}
-
-// every argument is checked here, on the host, before any device work.  path: -1 the launcher's rule, 0 the narrow loads,
-// 1 the 16-byte loads
-static int gram_checked(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot,
-                        void* ws, size_t ws_bytes, double* s, double* G, int cov, int path, void* stream) {
-    if (!data || !pivot || !ws || !s || !G) { set_error("gram: null pointer"); return MMVAE_E_BADARG; }
-    if (n < 2 || n > ((int64_t)1 << 31)) { set_error("gram: n outside [2, 2^31]"); return MMVAE_E_BADARG; }
-    if (n_total < 1) { set_error("gram: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
-    if (!rows && n > n_total) { set_error("gram: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
-    if (D < 1) { set_error("gram: D = %d below 1", D); return MMVAE_E_BADARG; }
-    if (ld < D) { set_error("gram: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("gram: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-    if (cov < 0 || cov > 1) { set_error("gram: cov = %d outside [0, 1]", cov); return MMVAE_E_BADARG; }
-    if (path < -1 || path > 1) { set_error("gram: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
-    if (D > GRAM_MAX_D) { set_error("gram: D = %d above %d", D, GRAM_MAX_D); return MMVAE_E_UNSUPPORTED; }
-    const size_t need = mmvae_gram_workspace_bytes(n, D);
-    if (ws_bytes < need) {
-        set_error("gram: workspace of %zu bytes below the %zu needed", ws_bytes, need);
-        return MMVAE_E_WORKSPACE;
-    }
-    if (path == 1 && !gram_wide(data, ld)) {
-        set_error("gram: 16-byte loads need a 16-byte aligned base and ld a multiple of 4 (ld = %lld)", (long long)ld);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    return launch_gram(data, ld, n_total, rows, n, D, pivot, ws, s, G, cov, path < 0 ? gram_wide(data, ld) : path == 1,
-                       reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot, void* ws,
-               size_t ws_bytes, double* s, double* G, int cov, void* stream) {
-    return gram_checked(data, ld, n_total, rows, n, D, pivot, ws, ws_bytes, s, G, cov, -1, stream);
-}
-
-int mmvae_debug_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot,
-                     void* ws, size_t ws_bytes, double* s, double* G, int cov, int path, void* stream) {
-    return gram_checked(data, ld, n_total, rows, n, D, pivot, ws, ws_bytes, s, G, cov, path, stream);
-}
-
-// the kernel keeps nothing between launches
-size_t mmvae_symm_mul_workspace_bytes(int D, int b) {
-    (void)D; (void)b;
-    return 0;
-}
-
-int mmvae_symm_mul(const double* C, int64_t ldc, int D, const double* Q, int b, double* Y, void* stream) {
-    if (!C || !Q || !Y) { set_error("symm_mul: null pointer"); return MMVAE_E_BADARG; }
-    if (D < 1 || b < 1) { set_error("symm_mul: D = %d, b = %d: each must be at least 1", D, b); return MMVAE_E_BADARG; }
-    if (ldc < D) { set_error("symm_mul: ldc = %lld below D = %d", (long long)ldc, D); return MMVAE_E_BADARG; }
-    if (D > GRAM_MAX_D || b > RM_CHUNK) { set_error("symm_mul: D = %d, b = %d above %d, %d", D, b, GRAM_MAX_D, RM_CHUNK); return MMVAE_E_UNSUPPORTED; }
-    return launch_symm_mul(C, ldc, D, Q, b, Y, reinterpret_cast<hipStream_t>(stream));
-}
-
-size_t mmvae_pca_project_workspace_bytes(int64_t n, int D, int k) {
-    (void)n; (void)D; (void)k;
-    return 0;
-}
-
-int mmvae_pca_project(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const double* mean,
-                      const double* V, int k, double* Z, void* stream) {
-    if (!data || !mean || !V || !Z) { set_error("pca_project: null pointer"); return MMVAE_E_BADARG; }
-    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("pca_project: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
-    if (n_total < 1) { set_error("pca_project: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
-    if (!rows && n > n_total) { set_error("pca_project: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
-    if (D < 1 || k < 1) { set_error("pca_project: D = %d, k = %d: each must be at least 1", D, k); return MMVAE_E_BADARG; }
-    if (ld < D) { set_error("pca_project: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
-    if (k > RM_CHUNK) { set_error("pca_project: k = %d above %d", k, RM_CHUNK); return MMVAE_E_UNSUPPORTED; }
-    return launch_pca_project(data, ld, n_total, rows, n, D, mean, V, k, Z, reinterpret_cast<hipStream_t>(stream));
-}
-
-// ---- data preparation (dataprep.hip): every argument is checked here, on the host, before any device work ----
-static int cpm_vsize(int vtype) { return vtype == 2 ? 8 : 4; }
-
-static int cpm_common_checked(const char* who, int vtype, int64_t n_total, int G, const int64_t* rows, int64_t n, int ng,
-                              double scaler, int mode, const void* out, int otype, const double* norms) {
-    if (!out || !norms) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
-    if (vtype < 0 || vtype > 2) { set_error("%s: value type %d outside [0, 2] (int32, float, double)", who, vtype); return MMVAE_E_BADARG; }
-    if (otype < 0 || otype > 1) { set_error("%s: output type %d outside [0, 1] (float, double)", who, otype); return MMVAE_E_BADARG; }
-    if (mode < 0 || mode > 1) { set_error("%s: mode %d outside [0, 1] (normalise, log1p)", who, mode); return MMVAE_E_BADARG; }
-    if (n < 1 || n >= ((int64_t)1 << 31)) { set_error("%s: n outside [1, 2^31)", who); return MMVAE_E_BADARG; }
-    if (n_total < 1) { set_error("%s: n_total = %lld below 1", who, (long long)n_total); return MMVAE_E_BADARG; }
-    if (!rows && n > n_total) { set_error("%s: n = %lld rows of a matrix of %lld without a row map", who, (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
-    if (G < 1 || ng < 1) { set_error("%s: G = %d, ng = %d: each must be at least 1", who, G, ng); return MMVAE_E_BADARG; }
-    if (!(scaler == scaler) || scaler - scaler != 0.0) { set_error("%s: scaler is not finite", who); return MMVAE_E_BADARG; }
-    if (G > CPM_MAX_G || ng > CPM_MAX_G) { set_error("%s: G = %d, ng = %d above %d", who, G, ng, CPM_MAX_G); return MMVAE_E_UNSUPPORTED; }
-    return 0;
-}
-
-static int cpm_dense_checked(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n,
-                             const int32_t* genes, int ng, double scaler, int mode, void* out, int otype, double* norms, int path,
-                             void* stream) {
-    if (!x) { set_error("cpm_dense: null pointer"); return MMVAE_E_BADARG; }
-    if (int rc = cpm_common_checked("cpm_dense", vtype, n_total, G, rows, n, ng, scaler, mode, out, otype, norms)) return rc;
-    if (ld < G) { set_error("cpm_dense: ld = %lld below G = %d", (long long)ld, G); return MMVAE_E_BADARG; }
-    if (!genes && ng != G) { set_error("cpm_dense: ng = %d without a gene list must be G = %d", ng, G); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(x) % cpm_vsize(vtype)) { set_error("cpm_dense: x not aligned to its value type"); return MMVAE_E_BADARG; }
-    if (path < -1 || path > 1) { set_error("cpm_dense: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
-    const bool can = cpm_wide(x, ld, cpm_vsize(vtype));
-    if (path == 1 && !can) {
-        set_error("cpm_dense: 16-byte loads need a 16-byte aligned base and a row pitch of whole 16 bytes (ld = %lld)", (long long)ld);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    return launch_cpm_dense(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, path < 0 ? can : path == 1,
-                            reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n, const int32_t* genes,
-                    int ng, double scaler, int mode, void* out, int otype, double* norms, void* stream) {
-    return cpm_dense_checked(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, -1, stream);
-}
-
-int mmvae_debug_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n,
-                          const int32_t* genes, int ng, double scaler, int mode, void* out, int otype, double* norms, int path,
-                          void* stream) {
-    return cpm_dense_checked(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, path, stream);
-}
-
-int mmvae_cpm_csr(const int64_t* indptr, const int32_t* indices, const void* data, int vtype, int64_t nnz, int64_t n_total, int G,
-                  const int64_t* rows, int64_t n, const int32_t* inv, int ng, double scaler, int mode, void* out, int otype,
-                  double* norms, void* stream) {
-    if (!indptr || !inv) { set_error("cpm_csr: null pointer"); return MMVAE_E_BADARG; }
-    if (nnz < 0) { set_error("cpm_csr: nnz = %lld below 0", (long long)nnz); return MMVAE_E_BADARG; }
-    if (nnz > 0 && (!indices || !data)) { set_error("cpm_csr: null indices / data with nnz = %lld", (long long)nnz); return MMVAE_E_BADARG; }
-    if (int rc = cpm_common_checked("cpm_csr", vtype, n_total, G, rows, n, ng, scaler, mode, out, otype, norms)) return rc;
-    if (ng > G) { set_error("cpm_csr: ng = %d above G = %d", ng, G); return MMVAE_E_BADARG; }
-    return launch_cpm_csr(indptr, indices, data, vtype, nnz, n_total, G, rows, n, inv, ng, scaler, mode, out, otype, norms,
-                          reinterpret_cast<hipStream_t>(stream));
-}
-
-static bool gs_shape_ok(int64_t n, int D) {
-    return (unsigned __int128)gs_nseg(n) * (unsigned __int128)cdiv64(D, GS_TILE) <= (unsigned __int128)GS_MAX_BLOCKS;
-}
-
-size_t mmvae_gene_stats_workspace_bytes(int64_t n, int D) {
-    if (n < 1 || n > ((int64_t)1 << 31) || D < 1 || !gs_shape_ok(n, D)) return 0;
-    const unsigned __int128 bytes = (unsigned __int128)8 * 3 * (unsigned __int128)gs_nseg(n) * (unsigned __int128)D;
-    return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes;
-}
-
-static int gene_stats_checked(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n,
-                              double eps, void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, int path,
-                              void* stream) {
-    if (!data || !ws || !n_above || !mean || !sd) { set_error("gene_stats: null pointer"); return MMVAE_E_BADARG; }
-    if (vtype < 1 || vtype > 2) { set_error("gene_stats: value type %d outside [1, 2] (float, double)", vtype); return MMVAE_E_BADARG; }
-    if (n < 1 || n > ((int64_t)1 << 31)) { set_error("gene_stats: n outside [1, 2^31]"); return MMVAE_E_BADARG; }
-    if (n_total < 1) { set_error("gene_stats: n_total = %lld below 1", (long long)n_total); return MMVAE_E_BADARG; }
-    if (!rows && n > n_total) { set_error("gene_stats: n = %lld rows of a matrix of %lld without a row map", (long long)n, (long long)n_total); return MMVAE_E_BADARG; }
-    if (D < 1) { set_error("gene_stats: D = %d below 1", D); return MMVAE_E_BADARG; }
-    if (ld < D) { set_error("gene_stats: ld = %lld below D = %d", (long long)ld, D); return MMVAE_E_BADARG; }
-    if (!(eps == eps)) { set_error("gene_stats: eps is NaN"); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("gene_stats: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
-    if (reinterpret_cast<uintptr_t>(data) % cpm_vsize(vtype)) { set_error("gene_stats: data not aligned to its value type"); return MMVAE_E_BADARG; }
-    if (path < -1 || path > 1) { set_error("gene_stats: path = %d outside [-1, 1]", path); return MMVAE_E_BADARG; }
-    const size_t need = mmvae_gene_stats_workspace_bytes(n, D);
-    if (need == 0) {
-        set_error("gene_stats: n = %lld, D = %d need a grid of more than %lld workgroups", (long long)n, D, (long long)GS_MAX_BLOCKS);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (ws_bytes < need) {
-        set_error("gene_stats: workspace of %zu bytes below the %zu needed", ws_bytes, need);
-        return MMVAE_E_WORKSPACE;
-    }
-    const bool can = gs_wide(data, ld, cpm_vsize(vtype));
-    if (path == 1 && !can) {
-        set_error("gene_stats: 16-byte loads need a 16-byte aligned base and a row pitch of whole 16 bytes (ld = %lld)", (long long)ld);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    return launch_gene_stats(data, vtype, ld, n_total, D, rows, n, eps, ws, n_above, mean, sd, path < 0 ? can : path == 1,
-                             reinterpret_cast<hipStream_t>(stream));
-}
-
-int mmvae_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
-                     void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, void* stream) {
-    return gene_stats_checked(data, vtype, ld, n_total, D, rows, n, eps, ws, ws_bytes, n_above, mean, sd, -1, stream);
-}
-
-int mmvae_debug_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
-                           void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, int path, void* stream) {
-    return gene_stats_checked(data, vtype, ld, n_total, D, rows, n, eps, ws, ws_bytes, n_above, mean, sd, path, stream);
-}
-
 int mmvae_debug_stage(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, int stage,
                       const float* params, const float* x, int64_t x_arm_stride, void* ws, size_t ws_bytes,
                       float* grads, mmvae_exec* ex, void* stream) {

@@ -1,0 +1,504 @@
+// C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
+// state-gene correlation, the Gaussian classifiers, PCA and data preparation.  Every argument is checked here, on the host,
+// before any device work; the training step's entry points, the plan and set_error live in api.hip.
+#include "common.hpp"
+
+using namespace mmvae;
+
+// ---- the checks the analysis entry points share.  who: the entry's name as its messages give it.  Each returns 0 or, after
+// ---- set_error, the refusal's code; an entry lists its checks in the order that decides which refusal a doubly-bad call gets.
+constexpr int64_t N_MAX = (int64_t)1 << 31;     // rows of one call at most
+
+static int check_count(const char* who, const char* name, int64_t v, int64_t lo, int64_t hi) {
+    if (v >= lo && v <= hi) return 0;
+    set_error("%s: %s outside [%lld, %lld] (got %lld)", who, name, (long long)lo, (long long)hi, (long long)v);
+    return MMVAE_E_BADARG;
+}
+
+// n selected rows of a matrix of n_total: without a row map they are its first n
+static int check_rowmap(const char* who, const int64_t* rows, int64_t n, int64_t n_total) {
+    if (n_total < 1) { set_error("%s: n_total = %lld below 1", who, (long long)n_total); return MMVAE_E_BADARG; }
+    if (rows || n <= n_total) return 0;
+    set_error("%s: n = %lld rows of a matrix of %lld without a row map", who, (long long)n, (long long)n_total);
+    return MMVAE_E_BADARG;
+}
+
+static int check_pitch(const char* who, const char* ldname, int64_t ld, const char* dname, int64_t d) {
+    if (ld >= d) return 0;
+    set_error("%s: %s = %lld below %s = %lld", who, ldname, (long long)ld, dname, (long long)d);
+    return MMVAE_E_BADARG;
+}
+
+static int check_aligned(const char* who, const char* what, const void* p, size_t bytes) {
+    if (reinterpret_cast<uintptr_t>(p) % bytes == 0) return 0;
+    set_error("%s: %s %p not %zu-byte aligned", who, what, p, bytes);
+    return MMVAE_E_BADARG;
+}
+
+static int check_ws(const char* who, size_t ws_bytes, size_t need) {
+    if (ws_bytes >= need) return 0;
+    set_error("%s: workspace of %zu bytes below the %zu needed", who, ws_bytes, need);
+    return MMVAE_E_WORKSPACE;
+}
+
+// path: -1 the launcher's rule (the 16-byte loads where the base and the row pitch allow them), 0 the narrow loads, 1 the
+// 16-byte loads
+static int pick_wide(const char* who, int path, const void* base, int64_t ld, int elem_bytes, bool* wide) {
+    if (int rc = check_count(who, "path", path, -1, 1)) return rc;
+    const bool can = wide16(base, ld, elem_bytes);
+    if (path == 1 && !can) {
+        set_error("%s: path = 1 (16-byte loads) needs a 16-byte aligned base and a row pitch of whole 16 bytes (base %p, ld = %lld)",
+                  who, base, (long long)ld);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    *wide = path < 0 ? can : path == 1;
+    return 0;
+}
+
+extern "C" {
+
+int mmvae_classify(const float* c_probs, int64_t n_cells, int C, int32_t* labels, void* stream) {
+    if (!c_probs || !labels || n_cells <= 0 || C <= 0) { set_error("classify: bad argument"); return MMVAE_E_BADARG; }
+    return launch_classify(c_probs, n_cells, C, labels, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_confmat_accumulate(const int32_t* labels, int A, int64_t n, int C, int64_t* counts, void* stream) {
+    if (!labels || !counts || A < 1 || A > MMVAE_MAX_ARMS || n <= 0 || C <= 0) {
+        set_error("confmat_accumulate: bad argument");
+        return MMVAE_E_BADARG;
+    }
+    return launch_confmat(labels, A, n, C, counts, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_consensus(const int64_t* counts, int npairs, int C, double* cm_norm, double* consensus, void* stream) {
+    if (!counts || !consensus || npairs < 1 || C < 1) { set_error("consensus: bad argument"); return MMVAE_E_BADARG; }
+    if (C > 128) { set_error("consensus: C > 128 unsupported"); return MMVAE_E_UNSUPPORTED; }
+    return launch_consensus(counts, npairs, C, cm_norm, consensus, reinterpret_cast<hipStream_t>(stream));
+}
+
+// every argument of mmvae_pair_stats is checked here, on the host, before any device work
+static int pair_stats_args(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
+                           int n_pairs, const int64_t* counts, const int64_t* dist_acc) {
+    if (!labels || !probs || !pairs || !counts || !dist_acc) { set_error("pair_stats: null pointer"); return MMVAE_E_BADARG; }
+    if (C < 1 || C > 128) { set_error("pair_stats: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (n < 0 || n_pairs < 0) { set_error("pair_stats: negative n or n_pairs"); return MMVAE_E_BADARG; }
+    if (n > ((int64_t)1 << 31)) { set_error("pair_stats: more than 2^31 cells in one call"); return MMVAE_E_BADARG; }
+    if (n_arms_total < 1 || n_arms_total > 2 * MMVAE_MAX_ARMS) {
+        set_error("pair_stats: n_arms_total = %d outside [1, %d]", n_arms_total, 2 * MMVAE_MAX_ARMS);
+        return MMVAE_E_BADARG;
+    }
+    for (int64_t k = 0; k < 4 * (int64_t)n_pairs; ++k)
+        if (pairs[k] < 0 || pairs[k] >= n_arms_total) {
+            set_error("pair_stats: pairs[%lld][%d] = %d outside [0, %d)", (long long)(k / 4), (int)(k % 4), pairs[k], n_arms_total);
+            return MMVAE_E_BADARG;
+        }
+    return 0;
+}
+
+int mmvae_pair_stats(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
+                     int n_pairs, int64_t* counts, int64_t* dist_acc, void* stream) {
+    if (int rc = pair_stats_args(labels, probs, n_arms_total, n, C, pairs, n_pairs, counts, dist_acc)) return rc;
+    if (n == 0 || n_pairs == 0) return 0;
+    return launch_pair_stats(labels, probs, n, C, pairs, n_pairs, counts, dist_acc, -1, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_pair_stats(const int32_t* labels, const float* probs, int n_arms_total, int64_t n, int C, const int32_t* pairs,
+                           int n_pairs, int64_t* counts, int64_t* dist_acc, int path, void* stream) {
+    if (int rc = pair_stats_args(labels, probs, n_arms_total, n, C, pairs, n_pairs, counts, dist_acc)) return rc;
+    if (path < -1 || path > 1) { set_error("debug_pair_stats: path %d outside {-1, 0, 1}", path); return MMVAE_E_BADARG; }
+    if (n == 0 || n_pairs == 0) return 0;
+    return launch_pair_stats(labels, probs, n, C, pairs, n_pairs, counts, dist_acc, path, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_pair_stats_finish(const int64_t* counts, const int64_t* dist_acc, int n_pairs, int C, double* cm_norm, double* emp,
+                            double* dist_norm, double* diag_mean, double* diag_min, void* stream) {
+    if (!counts || !dist_acc || !cm_norm || !emp || !dist_norm || !diag_mean || !diag_min) {
+        set_error("pair_stats_finish: null pointer");
+        return MMVAE_E_BADARG;
+    }
+    if (C < 1 || C > 128) { set_error("pair_stats_finish: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (n_pairs < 0) { set_error("pair_stats_finish: negative n_pairs"); return MMVAE_E_BADARG; }
+    if (n_pairs == 0) return 0;
+    return launch_pair_finish(counts, dist_acc, n_pairs, C, cm_norm, emp, dist_norm, diag_mean, diag_min,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+
+// every argument of mmvae_mutinfo_counts is checked here, on the host, before any device work
+static int mutinfo_counts_args(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt,
+                               int F, const int64_t* counts, const int64_t* t_sum, const int64_t* p_sum) {
+    if (!labels || !targets || !counts || !t_sum || !p_sum) { set_error("mutinfo_counts: null pointer"); return MMVAE_E_BADARG; }
+    if (A < 1 || A > MMVAE_MAX_ARMS) { set_error("mutinfo_counts: A = %d outside [1, %d]", A, MMVAE_MAX_ARMS); return MMVAE_E_BADARG; }
+    if (C < 1 || C > 128) { set_error("mutinfo_counts: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (F < 1 || F > 4096) { set_error("mutinfo_counts: F = %d outside [1, 4096]", F); return MMVAE_E_BADARG; }
+    if (n < 0 || n > ((int64_t)1 << 31)) { set_error("mutinfo_counts: n outside [0, 2^31]"); return MMVAE_E_BADARG; }
+    if (ldt < F) { set_error("mutinfo_counts: ldt = %lld below F = %d", (long long)ldt, F); return MMVAE_E_BADARG; }
+    if (target_bytes != 1 && target_bytes != 4) {
+        set_error("mutinfo_counts: target_bytes = %d is neither 1 (uint8) nor 4 (int32)", target_bytes);
+        return MMVAE_E_BADARG;
+    }
+    return 0;
+}
+
+int mmvae_mutinfo_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt, int F,
+                         int64_t* counts, int64_t* t_sum, int64_t* p_sum, void* stream) {
+    if (int rc = mutinfo_counts_args(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum)) return rc;
+    if (n == 0) return 0;
+    return launch_mi_counts(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum, -1,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_mutinfo_counts(const int32_t* labels, int A, int64_t n, int C, const void* targets, int target_bytes, int64_t ldt,
+                               int F, int64_t* counts, int64_t* t_sum, int64_t* p_sum, int path, void* stream) {
+    if (int rc = mutinfo_counts_args(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum)) return rc;
+    if (path < -1 || path > 1) { set_error("debug_mutinfo_counts: path %d outside {-1, 0, 1}", path); return MMVAE_E_BADARG; }
+    if (n == 0) return 0;
+    return launch_mi_counts(labels, A, n, C, targets, target_bytes, ldt, F, counts, t_sum, p_sum, path,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mmvae_ami_binary_workspace_bytes(int64_t N) {
+    return N < 1 || N > ((int64_t)1 << 31) ? 0 : 2 * (size_t)(N + 1) * sizeof(double);
+}
+
+int mmvae_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_sum, int A, int F, int C, int64_t N, void* ws,
+                     size_t ws_bytes, double* ami, void* stream) {
+    if (!n11 || !t_sum || !p_sum || !ami) { set_error("ami_binary: null pointer"); return MMVAE_E_BADARG; }
+    if (A < 0 || A > MMVAE_MAX_ARMS) { set_error("ami_binary: A = %d outside [0, %d]", A, MMVAE_MAX_ARMS); return MMVAE_E_BADARG; }
+    if (C < 1 || C > 128) { set_error("ami_binary: C = %d outside [1, 128]", C); return MMVAE_E_BADARG; }
+    if (F < 1 || F > 4096) { set_error("ami_binary: F = %d outside [1, 4096]", F); return MMVAE_E_BADARG; }
+    if (N < 1 || N > ((int64_t)1 << 31)) { set_error("ami_binary: N outside [1, 2^31]"); return MMVAE_E_BADARG; }
+    if (ws) {
+        if (reinterpret_cast<uintptr_t>(ws) % sizeof(double)) { set_error("ami_binary: workspace not 8-byte aligned"); return MMVAE_E_BADARG; }
+        if (ws_bytes < mmvae_ami_binary_workspace_bytes(N)) {
+            set_error("ami_binary: workspace of %zu bytes below the %zu needed", ws_bytes, mmvae_ami_binary_workspace_bytes(N));
+            return MMVAE_E_WORKSPACE;
+        }
+    }
+    if (A == 0) return 0;
+    return launch_ami_binary(n11, t_sum, p_sum, A, F, C, N, static_cast<double*>(ws), ami, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- silhouette (silhouette.hip) ----
+size_t mmvae_silhouette_workspace_bytes(int64_t n, int K) {
+    if (n < 3 || n > N_MAX || K < 2 || K > n - 1) return 0;
+    return seg_ws_bytes(nseg_max(n, K, SIL_SEG_COLS), n, K);
+}
+
+int mmvae_silhouette(const float* x_sorted, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
+                     size_t ws_bytes, double* s, void* stream) {
+    const char* who = "silhouette";
+    if (!x_sorted || !offsets || !ws || !s) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 3, N_MAX)) return rc;
+    if (int rc = check_count(who, "K", K, 2, n - 1)) return rc;
+    if (int rc = check_count(who, "d", d, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "d", d)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (d > SIL_MAX_D) { set_error("%s: d = %d above %d", who, d, SIL_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    const int64_t nseg = nseg_max(n, K, SIL_SEG_COLS);
+    const size_t need = mmvae_silhouette_workspace_bytes(n, K);
+    if (nseg > SIL_MAX_SEGMENTS || need == 0) {
+        set_error("%s: K + n / %d = %lld segments above %lld", who, SIL_SEG_COLS, (long long)nseg, (long long)SIL_MAX_SEGMENTS);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    return launch_silhouette(x_sorted, ld, n, d, offsets, K, perm, ws, s, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- state-gene correlation (statecorr.hip) ----
+// the most segments and the most workgroups of one grid that mmvae_state_corr launches; false where it refuses the shape
+static bool sc_shape_ok(int64_t n, int D, int S, int G) {
+    if (S > SC_MAX_S) return false;
+    const unsigned __int128 tiles = (unsigned __int128)cdiv64(D, SC_TILE);
+    return (unsigned __int128)nseg_max(n, G, SC_SEG_ROWS) * tiles <= (unsigned __int128)SC_MAX_BLOCKS &&
+           (unsigned __int128)G * (unsigned __int128)cdiv64(D, 256) <= (unsigned __int128)SC_MAX_BLOCKS;
+}
+
+size_t mmvae_state_corr_workspace_bytes(int64_t n, int D, int S, int G) {
+    if (n < 1 || n > N_MAX || D < 1 || S < 1 || G < 1 || !sc_shape_ok(n, D, S, G)) return 0;
+    return seg_ws_bytes(nseg_max(n, G, SC_SEG_ROWS), (5 + 5 * (int64_t)S) * D, G);
+}
+
+static int state_corr_checked(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state,
+                              int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
+                              int64_t* count, int path, void* stream) {
+    const char* who = "state_corr";
+    if (!data || !state || !ws || !r || !count) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, N_MAX)) return rc;
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "S", S, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "D", D)) return rc;
+    if (int rc = check_pitch(who, "lds", lds, "S", S)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (S > SC_MAX_S) { set_error("%s: S = %d above %d", who, S, SC_MAX_S); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_state_corr_workspace_bytes(n, D, S, G);
+    if (need == 0) {     // (the shape rule of sc_shape_ok, or a size no size_t holds)
+        set_error("%s: n = %lld, D = %d, G = %d need a grid of more than %lld workgroups", who, (long long)n, D, G, (long long)SC_MAX_BLOCKS);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    bool wide;
+    if (int rc = pick_wide(who, path, data, ld, sizeof(float), &wide)) return rc;
+    return launch_state_corr(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, r, count, wide,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
+                     int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r, int64_t* count,
+                     void* stream) {
+    return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, -1, stream);
+}
+
+int mmvae_debug_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state,
+                           int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
+                           int64_t* count, int path, void* stream) {
+    return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, path, stream);
+}
+
+// ---- Gaussian classifiers (gaussclf.hip) ----
+size_t mmvae_group_moments_workspace_bytes(int64_t n, int d, int G) {
+    if (n < 1 || n > N_MAX || d < 1 || d > GC_MAX_D || G < 1 || G > GC_MAX_G) return 0;
+    return seg_ws_bytes(nseg_max(n, G, GC_SEG_ROWS), d * (d + 3) / 2, G);
+}
+
+// dclass: -1 the launcher's rule (the first instance of GC_DC that holds d), 0 .. GC_N_DC - 1 that instance
+static int group_moments_checked(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot,
+                                 void* ws, size_t ws_bytes, double* s, double* M, int dclass, void* stream) {
+    const char* who = "group_moments";
+    if (!x || !offsets || !pivot || !ws || !s || !M) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, N_MAX)) return rc;
+    if (int rc = check_count(who, "d", d, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "d", d)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (int rc = check_count(who, "dclass", dclass, -1, GC_N_DC - 1)) return rc;
+    if (d > GC_MAX_D) { set_error("%s: d = %d above %d", who, d, GC_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    if (G > GC_MAX_G) { set_error("%s: G = %d above %d", who, G, GC_MAX_G); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_group_moments_workspace_bytes(n, d, G);
+    if (need == 0) { set_error("%s: n = %lld, d = %d, G = %d need a workspace size_t cannot hold", who, (long long)n, d, G); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    if (dclass >= 0 && d > GC_DC[dclass]) {
+        set_error("%s: the instance for d <= %d cannot run d = %d", who, GC_DC[dclass], d);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_group_moments(x, ld, n, d, offsets, G, pivot, ws, s, M, dclass < 0 ? gc_dclass(d) : dclass,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot, void* ws,
+                        size_t ws_bytes, double* s, double* M, void* stream) {
+    return group_moments_checked(x, ld, n, d, offsets, G, pivot, ws, ws_bytes, s, M, -1, stream);
+}
+
+int mmvae_debug_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot,
+                              void* ws, size_t ws_bytes, double* s, double* M, int dclass, void* stream) {
+    return group_moments_checked(x, ld, n, d, offsets, G, pivot, ws, ws_bytes, s, M, dclass, stream);
+}
+
+// the kernel keeps nothing between launches
+size_t mmvae_gauss_scores_workspace_bytes(int64_t n, int d, int F, int K) {
+    (void)n; (void)d; (void)F; (void)K;
+    return 0;
+}
+
+int mmvae_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int32_t* model, int F, int K, const double* mu,
+                       const double* W, const double* c0, const int64_t* perm, void* ws, size_t ws_bytes, int32_t* label,
+                       double* best, double* second, double* scores, void* stream) {
+    (void)ws_bytes;
+    const char* who = "gauss_scores";
+    if (!x || !model || !mu || !W || !c0 || !label || !best || !second) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, N_MAX)) return rc;
+    if (int rc = check_count(who, "d", d, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "F", F, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "K", K, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "d", d)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;     // (a null workspace is aligned)
+    if (d > GC_MAX_D || K > GC_MAX_K || F > GC_MAX_F) {
+        set_error("%s: d = %d, K = %d, F = %d above %d, %d, %d", who, d, K, F, GC_MAX_D, GC_MAX_K, GC_MAX_F);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_gauss_scores(x, ld, n, d, model, F, K, mu, W, c0, perm, label, best, second, scores,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- principal components (pca.hip) ----
+int mmvae_gram_segments(int64_t n, int D, int64_t* seg_rows) {
+    if (n < 2 || n > N_MAX || D < 1 || D > GRAM_MAX_D) return 0;
+    return gram_segments(n, D, seg_rows);
+}
+
+size_t mmvae_gram_workspace_bytes(int64_t n, int D) {
+    const int nseg = mmvae_gram_segments(n, D, nullptr);
+    if (nseg == 0) return 0;
+    return sizeof(double) * ((size_t)(nseg - 1) * (size_t)D * (size_t)D + (size_t)nseg * (size_t)D);
+}
+
+static int gram_checked(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot,
+                        void* ws, size_t ws_bytes, double* s, double* G, int cov, int path, void* stream) {
+    const char* who = "gram";
+    if (!data || !pivot || !ws || !s || !G) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 2, N_MAX)) return rc;
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "D", D)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (int rc = check_count(who, "cov", cov, 0, 1)) return rc;
+    if (int rc = check_count(who, "path", path, -1, 1)) return rc;      // (before the limits below: a bad argument first)
+    if (D > GRAM_MAX_D) { set_error("%s: D = %d above %d", who, D, GRAM_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_ws(who, ws_bytes, mmvae_gram_workspace_bytes(n, D))) return rc;
+    bool wide;
+    if (int rc = pick_wide(who, path, data, ld, sizeof(float), &wide)) return rc;
+    return launch_gram(data, ld, n_total, rows, n, D, pivot, ws, s, G, cov, wide, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot, void* ws,
+               size_t ws_bytes, double* s, double* G, int cov, void* stream) {
+    return gram_checked(data, ld, n_total, rows, n, D, pivot, ws, ws_bytes, s, G, cov, -1, stream);
+}
+
+int mmvae_debug_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot,
+                     void* ws, size_t ws_bytes, double* s, double* G, int cov, int path, void* stream) {
+    return gram_checked(data, ld, n_total, rows, n, D, pivot, ws, ws_bytes, s, G, cov, path, stream);
+}
+
+// the kernel keeps nothing between launches
+size_t mmvae_symm_mul_workspace_bytes(int D, int b) {
+    (void)D; (void)b;
+    return 0;
+}
+
+int mmvae_symm_mul(const double* C, int64_t ldc, int D, const double* Q, int b, double* Y, void* stream) {
+    const char* who = "symm_mul";
+    if (!C || !Q || !Y) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "b", b, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldc", ldc, "D", D)) return rc;
+    if (D > GRAM_MAX_D || b > RM_CHUNK) { set_error("%s: D = %d, b = %d above %d, %d", who, D, b, GRAM_MAX_D, RM_CHUNK); return MMVAE_E_UNSUPPORTED; }
+    return launch_symm_mul(C, ldc, D, Q, b, Y, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mmvae_pca_project_workspace_bytes(int64_t n, int D, int k) {
+    (void)n; (void)D; (void)k;
+    return 0;
+}
+
+int mmvae_pca_project(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const double* mean,
+                      const double* V, int k, double* Z, void* stream) {
+    const char* who = "pca_project";
+    if (!data || !mean || !V || !Z) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, N_MAX)) return rc;
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "k", k, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "D", D)) return rc;
+    if (k > RM_CHUNK) { set_error("%s: k = %d above %d", who, k, RM_CHUNK); return MMVAE_E_UNSUPPORTED; }
+    return launch_pca_project(data, ld, n_total, rows, n, D, mean, V, k, Z, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- data preparation (dataprep.hip) ----
+static int cpm_vsize(int vtype) { return vtype == 2 ? 8 : 4; }
+
+// what mmvae_cpm_dense and mmvae_cpm_csr check alike.  vtype 0 int32, 1 float, 2 double; otype 0 float, 1 double; mode 0
+// normalise, 1 log1p
+static int cpm_common_checked(const char* who, int vtype, int64_t n_total, int G, const int64_t* rows, int64_t n, int ng,
+                              double scaler, int mode, const void* out, int otype, const double* norms) {
+    if (!out || !norms) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "value type", vtype, 0, 2)) return rc;
+    if (int rc = check_count(who, "output type", otype, 0, 1)) return rc;
+    if (int rc = check_count(who, "mode", mode, 0, 1)) return rc;
+    if (int rc = check_count(who, "n", n, 1, N_MAX - 1)) return rc;
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "ng", ng, 1, INT32_MAX)) return rc;
+    if (!(scaler == scaler) || scaler - scaler != 0.0) { set_error("%s: scaler = %g is not finite", who, scaler); return MMVAE_E_BADARG; }
+    if (G > CPM_MAX_G || ng > CPM_MAX_G) { set_error("%s: G = %d, ng = %d above %d", who, G, ng, CPM_MAX_G); return MMVAE_E_UNSUPPORTED; }
+    return 0;
+}
+
+static int cpm_dense_checked(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n,
+                             const int32_t* genes, int ng, double scaler, int mode, void* out, int otype, double* norms, int path,
+                             void* stream) {
+    const char* who = "cpm_dense";
+    if (!x) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = cpm_common_checked(who, vtype, n_total, G, rows, n, ng, scaler, mode, out, otype, norms)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "G", G)) return rc;
+    if (!genes && ng != G) { set_error("%s: ng = %d without a gene list must be G = %d", who, ng, G); return MMVAE_E_BADARG; }
+    if (int rc = check_aligned(who, "x", x, cpm_vsize(vtype))) return rc;
+    bool wide;
+    if (int rc = pick_wide(who, path, x, ld, cpm_vsize(vtype), &wide)) return rc;
+    return launch_cpm_dense(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, wide,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n, const int32_t* genes,
+                    int ng, double scaler, int mode, void* out, int otype, double* norms, void* stream) {
+    return cpm_dense_checked(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, -1, stream);
+}
+
+int mmvae_debug_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n,
+                          const int32_t* genes, int ng, double scaler, int mode, void* out, int otype, double* norms, int path,
+                          void* stream) {
+    return cpm_dense_checked(x, vtype, ld, n_total, G, rows, n, genes, ng, scaler, mode, out, otype, norms, path, stream);
+}
+
+int mmvae_cpm_csr(const int64_t* indptr, const int32_t* indices, const void* data, int vtype, int64_t nnz, int64_t n_total, int G,
+                  const int64_t* rows, int64_t n, const int32_t* inv, int ng, double scaler, int mode, void* out, int otype,
+                  double* norms, void* stream) {
+    const char* who = "cpm_csr";
+    if (!indptr || !inv) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "nnz", nnz, 0, INT64_MAX)) return rc;
+    if (nnz > 0 && (!indices || !data)) { set_error("%s: null indices / data with nnz = %lld", who, (long long)nnz); return MMVAE_E_BADARG; }
+    if (int rc = cpm_common_checked(who, vtype, n_total, G, rows, n, ng, scaler, mode, out, otype, norms)) return rc;
+    if (int rc = check_count(who, "ng", ng, 1, G)) return rc;
+    return launch_cpm_csr(indptr, indices, data, vtype, nnz, n_total, G, rows, n, inv, ng, scaler, mode, out, otype, norms,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+static bool gs_shape_ok(int64_t n, int D) {
+    return (unsigned __int128)gs_nseg(n) * (unsigned __int128)cdiv64(D, GS_TILE) <= (unsigned __int128)GS_MAX_BLOCKS;
+}
+
+size_t mmvae_gene_stats_workspace_bytes(int64_t n, int D) {
+    if (n < 1 || n > N_MAX || D < 1 || !gs_shape_ok(n, D)) return 0;
+    return bytes_or_0((unsigned __int128)8 * 3 * (unsigned __int128)gs_nseg(n) * (unsigned __int128)D);
+}
+
+// vtype 1 float, 2 double
+static int gene_stats_checked(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n,
+                              double eps, void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, int path,
+                              void* stream) {
+    const char* who = "gene_stats";
+    if (!data || !ws || !n_above || !mean || !sd) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "value type", vtype, 1, 2)) return rc;
+    if (int rc = check_count(who, "n", n, 1, N_MAX)) return rc;
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "D", D)) return rc;
+    if (!(eps == eps)) { set_error("%s: eps is NaN", who); return MMVAE_E_BADARG; }
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (int rc = check_aligned(who, "data", data, cpm_vsize(vtype))) return rc;
+    if (int rc = check_count(who, "path", path, -1, 1)) return rc;      // (before the limits below: a bad argument first)
+    const size_t need = mmvae_gene_stats_workspace_bytes(n, D);
+    if (need == 0) {
+        set_error("%s: n = %lld, D = %d need a grid of more than %lld workgroups", who, (long long)n, D, (long long)GS_MAX_BLOCKS);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    bool wide;
+    if (int rc = pick_wide(who, path, data, ld, cpm_vsize(vtype), &wide)) return rc;
+    return launch_gene_stats(data, vtype, ld, n_total, D, rows, n, eps, ws, n_above, mean, sd, wide,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
+                     void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, void* stream) {
+    return gene_stats_checked(data, vtype, ld, n_total, D, rows, n, eps, ws, ws_bytes, n_above, mean, sd, -1, stream);
+}
+
+int mmvae_debug_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
+                           void* ws, size_t ws_bytes, int64_t* n_above, double* mean, double* sd, int path, void* stream) {
+    return gene_stats_checked(data, vtype, ld, n_total, D, rows, n, eps, ws, ws_bytes, n_above, mean, sd, path, stream);
+}
+
+}  // extern "C"

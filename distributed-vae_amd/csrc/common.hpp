@@ -22,6 +22,18 @@ __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int rup(int a, int b) { return cdiv(a, b) * b; }
 __host__ __device__ inline int64_t imin64(int64_t a, int64_t b) { return a < b ? a : b; }
+__host__ __device__ inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// the row of a matrix of n_total rows that position pos of a selection reads: rows[pos] (rows null: pos itself), clamped, so
+// that a row map that is none reads a wrong row, never outside the matrix
+__host__ __device__ inline int64_t src_row(const int64_t* rows, int64_t pos, int64_t n_total) {
+    return clamp64(rows ? rows[pos] : pos, 0, n_total - 1);
+}
+// the rows [c0, c1) of segment seg of a segment table (launch_segments, below): inside [0, n] and at most seg_len of them,
+// whatever the table holds
+__host__ __device__ inline void seg_range(const int64_t* seg_begin, int seg, int64_t n, int64_t seg_len, int64_t& c0, int64_t& c1) {
+    c0 = clamp64(seg_begin[seg], 0, n);
+    c1 = imin64(clamp64(seg_begin[seg + 1], c0, n), c0 + seg_len);
+}
 
 // ------------------------------------------------------------------------------------------
 // Workspace layout (offsets in floats).  Authoritative copy; Python asks through
@@ -974,6 +986,31 @@ int launch_mi_counts(const int32_t* labels, int A, int64_t n, int C, const void*
                      int64_t* counts, int64_t* t_sum, int64_t* p_sum, int path, hipStream_t s);
 int launch_ami_binary(const int64_t* n11, const int64_t* t_sum, const int64_t* p_sum, int A, int F, int C, int64_t N, double* ws,
                       double* ami, hipStream_t s);
+// ---- what the analysis routines below share ----
+// 16-byte loads of a row's elements: the base is 16-byte aligned and the row pitch a whole number of 16 bytes
+inline bool wide16(const void* p, int64_t ld, int elem_bytes) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (ld * elem_bytes) % 16 == 0; }
+// a byte count as a size_t; 0 where it is beyond SIZE_MAX / 2 (a workspace nobody can have)
+inline size_t bytes_or_0(unsigned __int128 bytes) { return bytes > (unsigned __int128)(SIZE_MAX / 2) ? 0 : (size_t)bytes; }
+// The segment scheme of silhouette, state_corr and group_moments (segments.hip).  n rows arrive ordered by group, offsets
+// [G + 1] cutting them; group g with f_g > 0 rows is cut into ceil(f_g / seg_len) consecutive segments that never cross a group
+// boundary, at most nseg_max(n, G, seg_len) in all.  One launch writes the table: gseg[g] the group's first segment,
+// gseg[G] their number, seg_begin[s] the first row of segment s, seg_begin[gseg[G]] = offsets[G] (launch_segments; offsets
+// null: one group, 0 and n).  A partial kernel then owns one segment (seg_range) and a finish kernel adds each group's
+// segments in order.  The workspace: part double [nseg_max][doubles_per_segment], seg_begin int64 [nseg_max + 1], gseg int32
+// [G + 1] rounded up to whole 8 bytes.
+inline int64_t nseg_max(int64_t n, int G, int seg_len) { return (int64_t)G + n / seg_len; }
+inline size_t seg_ws_bytes(int64_t nseg, int64_t doubles_per_segment, int G) {
+    const unsigned __int128 s = (unsigned __int128)nseg;
+    return bytes_or_0(8 * (s * (unsigned __int128)doubles_per_segment + s + 1) + 4 * (((unsigned __int128)G + 2) / 2 * 2));
+}
+struct SegWs { double* part; int64_t* seg_begin; int* gseg; };
+inline SegWs seg_ws_carve(void* ws, int64_t nseg, int64_t doubles_per_segment) {
+    double* part = static_cast<double*>(ws);
+    int64_t* seg_begin = reinterpret_cast<int64_t*>(part + nseg * doubles_per_segment);
+    return SegWs{part, seg_begin, reinterpret_cast<int*>(seg_begin + nseg + 1)};
+}
+int launch_segments(const int64_t* offsets, int G, int64_t n, int seg_len, int64_t nseg_max, int* gseg, int64_t* seg_begin,
+                    hipStream_t st);
 // silhouette samples (silhouette.hip)
 constexpr int SIL_SEG_COLS = 512;      // columns per segment at most: a longer cluster is cut into pieces of this many
 constexpr int SIL_ROW_TILE = 256;      // rows per workgroup of k_sil_partial, one thread each
@@ -982,7 +1019,6 @@ constexpr int SIL_MAX_D = 128;
 constexpr int SIL_N_DV = 10;
 constexpr int SIL_DV[SIL_N_DV] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};   // float4 pieces per point k_sil_partial is built for
 constexpr int64_t SIL_MAX_SEGMENTS = (int64_t)1 << 23;                 // a grid's x extent times 256 threads stays below 2^32
-int64_t sil_nseg_max(int64_t n, int K);
 int sil_dv(int d);
 int launch_silhouette(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
                       double* s, hipStream_t st);
@@ -991,8 +1027,6 @@ constexpr int SC_SEG_ROWS = 256;       // rows per segment at most: a longer gro
 constexpr int SC_TILE = 256;           // genes per workgroup of k_sc_partial: one wave, four consecutive genes a lane
 constexpr int SC_MAX_S = 32;           // the model's limit on state_dim; more passes of 4, 2 or 1 states, not more registers
 constexpr int64_t SC_MAX_BLOCKS = ((int64_t)1 << 31) - 1;              // segments x gene tiles, and groups x gene tiles, one grid each
-int64_t sc_nseg_max(int64_t n, int G);
-bool sc_wide(const float* data, int64_t ld);
 int launch_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
                       int64_t n, int S, const int64_t* offsets, int G, void* ws, double* r, int64_t* count, bool wide, hipStream_t st);
 // Gaussian classifiers: group moments and class scores (gaussclf.hip)
@@ -1007,7 +1041,6 @@ constexpr int GC_MAX_D = 128;
 constexpr int GC_MAX_K = 4096;
 constexpr int GC_MAX_F = 64;
 constexpr int GC_MAX_G = 1 << 20;      // groups of one mmvae_group_moments call (GC_MAX_K x GC_MAX_F fits four times)
-int64_t gc_nseg_max(int64_t n, int G);
 int gc_dclass(int d);
 int launch_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot, void* ws,
                          double* s, double* M, int dclass, hipStream_t st);
@@ -1025,7 +1058,6 @@ constexpr int GRAM_MAX_D = 32768;
 constexpr int RM_ROWS = 16;            // rows per workgroup of k_rows_mul: four a wave
 constexpr int RM_CHUNK = 64;           // coordinates staged at a time, and the most columns of the block (b, k <= 64)
 int gram_segments(int64_t n, int D, int64_t* seg_rows);
-bool gram_wide(const float* data, int64_t ld);
 int launch_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot, void* ws,
                 double* s, double* G, int cov, bool wide, hipStream_t st);
 int launch_symm_mul(const double* C, int64_t ldc, int D, const double* Q, int b, double* Y, hipStream_t st);
@@ -1038,14 +1070,12 @@ constexpr int CPM_MAX_G = 1 << 20;     // genes at most: an int32 row sums to be
 constexpr int GS_SEG_ROWS = 256;       // rows per segment of k_gs_partial
 constexpr int GS_TILE = 256;           // genes per workgroup of k_gs_partial: one wave, four consecutive genes a lane
 constexpr int64_t GS_MAX_BLOCKS = ((int64_t)1 << 31) - 1;              // segments x gene tiles of one grid
-bool cpm_wide(const void* x, int64_t ld, int vsize);
 int launch_cpm_dense(const void* x, int vtype, int64_t ld, int64_t n_total, int G, const int64_t* rows, int64_t n, const int* genes,
                      int ng, double scaler, int log_mode, void* out, int otype, double* norms, bool wide, hipStream_t st);
 int launch_cpm_csr(const int64_t* indptr, const int* indices, const void* data, int vtype, int64_t nnz, int64_t n_total, int G,
                    const int64_t* rows, int64_t n, const int* inv, int ng, double scaler, int log_mode, void* out, int otype,
                    double* norms, hipStream_t st);
 int64_t gs_nseg(int64_t n);
-bool gs_wide(const void* data, int64_t ld, int vsize);
 int launch_gene_stats(const void* data, int vtype, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps,
                       void* ws, int64_t* n_above, double* mean, double* sd, bool wide, hipStream_t st);
 int launch_dump_noise(const mmvae_dims& d, const mmvae_hyper& h, const mmvae_noise* nz, uint8_t* x_mask,

@@ -15,8 +15,6 @@
 
 namespace mmvae {
 
-__device__ inline int64_t dp_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // the accumulator of a norm: integer counts add exactly in int64 (G <= 2^20 values below 2^31: below 2^51), floats in fp64
 template <typename T> struct CpmAcc { typedef double type; };
 template <> struct CpmAcc<int> { typedef int64_t type; };
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(CPM_THREADS) void k_cpm_dense(const T* __restrict__
     __shared__ A red[CPM_THREADS];
     const int tid = threadIdx.x;
     const int64_t r = blockIdx.x;
-    const int64_t row = dp_clamp(rows ? rows[r] : r, 0, n_total - 1);
+    const int64_t row = src_row(rows, r, n_total);
     const T* xr = x + row * ld;
     const int pieces = (G + V - 1) / V;
     A acc = 0;
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(CPM_THREADS) void k_cpm_dense(const T* __restrict__
     const double norm = raw == 0.0 ? 1.0 : raw;
     O* orow = out + r * (int64_t)ng;
     for (int j = tid; j < ng; j += CPM_THREADS) {
-        const int g = genes ? (int)dp_clamp(genes[j], 0, G - 1) : j;       // (genes null: ng == G, the launcher's check)
+        const int g = genes ? (int)clamp64(genes[j], 0, G - 1) : j;       // (genes null: ng == G, the launcher's check)
         orow[j] = cpm_value<O>((double)xr[g], norm, scaler, log_mode);
     }
 }
@@ -124,8 +122,8 @@ __global__ __launch_bounds__(CPM_THREADS) void k_cpm_csr(const int64_t* __restri
     __shared__ A red[CPM_THREADS];
     const int tid = threadIdx.x;
     const int64_t r = blockIdx.x;
-    const int64_t row = dp_clamp(rows ? rows[r] : r, 0, n_total - 1);
-    const int64_t e0 = dp_clamp(indptr[row], 0, nnz), e1 = dp_clamp(indptr[row + 1], e0, nnz);
+    const int64_t row = src_row(rows, r, n_total);
+    const int64_t e0 = clamp64(indptr[row], 0, nnz), e1 = clamp64(indptr[row + 1], e0, nnz);
     O* orow = out + r * (int64_t)ng;
     for (int j = tid; j < ng; j += CPM_THREADS) orow[j] = (O)0;
     A acc = 0;
@@ -167,10 +165,6 @@ __global__ __launch_bounds__(CPM_THREADS) void k_cpm_csr(const int64_t* __restri
         if (j < 0 || j >= ng) continue;
         orow[j] = cpm_value<O>((double)data[k], norm, scaler, log_mode);
     }
-}
-
-bool cpm_wide(const void* x, int64_t ld, int vsize) {
-    return reinterpret_cast<uintptr_t>(x) % 16 == 0 && (ld * vsize) % 16 == 0;
 }
 
 // vtype 0 int32, 1 float, 2 double; otype 0 float, 1 double (checked by the caller)
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(64) void k_gs_partial(const T* __restrict__ data, i
         }
     };
     T piv[4];
-    load4(data + dp_clamp(rows ? rows[0] : 0, 0, n_total - 1) * ld, piv);
+    load4(data + src_row(rows, 0, n_total) * ld, piv);
     double cnt[4], s1[4], s2[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) cnt[e] = s1[e] = s2[e] = 0.0;
@@ -273,7 +267,7 @@ __global__ __launch_bounds__(64) void k_gs_partial(const T* __restrict__ data, i
         for (int u = 0; u < 4; ++u) {
             valid[u] = i + u < c1;
             const int64_t pos = valid[u] ? i + u : c0;                       // c0 < c1 <= n here: a row that exists
-            load4(data + dp_clamp(rows ? rows[pos] : pos, 0, n_total - 1) * ld, xv[u]);
+            load4(data + src_row(rows, pos, n_total) * ld, xv[u]);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -312,7 +306,7 @@ __global__ __launch_bounds__(256) void k_gs_finish(const T* __restrict__ data, i
         s1 += b[(int64_t)D];
         s2 += b[2 * (int64_t)D];
     }
-    const double p = (double)data[dp_clamp(rows ? rows[0] : 0, 0, n_total - 1) * ld + d];
+    const double p = (double)data[src_row(rows, 0, n_total) * ld + d];
     const double nn = (double)n;
     const double m = s1 / nn;
     double var = (s2 - s1 * m) / nn;
@@ -323,8 +317,6 @@ __global__ __launch_bounds__(256) void k_gs_finish(const T* __restrict__ data, i
 }
 
 int64_t gs_nseg(int64_t n) { return cdiv64(n, GS_SEG_ROWS); }
-
-bool gs_wide(const void* data, int64_t ld, int vsize) { return cpm_wide(data, ld, vsize); }
 
 template <typename T>
 static int gene_stats_t(const void* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, int64_t n, double eps, void* ws,

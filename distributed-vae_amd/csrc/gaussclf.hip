@@ -4,7 +4,7 @@
 // fold of a k-fold split, one Gaussian per cell type to the training cells and scores the held-out cells under each.  Two
 // launches carry the dense part of that.  mmvae_group_moments: the first and second moments about one pivot of every
 // (class, fold) group of cells in one pass -- the rows arrive ordered by group, are cut into segments of at most GC_SEG_ROWS
-// that never cross a group boundary (k_gc_segments, as k_sc_segments), a workgroup owns one segment and all d (d + 3) / 2 of
+// that never cross a group boundary (k_segments, segments.hip: the scheme is described once, in common.hpp), a workgroup owns one segment and all d (d + 3) / 2 of
 // its sums (k_gc_partial), and a last launch adds each group's segments in order (k_gc_finish).  Moments about one pivot are
 // additive over groups, so the host forms every fold's training moments from them without a second pass.
 // mmvae_gauss_scores: score(i, k) = c0[m, k] - |W_mk^T (x_i - mu_mk)|^2 / 2 of every cell under every class of the model m
@@ -14,50 +14,6 @@
 #include "common.hpp"
 
 namespace mmvae {
-
-__device__ inline int64_t gc_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// The segment table, by one workgroup: k_sc_segments with GC_SEG_ROWS.  offsets [G + 1] non-decreasing from 0 to n (the
-// caller's contract).  Group g with f_g > 0 rows gets ceil(f_g / GC_SEG_ROWS) consecutive segments, gseg[g] the first of
-// them, gseg[G] = their number (<= nseg_max = G + n / GC_SEG_ROWS); seg_begin[s] the first row of segment s,
-// seg_begin[gseg[G]] = offsets[G].  Every offset is clamped to [0, n]: offsets that break the contract give a table that is
-// wrong but stays inside [0, nseg_max] x [0, n], and the later launches clamp as well.
-__global__ __launch_bounds__(256) void k_gc_segments(const int64_t* __restrict__ offsets, int G, int64_t n, int64_t nseg_max,
-                                                     int* __restrict__ gseg, int64_t* __restrict__ seg_begin) {
-    __shared__ int64_t part[257];
-    const int tid = threadIdx.x;
-    const int per = (G + 255) / 256;
-    const int k0 = (int)imin64((int64_t)tid * per, G), k1 = (int)imin64((int64_t)k0 + per, G);
-    auto off = [&](int k) { return gc_clamp(offsets[k], 0, n); };
-    int64_t cnt = 0;
-    for (int k = k0; k < k1; ++k) {
-        const int64_t f = off(k + 1) - off(k);
-        if (f > 0) cnt += cdiv64(f, GC_SEG_ROWS);
-    }
-    part[tid] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int t = 0; t < 256; ++t) {
-            const int64_t c = part[t];
-            part[t] = run;
-            run += c;
-        }
-        part[256] = run;
-    }
-    __syncthreads();
-    int64_t s = part[tid];
-    for (int k = k0; k < k1; ++k) {
-        gseg[k] = (int)imin64(s, nseg_max);
-        const int64_t beg = off(k), f = off(k + 1) - beg;
-        for (int64_t c = 0; c < f && s < nseg_max; c += GC_SEG_ROWS, ++s) seg_begin[s] = beg + c;
-    }
-    if (tid == 0) {
-        const int64_t total = imin64(part[256], nseg_max);
-        gseg[G] = (int)total;
-        seg_begin[total] = off(G);
-    }
-}
 
 // The first row of packed upper-triangle row i of a d x d matrix: i d - i (i - 1) / 2.
 __device__ inline int gc_tri_row(int i, int d) { return i * (2 * d - i + 1) / 2; }
@@ -76,8 +32,8 @@ __global__ __launch_bounds__(256) void k_gc_partial(const float* __restrict__ x,
     __shared__ double tile[GC_ROW_CHUNK * (DMAX + 1)];
     const int seg = blockIdx.x;
     if (seg >= gseg[G]) return;                     // the whole workgroup
-    const int64_t c0 = gc_clamp(seg_begin[seg], 0, n);
-    const int64_t c1 = imin64(gc_clamp(seg_begin[seg + 1], c0, n), c0 + GC_SEG_ROWS);
+    int64_t c0, c1;
+    seg_range(seg_begin, seg, n, GC_SEG_ROWS, c0, c1);
     const int tid = threadIdx.x;
     const int Q = d * (d + 3) / 2, pitch = d + 1;
     int ia[NPT], ja[NPT];
@@ -132,7 +88,7 @@ __global__ __launch_bounds__(256) void k_gc_finish(const double* __restrict__ pa
     const int q = (blockIdx.x - g * tiles) * 256 + threadIdx.x;
     const int Q = d * (d + 3) / 2;
     if (q >= Q) return;
-    const int64_t sg0 = gc_clamp(gseg[g], 0, nseg_max), sg1 = gc_clamp(gseg[g + 1], sg0, nseg_max);
+    const int64_t sg0 = clamp64(gseg[g], 0, nseg_max), sg1 = clamp64(gseg[g + 1], sg0, nseg_max);
     double a = 0.0;
     for (int64_t sg = sg0; sg < sg1; ++sg) a += part[sg * Q + q];
     if (q < d) s[(int64_t)g * d + q] = a;
@@ -185,7 +141,7 @@ __global__ __launch_bounds__(GC_ROW_TILE * GC_SCORE_WAVES) void k_gc_scores(
     __syncthreads();
     int mine = model[rr];
     mine = mine < 0 ? 0 : (mine > F - 1 ? F - 1 : mine);
-    const int64_t out = perm ? gc_clamp(perm[rr], 0, n - 1) : rr;
+    const int64_t out = perm ? clamp64(perm[rr], 0, n - 1) : rr;
     const double* xd = xs + lane;
     const double ninf = -__builtin_inf();
     const int per = (K + nw - 1) / nw;
@@ -244,8 +200,6 @@ __global__ __launch_bounds__(GC_ROW_TILE * GC_SCORE_WAVES) void k_gc_scores(
     second[out] = b2;
 }
 
-int64_t gc_nseg_max(int64_t n, int G) { return (int64_t)G + n / GC_SEG_ROWS; }
-
 // the instance of k_gc_partial that runs dimension d: the first entry of GC_DC that holds it
 int gc_dclass(int d) {
     for (int c = 0; c < GC_N_DC; ++c)
@@ -258,13 +212,10 @@ int gc_dclass(int d) {
 // (mmvae_group_moments_workspace_bytes)
 int launch_group_moments(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int G, const float* pivot, void* ws,
                          double* s, double* M, int dclass, hipStream_t st) {
-    const int64_t nseg = gc_nseg_max(n, G);
+    const int64_t nseg = nseg_max(n, G, GC_SEG_ROWS);
     const int Q = d * (d + 3) / 2;
-    double* part = static_cast<double*>(ws);
-    int64_t* seg_begin = reinterpret_cast<int64_t*>(part + nseg * Q);
-    int* gseg = reinterpret_cast<int*>(seg_begin + nseg + 1);
-    hipLaunchKernelGGL(k_gc_segments, dim3(1), dim3(256), 0, st, offsets, G, n, nseg, gseg, seg_begin);
-    HIP_LAUNCH_CHECK("k_gc_segments");
+    const auto [part, seg_begin, gseg] = seg_ws_carve(ws, nseg, Q);
+    if (int rc = launch_segments(offsets, G, n, GC_SEG_ROWS, nseg, gseg, seg_begin, st)) return rc;
     const dim3 grid((unsigned)nseg), block(256);
     switch (dclass) {
         case 0: hipLaunchKernelGGL((k_gc_partial<GC_DC[0]>), grid, block, 0, st, x, ld, n, d, pivot, gseg, G, seg_begin, part); break;

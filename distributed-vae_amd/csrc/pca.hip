@@ -15,8 +15,6 @@ namespace mmvae {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-__device__ inline int64_t pca_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // The four floats at p[c] .. p[c + 3] of a row of D columns; a column at or past D reads as its pivot would make t = 0
 // (the caller masks it).  WIDE: one 16-byte load where all four columns exist, else one float at a time: the same values.
 template <bool WIDE>
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(256) void k_gram_partial(const float* __restrict__ 
             const int64_t pos = r0 + sr + 16 * h;
             live[h] = pos < r_end;
             const int64_t at = live[h] ? pos : r_begin;                   // r_begin < r_end <= n: a row that exists
-            const int64_t row = pca_clamp(rows ? rows[at] : at, 0, n_total - 1);
+            const int64_t row = src_row(rows, at, n_total);
             const float* p = data + row * ld;
             gram_load4<WIDE>(p, i0 + sc, D, xI[h]);
             if (!diag) gram_load4<WIDE>(p, j0 + sc, D, xJ[h]);
@@ -183,7 +181,8 @@ __global__ __launch_bounds__(256) void k_rows_mul(const T* __restrict__ X, int64
     for (int h = 0; h < 4; ++h) {
         const int64_t pos = r0 + 4 * w + h;
         live[h] = pos < n;
-        rowoff[h] = pca_clamp(live[h] ? (rows ? rows[pos] : pos) : 0, 0, n_total - 1) * ld;
+        // (src_row's clamp, around the choice of a row past n as well: this form keeps the kernel's schedule as it was)
+        rowoff[h] = clamp64(live[h] ? (rows ? rows[pos] : pos) : 0, 0, n_total - 1) * ld;
     }
 #pragma unroll
     for (int e = 0; e < VPT; ++e) {
@@ -255,8 +254,6 @@ int gram_segments(int64_t n, int D, int64_t* seg_rows) {
     if (seg_rows) *seg_rows = len;
     return nseg;
 }
-
-bool gram_wide(const float* data, int64_t ld) { return reinterpret_cast<uintptr_t>(data) % 16 == 0 && ld % 4 == 0; }
 
 // ws: ws_mat double [nseg - 1][D][D], ws_s double [nseg][D] (mmvae_gram_workspace_bytes)
 int launch_gram(const float* data, int64_t ld, int64_t n_total, const int64_t* rows, int64_t n, int D, const float* pivot, void* ws,

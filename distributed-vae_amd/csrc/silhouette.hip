@@ -5,7 +5,8 @@
 //   S(i, k) = sum over the cells j of cluster k of |x_i - x_j|,  a_i = S(i, l_i) / (f_{l_i} - 1),
 //   b_i = min over k != l_i of S(i, k) / f_k,  s_i = (b_i - a_i) / max(a_i, b_i),  0 for a singleton and for a_i = b_i = 0.
 // That is n^2 distances.  The caller hands the cells sorted by label, so a cluster is a run of columns; the runs are cut into
-// segments of at most SIL_SEG_COLS columns (k_sil_segments), one workgroup adds one segment's distances for 256 rows
+// segments of at most SIL_SEG_COLS columns (k_segments, segments.hip: the scheme is described once, in common.hpp above
+// launch_segments; cseg here is its gseg), one workgroup adds one segment's distances for 256 rows
 // (k_sil_partial: one thread per row, the segment's columns staged in LDS and read by all lanes at one address) and a last
 // launch adds every cluster's segments in order and forms a, b and s (k_sil_finish).  Distances are fp32 in difference form
 // (subtract, fma the squares in coordinate order, v_sqrt_f32), everything after them fp64.  No atomics: every sum has one
@@ -13,46 +14,6 @@
 #include "common.hpp"
 
 namespace mmvae {
-
-// The segment table, by one workgroup.  offsets [K + 1] non-decreasing from 0 to n (the caller's contract).  Cluster k with
-// f_k > 0 columns gets ceil(f_k / SIL_SEG_COLS) consecutive segments, cseg[k] the first of them, cseg[K] = their number
-// (<= nseg_max = K + n / SIL_SEG_COLS); seg_begin[s] the first column of segment s, seg_begin[cseg[K]] = offsets[K].  Offsets
-// that break the contract give a table that is wrong but stays inside [0, nseg_max] x [0, n]: later launches clamp as well.
-__global__ __launch_bounds__(256) void k_sil_segments(const int64_t* __restrict__ offsets, int K, int64_t n, int64_t nseg_max,
-                                                      int* __restrict__ cseg, int64_t* __restrict__ seg_begin) {
-    __shared__ int64_t part[257];
-    const int tid = threadIdx.x;
-    const int per = (K + 255) / 256;
-    const int k0 = imin64((int64_t)tid * per, K), k1 = imin64((int64_t)k0 + per, K);
-    int64_t cnt = 0;
-    for (int k = k0; k < k1; ++k) {
-        const int64_t f = offsets[k + 1] - offsets[k];
-        if (f > 0) cnt += cdiv64(f, SIL_SEG_COLS);
-    }
-    part[tid] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int t = 0; t < 256; ++t) {
-            const int64_t c = part[t];
-            part[t] = run;
-            run += c;
-        }
-        part[256] = run;
-    }
-    __syncthreads();
-    int64_t s = part[tid];
-    for (int k = k0; k < k1; ++k) {
-        cseg[k] = (int)imin64(s, nseg_max);
-        const int64_t beg = offsets[k], f = offsets[k + 1] - beg;
-        for (int64_t c = 0; c < f && s < nseg_max; c += SIL_SEG_COLS, ++s) seg_begin[s] = beg + c;
-    }
-    if (tid == 0) {
-        const int64_t total = imin64(part[256], nseg_max);
-        cseg[K] = (int)total;
-        seg_begin[total] = offsets[K];
-    }
-}
 
 // grid (nseg_max segments, row tiles of SIL_ROW_TILE), 256 threads: part[s][i] = the sum over the columns j of segment s of
 // |x_i - x_j|, added in column order into one fp64 register per row; four columns per iteration, their distances independent.
@@ -68,10 +29,8 @@ __global__ __launch_bounds__(256) void k_sil_partial(const float* __restrict__ x
     __shared__ float4 cols[SIL_LDS_FLOATS / 4];
     const int seg = blockIdx.x;
     if (seg >= cseg[K]) return;                     // the whole workgroup
-    int64_t c0 = seg_begin[seg], c1 = seg_begin[seg + 1];
-    c0 = c0 < 0 ? 0 : (c0 > n ? n : c0);
-    c1 = c1 < c0 ? c0 : (c1 > n ? n : c1);
-    if (c1 - c0 > SIL_SEG_COLS) c1 = c0 + SIL_SEG_COLS;
+    int64_t c0, c1;
+    seg_range(seg_begin, seg, n, SIL_SEG_COLS, c0, c1);
     const int tid = threadIdx.x;
     float* cf = reinterpret_cast<float*>(cols);
     for (int64_t rt = blockIdx.y; rt * SIL_ROW_TILE < n; rt += gridDim.y) {
@@ -163,8 +122,6 @@ __global__ __launch_bounds__(256) void k_sil_finish(const double* __restrict__ p
     s[dst] = out;
 }
 
-int64_t sil_nseg_max(int64_t n, int K) { return (int64_t)K + n / SIL_SEG_COLS; }
-
 int sil_dv(int d) {
     for (int i = 0; i < SIL_N_DV; ++i)
         if (4 * SIL_DV[i] >= d) return SIL_DV[i];
@@ -174,12 +131,9 @@ int sil_dv(int d) {
 // ws: part double [nseg_max][n], seg_begin int64 [nseg_max + 1], cseg int32 [K + 1] (mmvae_silhouette_workspace_bytes)
 int launch_silhouette(const float* x, int64_t ld, int64_t n, int d, const int64_t* offsets, int K, const int64_t* perm, void* ws,
                       double* s, hipStream_t st) {
-    const int64_t nseg = sil_nseg_max(n, K);
-    double* part = static_cast<double*>(ws);
-    int64_t* seg_begin = reinterpret_cast<int64_t*>(part + nseg * n);
-    int* cseg = reinterpret_cast<int*>(seg_begin + nseg + 1);
-    hipLaunchKernelGGL(k_sil_segments, dim3(1), dim3(256), 0, st, offsets, K, n, nseg, cseg, seg_begin);
-    HIP_LAUNCH_CHECK("k_sil_segments");
+    const int64_t nseg = nseg_max(n, K, SIL_SEG_COLS);
+    const auto [part, seg_begin, cseg] = seg_ws_carve(ws, nseg, n);
+    if (int rc = launch_segments(offsets, K, n, SIL_SEG_COLS, nseg, cseg, seg_begin, st)) return rc;
     const dim3 grid((unsigned)nseg, (unsigned)imin64(cdiv64(n, SIL_ROW_TILE), 65535)), block(256);
 #define SIL_CASE(V)                                                                                              \
     case V:                                                                                                      \

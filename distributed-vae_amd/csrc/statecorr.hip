@@ -7,56 +7,12 @@
 // consecutive genes (four a lane, one float4 a row) and one segment of at most SC_SEG_ROWS rows, and keeps per gene the
 // masked count, sum x, sum x^2, min x, max x and per (gene, state) sum s, sum s^2, sum x s, min s, max s -- all sums fp64,
 // every product of two fp32 values exact in fp64 (k_sc_partial).  The rows arrive ordered by group and the segments never
-// cross a group boundary (k_sc_segments, as k_sil_segments cuts clusters); a last launch adds each group's segments in order
+// cross a group boundary (k_segments, segments.hip: the scheme is described once, in common.hpp); a last launch adds each group's segments in order
 // and forms r in fp64 (k_sc_finish).  No atomics: every sum has one owner and a fixed order, so the result is the same bits
 // on every run, and a group's values are those of a call on that group's rows alone.
 #include "common.hpp"
 
 namespace mmvae {
-
-__device__ inline int64_t sc_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// The segment table, by one workgroup.  offsets [G + 1] non-decreasing from 0 to n (the caller's contract; null: one group,
-// 0 and n).  Group g with f_g > 0 rows gets ceil(f_g / SC_SEG_ROWS) consecutive segments, gseg[g] the first of them,
-// gseg[G] = their number (<= nseg_max = G + n / SC_SEG_ROWS); seg_begin[s] the first row of segment s,
-// seg_begin[gseg[G]] = offsets[G].  Every offset is clamped to [0, n]: offsets that break the contract give a table that is
-// wrong but stays inside [0, nseg_max] x [0, n], and the later launches clamp as well.
-__global__ __launch_bounds__(256) void k_sc_segments(const int64_t* __restrict__ offsets, int G, int64_t n, int64_t nseg_max,
-                                                     int* __restrict__ gseg, int64_t* __restrict__ seg_begin) {
-    __shared__ int64_t part[257];
-    const int tid = threadIdx.x;
-    const int per = (G + 255) / 256;
-    const int k0 = (int)imin64((int64_t)tid * per, G), k1 = (int)imin64((int64_t)k0 + per, G);
-    auto off = [&](int k) { return offsets ? sc_clamp(offsets[k], 0, n) : (k == 0 ? (int64_t)0 : n); };
-    int64_t cnt = 0;
-    for (int k = k0; k < k1; ++k) {
-        const int64_t f = off(k + 1) - off(k);
-        if (f > 0) cnt += cdiv64(f, SC_SEG_ROWS);
-    }
-    part[tid] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int t = 0; t < 256; ++t) {
-            const int64_t c = part[t];
-            part[t] = run;
-            run += c;
-        }
-        part[256] = run;
-    }
-    __syncthreads();
-    int64_t s = part[tid];
-    for (int k = k0; k < k1; ++k) {
-        gseg[k] = (int)imin64(s, nseg_max);
-        const int64_t beg = off(k), f = off(k + 1) - beg;
-        for (int64_t c = 0; c < f && s < nseg_max; c += SC_SEG_ROWS, ++s) seg_begin[s] = beg + c;
-    }
-    if (tid == 0) {
-        const int64_t total = imin64(part[256], nseg_max);
-        gseg[G] = (int)total;
-        seg_begin[total] = off(G);
-    }
-}
 
 // grid nseg_max x tiles workgroups (segment-major, so that neighbours read neighbouring pieces of the same rows), one wave
 // each: lane l owns the genes tile * SC_TILE + 4 l .. + 3 and walks the segment's rows in order, four rows' loads in flight.
@@ -73,8 +29,8 @@ __global__ __launch_bounds__(64) void k_sc_partial(const float* __restrict__ dat
                                                    const int64_t* __restrict__ seg_begin, int tiles, double* __restrict__ part) {
     const int seg = blockIdx.x / tiles, tile = blockIdx.x - seg * tiles;
     if (seg >= gseg[G]) return;                     // the whole workgroup
-    const int64_t c0 = sc_clamp(seg_begin[seg], 0, n);
-    const int64_t c1 = imin64(sc_clamp(seg_begin[seg + 1], c0, n), c0 + SC_SEG_ROWS);
+    int64_t c0, c1;
+    seg_range(seg_begin, seg, n, SC_SEG_ROWS, c0, c1);
     const int g0 = tile * SC_TILE + 4 * threadIdx.x;
     const bool quad = WIDE && g0 + 4 <= D;
     double cnt[4], sx[4], sxx[4], ss[NS][4], sss[NS][4], sxs[NS][4];
@@ -97,7 +53,7 @@ __global__ __launch_bounds__(64) void k_sc_partial(const float* __restrict__ dat
         for (int u = 0; u < 4; ++u) {
             const bool valid = i + u < c1;
             const int64_t pos = valid ? i + u : c0;                       // c0 < c1 <= n here: a row that exists
-            const int64_t row = sc_clamp(rows ? rows[pos] : pos, 0, n_total - 1);
+            const int64_t row = src_row(rows, pos, n_total);
             const float* p = data + row * ld;
             if (quad) {
                 const float4 v = *reinterpret_cast<const float4*>(p + g0);
@@ -171,7 +127,7 @@ __global__ __launch_bounds__(256) void k_sc_finish(const double* __restrict__ pa
     const int g = blockIdx.x / tiles;
     const int d = (blockIdx.x - g * tiles) * 256 + threadIdx.x;
     if (d >= D) return;
-    const int64_t sg0 = sc_clamp(gseg[g], 0, nseg_max), sg1 = sc_clamp(gseg[g + 1], sg0, nseg_max);
+    const int64_t sg0 = clamp64(gseg[g], 0, nseg_max), sg1 = clamp64(gseg[g + 1], sg0, nseg_max);
     const int Q = 5 + 5 * S;
     const int64_t segstride = (int64_t)Q * D;
     double c = 0.0, sx = 0.0, sxx = 0.0, minx = __builtin_inf(), maxx = -__builtin_inf();
@@ -208,21 +164,14 @@ __global__ __launch_bounds__(256) void k_sc_finish(const double* __restrict__ pa
     }
 }
 
-int64_t sc_nseg_max(int64_t n, int G) { return (int64_t)G + n / SC_SEG_ROWS; }
-
-bool sc_wide(const float* data, int64_t ld) { return reinterpret_cast<uintptr_t>(data) % 16 == 0 && ld % 4 == 0; }
-
-// wide: the 16-byte loads (the caller has checked sc_wide), else the narrow ones; equal bits.
+// wide: the 16-byte loads (the caller has checked wide16), else the narrow ones; equal bits.
 // ws: part double [nseg_max][5 + 5 S][D], seg_begin int64 [nseg_max + 1], gseg int32 [G + 1]
 // (mmvae_state_corr_workspace_bytes)
 int launch_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
                       int64_t n, int S, const int64_t* offsets, int G, void* ws, double* r, int64_t* count, bool wide, hipStream_t st) {
-    const int64_t nseg = sc_nseg_max(n, G);
-    double* part = static_cast<double*>(ws);
-    int64_t* seg_begin = reinterpret_cast<int64_t*>(part + nseg * (5 + 5 * (int64_t)S) * D);
-    int* gseg = reinterpret_cast<int*>(seg_begin + nseg + 1);
-    hipLaunchKernelGGL(k_sc_segments, dim3(1), dim3(256), 0, st, offsets, G, n, nseg, gseg, seg_begin);
-    HIP_LAUNCH_CHECK("k_sc_segments");
+    const int64_t nseg = nseg_max(n, G, SC_SEG_ROWS);
+    const auto [part, seg_begin, gseg] = seg_ws_carve(ws, nseg, (5 + 5 * (int64_t)S) * D);
+    if (int rc = launch_segments(offsets, G, n, SC_SEG_ROWS, nseg, gseg, seg_begin, st)) return rc;
     const int tiles = (int)cdiv64(D, SC_TILE);
     const dim3 grid((unsigned)(nseg * tiles)), block(64);
 #define SC_PASS(NS)                                                                                                          \

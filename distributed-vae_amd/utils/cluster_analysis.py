@@ -29,7 +29,7 @@ import torch
 
 from .. import _native as N
 from .. import dist as D
-from ..cpl_mixvae import get_device
+from .._utils import float32_on_device
 
 
 def _encode(labels, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -47,21 +47,8 @@ def _encode(labels, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
 
 
 def _points_on_device(x, device) -> torch.Tensor:
-    """float32 [n, d] on ``device``: a float32 device tensor as it is, anything else converted (float64 is rounded)."""
-    if isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.device.type == "cuda":
-        if x.dim() != 2:
-            raise ValueError(f"x of shape {tuple(x.shape)} is not [n, d]")
-        if not bool(torch.isfinite(x).all()):
-            raise ValueError("x holds NaN or infinity")
-        return x
-    h = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    if h.ndim != 2:
-        raise ValueError(f"x of shape {h.shape} is not [n, d]")
-    with np.errstate(over="ignore"):
-        h = np.ascontiguousarray(h, dtype=np.float32)
-    if not np.isfinite(h).all():
-        raise ValueError("x holds NaN or infinity (or a value float32 cannot hold)")
-    return torch.from_numpy(h).to(get_device(device))
+    """float32 [n, d] on ``device``, finite (a device tensor is checked too)."""
+    return float32_on_device(x, device, "x", "[n, d]", check_device_finite=True)
 
 
 def _samples(x_dev: torch.Tensor, codes: np.ndarray, n_classes: int) -> np.ndarray:

@@ -23,7 +23,7 @@ import torch
 
 from .. import _native as N
 from .. import dist as D
-from ..cpl_mixvae import get_device
+from .._utils import float32_on_device
 
 MAX_COMPONENTS = N.PCA_MAX_BLOCK      # the widest block of mmvae_symm_mul and mmvae_pca_project
 
@@ -134,19 +134,8 @@ def fit_from_covariance(mul, C_host: Callable[[], np.ndarray], mean, total_varia
 
 
 def _matrix_on_device(data, device) -> torch.Tensor:
-    """float32 [n_total, D] on the device: a float32 device tensor as it is, anything else converted (float64 is rounded)."""
-    if isinstance(data, torch.Tensor) and data.dtype == torch.float32 and data.device.type == "cuda":
-        if data.dim() != 2:
-            raise ValueError(f"data of shape {tuple(data.shape)} is not [n, D]")
-        return data
-    h = data.detach().cpu().numpy() if isinstance(data, torch.Tensor) else np.asarray(data)
-    if h.ndim != 2:
-        raise ValueError(f"data of shape {h.shape} is not [n, D]")
-    with np.errstate(over="ignore"):
-        h = np.ascontiguousarray(h, dtype=np.float32)
-    if not np.isfinite(h).all():
-        raise ValueError("data holds NaN or infinity (or a value float32 cannot hold)")
-    return torch.from_numpy(h).to(get_device(device))
+    """float32 [n_total, D] on the device (its values are checked later, in chunks: ``_pivot``)."""
+    return float32_on_device(data, device, "data", "[n, D]")
 
 
 def _rows_on_device(rows, n_total: int, device) -> Optional[torch.Tensor]:

@@ -16,24 +16,7 @@ import torch
 
 from .. import _native as N
 from .. import dist as D
-from ..cpl_mixvae import get_device
-
-
-def _float32_on_device(a, device, what: str) -> torch.Tensor:
-    """float32 [., .] on ``device``: a float32 device tensor as it is (with its stride), anything else rounded to float32
-    and uploaded.  Host input is checked for NaN and infinity; a device tensor is the caller's (the kernel's contract)."""
-    if isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.device.type == "cuda":
-        if a.dim() != 2:
-            raise ValueError(f"{what} of shape {tuple(a.shape)} is not 2-D")
-        return a
-    h = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    if h.ndim != 2:
-        raise ValueError(f"{what} of shape {h.shape} is not 2-D")
-    with np.errstate(over="ignore"):
-        h = np.ascontiguousarray(h, dtype=np.float32)
-    if not np.isfinite(h).all():
-        raise ValueError(f"{what} holds NaN or infinity (or a value float32 cannot hold)")
-    return torch.from_numpy(h if h.flags.writeable else h.copy()).to(get_device(device))
+from .._utils import float32_on_device
 
 
 def grouped_state_corr(state: torch.Tensor, data: torch.Tensor, rows: Optional[torch.Tensor], codes: Optional[torch.Tensor],
@@ -98,8 +81,8 @@ def corr_analysis(state, cell, groups=None, rows=None, return_r: bool = False, d
         raise ValueError("corr_analysis needs at least one cell")
     on_gpu = [t.device for t in (cell, state) if isinstance(t, torch.Tensor) and t.device.type == "cuda"]
     dev = on_gpu[0] if on_gpu and device is None else device
-    data_d = _float32_on_device(cell, dev, "cell")
-    state_d = _float32_on_device(state, data_d.device, "state")
+    data_d = float32_on_device(cell, dev, "cell", "2-D")
+    state_d = float32_on_device(state, data_d.device, "state", "2-D")
     to_dev = lambda a: None if a is None else torch.from_numpy(a).to(data_d.device)
     r_d, c_d = grouped_state_corr(state_d, data_d, to_dev(rows_h), to_dev(codes_h), n_groups)
     r, counts = r_d.cpu().numpy(), c_d.cpu().numpy()
