@@ -219,6 +219,9 @@ def lib():
     L.mmvae_gauss_scores_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_gauss_scores_workspace_bytes.restype = C.c_size_t
     L.mmvae_gauss_scores.argtypes = [vp, i64, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.mmvae_forest_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    L.mmvae_forest_workspace_bytes.restype = C.c_size_t
+    L.mmvae_forest_cv.argtypes = [vp, i64, i64, i32, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.mmvae_gram_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_gram_workspace_bytes.restype = C.c_size_t
     L.mmvae_gram_segments.argtypes = [i64, i32, C.POINTER(C.c_int64)]
@@ -928,6 +931,45 @@ def gauss_scores(x: torch.Tensor, model: torch.Tensor, mu: torch.Tensor, W: torc
                                    None, 0, _ptr(label), _ptr(best), _ptr(second), _ptr(scores), _stream(xs.device)),
           "mmvae_gauss_scores")
     return label, best, second, scores
+
+
+# launch_forest (csrc/forest.hip; the constants are those of csrc/common.hpp)
+FOREST_BINS = 256               # RF_BINS: bins of a feature
+FOREST_MAX_D, FOREST_MAX_K, FOREST_MAX_F, FOREST_MAX_T, FOREST_MAX_N = 128, 128, 64, 4096, 1 << 24
+FOREST_TREE_BYTES_PER_ROW = 56  # RF_TREE_BYTES_PER_ROW: a tree's node table, stack and index lists per row of the call
+FOREST_CHUNK_BYTES = 1 << 30    # RF_CHUNK_BYTES: per-tree tables of one chunk of launches at most
+
+
+def forest_chunk(n: int, F: int, T: int) -> int:
+    """The trees of one chunk of launches (rf_chunk, csrc/forest.hip)."""
+    return min(F * T, max(1, FOREST_CHUNK_BYTES // (FOREST_TREE_BYTES_PER_ROW * n + 4)))
+
+
+def forest_cv(bins: torch.Tensor, codes: torch.Tensor, fold: torch.Tensor, K: int, F: int, T: int, mtry: int, seed: int,
+              return_votes: bool = False, return_trees: bool = False):
+    """mmvae_forest_cv: uint8 ``bins`` [n, d] on the GPU (rows may be strided, columns not), int32 ``codes`` [n] in [0, K) and
+    ``fold`` [n] in [0, F) -> (label, best, second int32 [n], votes int32 [n, K] or None, trees or None) on the device:
+    ``T`` trees a fold grown on the rows outside it, every row voted on by its own fold's trees.  trees = {"count": int32
+    [F T], "nodes": int32 [F T, 2 n, 4]}: node j of tree g is (feature, thr, left child, rows) or (-1, class, 0, rows); rows
+    past the count are zero."""
+    _need_cuda("forest_cv", bins, codes, fold)
+    if bins.dtype != torch.uint8 or bins.dim() != 2:
+        raise TypeError("forest_cv: bins must be uint8 [n, d]")
+    n, d = (int(v) for v in bins.shape)
+    if codes.dtype != torch.int32 or tuple(codes.shape) != (n,) or fold.dtype != torch.int32 or tuple(fold.shape) != (n,):
+        raise TypeError(f"forest_cv: codes and fold must be int32 [{n}]")
+    b, codes, fold = _row_major(bins), codes.contiguous(), fold.contiguous()
+    i32 = dict(dtype=torch.int32, device=b.device)
+    label, best, second = (torch.empty(n, **i32) for _ in range(3))
+    votes = torch.empty(n, K, **i32) if return_votes else None
+    count = torch.zeros(F * T, **i32) if return_trees else None
+    nodes = torch.zeros(F * T, 2 * n, 4, **i32) if return_trees else None
+    ws_bytes = int(lib().mmvae_forest_workspace_bytes(n, d, F, K, T))
+    ws = _workspace(ws_bytes, b.device)
+    check(lib().mmvae_forest_cv(_ptr(b), int(b.stride(0)), n, d, _ptr(codes), _ptr(fold), K, F, T, mtry,
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ws), ws_bytes, _ptr(label), _ptr(best), _ptr(second),
+                                _ptr(votes), _ptr(count), _ptr(nodes), _stream(b.device)), "mmvae_forest_cv")
+    return label, best, second, votes, ({"count": count, "nodes": nodes} if return_trees else None)
 
 
 # launch_gram / launch_symm_mul / launch_pca_project (csrc/pca.hip; the constants are those of csrc/common.hpp)

@@ -866,21 +866,30 @@ class cpl_mixVAE:
         class is known), ``"fold"`` int64 [n] and ``"data_indx"``.  The loader must serve every row once (no ``drop_last``)."""
         if D.is_dist():
             raise NotImplementedError("classify_latents is not data-parallel: run it on one rank, outside the process group")
+        from .utils import cluster_analysis as CA
+        points, y, data_indx = self._latents_to_classify(dl, labels, arm, on, "classify_latents")
+        acc, ref, pred, res = CA.classify_points(points, y, kfold, seed, kind)
+        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
+                "data_indx": data_indx}
+
+    def _latents_to_classify(self, dl, labels, arm, on, who, also=()):
+        """What ``classify_latents`` and ``classify_forest`` share: their refusals, the encode of ``dl`` on the device and the
+        labels of the cells it serves -> (arm ``arm``'s latents ``on``, float32 [n, .] on the device; the cells' labels;
+        ``data_indx``).  ``also``: what else the caller takes for ``on``, for the message."""
         if self.ref_prior:
             raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
         if not 0 <= int(arm) < self.n_arm:
             raise ValueError(f"arm = {arm} outside [0, {self.n_arm})")
         names = {"x_low": "x_low", "state_mu": "s_mean", "z_prob": "c"}
         if on not in names:
-            raise ValueError(f"on = {on!r}: one of {sorted(names)}")
+            raise ValueError(f"on = {on!r}: one of {sorted(names) + list(also)}")
         from .model import fill_latents
         from .utils.dataloader import DeviceLoader
-        from .utils import cluster_analysis as CA
         A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
         dev = self.device
         resident = isinstance(dl, DeviceLoader)
         if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
-            raise ValueError("classify_latents needs a loader that serves every row once (no drop_last, no sharding)")
+            raise ValueError(f"{who} needs a loader that serves every row once (no drop_last, no sharding)")
         if not resident:
             dl = _Replay(dl, dev)
         n_rows = len(dl.dataset)
@@ -895,10 +904,25 @@ class cpl_mixVAE:
         inds = fill_latents(dl, [(self.model, pruning_mask, out, None)], self.temp)
         self.model.train(was_training)
         data_indx = inds.cpu().numpy()
-        y = np.asarray(labels)[data_indx.astype(np.int64)]
-        acc, ref, pred, res = CA.classify_points(out[names[on]][int(arm)], y, kfold, seed, kind)
-        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
-                "data_indx": data_indx}
+        return out[names[on]][int(arm)], np.asarray(labels)[data_indx.astype(np.int64)], data_indx
+
+    def _expression_to_classify(self, dl, labels, who):
+        """What ``classify_pcs`` and ``classify_forest(on="pcs")`` share: the loaders they refuse and the expression of the cells
+        ``dl`` serves -> (the matrix on the device; its rows in visiting order, or None for all; the cells' labels;
+        ``data_indx``)."""
+        from .utils.dataloader import DeviceLoader
+        resident = isinstance(dl, DeviceLoader)
+        if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
+            raise ValueError(f"{who} needs a loader that serves every row once (no drop_last, no sharding)")
+        if resident:
+            rows = torch.cat(list(dl.iter_rows()))                         # the epoch's rows of the matrix, in visiting order
+            data, inds = dl.data, rows
+        else:
+            dl = _Replay(dl, self.device)
+            data, rows = dl.matrix(), None
+            inds = torch.cat([torch.as_tensor(i_x).reshape(-1) for _, i_x in dl])
+        data_indx = inds.cpu().numpy()
+        return data, rows, np.asarray(labels)[data_indx.astype(np.int64)], data_indx
 
     @torch.no_grad()
     def classify_pcs(self, dl, labels, num_pc: int = 10, kfold: int = 10, seed=0, kind: str = "qda"):
@@ -913,26 +937,41 @@ class cpl_mixVAE:
         loaders it refuses (``drop_last`` with a remainder, sharding)."""
         if D.is_dist():
             raise NotImplementedError("classify_pcs is not data-parallel: run it on one rank, outside the process group")
-        from .utils.dataloader import DeviceLoader
         from .utils import cluster_analysis as CA
         from .utils.pca import pca_project
-        resident = isinstance(dl, DeviceLoader)
-        if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
-            raise ValueError("classify_pcs needs a loader that serves every row once (no drop_last, no sharding)")
-        if resident:
-            rows = torch.cat(list(dl.iter_rows()))                         # the epoch's rows of the matrix, in visiting order
-            data, inds = dl.data, rows
-        else:
-            dl = _Replay(dl, self.device)
-            data, rows = dl.matrix(), None
-            inds = torch.cat([torch.as_tensor(i_x).reshape(-1) for _, i_x in dl])
-        data_indx = inds.cpu().numpy()
-        y = np.asarray(labels)[data_indx.astype(np.int64)]
+        data, rows, y, data_indx = self._expression_to_classify(dl, labels, "classify_pcs")
         checked = CA._cv_refusals(y, int(data_indx.shape[0]), kfold, seed, kind)       # every refusal before any device work
         z = pca_project(data, num_pc, rows=rows, out="device")
         acc, ref, pred, res = CA.classify_points(z, y, kfold, seed, kind, checked)
         return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
                 "data_indx": data_indx}
+
+    @torch.no_grad()
+    def classify_forest(self, dl, labels, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", n_trees: int = 100,
+                        num_pc: int = 10):
+        """How well a random forest recovers ``labels`` under k-fold cross-validation: the reference's ``RF_classifier``
+        (mmidas/utils/cluster_analysis.py:14-35; ``utils.cluster_analysis.forest_cv_predict`` states the forest and its
+        departures from sklearn's) on arm ``arm``'s latents -- ``on`` = "x_low", "state_mu" or "z_prob", as
+        ``classify_latents`` -- or, with ``on="pcs"``, on the top ``num_pc`` principal components of the expression of the
+        cells of ``dl``, the linear baseline of ``classify_pcs`` (the model is then not used).  Nothing leaves the device
+        between the encoder (or the projection) and the forest.  ``labels``, the loaders it takes and refuses and the
+        returned dict (``"acc"``, ``"ref_labels"``, ``"pred_labels"``, ``"margin"``, ``"fold"``, ``"data_indx"``) are those of
+        ``classify_latents``; ``"margin"`` float64 [n] is (the prediction's votes minus the most votes of another class) /
+        ``n_trees``, in the loader's order."""
+        if D.is_dist():
+            raise NotImplementedError("classify_forest is not data-parallel: run it on one rank, outside the process group")
+        from .utils import cluster_analysis as CA
+        if on == "pcs":
+            from .utils.pca import pca_project
+            data, rows, y, data_indx = self._expression_to_classify(dl, labels, "classify_forest")
+            checked = CA._forest_refusals(y, int(data_indx.shape[0]), int(num_pc), kfold, seed, n_trees, "sqrt")    # before the projection
+            points = pca_project(data, num_pc, rows=rows, out="device")
+        else:
+            points, y, data_indx = self._latents_to_classify(dl, labels, arm, on, "classify_forest", also=("pcs",))
+            checked = CA._forest_refusals(y, int(points.shape[0]), int(points.shape[1]), kfold, seed, n_trees, "sqrt")
+        acc, ref, pred, res = CA.classify_forest_points(CA._bins_on_device(points), y, kfold, seed, n_trees, checked)
+        margin = (res["best"].astype(np.float64) - res["second"].astype(np.float64)) / float(n_trees)
+        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": margin, "fold": res["fold"], "data_indx": data_indx}
 
 
 class _Replay:

@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the Gaussian classifiers, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the Gaussian classifiers, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -320,6 +320,37 @@ int mmvae_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int32
     }
     return launch_gauss_scores(x, ld, n, d, model, F, K, mu, W, c0, perm, label, best, second, scores,
                                reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- random forest on 256-bin features (forest.hip) ----
+size_t mmvae_forest_workspace_bytes(int64_t n, int d, int F, int K, int T) {
+    if (n < 2 || n > RF_MAX_N || d < 1 || d > RF_MAX_D || F < 2 || F > RF_MAX_F || K < 2 || K > RF_MAX_K || T < 1 || T > RF_MAX_T)
+        return 0;
+    return rf_ws_bytes(n, F, K, T);
+}
+
+int mmvae_forest_cv(const uint8_t* bins, int64_t ld, int64_t n, int d, const int32_t* codes, const int32_t* fold, int K, int F, int T,
+                    int mtry, uint64_t seed, void* ws, size_t ws_bytes, int32_t* label, int32_t* best, int32_t* second,
+                    int32_t* votes, int32_t* tree_count, int32_t* tree_nodes, void* stream) {
+    const char* who = "forest_cv";
+    if (!bins || !codes || !fold || !ws || !label || !best || !second) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (!tree_count != !tree_nodes) { set_error("%s: tree_count and tree_nodes go together", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 2, INT64_MAX)) return rc;
+    if (int rc = check_count(who, "d", d, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "K", K, 2, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "F", F, 2, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "T", T, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "mtry", mtry, 1, d)) return rc;
+    if (int rc = check_pitch(who, "ld", ld, "d", d)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, 16)) return rc;
+    if (n > RF_MAX_N || d > RF_MAX_D || K > RF_MAX_K || F > RF_MAX_F || T > RF_MAX_T) {
+        set_error("%s: n = %lld, d = %d, K = %d, F = %d, T = %d above %lld, %d, %d, %d, %d", who, (long long)n, d, K, F, T,
+                  (long long)RF_MAX_N, RF_MAX_D, RF_MAX_K, RF_MAX_F, RF_MAX_T);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, mmvae_forest_workspace_bytes(n, d, F, K, T))) return rc;
+    return launch_forest(bins, ld, n, d, codes, fold, K, F, T, mtry, seed, ws, label, best, second, votes, tree_count, tree_nodes,
+                         reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- principal components (pca.hip) ----

@@ -1047,6 +1047,21 @@ int launch_group_moments(const float* x, int64_t ld, int64_t n, int d, const int
 int launch_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int* model, int F, int K, const double* mu,
                         const double* W, const double* c0, const int64_t* perm, int* label, double* best, double* second,
                         double* scores, hipStream_t st);
+// random forest on 256-bin features (forest.hip)
+constexpr int RF_THREADS = 256;        // threads of every workgroup: k_rf_fit one tree, k_rf_predict four rows (one a wave)
+constexpr int RF_BINS = 256;           // bins of a feature: one a thread of the candidate search, four a lane of the scan
+constexpr int RF_MAX_D = 128;
+constexpr int RF_MAX_K = 128;          // the class x bin histogram of uint32 in LDS: 128 KiB at most, 21.5 KiB of partial sums
+constexpr int RF_MAX_F = 64;
+constexpr int RF_MAX_T = 4096;         // trees a fold
+constexpr int64_t RF_MAX_N = (int64_t)1 << 24;   // rows: n^2 exact in a double, 2 n nodes and F n rows in an int
+constexpr int64_t RF_TREE_BYTES_PER_ROW = 56;    // a tree's tables per row of the call: 2 nodes and 1 stack entry of 16, 2 list entries of 4
+constexpr int64_t RF_CHUNK_BYTES = (int64_t)1 << 30;   // per-tree tables of one chunk of launches at most (at least one tree)
+int rf_chunk(int64_t n, int F, int T);
+size_t rf_ws_bytes(int64_t n, int F, int K, int T);
+int launch_forest(const uint8_t* bins, int64_t ld, int64_t n, int d, const int* codes, const int* fold, int K, int F, int T,
+                  int mtry, uint64_t seed, void* ws, int* label, int* best, int* second, int* votes, int* tree_count,
+                  int* tree_nodes, hipStream_t st);
 // principal components: Gram matrix on the fp64 MFMA, block product, projection (pca.hip)
 constexpr int GRAM_TILE = 64;          // rows and columns of G per workgroup of k_gram_partial: four waves of 32 x 32
 constexpr int GRAM_KC = 32;            // rows of the data staged in LDS at a time: eight MFMA steps of four

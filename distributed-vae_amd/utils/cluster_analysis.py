@@ -1,6 +1,6 @@
 """The clusterability analysis of the reference's ``mmidas/utils/cluster_analysis.py``: ``get_SilhScore``,
-``cluster_compare`` and the two Gaussian classifiers ``QDA_classifier`` / ``LDA_classifier``, on the device, without
-sklearn.  The principal components that ``cluster_compare`` scores on are the one O(N D^2) step of the analysis: at the data
+``cluster_compare``, the two Gaussian classifiers ``QDA_classifier`` / ``LDA_classifier`` and ``RF_classifier``, on the
+device, without sklearn.  The principal components that ``cluster_compare`` scores on are the one O(N D^2) step of the analysis: at the data
 set's size a minute of host SVD in front of a silhouette of milliseconds.  ``cluster_compare(pca="device")`` takes them from
 ``utils/pca.py`` (``mmvae_gram`` on the fp64 MFMA, subspace iteration, ``mmvae_pca_project``); the
 default ``pca="host"`` is numpy's exact SVD, kept as it was.
@@ -18,8 +18,14 @@ built on the host in fp64 (F K eigen-decompositions of d x d matrices, plumbing)
 cell under every class of its own fold's model and takes the arg-max.  ``gaussian_cv_predict`` is the one function under
 both; it also returns the two best scores of every cell, whose difference is a confidence the reference does not offer.
 
-``RF_classifier`` and ``K_selection`` of that module are not part of this package (a random forest is not a dense, regular
-computation), and neither are ``custom_QDA`` and ``predict_leaf_gmm`` of ``analysis_tree_helpers.py``."""
+``RF_classifier`` is the sixth function of that module and the one its published figure is made with.  A forest on exact
+thresholds is not a regular computation; on features quantised to 256 rank bins (``quantile_bins``) it is: per node and
+feature a class x bin histogram of integers in LDS and a scan of it (``mmvae_forest_cv``, csrc/forest.hip; DESIGN.md section
+9i).  ``forest_cv_predict`` is the function under it; it is seeded and gives the same bits on every run, which the
+reference's own call does not.
+
+``K_selection`` of that module is not part of this package, and neither are ``custom_QDA`` and ``predict_leaf_gmm`` of
+``analysis_tree_helpers.py``."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -392,3 +398,157 @@ def LDA_classifier(data, labels, kfold, seed):
     """The reference's ``LDA_classifier`` (cluster_analysis.py:38-59): as ``QDA_classifier`` with
     ``gaussian_cv_predict(kind="lda")``."""
     return _classifier(data, labels, kfold, seed, "lda")
+
+
+# ---- the random forest ----------------------------------------------------------------------------------------------------
+FOREST_TREES = 100              # sklearn's RandomForestClassifier(n_estimators=100), the reference's default forest
+
+
+def _bins_on_device(x_dev: torch.Tensor) -> torch.Tensor:
+    """uint8 [n, d] on the device: per column, (the rank of a value's first occurrence in the sorted column * 256) // n."""
+    n, d = (int(v) for v in x_dev.shape)
+    sv, idx = torch.sort(x_dev + 0.0, dim=0, stable=True)                            # (+ 0.0: -0.0 becomes 0.0, one key)
+    pos = torch.arange(n, dtype=torch.int64, device=x_dev.device).unsqueeze(1).repeat(1, d)
+    pos[1:][sv[1:] == sv[:-1]] = 0
+    first = torch.cummax(pos, dim=0).values
+    out = torch.empty(n, d, dtype=torch.uint8, device=x_dev.device)
+    out.scatter_(0, idx, ((first * N.FOREST_BINS) // n).to(torch.uint8))
+    return out
+
+
+def quantile_bins(x, device=None) -> torch.Tensor:
+    """The forest's features: uint8 [n, d] on the device, per column ``bin = (r * 256) // n`` with r the rank of the value's
+    first occurrence in the stably sorted column.  Equal values share a bin (-0.0 == 0.0), bins rise with the values, and
+    with n <= 256 every distinct value has its own bin.  Integer arithmetic on ranks: the host restatement gives the same
+    entries.  ``x`` as for ``silhouette_samples`` (FLOAT64 INPUT IS ROUNDED to float32 first); ValueError on NaN or
+    infinity.  The sort is ``torch.sort`` on the device."""
+    return _bins_on_device(_points_on_device(x, device))
+
+
+def _forest_shape_of(x):
+    if not hasattr(x, "shape"):
+        x = np.asarray(x)
+    if len(x.shape) != 2:
+        raise ValueError(f"x of shape {tuple(x.shape)} is not [n, d]")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= d <= N.FOREST_MAX_D:
+        raise NotImplementedError(f"d = {d} outside [1, {N.FOREST_MAX_D}]")
+    if n > N.FOREST_MAX_N:
+        raise NotImplementedError(f"n = {n} above {N.FOREST_MAX_N}")
+    return n, d
+
+
+def _forest_refusals(labels, n, d, kfold, seed, n_trees, max_features):
+    """(classes, codes, fold, mtry) after every refusal that needs no device."""
+    y = np.asarray(labels)
+    if y.ndim != 1:
+        raise ValueError(f"labels of shape {y.shape} are not 1-D")
+    if y.shape[0] != n:
+        raise ValueError(f"{y.shape[0]} labels for {n} samples")
+    if int(kfold) != kfold or not 2 <= kfold <= n:
+        raise ValueError(f"kfold = {kfold} outside [2, n = {n}]")
+    if int(n_trees) != n_trees or n_trees < 1:
+        raise ValueError(f"n_trees = {n_trees} below 1")
+    if max_features == "sqrt":
+        mtry = max(1, int(np.floor(np.sqrt(d))))
+    elif isinstance(max_features, (int, np.integer)) and 1 <= max_features <= d:
+        mtry = int(max_features)
+    else:
+        raise ValueError(f"max_features = {max_features!r}: 'sqrt' or an int in [1, d = {d}]")
+    classes, codes = np.unique(y, return_inverse=True)
+    if len(classes) < 2:
+        raise ValueError(f"The number of classes has to be greater than one; got {len(classes)} class")
+    if len(classes) > N.FOREST_MAX_K or kfold > N.FOREST_MAX_F or n_trees > N.FOREST_MAX_T:
+        raise NotImplementedError(f"{len(classes)} classes, {kfold} folds and {n_trees} trees: at most {N.FOREST_MAX_K}, "
+                                  f"{N.FOREST_MAX_F} and {N.FOREST_MAX_T}")
+    return classes, codes.reshape(-1), kfold_of(n, int(kfold), seed), mtry
+
+
+def _forest_on_device(bins_dev, checked, kfold, n_trees, forest_seed, return_votes=False, return_trees=False):
+    """The launches, for bins already on the device."""
+    classes, codes, fold, mtry = checked
+    dev = bins_dev.device
+    label, best, second, votes, trees = N.forest_cv(bins_dev, torch.from_numpy(codes.astype(np.int32)).to(dev),
+                                                    torch.from_numpy(fold.astype(np.int32)).to(dev), len(classes), int(kfold),
+                                                    int(n_trees), mtry, forest_seed, return_votes, return_trees)
+    out = {"pred": label.cpu().numpy().astype(np.int64), "fold": fold, "best": best.cpu().numpy(),
+           "second": second.cpu().numpy(), "classes": classes}
+    if return_votes:
+        out["votes"] = votes.cpu().numpy()
+    if return_trees:
+        out["trees"] = {"count": trees["count"].cpu().numpy(), "nodes": trees["nodes"].cpu().numpy()}
+    return out
+
+
+def forest_cv_predict(x, labels, kfold, seed, n_trees=FOREST_TREES, max_features="sqrt", forest_seed=None, return_votes=False,
+                      return_trees=False, device=None):
+    """k-fold cross-validated prediction of ``labels`` from the points ``x`` by a random forest, every cell voted on by the
+    ``n_trees`` trees grown on the folds it is not in (``mmvae_forest_cv``, csrc/forest.hip; the contract is stated in
+    include/mmvae.h and DESIGN.md section 9i).
+
+    The forest is sklearn's ``RandomForestClassifier(n_estimators=n_trees)``: bootstrap samples of the training rows, at every
+    node ``max_features`` ("sqrt": max(1, floor(sqrt(d))); or an int in [1, d]) features drawn without replacement -- more
+    while none of them can split --, the Gini-best split among them, the midpoint between adjacent training values as the
+    threshold, trees grown until the leaves are pure.  DEPARTURES from sklearn: (1) the features are their 256 rank bins
+    (``quantile_bins``), so thresholds are bin boundaries and not exact values; (2) every tree casts one hard vote, where
+    sklearn averages the trees' leaf distributions -- the two are equal where leaves are pure, which they are unless rows
+    with different labels share every bin; (3) the random numbers are Philox4x32-10 streams keyed by ``forest_seed``, not
+    MT19937; (4) the forest is seeded: ``forest_seed`` defaults to ``seed``, and the same inputs give the same bits on every
+    run, where the reference's ``RandomForestClassifier()`` draws from numpy's global state.
+
+    ``x``: array-like or tensor [n, d], d <= 128; a float32 tensor on the GPU is used where it lies, anything else is
+    ROUNDED to float32 and uploaded.  ``labels``: 1-D, ints or hashables, encoded by ``np.unique``; at most 128 classes.
+    The folds are those of ``KFold(n_splits=kfold, shuffle=True, random_state=seed)`` (``kfold_of``); a class absent from a
+    fold's training rows gets no votes in that fold.  Returns a dict: ``pred`` int64 [n] the predicted code
+    (``classes[pred]`` the label; the lowest code on ties), ``fold`` int64 [n], ``best`` and ``second`` int32 [n] the votes
+    of the prediction and the most votes among the other classes, ``classes``, with ``return_votes`` the int32 ``votes``
+    [n, K], and with ``return_trees`` ``trees`` = {"count": int32 [kfold * n_trees], "nodes": int32 [kfold * n_trees, 2 n,
+    4]}, tree f * n_trees + t the t-th of fold f, node j = (feature, thr, left child, rows) or (-1, class, 0, rows).
+
+    ValueError for fewer than two classes, ``kfold`` outside [2, n], ``n_trees`` < 1, a bad ``max_features``, a label length
+    mismatch, non-finite ``x``; NotImplementedError under a process group and past d = 128, 128 classes, 64 folds, 4096
+    trees a fold or 2^24 cells."""
+    if D.is_dist():
+        raise NotImplementedError("forest_cv_predict is not data-parallel: run it on one rank, outside the process group")
+    n, d = _forest_shape_of(x)
+    checked = _forest_refusals(labels, n, d, kfold, seed, n_trees, max_features)
+    bins_dev = _bins_on_device(_points_on_device(x, device))
+    return _forest_on_device(bins_dev, checked, kfold, n_trees, seed if forest_seed is None else forest_seed, return_votes,
+                             return_trees)
+
+
+def classify_forest_points(bins_dev, y, kfold, seed, n_trees, checked):
+    """One label set on bins already on the device: (acc, ref_labels, pred_labels, the ``forest_cv_predict`` dict), the first
+    three lists over the folds with every test set in ascending order of the cell index."""
+    y = np.asarray(y)
+    classes, fold = checked[0], checked[2]
+    res = _forest_on_device(bins_dev, checked, kfold, n_trees, seed)
+    acc, ref_labels, pred_labels = [], [], []
+    for f in range(int(kfold)):
+        test = np.flatnonzero(fold == f)
+        pred = classes[res["pred"][test]]
+        acc.append(float(np.average(y[test] == pred)))                             # sklearn's accuracy_score
+        pred_labels.append(pred)
+        ref_labels.append(y[test])
+    return acc, ref_labels, pred_labels, res
+
+
+def RF_classifier(data, labels, kfold, seed):
+    """The reference's ``RF_classifier`` (cluster_analysis.py:14-35): ``(acc, ref_labels, pred_labels)``, dicts over the keys
+    of the dict ``labels``, each a list over the folds of ``KFold(n_splits=kfold, random_state=seed, shuffle=True)``: the
+    accuracy (a Python float), the held-out cells' labels and their predictions, in the caller's label values and in
+    ascending order of the cell index.  ``data`` is uploaded and binned once for all keys (a float32 device tensor is used
+    where it lies; anything else is rounded to float32).  The forest is ``forest_cv_predict``'s with 100 trees and
+    ``forest_seed = seed``; its departures from sklearn's forest are stated there: 256 rank bins instead of exact
+    thresholds, hard votes instead of averaged leaf distributions, Philox instead of MT19937 streams, and a seeded forest
+    -- the reference's own call draws from numpy's global state and cannot be reproduced; this one can."""
+    if D.is_dist():
+        raise NotImplementedError("RF_classifier is not data-parallel: run it on one rank, outside the process group")
+    n, d = _forest_shape_of(data)
+    checked = {key: _forest_refusals(labels[key], n, d, kfold, seed, FOREST_TREES, "sqrt") for key in labels}   # before any device work
+    bins_dev = _bins_on_device(_points_on_device(data, None))
+    acc, ref_labels, pred_labels = {}, {}, {}
+    for key in checked:
+        acc[key], ref_labels[key], pred_labels[key], _ = classify_forest_points(bins_dev, labels[key], kfold, seed, FOREST_TREES,
+                                                                                 checked[key])
+    return acc, ref_labels, pred_labels

@@ -531,6 +531,66 @@ int mmvae_gauss_scores(const float *x, int64_t ld, int64_t n, int d, const int32
                        void *ws /* may be NULL */, size_t ws_bytes, int32_t *label, double *best, double *second,
                        double *scores /* NULL = not wanted */, void *stream);
 
+/* ---- random forest on 256-bin features (mmidas/utils/cluster_analysis.py: RF_classifier) ----
+ * A forest under k-fold cross-validation on features quantised to 256 rank bins.  All arithmetic is integer up to one fp64
+ * score per candidate split, so a tree is fixed by its inputs: bit-identical from run to run, independent of the order of
+ * the LDS atomics (which only add integers), and the tree that tests/forest_restatement.py grows on the host.
+ *
+ * mmvae_forest_cv.  Inputs, all on the device: bins uint8 row-major [n, ld], columns 0..d-1 used; codes int32 [n] in [0, K);
+ *   fold int32 [n] in [0, F).  T trees a fold, mtry in [1, d], a 64-bit seed.  Tree g = f T + t is trained on the n_f rows
+ *   whose fold is not f, taken in ascending row order (train_rows).  codes are clamped to [0, K - 1] and fold values, where a
+ *   row picks its trees, to [0, F - 1]: a bad table gives wrong values and no access outside the arrays.
+ *   Bins are the caller's; the package's quantile_bins gives, per column, bin = (r 256) // n with r the rank of a value's first
+ *   occurrence in the stably sorted column: equal values share a bin (-0.0 == 0.0), and with n <= 256 every distinct value
+ *   has its own.  They are computed once over all n rows, without labels, and shared by every fold and tree.
+ *   Randomness: philox4x32 (Philox4x32-10) with key = (seed's low word, seed's high word) and counter (i, g, node, stream);
+ *   the training step's noise counters are another entry point with another key.  Stream 0, node 0, is the bootstrap:
+ *   call i yields draws 4 i .. 4 i + 3 (its words in order), draw j picks row train_rows[(uint64(u_j) n_f) >> 32], n_f draws.
+ *   Stream 1 is the feature order of node `node`: a lazy Fisher-Yates over 0 .. d - 1; step s swaps position s with
+ *   s + ((uint64(u_s) (d - s)) >> 32), u_s word s & 3 of call i = s >> 2; the feature visited s-th is then at position s.
+ *   Nodes: node 0 is the root; a node that splits allocates its children at the next two indices, left then right; nodes
+ *   leave a stack onto which a split pushes right, then left -- so a node's index, which is the RNG's node field, is fixed
+ *   by the inputs.  No depth cap: stack and tables are sized by n.
+ *   Leaf: a node in which one class holds all rows, or in which, after all d features, none has two occupied bins.  Its
+ *   class is the class with the most rows, the lowest code on ties.
+ *   Split search: features in the drawn order; stop after mtry features once at least one candidate has been seen, else go
+ *   on up to d (sklearn's rule).  For a feature, L_k(b) = the node's rows of class k with bin <= b, R_k = tot_k - L_k.  A
+ *   candidate is an occupied bin b_lo that has a later occupied bin b_hi in the node.  SL2 = sum_k L_k^2 and SR2 = sum_k R_k^2
+ *   are exact in uint64;  score = double(SL2) / double(nL) + double(SR2) / double(nR): two IEEE divisions and one addition,
+ *   each rounded once, never contracted (n <= 2^24 keeps every operand an exact double).  Across features and bins a
+ *   strictly larger score wins, so the first best in (visiting order, lowest b_lo) stands, and the node splits there
+ *   whatever the gain (sklearn with min_impurity_decrease = 0).  thr = (b_lo + b_hi) >> 1; rows with bin <= thr go left:
+ *   sklearn's midpoint between adjacent training values.  Only counts enter a tree; the rows of a node are nevertheless
+ *   partitioned stably (left rows, then right rows, each in their order) between two index lists.
+ *   Prediction: a row of fold f walks the T trees of fold f; each casts one hard vote, an integer; label = the class with the
+ *   most votes, the lowest code on ties.  A class absent from a fold's training rows gets no votes in that fold.
+ *   Outputs, on the device: label int32 [n]; best and second int32 [n], the votes of the label and the most votes among the
+ *   other classes (0 where there are none); votes int32 [n, K] or NULL.  tree_count int32 [F T] and tree_nodes int32
+ *   [F T, 2 n, 4], both or neither NULL: tree g has tree_count[g] <= 2 n_f - 1 nodes, node j = (feature, thr, left child,
+ *   rows) for a split (the right child is left + 1) and (-1, class, 0, rows) for a leaf, rows the node's bootstrap rows;
+ *   entries past the count are not written.  A fold that holds every row leaves its trees one leaf of class 0 and 0 rows.
+ *   Departures from sklearn's RandomForestClassifier: 256 rank bins instead of exact thresholds; hard votes instead of
+ *   averaged leaf distributions (equal where leaves are pure); Philox instead of MT19937 streams; the forest is seeded.
+ *   Kernels: one workgroup of 256 threads grows one tree.  Per node and feature a uint32 histogram [present classes][256]
+ *   in LDS (up to 128 KiB of dynamic LDS), filled by LDS integer atomics; a wave takes every fourth present class, a lane
+ *   four consecutive bins (one 16-byte read, conflict-free) and the prefix is a wave scan; bin b's thread adds the waves'
+ *   partial SL2, SR2 and nL, scores its candidate, and the workgroup takes the arg-max under the total order (score, then
+ *   lowest bin).  Classes with no row in the node cost nothing, so small nodes are cheap on the one path there is (no
+ *   debug entry).  Prediction: one launch a chunk, a wave a row, a lane a tree.  The trees are grown in chunks of launches
+ *   of at most 2^30 bytes of per-tree tables (56 n + 4 bytes a tree, at least one tree); votes add across chunks.
+ *   ws: mmvae_forest_workspace_bytes(n, d, F, K, T) bytes of device memory, 16-byte aligned: with c = min(F T,
+ *   max(1, 2^30 // (56 n + 4))) trees a chunk, c (56 n + 4) + 4 n F + 4 n K + 4 F bytes rounded up to 16 (node tables, stacks
+ *   and index lists of a chunk, the folds' training rows, the votes, the counts); 0 for arguments that mmvae_forest_cv
+ *   refuses.  1.01 GiB at n = 22365, F = 10, K = 92, T = 100 (two chunks, of 857 and 143 trees).
+ *   MMVAE_E_BADARG, before any device work, for a null bins / codes / fold / ws / label / best / second, one of tree_count /
+ *   tree_nodes without the other, n < 2, d < 1, K < 2, F < 2, T < 1, mtry outside [1, d], ld < d, a misaligned ws;
+ *   MMVAE_E_UNSUPPORTED for n > 2^24, d > 128, K > 128, F > 64 or T > 4096; MMVAE_E_WORKSPACE for a ws below the size. */
+size_t mmvae_forest_workspace_bytes(int64_t n, int d, int F, int K, int T);
+int mmvae_forest_cv(const uint8_t *bins, int64_t ld, int64_t n, int d, const int32_t *codes, const int32_t *fold, int K,
+                    int F, int T, int mtry, uint64_t seed, void *ws, size_t ws_bytes, int32_t *label, int32_t *best,
+                    int32_t *second, int32_t *votes /* NULL = not wanted */, int32_t *tree_count /* NULL = not wanted */,
+                    int32_t *tree_nodes /* NULL = not wanted */, void *stream);
+
 /* ---- principal components (mmidas/utils/cluster_analysis.py: cluster_compare's PCA) ----
  * The top-k principal subspace of an fp32 matrix needs three dense products: the covariance (once), the covariance times a
  * block of at most 64 vectors (once per step of a subspace iteration, which the host drives), and the centred data times the
