@@ -1,6 +1,7 @@
 """The switch points of make_plan (csrc/api.hip) as one table: shapes that sit on either side of every shape rule, and the
-plan each of them must take on each GEMM engine.  Used by tests/test_plan_cpu.py (the plan read-back, host only) and
-tests/test_gpu_plan_matrix.py (the same rows on the GPU: plan first, then the numbers).
+plan each of them must take on each GEMM engine.  Used by tests/test_plan_cpu.py (the plan read-back, host only),
+tests/test_gpu_plan_matrix.py (the same rows on the GPU: plan first, then the numbers) and tests/test_gpu_noside.py (the rows
+of NOSIDE_GPU on engines built without a side stream: `without_side()` of the same plans, then the numbers).
 
 A new `Plan` field or shape rule comes with a row here.
 
@@ -50,11 +51,24 @@ ROWS = [
     _r("b129", 2, 129, 256, 100), _r("b385", 2, 385, 256, 100),
     _r("xdrop0", 2, 300, 520, 100, x_drop=0.0),
     _r("sdrop_hard", 3, 130, 192, 100, hard=True, s_drop=0.2),
-    # planner only (the GPU matrix runs its engines with their side stream): the step without one
+    # the step without a side stream, as a literal row (every other row's plan without one: without_side(); on the GPU:
+    # NOSIDE_GPU, tests/test_gpu_noside.py)
     _r("noside", 2, 300, 520, 100, side=False),
 ]
 BY_NAME = {r.name: r for r in ROWS}
 GPU_ROWS = [r for r in ROWS if r.side]
+# The rows the GPU runs on engines WITHOUT a side stream (tests/test_gpu_noside.py), the smallest shapes that reach each thing
+# make_plan does differently then:
+#   h100         FC11_ZG / FC11_BF16 / FC11_X3 without a riding fork; dW11 inline behind dW1
+#   h104         engine 0: FC11_ZT, d(d10) as a launch of its own
+#   h112         fp32x3: [d10 | 1] planes written, fc11 on the fp32 pair
+#   a4           planes engines: COUPLE_IN_DEC with a side stream becomes the inline k_couple
+#   lat_c97_b57  wave-form latent kernels, ragged batch
+#   b129         ragged row tiles; dw11_slabs 5
+#   xdrop0       ZERO_MEMSET, no head fill
+#   sdrop_hard   A = 3, hard samples, state dropout
+#   h102         general path: COUPLE_SIDE joined on the main stream becomes inline
+NOSIDE_GPU = ("h100", "h104", "h112", "a4", "lat_c97_b57", "b129", "xdrop0", "sdrop_hard", "h102")
 
 # ---- the fused step's plan, by hand -----------------------------------------------------------------------------------
 # engine 0, fast path, fc_dim 100: d(d10) folded into the fc11 kernel, keep-mask bit image, everything fp32
@@ -201,6 +215,13 @@ def expected(row, engine, kind, has_x16=False):
         p["dec_planes"] = p["d10_planes"] or p["chain_planes"]
     p["kind"] = {"FORWARD_XREC": "FORWARD"}.get(kind, kind)
     return p
+
+
+def without_side(plan):
+    """`plan` (of any kind) as make_plan builds it for an mmvae_exec without a side stream: nothing runs beside the main
+    stream and no fork event has a kernel to ride on; every other field is unchanged.  By hand from make_plan's text (`side`
+    enters dw11_side, loss_on_side and couple; the two riding forks follow from those)."""
+    return dict(plan, dw11_side=False, loss_on_side=False, couple="COUPLE_INLINE", lat_fork_rides=False, fc11_fork_rides=False)
 
 
 def plan_args(row, kind):

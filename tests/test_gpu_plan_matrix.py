@@ -21,6 +21,9 @@ path fails here, whatever its numbers), then the numbers of that path:
   * the eval-mode forward and eval_classify on the width and latent rows against the fp64 oracle: labels equal but for at
     most plan_cases.EVAL_LABEL_CAP cells, the forward's outputs at the gates of test_golden_eval_forward.
 
+The engines here have their side stream; tests/test_gpu_noside.py runs the rows plan_cases.NOSIDE_GPU on engines without
+one, through this module's helpers (`side=False`).
+
 The engines are driven through _native.Engine directly (as tests/test_gpu_batchsums.py does): the Python boundary cannot hand
 the library a misaligned pointer.
 """
@@ -39,7 +42,14 @@ ENGINES = list(P.ENGINES)
 ROW_IDS = [r.name for r in P.GPU_ROWS]
 
 
-def _env(row, engine, seed=546):
+def _no_side_stream(monkeypatch):
+    """The switch of the Python layer that builds engines without a side stream (_native.Engine reads it when it is built)."""
+    monkeypatch.setenv("MMVAE_SIDE_STREAM", "0")
+
+
+def _env(row, engine, seed=546, side=True, monkeypatch=None):
+    """side=False: the engine is built under MMVAE_SIDE_STREAM=0, set through pytest's `monkeypatch` (the test's fixture; a
+    caller without one -- a result shared between tests -- gets a context of its own, undone once the engine exists)."""
     from tests import gpu_util as U
     h = R.Hyper(input_dim=row.D, fc_dim=row.H, n_categories=row.C, state_dim=row.S, lowD_dim=row.L, x_drop=row.x_drop,
                 s_drop=row.s_drop, n_arm=row.A, hard=row.hard)
@@ -49,8 +59,14 @@ def _env(row, engine, seed=546):
     m = U.build_model(h, sd)
     m.train()
     m.gemm_dtype = engine
-    eng = m._ensure(row.B)
-    assert eng.side is not None, "the matrix pins the plans of an engine with its side stream"
+    if side:
+        eng = m._ensure(row.B)
+        assert eng.side is not None, "the matrix pins the plans of an engine with its side stream"
+    else:
+        with (pytest.MonkeyPatch.context() if monkeypatch is None else monkeypatch.context()) as mp:
+            _no_side_stream(mp)
+            eng = m._ensure(row.B)
+        assert eng.side is None and not eng.ex.side_stream, "MMVAE_SIDE_STREAM=0 builds an engine without a side stream"
     return U, h, sd, x, noise, m, eng
 
 
@@ -77,14 +93,18 @@ def _place(m, x, misalign):
     return params, xd, xs
 
 
-def _assert_plan(row, engine, eng, hyper, params, xd, xs, kind="STEP", fields=None):
+def _assert_plan(row, engine, eng, hyper, params, xd, xs, kind="STEP", fields=None, side=True):
     """The live engine's plan for `kind` (a kind of plan_cases.KINDS) equals the table's; `fields`: only these (an engine
-    whose A or B differ from the row's, as decode's)."""
+    whose A or B differ from the row's, as decode's); side=False: an engine without a side stream, held to
+    plan_cases.without_side() of the table's plan."""
     from distributed_vae_amd import _native as N
     got = N.debug_plan(eng.dims, hyper, eng.ex, {"FORWARD_XREC": "FORWARD"}.get(kind, kind),
                        params_align=params.data_ptr() % 16 or 16, x_align=xd.data_ptr() % 16 or 16, x_arm_stride=xs,
                        fc11_grad=kind != "FORWARD_XREC")
     want = P.expected(row, engine, kind)
+    if not side:
+        assert not eng.ex.side_stream
+        want = P.without_side(want)
     if not hyper.training:
         want["zero"] = "ZERO_NONE"                       # eval mode: nothing accumulates, no head fill
     if not fields:
@@ -149,15 +169,15 @@ def _same_to_api_gates(a, b, what):
             assert float(ga[k].abs().max()) == 0.0, (what, k)
 
 
-@pytest.mark.parametrize("engine", ENGINES)
-@pytest.mark.parametrize("name", ROW_IDS)
-def test_plan_then_fused_step_against_oracle(name, engine):
+def _plan_then_fused_step_against_oracle(name, engine, side=True, monkeypatch=None):
+    """The row's plan on the live engine, then its fused step (no Adam, explicit noise) against the oracle, at the gates the
+    module's docstring names.  side=False: the same on an engine without a side stream (tests/test_gpu_noside.py)."""
     row = P.BY_NAME[name]
-    U, h, sd, x, noise, m, eng = _env(row, engine)
+    U, h, sd, x, noise, m, eng = _env(row, engine, side=side, monkeypatch=monkeypatch)
     A = row.A
     noise_dev = U.noise_to_device(noise)
     params, xd, xs = _place(m, x, row.misalign)
-    plan = _assert_plan(row, engine, eng, m._hyper(1.0, False), params, xd, xs)
+    plan = _assert_plan(row, engine, eng, m._hyper(1.0, False), params, xd, xs, side=side)
     state0 = (m._bn_flat.clone(), m._nbt.clone())
     buf, g = _fused(m, eng, noise_dev, params, xd, xs, state0)
     assert bool(torch.isfinite(buf).all()) and bool(torch.isfinite(g).all())
@@ -209,6 +229,12 @@ def test_plan_then_fused_step_against_oracle(name, engine):
         for k, e_gpu in noisy.items():
             assert e_gpu < 3.0 * floor, (k, e_gpu, floor)
     U.assert_gradients_tight(live, fo, GRAD_TOL)
+
+
+@pytest.mark.parametrize("engine", ENGINES)
+@pytest.mark.parametrize("name", ROW_IDS)
+def test_plan_then_fused_step_against_oracle(name, engine):
+    _plan_then_fused_step_against_oracle(name, engine)
 
 
 GENERAL = [r.name for r in P.GPU_ROWS if not P.STEP[r.name]["fp32_mfma"]["fast"]]
@@ -277,13 +303,21 @@ def test_general_path_fused_step_matches_api_path(name, engine):
                 U.assert_gradients_tight(_named(m, g0), fo, GRAD_TOL)
 
 
-def _two_adam_steps(row, engine, h, sd, data, rows, indexed):
+def _two_adam_steps(row, engine, h, sd, data, rows, indexed, side=True, weight_decay=0.0, decoupled=False):
+    """Two fused Adam steps on explicit noise: [loss vectors, parameters, gradients, running statistics, exp_avg, exp_avg_sq].
+    side=False: on an engine without a side stream (one k_reduce launch with the update fused in over all tensors, not the
+    fc11 tensors' on the side stream and the rest's on the main one)."""
     from tests import gpu_util as U
     from distributed_vae_amd.cpl_mixvae import FusedAdam
     m = U.build_model(h, sd)
     m.train()
     m.gemm_dtype = engine
-    opt = FusedAdam(m, lr=1e-3)
+    with pytest.MonkeyPatch.context() as mp:
+        if not side:
+            _no_side_stream(mp)
+        eng = m._ensure(row.B)
+    assert (eng.side is not None) == side and bool(eng.ex.side_stream) == side
+    opt = FusedAdam(m, lr=1e-3, weight_decay=weight_decay, decoupled=decoupled)
     bufs = []
     for s in range(2):
         m.set_explicit_noise(U.noise_to_device(R.draw_noise(h, row.B, seed=40 + s)))
@@ -293,8 +327,9 @@ def _two_adam_steps(row, engine, h, sd, data, rows, indexed):
         else:
             bufs.append(m.fused_train_step(data[r].contiguous().expand(row.A, -1, -1), 1.0, opt, do_adam=True).clone())
     torch.cuda.synchronize()
+    assert m._engine is eng and opt.step_count == 2
     return [torch.stack(bufs).cpu(), m.flat_parameters().detach().cpu().clone(), m._flat_grad.detach().cpu().clone(),
-            m._bn_flat.detach().cpu().clone()]
+            m._bn_flat.detach().cpu().clone(), opt.exp_avg.detach().cpu().clone(), opt.exp_avg_sq.detach().cpu().clone()]
 
 
 @pytest.mark.parametrize("engine", ["bf16", "fp32x3"])

@@ -1,6 +1,7 @@
 """CPU (no GPU): make_plan's decision table, read back through mmvae_debug_plan (host only) and held to tests/plan_cases.py.
 
   * every (row, engine, call kind) of the table returns exactly its hand-written plan;
+  * the same without a side stream: plan_cases.without_side() of that plan, on the same split factors and workspace size;
   * closure: over the table, the fused step reaches every kernel family, zero fill, coupling placement and both values of
     every bool -- or the value is named in UNREACHABLE with its reason, and a brute-force sweep proves it never appears;
   * the invariants make_plan states in its comments hold over the same sweep.
@@ -36,12 +37,16 @@ def _splits(dims, ex):
     return list(sp)
 
 
-def _check(row, engine, kind, has_x16=False):
+def _check(row, engine, kind, has_x16=False, side=None):
+    """side: None -- the exec has a side stream where the row says so; False -- it has none, and the plan is
+    plan_cases.without_side() of the row's."""
     d = N.Dims(row.A, row.B, row.D, row.H, row.L, row.C, row.S)
-    ex = _exec(engine, row.side)
+    ex = _exec(engine, row.side if side is None else side)
     training = 0 if kind in ("DECODE", "TRAVERSE") else 1   # (CLASSIFY too is planned in eval mode whatever it is handed)
     got = N.debug_plan(d, _hyper(row, engine, training), ex, has_x16=has_x16, **P.plan_args(row, kind))
     want = P.expected(row, engine, kind, has_x16)
+    if side is False:
+        want = P.without_side(want)
     sp = _splits(d, ex)
     i_gd10, i_dw11 = P.slab_sources(want)
     want["gd10_slabs"], want["dw11_slabs"] = sp[i_gd10], sp[i_dw11]
@@ -58,6 +63,45 @@ def _check(row, engine, kind, has_x16=False):
 def test_every_row_takes_its_hand_written_plan(row, engine):
     for kind in P.KINDS:
         _check(row, engine, kind)
+
+
+SIDE_ROWS = [r for r in P.ROWS if r.side]
+
+
+@pytest.mark.parametrize("engine", list(P.ENGINES))
+@pytest.mark.parametrize("row", SIDE_ROWS, ids=lambda r: r.name)
+def test_every_row_without_a_side_stream_takes_without_side_of_its_plan(row, engine):
+    """An mmvae_exec without a side stream: every call kind's plan is the row's with exactly the five fields
+    plan_cases.without_side() names changed; the slab counts are the same split factors."""
+    for kind in P.KINDS:
+        _check(row, engine, kind, side=False)
+
+
+def test_without_side_is_the_literal_noside_row():
+    for engine in P.ENGINES:
+        assert P.STEP["noside"][engine] == P.without_side(P.STEP["h100"][engine]), engine
+        assert P.without_side(P.STEP["noside"][engine]) == P.STEP["noside"][engine], engine
+    assert P.BY_NAME["noside"]._replace(name="h100", side=True) == P.BY_NAME["h100"]
+    assert set(P.NOSIDE_GPU) <= {r.name for r in P.GPU_ROWS} and len(set(P.NOSIDE_GPU)) == len(P.NOSIDE_GPU) == 9
+
+
+@pytest.mark.parametrize("engine", list(P.ENGINES))
+@pytest.mark.parametrize("row", P.ROWS, ids=lambda r: r.name)
+def test_splits_and_workspace_do_not_depend_on_the_side_stream(row, engine):
+    """default_splits and make_layout do not read mmvae_exec.side_stream: the same split factors and the same workspace size
+    with and without one (and without an exec at all on engine 0, whose tune[] is all zeros).  The bit-identity checks of
+    tests/test_gpu_noside.py rest on this: the same number of slabs summed in the same order on either engine."""
+    d = N.Dims(row.A, row.B, row.D, row.H, row.L, row.C, row.S)
+    L = N.lib()
+    with_side, without = _exec(engine, True), _exec(engine, False)
+    assert with_side.side_stream and not without.side_stream
+    assert _splits(d, with_side) == _splits(d, without), (row.name, engine)
+    nbytes = [int(L.mmvae_workspace_bytes(C.byref(d), C.byref(ex))) for ex in (with_side, without)]
+    assert nbytes[0] == nbytes[1] > 0, (row.name, engine, nbytes)
+    if engine == "fp32_mfma":
+        sp = (C.c_int32 * 6)()
+        assert L.mmvae_splits(C.byref(d), None, C.byref(sp)) == 0
+        assert list(sp) == _splits(d, without) and int(L.mmvae_workspace_bytes(C.byref(d), None)) == nbytes[1]
 
 
 def test_table_is_complete():
