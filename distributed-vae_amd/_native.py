@@ -9,6 +9,7 @@ import ctypes as C
 import os
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -219,6 +220,9 @@ def lib():
     L.mmvae_gauss_scores_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_gauss_scores_workspace_bytes.restype = C.c_size_t
     L.mmvae_gauss_scores.argtypes = [vp, i64, i64, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.mmvae_leaf_merge_workspace_bytes.argtypes = [i64, i32, i32]
+    L.mmvae_leaf_merge_workspace_bytes.restype = C.c_size_t
+    L.mmvae_leaf_merge.argtypes = [vp, i64, i64, i32, vp, i32, vp, i64, i32, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, i32, vp]
     L.mmvae_forest_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     L.mmvae_forest_workspace_bytes.restype = C.c_size_t
     L.mmvae_forest_cv.argtypes = [vp, i64, i64, i32, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
@@ -931,6 +935,63 @@ def gauss_scores(x: torch.Tensor, model: torch.Tensor, mu: torch.Tensor, W: torc
                                    None, 0, _ptr(label), _ptr(best), _ptr(second), _ptr(scores), _stream(xs.device)),
           "mmvae_gauss_scores")
     return label, best, second, scores
+
+
+# launch_leaf_merge (csrc/leafmerge.hip; the constants are those of csrc/common.hpp)
+LEAFMERGE_WAVES = 4             # LM_WAVES: waves per workgroup of both kernels, one cell a wave
+LEAFMERGE_MAX_L, LEAFMERGE_MAX_K, LEAFMERGE_MAX_T = GAUSSCLF_MAX_K, 4096, 4096
+
+
+def merge_tables(levels):
+    """The three int32 tables of ``mmvae_leaf_merge`` from ``levels``, a list over the merge levels of lists over the labels
+    of lists of leaf indices -> (level_start [T + 1], start [K_total + 1], leaf [nnz]), numpy arrays on the host."""
+    level_start, start, leaf = [0], [0], []
+    for labels in levels:
+        for members in labels:
+            leaf.extend(int(v) for v in members)
+            start.append(len(leaf))
+        level_start.append(len(start) - 1)
+    return np.array(level_start, dtype=np.int32), np.array(start, dtype=np.int32), np.array(leaf, dtype=np.int32)
+
+
+def leaf_merge(p: torch.Tensor, level_start, start, leaf, return_second: bool = True, return_merged: bool = False):
+    """mmvae_leaf_merge: the float64 scores ``p`` [n, L] on the GPU (rows may be strided, columns not; -inf for a leaf without
+    a model) BECOME THE POSTERIORS IN PLACE, and the merge tables (``merge_tables``; int arrays on the host, uploaded here)
+    -> (label int32 [T, n], prob float64 [T, n], second float64 [T, n] or None, merged float64 [n, K_0] or None) on the
+    device: per level the arg-max over its labels of the posteriors added over each label's leaves, that sum, the largest
+    sum among the other labels, and every sum of level 0.  The tables are checked here, where they can be read: ValueError
+    unless they are non-decreasing from 0, every level has a label and every leaf is a column of ``p``."""
+    _need_cuda("leaf_merge", p)
+    if p.dtype != torch.float64 or p.dim() != 2:
+        raise TypeError("leaf_merge: p must be float64 [n, L]")
+    if p.shape[1] > 1 and p.stride(1) != 1 or p.shape[0] > 1 and p.stride(0) < p.shape[1]:
+        raise TypeError("leaf_merge: p is written in place: its columns must be contiguous")
+    n, L = (int(v) for v in p.shape)
+    ls, st, lf = (np.asarray(a) for a in (level_start, start, leaf))
+    if any(a.ndim != 1 or (a.size and a.dtype.kind not in "iu") for a in (ls, st, lf)) or ls.size < 2 or st.size < 2:
+        raise TypeError("leaf_merge: level_start [T + 1], start [K_total + 1] and leaf [nnz] must be 1-D integer arrays")
+    ls, st, lf = ls.astype(np.int64), st.astype(np.int64), lf.astype(np.int64)
+    T, K_total, nnz = ls.size - 1, st.size - 1, lf.size
+    sizes = np.diff(ls)
+    if ls[0] != 0 or ls[-1] != K_total or (sizes < 1).any():
+        raise ValueError("leaf_merge: level_start must rise from 0 to the number of labels, every level with a label")
+    if st[0] != 0 or st[-1] != nnz or (np.diff(st) < 0).any():
+        raise ValueError("leaf_merge: start must be non-decreasing from 0 to the number of leaf entries")
+    if nnz and (lf.min() < 0 or lf.max() >= L):
+        raise ValueError(f"leaf_merge: a leaf index outside [0, L = {L})")
+    dev = p.device
+    i32 = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev)
+    d_ls, d_st = i32(ls), i32(st)
+    d_lf = i32(lf) if nnz else torch.zeros(1, dtype=torch.int32, device=dev)
+    K_max, K0 = int(sizes.max()), int(sizes[0])
+    label = torch.empty(T, n, dtype=torch.int32, device=dev)
+    prob = torch.empty(T, n, dtype=torch.float64, device=dev)
+    second = torch.empty(T, n, dtype=torch.float64, device=dev) if return_second else None
+    merged = torch.empty(n, K0, dtype=torch.float64, device=dev) if return_merged else None
+    check(lib().mmvae_leaf_merge(_ptr(p), int(p.stride(0)) if n > 1 else max(L, 1), n, L, _ptr(d_ls), T, _ptr(d_st), K_total, K_max,
+                                 _ptr(d_lf), nnz, None, 0, _ptr(label), _ptr(prob), _ptr(second), _ptr(merged), K0,
+                                 _stream(dev)), "mmvae_leaf_merge")
+    return label, prob, second, merged
 
 
 # launch_forest (csrc/forest.hip; the constants are those of csrc/common.hpp)

@@ -872,6 +872,26 @@ class cpl_mixVAE:
         return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
                 "data_indx": data_indx}
 
+    @torch.no_grad()
+    def classify_tree(self, dl, labels, list_changes, leaves, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", levels=None):
+        """How well the cell types are recovered from arm ``arm``'s latents at EVERY resolution of the taxonomy: the
+        reference's ``predict_leaf_gmm`` (mmidas/utils/analysis_tree_helpers.py) under k-fold cross-validation and at all
+        merge levels of the dendrogram at once (``utils.analysis_tree_helpers.merge_sweep``).  ``labels``: one leaf label per row
+        of the data set; ``list_changes`` and ``leaves``: the merge sequence and the leaf names (``parse_dend``); ``levels``:
+        the numbers of merges to evaluate (default: every one that leaves at least two labels).  ``dl``, ``arm`` and ``on`` as
+        for ``classify_latents``; the latents never leave the device.  Every cell is scored under the leaf Gaussians fitted to
+        the folds it is not in (``kfold_of``): one ``mmvae_group_moments`` launch, one ``mmvae_gauss_scores`` launch with
+        kfold models, one ``mmvae_leaf_merge``.  Returns ``{"n_classes" [T], "acc" [kfold, T], "pred" [T, n], "prob" [T, n],
+        "fold" [n], "data_indx"}`` and ``"levels"`` and ``"keep"`` [n]: the accuracy of a fold is over its kept cells, those
+        whose label is a leaf that has a model in their fold (NaN where a fold keeps none), in the loader's order."""
+        if D.is_dist():
+            raise NotImplementedError("classify_tree is not data-parallel: run it on one rank, outside the process group")
+        from .utils import analysis_tree_helpers as TH
+        points, y, data_indx = self._latents_to_classify(dl, labels, arm, on, "classify_tree")
+        res = TH.classify_tree_points(points, y, list_changes, leaves, kfold, seed, levels)
+        res["data_indx"] = data_indx
+        return res
+
     def _latents_to_classify(self, dl, labels, arm, on, who, also=()):
         """What ``classify_latents`` and ``classify_forest`` share: their refusals, the encode of ``dl`` on the device and the
         labels of the cells it serves -> (arm ``arm``'s latents ``on``, float32 [n, .] on the device; the cells' labels;

@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the Gaussian classifiers, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the Gaussian classifiers, the leaf merge, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -320,6 +320,46 @@ int mmvae_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int32
     }
     return launch_gauss_scores(x, ld, n, d, model, F, K, mu, W, c0, perm, label, best, second, scores,
                                reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- leaf posteriors merged up a tree (leafmerge.hip) ----
+// the kernels keep nothing between launches
+size_t mmvae_leaf_merge_workspace_bytes(int64_t n, int L, int T) {
+    (void)n; (void)L; (void)T;
+    return 0;
+}
+
+int mmvae_leaf_merge(double* p, int64_t ldp, int64_t n, int L, const int32_t* level_start, int T, const int32_t* start,
+                     int64_t K_total, int K_max, const int32_t* leaf, int64_t nnz, void* ws, size_t ws_bytes, int32_t* label,
+                     double* prob, double* second, double* merged, int K0, void* stream) {
+    const char* who = "leaf_merge";
+    if (!p || !level_start || !start || !leaf || !label || !prob) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, N_MAX)) return rc;
+    if (int rc = check_count(who, "L", L, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "T", T, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "K_max", K_max, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "K_total", K_total, 1, (int64_t)T * K_max)) return rc;
+    if (int rc = check_count(who, "nnz", nnz, 0, INT64_MAX)) return rc;
+    if (merged)
+        if (int rc = check_count(who, "K0", K0, 1, K_max)) return rc;
+    if (int rc = check_pitch(who, "ldp", ldp, "L", L)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;     // (a null workspace is aligned)
+    if (int rc = check_aligned(who, "p", p, sizeof(double))) return rc;
+    if (int rc = check_aligned(who, "prob", prob, sizeof(double))) return rc;
+    if (int rc = check_aligned(who, "second", second, sizeof(double))) return rc;
+    if (int rc = check_aligned(who, "merged", merged, sizeof(double))) return rc;
+    if (int rc = check_aligned(who, "label", label, sizeof(int32_t))) return rc;
+    if (int rc = check_aligned(who, "level_start", level_start, sizeof(int32_t))) return rc;
+    if (int rc = check_aligned(who, "start", start, sizeof(int32_t))) return rc;
+    if (int rc = check_aligned(who, "leaf", leaf, sizeof(int32_t))) return rc;
+    if (L > LM_MAX_L || K_max > LM_MAX_K || T > LM_MAX_T) {
+        set_error("%s: L = %d, K_max = %d, T = %d above %d, %d, %d", who, L, K_max, T, LM_MAX_L, LM_MAX_K, LM_MAX_T);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (nnz > INT32_MAX) { set_error("%s: nnz = %lld at or above 2^31", who, (long long)nnz); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_ws(who, ws_bytes, mmvae_leaf_merge_workspace_bytes(n, L, T))) return rc;
+    return launch_leaf_merge(p, ldp, n, L, level_start, T, start, (int)K_total, K_max, leaf, (int)nnz, label, prob, second, merged,
+                             merged ? K0 : 0, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- random forest on 256-bin features (forest.hip) ----

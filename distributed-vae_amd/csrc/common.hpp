@@ -1047,6 +1047,15 @@ int launch_group_moments(const float* x, int64_t ld, int64_t n, int d, const int
 int launch_gauss_scores(const float* x, int64_t ld, int64_t n, int d, const int* model, int F, int K, const double* mu,
                         const double* W, const double* c0, const int64_t* perm, int* label, double* best, double* second,
                         double* scores, hipStream_t st);
+// leaf posteriors merged up a tree (leafmerge.hip)
+constexpr int LM_WAVES = 4;            // waves per workgroup of k_lm_normalise and k_lm_merge: one cell a wave
+constexpr int LM_MAX_L = GC_MAX_K;     // leaves: the classes one mmvae_gauss_scores call can score
+constexpr int LM_MAX_K = 4096;         // labels of one merge level
+constexpr int LM_MAX_T = 4096;         // merge levels of one call
+constexpr int LM_MAX_GRID = 1 << 20;   // workgroups along the cells at most: a workgroup strides over the rest
+int launch_leaf_merge(double* p, int64_t ldp, int64_t n, int L, const int* level_start, int T, const int* start, int K_total,
+                      int K_max, const int* leaf, int nnz, int* label, double* prob, double* second, double* merged, int K0,
+                      hipStream_t st);
 // random forest on 256-bin features (forest.hip)
 constexpr int RF_THREADS = 256;        // threads of every workgroup: k_rf_fit one tree, k_rf_predict four rows (one a wave)
 constexpr int RF_BINS = 256;           // bins of a feature: one a thread of the candidate search, four a lane of the scan

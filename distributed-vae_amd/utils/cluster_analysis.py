@@ -24,8 +24,8 @@ feature a class x bin histogram of integers in LDS and a scan of it (``mmvae_for
 9i).  ``forest_cv_predict`` is the function under it; it is seeded and gives the same bits on every run, which the
 reference's own call does not.
 
-``K_selection`` of that module is not part of this package, and neither are ``custom_QDA`` and ``predict_leaf_gmm`` of
-``analysis_tree_helpers.py``."""
+``K_selection`` of that module is not part of this package.  ``custom_QDA`` and ``predict_leaf_gmm`` of the reference's
+``analysis_tree_helpers.py`` are in ``utils/analysis_tree_helpers.py``."""
 from __future__ import annotations
 
 from typing import Optional, Tuple

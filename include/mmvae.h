@@ -531,6 +531,53 @@ int mmvae_gauss_scores(const float *x, int64_t ld, int64_t n, int d, const int32
                        void *ws /* may be NULL */, size_t ws_bytes, int32_t *label, double *best, double *second,
                        double *scores /* NULL = not wanted */, void *stream);
 
+/* ---- leaf posteriors merged up a tree (mmidas/utils/analysis_tree_helpers.py: predict_leaf_gmm) ----
+ * One Gaussian per leaf type scores a cell (mmvae_gauss_scores with c0 = log weight - log-determinant terms); the cell's
+ * posterior over the L leaves is normalised in the log domain, and at every merge level of the dendrogram the posteriors
+ * of the leaves under each label are added and the label with the largest sum is the prediction.
+ *
+ * mmvae_leaf_merge: p double [n, ldp] on the device, columns 0..L-1 used.  On entry the scores s of the cell under the L
+ *   leaves, each finite or -inf (a leaf without a model); on return its posteriors.  The merge tables, int32 on the
+ *   device, cover T levels: level_start [T + 1], level t the labels level_start[t] .. level_start[t + 1] - 1 of start;
+ *   start [K_total + 1], label k the entries start[k] .. start[k + 1] - 1 of leaf; leaf [nnz] the leaves (columns of p) of
+ *   one label after the other.  A label's list may be empty (its sum is exactly 0) and the lists of a level may overlap.
+ *   K_max: the most labels of one level.  The host cannot read device memory without a synchronisation, so the tables'
+ *   contents are the CALLER'S CONTRACT: level_start and start non-decreasing from 0 to K_total and nnz, at least one
+ *   and at most K_max labels a level, leaves in [0, L).  Every index read from them is clamped to its array (a level's
+ *   labels to the first K_max), so a bad table gives wrong values and no access outside the arrays; a level without
+ *   labels gives label 0 and prob 0.
+ *   Out, all on the device, entry [t, r] level t's value for cell r: label int32 [T, n] the index of the predicted label
+ *   within its level; prob double [T, n] its sum; second double [T, n] or NULL, the largest sum among the level's other
+ *   labels (equal to prob on a tie), 0 where the level has one label; merged double [n, K0] or NULL, every sum of level 0
+ *   (K0 its number of labels; columns past the table's own count are 0).
+ *   Arithmetic per cell, all fp64: m = max_l s_l (exact); e_l = exp(s_l - m); Z = sum_l e_l, lane j of a wave of 64 adding
+ *   e_j, e_(j+64), ... in that order from 0.0, then z_j <- z_j + z_(j xor h) for h = 32, 16, 8, 4, 2, 1 (which is the
+ *   pairwise tree that adds halves: z[0:32] + z[32:64], then [0:16] + [16:32], ...); p_l = e_l / Z, a correctly rounded
+ *   division.  P_k = the p of label k's list added one by one in list order from 0.0, so that GIVEN THE POSTERIORS EVERY
+ *   SUM IS DEFINED TO THE BIT; label = the lowest index of the largest P_k, as np.argmax, prob as np.max (a NaN is above
+ *   every number).  Error of a posterior against exact arithmetic on the same scores (u = 2^-53): s_l - m carries one
+ *   rounding, at most u |s_l - m| <= 745 u in the exponent wherever e_l is not below the normal range; the device exp is
+ *   within 1 ulp (2 u); the L terms of Z, each within that and none negative, add to within (L + 2) u; the division adds
+ *   u: |p_l - exact| <= (745 + L + 8) u p_l + 2^-1070, the last term for an e_l below 2^-1022 (denormal, or exactly 0
+ *   from a spread above 745).  Two evaluations that form s_l - m alike (this one and tests/leafgmm_restatement.py) share
+ *   that rounding and differ by at most (2 L + 12) u p_l + 2^-1070.
+ *   A row of -inf only has s - m = NaN: NaN posteriors, NaN sums for every label with a leaf, label = the first of them
+ *   (0 where label 0 has a leaf), prob NaN -- what the reference's 0 / 0 followed by np.argmax gives.  A NaN or +inf
+ *   score gives a NaN row in the same way.
+ *   No atomics and no value shared between cells: bit-identical from run to run and equal to a call on the cell alone.
+ *   Levels do not build on each other: level t of a call is bit for bit a call with that level's table alone.
+ *   Two launches: one wave a cell (normalise), one wave a (cell, level) with lane j on the labels j, j + 64, ... (merge).
+ *   ws: mmvae_leaf_merge_workspace_bytes(n, L, T) = 0 bytes: ws may be NULL.
+ *   MMVAE_E_BADARG, before any device work, for a null p / level_start / start / leaf / label / prob, n < 1 or n > 2^31,
+ *   L < 1, T < 1, K_max < 1, K_total < 1 or K_total > T K_max, nnz < 0, K0 outside [1, K_max] where merged is given,
+ *   ldp < L, a pointer not aligned to its element; MMVAE_E_UNSUPPORTED for L > 4096 (the limit of mmvae_gauss_scores),
+ *   K_max > 4096, T > 4096 or nnz >= 2^31. */
+size_t mmvae_leaf_merge_workspace_bytes(int64_t n, int L, int T);
+int mmvae_leaf_merge(double *p, int64_t ldp, int64_t n, int L, const int32_t *level_start, int T, const int32_t *start,
+                     int64_t K_total, int K_max, const int32_t *leaf, int64_t nnz, void *ws /* may be NULL */, size_t ws_bytes,
+                     int32_t *label, double *prob, double *second /* NULL = not wanted */,
+                     double *merged /* NULL = not wanted */, int K0, void *stream);
+
 /* ---- random forest on 256-bin features (mmidas/utils/cluster_analysis.py: RF_classifier) ----
  * A forest under k-fold cross-validation on features quantised to 256 rank bins.  All arithmetic is integer up to one fp64
  * score per candidate split, so a tree is fixed by its inputs: bit-identical from run to run, independent of the order of
