@@ -223,6 +223,13 @@ def lib():
     L.mmvae_leaf_merge_workspace_bytes.argtypes = [i64, i32, i32]
     L.mmvae_leaf_merge_workspace_bytes.restype = C.c_size_t
     L.mmvae_leaf_merge.argtypes = [vp, i64, i64, i32, vp, i32, vp, i64, i32, vp, i64, vp, C.c_size_t, vp, vp, vp, vp, i32, vp]
+    L.mmvae_zinb_heads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.mmvae_zinb_nll_workspace_bytes.argtypes = [i64, i32]
+    L.mmvae_zinb_nll_workspace_bytes.restype = C.c_size_t
+    L.mmvae_zinb_nll.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, vp, C.c_size_t, vp, vp, vp]
+    L.mmvae_zinb_terms_workspace_bytes.argtypes = [i64, i32]
+    L.mmvae_zinb_terms_workspace_bytes.restype = C.c_size_t
+    L.mmvae_zinb_terms.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, vp, C.c_size_t, vp, vp, vp, i64, vp]
     L.mmvae_forest_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     L.mmvae_forest_workspace_bytes.restype = C.c_size_t
     L.mmvae_forest_cv.argtypes = [vp, i64, i64, i32, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
@@ -992,6 +999,92 @@ def leaf_merge(p: torch.Tensor, level_start, start, leaf, return_second: bool = 
                                  _ptr(d_lf), nnz, None, 0, _ptr(label), _ptr(prob), _ptr(second), _ptr(merged), K0,
                                  _stream(dev)), "mmvae_leaf_merge")
     return label, prob, second, merged
+
+
+# zero-inflated negative binomial inference (csrc/zinb.hip)
+ZINB_MAX_H = 128                # ZB_MAX_H: the K extent one LDS tile holds
+
+
+def _zinb_mat(what: str, name: str, t: torch.Tensor, cols: Optional[int] = None) -> torch.Tensor:
+    if t.dtype != torch.float32 or t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise TypeError(f"{what}: {name} must be float32 [n, {cols if cols is not None else 'width'}]; got {t.dtype} {tuple(t.shape)}")
+    return _row_major(t)
+
+
+def _zinb_pitch(t: torch.Tensor) -> int:
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def _zinb_layer(what: str, name: str, W: torch.Tensor, b: torch.Tensor, D: int, H: int):
+    if W.dtype != torch.float32 or b.dtype != torch.float32 or tuple(W.shape) != (D, H) or tuple(b.shape) != (D,):
+        raise TypeError(f"{what}: {name} must be a float32 weight [{D}, {H}] and bias [{D}]")
+    return W.contiguous(), b.contiguous()
+
+
+def zinb_heads(d10: torch.Tensor, Wp, bp, Wr, br):
+    """mmvae_zinb_heads: (sigmoid(d10 Wp^T + bp), sigmoid(d10 Wr^T + br)), float32 [N, D] each, from float32 d10 [N, H] on
+    the GPU (rows may be strided) and two ``nn.Linear`` layers' weight [D, H] and bias [D]."""
+    what = "zinb_heads"
+    _need_cuda(what, d10, Wp, bp, Wr, br)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(Wp.shape[0])
+    (Wp, bp), (Wr, br) = _zinb_layer(what, "fc11_p", Wp, bp, D, H), _zinb_layer(what, "fc11_r", Wr, br, D, H)
+    x_p = torch.empty(n, D, dtype=torch.float32, device=d10.device)
+    x_r = torch.empty_like(x_p)
+    with torch.cuda.device(d10.device):
+        check(lib().mmvae_zinb_heads(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(Wp), _ptr(bp), _ptr(Wr), _ptr(br), _ptr(x_p),
+                                     _ptr(x_r), D, _stream(d10.device)), "mmvae_zinb_heads")
+    return x_p, x_r
+
+
+def zinb_nll(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: float = 1e-6):
+    """mmvae_zinb_nll: the ZINB term of every element of X [N, D] under the three heads of d10 [N, H] (fc11: W, b; fc11_p: Wp,
+    bp; fc11_r: Wr, br), summed -> (cell_sum float64 [N], gene_sum float64 [D]) on the device; no head is written."""
+    what = "zinb_nll"
+    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(W.shape[0])
+    X = _zinb_mat(what, "X", X, D)
+    if X.shape[0] != n:
+        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
+    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
+                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
+    dev = d10.device
+    with torch.cuda.device(dev):
+        nbytes = int(lib().mmvae_zinb_nll_workspace_bytes(n, D))
+        ws = _workspace(nbytes, dev)
+        cell = torch.empty(n, dtype=torch.float64, device=dev)
+        gene = torch.empty(D, dtype=torch.float64, device=dev)
+        check(lib().mmvae_zinb_nll(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr), _ptr(br),
+                                   _ptr(X), _zinb_pitch(X), float(eps), _ptr(ws), nbytes, _ptr(cell), _ptr(gene), _stream(dev)),
+              "mmvae_zinb_nll")
+    return cell, gene
+
+
+def zinb_terms(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X: torch.Tensor, eps: float = 1e-6,
+               return_terms: bool = False):
+    """mmvae_zinb_terms: the ZINB term of every element from given heads (float32 [N, D] on the GPU, rows may be strided)
+    -> (cell_sum float64 [N], gene_sum float64 [D], terms float32 [N, D] or None) on the device."""
+    what = "zinb_terms"
+    _need_cuda(what, x_rec, x_p, x_r, X)
+    X = _zinb_mat(what, "X", X)
+    n, D = (int(v) for v in X.shape)
+    x_rec, x_p, x_r = (_zinb_mat(what, nm, t, D) for nm, t in (("rec_x", x_rec), ("x_p", x_p), ("x_r", x_r)))
+    if not (x_rec.shape[0] == x_p.shape[0] == x_r.shape[0] == n):
+        raise ValueError(f"{what}: the four matrices must have the same number of rows")
+    dev = X.device
+    with torch.cuda.device(dev):
+        nbytes = int(lib().mmvae_zinb_terms_workspace_bytes(n, D))
+        ws = _workspace(nbytes, dev)
+        cell = torch.empty(n, dtype=torch.float64, device=dev)
+        gene = torch.empty(D, dtype=torch.float64, device=dev)
+        terms = torch.empty(n, D, dtype=torch.float32, device=dev) if return_terms else None
+        check(lib().mmvae_zinb_terms(_ptr(x_rec), _zinb_pitch(x_rec), _ptr(x_p), _zinb_pitch(x_p), _ptr(x_r), _zinb_pitch(x_r),
+                                     _ptr(X), _zinb_pitch(X), n, D, float(eps), _ptr(ws), nbytes, _ptr(cell), _ptr(gene),
+                                     _ptr(terms), D, _stream(dev)), "mmvae_zinb_terms")
+    return cell, gene, terms
 
 
 # launch_forest (csrc/forest.hip; the constants are those of csrc/common.hpp)

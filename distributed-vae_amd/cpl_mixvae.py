@@ -804,6 +804,41 @@ class cpl_mixVAE:
         }
 
     @torch.no_grad()
+    def score_zinb(self, dl):
+        """The ZINB negative log-likelihood of the cells of ``dl`` under a model built with ``mode="ZINB"``:
+        ``mixVAE_model.zinb_nll`` (eval forward, ``temp = self.temp``, the category mask of ``eval_model``) on every batch
+        ``(x, index)`` in order.  Returns numpy arrays: ``cell`` float64 [A, N], a cell's term summed over the genes, batches
+        concatenated in the loader's order; ``gene`` float64 [A, D], the batches' per-gene sums added batch by batch in
+        fp64; ``mean`` float64 [A], the sum of ``cell`` over N D (``zinb_loss`` of the whole set); ``data_indx`` [N]."""
+        if D.is_dist():
+            raise NotImplementedError("score_zinb is not data-parallel: run it on one rank, outside the process group")
+        self.model._need_zinb("score_zinb()")
+        A, Dm = self.n_arm, self.input_dim
+        n_rows = len(dl.dataset)
+        B = dl.batch_size
+        if B is None:
+            raise ValueError("error: expected non-None value")            # unwrap(dl.batch_size), cpl_mixvae.py:104-107
+        dev = self.device
+        was_training = self.model.training
+        self.model.eval()
+        pruning_mask = np.where(self.model.fcc[0].bias.detach().cpu().numpy() != 0.0)[0]
+        cell = torch.zeros(A, n_rows, dtype=torch.float64, device=dev)
+        gene = torch.zeros(A, Dm, dtype=torch.float64, device=dev)
+        inds = torch.zeros(n_rows, dtype=torch.float64, device=dev)
+        try:
+            for i, (x, i_x) in enumerate(dl):
+                n_fst, n_lst = i * B, min((i + 1) * B, n_rows)
+                out = self.model.zinb_nll(x.to(dev).expand(A, -1, -1), self.temp, mask=pruning_mask)
+                cell[:, n_fst:n_lst] = out["cell"]
+                gene += out["gene"]
+                inds[n_fst:n_lst] = torch.as_tensor(i_x).to(dev).to(torch.float64)
+        finally:
+            self.model.train(was_training)
+        mean = cell.sum(dim=1) / (float(n_rows) * float(Dm)) if n_rows else torch.full((A,), float("nan"), dtype=torch.float64)
+        return {"cell": cell.cpu().numpy(), "gene": gene.cpu().numpy(), "mean": mean.cpu().numpy(),
+                "data_indx": inds.cpu().numpy()}
+
+    @torch.no_grad()
     def state_gene_corr(self, dl, arm: int = 0, by_category: bool = True):
         """Which genes follow the state variable: the reference's ``corr_analysis`` (mmidas/utils/tree_based_analysis.py:7-59)
         of arm ``arm``'s ``s_mean`` with the expression of the cells of ``dl``, for every category of that arm at once ("S

@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the Gaussian classifiers, the leaf merge, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the Gaussian classifiers, the leaf merge, ZINB scoring, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -360,6 +360,86 @@ int mmvae_leaf_merge(double* p, int64_t ldp, int64_t n, int L, const int32_t* le
     if (int rc = check_ws(who, ws_bytes, mmvae_leaf_merge_workspace_bytes(n, L, T))) return rc;
     return launch_leaf_merge(p, ldp, n, L, level_start, T, start, (int)K_total, K_max, leaf, (int)nnz, label, prob, second, merged,
                              merged ? K0 : 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- zero-inflated negative binomial inference (zinb.hip) ----
+// what the three entries check alike: the extents, then the grid
+static int zinb_extent(const char* who, int64_t N, int D) {
+    if (int rc = check_count(who, "N", N, 1, N_MAX)) return rc;
+    return check_count(who, "D", D, 1, INT32_MAX);
+}
+
+static int zinb_grid(const char* who, int64_t N, int D) {
+    if (zb_tiles(N, D) > 0 && zb_ws_bytes(N, D) > 0) return 0;
+    set_error("%s: N = %lld, D = %d need more than 2^31 - 1 tiles of 64 x 64", who, (long long)N, D);
+    return MMVAE_E_UNSUPPORTED;
+}
+
+static int zinb_eps(const char* who, double eps) {
+    if (eps >= 0.0 && eps < 1.0) return 0;
+    set_error("%s: eps = %g outside [0, 1)", who, eps);
+    return MMVAE_E_BADARG;
+}
+
+int mmvae_zinb_heads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* Wp, const float* bp, const float* Wr,
+                     const float* br, float* x_p, float* x_r, int64_t ldo, void* stream) {
+    const char* who = "zinb_heads";
+    if (!d10 || !Wp || !bp || !Wr || !br || !x_p || !x_r) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
+    if (int rc = check_pitch(who, "ldo", ldo, "D", D)) return rc;
+    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    return launch_zinb_heads(d10, ldh, N, H, D, Wp, bp, Wr, br, x_p, x_r, ldo, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mmvae_zinb_nll_workspace_bytes(int64_t N, int D) {
+    if (N < 1 || N > N_MAX || D < 1 || zb_tiles(N, D) == 0) return 0;
+    return zb_ws_bytes(N, D);
+}
+
+size_t mmvae_zinb_terms_workspace_bytes(int64_t N, int D) { return mmvae_zinb_nll_workspace_bytes(N, D); }
+
+int mmvae_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                   const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, void* ws,
+                   size_t ws_bytes, double* cell_sum, double* gene_sum, void* stream) {
+    const char* who = "zinb_nll";
+    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !cell_sum || !gene_sum) {
+        set_error("%s: null pointer", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    if (int rc = check_ws(who, ws_bytes, mmvae_zinb_nll_workspace_bytes(N, D))) return rc;
+    return launch_zinb_nll(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, ws, cell_sum, gene_sum,
+                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,
+                     int64_t ldx, int64_t N, int D, double eps, void* ws, size_t ws_bytes, double* cell_sum, double* gene_sum,
+                     float* terms, int64_t ld_t, void* stream) {
+    const char* who = "zinb_terms";
+    if (!x_rec || !x_p || !x_r || !X || !ws || !cell_sum || !gene_sum) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_pitch(who, "ld_rec", ld_rec, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ld_p", ld_p, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ld_r", ld_r, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (terms)
+        if (int rc = check_pitch(who, "ld_t", ld_t, "D", D)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    if (int rc = check_ws(who, ws_bytes, mmvae_zinb_terms_workspace_bytes(N, D))) return rc;
+    return launch_zinb_terms(x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N, D, eps, ws, cell_sum, gene_sum, terms, ld_t,
+                             reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- random forest on 256-bin features (forest.hip) ----

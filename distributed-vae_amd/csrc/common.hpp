@@ -1056,6 +1056,18 @@ constexpr int LM_MAX_GRID = 1 << 20;   // workgroups along the cells at most: a 
 int launch_leaf_merge(double* p, int64_t ldp, int64_t n, int L, const int* level_start, int T, const int* start, int K_total,
                       int K_max, const int* leaf, int nnz, int* label, double* prob, double* second, double* merged, int K0,
                       hipStream_t st);
+// zero-inflated negative binomial heads, terms and sums (zinb.hip)
+constexpr int ZB_MAX_H = 128;          // the K extent one LDS tile holds
+size_t zb_ws_bytes(int64_t N, int D);  // the partial sums of the 32 x 32 sub-tiles; 0 for a size no size_t holds
+int64_t zb_tiles(int64_t N, int D);    // the workgroups of one grid; 0 where a grid cannot hold them
+int launch_zinb_heads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* Wp, const float* bp, const float* Wr,
+                      const float* br, float* x_p, float* x_r, int64_t ldo, hipStream_t st);
+int launch_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                    const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, void* ws,
+                    double* cell_sum, double* gene_sum, hipStream_t st);
+int launch_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,
+                      int64_t ldx, int64_t N, int D, double eps, void* ws, double* cell_sum, double* gene_sum, float* terms,
+                      int64_t ld_t, hipStream_t st);
 // random forest on 256-bin features (forest.hip)
 constexpr int RF_THREADS = 256;        // threads of every workgroup: k_rf_fit one tree, k_rf_predict four rows (one a wave)
 constexpr int RF_BINS = 256;           // bins of a feature: one a thread of the candidate search, four a lane of the scan

@@ -1,0 +1,272 @@
+// Zero-inflated negative binomial inference (mmidas/nn_model.py: decoder_zinb :289-295, zinb_loss :642-676; include/mmvae.h,
+// DESIGN.md section 9k).  Three entry points share one tile shape, one term and one reduction:
+//   mmvae_zinb_heads   x_p = sigmoid(fc11_p(d10)), x_r = sigmoid(fc11_r(d10)), written out;
+//   mmvae_zinb_nll     the three heads of a tile from d10, the term of every element in the epilogue, per-cell and per-gene
+//                      sums; no head is written;
+//   mmvae_zinb_terms   the same sums from heads the caller gives, the terms optionally written.
+// A workgroup of four waves owns 64 cells x 64 genes, wave w the 32 x 32 sub-tile (w & 1, w >> 1).  The d10 tile and the
+// heads' weight tiles pass through LDS in K chunks of 32 (rows of an odd pitch, 33 floats): H <= 128 would fit whole, 103 KB
+// at H = 100, but then a CU holds one workgroup and nothing overlaps its staging, its products and its fp64 epilogue; in
+// chunks the tiles take 34 KB, the accumulator image of the epilogue 48 KB, and three workgroups share a CU.  The products
+// are one run of v_mfma_f32_32x32x2_f32 per head with the bias as C, k rising through the chunks: every pre-activation is
+// the k-ordered fp32 fma chain fma(h_{H-1}, w_{H-1}, ... fma(h_0, w_0, b)), whatever the other rows and columns of the call are.
+// The term and everything behind the fp32 pre-activation is fp64.  Sums: a sub-tile leaves, for each of its cells, the sum
+// over its 32 genes (a butterfly over the lanes: the pairwise tree on the gene index), and for each of its genes the sum over
+// its 32 cells (a lane's 16 cells in register order, then the two lane halves); k_zb_finish adds the sub-tiles' partials
+// in tile order.  No atomics: bit-identical from run to run, and a cell's sum depends on that cell's row alone.
+#include "common.hpp"
+
+namespace mmvae {
+
+constexpr int ZB_T = 64;             // cells and genes of a workgroup's tile
+constexpr int ZB_THREADS = 256;
+
+constexpr int ZB_KC = 32;            // the K extent of one LDS chunk (even: whole steps of the instruction's k = 2)
+constexpr int ZB_P = ZB_KC + 1;      // the LDS row pitch in floats, odd
+
+template <int NH>
+constexpr size_t zb_lds_bytes(bool dump) {
+    const size_t stage = (size_t)(ZB_T + ZB_T * NH) * ZB_P;
+    const size_t regs = dump ? (size_t)4 * NH * 16 * 64 : 0;
+    return sizeof(float) * (stage > regs ? stage : regs);
+}
+
+template <int NH>
+struct ZbHeads {
+    const float* W[NH];      // [D, H] each, nn.Linear's layout
+    const float* b[NH];      // [D]
+};
+
+// the row of the wave's 32 x 32 sub-tile that register g of lane half h holds (the 32x32 C/D map; the column is lane & 31)
+__device__ __forceinline__ int zb_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
+
+// One element's term.  r = x_rec + eps, p and z the two probabilities after the eps guard, q = 1 - p, y = 1 - z.  Only the
+// branch that [X > 0] selects is evaluated (the reference multiplies the other by an exact 0, which differs only where that
+// other branch is not finite).
+__device__ inline double zinb_term(double X, double r, double p, double q, double z, double y) {
+    if (X > 0.0) {
+        const double k = exp(X) - 1.0;
+        return -lgamma(k + r) + lgamma(r) - k * log(p) - r * log(q) - log(y);
+    }
+    return -log(z + y * exp(r * log(q)));
+}
+
+// sigmoid(a) after the guard, and one minus it, from the pre-activation: with e = exp(-|a|) the larger of s, 1 - s is
+// 1 / (1 + e) and the smaller e / (1 + e), neither formed by a cancelling subtraction;
+// 1 - (1 - eps)(s + eps) = (1 - eps)(1 - s) + eps^2.
+__device__ inline void zb_gate(float a, double eps, double& p, double& q) {
+    const double e = exp(-fabs((double)a));
+    const double big = 1.0 / (1.0 + e), small = e * big;
+    const double s = a >= 0.f ? big : small, c = a >= 0.f ? small : big;
+    p = (1.0 - eps) * (s + eps);
+    q = (1.0 - eps) * c + eps * eps;
+}
+
+// K chunk k0 .. k0 + 31 of the tile's operands into LDS: rows 0..63 the cells' d10, rows 64 + 64 j .. the weights of head
+// j's genes; cells past N, genes past D and k >= H are zero
+template <int NH>
+__device__ inline void zb_stage(float* lds, const float* __restrict__ d10, int64_t ldh, int64_t cell0, int64_t N, const ZbHeads<NH>& hd,
+                                int64_t gene0, int D, int H, int k0) {
+    for (int idx = threadIdx.x; idx < ZB_T * ZB_KC; idx += ZB_THREADS) {
+        const int r = idx / ZB_KC, k = idx % ZB_KC;
+        const int64_t cell = cell0 + r;
+        lds[r * ZB_P + k] = (cell < N && k0 + k < H) ? d10[cell * ldh + k0 + k] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+        float* dst = lds + (ZB_T + ZB_T * j) * ZB_P;
+        for (int idx = threadIdx.x; idx < ZB_T * ZB_KC; idx += ZB_THREADS) {
+            const int r = idx / ZB_KC, k = idx % ZB_KC;
+            const int64_t gene = gene0 + r;
+            dst[r * ZB_P + k] = (gene < D && k0 + k < H) ? hd.W[j][gene * H + k0 + k] : 0.f;
+        }
+    }
+}
+
+// the wave's 32 x 32 pre-activations of every head: A = d10 (lane l: cell l & 31, k = l >> 5), B = the weights (gene
+// l & 31, k = l >> 5), C = the gene's bias; chunk after chunk, k rising.  Ends behind a barrier: LDS is free again.
+template <int NH>
+__device__ inline void zb_products(float* lds, const float* __restrict__ d10, int64_t ldh, int64_t cell0, int64_t N, const ZbHeads<NH>& hd,
+                                   int64_t gene0, int D, int H, int wm, int wn, int lane, f32x16 (&acc)[NH]) {
+    const int i = lane & 31, kh = lane >> 5;
+    const int64_t gene = gene0 + wn * 32 + i;
+#pragma unroll
+    for (int j = 0; j < NH; ++j) {
+        const float bj = gene < D ? hd.b[j][gene] : 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[j][g] = bj;
+    }
+    const float* a = lds + (wm * 32 + i) * ZB_P + kh;
+    const float* b = lds + (ZB_T + wn * 32 + i) * ZB_P + kh;
+    for (int k0 = 0; k0 < H; k0 += ZB_KC) {
+        zb_stage<NH>(lds, d10, ldh, cell0, N, hd, gene0, D, H, k0);
+        __syncthreads();
+        const int kc = H - k0 < ZB_KC ? (H - k0 + 1) & ~1 : ZB_KC;
+        for (int k = 0; k < kc; k += 2) {
+            const float av = a[k];
+#pragma unroll
+            for (int j = 0; j < NH; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[j * ZB_T * ZB_P + k], acc[j], 0, 0, 0);
+        }
+        __syncthreads();                 // every wave is done with the chunk
+    }
+}
+
+// The sums of the wave's sub-tile.  term(g, cell, gene) is asked for the valid elements only; the others count an exact 0.
+// gene partial: the lane's cells in register order from 0.0, then lane + (lane xor 32).  cell partial of register g: the
+// 32 genes by c <- c + c(lane xor s), s = 16, 8, 4, 2, 1.
+template <class Term>
+__device__ inline void zb_reduce(Term&& term, int lane, int64_t cell0, int64_t gene0, int64_t N, int D, double* __restrict__ ws_cell,
+                                 double* __restrict__ ws_gene) {
+    const int h = lane >> 5;
+    const int64_t gene = gene0 + (lane & 31);
+    double gsum = 0.0, mine = 0.0;
+#pragma unroll 1
+    for (int g = 0; g < 16; ++g) {
+        const int64_t cell = cell0 + zb_row(g, h);
+        double t = 0.0;
+        if (cell < N && gene < D) t = term(g, cell, gene);
+        gsum += t;
+        for (int s = 16; s > 0; s >>= 1) t += __shfl_xor(t, s);
+        if ((lane & 15) == g) mine = t;
+    }
+    gsum += __shfl_xor(gsum, 32);
+    if (lane < 32 && gene < D) ws_gene[(cell0 >> 5) * D + gene] = gsum;
+    const int64_t cell = cell0 + zb_row(lane & 15, h);
+    if ((lane & 31) < 16 && cell < N) ws_cell[(gene0 >> 5) * N + cell] = mine;
+}
+
+__global__ __launch_bounds__(ZB_THREADS) void k_zb_heads(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<2> hd,
+                                                         float* __restrict__ x_p, float* __restrict__ x_r, int64_t ldo, int tiles_n) {
+    __shared__ float zb_lds[zb_lds_bytes<2>(false) / sizeof(float)];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = w & 1, wn = w >> 1;
+    const int64_t cell0 = (int64_t)(blockIdx.x / tiles_n) * ZB_T, gene0 = (int64_t)(blockIdx.x % tiles_n) * ZB_T;
+    const int64_t gene = gene0 + wn * 32 + (lane & 31);
+    f32x16 acc[2];
+    zb_products<2>(zb_lds, d10, ldh, cell0, N, hd, gene0, D, H, wm, wn, lane, acc);
+    if (gene >= D) return;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+        const int64_t cell = cell0 + wm * 32 + zb_row(g, lane >> 5);
+        if (cell < N) {
+            // sigmoid in fp64, rounded once
+            x_p[cell * ldo + gene] = (float)(1.0 / (1.0 + exp(-(double)acc[0][g])));
+            x_r[cell * ldo + gene] = (float)(1.0 / (1.0 + exp(-(double)acc[1][g])));
+        }
+    }
+}
+
+__global__ __launch_bounds__(ZB_THREADS) void k_zb_nll(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<3> hd,
+                                                       const float* __restrict__ X, int64_t ldx, double eps, double* __restrict__ ws_cell,
+                                                       double* __restrict__ ws_gene, int tiles_n) {
+    __shared__ float zb_lds[zb_lds_bytes<3>(true) / sizeof(float)];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = w & 1, wn = w >> 1;
+    const int64_t cell0 = (int64_t)(blockIdx.x / tiles_n) * ZB_T, gene0 = (int64_t)(blockIdx.x % tiles_n) * ZB_T;
+    f32x16 acc[3];
+    zb_products<3>(zb_lds, d10, ldh, cell0, N, hd, gene0, D, H, wm, wn, lane, acc);
+    // every wave is done with the operands: LDS now holds the accumulators, [head][register][lane] per wave, so that the
+    // term loop can stay rolled (unrolled, 16 copies of the fp64 term would not fit the instruction cache)
+    float* mine = zb_lds + w * (3 * 16 * 64) + lane;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) mine[(j * 16 + g) * 64] = acc[j][g];
+    const int64_t wc0 = cell0 + wm * 32, wg0 = gene0 + wn * 32;
+    if (wc0 >= N || wg0 >= D) return;                  // (no barrier follows)
+    zb_reduce(
+        [&](int g, int64_t cell, int64_t gene) {
+            const float a_rec = mine[g * 64], a_p = mine[(16 + g) * 64], a_r = mine[(32 + g) * 64];
+            double p, q, z, y;
+            zb_gate(a_p, eps, p, q);
+            zb_gate(a_r, eps, z, y);
+            return zinb_term((double)X[cell * ldx + gene], (double)fmaxf(a_rec, 0.f) + eps, p, q, z, y);
+        },
+        lane, wc0, wg0, N, D, ws_cell, ws_gene);
+}
+
+__global__ __launch_bounds__(ZB_THREADS) void k_zb_terms(const float* __restrict__ x_rec, int64_t ld_rec, const float* __restrict__ x_p,
+                                                         int64_t ld_p, const float* __restrict__ x_r, int64_t ld_r,
+                                                         const float* __restrict__ X, int64_t ldx, int64_t N, int D, double eps,
+                                                         double* __restrict__ ws_cell, double* __restrict__ ws_gene,
+                                                         float* __restrict__ terms, int64_t ld_t, int tiles_n) {
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wc0 = (int64_t)(blockIdx.x / tiles_n) * ZB_T + (w & 1) * 32, wg0 = (int64_t)(blockIdx.x % tiles_n) * ZB_T + (w >> 1) * 32;
+    if (wc0 >= N || wg0 >= D) return;
+    zb_reduce(
+        [&](int, int64_t cell, int64_t gene) {
+            const double p = (1.0 - eps) * ((double)x_p[cell * ld_p + gene] + eps);
+            const double z = (1.0 - eps) * ((double)x_r[cell * ld_r + gene] + eps);
+            const double t = zinb_term((double)X[cell * ldx + gene], (double)x_rec[cell * ld_rec + gene] + eps, p, 1.0 - p, z, 1.0 - z);
+            if (terms) terms[cell * ld_t + gene] = (float)t;
+            return t;
+        },
+        lane, wc0, wg0, N, D, ws_cell, ws_gene);
+}
+
+// cell_sum[i] = the partials of the cell over the 32-gene sub-tiles, gene_sum[d] = those of the gene over the 32-cell
+// sub-tiles, each added in tile order from 0.0
+__global__ __launch_bounds__(256) void k_zb_finish(const double* __restrict__ ws_cell, const double* __restrict__ ws_gene, int64_t N, int D,
+                                                   double* __restrict__ cell_sum, double* __restrict__ gene_sum) {
+    const int64_t n_gt = cdiv64(D, 32), n_ct = cdiv64(N, 32);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N + D; i += (int64_t)gridDim.x * 256) {
+        double s = 0.0;
+        if (i < N) {
+            for (int64_t t = 0; t < n_gt; ++t) s += ws_cell[t * N + i];
+            cell_sum[i] = s;
+        } else {
+            for (int64_t t = 0; t < n_ct; ++t) s += ws_gene[t * D + (i - N)];
+            gene_sum[i - N] = s;
+        }
+    }
+}
+
+size_t zb_ws_bytes(int64_t N, int D) {
+    return bytes_or_0(8 * ((unsigned __int128)cdiv64(D, 32) * (unsigned __int128)N + (unsigned __int128)cdiv64(N, 32) * (unsigned __int128)D));
+}
+
+// the tiles of one grid, 0 where a grid cannot hold them
+int64_t zb_tiles(int64_t N, int D) {
+    const unsigned __int128 t = (unsigned __int128)cdiv64(N, ZB_T) * (unsigned __int128)cdiv64(D, ZB_T);
+    return t > (unsigned __int128)INT32_MAX ? 0 : (int64_t)t;
+}
+
+static int zb_finish(void* ws, int64_t N, int D, double* cell_sum, double* gene_sum, hipStream_t st) {
+    double* ws_cell = static_cast<double*>(ws);
+    const unsigned gx = (unsigned)imin64(cdiv64(N + D, 256), 1 << 20);
+    hipLaunchKernelGGL(k_zb_finish, dim3(gx), dim3(256), 0, st, ws_cell, ws_cell + cdiv64(D, 32) * N, N, D, cell_sum, gene_sum);
+    HIP_LAUNCH_CHECK("k_zb_finish");
+    return 0;
+}
+
+int launch_zinb_heads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* Wp, const float* bp, const float* Wr,
+                      const float* br, float* x_p, float* x_r, int64_t ldo, hipStream_t st) {
+    ZbHeads<2> hd{{Wp, Wr}, {bp, br}};
+    hipLaunchKernelGGL(k_zb_heads, dim3((unsigned)zb_tiles(N, D)), dim3(ZB_THREADS), 0, st, d10, ldh, N, H, D, hd, x_p, x_r, ldo,
+                       (int)cdiv64(D, ZB_T));
+    HIP_LAUNCH_CHECK("k_zb_heads");
+    return 0;
+}
+
+int launch_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                    const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, void* ws,
+                    double* cell_sum, double* gene_sum, hipStream_t st) {
+    ZbHeads<3> hd{{W, Wp, Wr}, {b, bp, br}};
+    double* ws_cell = static_cast<double*>(ws);
+    hipLaunchKernelGGL(k_zb_nll, dim3((unsigned)zb_tiles(N, D)), dim3(ZB_THREADS), 0, st, d10, ldh, N, H, D, hd, X, ldx, eps, ws_cell,
+                       ws_cell + cdiv64(D, 32) * N, (int)cdiv64(D, ZB_T));
+    HIP_LAUNCH_CHECK("k_zb_nll");
+    return zb_finish(ws, N, D, cell_sum, gene_sum, st);
+}
+
+int launch_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,
+                      int64_t ldx, int64_t N, int D, double eps, void* ws, double* cell_sum, double* gene_sum, float* terms,
+                      int64_t ld_t, hipStream_t st) {
+    double* ws_cell = static_cast<double*>(ws);
+    hipLaunchKernelGGL(k_zb_terms, dim3((unsigned)zb_tiles(N, D)), dim3(ZB_THREADS), 0, st, x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N,
+                       D, eps, ws_cell, ws_cell + cdiv64(D, 32) * N, terms, ld_t, (int)cdiv64(D, ZB_T));
+    HIP_LAUNCH_CHECK("k_zb_terms");
+    return zb_finish(ws, N, D, cell_sum, gene_sum, st);
+}
+
+}  // namespace mmvae

@@ -142,6 +142,7 @@ def dp_train_step(model, xs, temp, optimizer, rehearse: bool = False, rows=None)
     step's own stream."""
     import os
     from . import _native as N
+    model._refuse_zinb_training()         # before the engine is made: no device work for a model that cannot train
     active = is_dist() or (rehearse and dist.is_available() and dist.is_initialized())   # rehearse: world size 1
     overlap = (active and dist.get_backend() == "nccl" and os.environ.get("MMVAE_DP_OVERLAP", "0") == "1")
     B = xs.shape[-2] if rows is None else int(rows[1].numel())

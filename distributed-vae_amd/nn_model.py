@@ -3,7 +3,9 @@
 Mirrors (names, argument meaning, return contract, error behaviour):
 
 * ``mixVAE_model``            mmidas/nn_model.py:89   (``__init__`` :112-261, ``forward`` :297-368,
-                              ``loss`` :495-598, ``decoder`` :277-287, ``state_changes`` :370-411)
+                              ``loss`` :495-598, ``decoder`` :277-287, ``decoder_zinb`` :289-295,
+                              ``state_changes`` :370-411)
+* ``zinb_loss``               mmidas/nn_model.py:642-676 (the value; no backward)
 * ``mk_vae``                  mmidas/nn_model.py:679-721
 * ``VAEConfig``               mmidas/nn_model.py:14-36
 
@@ -108,7 +110,7 @@ class mixVAE_model(nn.Module):
         for name in _LINEAR_ORDER:
             i, o = shapes[name]
             setattr(self, name, mdl([nn.Linear(i, o) for _ in range(n_arm)]))
-        if loss_mode == "ZINB":   # nn_model.py:204-206 builds them; forward rejects ZINB (:315)
+        if loss_mode == "ZINB":   # nn_model.py:204-206; used by decoder_zinb, the eval forward and zinb_nll, never trained
             self.fc11_p = mdl([nn.Linear(H, D) for _ in range(n_arm)])
             self.fc11_r = mdl([nn.Linear(H, D) for _ in range(n_arm)])
         bn_dims = {"batch_l1": H, "batch_l2": H, "batch_l3": H, "batch_l4": H, "batch_l5": L, "batch_s": S}
@@ -282,8 +284,16 @@ class mixVAE_model(nn.Module):
 
     def forward(self, x, temp, prior_c=[], eval=False, mask=None):
         """Same contract as nn_model.py:297-368: returns
-        ``x_recs, [], [], x_lows, cs, s_smps, c_smps, s_means, s_logvars, c_probs`` (lists over arms)."""
-        assert not self.loss_mode == "ZINB", "ZINB not implemented"
+        ``x_recs, [], [], x_lows, cs, s_smps, c_smps, s_means, s_logvars, c_probs`` (lists over arms).  A model built with
+        ``loss_mode="ZINB"`` runs in eval mode with ``eval=True`` only (anything else asserts, as the reference does), and
+        positions 1 and 2 then hold the per-arm ``x_p`` and ``x_r`` [B, D] (mmvae_zinb_heads on the workspace's d10)."""
+        return self._forward(x, temp, eval, mask, True)
+
+    def _forward(self, x, temp, eval, mask, heads):
+        """``forward``; ``heads=False`` leaves the two ZINB heads out (``zinb_nll`` forms them tile by tile)."""
+        zinb = self.loss_mode == "ZINB"
+        # ZINB: the eval-mode forward only (the heads from the workspace's d10); training keeps the reference's refusal
+        assert not zinb or (eval and not self.training), "ZINB not implemented"
         assert self.varitional, "Non-variational not implemented"
         assert len(x) == self.n_arm
         mask_words = None
@@ -322,7 +332,14 @@ class mixVAE_model(nn.Module):
                      "keep": self._explicit_noise}
         L, Cc, S = self.lowD_dim, self.n_categories, self.state_dim
         grab = lambda name, w: list(eng.ws_view(name, w).clone().unbind(0))
-        out = (list(x_rec.unbind(0)), [], [], grab("x_low", L), grab("c", Cc), grab("s_smp", S), grab("c_smp", Cc),
+        x_ps, x_rs = [], []
+        if zinb and heads:              # positions 1 and 2: the older snapshot's zinb_pi and zinb_r
+            d10 = eng.ws_view("d10", self.fc_dim)
+            for a in range(A):
+                x_p, x_r = N.zinb_heads(d10[a], *self._zinb_layers(a)[2:])
+                x_ps.append(x_p)
+                x_rs.append(x_r)
+        out = (list(x_rec.unbind(0)), x_ps, x_rs, grab("x_low", L), grab("c", Cc), grab("s_smp", S), grab("c_smp", Cc),
                grab("s_mean", S), grab("s_logvar", S), grab("c_prob", Cc))
         self._ctx["outs"] = out           # loss() checks that it is handed exactly these, unmodified
         self._ctx["versions"] = {i: [t._version for t in out[i]] for i in (0, 4, 6, 7, 8)}
@@ -351,6 +368,9 @@ class mixVAE_model(nn.Module):
         other tensors (the reference, mmidas/model.py:108-113, computes from whatever it is handed)."""
         assert len(recon_x) == len(c) == self.n_arm
         assert not self.ref_prior
+        if self.loss_mode == "ZINB":
+            raise NotImplementedError("loss() under loss_mode='ZINB' is not built (the reference asserts there, nn_model.py:548); "
+                                      "zinb_nll() scores a batch under the model")
         if self._ctx is None:
             raise RuntimeError("loss() must follow forward()")
         A = self.n_arm
@@ -568,11 +588,8 @@ class mixVAE_model(nn.Module):
             self._dec_engines.pop(next(iter(self._dec_engines)))
         return eng
 
-    @torch.no_grad()
-    def decoder(self, c, s, arm):
-        """nn_model.py:277-287: ``relu(fc11(relu(fc10(... relu(fc6([c | s]))))))`` of arm ``arm`` for c [N, C], s [N, S]
-        (device tensors); returns the device tensor [N, D].  State dropout is the identity in eval mode; in training mode
-        with s_drop > 0 this raises NotImplementedError (the library does not offer a decode with state dropout)."""
+    def _decode_run(self, c, s, arm):
+        """``decoder``: (x_rec [N, D], the decode engine whose workspace now holds the chain's activations)."""
         if self.training and self.s_dp.p > 0:
             raise NotImplementedError("decoder(): state dropout (training mode, s_drop > 0) is not supported; call model.eval()")
         if not (0 <= int(arm) < self.n_arm):
@@ -589,7 +606,61 @@ class mixVAE_model(nn.Module):
         per_arm = int(self._layout.per_arm)
         params = self._flat[int(arm) * per_arm:]                     # that arm's segment: a one-arm model
         eng.decode(self._hyper(1.0, True), params, c, 0, s, 0, x_rec)
-        return x_rec
+        return x_rec, eng
+
+    @torch.no_grad()
+    def decoder(self, c, s, arm):
+        """nn_model.py:277-287: ``relu(fc11(relu(fc10(... relu(fc6([c | s]))))))`` of arm ``arm`` for c [N, C], s [N, S]
+        (device tensors); returns the device tensor [N, D].  State dropout is the identity in eval mode; in training mode
+        with s_drop > 0 this raises NotImplementedError (the library does not offer a decode with state dropout)."""
+        return self._decode_run(c, s, arm)[0]
+
+    # ------------------------------------------------------------------ zero-inflated negative binomial inference
+    def _need_zinb(self, what: str):
+        if self.loss_mode != "ZINB":
+            raise RuntimeError(f"{what} needs a model built with loss_mode='ZINB' (this one has loss_mode={self.loss_mode!r}: "
+                               "it has no fc11_p / fc11_r heads)")
+
+    def _zinb_layers(self, arm: int):
+        """(fc11.weight, fc11.bias, fc11_p.weight, fc11_p.bias, fc11_r.weight, fc11_r.bias) of arm ``arm``, detached."""
+        return tuple(t.detach() for m in (self.fc11[arm], self.fc11_p[arm], self.fc11_r[arm]) for t in (m.weight, m.bias))
+
+    def _refuse_zinb_training(self):
+        if self.loss_mode == "ZINB":
+            raise NotImplementedError("training under loss_mode='ZINB' is not built")
+
+    @torch.no_grad()
+    def decoder_zinb(self, c, s, arm):
+        """nn_model.py:289-295: ``(relu(fc11(h)), sigmoid(fc11_p(h)), sigmoid(fc11_r(h)))`` with h the decoder's last hidden
+        layer, for c [N, C], s [N, S] (device tensors) -> three device tensors [N, D].  x_rec is ``decoder``'s output bit for
+        bit (the same decode runs); the two heads come from that decode's fp32 d10 (mmvae_zinb_heads).  Refusals: those of
+        ``decoder``; RuntimeError for a model not built with ``loss_mode="ZINB"``."""
+        self._need_zinb("decoder_zinb()")
+        x_rec, eng = self._decode_run(c, s, arm)
+        x_p, x_r = N.zinb_heads(eng.ws_view("d10", self.fc_dim)[0], *self._zinb_layers(int(arm))[2:])
+        return x_rec, x_p, x_r
+
+    @torch.no_grad()
+    def zinb_nll(self, x, temp=1.0, mask=None):
+        """The ZINB negative log-likelihood of the batch ``x`` (as ``forward`` takes it) under the model: an eval forward, then
+        mmvae_zinb_nll per arm on the forward workspace's d10 -- the three heads are formed tile by tile and never written.
+        Returns ``{"cell": float64 [A, B] (the term summed over the genes), "gene": float64 [A, D] (over the cells), "n": B}``
+        on the device.  The eval forward samples s_smp, as the reference's does: a cell's value depends on its draw
+        (``set_explicit_noise`` fixes it).  Needs model.eval()."""
+        self._need_zinb("zinb_nll()")
+        if self.training:
+            raise RuntimeError("zinb_nll() needs model.eval()")
+        self._forward(x, temp, True, mask, False)
+        eng, xt, xs = self._engine, self._ctx["x"], self._ctx["x_arm_stride"]
+        A, B, D = self.n_arm, xt.shape[-2], self.input_dim
+        d10 = eng.ws_view("d10", self.fc_dim)
+        cell = torch.empty(A, B, dtype=torch.float64, device=xt.device)
+        gene = torch.empty(A, D, dtype=torch.float64, device=xt.device)
+        for a in range(A):
+            xa = xt if xs == 0 else xt[a]
+            cell[a], gene[a] = N.zinb_nll(d10[a], *self._zinb_layers(a), xa)
+        self._ctx = None
+        return {"cell": cell, "gene": gene, "n": B}
 
     def set_explicit_state_noise(self, u):
         """Test hook of ``state_changes`` (as ``set_explicit_noise`` is of ``forward``): u float32 [A, n_samp, B] on the
@@ -672,6 +743,7 @@ class mixVAE_model(nn.Module):
         step, so the effective weights are torch's ``weight_orig * mask`` after every step; the moments of pruned entries
         are held at 0, where torch keeps decaying remnants that never reach an effective weight.  Without ``do_adam`` the
         gradients are zeroed there; the caller steps its optimizer and then calls ``prune_apply(mask, grads=False)``."""
+        self._refuse_zinb_training()
         words = self._mask_words(mask)
         xt, xs = self._prep_x(x)
         eng = self._ensure(xt.shape[-2])
@@ -705,6 +777,7 @@ class mixVAE_model(nn.Module):
         matrix beyond 4 GB --: gather the batch and call ``fused_train_step`` then.  ``data16`` (``gemm_dtype == "bf16"``
         only): the matrix's bf16 copy (``_native.to_bf16``, ``DeviceLoader.data_bf16()``): bf16 storage, see DESIGN.md section 13.
         ``mask``: as ``fused_train_step`` takes it (the pruning phase), with the same zeroing behind the step."""
+        self._refuse_zinb_training()
         words = self._mask_words(mask)
         if data.device.type != "cuda" or data.dtype != torch.float32 or data.shape[1] != self.input_dim:
             raise N.NativeError("fused_train_step_rows needs the float32 cells x genes matrix on the GPU")
@@ -737,6 +810,23 @@ class mixVAE_model(nn.Module):
         if words is not None:
             self._prune_words(words, opt if do_adam else None, bool(do_adam), True)
         return buf
+
+
+def zinb_loss(rec_x, x_p, x_r, X, eps=1e-6):
+    """nn_model.py:642-676: the mean over all elements of the ZINB term of ``X`` (the log1p matrix) under the heads ``rec_x``,
+    ``x_p``, ``x_r`` -- device tensors of one shape [..., D]; returns a 0-dim float32 device tensor: the fp64 sum of
+    mmvae_zinb_terms' per-cell sums divided by the element count.  No backward: an input that requires grad raises
+    NotImplementedError."""
+    ts = (rec_x, x_p, x_r, X)
+    if any(t.requires_grad for t in ts):
+        raise NotImplementedError("zinb_loss has no backward: training under loss_mode='ZINB' is not built; detach the inputs")
+    if not all(t.shape == X.shape for t in ts) or X.dim() < 1 or X.numel() == 0:
+        raise ValueError("zinb_loss: rec_x, x_p, x_r and X must have one non-empty shape")
+    if any(t.device.type != "cuda" for t in ts):
+        raise N.NativeError("zinb_loss needs GPU tensors: it runs only on the HIP engine")
+    flat = [t.float().reshape(-1, X.shape[-1]) for t in ts]
+    cell, _, _ = N.zinb_terms(*flat, eps=eps)
+    return (cell.sum() / X.numel()).to(torch.float32)
 
 
 def mk_vae(C, state_dim, input_dim, device, eps=1e-8, fc_dim=100, latent_dim=10, x_drop=0.5, s_drop=0.2, lr=0.001,

@@ -578,6 +578,56 @@ int mmvae_leaf_merge(double *p, int64_t ldp, int64_t n, int L, const int32_t *le
                      int32_t *label, double *prob, double *second /* NULL = not wanted */,
                      double *merged /* NULL = not wanted */, int K0, void *stream);
 
+/* ---- zero-inflated negative binomial inference (mmidas/nn_model.py: decoder_zinb :289-295, zinb_loss :642-676; DESIGN.md
+ * section 9k) ----
+ * With h = d10, the decoder's last hidden layer [N, H]: x_rec = relu(fc11(h)), x_p = sigmoid(fc11_p(h)),
+ * x_r = sigmoid(fc11_r(h)).  For one element with input X (the log1p matrix) and eps: k = exp(X) - 1, r = x_rec + eps,
+ * p = (1 - eps)(x_p + eps), z = (1 - eps)(x_r + eps) and
+ *   term = -log(z + (1 - z)(1 - p)^r)                                                          where X <= 0 (or X is NaN),
+ *   term = -lgamma(k + r) + lgamma(r) - k log p - r log(1 - p) - log(1 - z), added in that order, where X > 0.
+ * Only the selected branch is evaluated; the reference multiplies the other by an exact 0, which differs only where that
+ * other branch is not finite.  zinb_loss is the mean of term over the elements.
+ * All matrices are float32, row-major, on the device, with a row pitch in elements; weights [D, H] and biases [D] are
+ * nn.Linear's, contiguous.  Every pre-activation is the k-ordered fp32 fma chain fma(h_{H-1}, w_{H-1}, ... fma(h_0, w_0, b))
+ * of v_mfma_f32_32x32x2_f32 with the bias as C: |a - exact| <= (H + 2) 2^-24 (sum_k |w_k h_k| + |b|), and with
+ * integer-valued operands whose sums stay below 2^24 it is exact.  Everything behind the fp32 pre-activation is fp64.
+ *
+ * mmvae_zinb_heads: x_p, x_r [N, ldo] from d10 [N, ldh] and the two layers.  sigmoid(a) = 1 / (1 + exp(-a)) in fp64,
+ *   rounded once to float32: within 0.5 ulp + 2^-50 relative of the sigmoid of the fp32 pre-activation; with the bound
+ *   above and the sigmoid's slope <= 1/4, |x - exact| <= (H + 2) 2^-26 (sum |w h| + |b|) + 2^-24 x.  One launch.
+ *
+ * mmvae_zinb_nll: the three heads of every 64 x 64 tile from d10 and the six arrays W, b (fc11), Wp, bp, Wr, br, the
+ *   term of every element against X [N, ldx] in the epilogue; no head is written.  p and 1 - p come from the
+ *   pre-activation a without a cancelling subtraction: e = exp(-|a|), s = 1 / (1 + e) or e / (1 + e),
+ *   1 - p = (1 - eps)(1 - s) + eps^2; z and 1 - z alike; pow as exp(r log(1 - p)).  Out: cell_sum double [N] (over the
+ *   genes) and gene_sum double [D] (over the cells).
+ * mmvae_zinb_terms: the same sums from heads the caller gives (x_rec, x_p, x_r and X, four pitches); 1 - p and 1 - z are
+ *   the fp64 differences.  terms float32 [N, ld_t] or NULL: every term, rounded once.
+ *   Error of a term given its fp32 inputs: the fp64 evaluation, a few 2^-53 of M, the sum of the magnitudes of its
+ *   addends -- far below what the fp32 pre-activations carry.
+ *   Sums, both entries: a 32 x 32 sub-tile (cells 32 i .., genes 32 j ..) leaves for each cell the sum over its genes by
+ *   the pairwise tree on the gene index (c <- c + c(g xor s), s = 16, 8, 4, 2, 1; genes past D count an exact 0) and for
+ *   each gene the sum over its cells (rows (g & 3) + 8 (g >> 2) for g = 0..15 one by one from 0.0, the same for rows + 4,
+ *   then the two added); a last launch adds the sub-tiles' partials in tile order from 0.0.  No floating-point atomics:
+ *   bit-identical from run to run; a cell's cell_sum depends on that cell's rows of d10 and X alone, not on N or on the
+ *   other cells of the call.
+ *   ws: mmvae_zinb_nll_workspace_bytes(N, D) = mmvae_zinb_terms_workspace_bytes(N, D) = 8 (ceil(D / 32) N + ceil(N / 32) D)
+ *   bytes of device memory, 8-byte aligned; 0 for arguments the entries refuse.
+ * All three: MMVAE_E_BADARG, before any device work, for a null pointer (terms excepted), N < 1 or N > 2^31, D < 1, H < 1,
+ *   a pitch below its width, eps outside [0, 1), a misaligned ws; MMVAE_E_UNSUPPORTED for H > 128 or more than 2^31 - 1
+ *   tiles; MMVAE_E_WORKSPACE for a ws below the size.  Any N and D otherwise: no multiple is required. */
+int mmvae_zinb_heads(const float *d10, int64_t ldh, int64_t N, int H, int D, const float *Wp, const float *bp,
+                     const float *Wr, const float *br, float *x_p, float *x_r, int64_t ldo, void *stream);
+size_t mmvae_zinb_nll_workspace_bytes(int64_t N, int D);
+int mmvae_zinb_nll(const float *d10, int64_t ldh, int64_t N, int H, int D, const float *W, const float *b,
+                   const float *Wp, const float *bp, const float *Wr, const float *br, const float *X, int64_t ldx,
+                   double eps, void *ws, size_t ws_bytes, double *cell_sum, double *gene_sum, void *stream);
+size_t mmvae_zinb_terms_workspace_bytes(int64_t N, int D);
+int mmvae_zinb_terms(const float *x_rec, int64_t ld_rec, const float *x_p, int64_t ld_p, const float *x_r, int64_t ld_r,
+                     const float *X, int64_t ldx, int64_t N, int D, double eps, void *ws, size_t ws_bytes,
+                     double *cell_sum, double *gene_sum, float *terms /* NULL = not wanted */, int64_t ld_t,
+                     void *stream);
+
 /* ---- random forest on 256-bin features (mmidas/utils/cluster_analysis.py: RF_classifier) ----
  * A forest under k-fold cross-validation on features quantised to 256 rank bins.  All arithmetic is integer up to one fp64
  * score per candidate split, so a tree is fixed by its inputs: bit-identical from run to run, independent of the order of
