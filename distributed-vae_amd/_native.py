@@ -77,6 +77,24 @@ class EncodeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x_low", "c_prob", "c", "c_smp", "s_mean", "s_logvar", "labels", "counts")]
 
 
+class CountLogp(C.Structure):
+    """mmvae_count_logp_t"""
+    _fields_ = [("kind", C.c_int), ("N", C.c_int64), ("D", C.c_int), ("eps", C.c_double),
+                ("x", C.c_void_p), ("ldx", C.c_int64), ("mu", C.c_void_p), ("ld_mu", C.c_int64),
+                ("theta", C.c_void_p), ("ld_theta", C.c_int64), ("pi", C.c_void_p), ("ld_pi", C.c_int64),
+                ("mu2", C.c_void_p), ("ld_mu2", C.c_int64), ("theta2", C.c_void_p), ("ld_theta2", C.c_int64),
+                ("terms", C.c_void_p), ("ld_t", C.c_int64), ("cell_sum", C.c_void_p), ("gene_sum", C.c_void_p)]
+
+
+class CountSample(C.Structure):
+    """mmvae_count_sample_t"""
+    _fields_ = [("param", C.c_int), ("zi_kind", C.c_int), ("N", C.c_int64), ("D", C.c_int), ("cell0", C.c_int64),
+                ("eps", C.c_double), ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("a", C.c_void_p), ("ld_a", C.c_int64), ("b", C.c_void_p), ("ld_b", C.c_int64),
+                ("zi", C.c_void_p), ("ld_zi", C.c_int64), ("out_int32", C.c_int), ("log1p", C.c_int),
+                ("out", C.c_void_p), ("ld_out", C.c_int64), ("exhausted", C.c_void_p)]
+
+
 N_EVENTS = 8
 N_TUNE = 24
 # mmvae_exec.tune indices (private: csrc/tune.h; public: MMVAE_TUNE_ENGINE in include/mmvae.h) and the
@@ -230,6 +248,13 @@ def lib():
     L.mmvae_zinb_terms_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_zinb_terms_workspace_bytes.restype = C.c_size_t
     L.mmvae_zinb_terms.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, vp, C.c_size_t, vp, vp, vp, i64, vp]
+    L.mmvae_count_logp_workspace_bytes.argtypes = [i64, i32]
+    L.mmvae_count_logp_workspace_bytes.restype = C.c_size_t
+    L.mmvae_count_logp.argtypes = [C.POINTER(CountLogp), vp, C.c_size_t, vp]
+    L.mmvae_debug_count_logp_host.argtypes = [C.POINTER(CountLogp)]
+    L.mmvae_count_sample.argtypes = [C.POINTER(CountSample), vp]
+    L.mmvae_debug_count_sample_host.argtypes = [C.POINTER(CountSample)]
+    L.mmvae_zinb_sample.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp, C.POINTER(CountSample), vp]
     L.mmvae_forest_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     L.mmvae_forest_workspace_bytes.restype = C.c_size_t
     L.mmvae_forest_cv.argtypes = [vp, i64, i64, i32, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
@@ -1085,6 +1110,138 @@ def zinb_terms(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X: tor
                                      _ptr(X), _zinb_pitch(X), n, D, float(eps), _ptr(ws), nbytes, _ptr(cell), _ptr(gene),
                                      _ptr(terms), D, _stream(dev)), "mmvae_zinb_terms")
     return cell, gene, terms
+
+
+# count distributions (csrc/countdist.hip)
+COUNT_KINDS = {"nb": 0, "zinb": 1, "mixture": 2}
+COUNT_ZI = {None: 0, "logits": 1, "probs": 2}
+
+
+def _count_theta(what: str, name: str, t: torch.Tensor, n: int, D: int):
+    """(theta as the kernels read it, its pitch): float32 [D] (pitch 0) or [n, D]."""
+    if t.dtype == torch.float32 and t.dim() == 1 and t.shape[0] == D:
+        return t.contiguous(), 0
+    if t.dim() != 2 or t.shape[0] != n:
+        raise ValueError(f"{what}: {name} must be float32 [{D}] or [{n}, {D}]; got {t.dtype} {tuple(t.shape)}")
+    t = _zinb_mat(what, name, t, D)
+    return t, _zinb_pitch(t)
+
+
+def _count_mat(what: str, name: str, t: torch.Tensor, n: int, D: int):
+    t = _zinb_mat(what, name, t, D)
+    if t.shape[0] != n:
+        raise ValueError(f"{what}: {name} has {t.shape[0]} rows where {n} are expected")
+    return t, _zinb_pitch(t)
+
+
+def count_logp(kind: str, x: torch.Tensor, mu: torch.Tensor, theta: torch.Tensor, pi: Optional[torch.Tensor] = None,
+               mu2: Optional[torch.Tensor] = None, theta2: Optional[torch.Tensor] = None, eps: float = 1e-8,
+               return_terms: bool = True, return_sums: bool = False):
+    """mmvae_count_logp: the log-likelihood of every element of x [N, D] (float32 on the GPU, rows may be strided) under NB
+    (``kind`` "nb"), ZINB ("zinb": ``pi`` the zero-inflation logits) or the NB mixture ("mixture": ``mu2``, optional ``theta2``,
+    ``pi`` the mixture logits); theta float32 [D] or [N, D].  -> (terms float32 [N, D] or None, cell_sum float64 [N] or None,
+    gene_sum float64 [D] or None) on the device."""
+    what = "count_logp"
+    if kind not in COUNT_KINDS:
+        raise ValueError(f"{what}: kind must be one of {sorted(COUNT_KINDS)}; got {kind!r}")
+    if (pi is None) != (kind == "nb") or (mu2 is None) != (kind != "mixture") or (theta2 is not None and kind != "mixture"):
+        raise ValueError(f"{what}: kind {kind!r} takes pi for zinb and mixture, mu2 (and theta2) for mixture only")
+    _need_cuda(what, x, mu, theta, pi, mu2, theta2)
+    x = _zinb_mat(what, "x", x)
+    n, D = (int(v) for v in x.shape)
+    a = CountLogp(kind=COUNT_KINDS[kind], N=n, D=D, eps=float(eps), x=x.data_ptr(), ldx=_zinb_pitch(x))
+    keep = [x]
+    for name, t, vec in (("mu", mu, False), ("theta", theta, True), ("pi", pi, False), ("mu2", mu2, False), ("theta2", theta2, True)):
+        if t is None:
+            continue
+        t, ld = _count_theta(what, name, t, n, D) if vec else _count_mat(what, name, t, n, D)
+        keep.append(t)
+        setattr(a, name, t.data_ptr())
+        setattr(a, "ld_" + name, ld)
+    dev = x.device
+    with torch.cuda.device(dev):
+        terms = torch.empty(n, D, dtype=torch.float32, device=dev) if return_terms else None
+        cell = gene = ws = None
+        nbytes = 0
+        if return_sums:
+            nbytes = int(lib().mmvae_count_logp_workspace_bytes(n, D))
+            ws = _workspace(nbytes, dev)
+            cell = torch.empty(n, dtype=torch.float64, device=dev)
+            gene = torch.empty(D, dtype=torch.float64, device=dev)
+            a.cell_sum, a.gene_sum = cell.data_ptr(), gene.data_ptr()
+        if terms is not None:
+            a.terms, a.ld_t = terms.data_ptr(), D
+        check(lib().mmvae_count_logp(C.byref(a), _ptr(ws), nbytes, _stream(dev)), "mmvae_count_logp")
+    return terms, cell, gene
+
+
+def _count_sample_out(n: int, D: int, dev, out_int32: bool):
+    return (torch.empty(n, D, dtype=torch.int32 if out_int32 else torch.float32, device=dev),
+            torch.zeros(1, dtype=torch.int32, device=dev))
+
+
+def _count_exhausted(what: str, counter: torch.Tensor):
+    k = int(counter.item())
+    if k:
+        raise NativeError(f"{what}: {k} elements ran out of attempts in a bounded rejection loop and took the fallback value")
+
+
+def count_sample(mu: torch.Tensor, theta: torch.Tensor, zi: Optional[torch.Tensor] = None, zi_kind: Optional[str] = None,
+                 seed: int = 0, offset: int = 0, cell0: int = 0, out_int32: bool = False, log1p: bool = False,
+                 heads_eps: Optional[float] = None):
+    """mmvae_count_sample: one draw per element of NB(mu, theta) or, with ``zi`` (``zi_kind`` "logits" or "probs"), of
+    ZINB(mu, theta, zi); mu float32 [N, D] on the GPU, theta [D] or [N, D].  With ``heads_eps`` the three arguments are the
+    model's heads (x_rec, x_p, x_r) and are mapped under zinb_loss's eps guards.  Draws are keyed by (seed, offset,
+    (cell0 + row) D + gene).  -> float32 (``log1p``: log1p of the count) or int32 [N, D]; raises if any element exhausted a
+    bounded loop."""
+    what = "count_sample"
+    heads = heads_eps is not None
+    if heads and (zi is None or zi_kind is not None):
+        raise ValueError(f"{what}: the heads' mapping takes x_r as zi and no zi_kind")
+    if not heads and ((zi is None) != (zi_kind is None) or zi_kind not in COUNT_ZI):
+        raise ValueError(f"{what}: zi comes with zi_kind 'logits' or 'probs'; got zi_kind {zi_kind!r}")
+    _need_cuda(what, mu, theta, zi)
+    mu = _zinb_mat(what, "x_rec" if heads else "mu", mu)
+    n, D = (int(v) for v in mu.shape)
+    theta, ld_th = _count_mat(what, "x_p", theta, n, D) if heads else _count_theta(what, "theta", theta, n, D)
+    s = CountSample(param=int(heads), zi_kind=0 if heads else COUNT_ZI[zi_kind], N=n, D=D, cell0=int(cell0),
+                    eps=float(heads_eps) if heads else 0.0, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, offset=int(offset),
+                    a=mu.data_ptr(), ld_a=_zinb_pitch(mu), b=theta.data_ptr(), ld_b=ld_th, out_int32=int(out_int32),
+                    log1p=int(log1p), ld_out=D)
+    if zi is not None:
+        zi, s.ld_zi = _count_mat(what, "x_r" if heads else "zi", zi, n, D)
+        s.zi = zi.data_ptr()
+    dev = mu.device
+    with torch.cuda.device(dev):
+        out, counter = _count_sample_out(n, D, dev, out_int32)
+        s.out, s.exhausted = out.data_ptr(), counter.data_ptr()
+        check(lib().mmvae_count_sample(C.byref(s), _stream(dev)), "mmvae_count_sample")
+        _count_exhausted(what, counter)
+    return out
+
+
+def zinb_sample(d10: torch.Tensor, W, b, Wp, bp, Wr, br, seed: int, offset: int = 0, cell0: int = 0, eps: float = 1e-6,
+                out_int32: bool = False, log1p: bool = False):
+    """mmvae_zinb_sample: one ZINB draw per (cell, gene) under the three heads of d10 [N, H] (fc11: W, b; fc11_p: Wp, bp;
+    fc11_r: Wr, br), the heads never written: bit for bit ``count_sample(x_rec, x_p, x_r, heads_eps=eps)`` on the heads that
+    the decode and ``zinb_heads`` write.  -> float32 or int32 [N, D]."""
+    what = "zinb_sample"
+    _need_cuda(what, d10, W, b, Wp, bp, Wr, br)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(W.shape[0])
+    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
+                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
+    dev = d10.device
+    with torch.cuda.device(dev):
+        out, counter = _count_sample_out(n, D, dev, out_int32)
+        s = CountSample(param=1, N=n, D=D, cell0=int(cell0), eps=float(eps), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                        offset=int(offset), out_int32=int(out_int32), log1p=int(log1p), out=out.data_ptr(), ld_out=D,
+                        exhausted=counter.data_ptr())
+        check(lib().mmvae_zinb_sample(_ptr(d10), _zinb_pitch(d10), H, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr), _ptr(br),
+                                      C.byref(s), _stream(dev)), "mmvae_zinb_sample")
+        _count_exhausted(what, counter)
+    return out
 
 
 # launch_forest (csrc/forest.hip; the constants are those of csrc/common.hpp)

@@ -839,6 +839,42 @@ class cpl_mixVAE:
                 "data_indx": inds.cpu().numpy()}
 
     @torch.no_grad()
+    def sample_counts(self, dl, seed, arm=None, log1p=False):
+        """Synthetic counts for the cells of ``dl`` from a model built with ``mode="ZINB"``: per batch ``(x, index)`` an eval
+        forward as ``score_zinb`` runs it (``temp = self.temp``, the category mask of ``eval_model``), then one ZINB draw per
+        gene under each arm's heads (``mixVAE_model.zinb_sample_batch``; the heads are never written).  A draw is keyed by
+        ``seed`` and the cell's position in the loader's order, so the result does not depend on the batch size beyond what the
+        forward itself does.  ``arm=None`` draws for every arm.  Returns numpy arrays: ``counts`` float32 [A, n, D] (A = 1 for a
+        chosen arm; ``log1p`` of the counts on request) and ``data_indx`` [n].  The training mode is restored afterwards;
+        RuntimeError for a model built with ``mode="MSE"``."""
+        if D.is_dist():
+            raise NotImplementedError("sample_counts is not data-parallel: run it on one rank, outside the process group")
+        self.model._need_zinb("sample_counts()")
+        if arm is not None and not 0 <= int(arm) < self.n_arm:
+            raise ValueError(f"arm = {arm} outside [0, {self.n_arm})")
+        arms = list(range(self.n_arm)) if arm is None else [int(arm)]
+        n_rows = len(dl.dataset)
+        B = dl.batch_size
+        if B is None:
+            raise ValueError("error: expected non-None value")            # unwrap(dl.batch_size), cpl_mixvae.py:104-107
+        dev = self.device
+        was_training = self.model.training
+        self.model.eval()
+        pruning_mask = np.where(self.model.fcc[0].bias.detach().cpu().numpy() != 0.0)[0]
+        counts = np.empty((len(arms), n_rows, self.input_dim), dtype=np.float32)
+        inds = np.zeros(n_rows, dtype=np.float64)
+        try:
+            for i, (x, i_x) in enumerate(dl):
+                n_fst, n_lst = i * B, min((i + 1) * B, n_rows)
+                out = self.model.zinb_sample_batch(x.to(dev).expand(self.n_arm, -1, -1), seed, self.temp, mask=pruning_mask,
+                                                   cell0=n_fst, log1p=log1p, arms=arms)
+                counts[:, n_fst:n_lst] = out.cpu().numpy()
+                inds[n_fst:n_lst] = torch.as_tensor(i_x).double().cpu().numpy()
+        finally:
+            self.model.train(was_training)
+        return {"counts": counts, "data_indx": inds}
+
+    @torch.no_grad()
     def state_gene_corr(self, dl, arm: int = 0, by_category: bool = True):
         """Which genes follow the state variable: the reference's ``corr_analysis`` (mmidas/utils/tree_based_analysis.py:7-59)
         of arm ``arm``'s ``s_mean`` with the expression of the cells of ``dl``, for every category of that arm at once ("S

@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the Gaussian classifiers, the leaf merge, ZINB scoring, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the Gaussian classifiers, the leaf merge, ZINB scoring, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -440,6 +440,112 @@ int mmvae_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64
     if (int rc = check_ws(who, ws_bytes, mmvae_zinb_terms_workspace_bytes(N, D))) return rc;
     return launch_zinb_terms(x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N, D, eps, ws, cell_sum, gene_sum, terms, ld_t,
                              reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- count distributions (countdist.hip) ----
+// a pitch of 0 reads a vector [D] where vec_ok says so
+static int cd_pitch(const char* who, const char* ldname, int64_t ld, int D, bool vec_ok) {
+    if (vec_ok && ld == 0) return 0;
+    return check_pitch(who, ldname, ld, "D", D);
+}
+
+static int count_logp_check(const char* who, const mmvae_count_logp_t* a) {
+    if (!a) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "kind", a->kind, 0, 2)) return rc;
+    if (!a->x || !a->mu || !a->theta || (a->kind != 0 && !a->pi) || (a->kind == 2 && !a->mu2)) {
+        set_error("%s: null pointer", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = zinb_extent(who, a->N, a->D)) return rc;
+    if (int rc = cd_pitch(who, "ldx", a->ldx, a->D, false)) return rc;
+    if (int rc = cd_pitch(who, "ld_mu", a->ld_mu, a->D, false)) return rc;
+    if (int rc = cd_pitch(who, "ld_theta", a->ld_theta, a->D, true)) return rc;
+    if (a->kind != 0)
+        if (int rc = cd_pitch(who, "ld_pi", a->ld_pi, a->D, false)) return rc;
+    if (a->kind == 2) {
+        if (int rc = cd_pitch(who, "ld_mu2", a->ld_mu2, a->D, false)) return rc;
+        if (a->theta2)
+            if (int rc = cd_pitch(who, "ld_theta2", a->ld_theta2, a->D, true)) return rc;
+    }
+    if (a->terms)
+        if (int rc = cd_pitch(who, "ld_t", a->ld_t, a->D, false)) return rc;
+    return zinb_eps(who, a->eps);
+}
+
+size_t mmvae_count_logp_workspace_bytes(int64_t N, int D) { return mmvae_zinb_nll_workspace_bytes(N, D); }
+
+int mmvae_count_logp(const mmvae_count_logp_t* a, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "count_logp";
+    if (int rc = count_logp_check(who, a)) return rc;
+    if (!a->cell_sum != !a->gene_sum) { set_error("%s: cell_sum and gene_sum come together", who); return MMVAE_E_BADARG; }
+    if (!a->terms && !a->cell_sum) { set_error("%s: neither terms nor sums are wanted", who); return MMVAE_E_BADARG; }
+    if (a->cell_sum) {
+        if (!ws) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+        if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    }
+    if (int rc = zinb_grid(who, a->N, a->D)) return rc;
+    if (a->cell_sum)
+        if (int rc = check_ws(who, ws_bytes, mmvae_count_logp_workspace_bytes(a->N, a->D))) return rc;
+    return launch_count_logp(*a, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_count_logp_host(const mmvae_count_logp_t* a) {
+    const char* who = "debug_count_logp_host";
+    if (int rc = count_logp_check(who, a)) return rc;
+    if (!a->terms) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    host_count_logp(*a);
+    return 0;
+}
+
+// what the draws check alike; heads_given: a, b and zi are read (mmvae_zinb_sample forms them itself)
+static int count_sample_check(const char* who, const mmvae_count_sample_t* s, bool heads_given) {
+    if (!s) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "param", s->param, 0, 1)) return rc;
+    if (int rc = check_count(who, "zi_kind", s->zi_kind, 0, 2)) return rc;
+    const bool zi = s->param == 1 || s->zi_kind != 0;
+    if (!s->out || !s->exhausted || (heads_given && (!s->a || !s->b || (zi && !s->zi)))) {
+        set_error("%s: null pointer", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = zinb_extent(who, s->N, s->D)) return rc;
+    if (heads_given) {
+        if (int rc = cd_pitch(who, "ld_a", s->ld_a, s->D, false)) return rc;
+        if (int rc = cd_pitch(who, "ld_b", s->ld_b, s->D, s->param == 0)) return rc;
+        if (zi)
+            if (int rc = cd_pitch(who, "ld_zi", s->ld_zi, s->D, false)) return rc;
+    }
+    if (int rc = cd_pitch(who, "ld_out", s->ld_out, s->D, false)) return rc;
+    if (s->cell0 < 0 || (unsigned __int128)((uint64_t)s->cell0 + (uint64_t)s->N) * (unsigned __int128)s->D >= ((unsigned __int128)1 << 63)) {
+        set_error("%s: cell0 = %lld with N = %lld, D = %d leaves the 63-bit element index", who, (long long)s->cell0, (long long)s->N, s->D);
+        return MMVAE_E_BADARG;
+    }
+    if (s->offset >> 56) { set_error("%s: offset = %llu not below 2^56", who, (unsigned long long)s->offset); return MMVAE_E_BADARG; }
+    if (s->out_int32 && s->log1p) { set_error("%s: log1p needs the float32 output", who); return MMVAE_E_BADARG; }
+    return s->param == 1 ? zinb_eps(who, s->eps) : 0;
+}
+
+int mmvae_count_sample(const mmvae_count_sample_t* s, void* stream) {
+    if (int rc = count_sample_check("count_sample", s, true)) return rc;
+    return launch_count_sample(*s, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_count_sample_host(const mmvae_count_sample_t* s) {
+    if (int rc = count_sample_check("debug_count_sample_host", s, true)) return rc;
+    host_count_sample(*s);
+    return 0;
+}
+
+int mmvae_zinb_sample(const float* d10, int64_t ldh, int H, const float* W, const float* b, const float* Wp, const float* bp,
+                      const float* Wr, const float* br, const mmvae_count_sample_t* s, void* stream) {
+    const char* who = "zinb_sample";
+    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = count_sample_check(who, s, false)) return rc;
+    if (s->param != 1) { set_error("%s: param = %d, the heads' mapping (1) is the only one", who, s->param); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
+    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, s->N, s->D)) return rc;
+    return launch_zinb_sample(d10, ldh, H, W, b, Wp, bp, Wr, br, *s, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- random forest on 256-bin features (forest.hip) ----

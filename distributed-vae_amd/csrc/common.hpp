@@ -1068,6 +1068,15 @@ int launch_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, cons
 int launch_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,
                       int64_t ldx, int64_t N, int D, double eps, void* ws, double* cell_sum, double* gene_sum, float* terms,
                       int64_t ld_t, hipStream_t st);
+// the sub-tiles' partials of zb_reduce (zb_tile.hpp) added in tile order: cell_sum [N], gene_sum [D]
+int zb_finish(void* ws, int64_t N, int D, double* cell_sum, double* gene_sum, hipStream_t st);
+// count distributions (countdist.hip); the host_ pair runs the element code on the host
+int launch_count_logp(const mmvae_count_logp_t& a, void* ws, hipStream_t st);
+int launch_count_sample(const mmvae_count_sample_t& s, hipStream_t st);
+int launch_zinb_sample(const float* d10, int64_t ldh, int H, const float* W, const float* b, const float* Wp, const float* bp,
+                       const float* Wr, const float* br, const mmvae_count_sample_t& s, hipStream_t st);
+void host_count_logp(const mmvae_count_logp_t& a);
+void host_count_sample(const mmvae_count_sample_t& s);
 // random forest on 256-bin features (forest.hip)
 constexpr int RF_THREADS = 256;        // threads of every workgroup: k_rf_fit one tree, k_rf_predict four rows (one a wave)
 constexpr int RF_BINS = 256;           // bins of a feature: one a thread of the candidate search, four a lane of the scan

@@ -662,6 +662,48 @@ class mixVAE_model(nn.Module):
         self._ctx = None
         return {"cell": cell, "gene": gene, "n": B}
 
+    @torch.no_grad()
+    def zinb_sample_batch(self, x, seed, temp=1.0, mask=None, offset=0, cell0=0, log1p=False, arms=None):
+        """One ZINB draw per (arm, cell, gene) of the batch ``x`` (as ``forward`` takes it) at the model's own codes: an eval
+        forward, then mmvae_zinb_sample per arm of ``arms`` (all by default) on the forward workspace's d10, as ``zinb_nll``
+        scores it.  Returns float32 [len(arms), B, D] on the device.  Every arm uses the same key, so two arms differ by
+        their heads alone.  Needs model.eval()."""
+        self._need_zinb("zinb_sample_batch()")
+        if self.training:
+            raise RuntimeError("zinb_sample_batch() needs model.eval()")
+        self._forward(x, temp, True, mask, False)
+        d10 = self._engine.ws_view("d10", self.fc_dim)
+        arms = list(range(self.n_arm)) if arms is None else [int(a) for a in arms]
+        out = torch.stack([N.zinb_sample(d10[a], *self._zinb_layers(a), seed=seed, offset=offset, cell0=cell0, log1p=log1p)
+                           for a in arms])
+        self._ctx = None
+        return out
+
+    def zinb_distribution(self, x_rec, x_p, x_r, eps=1e-6):
+        """The likelihood of ``zinb_loss`` as a distribution object: with r = x_rec + eps and p = (1 - eps)(x_p + eps) the NB has
+        ``theta = r`` and ``mu = r p / (1 - p)``, and z = (1 - eps)(x_r + eps) is the zero-inflation probability.  The three are
+        formed in fp64 from the heads (``decoder_zinb``'s device tensors) and rounded once to float32.  Returns a
+        ``utils.distributions.ZeroInflatedNegativeBinomial`` (``mean``, ``log_prob``, ``sample``)."""
+        from .utils.distributions import ZeroInflatedNegativeBinomial
+        self._need_zinb("zinb_distribution()")
+        N._need_cuda("zinb_distribution()", x_rec, x_p, x_r)
+        r = x_rec.detach().double() + eps
+        p = (1.0 - eps) * (x_p.detach().double() + eps)
+        z = (1.0 - eps) * (x_r.detach().double() + eps)
+        return ZeroInflatedNegativeBinomial(mu=(r * p / (1.0 - p)).float(), theta=r.float(), zi_probs=z.float())
+
+    @torch.no_grad()
+    def sample_zinb(self, c, s, arm, seed, offset=0, cell0=0, log1p=False):
+        """One count per (cell, gene) drawn from the model's ZINB likelihood at the codes c [N, C], s [N, S] of arm ``arm``: the
+        decode runs, then mmvae_zinb_sample forms the three heads of every tile from the decode workspace's d10 and draws in
+        the epilogue -- the N x D heads are never written.  Draws are keyed by (seed, offset, (cell0 + row) D + gene): batches
+        with ``cell0`` advancing equal one call.  Returns float32 [N, D] on the device, ``log1p`` of the counts on request (the
+        space the model's input lives in).  Refusals: those of ``decoder_zinb``."""
+        self._need_zinb("sample_zinb()")
+        _, eng = self._decode_run(c, s, arm)
+        return N.zinb_sample(eng.ws_view("d10", self.fc_dim)[0], *self._zinb_layers(int(arm)), seed=seed, offset=offset,
+                             cell0=cell0, log1p=log1p)
+
     def set_explicit_state_noise(self, u):
         """Test hook of ``state_changes`` (as ``set_explicit_noise`` is of ``forward``): u float32 [A, n_samp, B] on the
         device, the U(0,1) draws of the reference's ``torch.rand_like`` (nn_model.py:427) in its order -- arm, sample,

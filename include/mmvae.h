@@ -628,6 +628,94 @@ int mmvae_zinb_terms(const float *x_rec, int64_t ld_rec, const float *x_p, int64
                      double *cell_sum, double *gene_sum, float *terms /* NULL = not wanted */, int64_t ld_t,
                      void *stream);
 
+/* ---- count distributions (mmidas/utils/distributions.py) ----
+ * The scVI-parameterised likelihoods of count data and one draw per element of NB / ZINB.  All matrices are float32 [N, D],
+ * row-major, on the device, with a row pitch in elements; theta (and theta2) may be a vector [D], given with a pitch of 0.
+ * Everything behind the float32 inputs is fp64.  With lt = log(theta + mu + eps), per element:
+ *   kind 0, log_nb_positive:   theta (log(theta + eps) - lt) + x (log(mu + eps) - lt) + lgamma(x + theta) - lgamma(theta)
+ *                              - lgamma(x + 1), added in that order;
+ *   kind 1, log_zinb_positive: sp = softplus(-pi), ptl = -pi + theta (log(theta + eps) - lt);
+ *                              x < eps: softplus(ptl) - sp;   x > eps: -sp + ptl + x (log(mu + eps) - lt) + lgamma(x + theta)
+ *                              - lgamma(theta) - lgamma(x + 1);   x == eps: 0;   x NaN: NaN.  Only the selected branch is
+ *                              evaluated; the reference multiplies the other by an exact 0, which differs only where that
+ *                              other branch is not finite;
+ *   kind 2, log_mixture_nb:    l1 = nb(x, mu, theta), l2 = nb(x, mu2, theta2 or theta), b = l2 - pi:
+ *                              max(l1, b) + log1p(exp(-|l1 - b|)) - softplus(-pi).
+ *   softplus(a) = max(a, 0) + log1p(exp(-|a|)): the reference's softplus switches to the identity above 20, which this does
+ *   not.  Error of a term given its inputs: a few 2^-53 of the sum of the magnitudes of its addends, then one rounding to
+ *   float32.
+ * mmvae_count_logp.  Out, either or both: terms float32 [N, ld_t]; cell_sum double [N] and gene_sum double [D] (both or
+ *   neither), by the tile scheme of mmvae_zinb_terms: 64 x 64 tiles, a partial per 32 x 32 sub-tile, the partials added in
+ *   tile order.  No atomics: bit-identical from run to run, and a cell's sum depends on that cell's rows alone.
+ *   ws: mmvae_count_logp_workspace_bytes(N, D) = mmvae_zinb_terms_workspace_bytes(N, D), needed for the sums only.
+ *   MMVAE_E_BADARG for a null input that the kind needs, neither output, one sum without the other, N < 1 or N > 2^31,
+ *   D < 1, a pitch below D (0 excepted for theta and theta2), eps outside [0, 1), a kind outside 0..2, a misaligned ws;
+ *   MMVAE_E_UNSUPPORTED for more than 2^31 - 1 tiles; MMVAE_E_WORKSPACE for a ws below the size.
+ * mmvae_debug_count_logp_host: the same element code on the host, every pointer host memory, terms only; no GPU call. */
+typedef struct mmvae_count_logp {
+    int kind;                               /* 0 NB, 1 ZINB, 2 NB mixture */
+    int64_t N;
+    int D;
+    double eps;                             /* the reference's default: 1e-8 */
+    const float *x; int64_t ldx;
+    const float *mu; int64_t ld_mu;         /* mixture: mu_1 */
+    const float *theta; int64_t ld_theta;   /* mixture: theta_1; pitch 0: a vector [D] */
+    const float *pi; int64_t ld_pi;         /* ZINB: zero-inflation logits; mixture: mixture logits; NB: unused */
+    const float *mu2; int64_t ld_mu2;       /* mixture only */
+    const float *theta2; int64_t ld_theta2; /* mixture only; NULL = theta_1 */
+    float *terms; int64_t ld_t;             /* NULL = not wanted */
+    double *cell_sum; double *gene_sum;     /* NULL, NULL = not wanted */
+} mmvae_count_logp_t;
+size_t mmvae_count_logp_workspace_bytes(int64_t N, int D);
+int mmvae_count_logp(const mmvae_count_logp_t *a, void *ws, size_t ws_bytes, void *stream);
+int mmvae_debug_count_logp_host(const mmvae_count_logp_t *a);
+
+/* mmvae_count_sample: one draw per element.  param 0: a = mu, b = theta (pitch 0: a vector [D]), zi by zi_kind: 0 none (NB),
+ *   1 a logit, 2 a probability.  param 1: the model's heads a = x_rec, b = x_p, zi = x_r, mapped in fp64 under zinb_loss's
+ *   eps guards: theta = x_rec + eps, p = (1 - eps)(x_p + eps), mu = theta p / (1 - p), z = (1 - eps)(x_r + eps).
+ *   Steps: w ~ Gamma(shape theta, rate theta / mu); count ~ Poisson(min(w, 1e8)); ZINB: 0 where u <= z.  mu = 0 gives 0;
+ *   mu < 0, theta <= 0, a parameter that is not finite or a NaN zi give NaN (int32 out: -1) before any loop.
+ *   Out: float32 (log1p = 1: log1p of the count) or int32 (out_int32 = 1; log1p refused) [N, ld_out].
+ *   Randomness: Philox4x32-10, key = seed.  The call for element i = (cell0 + row) D + gene, stage s (0 gamma, 1 boost,
+ *   2 poisson, 3 inflation) and attempt t has the counter (i_lo, i_hi, (s + 4 t) ^ (offset_hi << 8), offset_lo);
+ *   offset < 2^56.  Words to uniforms: u52(lo, hi) = (((hi << 32 | lo) >> 12) + 0.5) 2^-52, u32(w) = (w + 0.5) 2^-32.
+ *     gamma, shape a >= 1 (Marsaglia-Tsang, d = a - 1/3, c = 1 / sqrt(9 d)), attempt t: n = sqrt(-2 log u52(w0, w1))
+ *       cos(2 pi u32(w2)), y = c n; rejected if y <= -1; accepted if log u32(w3) < n^2 / 2 + d (3 log1p(y) - y (3 + y (3 + y)))
+ *       with the value d (1 + y)^3.  theta < 1: shape theta + 1, times exp(log(u52 of (boost, 0)) / theta).
+ *     poisson, lam < 10: u = u52 of (poisson, 0); k rises from 0 while u > the running cdf (p <- p lam / k), to 64 at most.
+ *     poisson, lam >= 10: PTRS (Hoermann 1993), attempt t: U = u52(w0, w1) - 0.5, V = u52(w2, w3).
+ *     inflation: u52 of (inflation, 0).
+ *   A draw therefore depends on (seed, offset, i, its parameters) alone: batches with cell0 advancing equal the one call.
+ *   Both rejection loops stop after 64 attempts and the inversion at k = 64; an element that gets there takes the gamma's
+ *   mean (its shape) or floor(lam), and *exhausted (one int on the device, set by the call) counts such elements.
+ *   MMVAE_E_BADARG for a null pointer that the mode needs, N < 1 or N > 2^31, D < 1, a pitch below D (0 excepted for
+ *   param 0's b), cell0 < 0 or (cell0 + N) D >= 2^63, offset >= 2^56, eps outside [0, 1), log1p with out_int32, a param /
+ *   zi_kind outside their values.
+ * mmvae_zinb_sample: the three heads of every 64 x 64 tile from d10 [N, ldh] as mmvae_zinb_nll forms them, rounded to
+ *   float32 as mmvae_zinb_heads and the decode write them, then param 1's mapping and draw in the epilogue: bit for bit
+ *   mmvae_count_sample with param = 1 on the written heads.  Of *s it reads eps, N, D, cell0, seed, offset, out_int32, log1p,
+ *   out, ld_out, exhausted.  Refusals as mmvae_zinb_nll's and mmvae_count_sample's.
+ * mmvae_debug_count_sample_host: mmvae_count_sample's element code on the host, every pointer host memory; no GPU call. */
+typedef struct mmvae_count_sample {
+    int param;                              /* 0: (mu, theta[, zi]); 1: the heads (x_rec, x_p, x_r) */
+    int zi_kind;                            /* param 0: 0 none, 1 logit, 2 probability */
+    int64_t N;
+    int D;
+    int64_t cell0;                          /* the logical index of row 0 */
+    double eps;                             /* param 1 only */
+    uint64_t seed, offset;
+    const float *a; int64_t ld_a;
+    const float *b; int64_t ld_b;
+    const float *zi; int64_t ld_zi;
+    int out_int32, log1p;
+    void *out; int64_t ld_out;
+    int *exhausted;
+} mmvae_count_sample_t;
+int mmvae_count_sample(const mmvae_count_sample_t *s, void *stream);
+int mmvae_zinb_sample(const float *d10, int64_t ldh, int H, const float *W, const float *b, const float *Wp,
+                      const float *bp, const float *Wr, const float *br, const mmvae_count_sample_t *s, void *stream);
+int mmvae_debug_count_sample_host(const mmvae_count_sample_t *s);
+
 /* ---- random forest on 256-bin features (mmidas/utils/cluster_analysis.py: RF_classifier) ----
  * A forest under k-fold cross-validation on features quantised to 256 rank bins.  All arithmetic is integer up to one fp64
  * score per candidate split, so a tree is fixed by its inputs: bit-identical from run to run, independent of the order of
