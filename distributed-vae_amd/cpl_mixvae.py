@@ -755,6 +755,28 @@ class cpl_mixVAE:
             "cnss": cnss,
         }
 
+    def _encode_all(self, dl, counts=None):
+        """The device encode of every batch ``(x, index)`` of ``dl`` (``fill_latents``, under the category mask of
+        ``eval_model``) in eval mode, the training mode restored afterwards whether or not the pass raises -> (the [A, N, .]
+        float32 device buffers ``x_low``, ``c``, ``c_smp``, ``s_mean``, ``s_logvar`` and the int32 ``labels`` [A, N]; the
+        batches' indices, float64 [N] on the device).  ``counts``: the between-arm confusion counts to add to, or None."""
+        from ._utils import mk_masks
+        from .model import fill_latents
+        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
+        n_rows = len(dl.dataset)
+        pruning_mask = mk_masks(self.model.fcc[0].bias)[0]
+        f32 = dict(dtype=torch.float32, device=self.device)
+        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
+               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
+               "s_logvar": torch.zeros(A, n_rows, S, **f32),
+               "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=self.device)}
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return out, fill_latents(dl, [(self.model, pruning_mask, out, counts)], self.temp)
+        finally:
+            self.model.train(was_training)
+
     @torch.no_grad()
     def encode_dataset(self, dl, c_p=0, c_onehot=0):
         """``eval_model`` without everything that needs the decoder: the latents of every batch ``(x, index)`` of ``dl`` from
@@ -765,28 +787,15 @@ class cpl_mixVAE:
         the loss means are not in it."""
         if self.ref_prior:
             raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
-        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
-        n_rows = len(dl.dataset)
-        B = dl.batch_size
-        if B is None:
+        if dl.batch_size is None:
             raise ValueError("error: expected non-None value")            # unwrap(dl.batch_size), cpl_mixvae.py:104-107
-        dev = self.device
-        was_training = self.model.training
-        self.model.eval()
-        bias = self.model.fcc[0].bias.detach().cpu().numpy()
-        pruning_mask = np.where(bias != 0.0)[0]
-        prune_indx = np.where(bias == 0.0)[0]
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
-               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
-               "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
-        from ._utils import confmat_counts, consensus_from_counts
-        from .model import fill_latents
-        counts = confmat_counts(A, Cc, dev)
-        data_indx = fill_latents(dl, [(self.model, pruning_mask, out, counts if A > 1 else None)], self.temp)
+        from ._utils import confmat_counts, consensus_from_counts, mk_masks
+        A = self.n_arm
+        counts = confmat_counts(A, self.n_categories, self.device)
+        out, data_indx = self._encode_all(dl, counts if A > 1 else None)
+        prune_indx = mk_masks(self.model.fcc[0].bias)[1]
         prob = out["c"].max(dim=-1).values
-        cnss = float(np.mean(consensus_from_counts(counts).cpu().numpy())) if A > 1 and n_rows else float("nan")
-        self.model.train(was_training)
+        cnss = float(np.mean(consensus_from_counts(counts).cpu().numpy())) if A > 1 and len(dl.dataset) else float("nan")
         to64 = lambda t: t.double().cpu().numpy()
         lab1 = to64(out["labels"]) + 1.0
         return {
@@ -893,27 +902,15 @@ class cpl_mixVAE:
             raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
         if not 0 <= int(arm) < self.n_arm:
             raise ValueError(f"arm = {arm} outside [0, {self.n_arm})")
-        from .model import fill_latents
         from .utils.dataloader import DeviceLoader
         from .utils.tree_based_analysis import grouped_state_corr
-        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
-        dev = self.device
+        Cc = self.n_categories
         resident = isinstance(dl, DeviceLoader)
         if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
             raise ValueError("state_gene_corr needs a loader that serves every row once (no drop_last, no sharding)")
         if not resident:
-            dl = _Replay(dl, dev)                                         # one walk of the loader: the same batches twice
-        n_rows = len(dl.dataset)
-        was_training = self.model.training
-        self.model.eval()
-        bias = self.model.fcc[0].bias.detach().cpu().numpy()
-        pruning_mask = np.where(bias != 0.0)[0]
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
-               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
-               "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
-        inds = fill_latents(dl, [(self.model, pruning_mask, out, None)], self.temp)
-        self.model.train(was_training)
+            dl = _Replay(dl, self.device)                                 # one walk of the loader: the same batches twice
+        out, inds = self._encode_all(dl)
         if resident:
             data, rows = dl.data, inds.to(torch.int64)                     # the batches' indices are rows of the matrix
         else:
@@ -939,9 +936,7 @@ class cpl_mixVAE:
             raise NotImplementedError("classify_latents is not data-parallel: run it on one rank, outside the process group")
         from .utils import cluster_analysis as CA
         points, y, data_indx = self._latents_to_classify(dl, labels, arm, on, "classify_latents")
-        acc, ref, pred, res = CA.classify_points(points, y, kfold, seed, kind)
-        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
-                "data_indx": data_indx}
+        return self._cv_result(CA.classify_points(points, y, kfold, seed, kind), data_indx)
 
     @torch.no_grad()
     def classify_tree(self, dl, labels, list_changes, leaves, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", levels=None):
@@ -974,26 +969,11 @@ class cpl_mixVAE:
         names = {"x_low": "x_low", "state_mu": "s_mean", "z_prob": "c"}
         if on not in names:
             raise ValueError(f"on = {on!r}: one of {sorted(names) + list(also)}")
-        from .model import fill_latents
         from .utils.dataloader import DeviceLoader
-        A, Cc, L, S = self.n_arm, self.n_categories, self.lowD_dim, self.state_dim
-        dev = self.device
         resident = isinstance(dl, DeviceLoader)
         if resident and (dl.world_size > 1 or (dl.drop_last and len(dl.dataset) % dl.batch_size)):
             raise ValueError(f"{who} needs a loader that serves every row once (no drop_last, no sharding)")
-        if not resident:
-            dl = _Replay(dl, dev)
-        n_rows = len(dl.dataset)
-        was_training = self.model.training
-        self.model.eval()
-        bias = self.model.fcc[0].bias.detach().cpu().numpy()
-        pruning_mask = np.where(bias != 0.0)[0]
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = {"x_low": torch.zeros(A, n_rows, L, **f32), "c": torch.zeros(A, n_rows, Cc, **f32),
-               "c_smp": torch.zeros(A, n_rows, Cc, **f32), "s_mean": torch.zeros(A, n_rows, S, **f32),
-               "s_logvar": torch.zeros(A, n_rows, S, **f32), "labels": torch.zeros(A, n_rows, dtype=torch.int32, device=dev)}
-        inds = fill_latents(dl, [(self.model, pruning_mask, out, None)], self.temp)
-        self.model.train(was_training)
+        out, inds = self._encode_all(dl if resident else _Replay(dl, self.device))
         data_indx = inds.cpu().numpy()
         return out[names[on]][int(arm)], np.asarray(labels)[data_indx.astype(np.int64)], data_indx
 
@@ -1015,6 +995,15 @@ class cpl_mixVAE:
         data_indx = inds.cpu().numpy()
         return data, rows, np.asarray(labels)[data_indx.astype(np.int64)], data_indx
 
+    @staticmethod
+    def _cv_result(classified, data_indx, per=1.0):
+        """The dict of ``classify_latents``, ``classify_pcs`` and ``classify_forest`` from the (acc, ref_labels, pred_labels,
+        prediction dict) of one label set; ``margin`` = (best - second) / ``per``: the scores' difference as it is, or the
+        votes' as a share of the ``per`` trees."""
+        acc, ref, pred, res = classified
+        margin = (res["best"].astype(np.float64) - res["second"].astype(np.float64)) / per
+        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": margin, "fold": res["fold"], "data_indx": data_indx}
+
     @torch.no_grad()
     def classify_pcs(self, dl, labels, num_pc: int = 10, kfold: int = 10, seed=0, kind: str = "qda"):
         """The linear baseline beside ``classify_latents``: how well the same Gaussian classifier recovers ``labels`` from
@@ -1033,9 +1022,7 @@ class cpl_mixVAE:
         data, rows, y, data_indx = self._expression_to_classify(dl, labels, "classify_pcs")
         checked = CA._cv_refusals(y, int(data_indx.shape[0]), kfold, seed, kind)       # every refusal before any device work
         z = pca_project(data, num_pc, rows=rows, out="device")
-        acc, ref, pred, res = CA.classify_points(z, y, kfold, seed, kind, checked)
-        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": res["best"] - res["second"], "fold": res["fold"],
-                "data_indx": data_indx}
+        return self._cv_result(CA.classify_points(z, y, kfold, seed, kind, checked), data_indx)
 
     @torch.no_grad()
     def classify_forest(self, dl, labels, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", n_trees: int = 100,
@@ -1060,9 +1047,8 @@ class cpl_mixVAE:
         else:
             points, y, data_indx = self._latents_to_classify(dl, labels, arm, on, "classify_forest", also=("pcs",))
             checked = CA._forest_refusals(y, int(points.shape[0]), int(points.shape[1]), kfold, seed, n_trees, "sqrt")
-        acc, ref, pred, res = CA.classify_forest_points(CA._bins_on_device(points), y, kfold, seed, n_trees, checked)
-        margin = (res["best"].astype(np.float64) - res["second"].astype(np.float64)) / float(n_trees)
-        return {"acc": acc, "ref_labels": ref, "pred_labels": pred, "margin": margin, "fold": res["fold"], "data_indx": data_indx}
+        return self._cv_result(CA.classify_forest_points(CA._bins_on_device(points), y, kfold, seed, n_trees, checked), data_indx,
+                               float(n_trees))
 
 
 class _Replay:

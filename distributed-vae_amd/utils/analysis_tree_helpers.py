@@ -19,11 +19,11 @@ from __future__ import annotations
 from collections import deque
 
 import numpy as np
-import torch
 
 from .. import _native as N
 from .. import dist as D
 from .._utils import float32_on_device
+from .cluster_analysis import _moments_on_device, _scores_by_fold, _shape_of, fold_training_moments, kfold_of
 
 LEAF_REG = 1e-4                 # the reference's cov + 1e-4 I (predict_leaf_gmm)
 SINGULAR_EPS = 1e6 * 2.0 ** -52  # scipy's multivariate_normal: an eigenvalue at or below this share of the largest counts as 0
@@ -212,19 +212,6 @@ def parse_dend(htree_file):
 
 
 # ---- the leaf models ------------------------------------------------------------------------------------------------------
-def _shape_of(x, who, name):
-    if not hasattr(x, "shape"):
-        x = np.asarray(x)
-    if len(x.shape) != 2:
-        raise ValueError(f"{who}: {name} of shape {tuple(x.shape)} is not [n, d]")
-    n, d = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= d <= N.GAUSSCLF_MAX_D:
-        raise NotImplementedError(f"{who}: d = {d} outside [1, {N.GAUSSCLF_MAX_D}]")
-    if n < 1:
-        raise ValueError(f"{who}: {name} has no rows")
-    return n, d
-
-
 def _labels_of(lbl, n, who, name):
     y = np.asarray(lbl)
     if y.ndim != 1 or y.shape[0] != n:
@@ -263,27 +250,16 @@ def models_from_leaf_moments(s, M, counts, pivot, logw, n_per_class_thr, diag_co
     N <= n_per_class_thr.  ValueError naming the leaf (``names[l]``, or its index) where C is singular by scipy's rule for
     ``multivariate_normal`` (smallest eigenvalue <= 1e6 x 2^-52 x the largest), where the reference raises ``LinAlgError``."""
     L, F, d = s.shape
-    iu = np.triu_indices(d)
     pivot = np.asarray(pivot, dtype=np.float64)
     mu, W, c0 = np.zeros((F, L, d)), np.zeros((F, L, d, d)), np.full((F, L), -np.inf)
     train = np.zeros((F, L), dtype=np.int64)
-    for f in range(F):
-        cnt, s_tr, M_tr = np.zeros(L), np.zeros((L, d)), np.zeros((L, M.shape[2]))
-        for g in range(F):
-            if g != f or F == 1:
-                cnt += counts[:, g]
-                s_tr += s[:, g]
-                M_tr += M[:, g]
+    for f, (cnt, offset, scatter) in enumerate(fold_training_moments(s, M, counts)):
         train[f] = cnt.astype(np.int64)
         have = np.flatnonzero(cnt > n_per_class_thr)
         if have.size == 0:
             continue
-        Nk = cnt[have][:, None]
-        mu[f, have] = pivot[None] + s_tr[have] / Nk
-        full = np.zeros((have.size, d, d))
-        full[:, iu[0], iu[1]] = M_tr[have]
-        full[:, iu[1], iu[0]] = M_tr[have]
-        C = (full - s_tr[have][:, :, None] * s_tr[have][:, None, :] / Nk[:, :, None]) / (Nk[:, :, None] - 1.0) + reg * np.eye(d)[None]
+        mu[f, have] = pivot[None] + offset[have]
+        C = scatter[have] / (cnt[have][:, None, None] - 1.0) + reg * np.eye(d)[None]
         diag = cnt[have] < diag_cov_n_sample_thr
         C[diag] = C[diag] * np.eye(d)[None]
         lam, V = np.linalg.eigh(C)
@@ -299,21 +275,9 @@ def models_from_leaf_moments(s, M, counts, pivot, logw, n_per_class_thr, diag_co
 def _fit(train_dev, codes, L, fold, F, logw, n_per_class_thr, diag_cov_n_sample_thr, reg, who, names):
     """One ``group_moments`` launch over the training cells of the leaves (``codes`` >= 0) sorted by (leaf, fold) and the host
     models of it; ``pivot`` is the mean of all training cells."""
-    d, dev = int(train_dev.shape[1]), train_dev.device
-    rows = np.flatnonzero(codes >= 0)
-    group = codes[rows] * F + (fold[rows] if fold is not None else 0)
-    order = rows[np.argsort(group, kind="stable")]
-    counts = np.bincount(group, minlength=L * F).astype(np.int64)
-    pivot = train_dev.mean(dim=0)
-    if rows.size:
-        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        perm = torch.from_numpy(order.astype(np.int64)).to(dev)
-        s, M = N.group_moments(train_dev.index_select(0, perm), torch.from_numpy(offsets).to(dev), pivot)
-        s, M = s.cpu().numpy().reshape(L, F, d), M.cpu().numpy().reshape(L, F, -1)
-    else:
-        s, M = np.zeros((L, F, d)), np.zeros((L, F, d * (d + 1) // 2))
-    mu, W, c0, train = models_from_leaf_moments(s, M, counts.reshape(L, F).astype(np.float64), pivot.cpu().numpy(), logw,
-                                                n_per_class_thr, diag_cov_n_sample_thr, reg, who, names)
+    s, M, counts, pivot = _moments_on_device(train_dev, codes, L, fold, F)
+    mu, W, c0, train = models_from_leaf_moments(s, M, counts, pivot.cpu().numpy(), logw, n_per_class_thr, diag_cov_n_sample_thr,
+                                                reg, who, names)
     return {"mu": mu, "W": W, "c0": c0, "counts": train, "pivot": pivot.cpu().numpy().astype(np.float64)}
 
 
@@ -345,7 +309,7 @@ def leaf_gaussians(train_z, true_train_lbl, unique_leaf_lbl, n_per_class_thr=6, 
     who = "leaf_gaussians"
     if D.is_dist():
         raise NotImplementedError(f"{who} is not data-parallel: run it on one rank, outside the process group")
-    n, d = _shape_of(train_z, who, "train_z")
+    n, d = _shape_of(train_z, N.GAUSSCLF_MAX_D, min_n=1, who=who, name="train_z")
     lbl = _labels_of(true_train_lbl, n, who, "true_train_lbl")
     leaves, logw = _leaf_refusals(who, unique_leaf_lbl, label_weight, n_per_class_thr)
     F = 1
@@ -366,16 +330,7 @@ def leaf_gaussians(train_z, true_train_lbl, unique_leaf_lbl, n_per_class_thr=6, 
 
 def _scores(x_dev, models, fold=None):
     """float64 [n, L] on the device: every cell's log weight + log density under every leaf (of its fold's model)."""
-    dev = x_dev.device
-    mu, W, c0 = (torch.from_numpy(np.ascontiguousarray(models[k])).to(dev) for k in ("mu", "W", "c0"))
-    n = int(x_dev.shape[0])
-    if fold is None:
-        model = torch.zeros(n, dtype=torch.int32, device=dev)
-        return N.gauss_scores(x_dev, model, mu, W, c0, None, True)[3]
-    by_fold = np.argsort(fold, kind="stable")
-    perm = torch.from_numpy(by_fold.astype(np.int64)).to(dev)
-    model = torch.from_numpy(fold[by_fold].astype(np.int32)).to(dev)
-    return N.gauss_scores(x_dev.index_select(0, perm), model, mu, W, c0, perm, True)[3]
+    return _scores_by_fold(x_dev, models["mu"], models["W"], models["c0"], fold, True)[3]
 
 
 def _label_lists(who, dataset_lbl, leaves, descendant_dict):
@@ -448,8 +403,8 @@ def predict_leaf_gmm(train_z, true_train_lbl, test_z, true_test_lbl=None, n_per_
 
 def _prepare(who, train_z, true_train_lbl, test_z, true_test_lbl, unique_leaf_lbl, label_weight, n_per_class_thr):
     """(leaves, log weights, training labels, test labels or None) after the refusals that need no device."""
-    n, d = _shape_of(train_z, who, "train_z")
-    n_test, d_test = _shape_of(test_z, who, "test_z")
+    n, d = _shape_of(train_z, N.GAUSSCLF_MAX_D, min_n=1, who=who, name="train_z")
+    n_test, d_test = _shape_of(test_z, N.GAUSSCLF_MAX_D, min_n=1, who=who, name="test_z")
     if d_test != d:
         raise ValueError(f"{who}: test_z has {d_test} columns and train_z {d}")
     train_lbl = _labels_of(true_train_lbl, n, who, "true_train_lbl")
@@ -475,7 +430,7 @@ def custom_QDA(train_z, true_train_lbl, test_z, true_test_lbl, n_per_class_thr=6
         raise NotImplementedError(f"{who} is not data-parallel: run it on one rank, outside the process group")
     if true_test_lbl is None:
         raise ValueError(f"{who}: true_test_lbl is needed: the classes are those of the train and the test labels")
-    n_test, _ = _shape_of(test_z, who, "test_z")
+    n_test, _ = _shape_of(test_z, N.GAUSSCLF_MAX_D, min_n=1, who=who, name="test_z")
     test_all = _labels_of(true_test_lbl, n_test, who, "true_test_lbl")
     classes = np.unique(np.concatenate([np.asarray(true_train_lbl).reshape(-1), test_all]))
     leaves, logw, train_lbl, test_lbl = _prepare(who, train_z, true_train_lbl, test_z, test_all, classes, None, n_per_class_thr)
@@ -483,9 +438,7 @@ def custom_QDA(train_z, true_train_lbl, test_z, true_test_lbl, n_per_class_thr=6
     test_dev = float32_on_device(test_z, train_dev.device, "test_z", "[n, d]", check_device_finite=True)
     models = _fit(train_dev, _codes_of(train_lbl, leaves), len(leaves), None, 1, logw, n_per_class_thr, diag_cov_n_sample_thr, 0.0,
                   who, leaves)
-    dev = test_dev.device
-    mu, W, c0 = (torch.from_numpy(np.ascontiguousarray(models[k])).to(dev) for k in ("mu", "W", "c0"))
-    label = N.gauss_scores(test_dev, torch.zeros(n_test, dtype=torch.int32, device=dev), mu, W, c0, None, False)[0]
+    label = _scores_by_fold(test_dev, models["mu"], models["W"], models["c0"], None, False)[0]
     excluded = leaves[models["counts"][0] <= n_per_class_thr]
     pred = _roomy(leaves[label.cpu().numpy().astype(np.int64)], ["excluded"] if len(excluded) else [])
     true = _roomy(test_all, ["excluded"] if len(excluded) else [])
@@ -584,7 +537,6 @@ def classify_tree_points(x_dev, y, list_changes, leaves, kfold, seed, levels=Non
     ``mmvae_gauss_scores`` launch with F = kfold models, one ``mmvae_leaf_merge``).  Returns ``n_classes`` [T], ``acc``
     [kfold, T] (over the fold's kept cells: those whose label is a leaf that has a model in their fold; NaN where a fold keeps
     none), ``pred`` [T, n] (labels), ``prob`` [T, n], ``keep`` [n], ``fold`` [n], ``levels``."""
-    from .cluster_analysis import kfold_of
     who = "classify_tree"
     y = np.asarray(y)
     n = int(x_dev.shape[0])

@@ -230,28 +230,40 @@ def _lda_models(counts, scatter):
     return np.broadcast_to(Wone, (K, d, d)), c0
 
 
+def fold_training_moments(s, M, counts):
+    """The training moments of every fold, one fold at a time, from the moments of the K x F (class, fold) groups about one
+    pivot: ``s`` [K, F, d], ``M`` [K, F, d (d + 1) / 2] (``mmvae_group_moments``), ``counts`` [K, F].  The training set of
+    fold f is the sum of the groups of the other folds, added in fold order from zeros with no subtraction (F = 1: the one
+    group is the training set).  Yields, fold after fold, for all K classes: (the training count N [K], the mean's offset
+    from the pivot s / max(N, 1) [K, d], scatter = M - s s^T / max(N, 1) [K, d, d]).  Every builder of fold models reads
+    these sums, so the order of the additions, which decides the bits, is stated once; one fold's [K, d, d] is alive at a
+    time, never all folds'."""
+    K, F, d = s.shape
+    iu = np.triu_indices(d)
+    for f in range(F):
+        cnt, s_tr, M_tr = np.zeros(K), np.zeros((K, d)), np.zeros((K, M.shape[2]))
+        for g in range(F):
+            if g != f or F == 1:
+                cnt += counts[:, g]
+                s_tr += s[:, g]
+                M_tr += M[:, g]
+        Nk = np.maximum(cnt, 1.0)[:, None]
+        full = np.zeros((K, d, d))
+        full[:, iu[0], iu[1]] = M_tr
+        full[:, iu[1], iu[0]] = M_tr
+        yield cnt, s_tr / Nk, full - s_tr[:, :, None] * s_tr[:, None, :] / Nk[:, :, None]
+
+
 def models_from_moments(s, M, counts, pivot, kind, reg_param=QDA_REG_PARAM):
     """The F models of a k-fold cross-validation from the moments of the K x F (class, fold) groups about ``pivot``:
     ``s`` [K, F, d], ``M`` [K, F, d (d + 1) / 2] (``mmvae_group_moments``), ``counts`` [K, F] -> (mu [F, K, d],
     W [F, K, d, d], c0 [F, K]) in fp64.  The training set of fold f is the sum of the groups of the other folds, added in
     fold order with no subtraction; mean = pivot + s / N, scatter = M - s s^T / N."""
     K, F, d = s.shape
-    iu = np.triu_indices(d)
     pivot = np.asarray(pivot, dtype=np.float64)
     mu, W, c0 = np.zeros((F, K, d)), np.zeros((F, K, d, d)), np.zeros((F, K))
-    for f in range(F):
-        cnt, s_tr, M_tr = np.zeros(K), np.zeros((K, d)), np.zeros((K, M.shape[2]))
-        for g in range(F):
-            if g != f:
-                cnt += counts[:, g]
-                s_tr += s[:, g]
-                M_tr += M[:, g]
-        Nk = np.maximum(cnt, 1.0)[:, None]
-        mu[f] = pivot[None] + s_tr / Nk
-        full = np.zeros((K, d, d))
-        full[:, iu[0], iu[1]] = M_tr
-        full[:, iu[1], iu[0]] = M_tr
-        scatter = full - s_tr[:, :, None] * s_tr[:, None, :] / Nk[:, :, None]
+    for f, (cnt, offset, scatter) in enumerate(fold_training_moments(s, M, counts)):
+        mu[f] = pivot[None] + offset
         if kind == "qda":
             W[f], c0[f] = _qda_models(cnt, scatter, reg_param)
         else:
@@ -259,25 +271,47 @@ def models_from_moments(s, M, counts, pivot, kind, reg_param=QDA_REG_PARAM):
     return mu, W, c0
 
 
+def _moments_on_device(x_dev, codes, K, fold, F):
+    """One ``group_moments`` launch over the rows of ``x_dev`` that have a code (``codes`` in [0, K); -1: the row is left
+    out), stable-sorted by (code, fold) (``fold`` None: F = 1, by code alone) -> (s [K, F, d], M [K, F, d (d + 1) / 2],
+    counts [K, F], fp64 numpy; the pivot, on the device): the mean of ALL rows of ``x_dev``.  No row with a code: zeros and
+    no launch."""
+    d, dev = int(x_dev.shape[1]), x_dev.device
+    group = (codes + 1) * F + (fold if fold is not None else 0)                    # class-major: [1 + K, F], code -1 first
+    counts = np.bincount(group, minlength=(K + 1) * F).astype(np.int64)
+    order = np.argsort(group, kind="stable")[counts[:F].sum():]                    # without the rows that have no code
+    counts = counts[F:]
+    pivot = x_dev.mean(dim=0)                               # any pivot gives the same moments in exact arithmetic; the data's
+    if order.size:                                          # mean keeps kappa = 1 + (mean - pivot)^2 / var as small as one pivot can
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        perm = torch.from_numpy(order.astype(np.int64)).to(dev)
+        s, M = N.group_moments(x_dev.index_select(0, perm), torch.from_numpy(offsets).to(dev), pivot)
+        s, M = s.cpu().numpy().reshape(K, F, d), M.cpu().numpy().reshape(K, F, -1)
+    else:
+        s, M = np.zeros((K, F, d)), np.zeros((K, F, d * (d + 1) // 2))
+    return s, M, counts.reshape(K, F).astype(np.float64), pivot
+
+
+def _scores_by_fold(x_dev, mu, W, c0, fold, return_scores):
+    """``gauss_scores``' (label, best, second, scores) in the caller's order for the host models ``mu`` [F, K, d], ``W``
+    [F, K, d, d], ``c0`` [F, K]: every cell under its own fold's model (the rows go to the kernel sorted by fold, with the
+    permutation), or with ``fold`` None all of them under model 0."""
+    dev = x_dev.device
+    mu, W, c0 = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (mu, W, c0))
+    if fold is None:
+        model = torch.zeros(int(x_dev.shape[0]), dtype=torch.int32, device=dev)
+        return N.gauss_scores(x_dev, model, mu, W, c0, None, return_scores)
+    by_fold = np.argsort(fold, kind="stable")
+    perm = torch.from_numpy(by_fold.astype(np.int64)).to(dev)
+    model = torch.from_numpy(fold[by_fold].astype(np.int32)).to(dev)
+    return N.gauss_scores(x_dev.index_select(0, perm), model, mu, W, c0, perm, return_scores)
+
+
 def _cv_on_device(x_dev, codes, classes, fold, kfold, kind, reg_param, return_scores):
     """The two launches and the host factorisations between them, for points already on the device."""
-    n, d = (int(v) for v in x_dev.shape)
-    K, dev = len(classes), x_dev.device
-    group = codes * kfold + fold                                                    # class-major: [K, F]
-    order = np.argsort(group, kind="stable")
-    counts = np.bincount(group, minlength=K * kfold).astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    pivot = x_dev.mean(dim=0)                               # any pivot gives the same moments in exact arithmetic; the data's
-    perm = torch.from_numpy(order.astype(np.int64)).to(dev)  # mean keeps kappa = 1 + (mean - pivot)^2 / var as small as one pivot can
-    s, M = N.group_moments(x_dev.index_select(0, perm), torch.from_numpy(offsets).to(dev), pivot)
-    mu, W, c0 = models_from_moments(s.cpu().numpy().reshape(K, kfold, d), M.cpu().numpy().reshape(K, kfold, -1),
-                                    counts.reshape(K, kfold).astype(np.float64), pivot.cpu().numpy(), kind, reg_param)
-    by_fold = np.argsort(fold, kind="stable")
-    perm2 = torch.from_numpy(by_fold.astype(np.int64)).to(dev)
-    model = torch.from_numpy(fold[by_fold].astype(np.int32)).to(dev)
-    label, best, second, scores = N.gauss_scores(x_dev.index_select(0, perm2), model, torch.from_numpy(mu).to(dev),
-                                                 torch.from_numpy(np.ascontiguousarray(W)).to(dev), torch.from_numpy(c0).to(dev),
-                                                 perm2, return_scores)
+    s, M, counts, pivot = _moments_on_device(x_dev, codes, len(classes), fold, kfold)
+    mu, W, c0 = models_from_moments(s, M, counts, pivot.cpu().numpy(), kind, reg_param)
+    label, best, second, scores = _scores_by_fold(x_dev, mu, W, c0, fold, return_scores)
     out = {"pred": label.cpu().numpy().astype(np.int64), "fold": fold, "best": best.cpu().numpy(),
            "second": second.cpu().numpy(), "classes": classes}
     if return_scores:
@@ -285,10 +319,8 @@ def _cv_on_device(x_dev, codes, classes, fold, kfold, kind, reg_param, return_sc
     return out
 
 
-def _cv_refusals(labels, n, kfold, seed, kind):
-    """(classes, codes, fold) after every refusal that needs no device."""
-    if kind not in ("qda", "lda"):
-        raise ValueError(f"kind = {kind!r}: one of 'qda', 'lda'")
+def _label_refusals(labels, n, kfold):
+    """The labels as an array, after the refusals every cross-validated classifier begins with."""
     y = np.asarray(labels)
     if y.ndim != 1:
         raise ValueError(f"labels of shape {y.shape} are not 1-D")
@@ -296,6 +328,14 @@ def _cv_refusals(labels, n, kfold, seed, kind):
         raise ValueError(f"{y.shape[0]} labels for {n} samples")
     if int(kfold) != kfold or not 2 <= kfold <= n:
         raise ValueError(f"kfold = {kfold} outside [2, n = {n}]")
+    return y
+
+
+def _cv_refusals(labels, n, kfold, seed, kind):
+    """(classes, codes, fold) after every refusal that needs no device."""
+    if kind not in ("qda", "lda"):
+        raise ValueError(f"kind = {kind!r}: one of 'qda', 'lda'")
+    y = _label_refusals(labels, n, kfold)
     classes, codes = np.unique(y, return_inverse=True)
     codes = codes.reshape(-1)
     if len(classes) < 2:
@@ -312,15 +352,22 @@ def _cv_refusals(labels, n, kfold, seed, kind):
     return classes, codes, fold
 
 
-def _shape_of(x):
+def _shape_of(x, max_d, max_n=None, min_n=0, who="", name="x"):
+    """(n, d) of the points ``x`` after the refusals of its shape: 1 <= d <= ``max_d``, ``min_n`` <= n <= ``max_n``.  The
+    messages begin with the function's name ``who``, where one is given, and call ``x`` ``name``."""
+    lead = f"{who}: " if who else ""
     if not hasattr(x, "shape"):
         x = np.asarray(x)
     if len(x.shape) != 2:
-        raise ValueError(f"x of shape {tuple(x.shape)} is not [n, d]")
+        raise ValueError(f"{lead}{name} of shape {tuple(x.shape)} is not [n, d]")
     n, d = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= d <= N.GAUSSCLF_MAX_D:
-        raise NotImplementedError(f"d = {d} outside [1, {N.GAUSSCLF_MAX_D}]")
-    return n
+    if not 1 <= d <= max_d:
+        raise NotImplementedError(f"{lead}d = {d} outside [1, {max_d}]")
+    if max_n is not None and n > max_n:
+        raise NotImplementedError(f"{lead}n = {n} above {max_n}")
+    if n < min_n:
+        raise ValueError(f"{lead}{name} has no rows")
+    return n, d
 
 
 def gaussian_cv_predict(x, labels, kfold, seed, kind="qda", reg_param=QDA_REG_PARAM, return_scores=False, device=None):
@@ -351,9 +398,22 @@ def gaussian_cv_predict(x, labels, kfold, seed, kind="qda", reg_param=QDA_REG_PA
     NotImplementedError under a process group and past d = 128, 4096 classes or 64 folds."""
     if D.is_dist():
         raise NotImplementedError("gaussian_cv_predict is not data-parallel: run it on one rank, outside the process group")
-    n = _shape_of(x)
+    n, _ = _shape_of(x, N.GAUSSCLF_MAX_D)
     classes, codes, fold = _cv_refusals(labels, n, kfold, seed, kind)
     return _cv_on_device(_points_on_device(x, device), codes, classes, fold, int(kfold), kind, float(reg_param), return_scores)
+
+
+def _fold_lists(y, classes, pred, fold, kfold):
+    """(acc, ref_labels, pred_labels) of the predicted codes ``pred``: lists over the folds, every test set in ascending order
+    of the cell index."""
+    acc, ref_labels, pred_labels = [], [], []
+    for f in range(int(kfold)):
+        test = np.flatnonzero(fold == f)
+        predicted = classes[pred[test]]
+        acc.append(float(np.average(y[test] == predicted)))                        # sklearn's accuracy_score
+        pred_labels.append(predicted)
+        ref_labels.append(y[test])
+    return acc, ref_labels, pred_labels
 
 
 def classify_points(x_dev, y, kfold, seed, kind, checked=None):
@@ -362,25 +422,28 @@ def classify_points(x_dev, y, kfold, seed, kind, checked=None):
     y = np.asarray(y)
     classes, codes, fold = checked if checked is not None else _cv_refusals(y, int(x_dev.shape[0]), kfold, seed, kind)
     res = _cv_on_device(x_dev, codes, classes, fold, int(kfold), kind, QDA_REG_PARAM, False)
-    acc, ref_labels, pred_labels = [], [], []
-    for f in range(int(kfold)):
-        test = np.flatnonzero(fold == f)
-        pred = classes[res["pred"][test]]
-        acc.append(float(np.average(y[test] == pred)))                             # sklearn's accuracy_score
-        pred_labels.append(pred)
-        ref_labels.append(y[test])
-    return acc, ref_labels, pred_labels, res
+    return (*_fold_lists(y, classes, res["pred"], fold, kfold), res)
 
 
 def _classifier(data, labels, kfold, seed, kind):
+    """The three classifiers over a dict of label sets, ``kind`` "qda", "lda" or "rf": every key's refusals before any device
+    work, one upload (and for the forest one binning) for all keys, then the keys in the dict's order."""
     if D.is_dist():
         raise NotImplementedError(f"{kind.upper()}_classifier is not data-parallel: run it on one rank, outside the process group")
-    n = _shape_of(data)
-    checked = {key: _cv_refusals(labels[key], n, kfold, seed, kind) for key in labels}      # every refusal before any device work
-    x_dev = _points_on_device(data, None)
+    forest = kind == "rf"
+    n, d = _shape_of(data, N.FOREST_MAX_D, N.FOREST_MAX_N) if forest else _shape_of(data, N.GAUSSCLF_MAX_D)
+    checked = {key: _forest_refusals(labels[key], n, d, kfold, seed, FOREST_TREES, "sqrt") if forest
+               else _cv_refusals(labels[key], n, kfold, seed, kind) for key in labels}
+    points = _points_on_device(data, None)
+    if forest:
+        points = _bins_on_device(points)
     acc, ref_labels, pred_labels = {}, {}, {}
     for key in checked:
-        acc[key], ref_labels[key], pred_labels[key], _ = classify_points(x_dev, labels[key], kfold, seed, kind, checked[key])
+        if forest:
+            out = classify_forest_points(points, labels[key], kfold, seed, FOREST_TREES, checked[key])
+        else:
+            out = classify_points(points, labels[key], kfold, seed, kind, checked[key])
+        acc[key], ref_labels[key], pred_labels[key], _ = out
     return acc, ref_labels, pred_labels
 
 
@@ -425,28 +488,9 @@ def quantile_bins(x, device=None) -> torch.Tensor:
     return _bins_on_device(_points_on_device(x, device))
 
 
-def _forest_shape_of(x):
-    if not hasattr(x, "shape"):
-        x = np.asarray(x)
-    if len(x.shape) != 2:
-        raise ValueError(f"x of shape {tuple(x.shape)} is not [n, d]")
-    n, d = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= d <= N.FOREST_MAX_D:
-        raise NotImplementedError(f"d = {d} outside [1, {N.FOREST_MAX_D}]")
-    if n > N.FOREST_MAX_N:
-        raise NotImplementedError(f"n = {n} above {N.FOREST_MAX_N}")
-    return n, d
-
-
 def _forest_refusals(labels, n, d, kfold, seed, n_trees, max_features):
     """(classes, codes, fold, mtry) after every refusal that needs no device."""
-    y = np.asarray(labels)
-    if y.ndim != 1:
-        raise ValueError(f"labels of shape {y.shape} are not 1-D")
-    if y.shape[0] != n:
-        raise ValueError(f"{y.shape[0]} labels for {n} samples")
-    if int(kfold) != kfold or not 2 <= kfold <= n:
-        raise ValueError(f"kfold = {kfold} outside [2, n = {n}]")
+    y = _label_refusals(labels, n, kfold)
     if int(n_trees) != n_trees or n_trees < 1:
         raise ValueError(f"n_trees = {n_trees} below 1")
     if max_features == "sqrt":
@@ -510,7 +554,7 @@ def forest_cv_predict(x, labels, kfold, seed, n_trees=FOREST_TREES, max_features
     trees a fold or 2^24 cells."""
     if D.is_dist():
         raise NotImplementedError("forest_cv_predict is not data-parallel: run it on one rank, outside the process group")
-    n, d = _forest_shape_of(x)
+    n, d = _shape_of(x, N.FOREST_MAX_D, N.FOREST_MAX_N)
     checked = _forest_refusals(labels, n, d, kfold, seed, n_trees, max_features)
     bins_dev = _bins_on_device(_points_on_device(x, device))
     return _forest_on_device(bins_dev, checked, kfold, n_trees, seed if forest_seed is None else forest_seed, return_votes,
@@ -523,14 +567,7 @@ def classify_forest_points(bins_dev, y, kfold, seed, n_trees, checked):
     y = np.asarray(y)
     classes, fold = checked[0], checked[2]
     res = _forest_on_device(bins_dev, checked, kfold, n_trees, seed)
-    acc, ref_labels, pred_labels = [], [], []
-    for f in range(int(kfold)):
-        test = np.flatnonzero(fold == f)
-        pred = classes[res["pred"][test]]
-        acc.append(float(np.average(y[test] == pred)))                             # sklearn's accuracy_score
-        pred_labels.append(pred)
-        ref_labels.append(y[test])
-    return acc, ref_labels, pred_labels, res
+    return (*_fold_lists(y, classes, res["pred"], fold, kfold), res)
 
 
 def RF_classifier(data, labels, kfold, seed):
@@ -542,13 +579,4 @@ def RF_classifier(data, labels, kfold, seed):
     ``forest_seed = seed``; its departures from sklearn's forest are stated there: 256 rank bins instead of exact
     thresholds, hard votes instead of averaged leaf distributions, Philox instead of MT19937 streams, and a seeded forest
     -- the reference's own call draws from numpy's global state and cannot be reproduced; this one can."""
-    if D.is_dist():
-        raise NotImplementedError("RF_classifier is not data-parallel: run it on one rank, outside the process group")
-    n, d = _forest_shape_of(data)
-    checked = {key: _forest_refusals(labels[key], n, d, kfold, seed, FOREST_TREES, "sqrt") for key in labels}   # before any device work
-    bins_dev = _bins_on_device(_points_on_device(data, None))
-    acc, ref_labels, pred_labels = {}, {}, {}
-    for key in checked:
-        acc[key], ref_labels[key], pred_labels[key], _ = classify_forest_points(bins_dev, labels[key], kfold, seed, FOREST_TREES,
-                                                                                 checked[key])
-    return acc, ref_labels, pred_labels
+    return _classifier(data, labels, kfold, seed, "rf")

@@ -126,6 +126,46 @@ def test_models_from_moments_equal_the_restatement(k, clf, key):
     assert not ((res["best"] - res["second"]) <= 2.0 * gate.max(axis=1)).any()
 
 
+@pytest.mark.parametrize("K,F,d,n", [(4, 3, 3, 60), (5, 1, 4, 90), (6, 5, 17, 400)])
+def test_fold_sums_are_formed_once_for_both_model_builders(K, F, d, n):
+    """The one fold sum: ``fold_training_moments`` against the sum written out here (the groups g != f in increasing g from
+    zeros; F = 1: the one group), and the two model builders that read it against each other.  Exact: no tolerance."""
+    from distributed_vae_amd.utils import analysis_tree_helpers as TH
+    rng = np.random.default_rng(3)
+    codes = rng.integers(0, K - 1, size=n)                                     # the last class has no cell at all
+    fold = rng.integers(0, F, size=n)
+    x = rng.normal(size=(n, d)).astype(np.float32).astype(np.float64) + codes[:, None]     # float32-representable points
+    pivot = x.mean(axis=0)
+    iu = np.triu_indices(d)
+    s, M, counts = np.zeros((K, F, d)), np.zeros((K, F, len(iu[0]))), np.zeros((K, F))
+    for k in range(K):
+        for f in range(F):
+            t = x[(codes == k) & (fold == f)] - pivot
+            s[k, f], M[k, f], counts[k, f] = t.sum(axis=0), (t.T @ t)[iu], len(t)
+    assert not counts[K - 1].any() and counts.sum() == n
+    folds = list(CA.fold_training_moments(s, M, counts))
+    assert len(folds) == F
+    for f, (cnt, offset, scatter) in enumerate(folds):
+        c_tr, s_tr, M_tr = np.zeros(K), np.zeros((K, d)), np.zeros((K, len(iu[0])))
+        for g in range(F):
+            if g != f or F == 1:
+                c_tr, s_tr, M_tr = c_tr + counts[:, g], s_tr + s[:, g], M_tr + M[:, g]
+        full = np.zeros((K, d, d))
+        full[:, iu[0], iu[1]] = M_tr
+        full[:, iu[1], iu[0]] = M_tr
+        Nk = np.maximum(c_tr, 1.0)
+        assert np.array_equal(cnt, c_tr) and np.array_equal(offset, s_tr / Nk[:, None])
+        assert np.array_equal(scatter, full - s_tr[:, :, None] * s_tr[:, None, :] / Nk[:, None, None])
+    if F > 1:
+        with np.errstate(all="ignore"):
+            mu_leaf, _, c0_leaf, _ = TH.models_from_leaf_moments(s, M, counts, pivot, np.zeros(K), 6, 12, 1e-4)
+            has_model = np.isfinite(c0_leaf)
+            assert has_model.any() and not has_model[:, K - 1].any()
+            for kind in ("qda", "lda"):
+                mu = CA.models_from_moments(s, M, counts, pivot, kind)[0]
+                assert np.array_equal(mu[has_model], mu_leaf[has_model])
+
+
 # ---- 4. the preconditions the GPU tests lean on -----------------------------------------------------------------------------
 def test_constants_of_the_inputs_are_those_of_the_source():
     assert (GI.ROW_TILE, GI.SEG) == (N.GAUSSCLF_ROW_TILE, N.GAUSSCLF_SEG_ROWS)
