@@ -248,6 +248,14 @@ def lib():
     L.mmvae_zinb_terms_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_zinb_terms_workspace_bytes.restype = C.c_size_t
     L.mmvae_zinb_terms.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, vp, C.c_size_t, vp, vp, vp, i64, vp]
+    L.mmvae_zinb_head_grads_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.mmvae_zinb_head_grads_workspace_bytes.restype = C.c_size_t
+    L.mmvae_zinb_head_grads_segments.argtypes = [i64, i32, i32]
+    L.mmvae_zinb_head_grads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
+                                        C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mmvae_zinb_terms_grad.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, C.c_double, vp, vp, vp, i64, vp]
+    L.mmvae_debug_zinb_grad_host.argtypes = [i64, vp, vp, vp, vp, C.c_double, vp, vp]
+    L.mmvae_debug_digamma_host.argtypes = [i64, vp, vp]
     L.mmvae_count_logp_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_count_logp_workspace_bytes.restype = C.c_size_t
     L.mmvae_count_logp.argtypes = [C.POINTER(CountLogp), vp, C.c_size_t, vp]
@@ -1110,6 +1118,119 @@ def zinb_terms(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X: tor
                                      _ptr(X), _zinb_pitch(X), n, D, float(eps), _ptr(ws), nbytes, _ptr(cell), _ptr(gene),
                                      _ptr(terms), D, _stream(dev)), "mmvae_zinb_terms")
     return cell, gene, terms
+
+
+# gradients of the ZINB term with respect to the heads (csrc/zinb_grad.hip)
+ZINB_HEADS = ("rec", "p", "r")          # fc11, fc11_p, fc11_r: bits 1, 2, 4 of the head mask
+ZINB_PSI_SERIES = 10.0                  # ZB_PSI_SERIES: where psi leaves the recurrence for the asymptotic series
+
+
+def zinb_head_mask(heads) -> int:
+    """The 3-bit mask of a selection of ``ZINB_HEADS``; ValueError for an unknown name or an empty selection."""
+    heads = (heads,) if isinstance(heads, str) else tuple(heads)
+    bad = [h for h in heads if h not in ZINB_HEADS]
+    if bad or not heads:
+        raise ValueError(f"heads must be a non-empty selection of {ZINB_HEADS}; got {heads!r}")
+    return sum(1 << ZINB_HEADS.index(h) for h in set(heads))
+
+
+def zinb_head_grads_segments(n: int, D: int, segments: int = 0) -> int:
+    """The number of cell segments mmvae_zinb_head_grads uses for n cells and D genes when ``segments`` are asked for
+    (0: the library's rule)."""
+    return int(lib().mmvae_zinb_head_grads_segments(int(n), int(D), int(segments)))
+
+
+def zinb_head_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: float = 1e-6, scale: Optional[float] = None,
+                    heads=ZINB_HEADS, segments: int = 0, out=None):
+    """mmvae_zinb_head_grads: the gradient of ``scale`` x the sum of the ZINB terms of X [N, D] under the three heads of d10
+    [N, H] with respect to the weights and biases of the heads in ``heads`` ("rec": fc11, "p": fc11_p, "r": fc11_r).
+    ``scale=None`` is 1 / (N D), the mean that ``zinb_loss`` returns.  ``segments``: the number of cell segments, 0 the
+    library's rule.  ``out``: ``{head: (dW float32 [D, H], db float32 [D])}`` to write into (contiguous, on the device;
+    views of one flat buffer will do), by default new tensors.  Returns ``(grads, cell_sum, gene_sum)``: ``grads`` as ``out``
+    with the selected heads only; the float64 sums are mmvae_zinb_nll's bit for bit."""
+    what = "zinb_head_grads"
+    mask = zinb_head_mask(heads)
+    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(W.shape[0])
+    X = _zinb_mat(what, "X", X, D)
+    if X.shape[0] != n:
+        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
+    if segments < 0:
+        raise ValueError(f"{what}: segments = {segments} below 0")
+    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
+                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
+    dev = d10.device
+    grads, ptrs = {}, []
+    for j, h in enumerate(ZINB_HEADS):
+        if not mask >> j & 1:
+            ptrs += list(out[h]) if out is not None and h in out else [None, None]     # handed on, never written
+            continue
+        if out is not None:
+            dW, db = out[h]
+            if (dW.dtype != torch.float32 or db.dtype != torch.float32 or tuple(dW.shape) != (D, H) or tuple(db.shape) != (D,)
+                    or not dW.is_contiguous() or not db.is_contiguous() or dW.device != dev or db.device != dev):
+                raise TypeError(f"{what}: out[{h!r}] must be contiguous float32 ([{D}, {H}], [{D}]) on {dev}")
+        else:
+            dW = torch.empty(D, H, dtype=torch.float32, device=dev)
+            db = torch.empty(D, dtype=torch.float32, device=dev)
+        grads[h] = (dW, db)
+        ptrs += [dW, db]
+    with torch.cuda.device(dev):
+        nbytes = int(lib().mmvae_zinb_head_grads_workspace_bytes(n, D, H, int(segments)))
+        ws = _workspace(nbytes, dev)
+        cell = torch.empty(n, dtype=torch.float64, device=dev)
+        gene = torch.empty(D, dtype=torch.float64, device=dev)
+        check(lib().mmvae_zinb_head_grads(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr),
+                                          _ptr(br), _ptr(X), _zinb_pitch(X), float(eps),
+                                          1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments),
+                                          _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _stream(dev)),
+              "mmvae_zinb_head_grads")
+    return grads, cell, gene
+
+
+def zinb_terms_grad(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X: torch.Tensor, eps: float = 1e-6,
+                    scale: float = 1.0):
+    """mmvae_zinb_terms_grad: ``scale`` x the gradient of every element's ZINB term with respect to the given heads (float32
+    [N, D] on the GPU, rows may be strided) -> (g_rec, g_p, g_r) float32 [N, D] on the device."""
+    what = "zinb_terms_grad"
+    _need_cuda(what, x_rec, x_p, x_r, X)
+    X = _zinb_mat(what, "X", X)
+    n, D = (int(v) for v in X.shape)
+    x_rec, x_p, x_r = (_zinb_mat(what, nm, t, D) for nm, t in (("rec_x", x_rec), ("x_p", x_p), ("x_r", x_r)))
+    if not (x_rec.shape[0] == x_p.shape[0] == x_r.shape[0] == n):
+        raise ValueError(f"{what}: the four matrices must have the same number of rows")
+    dev = X.device
+    with torch.cuda.device(dev):
+        g = [torch.empty(n, D, dtype=torch.float32, device=dev) for _ in range(3)]
+        check(lib().mmvae_zinb_terms_grad(_ptr(x_rec), _zinb_pitch(x_rec), _ptr(x_p), _zinb_pitch(x_p), _ptr(x_r), _zinb_pitch(x_r),
+                                          _ptr(X), _zinb_pitch(X), n, D, float(eps), float(scale), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+                                          D, _stream(dev)), "mmvae_zinb_terms_grad")
+    return tuple(g)
+
+
+def debug_zinb_grad_host(X, a_rec, a_p, a_r, eps: float = 1e-6):
+    """mmvae_debug_zinb_grad_host: the kernels' element code on the host, no GPU.  float32 arrays of one shape: X and the three
+    pre-activations -> (g float64 [3, ...] = d term / d (a_rec, a_p, a_r) before the rounding, term float64 [...])."""
+    arrs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32)) for t in (X, a_rec, a_p, a_r)]
+    if any(a.shape != arrs[0].shape for a in arrs) or arrs[0].size == 0:
+        raise ValueError("debug_zinb_grad_host: X, a_rec, a_p, a_r must have one non-empty shape")
+    g = np.empty((3,) + arrs[0].shape, dtype=np.float64)
+    term = np.empty(arrs[0].shape, dtype=np.float64)
+    check(lib().mmvae_debug_zinb_grad_host(arrs[0].size, *(a.ctypes.data for a in arrs), float(eps), g.ctypes.data, term.ctypes.data),
+          "mmvae_debug_zinb_grad_host")
+    return g, term
+
+
+def debug_digamma_host(x):
+    """mmvae_debug_digamma_host: the kernels' psi on the host, float64 in and out."""
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    if x.size == 0:
+        raise ValueError("debug_digamma_host: empty input")
+    out = np.empty_like(x)
+    check(lib().mmvae_debug_digamma_host(x.size, x.ctypes.data, out.ctypes.data), "mmvae_debug_digamma_host")
+    return out
 
 
 # count distributions (csrc/countdist.hip)

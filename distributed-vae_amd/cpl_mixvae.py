@@ -848,6 +848,100 @@ class cpl_mixVAE:
                 "data_indx": inds.cpu().numpy()}
 
     @torch.no_grad()
+    def fit_zinb_heads(self, train_loader, n_epoch, lr=1e-3, heads=("rec", "p", "r"), test_loader=None, betas=(0.9, 0.999),
+                       eps=1e-8, weight_decay=0.0, state=None):
+        """Fit the decoder's ZINB heads of a model built with ``mode="ZINB"`` to the ZINB likelihood of the cells of
+        ``train_loader``, the trunk frozen: ``heads`` selects among "rec" (``fc11``), "p" (``fc11_p``) and "r" (``fc11_r``).
+        The model is in ``eval()`` throughout (no dropout, BatchNorm on its running statistics, ``temp = self.temp``, the
+        category mask of ``eval_model``); nothing but the selected heads is written.  Per batch ``(x, index)``:
+        ``mixVAE_model.zinb_head_grads`` (the gradient of the batch's mean term), then one mmvae_adam_step per arm on a flat
+        float32 buffer that holds the arm's selected heads (Adam with L2 ``weight_decay``, as ``torch.optim.Adam``).  The
+        heads' ``nn.Linear`` parameters hold the result afterwards -- and only then: during the fit the buffer is ahead of them
+        (they receive it before every ``score_zinb`` of a ``test_loader`` and on exit), so whatever reads ``model.fc11*``
+        between two batches, the eval forward's own ``x_rec`` included, sees the heads as they were at the last of those
+        points.  Returns ``{"train_loss": float64 [n_epoch, A], the mean
+        term over the epoch's cells (each batch under the heads it met); "val_loss": float64 [n_epoch, A] from
+        ``score_zinb(test_loader)["mean"]`` after each epoch, or None without a ``test_loader``; "state": Adam's step count
+        and moment buffers}``.  ``state=`` takes such a state back and resumes: two epochs and two more equal four in one
+        call bit for bit, given the same noise.  The model's mode is restored on exit, also after an exception.
+        RuntimeError for a model built with ``mode="MSE"``, NotImplementedError inside a process group, ValueError for an
+        unknown head, a negative ``n_epoch``, ``lr`` or ``weight_decay``, or ``betas`` outside [0, 1)."""
+        if D.is_dist():
+            raise NotImplementedError("fit_zinb_heads is not data-parallel: run it on one rank, outside the process group")
+        m = self.model
+        m._need_zinb("fit_zinb_heads()")
+        N.zinb_head_mask(heads)
+        if int(n_epoch) < 0 or not (0.0 <= lr < float("inf")) or not (0.0 <= weight_decay < float("inf")) or not eps >= 0.0:
+            raise ValueError(f"fit_zinb_heads: n_epoch = {n_epoch}, lr = {lr}, eps = {eps}, weight_decay = {weight_decay} must not "
+                             "be negative (or infinite)")
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"fit_zinb_heads: betas = {betas} outside [0, 1)")
+        sel = [h for h in N.ZINB_HEADS if h in ((heads,) if isinstance(heads, str) else tuple(heads))]
+        A, Dm, H = self.n_arm, self.input_dim, m.fc_dim
+        dev = self.device
+        m.flat_parameters()                       # the parameters sit where the engine reads them before views are taken
+        layer = {"rec": m.fc11, "p": m.fc11_p, "r": m.fc11_r}
+        per_head = Dm * H + Dm
+        n = len(sel) * per_head
+        buf = torch.empty(A, n, dtype=torch.float32, device=dev)
+        grad = torch.zeros_like(buf)
+
+        def views(t, a):
+            return {h: (t[a, j * per_head: j * per_head + Dm * H].view(Dm, H), t[a, j * per_head + Dm * H: (j + 1) * per_head])
+                    for j, h in enumerate(sel)}
+
+        if state is None:
+            step, m1, m2 = 0, torch.zeros_like(buf), torch.zeros_like(buf)
+        else:
+            if tuple(state["heads"]) != tuple(sel) or tuple(state["exp_avg"].shape) != (A, n):
+                raise ValueError(f"fit_zinb_heads: state is of heads {tuple(state['heads'])} and moments "
+                                 f"{tuple(state['exp_avg'].shape)}; this fit has {tuple(sel)} and {(A, n)}")
+            step = int(state["step"])
+            m1, m2 = state["exp_avg"].to(dev).clone(), state["exp_avg_sq"].to(dev).clone()
+        pv = [views(buf, a) for a in range(A)]
+        gv = [views(grad, a) for a in range(A)]
+        layers = []
+        for a in range(A):
+            for h in sel:
+                pv[a][h][0].copy_(layer[h][a].weight.detach())
+                pv[a][h][1].copy_(layer[h][a].bias.detach())
+            layers.append([t for h in N.ZINB_HEADS
+                           for t in (pv[a][h] if h in sel else (layer[h][a].weight.detach(), layer[h][a].bias.detach()))])
+
+        def write_back():
+            for a in range(A):
+                for h in sel:
+                    layer[h][a].weight.data.copy_(pv[a][h][0])
+                    layer[h][a].bias.data.copy_(pv[a][h][1])
+
+        train_loss = np.zeros((int(n_epoch), A))
+        val_loss = np.zeros((int(n_epoch), A)) if test_loader is not None else None
+        was_training = m.training
+        m.eval()
+        pruning_mask = np.where(m.fcc[0].bias.detach().cpu().numpy() != 0.0)[0]
+        try:
+            for epoch in range(int(n_epoch)):
+                total = torch.zeros(A, dtype=torch.float64, device=dev)
+                cells = 0
+                for x, _ in train_loader:
+                    B = int(x.shape[0])
+                    res = m._zinb_head_grads(x.to(dev).expand(A, -1, -1), self.temp, pruning_mask, sel, layers, gv)
+                    step += 1
+                    for a in range(A):
+                        N.adam_step(buf[a], grad[a], m1[a], m2[a], step, lr, betas[0], betas[1], eps, weight_decay, False)
+                        total[a] += res[a]["loss"] * B
+                    cells += B
+                train_loss[epoch] = (total / max(cells, 1)).cpu().numpy()
+                if test_loader is not None:
+                    write_back()
+                    val_loss[epoch] = self.score_zinb(test_loader)["mean"]
+        finally:
+            write_back()
+            m.train(was_training)
+        return {"train_loss": train_loss, "val_loss": val_loss,
+                "state": {"step": step, "exp_avg": m1, "exp_avg_sq": m2, "heads": tuple(sel)}}
+
+    @torch.no_grad()
     def sample_counts(self, dl, seed, arm=None, log1p=False):
         """Synthetic counts for the cells of ``dl`` from a model built with ``mode="ZINB"``: per batch ``(x, index)`` an eval
         forward as ``score_zinb`` runs it (``temp = self.temp``, the category mask of ``eval_model``), then one ZINB draw per

@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the Gaussian classifiers, the leaf merge, ZINB scoring, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the Gaussian classifiers, the leaf merge, ZINB scoring and the ZINB heads' gradients, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -440,6 +440,93 @@ int mmvae_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64
     if (int rc = check_ws(who, ws_bytes, mmvae_zinb_terms_workspace_bytes(N, D))) return rc;
     return launch_zinb_terms(x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N, D, eps, ws, cell_sum, gene_sum, terms, ld_t,
                              reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- gradients of the ZINB term with respect to the heads (zinb_grad.hip) ----
+static int zinb_scale(const char* who, double scale) {
+    if (std::isfinite(scale)) return 0;
+    set_error("%s: scale = %g is not finite", who, scale);
+    return MMVAE_E_BADARG;
+}
+
+size_t mmvae_zinb_head_grads_workspace_bytes(int64_t N, int D, int H, int segments) {
+    if (N < 1 || N > N_MAX || D < 1 || H < 1 || H > ZB_MAX_H || segments < 0 || zb_tiles(N, D) == 0 || zg_tiles(N, D, segments) == 0) return 0;
+    return zg_ws_bytes(N, D, H, segments);
+}
+
+int mmvae_zinb_head_grads_segments(int64_t N, int D, int segments) {
+    if (N < 1 || N > N_MAX || D < 1 || segments < 0) return 0;
+    return zg_segments(N, D, segments, nullptr);
+}
+
+int mmvae_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                          const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                          int head_mask, int segments, void* ws, size_t ws_bytes, float* dW, float* db, float* dWp, float* dbp,
+                          float* dWr, float* dbr, double* cell_sum, double* gene_sum, void* stream) {
+    const char* who = "zinb_head_grads";
+    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !cell_sum || !gene_sum) {
+        set_error("%s: null pointer", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = check_count(who, "head_mask", head_mask, 1, 7)) return rc;
+    float* const dWs[3] = {dW, dWp, dWr};
+    float* const dbs[3] = {db, dbp, dbr};
+    for (int j = 0; j < 3; ++j)
+        if ((head_mask >> j & 1) && (!dWs[j] || !dbs[j])) { set_error("%s: null pointer (a selected head's output)", who); return MMVAE_E_BADARG; }
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "segments", segments, 0, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    if (int rc = zinb_scale(who, scale)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    const size_t need = mmvae_zinb_head_grads_workspace_bytes(N, D, H, segments);
+    if (need == 0) {
+        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)N, D, segments);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    return launch_zinb_head_grads(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, scale, head_mask, segments, ws, dWs, dbs, cell_sum,
+                                  gene_sum, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,
+                          const float* X, int64_t ldx, int64_t N, int D, double eps, double scale, float* g_rec, float* g_p, float* g_r,
+                          int64_t ld_g, void* stream) {
+    const char* who = "zinb_terms_grad";
+    if (!x_rec || !x_p || !x_r || !X || !g_rec || !g_p || !g_r) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_pitch(who, "ld_rec", ld_rec, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ld_p", ld_p, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ld_r", ld_r, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ld_g", ld_g, "D", D)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    if (int rc = zinb_scale(who, scale)) return rc;
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    return launch_zinb_terms_grad(x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N, D, eps, scale, g_rec, g_p, g_r, ld_g,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_debug_zinb_grad_host(int64_t n, const float* X, const float* a_rec, const float* a_p, const float* a_r, double eps, double* g,
+                               double* term) {
+    const char* who = "debug_zinb_grad_host";
+    if (!X || !a_rec || !a_p || !a_r || !g) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    host_zinb_grad(n, X, a_rec, a_p, a_r, eps, g, term);
+    return 0;
+}
+
+int mmvae_debug_digamma_host(int64_t n, const double* x, double* out) {
+    const char* who = "debug_digamma_host";
+    if (!x || !out) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
+    host_digamma(n, x, out);
+    return 0;
 }
 
 // ---- count distributions (countdist.hip) ----

@@ -1070,6 +1070,19 @@ int launch_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int6
                       int64_t ld_t, hipStream_t st);
 // the sub-tiles' partials of zb_reduce (zb_tile.hpp) added in tile order: cell_sum [N], gene_sum [D]
 int zb_finish(void* ws, int64_t N, int D, double* cell_sum, double* gene_sum, hipStream_t st);
+// gradients of the ZINB term with respect to the heads (zinb_grad.hip); segments: 0 = the launcher's rule
+int zg_segments(int64_t N, int D, int asked, int* tiles_per_seg);   // the cell segments of a call (and the cell tiles of one)
+size_t zg_ws_bytes(int64_t N, int D, int H, int asked);             // zb_ws_bytes, then the segments' partials; 0 as zb_ws_bytes
+int64_t zg_tiles(int64_t N, int D, int asked);                      // the workgroups of one grid; 0 where a grid cannot hold them
+int launch_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                           int mask, int segments, void* ws, float* const* dW, float* const* db, double* cell_sum, double* gene_sum,
+                           hipStream_t st);
+int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,
+                           const float* X, int64_t ldx, int64_t N, int D, double eps, double scale, float* g_rec, float* g_p, float* g_r,
+                           int64_t ld_g, hipStream_t st);
+void host_zinb_grad(int64_t n, const float* X, const float* a_rec, const float* a_p, const float* a_r, double eps, double* g, double* term);
+void host_digamma(int64_t n, const double* x, double* out);
 // count distributions (countdist.hip); the host_ pair runs the element code on the host
 int launch_count_logp(const mmvae_count_logp_t& a, void* ws, hipStream_t st);
 int launch_count_sample(const mmvae_count_sample_t& s, hipStream_t st);

@@ -14,32 +14,12 @@
 // over its 32 genes (a butterfly over the lanes: the pairwise tree on the gene index), and for each of its genes the sum over
 // its 32 cells (a lane's 16 cells in register order, then the two lane halves); k_zb_finish adds the sub-tiles' partials
 // in tile order.  No atomics: bit-identical from run to run, and a cell's sum depends on that cell's row alone.
-// The tile's products and sums (zb_products, zb_reduce) live in zb_tile.hpp, which countdist.hip shares.
+// The tile's products and sums (zb_products, zb_reduce) live in zb_tile.hpp, which countdist.hip shares; the element's term and
+// its gates (zinb_term, zb_gate) in zinb_core.hpp, which zinb_grad.hip shares.
 #include "zb_tile.hpp"
+#include "zinb_core.hpp"
 
 namespace mmvae {
-
-// One element's term.  r = x_rec + eps, p and z the two probabilities after the eps guard, q = 1 - p, y = 1 - z.  Only the
-// branch that [X > 0] selects is evaluated (the reference multiplies the other by an exact 0, which differs only where that
-// other branch is not finite).
-__device__ inline double zinb_term(double X, double r, double p, double q, double z, double y) {
-    if (X > 0.0) {
-        const double k = exp(X) - 1.0;
-        return -lgamma(k + r) + lgamma(r) - k * log(p) - r * log(q) - log(y);
-    }
-    return -log(z + y * exp(r * log(q)));
-}
-
-// sigmoid(a) after the guard, and one minus it, from the pre-activation: with e = exp(-|a|) the larger of s, 1 - s is
-// 1 / (1 + e) and the smaller e / (1 + e), neither formed by a cancelling subtraction;
-// 1 - (1 - eps)(s + eps) = (1 - eps)(1 - s) + eps^2.
-__device__ inline void zb_gate(float a, double eps, double& p, double& q) {
-    const double e = exp(-fabs((double)a));
-    const double big = 1.0 / (1.0 + e), small = e * big;
-    const double s = a >= 0.f ? big : small, c = a >= 0.f ? small : big;
-    p = (1.0 - eps) * (s + eps);
-    q = (1.0 - eps) * c + eps * eps;
-}
 
 __global__ __launch_bounds__(ZB_THREADS) void k_zb_heads(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<2> hd,
                                                          float* __restrict__ x_p, float* __restrict__ x_r, int64_t ldo, int tiles_n) {

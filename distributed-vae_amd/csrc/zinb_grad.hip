@@ -1,0 +1,310 @@
+// Gradients of the ZINB term with respect to the three decoder heads (include/mmvae.h).  Two entries:
+//   mmvae_zinb_head_grads   dW_j [D, H], db_j [D] of fc11, fc11_p, fc11_r from d10 and X, and the per-cell / per-gene sums
+//                           of the term itself, the bits of mmvae_zinb_nll; no N x D array is written;
+//   mmvae_zinb_terms_grad   the elementwise gradient with respect to heads the caller gives.
+// k_zg_heads: a workgroup of four waves owns 64 genes and a segment of cell tiles (64 cells each) and walks them in order.
+// Per cell tile:
+//   1. the cells' d10 rows go to LDS whole ([64][PH], PH = H rounded up to even, plus 1: an odd pitch), the three heads'
+//      weights in K chunks of 32 as zb_stage lays them; the pre-activations are zb_products' run of v_mfma_f32_32x32x2_f32
+//      (wave w the 32 x 32 sub-tile (w & 1, w >> 1), the bias as C, k rising): the same operands in the same order, the
+//      same bits;
+//   2. the accumulators go to LDS as k_zb_nll dumps them ([wave][head][register][lane]); zb_reduce runs the term over them
+//      (its cell and gene partials land where k_zb_nll's do) and the same pass replaces each pre-activation, in place, by
+//      g = d term / d pre-activation: fp64, rounded once to float32; an element past N or D gets an exact 0;
+//   3. that image is the A operand of the second run: dW_j[gene, h] += sum_cell g_j[cell, gene] d10[cell, h], wave w the
+//      32 columns h = 32 w .. of every head and both gene halves (2 x 3 accumulators of 32 x 32 that live across the
+//      segment's cell tiles), the cells of the tile in rising order; B is the d10 tile of step 1, still in LDS.  db_j[gene]
+//      is a thread's sum down the image's column, cells rising, in fp64: the addends of a gate's db all have one sign, and
+//      a float32 chain over a few hundred of them would not hold section 9m's gate.
+// A segment's dW is one float32 chain over its cells in rising order, its db the fp64 sum rounded once.  The segments'
+// partials ([S][3][D][H + 1] float32, column H the bias) are added by k_zg_finish in segment order in fp64, scaled and
+// rounded once.  No atomics: bit-identical from run to run, and a gene's row depends on that gene's column of X and its
+// weights alone.
+// LDS: 4 (64 PH + 12288) bytes, 75 KB at H = 100: two workgroups a CU, which the launch bounds hold the registers to (256,
+// with 96 bytes of scratch a lane).  From H = 111 on the tile passes 80 KB and a CU holds one workgroup: there the register
+// cap and its scratch buy nothing, and the segment rule below (sized for two workgroups on each of 256 CUs) makes two
+// rounds of the grid.  Only H = 100 was timed; H = 128 is covered by the tests for its results, not for its speed.
+#include "zb_tile.hpp"
+#include "zinb_core.hpp"
+
+namespace mmvae {
+
+constexpr int ZG_WORK = 4 * 3 * 16 * 64;          // floats of the accumulator image; the weight chunks (3 x 64 x 33) alias it
+static_assert(3 * ZB_T * ZB_P <= ZG_WORK, "the weight chunks must fit the accumulator image");
+
+__host__ __device__ constexpr int zg_pitch(int H) { return ((H + 1) & ~1) + 1; }
+static size_t zg_lds_bytes(int H) { return sizeof(float) * ((size_t)ZB_T * zg_pitch(H) + ZG_WORK); }
+
+// the image's slot of g_j[cell c of the tile][gene gl of the tile], the inverse of zb_row: sub-tile (c >> 5, gl >> 5),
+// register (rr & 3) + 4 (rr >> 3) of lane half (rr >> 2) & 1 with rr = c & 31
+__device__ __forceinline__ int zg_slot(int j, int c, int gl) {
+    const int rr = c & 31;
+    return ((c >> 5) + 2 * (gl >> 5)) * (3 * 16 * 64) + (j * 16 + (rr & 3) + 4 * (rr >> 3)) * 64 + ((rr >> 2) & 1) * 32 + (gl & 31);
+}
+
+// One element: the term and g = d term / d (a_rec, a_p, a_r), rounded once.  A real call: inlined into k_zg_heads its fp64
+// temporaries compete with the 96 accumulators of dW for the registers of two waves a SIMD.
+__device__ __attribute__((noinline)) double zg_element(float X, float a_rec, float a_p, float a_r, double eps, float& g0, float& g1, float& g2) {
+    double p, q, z, y, gr, gp, gz;
+    zb_gate(a_p, eps, p, q);
+    zb_gate(a_r, eps, z, y);
+    const double x = (double)X, r = (double)fmaxf(a_rec, 0.f) + eps;
+    zinb_term_grad(x, r, p, q, z, y, gr, gp, gz);
+    g0 = a_rec > 0.f ? (float)gr : 0.f;
+    g1 = (float)(gp * zb_gate_slope(a_p, eps));
+    g2 = (float)(gz * zb_gate_slope(a_r, eps));
+    return zinb_term(x, r, p, q, z, y);
+}
+
+__global__ __launch_bounds__(ZB_THREADS, 2) void k_zg_heads(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<3> hd,
+                                                         const float* __restrict__ X, int64_t ldx, double eps, int mask,
+                                                         double* __restrict__ ws_cell, double* __restrict__ ws_gene,
+                                                         float* __restrict__ part, int tiles_n, int tiles_per_seg) {
+    extern __shared__ __attribute__((aligned(16))) float zg_lds[];
+    const int PH = zg_pitch(H);
+    float* tile = zg_lds;                              // [64][PH] the cell tile's d10, columns >= H zero
+    float* work = zg_lds + ZB_T * PH;                  // the weight chunks, then the accumulator image
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = w & 1, wn = w >> 1, i = lane & 31, kh = lane >> 5;
+    const int seg = blockIdx.x / tiles_n;
+    const int64_t gene0 = (int64_t)(blockIdx.x % tiles_n) * ZB_T;
+    const int64_t n_ct = cdiv64(N, ZB_T);
+    const int64_t ct0 = (int64_t)seg * tiles_per_seg, ct1 = imin64(ct0 + tiles_per_seg, n_ct);
+    const int nhb = (H + 31) >> 5;                     // the 32-column blocks of H; wave w owns block w
+    const int64_t gene = gene0 + wn * 32 + i;
+    float bias[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) bias[j] = gene < D ? hd.b[j][gene] : 0.f;
+
+    f32x16 dw[3][2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int gh = 0; gh < 2; ++gh)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) dw[j][gh][g] = 0.f;
+    double db = 0.0;                                   // thread t < 192: head t >> 6, gene t & 63 of the tile
+
+    for (int64_t ct = ct0; ct < ct1; ++ct) {
+        const int64_t cell0 = ct * ZB_T;
+        // 1. the d10 tile whole, then the pre-activations chunk after chunk
+        for (int idx = threadIdx.x; idx < ZB_T * PH; idx += ZB_THREADS) {
+            const int r = idx / PH, k = idx % PH;
+            const int64_t cell = cell0 + r;
+            tile[idx] = (cell < N && k < H) ? d10[cell * ldh + k] : 0.f;
+        }
+        f32x16 acc[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) acc[j][g] = bias[j];
+        const float* a = tile + (wm * 32 + i) * PH + kh;
+        const float* b = work + (wn * 32 + i) * ZB_P + kh;
+        for (int k0 = 0; k0 < H; k0 += ZB_KC) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                float* dst = work + ZB_T * j * ZB_P;
+                for (int idx = threadIdx.x; idx < ZB_T * ZB_KC; idx += ZB_THREADS) {
+                    const int r = idx / ZB_KC, k = idx % ZB_KC;
+                    const int64_t gr = gene0 + r;
+                    dst[r * ZB_P + k] = (gr < D && k0 + k < H) ? hd.W[j][gr * H + k0 + k] : 0.f;
+                }
+            }
+            __syncthreads();
+            const int kc = H - k0 < ZB_KC ? (H - k0 + 1) & ~1 : ZB_KC;
+            for (int k = 0; k < kc; k += 2) {
+                const float av = a[k0 + k];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[j * ZB_T * ZB_P + k], acc[j], 0, 0, 0);
+            }
+            __syncthreads();                           // every wave is done with the chunk
+        }
+        // 2. the accumulator image, the term's sums, g in place
+        float* mine = work + w * (3 * 16 * 64) + lane;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) mine[(j * 16 + g) * 64] = acc[j][g];
+        const int64_t wc0 = cell0 + wm * 32, wg0 = gene0 + wn * 32;
+        if (wc0 < N && wg0 < D)
+            zb_reduce(
+                [&](int g, int64_t cell, int64_t gn) {
+                    const float a_rec = mine[g * 64], a_p = mine[(16 + g) * 64], a_r = mine[(32 + g) * 64];
+                    float g0, g1, g2;
+                    const double t = zg_element(X[cell * ldx + gn], a_rec, a_p, a_r, eps, g0, g1, g2);
+                    mine[g * 64] = g0;
+                    mine[(16 + g) * 64] = g1;
+                    mine[(32 + g) * 64] = g2;
+                    return t;
+                },
+                lane, wc0, wg0, N, D, ws_cell, ws_gene);
+        for (int g = 0; g < 16; ++g)
+            if (wc0 + zb_row(g, kh) >= N || gene >= D) mine[g * 64] = mine[(16 + g) * 64] = mine[(32 + g) * 64] = 0.f;
+        __syncthreads();
+        // 3. dW += g^T d10 over the tile's cells; db down the image's columns
+        const int kmax = (int)imin64(ZB_T, (N - cell0 + 1) & ~(int64_t)1);
+        if (w < nhb) {
+            const int col = w * 32 + i < PH - 1 ? w * 32 + i : PH - 1;       // columns past H read the zero column
+            for (int k = 0; k < kmax; k += 2) {
+                const int c = k + kh;
+                const float bv = tile[c * PH + col];
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (mask >> j & 1) {
+#pragma unroll
+                        for (int gh = 0; gh < 2; ++gh)
+                            dw[j][gh] = __builtin_amdgcn_mfma_f32_32x32x2f32(work[zg_slot(j, c, gh * 32 + i)], bv, dw[j][gh], 0, 0, 0);
+                    }
+            }
+        }
+        if (threadIdx.x < 192 && (mask >> (threadIdx.x >> 6) & 1))
+            for (int c = 0; c < kmax; ++c) db += (double)work[zg_slot(threadIdx.x >> 6, c, threadIdx.x & 63)];
+        __syncthreads();                               // the image and the tile are free again
+    }
+
+    // the segment's partials: [seg][head][gene][H + 1]
+    const int64_t row = (int64_t)H + 1;
+    if (w < nhb) {
+        const int h = w * 32 + i;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (mask >> j & 1) {
+#pragma unroll
+                for (int gh = 0; gh < 2; ++gh)
+#pragma unroll
+                    for (int g = 0; g < 16; ++g) {
+                        const int64_t gn = gene0 + gh * 32 + zb_row(g, kh);
+                        if (gn < D && h < H) part[(((int64_t)seg * 3 + j) * D + gn) * row + h] = dw[j][gh][g];
+                    }
+            }
+    }
+    if (threadIdx.x < 192 && (mask >> (threadIdx.x >> 6) & 1)) {
+        const int64_t gn = gene0 + (threadIdx.x & 63);
+        if (gn < D) part[(((int64_t)seg * 3 + (threadIdx.x >> 6)) * D + gn) * row + H] = (float)db;
+    }
+}
+
+struct ZgOut {
+    float* dW[3];
+    float* db[3];
+};
+
+// dW_j, db_j = scale x the segments' partials added in segment order from 0.0 in fp64, rounded once
+__global__ __launch_bounds__(256) void k_zg_finish(const float* __restrict__ part, int nseg, int D, int H, int mask, double scale, ZgOut out) {
+    const int64_t row = (int64_t)H + 1, per_head = (int64_t)D * row;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < 3 * per_head; idx += (int64_t)gridDim.x * 256) {
+        const int j = (int)(idx / per_head);
+        if (!(mask >> j & 1)) continue;
+        const int64_t e = idx % per_head, gn = e / row, h = e % row;
+        double s = 0.0;
+        for (int sg = 0; sg < nseg; ++sg) s += (double)part[(int64_t)sg * 3 * per_head + idx];
+        const float v = (float)(scale * s);
+        if (h < H) out.dW[j][gn * H + h] = v;
+        else out.db[j][gn] = v;
+    }
+}
+
+// The elementwise gradient with respect to given heads: r = x_rec + eps (no relu: the subgradient is the reference's, which
+// takes rec_x as given), d p / d x_p = d z / d x_r = 1 - eps.  The loads and the tile of k_zb_terms.
+__global__ __launch_bounds__(ZB_THREADS) void k_zg_terms(const float* __restrict__ x_rec, int64_t ld_rec, const float* __restrict__ x_p,
+                                                         int64_t ld_p, const float* __restrict__ x_r, int64_t ld_r,
+                                                         const float* __restrict__ X, int64_t ldx, int64_t N, int D, double eps,
+                                                         double scale, float* __restrict__ g_rec, float* __restrict__ g_p,
+                                                         float* __restrict__ g_r, int64_t ld_g, int tiles_n) {
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wc0 = (int64_t)(blockIdx.x / tiles_n) * ZB_T + (w & 1) * 32, wg0 = (int64_t)(blockIdx.x % tiles_n) * ZB_T + (w >> 1) * 32;
+    const int64_t gene = wg0 + (lane & 31);
+    if (wc0 >= N || gene >= D) return;
+#pragma unroll 1
+    for (int g = 0; g < 16; ++g) {
+        const int64_t cell = wc0 + zb_row(g, lane >> 5);
+        if (cell >= N) continue;
+        const double p = (1.0 - eps) * ((double)x_p[cell * ld_p + gene] + eps);
+        const double z = (1.0 - eps) * ((double)x_r[cell * ld_r + gene] + eps);
+        double gr, gp, gz;
+        zinb_term_grad((double)X[cell * ldx + gene], (double)x_rec[cell * ld_rec + gene] + eps, p, 1.0 - p, z, 1.0 - z, gr, gp, gz);
+        g_rec[cell * ld_g + gene] = (float)(scale * gr);
+        g_p[cell * ld_g + gene] = (float)(scale * ((1.0 - eps) * gp));
+        g_r[cell * ld_g + gene] = (float)(scale * ((1.0 - eps) * gz));
+    }
+}
+
+// The segments of a call: asked = 0 is the launcher's rule, as many as keep the grid within 512 workgroups (two for each of
+// the MI355X's 256 CUs: one round at H <= 110, see above; the count is a constant, not read from the device, so that the
+// results do not depend on where a call runs); at most one segment a cell tile.  A segment is tiles_per_seg whole cell tiles, the last may be
+// shorter; the count is what that leaves.
+int zg_segments(int64_t N, int D, int asked, int* tiles_per_seg) {
+    const int64_t n_ct = cdiv64(N, ZB_T), n_gt = cdiv64(D, ZB_T);
+    int64_t s = asked > 0 ? asked : (512 / n_gt > 1 ? 512 / n_gt : 1);
+    s = imin64(s, n_ct);
+    const int64_t tps = cdiv64(n_ct, s);
+    if (tiles_per_seg) *tiles_per_seg = (int)imin64(tps, INT32_MAX);
+    return (int)cdiv64(n_ct, tps);
+}
+
+static unsigned __int128 zg_part_floats(int64_t N, int D, int H, int asked) {
+    return (unsigned __int128)zg_segments(N, D, asked, nullptr) * 3 * (unsigned __int128)D * (unsigned __int128)(H + 1);
+}
+
+// zb_ws_bytes(N, D), then the segments' partials (whole 8 bytes)
+size_t zg_ws_bytes(int64_t N, int D, int H, int asked) {
+    const size_t sums = zb_ws_bytes(N, D);
+    const size_t part = bytes_or_0(8 * ((zg_part_floats(N, D, H, asked) + 1) / 2));
+    return sums && part && sums + part > sums ? sums + part : 0;
+}
+
+// the workgroups of one grid, 0 where a grid cannot hold them
+int64_t zg_tiles(int64_t N, int D, int asked) {
+    const unsigned __int128 t = (unsigned __int128)zg_segments(N, D, asked, nullptr) * (unsigned __int128)cdiv64(D, ZB_T);
+    return t > (unsigned __int128)INT32_MAX ? 0 : (int64_t)t;
+}
+
+int launch_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                           int mask, int segments, void* ws, float* const* dW, float* const* db, double* cell_sum, double* gene_sum,
+                           hipStream_t st) {
+    ZbHeads<3> hd{{W, Wp, Wr}, {b, bp, br}};
+    int tps = 1;
+    const int nseg = zg_segments(N, D, segments, &tps);
+    const int tiles_n = (int)cdiv64(D, ZB_T);
+    double* ws_cell = static_cast<double*>(ws);
+    float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + zb_ws_bytes(N, D));
+    hipLaunchKernelGGL(k_zg_heads, dim3((unsigned)zg_tiles(N, D, segments)), dim3(ZB_THREADS), zg_lds_bytes(H), st, d10, ldh, N, H, D, hd, X,
+                       ldx, eps, mask, ws_cell, ws_cell + cdiv64(D, 32) * N, part, tiles_n, tps);
+    HIP_LAUNCH_CHECK("k_zg_heads");
+    ZgOut out{{dW[0], dW[1], dW[2]}, {db[0], db[1], db[2]}};
+    const unsigned gx = (unsigned)imin64(cdiv64((int64_t)3 * D * (H + 1), 256), 1 << 20);
+    hipLaunchKernelGGL(k_zg_finish, dim3(gx), dim3(256), 0, st, part, nseg, D, H, mask, scale, out);
+    HIP_LAUNCH_CHECK("k_zg_finish");
+    return zb_finish(ws, N, D, cell_sum, gene_sum, st);
+}
+
+int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,
+                           const float* X, int64_t ldx, int64_t N, int D, double eps, double scale, float* g_rec, float* g_p, float* g_r,
+                           int64_t ld_g, hipStream_t st) {
+    hipLaunchKernelGGL(k_zg_terms, dim3((unsigned)zb_tiles(N, D)), dim3(ZB_THREADS), 0, st, x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N, D,
+                       eps, scale, g_rec, g_p, g_r, ld_g, (int)cdiv64(D, ZB_T));
+    HIP_LAUNCH_CHECK("k_zg_terms");
+    return 0;
+}
+
+// The element code on the host: g [3][n] = d term / d (a_rec, a_p, a_r) as k_zg_heads forms it before the rounding, term [n]
+void host_zinb_grad(int64_t n, const float* X, const float* a_rec, const float* a_p, const float* a_r, double eps, double* g, double* term) {
+    for (int64_t e = 0; e < n; ++e) {
+        double p, q, z, y, gr, gp, gz;
+        zb_gate(a_p[e], eps, p, q);
+        zb_gate(a_r[e], eps, z, y);
+        const double x = (double)X[e], r = (double)fmaxf(a_rec[e], 0.f) + eps;
+        zinb_term_grad(x, r, p, q, z, y, gr, gp, gz);
+        g[e] = a_rec[e] > 0.f ? gr : 0.0;
+        g[n + e] = gp * zb_gate_slope(a_p[e], eps);
+        g[2 * n + e] = gz * zb_gate_slope(a_r[e], eps);
+        if (term) term[e] = zinb_term(x, r, p, q, z, y);
+    }
+}
+
+void host_digamma(int64_t n, const double* x, double* out) {
+    for (int64_t e = 0; e < n; ++e) out[e] = zb_digamma(x[e]);
+}
+
+}  // namespace mmvae

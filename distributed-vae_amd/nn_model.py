@@ -6,6 +6,7 @@ Mirrors (names, argument meaning, return contract, error behaviour):
                               ``loss`` :495-598, ``decoder`` :277-287, ``decoder_zinb`` :289-295,
                               ``state_changes`` :370-411)
 * ``zinb_loss``               mmidas/nn_model.py:642-676 (the value; no backward)
+* ``zinb_loss_grad``          no counterpart: the gradient of ``zinb_loss``'s value with respect to its three heads
 * ``mk_vae``                  mmidas/nn_model.py:679-721
 * ``VAEConfig``               mmidas/nn_model.py:14-36
 
@@ -663,6 +664,40 @@ class mixVAE_model(nn.Module):
         return {"cell": cell, "gene": gene, "n": B}
 
     @torch.no_grad()
+    def zinb_head_grads(self, x, temp=1.0, mask=None, heads=("rec", "p", "r")):
+        """The gradient of the batch's mean ZINB term (``zinb_loss`` of the batch) with respect to the weights and biases of
+        the decoder's heads, the trunk held fixed: one eval forward, then mmvae_zinb_head_grads per arm on the forward
+        workspace's d10 -- neither the pre-activations nor their gradients are written.  ``heads`` selects among "rec"
+        (``fc11``), "p" (``fc11_p``) and "r" (``fc11_r``).  Returns, per arm, ``{"loss": float64 0-dim, "fc11": (dW, db),
+        "fc11_p": (dW, db), "fc11_r": (dW, db)}`` on the device with the selected heads only; dW float32 [D, H], db float32
+        [D].  Needs model.eval()."""
+        return self._zinb_head_grads(x, temp, mask, heads, None, None)
+
+    def _zinb_head_grads(self, x, temp, mask, heads, layers, out):
+        """``zinb_head_grads`` for ``cpl_mixVAE.fit_zinb_heads``, which keeps the heads it fits and their gradients in flat
+        buffers of its own: ``layers`` (per arm, the six tensors of ``_zinb_layers``) stands in for the heads the model holds,
+        ``out`` (per arm, ``{head: (dW, db)}``) receives the gradients."""
+        self._need_zinb("zinb_head_grads()")
+        N.zinb_head_mask(heads)
+        if self.training:
+            raise RuntimeError("zinb_head_grads() needs model.eval()")
+        self._forward(x, temp, True, mask, False)
+        eng, xt, xs = self._engine, self._ctx["x"], self._ctx["x_arm_stride"]
+        B, D = xt.shape[-2], self.input_dim
+        d10 = eng.ws_view("d10", self.fc_dim)
+        names = {"rec": "fc11", "p": "fc11_p", "r": "fc11_r"}
+        res = []
+        for a in range(self.n_arm):
+            xa = xt if xs == 0 else xt[a]
+            g, cell, _ = N.zinb_head_grads(d10[a], *(self._zinb_layers(a) if layers is None else layers[a]), xa, heads=heads,
+                                           out=None if out is None else out[a])
+            r = {"loss": cell.sum() / (float(B) * float(D))}
+            r.update({names[h]: g[h] for h in N.ZINB_HEADS if h in g})
+            res.append(r)
+        self._ctx = None
+        return res
+
+    @torch.no_grad()
     def zinb_sample_batch(self, x, seed, temp=1.0, mask=None, offset=0, cell0=0, log1p=False, arms=None):
         """One ZINB draw per (arm, cell, gene) of the batch ``x`` (as ``forward`` takes it) at the model's own codes: an eval
         forward, then mmvae_zinb_sample per arm of ``arms`` (all by default) on the forward workspace's d10, as ``zinb_nll``
@@ -869,6 +904,20 @@ def zinb_loss(rec_x, x_p, x_r, X, eps=1e-6):
     flat = [t.float().reshape(-1, X.shape[-1]) for t in ts]
     cell, _, _ = N.zinb_terms(*flat, eps=eps)
     return (cell.sum() / X.numel()).to(torch.float32)
+
+
+def zinb_loss_grad(rec_x, x_p, x_r, X, eps=1e-6):
+    """The gradient of ``zinb_loss``'s value with respect to ``rec_x``, ``x_p`` and ``x_r`` -- device tensors of one shape
+    [..., D] as ``zinb_loss`` takes them; returns three float32 device tensors of that shape (mmvae_zinb_terms_grad: the
+    term's derivative in fp64, times 1 / numel, rounded once).  ``rec_x`` is taken as given: no relu stands in front of it
+    here, as none does in ``zinb_loss``.  ``zinb_loss`` itself stays without a backward."""
+    ts = (rec_x, x_p, x_r, X)
+    if not all(t.shape == X.shape for t in ts) or X.dim() < 1 or X.numel() == 0:
+        raise ValueError("zinb_loss_grad: rec_x, x_p, x_r and X must have one non-empty shape")
+    if any(t.device.type != "cuda" for t in ts):
+        raise N.NativeError("zinb_loss_grad needs GPU tensors: it runs only on the HIP engine")
+    flat = [t.detach().float().reshape(-1, X.shape[-1]) for t in ts]
+    return tuple(g.reshape(X.shape) for g in N.zinb_terms_grad(*flat, eps=eps, scale=1.0 / X.numel()))
 
 
 def mk_vae(C, state_dim, input_dim, device, eps=1e-8, fc_dim=100, latent_dim=10, x_drop=0.5, s_drop=0.2, lr=0.001,

@@ -628,6 +628,56 @@ int mmvae_zinb_terms(const float *x_rec, int64_t ld_rec, const float *x_p, int64
                      double *cell_sum, double *gene_sum, float *terms /* NULL = not wanted */, int64_t ld_t,
                      void *stream);
 
+/* ---- gradients of the ZINB term with respect to the decoder's three heads ----
+ * Notation as above; a_rec, a_p, a_r are the heads' fp32 pre-activations (the fma chain of mmvae_zinb_nll, unchanged),
+ * r = max(a_rec, 0) + eps, s = sigmoid(a), p = (1 - eps)(s_p + eps), z = (1 - eps)(s_r + eps), q = 1 - p, y = 1 - z.
+ *   X > 0:   d/dr = -psi(k + r) + psi(r) - log q     d/dp = -k / p + r / q        d/dz = 1 / y
+ *   X <= 0:  with w = q^r, u = z + y w:
+ *            d/dr = -y w log q / u                    d/dp = y r w / (q u)         d/dz = expm1(r log q) / u
+ * in fp64, only the selected branch; d r / d a_rec = [a_rec > 0], d p / d a_p = (1 - eps) s (1 - s) with s and 1 - s formed
+ * from exp(-|a|) without a cancelling subtraction, z alike.  psi: the recurrence up to 10, the asymptotic series through
+ * x^-14 from there on.
+ *
+ * mmvae_zinb_head_grads: with g_j[i, d] = d term / d a_j, for every head j whose bit of head_mask is set (1 fc11, 2 fc11_p,
+ *   4 fc11_r):  dW_j[d, h] = scale sum_i g_j[i, d] d10[i, h] (float32 [D, H]),  db_j[d] = scale sum_i g_j[i, d]
+ *   (float32 [D]); an unselected head's outputs may be NULL and are not written.  Also cell_sum [N] and gene_sum [D], the
+ *   bits of mmvae_zinb_nll's.  Neither the N x D pre-activations nor g are written to memory: a workgroup owns 64 genes
+ *   and a segment of the cells; per tile of 64 cells it forms the pre-activations, replaces them by g (fp64, rounded once
+ *   to float32) and multiplies g^T into the cells' d10 on v_mfma_f32_32x32x2_f32, the cells in rising order.  A segment's
+ *   dW is one float32 chain over its cells (db: an fp64 sum rounded once); the segments' partials are added in segment
+ *   order in fp64, times scale,
+ *   rounded once.  No atomics: bit-identical from run to run; a gene's row depends on that gene's column of X and its
+ *   weights alone, not on D.
+ *   segments: the number of cell segments asked for, 0 = the library's rule (about two workgroups a CU); the count used,
+ *   mmvae_zinb_head_grads_segments(N, D, segments), is at most ceil(N / 64): every segment has ceil(ceil(N / 64) / segments) cell tiles, the last what is left.
+ *   ws: mmvae_zinb_head_grads_workspace_bytes(N, D, H, segments) = mmvae_zinb_nll_workspace_bytes(N, D)
+ *   + 4 S 3 D (H + 1) bytes (rounded up to whole 8) with S the count used, 8-byte aligned; 0 for arguments the entry
+ *   refuses.
+ * mmvae_zinb_terms_grad: g_rec, g_p, g_r float32 [N, ld_g] = scale x the gradient of the term with respect to the given
+ *   heads x_rec, x_p, x_r (four pitches as mmvae_zinb_terms): r = x_rec + eps with no relu (the reference takes rec_x as
+ *   given), d p / d x_p = d z / d x_r = 1 - eps; fp64, rounded once.  The heads are not checked: psi is defined here for
+ *   a positive argument only (psi(0) = -inf; a negative argument, -inf or a NaN gives NaN, in at most ten steps of the
+ *   recurrence), so where X > 0 and x_rec + eps <= 0 or x_rec is not a number g_rec is -inf, +inf or NaN as that
+ *   arithmetic gives it, and x_p, x_r outside [0, 1] give what the logarithms and divisions of the table give (NaN or an
+ *   infinity); such an element costs no more time than any other and touches no other element.
+ * Refusals as mmvae_zinb_nll's; besides MMVAE_E_BADARG for head_mask outside [1, 7], a selected head's NULL output,
+ *   segments < 0, a scale that is not finite.
+ * mmvae_debug_zinb_grad_host, mmvae_debug_digamma_host: the element code on the host, no device work.  g double [3, n] =
+ *   (g_rec, g_p, g_r) before the rounding, term double [n] or NULL, from float32 X, a_rec, a_p, a_r [n]; psi(x). */
+size_t mmvae_zinb_head_grads_workspace_bytes(int64_t N, int D, int H, int segments);
+int mmvae_zinb_head_grads_segments(int64_t N, int D, int segments);
+int mmvae_zinb_head_grads(const float *d10, int64_t ldh, int64_t N, int H, int D, const float *W, const float *b,
+                          const float *Wp, const float *bp, const float *Wr, const float *br, const float *X, int64_t ldx,
+                          double eps, double scale, int head_mask, int segments, void *ws, size_t ws_bytes, float *dW,
+                          float *db, float *dWp, float *dbp, float *dWr, float *dbr, double *cell_sum, double *gene_sum,
+                          void *stream);
+int mmvae_zinb_terms_grad(const float *x_rec, int64_t ld_rec, const float *x_p, int64_t ld_p, const float *x_r,
+                          int64_t ld_r, const float *X, int64_t ldx, int64_t N, int D, double eps, double scale,
+                          float *g_rec, float *g_p, float *g_r, int64_t ld_g, void *stream);
+int mmvae_debug_zinb_grad_host(int64_t n, const float *X, const float *a_rec, const float *a_p, const float *a_r,
+                               double eps, double *g, double *term /* NULL = not wanted */);
+int mmvae_debug_digamma_host(int64_t n, const double *x, double *out);
+
 /* ---- count distributions (mmidas/utils/distributions.py) ----
  * The scVI-parameterised likelihoods of count data and one draw per element of NB / ZINB.  All matrices are float32 [N, D],
  * row-major, on the device, with a row pitch in elements; theta (and theta2) may be a vector [D], given with a pitch of 0.
