@@ -254,6 +254,15 @@ def lib():
     L.mmvae_zinb_head_grads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
                                         C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mmvae_zinb_terms_grad.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, C.c_double, vp, vp, vp, i64, vp]
+    L.mmvae_zinb_d10_grad_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.mmvae_zinb_d10_grad_workspace_bytes.restype = C.c_size_t
+    L.mmvae_zinb_d10_grad_segments.argtypes = [i64, i32, i32]
+    L.mmvae_zinb_d10_grad.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
+                                      C.c_size_t, vp, i64, vp]
+    L.mmvae_decoder_trunk_grads_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    L.mmvae_decoder_trunk_grads_workspace_bytes.restype = C.c_size_t
+    L.mmvae_decoder_trunk_grads_segments.argtypes = [i64, i32]
+    L.mmvae_decoder_trunk_grads.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp, vp, i64, vp]
     L.mmvae_debug_zinb_grad_host.argtypes = [i64, vp, vp, vp, vp, C.c_double, vp, vp]
     L.mmvae_debug_digamma_host.argtypes = [i64, vp, vp]
     L.mmvae_count_logp_workspace_bytes.argtypes = [i64, i32]
@@ -1188,6 +1197,104 @@ def zinb_head_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, ep
                                           _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _stream(dev)),
               "mmvae_zinb_head_grads")
     return grads, cell, gene
+
+
+def zinb_d10_grad_segments(n: int, D: int, segments: int = 0) -> int:
+    """The number of gene segments mmvae_zinb_d10_grad uses for n cells and D genes when ``segments`` are asked for (0: the
+    library's rule)."""
+    return int(lib().mmvae_zinb_d10_grad_segments(int(n), int(D), int(segments)))
+
+
+def zinb_d10_grad(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: float = 1e-6, heads=ZINB_HEADS, segments: int = 0,
+                  scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mmvae_zinb_d10_grad: the gradient of ``scale`` x the sum of the ZINB terms of X [N, D] with respect to d10 [N, H] through
+    the heads in ``heads`` (an unselected head still shapes the likelihood; its own path to d10 is left out).  ``scale=None``
+    is 1 / (N D); ``segments``: the number of gene segments, 0 the library's rule; ``out``: float32 [N, H] on the device to
+    write into (rows may be strided).  Returns gd10 float32 [N, H]."""
+    what = "zinb_d10_grad"
+    mask = zinb_head_mask(heads)
+    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(W.shape[0])
+    X = _zinb_mat(what, "X", X, D)
+    if X.shape[0] != n:
+        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
+    if segments < 0:
+        raise ValueError(f"{what}: segments = {segments} below 0")
+    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
+                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
+    dev = d10.device
+    if out is None:
+        out = torch.empty(n, H, dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or tuple(out.shape) != (n, H) or out.device != dev or out.stride(1) != 1
+          or (n > 1 and out.stride(0) < H)):
+        raise TypeError(f"{what}: out must be float32 [{n}, {H}] on {dev} with unit column stride")
+    with torch.cuda.device(dev):
+        nbytes = int(lib().mmvae_zinb_d10_grad_workspace_bytes(n, D, H, int(segments)))
+        ws = _workspace(nbytes, dev)
+        check(lib().mmvae_zinb_d10_grad(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr), _ptr(br),
+                                        _ptr(X), _zinb_pitch(X), float(eps),
+                                        1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments),
+                                        _ptr(ws), nbytes, _ptr(out), _zinb_pitch(out), _stream(dev)), "mmvae_zinb_d10_grad")
+    return out
+
+
+TRUNK_LAYERS = ("fc6", "fc7", "fc8", "fc9", "fc10")
+
+
+def decoder_trunk_grads_segments(n: int, segments: int = 0) -> int:
+    """The number of cell segments mmvae_decoder_trunk_grads uses for n cells when ``segments`` are asked for (0: the rule)."""
+    return int(lib().mmvae_decoder_trunk_grads_segments(int(n), int(segments)))
+
+
+def decoder_trunk_grads(acts, params, gd10: torch.Tensor, segments: int = 0, out=None, want_gzin: bool = True):
+    """mmvae_decoder_trunk_grads: the backward of one arm's decoder trunk.  ``acts``: (zin [N, C+S], d6 [N, L], d7, d8, d9, d10
+    [N, H]) float32 on the device as an eval forward leaves them (rows may be strided); ``params``: the ten tensors
+    fc6.weight, fc6.bias .. fc10.weight, fc10.bias in ``nn.Linear``'s layout; ``gd10`` float32 [N, H].  ``out``: ten
+    contiguous float32 tensors of the parameters' shapes to write into (views of one flat buffer will do), by default new
+    ones.  Returns ``(grads, gzin)``: the ten gradients in the order of ``params`` and the gradient with respect to zin
+    [N, C+S] (None with ``want_gzin=False``)."""
+    what = "decoder_trunk_grads"
+    acts, params = list(acts), list(params)
+    if len(acts) != 6 or len(params) != 10:
+        raise ValueError(f"{what}: needs six activations (zin, d6 .. d10) and ten parameter tensors (fc6.weight .. fc10.bias)")
+    _need_cuda(what, *acts, *params, gd10)
+    acts = [_zinb_mat(what, nm, t) for nm, t in zip(("zin", "d6", "d7", "d8", "d9", "d10"), acts)]
+    n = int(acts[0].shape[0])
+    Z, L, H = int(acts[0].shape[1]), int(acts[1].shape[1]), int(acts[2].shape[1])
+    width = [Z, L, H, H, H, H]
+    if any(tuple(a.shape) != (n, w) for a, w in zip(acts, width)):
+        raise ValueError(f"{what}: the activations must be [{n}, w] with w = {width}; got {[tuple(a.shape) for a in acts]}")
+    gd10 = _zinb_mat(what, "gd10", gd10, H)
+    if gd10.shape[0] != n:
+        raise ValueError(f"{what}: gd10 has {gd10.shape[0]} rows, the activations have {n}")
+    if not 0 <= int(segments) <= 1024:
+        raise ValueError(f"{what}: segments = {segments} outside [0, 1024]")
+    dev = gd10.device
+    shapes = [s for l in range(5) for s in ((width[l + 1], width[l]), (width[l + 1],))]
+    for k, (p, s) in enumerate(zip(params, shapes)):
+        if p.dtype != torch.float32 or tuple(p.shape) != s:
+            raise TypeError(f"{what}: {TRUNK_LAYERS[k // 2]}.{'bias' if k % 2 else 'weight'} must be float32 {s}; got {p.dtype} "
+                            f"{tuple(p.shape)}")
+    params = [p.contiguous() for p in params]
+    if out is None:
+        out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+    else:
+        out = list(out)
+        if len(out) != 10 or any(g.dtype != torch.float32 or tuple(g.shape) != s or not g.is_contiguous() or g.device != dev
+                                 for g, s in zip(out, shapes)):
+            raise TypeError(f"{what}: out must be ten contiguous float32 tensors of the parameters' shapes on {dev}")
+    gzin = torch.empty(n, Z, dtype=torch.float32, device=dev) if want_gzin else None
+    vp6, vp10 = C.c_void_p * 6, C.c_void_p * 10
+    with torch.cuda.device(dev):
+        nbytes = int(lib().mmvae_decoder_trunk_grads_workspace_bytes(n, Z, L, H, int(segments)))
+        ws = _workspace(nbytes, dev)
+        check(lib().mmvae_decoder_trunk_grads(n, Z, L, H, vp6(*(_ptr(a) for a in acts)), (C.c_int64 * 6)(*(_zinb_pitch(a) for a in acts)),
+                                              vp10(*(_ptr(p) for p in params)), _ptr(gd10), _zinb_pitch(gd10), int(segments),
+                                              _ptr(ws), nbytes, vp10(*(_ptr(g) for g in out)), _ptr(gzin), Z, _stream(dev)),
+              "mmvae_decoder_trunk_grads")
+    return out, gzin
 
 
 def zinb_terms_grad(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X: torch.Tensor, eps: float = 1e-6,

@@ -866,36 +866,64 @@ class cpl_mixVAE:
         call bit for bit, given the same noise.  The model's mode is restored on exit, also after an exception.
         RuntimeError for a model built with ``mode="MSE"``, NotImplementedError inside a process group, ValueError for an
         unknown head, a negative ``n_epoch``, ``lr`` or ``weight_decay``, or ``betas`` outside [0, 1)."""
+        return self._fit_zinb("fit_zinb_heads", False, train_loader, n_epoch, lr, heads, test_loader, betas, eps, weight_decay, state)
+
+    @torch.no_grad()
+    def fit_zinb_decoder(self, train_loader, n_epoch, lr=1e-3, heads=("rec", "p", "r"), test_loader=None, betas=(0.9, 0.999),
+                         eps=1e-8, weight_decay=0.0, state=None):
+        """Fit the whole decoder of a model built with ``mode="ZINB"`` -- the trunk ``fc6`` .. ``fc10`` and the selected heads
+        -- to the ZINB likelihood of the cells of ``train_loader``, the encoder frozen.  ``fit_zinb_heads``' contract, extended
+        by the trunk: the model is in ``eval()`` throughout (``temp = self.temp``, the category mask of ``eval_model``); per
+        batch ``mixVAE_model.zinb_decoder_grads`` (mmvae_zinb_head_grads, mmvae_zinb_d10_grad and mmvae_decoder_trunk_grads
+        per arm), then mmvae_adam_step on the trunk and on the selected heads.  The trunk's step runs in place on the arm's
+        ``fc6`` .. ``fc10`` range of the model's flat parameter buffer, which the eval forward reads: the forward of the next
+        batch sees the trunk of this step.  The padding between two tensors of that range is zero, has a zero gradient and so
+        stays exactly zero; the column of ``fc6`` of a category that ``prune`` switched off meets a zero input and stays exactly
+        zero too.  The heads keep ``fit_zinb_heads``' buffer and its write-back points.  The encoder, the latent block, the
+        BatchNorm statistics and the unselected heads are not written.  Return value, ``state=`` (its moments are [A, trunk
+        range + heads]: a state of ``fit_zinb_heads`` is refused), restored mode and refusals as ``fit_zinb_heads``."""
+        return self._fit_zinb("fit_zinb_decoder", True, train_loader, n_epoch, lr, heads, test_loader, betas, eps, weight_decay, state)
+
+    def _fit_zinb(self, what, trunk, train_loader, n_epoch, lr, heads, test_loader, betas, eps, weight_decay, state):
+        """``fit_zinb_heads`` (``trunk=False``) and ``fit_zinb_decoder`` (``trunk=True``)."""
         if D.is_dist():
-            raise NotImplementedError("fit_zinb_heads is not data-parallel: run it on one rank, outside the process group")
+            raise NotImplementedError(f"{what} is not data-parallel: run it on one rank, outside the process group")
         m = self.model
-        m._need_zinb("fit_zinb_heads()")
+        m._need_zinb(f"{what}()")
         N.zinb_head_mask(heads)
         if int(n_epoch) < 0 or not (0.0 <= lr < float("inf")) or not (0.0 <= weight_decay < float("inf")) or not eps >= 0.0:
-            raise ValueError(f"fit_zinb_heads: n_epoch = {n_epoch}, lr = {lr}, eps = {eps}, weight_decay = {weight_decay} must not "
+            raise ValueError(f"{what}: n_epoch = {n_epoch}, lr = {lr}, eps = {eps}, weight_decay = {weight_decay} must not "
                              "be negative (or infinite)")
         if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
-            raise ValueError(f"fit_zinb_heads: betas = {betas} outside [0, 1)")
+            raise ValueError(f"{what}: betas = {betas} outside [0, 1)")
         sel = [h for h in N.ZINB_HEADS if h in ((heads,) if isinstance(heads, str) else tuple(heads))]
         A, Dm, H = self.n_arm, self.input_dim, m.fc_dim
         dev = self.device
-        m.flat_parameters()                       # the parameters sit where the engine reads them before views are taken
+        flat = m.flat_parameters()                # the parameters sit where the engine reads them before views are taken
         layer = {"rec": m.fc11, "p": m.fc11_p, "r": m.fc11_r}
         per_head = Dm * H + Dm
         n = len(sel) * per_head
         buf = torch.empty(A, n, dtype=torch.float32, device=dev)
         grad = torch.zeros_like(buf)
+        # the trunk: tensors 16 .. 25 of the parameter layout, one range of an arm's segment of the flat buffer
+        lay = m._layout
+        o_lo, o_hi, per_arm = int(lay.offset[16]), int(lay.offset[26]), int(lay.per_arm)
+        T = o_hi - o_lo if trunk else 0
+        tgrad = torch.zeros(A, T, dtype=torch.float32, device=dev)
+        tviews = [[tgrad[a, int(lay.offset[t]) - o_lo: int(lay.offset[t]) - o_lo + m._param_of(t, a).numel()].view(m._param_of(t, a).shape)
+                   for t in range(16, 26)] for a in range(A)] if trunk else None
 
         def views(t, a):
             return {h: (t[a, j * per_head: j * per_head + Dm * H].view(Dm, H), t[a, j * per_head + Dm * H: (j + 1) * per_head])
                     for j, h in enumerate(sel)}
 
         if state is None:
-            step, m1, m2 = 0, torch.zeros_like(buf), torch.zeros_like(buf)
+            step = 0
+            m1, m2 = (torch.zeros(A, T + n, dtype=torch.float32, device=dev) for _ in range(2))
         else:
-            if tuple(state["heads"]) != tuple(sel) or tuple(state["exp_avg"].shape) != (A, n):
-                raise ValueError(f"fit_zinb_heads: state is of heads {tuple(state['heads'])} and moments "
-                                 f"{tuple(state['exp_avg'].shape)}; this fit has {tuple(sel)} and {(A, n)}")
+            if tuple(state["heads"]) != tuple(sel) or tuple(state["exp_avg"].shape) != (A, T + n):
+                raise ValueError(f"{what}: state is of heads {tuple(state['heads'])} and moments "
+                                 f"{tuple(state['exp_avg'].shape)}; this fit has {tuple(sel)} and {(A, T + n)}")
             step = int(state["step"])
             m1, m2 = state["exp_avg"].to(dev).clone(), state["exp_avg_sq"].to(dev).clone()
         pv = [views(buf, a) for a in range(A)]
@@ -925,10 +953,17 @@ class cpl_mixVAE:
                 cells = 0
                 for x, _ in train_loader:
                     B = int(x.shape[0])
-                    res = m._zinb_head_grads(x.to(dev).expand(A, -1, -1), self.temp, pruning_mask, sel, layers, gv)
+                    xb = x.to(dev).expand(A, -1, -1)
+                    if trunk:
+                        res = m._zinb_decoder_grads(xb, self.temp, pruning_mask, sel, layers, gv, tviews, False)
+                    else:
+                        res = m._zinb_head_grads(xb, self.temp, pruning_mask, sel, layers, gv)
                     step += 1
                     for a in range(A):
-                        N.adam_step(buf[a], grad[a], m1[a], m2[a], step, lr, betas[0], betas[1], eps, weight_decay, False)
+                        if trunk:
+                            N.adam_step(flat[a * per_arm + o_lo: a * per_arm + o_hi], tgrad[a], m1[a, :T], m2[a, :T], step, lr,
+                                        betas[0], betas[1], eps, weight_decay, False)
+                        N.adam_step(buf[a], grad[a], m1[a, T:], m2[a, T:], step, lr, betas[0], betas[1], eps, weight_decay, False)
                         total[a] += res[a]["loss"] * B
                     cells += B
                 train_loss[epoch] = (total / max(cells, 1)).cpu().numpy()

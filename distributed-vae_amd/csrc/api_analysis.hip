@@ -493,6 +493,85 @@ int mmvae_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int D
                                   gene_sum, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- the gradient with respect to d10, and the decoder trunk's backward (zinb_grad.hip, zinb_trunk.hip) ----
+size_t mmvae_zinb_d10_grad_workspace_bytes(int64_t N, int D, int H, int segments) {
+    if (N < 1 || N > N_MAX || D < 1 || H < 1 || H > ZB_MAX_H || segments < 0 || zb_tiles(N, D) == 0 || zd_tiles(N, D, segments) == 0) return 0;
+    return zd_ws_bytes(N, D, H, segments);
+}
+
+int mmvae_zinb_d10_grad_segments(int64_t N, int D, int segments) {
+    if (N < 1 || N > N_MAX || D < 1 || segments < 0) return 0;
+    return zd_segments(N, D, segments, nullptr);
+}
+
+int mmvae_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                        const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                        int head_mask, int segments, void* ws, size_t ws_bytes, float* gd10, int64_t ldg, void* stream) {
+    const char* who = "zinb_d10_grad";
+    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !gd10) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "head_mask", head_mask, 1, 7)) return rc;
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "segments", segments, 0, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ldg", ldg, "H", H)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    if (int rc = zinb_scale(who, scale)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    const size_t need = mmvae_zinb_d10_grad_workspace_bytes(N, D, H, segments);
+    if (need == 0) {
+        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)N, D, segments);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    return launch_zinb_d10_grad(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, scale, head_mask, segments, ws, gd10, ldg,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t mmvae_decoder_trunk_grads_workspace_bytes(int64_t N, int Z, int L, int H, int segments) {
+    if (N < 1 || N > N_MAX || Z < 1 || L < 1 || L > TR_MAX_W || H < 1 || H > TR_MAX_W || segments < 0 || segments > TR_MAX_SEG) return 0;
+    return tr_ws_bytes(N, Z, L, H, segments);
+}
+
+int mmvae_decoder_trunk_grads_segments(int64_t N, int segments) {
+    if (N < 1 || N > N_MAX || segments < 0 || segments > TR_MAX_SEG) return 0;
+    return tr_segments(N, segments, nullptr);
+}
+
+int mmvae_decoder_trunk_grads(int64_t N, int Z, int L, int H, const float* const* act, const int64_t* ld, const float* const* params,
+                              const float* gd10, int64_t ldg, int segments, void* ws, size_t ws_bytes, float* const* grads, float* gzin,
+                              int64_t ldgz, void* stream) {
+    const char* who = "decoder_trunk_grads";
+    if (!act || !ld || !params || !gd10 || !ws || !grads) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    for (int l = 0; l < 6; ++l)
+        if (!act[l]) { set_error("%s: null pointer (activation %d of zin, d6 .. d10)", who, l); return MMVAE_E_BADARG; }
+    for (int t = 0; t < 10; ++t)
+        if (!params[t] || !grads[t]) { set_error("%s: null pointer (tensor %d of fc6.weight .. fc10.bias)", who, t); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "N", N, 1, N_MAX)) return rc;
+    if (int rc = check_count(who, "Z", Z, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "L", L, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "segments", segments, 0, TR_MAX_SEG)) return rc;
+    const int width[6] = {Z, L, H, H, H, H};
+    static const char* const names[6] = {"zin", "d6", "d7", "d8", "d9", "d10"};
+    for (int l = 0; l < 6; ++l)
+        if (int rc = check_pitch(who, names[l], ld[l], "its width", width[l])) return rc;
+    if (int rc = check_pitch(who, "ldg", ldg, "H", H)) return rc;
+    if (gzin)
+        if (int rc = check_pitch(who, "ldgz", ldgz, "Z", Z)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (H > TR_MAX_W || L > TR_MAX_W) { set_error("%s: H = %d, L = %d above %d", who, H, L, TR_MAX_W); return MMVAE_E_UNSUPPORTED; }
+    const size_t need = mmvae_decoder_trunk_grads_workspace_bytes(N, Z, L, H, segments);
+    if (need == 0) { set_error("%s: N = %lld, Z = %d, L = %d, H = %d: no size_t holds the workspace", who, (long long)N, Z, L, H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    const float* W[5];
+    for (int l = 0; l < 5; ++l) W[l] = params[2 * l];
+    return launch_decoder_trunk_grads(N, Z, L, H, act, ld, W, gd10, ldg, segments, ws, grads, gzin, ldgz, reinterpret_cast<hipStream_t>(stream));
+}
+
 int mmvae_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,
                           const float* X, int64_t ldx, int64_t N, int D, double eps, double scale, float* g_rec, float* g_p, float* g_r,
                           int64_t ld_g, void* stream) {

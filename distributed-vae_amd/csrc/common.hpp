@@ -1081,6 +1081,21 @@ int launch_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int 
 int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,
                            const float* X, int64_t ldx, int64_t N, int D, double eps, double scale, float* g_rec, float* g_p, float* g_r,
                            int64_t ld_g, hipStream_t st);
+// the gradient with respect to d10 (zinb_grad.hip): the segments are of the gene tiles here
+int zd_segments(int64_t N, int D, int asked, int* tiles_per_seg);
+size_t zd_ws_bytes(int64_t N, int D, int H, int asked);             // the segments' partials; 0 for a size no size_t holds
+int64_t zd_tiles(int64_t N, int D, int asked);                      // the workgroups of one grid; 0 where a grid cannot hold them
+int launch_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                         const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                         int mask, int segments, void* ws, float* gd10, int64_t ldg, hipStream_t st);
+// the decoder trunk's backward from gd10 (zinb_trunk.hip); act / ld: zin, d6 .. d10; W: fc6 .. fc10; grads: dW6, db6, .. db10
+constexpr int TR_MAX_W = 128;          // H and L at most: a row of dZ in LDS
+constexpr int TR_MAX_SEG = 1024;       // cell segments one call may ask for
+int tr_segments(int64_t N, int asked, int64_t* cells_per_seg);
+size_t tr_ws_bytes(int64_t N, int Z, int L, int H, int asked);
+int launch_decoder_trunk_grads(int64_t N, int Z, int L, int H, const float* const* act, const int64_t* ld, const float* const* W,
+                               const float* gd10, int64_t ldg, int segments, void* ws, float* const* grads, float* gzin, int64_t ldgz,
+                               hipStream_t st);
 void host_zinb_grad(int64_t n, const float* X, const float* a_rec, const float* a_p, const float* a_r, double eps, double* g, double* term);
 void host_digamma(int64_t n, const double* x, double* out);
 // count distributions (countdist.hip); the host_ pair runs the element code on the host

@@ -1,6 +1,8 @@
-// Gradients of the ZINB term with respect to the three decoder heads (include/mmvae.h).  Two entries:
+// Gradients of the ZINB term with respect to the three decoder heads and to their input d10 (include/mmvae.h, DESIGN.md
+// sections 9m, 9n).  Three entries:
 //   mmvae_zinb_head_grads   dW_j [D, H], db_j [D] of fc11, fc11_p, fc11_r from d10 and X, and the per-cell / per-gene sums
 //                           of the term itself, the bits of mmvae_zinb_nll; no N x D array is written;
+//   mmvae_zinb_d10_grad     gd10 [N, H], the gradient with respect to d10 through the selected heads (k_zg_d10, below);
 //   mmvae_zinb_terms_grad   the elementwise gradient with respect to heads the caller gives.
 // k_zg_heads: a workgroup of four waves owns 64 genes and a segment of cell tiles (64 cells each) and walks them in order.
 // Per cell tile:
@@ -54,6 +56,19 @@ __device__ __attribute__((noinline)) double zg_element(float X, float a_rec, flo
     g1 = (float)(gp * zb_gate_slope(a_p, eps));
     g2 = (float)(gz * zb_gate_slope(a_r, eps));
     return zinb_term(x, r, p, q, z, y);
+}
+
+// zg_element without the term (k_zg_d10 has no use for it, and the term is two lgamma): the same g, statement for statement.
+// A real call for the same reason: two workgroups a CU.
+__device__ __attribute__((noinline)) void zd_element(float X, float a_rec, float a_p, float a_r, double eps, float& g0, float& g1, float& g2) {
+    double p, q, z, y, gr, gp, gz;
+    zb_gate(a_p, eps, p, q);
+    zb_gate(a_r, eps, z, y);
+    const double x = (double)X, r = (double)fmaxf(a_rec, 0.f) + eps;
+    zinb_term_grad(x, r, p, q, z, y, gr, gp, gz);
+    g0 = a_rec > 0.f ? (float)gr : 0.f;
+    g1 = (float)(gp * zb_gate_slope(a_p, eps));
+    g2 = (float)(gz * zb_gate_slope(a_r, eps));
 }
 
 __global__ __launch_bounds__(ZB_THREADS, 2) void k_zg_heads(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<3> hd,
@@ -204,6 +219,146 @@ __global__ __launch_bounds__(256) void k_zg_finish(const float* __restrict__ par
     }
 }
 
+// ---- the gradient with respect to d10: gd10[i, h] = scale sum_j sum_d g_j[i, d] W_j[d, h] ----
+// k_zg_d10 is k_zg_heads turned round: a workgroup owns 64 cells and a segment of the gene tiles and walks them in rising
+// order.  The cells' d10 tile ([64][PH]) is loaded once and stays in LDS.  Per gene tile:
+//   1. the pre-activations as k_zg_heads forms them (step 1 above: the same operands in the same order, the same bits);
+//   2. the element pass straight from the accumulator registers (no sums of the term are wanted here, so nothing goes
+//      through zb_reduce and there is no accumulator image): g in fp64, rounded once, an exact 0 past N or D, written
+//      cell-major, [head][cell][ZD_PG] with the odd pitch 65: the write has the gene on the lane, the read of step 3 the cell,
+//      and both are free of bank conflicts (bank = cell + gene mod 64);
+//   3. gd10[cell, h] += sum_gene g_j[cell, gene] W_j[gene, h] on v_mfma_f32_32x32x2_f32: A the image (M = cell, K = gene), B
+//      the wave's 32 columns h = 32 w .. of W_j read from global memory (two rows of 128 bytes a load; the three heads'
+//      weights are 6 MB at D = 5032 and stay in L2), wave w both cell halves: two accumulators of 32 x 32 that live across
+//      the segment's gene tiles.
+// The chain of one gd10[cell, h] of a segment, in float32: gene tiles rising; within a tile the gene pairs k = 0, 2, ..
+// rising; within a pair the selected heads in the order rec, p, r, each one instruction (its two genes as the instruction
+// adds them).  The segments' partials ([S][N][H] float32) are added by k_zd_finish in segment order in fp64, scaled and
+// rounded once.  No atomics; with D and the segments fixed a cell's row depends on that cell's rows of d10 and X and on the
+// weights alone.
+// LDS: 4 (64 PH + 3 x 64 x 65) bytes: 75.8 KB at H = 100 (two workgroups a CU, up to H = 124), 82.9 KB at H = 128 (one).
+constexpr int ZD_PG = ZB_T + 1;                   // the pitch of g's cell-major image, odd
+constexpr int ZD_WORK = 3 * ZB_T * ZD_PG;         // floats of that image; the weight chunks (3 x 64 x 33) alias it
+static_assert(3 * ZB_T * ZB_P <= ZD_WORK, "the weight chunks must fit g's image");
+static size_t zd_lds_bytes(int H) { return sizeof(float) * ((size_t)ZB_T * zg_pitch(H) + ZD_WORK); }
+
+__global__ __launch_bounds__(ZB_THREADS, 2) void k_zg_d10(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<3> hd,
+                                                       const float* __restrict__ X, int64_t ldx, double eps, int mask,
+                                                       float* __restrict__ part, int tiles_c, int tiles_per_seg) {
+    extern __shared__ __attribute__((aligned(16))) float zd_lds[];
+    const int PH = zg_pitch(H);
+    float* tile = zd_lds;                              // [64][PH] the cells' d10, columns >= H zero
+    float* work = zd_lds + ZB_T * PH;                  // the weight chunks, then g's image
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = w & 1, wn = w >> 1, i = lane & 31, kh = lane >> 5;
+    const int seg = blockIdx.x / tiles_c;
+    const int64_t cell0 = (int64_t)(blockIdx.x % tiles_c) * ZB_T;
+    const int64_t n_gt = cdiv64(D, ZB_T);
+    const int64_t gt0 = (int64_t)seg * tiles_per_seg, gt1 = imin64(gt0 + tiles_per_seg, n_gt);
+    const int nhb = (H + 31) >> 5;                     // the 32-column blocks of H; wave w owns block w
+    const int hcol = w * 32 + i;
+    const bool hok = hcol < H;
+
+    for (int idx = threadIdx.x; idx < ZB_T * PH; idx += ZB_THREADS) {
+        const int r = idx / PH, k = idx % PH;
+        const int64_t cell = cell0 + r;
+        tile[idx] = (cell < N && k < H) ? d10[cell * ldh + k] : 0.f;
+    }
+    f32x16 gd[2];
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) gd[ch][g] = 0.f;
+
+    for (int64_t gt = gt0; gt < gt1; ++gt) {
+        const int64_t gene0 = gt * ZB_T;
+        const int64_t gene = gene0 + wn * 32 + i;
+        // 1. the pre-activations, chunk after chunk (the first barrier also covers the d10 tile)
+        f32x16 acc[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float bj = gene < D ? hd.b[j][gene] : 0.f;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) acc[j][g] = bj;
+        }
+        const float* a = tile + (wm * 32 + i) * PH + kh;
+        const float* b = work + (wn * 32 + i) * ZB_P + kh;
+        for (int k0 = 0; k0 < H; k0 += ZB_KC) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                float* dst = work + ZB_T * j * ZB_P;
+                for (int idx = threadIdx.x; idx < ZB_T * ZB_KC; idx += ZB_THREADS) {
+                    const int r = idx / ZB_KC, k = idx % ZB_KC;
+                    const int64_t gr = gene0 + r;
+                    dst[r * ZB_P + k] = (gr < D && k0 + k < H) ? hd.W[j][gr * H + k0 + k] : 0.f;
+                }
+            }
+            __syncthreads();
+            const int kc = H - k0 < ZB_KC ? (H - k0 + 1) & ~1 : ZB_KC;
+            for (int k = 0; k < kc; k += 2) {
+                const float av = a[k0 + k];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[j * ZB_T * ZB_P + k], acc[j], 0, 0, 0);
+            }
+            __syncthreads();                           // every wave is done with the chunk
+        }
+        // 2. g from the registers to the cell-major image
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int cl = wm * 32 + zb_row(g, kh);
+            const int64_t cell = cell0 + cl;
+            float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+            if (cell < N && gene < D) zd_element(X[cell * ldx + gene], acc[0][g], acc[1][g], acc[2][g], eps, g0, g1, g2);
+            float* dst = work + cl * ZD_PG + wn * 32 + i;
+            dst[0] = g0;
+            dst[ZB_T * ZD_PG] = g1;
+            dst[2 * ZB_T * ZD_PG] = g2;
+        }
+        __syncthreads();
+        // 3. gd10 += g W over the tile's genes
+        const int kmax = (int)imin64(ZB_T, (D - gene0 + 1) & ~(int64_t)1);
+        if (w < nhb) {
+            const float* ga = work + i * ZD_PG + kh;
+#pragma unroll 4
+            for (int k = 0; k < kmax; k += 2) {
+                const int64_t gk = gene0 + k + kh;
+                const bool ok = hok && gk < D;
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (mask >> j & 1) {
+                        const float bv = ok ? hd.W[j][gk * H + hcol] : 0.f;
+#pragma unroll
+                        for (int ch = 0; ch < 2; ++ch)
+                            gd[ch] = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[(j * ZB_T + ch * 32) * ZD_PG + k], bv, gd[ch], 0, 0, 0);
+                    }
+            }
+        }
+        __syncthreads();                               // the image is free again
+    }
+
+    // the segment's partials: [seg][cell][H]
+    if (w < nhb && hok) {
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int64_t cell = cell0 + ch * 32 + zb_row(g, kh);
+                if (cell < N) part[((int64_t)seg * N + cell) * H + hcol] = gd[ch][g];
+            }
+    }
+}
+
+// gd10 = scale x the segments' partials added in segment order from 0.0 in fp64, rounded once
+__global__ __launch_bounds__(256) void k_zd_finish(const float* __restrict__ part, int nseg, int64_t N, int H, double scale,
+                                                   float* __restrict__ gd10, int64_t ldg) {
+    const int64_t total = N * H;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        double s = 0.0;
+        for (int sg = 0; sg < nseg; ++sg) s += (double)part[(int64_t)sg * total + idx];
+        gd10[(idx / H) * ldg + idx % H] = (float)(scale * s);
+    }
+}
+
 // The elementwise gradient with respect to given heads: r = x_rec + eps (no relu: the subgradient is the reference's, which
 // takes rec_x as given), d p / d x_p = d z / d x_r = 1 - eps.  The loads and the tile of k_zb_terms.
 __global__ __launch_bounds__(ZB_THREADS) void k_zg_terms(const float* __restrict__ x_rec, int64_t ld_rec, const float* __restrict__ x_p,
@@ -277,6 +432,44 @@ int launch_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int 
     hipLaunchKernelGGL(k_zg_finish, dim3(gx), dim3(256), 0, st, part, nseg, D, H, mask, scale, out);
     HIP_LAUNCH_CHECK("k_zg_finish");
     return zb_finish(ws, N, D, cell_sum, gene_sum, st);
+}
+
+// The gene segments of mmvae_zinb_d10_grad, zg_segments with the two extents exchanged: asked = 0 keeps the grid within 512
+// workgroups (a constant, not read from the device); at most one segment a gene tile; a segment is tiles_per_seg whole gene
+// tiles, the last may be shorter.
+int zd_segments(int64_t N, int D, int asked, int* tiles_per_seg) {
+    const int64_t n_ct = cdiv64(N, ZB_T), n_gt = cdiv64(D, ZB_T);
+    int64_t s = asked > 0 ? asked : (512 / n_ct > 1 ? 512 / n_ct : 1);
+    s = imin64(s, n_gt);
+    const int64_t tps = cdiv64(n_gt, s);
+    if (tiles_per_seg) *tiles_per_seg = (int)tps;
+    return (int)cdiv64(n_gt, tps);
+}
+
+// the segments' partials, [S][N][H] float32 (whole 8 bytes)
+size_t zd_ws_bytes(int64_t N, int D, int H, int asked) {
+    return bytes_or_0(8 * (((unsigned __int128)zd_segments(N, D, asked, nullptr) * (unsigned __int128)N * (unsigned __int128)H + 1) / 2));
+}
+
+int64_t zd_tiles(int64_t N, int D, int asked) {
+    const unsigned __int128 t = (unsigned __int128)zd_segments(N, D, asked, nullptr) * (unsigned __int128)cdiv64(N, ZB_T);
+    return t > (unsigned __int128)INT32_MAX ? 0 : (int64_t)t;
+}
+
+int launch_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                         const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                         int mask, int segments, void* ws, float* gd10, int64_t ldg, hipStream_t st) {
+    ZbHeads<3> hd{{W, Wp, Wr}, {b, bp, br}};
+    int tps = 1;
+    const int nseg = zd_segments(N, D, segments, &tps);
+    float* part = static_cast<float*>(ws);
+    hipLaunchKernelGGL(k_zg_d10, dim3((unsigned)zd_tiles(N, D, segments)), dim3(ZB_THREADS), zd_lds_bytes(H), st, d10, ldh, N, H, D, hd, X, ldx,
+                       eps, mask, part, (int)cdiv64(N, ZB_T), tps);
+    HIP_LAUNCH_CHECK("k_zg_d10");
+    const unsigned gx = (unsigned)imin64(cdiv64(N * H, 256), 1 << 20);
+    hipLaunchKernelGGL(k_zd_finish, dim3(gx), dim3(256), 0, st, part, nseg, N, H, scale, gd10, ldg);
+    HIP_LAUNCH_CHECK("k_zd_finish");
+    return 0;
 }
 
 int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,

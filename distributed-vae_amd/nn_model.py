@@ -698,6 +698,48 @@ class mixVAE_model(nn.Module):
         return res
 
     @torch.no_grad()
+    def zinb_decoder_grads(self, x, temp=1.0, mask=None, heads=("rec", "p", "r")):
+        """The gradient of the batch's mean ZINB term with respect to the whole decoder, the encoder held fixed: one eval
+        forward, then per arm mmvae_zinb_head_grads (the selected heads), mmvae_zinb_d10_grad (the decoder's last hidden
+        layer, through the selected heads) and mmvae_decoder_trunk_grads (``fc6`` .. ``fc10``) on the forward workspace's
+        ``zin``, ``d6`` .. ``d10``; nothing N x D is written.  Returns, per arm, ``{"loss": float64 0-dim, "fc6": (dW, db) ..
+        "fc10": (dW, db), "fc11" / "fc11_p" / "fc11_r": (dW, db) for the selected heads, "d10": float32 [B, H], "c": float32
+        [B, C], "s": float32 [B, S]}`` on the device; "c" and "s" are the gradient with respect to the decoder's input
+        ``[c | s]``.  Refusals: those of ``zinb_head_grads``."""
+        return self._zinb_decoder_grads(x, temp, mask, heads, None, None, None, True)
+
+    def _zinb_decoder_grads(self, x, temp, mask, heads, layers, out, trunk_out, want_gzin):
+        """``zinb_decoder_grads`` for ``cpl_mixVAE.fit_zinb_decoder``: ``layers`` and ``out`` as ``_zinb_head_grads`` takes
+        them, ``trunk_out`` (per arm, ten views of a flat gradient buffer) receives the trunk's gradients."""
+        self._need_zinb("zinb_decoder_grads()")
+        N.zinb_head_mask(heads)
+        if self.training:
+            raise RuntimeError("zinb_decoder_grads() needs model.eval()")
+        self._forward(x, temp, True, mask, False)
+        eng, xt, xs = self._engine, self._ctx["x"], self._ctx["x_arm_stride"]
+        B, D, H, Cc = xt.shape[-2], self.input_dim, self.fc_dim, self.n_categories
+        acts = [eng.ws_view("zin", Cc + self.state_dim), eng.ws_view("d6", self.lowD_dim)] + [eng.ws_view(f"d{k}", H) for k in (7, 8, 9, 10)]
+        names = {"rec": "fc11", "p": "fc11_p", "r": "fc11_r"}
+        res = []
+        for a in range(self.n_arm):
+            xa = xt if xs == 0 else xt[a]
+            lay = self._zinb_layers(a) if layers is None else layers[a]
+            act = [v[a] for v in acts]
+            g, cell, _ = N.zinb_head_grads(act[5], *lay, xa, heads=heads, out=None if out is None else out[a])
+            gd10 = N.zinb_d10_grad(act[5], *lay, xa, heads=heads)
+            params = [t.detach() for nm in N.TRUNK_LAYERS for t in (getattr(self, nm)[a].weight, getattr(self, nm)[a].bias)]
+            tg, gzin = N.decoder_trunk_grads(act, params, gd10, out=None if trunk_out is None else trunk_out[a], want_gzin=want_gzin)
+            r = {"loss": cell.sum() / (float(B) * float(D))}
+            r.update({nm: (tg[2 * k], tg[2 * k + 1]) for k, nm in enumerate(N.TRUNK_LAYERS)})
+            r.update({names[h]: g[h] for h in N.ZINB_HEADS if h in g})
+            r["d10"] = gd10
+            if gzin is not None:
+                r["c"], r["s"] = gzin[:, :Cc], gzin[:, Cc:]
+            res.append(r)
+        self._ctx = None
+        return res
+
+    @torch.no_grad()
     def zinb_sample_batch(self, x, seed, temp=1.0, mask=None, offset=0, cell0=0, log1p=False, arms=None):
         """One ZINB draw per (arm, cell, gene) of the batch ``x`` (as ``forward`` takes it) at the model's own codes: an eval
         forward, then mmvae_zinb_sample per arm of ``arms`` (all by default) on the forward workspace's d10, as ``zinb_nll``

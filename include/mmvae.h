@@ -671,6 +671,46 @@ int mmvae_zinb_head_grads(const float *d10, int64_t ldh, int64_t N, int H, int D
                           double eps, double scale, int head_mask, int segments, void *ws, size_t ws_bytes, float *dW,
                           float *db, float *dWp, float *dbp, float *dWr, float *dbr, double *cell_sum, double *gene_sum,
                           void *stream);
+/* mmvae_zinb_d10_grad: gd10[i, h] = scale sum_{j in head_mask} sum_d g_j[i, d] W_j[d, h], float32
+ *   [N, ldg], with g_j exactly as above.  The mirror of mmvae_zinb_head_grads: a workgroup owns 64 cells and a segment of
+ *   the 64-gene tiles, which it walks in rising order; per tile it forms the pre-activations (the bits of mmvae_zinb_nll),
+ *   replaces them by g (fp64, rounded once, an exact 0 past N or D) and multiplies g into the tile's rows of W_j on
+ *   v_mfma_f32_32x32x2_f32.  A segment's gd10[i, h] is one float32 chain: gene tiles rising, within a tile the gene pairs
+ *   rising, within a pair the selected heads in the order fc11, fc11_p, fc11_r; the segments' partials are added in segment
+ *   order in fp64, times scale, rounded once.  Nothing N x D is written, no atomics: bit-identical from run to run, and with
+ *   D and the segment count fixed a cell's row depends on that cell's rows of d10 and X and on the weights alone.  An
+ *   unselected head's weights enter the pre-activations only.
+ *   segments: the number of gene segments asked for, 0 = the library's rule (a grid of at most 512 workgroups: a constant,
+ *   not read from the device); the count used, mmvae_zinb_d10_grad_segments(N, D, segments), is at most ceil(D / 64): every
+ *   segment has ceil(ceil(D / 64) / segments) gene tiles, the last what is left.
+ *   ws: mmvae_zinb_d10_grad_workspace_bytes(N, D, H, segments) = 4 S N H bytes (rounded up to whole 8), 8-byte aligned; 0
+ *   for arguments the entry refuses.  Refusals as mmvae_zinb_head_grads'.
+ * mmvae_decoder_trunk_grads: one arm's decoder trunk backward from gd10.  act / ld: the six activations zin [N, Z], d6
+ *   [N, L], d7 .. d10 [N, H] as an eval forward or mmvae_decode leaves them, and their row pitches; params: the ten tensors
+ *   fc6.weight, fc6.bias .. fc10.weight, fc10.bias in nn.Linear's layout (the biases are not read); grads: the ten float32
+ *   gradients in that order, contiguous; gzin float32 [N, ldgz], the gradient with respect to the decoder's input, or NULL.
+ *   The four arrays of pointers are host arrays.  dZ10 = gd10 [d10 > 0], G_l-1 = dZ_l W_l, dZ_l-1 = G_l-1 [d_l-1 > 0],
+ *   dW_l = dZ_l^T in_l, db_l = sum_i dZ_l[i]: every product fp32 x fp32 exact in fp64, every sum an fp64 chain in a fixed
+ *   order (the layer's fan-out rising; the cells rising within a cell segment, the segments' partials in segment order),
+ *   rounded to float32 once where stored.  No atomics: bit-identical from run to run.
+ *   segments: the cell segments of the dW launch, 0 = the library's rule (one per 512 cells, at most 32), at most 1024; the
+ *   count used is mmvae_decoder_trunk_grads_segments(N, segments): whole chunks of 32 cells each.
+ *   ws: mmvae_decoder_trunk_grads_workspace_bytes(N, Z, L, H, segments) = 4 N (L + 4 H) (whole 8) + 8 S P bytes with P the
+ *   number of parameters of fc6 .. fc10, 8-byte aligned.
+ *   MMVAE_E_BADARG for a null pointer (gzin excepted), N < 1 or N > 2^31, Z, L or H < 1, segments outside [0, 1024], a pitch
+ *   below its width, a misaligned ws; MMVAE_E_UNSUPPORTED for H or L > 128; MMVAE_E_WORKSPACE for a ws below the size. */
+size_t mmvae_zinb_d10_grad_workspace_bytes(int64_t N, int D, int H, int segments);
+int mmvae_zinb_d10_grad_segments(int64_t N, int D, int segments);
+int mmvae_zinb_d10_grad(const float *d10, int64_t ldh, int64_t N, int H, int D, const float *W, const float *b,
+                        const float *Wp, const float *bp, const float *Wr, const float *br, const float *X, int64_t ldx,
+                        double eps, double scale, int head_mask, int segments, void *ws, size_t ws_bytes, float *gd10,
+                        int64_t ldg, void *stream);
+size_t mmvae_decoder_trunk_grads_workspace_bytes(int64_t N, int Z, int L, int H, int segments);
+int mmvae_decoder_trunk_grads_segments(int64_t N, int segments);
+int mmvae_decoder_trunk_grads(int64_t N, int Z, int L, int H, const float *const *act, const int64_t *ld,
+                              const float *const *params, const float *gd10, int64_t ldg, int segments, void *ws,
+                              size_t ws_bytes, float *const *grads, float *gzin /* NULL = not wanted */, int64_t ldgz,
+                              void *stream);
 int mmvae_zinb_terms_grad(const float *x_rec, int64_t ld_rec, const float *x_p, int64_t ld_p, const float *x_r,
                           int64_t ld_r, const float *X, int64_t ldx, int64_t N, int D, double eps, double scale,
                           float *g_rec, float *g_p, float *g_r, int64_t ld_g, void *stream);
