@@ -129,6 +129,11 @@ def exec_from_env(engine: int = 0) -> Exec:
     return ex
 
 
+class ZinbHeadLayout(C.Structure):
+    """mmvae_zinb_head_layout_t: the flat buffer of the p and r heads, per arm [fc11_p.w | fc11_p.b | fc11_r.w | fc11_r.b]"""
+    _fields_ = [("per_arm", C.c_int64), ("offset", C.c_int64 * 4)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -140,7 +145,7 @@ PLAN_NAMES = ("kind", "fast", "big", "small_x3", "fc11", "gd10_slabs", "dw11_sla
               "presplit", "bwd_small_planes", "d10_planes", "dz1_in_apply", "dec_planes", "zero", "rowmap", "dz11_bf16",
               "dw11_side", "loss_on_side", "couple", "lat_fork_rides", "fc11_fork_rides")
 CALL_KINDS = {"STEP": 0, "STEP_ROWS": 1, "FORWARD": 2, "BACKWARD": 3, "LOSS": 4, "CLASSIFY": 5, "REPLAY": 6, "DECODE": 7,
-              "TRAVERSE": 8, "ENCODE": 10}
+              "TRAVERSE": 8, "ENCODE": 10, "ZINB_STEP": 11}
 PLAN_ENUMS = {
     "big": ("GEMM_GENERAL", "GEMM_FP32", "GEMM_BF16", "GEMM_X3"),
     "fc11": ("FC11_GENERAL", "FC11_ZG", "FC11_ZT", "FC11_BF16", "FC11_X3", "FC11_OUT_BF16", "FC11_OUT_X3"),
@@ -259,10 +264,22 @@ def lib():
     L.mmvae_zinb_d10_grad_segments.argtypes = [i64, i32, i32]
     L.mmvae_zinb_d10_grad.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
                                       C.c_size_t, vp, i64, vp]
+    L.mmvae_zinb_step_grads_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.mmvae_zinb_step_grads_workspace_bytes.restype = C.c_size_t
+    L.mmvae_zinb_step_grads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
+                                        C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.mmvae_decoder_trunk_grads_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     L.mmvae_decoder_trunk_grads_workspace_bytes.restype = C.c_size_t
     L.mmvae_decoder_trunk_grads_segments.argtypes = [i64, i32]
     L.mmvae_decoder_trunk_grads.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp, vp, i64, vp]
+    L.mmvae_zinb_head_layout.argtypes = [C.POINTER(Dims), C.POINTER(ZinbHeadLayout)]
+    L.mmvae_zinb_step_workspace_bytes.argtypes = [C.POINTER(Dims), ex]
+    L.mmvae_zinb_step_workspace_bytes.restype = C.c_size_t
+    L.mmvae_zinb_train_step.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), C.POINTER(Noise), vp, vp, vp, vp, vp, i64, C.c_double, vp,
+                                        C.c_size_t, vp, C.c_size_t, vp, vp, vp, i32, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32,
+                                        ex, vp]
+    L.mmvae_zinb_objective.argtypes = [C.POINTER(Dims), C.POINTER(Hyper), vp, vp, vp, i64, C.c_double, vp, C.c_size_t, vp, C.c_size_t,
+                                       vp, ex, vp]
     L.mmvae_debug_zinb_grad_host.argtypes = [i64, vp, vp, vp, vp, C.c_double, vp, vp]
     L.mmvae_debug_digamma_host.argtypes = [i64, vp, vp]
     L.mmvae_count_logp_workspace_bytes.argtypes = [i64, i32]
@@ -546,6 +563,37 @@ class Engine:
                                           _ptr(rows), _ptr(self.ws), self.ws_bytes, _ptr(grads), _ptr(self.loss_buf),
                                           int(do_adam), _ptr(exp_avg), _ptr(exp_avg_sq), int(step), lr, b1, b2, adam_eps, wd,
                                           int(decoupled), self._x(), self._s()), "mmvae_train_step_rows")
+        return self.loss_buf
+
+    def _zws(self):
+        """The ZINB kernels' workspace of ``zinb_train_step`` / ``zinb_objective`` (mmvae_zinb_step_workspace_bytes), made once."""
+        if getattr(self, "zws", None) is None:
+            with torch.cuda.device(self.device):
+                self.zws_bytes = int(lib().mmvae_zinb_step_workspace_bytes(C.byref(self.dims), self._x()))
+                if self.zws_bytes == 0:
+                    raise NotImplementedError("mmvae_zinb_step_workspace_bytes: the ZINB step does not take these dimensions")
+                self.zws = _workspace(self.zws_bytes, self.device)
+        return self.zws
+
+    def zinb_train_step(self, hyper, noise, params, heads_pr, bn_running, nbt, x, x_arm_stride, grads, head_grads, do_adam,
+                        exp_avg, exp_avg_sq, hp_exp_avg, hp_exp_avg_sq, step, lr, b1=0.9, b2=0.999, adam_eps=1e-8, wd=0.0,
+                        decoupled=False, zinb_eps=1e-6):
+        """mmvae_zinb_train_step: the fused step under the ZINB objective; returns the device loss vector."""
+        zws = self._zws()
+        check(lib().mmvae_zinb_train_step(C.byref(self.dims), C.byref(hyper), C.byref(noise), _ptr(params), _ptr(heads_pr),
+                                          _ptr(bn_running), _ptr(nbt), _ptr(x), x_arm_stride, float(zinb_eps), _ptr(self.ws),
+                                          self.ws_bytes, _ptr(zws), self.zws_bytes, _ptr(grads), _ptr(head_grads),
+                                          _ptr(self.loss_buf), int(do_adam), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(hp_exp_avg),
+                                          _ptr(hp_exp_avg_sq), int(step), lr, b1, b2, adam_eps, wd, int(decoupled), self._x(),
+                                          self._s()), "mmvae_zinb_train_step")
+        return self.loss_buf
+
+    def zinb_objective(self, hyper, params, heads_pr, x, x_arm_stride, zinb_eps=1e-6):
+        """mmvae_zinb_objective on what the preceding ``forward`` left in the workspace; returns the device loss vector."""
+        zws = self._zws()
+        check(lib().mmvae_zinb_objective(C.byref(self.dims), C.byref(hyper), _ptr(params), _ptr(heads_pr), _ptr(x), x_arm_stride,
+                                         float(zinb_eps), _ptr(self.ws), self.ws_bytes, _ptr(zws), self.zws_bytes,
+                                         _ptr(self.loss_buf), self._x(), self._s()), "mmvae_zinb_objective")
         return self.loss_buf
 
     def eval_classify(self, hyper: Hyper, params, bn_running, x, x_arm_stride, labels, counts=None):
@@ -1063,6 +1111,18 @@ def _zinb_layer(what: str, name: str, W: torch.Tensor, b: torch.Tensor, D: int, 
     return W.contiguous(), b.contiguous()
 
 
+def zinb_head_layout(dims: Dims) -> ZinbHeadLayout:
+    """mmvae_zinb_head_layout: the offsets of the p and r heads in their flat buffer (host only)."""
+    out = ZinbHeadLayout()
+    check(lib().mmvae_zinb_head_layout(C.byref(dims), C.byref(out)), "mmvae_zinb_head_layout")
+    return out
+
+
+def zinb_step_workspace_bytes(dims: Dims, ex: Optional[Exec] = None) -> int:
+    """mmvae_zinb_step_workspace_bytes (host only); 0 for dimensions the ZINB step refuses."""
+    return int(lib().mmvae_zinb_step_workspace_bytes(C.byref(dims), C.byref(ex) if ex is not None else None))
+
+
 def zinb_heads(d10: torch.Tensor, Wp, bp, Wr, br):
     """mmvae_zinb_heads: (sigmoid(d10 Wp^T + bp), sigmoid(d10 Wr^T + br)), float32 [N, D] each, from float32 d10 [N, H] on
     the GPU (rows may be strided) and two ``nn.Linear`` layers' weight [D, H] and bias [D]."""
@@ -1241,6 +1301,45 @@ def zinb_d10_grad(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps:
 
 
 TRUNK_LAYERS = ("fc6", "fc7", "fc8", "fc9", "fc10")
+
+
+def zinb_step_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: float = 1e-6, scale: Optional[float] = None,
+                    heads=ZINB_HEADS, segments: int = 0):
+    """mmvae_zinb_step_grads: ``zinb_head_grads`` (at ``segments`` cell segments) and ``zinb_d10_grad`` (at a segment a gene
+    tile) from one evaluation of g.  Returns ``(grads, cell_sum, gene_sum, gd10)``, each bit for bit what the two give."""
+    what = "zinb_step_grads"
+    mask = zinb_head_mask(heads)
+    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(W.shape[0])
+    X = _zinb_mat(what, "X", X, D)
+    if X.shape[0] != n:
+        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
+    if segments < 0:
+        raise ValueError(f"{what}: segments = {segments} below 0")
+    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
+                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
+    dev = d10.device
+    grads, ptrs = {}, []
+    for j, h in enumerate(ZINB_HEADS):
+        if mask >> j & 1:
+            grads[h] = (torch.empty(D, H, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev))
+            ptrs += list(grads[h])
+        else:
+            ptrs += [None, None]
+    with torch.cuda.device(dev):
+        nbytes = int(lib().mmvae_zinb_step_grads_workspace_bytes(n, D, H, int(segments)))
+        ws = _workspace(nbytes, dev)
+        cell = torch.empty(n, dtype=torch.float64, device=dev)
+        gene = torch.empty(D, dtype=torch.float64, device=dev)
+        gd10 = torch.empty(n, H, dtype=torch.float32, device=dev)
+        check(lib().mmvae_zinb_step_grads(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr),
+                                          _ptr(br), _ptr(X), _zinb_pitch(X), float(eps),
+                                          1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments),
+                                          _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _ptr(gd10), H,
+                                          _stream(dev)), "mmvae_zinb_step_grads")
+    return grads, cell, gene, gd10
 
 
 def decoder_trunk_grads_segments(n: int, segments: int = 0) -> int:

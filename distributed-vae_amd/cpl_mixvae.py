@@ -977,6 +977,72 @@ class cpl_mixVAE:
                 "state": {"step": step, "exp_avg": m1, "exp_avg_sq": m2, "heads": tuple(sel)}}
 
     @torch.no_grad()
+    def fit_zinb(self, train_loader, n_epoch, lr=1e-3, test_loader=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, state=None):
+        """Train the whole model -- encoder, latent block, decoder and the three heads -- of a model built with ``mode="ZINB"``
+        under the ZINB objective: the reference's ``loss()`` with its reconstruction term replaced by ``zinb_loss``.  The model
+        is in ``train()`` throughout (input and state dropout, batch-statistic BatchNorm, ``temp = self.temp``); per batch
+        ``(x, index)`` one ``mixVAE_model.zinb_train_step`` on the gathered batch ``x.expand`` over the arms (Adam with L2
+        ``weight_decay``, as ``torch.optim.Adam``).  The rows path and the augmenter are not used.  Returns ``{"train_loss":
+        float64 [n_epoch, 5 + 3 A], the epoch's mean of every entry of the loss vector (MMVAE_LOSS_*: total, joint, .. , rec[a]
+        the ZINB loss, kl[a], ll[a]) over its batches; "val_loss": float64 [n_epoch, 5 + 3 A], the same entries from
+        ``zinb_objective`` (eval mode) over the batches of ``test_loader`` after each epoch, or None without one; "state":
+        Adam's step count and both moment pairs}``.  ``state=`` takes such a state back and resumes: two epochs and two more
+        equal four in one call bit for bit, given the same noise.  The model's mode is restored on exit, also after an
+        exception.  Refusals, all before any device work or noise is consumed: RuntimeError for a model built with
+        ``mode="MSE"``; NotImplementedError inside a process group ("not data-parallel"), for ``gemm_dtype="bf16"`` and for a
+        model whose categories ``prune`` has switched off (its mask is not offered in training); ValueError for a negative
+        ``n_epoch``, ``lr``, ``eps`` or ``weight_decay``, ``betas`` outside [0, 1), or a state of ``fit_zinb_heads`` /
+        ``fit_zinb_decoder``."""
+        what = "fit_zinb"
+        if D.is_dist():
+            raise NotImplementedError(f"{what} is not data-parallel: run it on one rank, outside the process group")
+        m = self.model
+        m._need_zinb(f"{what}()")
+        if int(n_epoch) < 0 or not (0.0 <= lr < float("inf")) or not (0.0 <= weight_decay < float("inf")) or not eps >= 0.0:
+            raise ValueError(f"{what}: n_epoch = {n_epoch}, lr = {lr}, eps = {eps}, weight_decay = {weight_decay} must not "
+                             "be negative (or infinite)")
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"{what}: betas = {betas} outside [0, 1)")
+        if m.gemm_dtype == "bf16":
+            raise NotImplementedError(f"{what}: gemm_dtype='bf16' is not offered under the ZINB objective (bf16 heads are not built)")
+        if state is not None:
+            m._check_zinb_step_state(what, state)
+        if int(np.count_nonzero(m.fcc[0].bias.detach().cpu().numpy() != 0.0)) < self.n_categories:
+            raise NotImplementedError(f"{what}: the model has pruned categories; a category mask is not offered in ZINB training")
+        A, dev = self.n_arm, self.device
+        if state is None:
+            st = m.zinb_step_state()
+        else:
+            st = {k: (v.to(dev).clone() if isinstance(v, torch.Tensor) else v) for k, v in state.items()}
+            st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].reshape(-1), st["exp_avg_sq"].reshape(-1)
+        n_loss = 5 + 3 * A
+        train_loss = np.zeros((int(n_epoch), n_loss))
+        val_loss = np.zeros((int(n_epoch), n_loss)) if test_loader is not None else None
+        was_training = m.training
+        try:
+            for epoch in range(int(n_epoch)):
+                m.train()
+                acc = torch.zeros(n_loss, dtype=torch.float64, device=dev)
+                batches = 0
+                for x, _ in train_loader:
+                    buf = m.zinb_train_step(x.to(dev).expand(A, -1, -1), self.temp, state=st, do_adam=True, lr=lr, betas=betas,
+                                            eps=eps, weight_decay=weight_decay)
+                    acc += buf.to(torch.float64)
+                    batches += 1
+                train_loss[epoch] = (acc / max(batches, 1)).cpu().numpy()
+                if test_loader is not None:
+                    m.eval()
+                    acc.zero_()
+                    batches = 0
+                    for x, _ in test_loader:
+                        acc += m._zinb_objective_vec(x.to(dev).expand(A, -1, -1), self.temp, None).to(torch.float64)
+                        batches += 1
+                    val_loss[epoch] = (acc / max(batches, 1)).cpu().numpy()
+        finally:
+            m.train(was_training)
+        return {"train_loss": train_loss, "val_loss": val_loss, "state": st}
+
+    @torch.no_grad()
     def sample_counts(self, dl, seed, arm=None, log1p=False):
         """Synthetic counts for the cells of ``dl`` from a model built with ``mode="ZINB"``: per batch ``(x, index)`` an eval
         forward as ``score_zinb`` runs it (``temp = self.temp``, the category mask of ``eval_model``), then one ZINB draw per

@@ -286,8 +286,8 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
     Plan& p = c.plan;
     p = Plan{};
     p.kind = kind;
-    const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS, fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY ||
-                                                                 kind == CALL_TRAVERSE || kind == CALL_ENCODE;
+    const bool step = kind == CALL_STEP || kind == CALL_STEP_ROWS || kind == CALL_ZINB_STEP;
+    const bool fwd = step || kind == CALL_FORWARD || kind == CALL_CLASSIFY || kind == CALL_TRAVERSE || kind == CALL_ENCODE;
     const bool dropout = c.dropout(), side = c.side() != nullptr;
     p.fast = fast_dims(d) && al16(params) && al16(x) && (xs & 3) == 0 && d.H >= 4 && (int64_t)d.B * d.D < ((int64_t)1 << 30);
     // engines of the five D x H products (mmvae_hyper.gemm_bf16: 1 bf16 operands, 2 fp32x3)
@@ -304,7 +304,8 @@ static void make_plan(Ctx& c, CallKind kind, const float* params, const float* x
     else if (p.big == GEMM_BF16) p.fc11 = FC11_BF16;
     else if (fc11_grad && d.H == 100 && (int64_t)cdiv(d.B, 256) * L.sp.ks_gd10 <= L.n11) p.fc11 = FC11_ZG;
     else p.fc11 = FC11_ZT;
-    p.gd10_slabs = p.fast ? L.sp.ks_gd10 : L.sp.ns_fc11;
+    // (the ZINB step: mmvae_zinb_step_grads' one array, written behind the fc11 launch as slab 0)
+    p.gd10_slabs = kind == CALL_ZINB_STEP ? 1 : p.fast ? L.sp.ks_gd10 : L.sp.ns_fc11;
     p.dw11_slabs = p.fast ? L.sp.ks_dw11 : L.sp.ks_dw;
     // the chain kernels' own GEMMs on the fp32x3 engine (also in the bf16 configuration: only its five D x H products round
     // their operands, everything else stays fp32-grade)
@@ -480,6 +481,9 @@ static int do_backward(const Ctx& c, const mmvae_noise* nz, const float* params,
                        float grad_scale, float* grads, const AdamHost* adam = nullptr, float* loss_out = nullptr) {
     const Plan& p = c.plan;
     int rc;
+    // the ZINB step: d(d10) and fc11's dW and db (already in `grads`) are mmvae_zinb_step_grads': no dW11 GEMM (off the fast
+    // path launch_dw_big still forms its slabs beside dW1; nothing reads them), no reduction of it
+    const bool zinb = p.kind == CALL_ZINB_STEP;
     // dW11 on the side stream (Plan::dw11_side)
     const bool early = p.dw11_side && !adam && c.ex.early_grad_event != nullptr;
     const bool side_red = p.dw11_side && adam;
@@ -519,11 +523,11 @@ static int do_backward(const Ctx& c, const mmvae_noise* nz, const float* params,
         if ((rc = launch_dw_big(c, nz, x, xs))) return rc;
     } else {
         if ((rc = dw1(c, x, xs))) return rc;
-        if (!p.dw11_side && (rc = dw11(c))) return rc;
+        if (!p.dw11_side && !zinb && (rc = dw11(c))) return rc;
     }
     if ((rc = launch_dw_small(c))) return rc;
     if (p.dw11_side && (rc = join_from_side(c, EV_JOIN))) return rc;
-    return launch_reduce_grads(c, grads, grad_scale, adam, early || side_red ? 2 : 3);
+    return launch_reduce_grads(c, grads, grad_scale, adam, zinb || early || side_red ? 2 : 3);
 }
 
 }  // namespace mmvae
@@ -713,6 +717,153 @@ int mmvae_train_step_rows(const mmvae_dims* d, const mmvae_hyper* h, const mmvae
     }
     return train_step_impl(c, h, nz, params, bn_running, nbt, data, 0, grads, loss_out, do_adam, exp_avg, exp_avg_sq, step,
                            lr, beta1, beta2, adam_eps, weight_decay, decoupled);
+}
+
+// ---- training under the ZINB likelihood: every argument is checked before the first launch
+int mmvae_zinb_head_layout(const mmvae_dims* d, mmvae_zinb_head_layout_t* out) {
+    if (int rc = check_dims(d)) return rc;
+    if (!out) { set_error("out is null"); return MMVAE_E_BADARG; }
+    const int64_t D = d->D, H = d->H;
+    out->offset[0] = 0;                 // fc11_p.weight [D, H]
+    out->offset[1] = D * H;             // fc11_p.bias [D]
+    out->offset[2] = D * H + D;         // fc11_r.weight [D, H]
+    out->offset[3] = 2 * D * H + D;     // fc11_r.bias [D]
+    out->per_arm = 2 * (D * H + D);
+    return 0;
+}
+
+// the ZINB kernels' workspace: mmvae_zinb_step_grads' (one arm's at a time; mmvae_zinb_nll's fits into its head), then the cell
+// sums double [A][B], the gene sums double [D] (one arm's at a time) and zinb_loss of every arm, double [A]
+struct ZinbWs { size_t grads, total; };
+static ZinbWs zinb_step_ws(const mmvae_dims& d) {
+    ZinbWs z{};
+    if (zb_tiles(d.B, d.D) == 0 || zg_tiles(d.B, d.D, 0) == 0) return z;
+    z.grads = zs_ws_bytes(d.B, d.D, d.H, 0);
+    if (!z.grads) return ZinbWs{};
+    z.total = bytes_or_0((unsigned __int128)z.grads + 8 * ((unsigned __int128)d.A * d.B + d.D + d.A));
+    return z;
+}
+
+size_t mmvae_zinb_step_workspace_bytes(const mmvae_dims* d, const mmvae_exec* ex) {
+    (void)ex;                           // (no size of it depends on the execution context)
+    if (check_dims(d)) return 0;
+    return zinb_step_ws(*d).total;
+}
+
+static int check_zinb_ws(const char* who, const mmvae_dims* d, double zinb_eps, const void* zws, size_t zws_bytes, ZinbWs& z) {
+    if (!(zinb_eps >= 0.0 && zinb_eps < 1.0)) { set_error("%s: zinb_eps = %g outside [0, 1)", who, zinb_eps); return MMVAE_E_BADARG; }
+    if (!zws || (reinterpret_cast<uintptr_t>(zws) & 7)) { set_error("%s: zws is null or not 8-byte aligned", who); return MMVAE_E_BADARG; }
+    z = zinb_step_ws(*d);
+    if (!z.total) { set_error("%s: B = %d, D = %d need more tiles of 64 x 64 than a grid holds", who, d->B, d->D); return MMVAE_E_UNSUPPORTED; }
+    if (zws_bytes < z.total) { set_error("%s: zws too small: need %zu bytes, got %zu", who, z.total, zws_bytes); return MMVAE_E_WORKSPACE; }
+    return 0;
+}
+
+struct ZinbArm {
+    const float *d10, *X, *W, *b, *Wp, *bp, *Wr, *br;
+};
+static ZinbArm zinb_arm(const Ctx& c, int a, const float* params, const float* heads_pr, const float* x, int64_t xs) {
+    const int64_t D = c.d.D, H = c.d.H;
+    const float* P = params + (int64_t)a * c.po.per_arm;
+    const float* Q = heads_pr + (int64_t)a * 2 * (D * H + D);
+    return ZinbArm{c.ws + c.lay.Dk[4] + (int64_t)a * c.d.B * H, x + (int64_t)a * xs, P + c.po.o[26], P + c.po.o[27],
+                   Q, Q + D * H, Q + D * H + D, Q + 2 * D * H + D};
+}
+
+int mmvae_zinb_train_step(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, float* params, float* heads_pr,
+                          float* bn_running, int64_t* nbt, const float* x, int64_t x_arm_stride, double zinb_eps, void* ws,
+                          size_t ws_bytes, void* zws, size_t zws_bytes, float* grads, float* head_grads, float* loss_out, int do_adam,
+                          float* exp_avg, float* exp_avg_sq, float* hp_exp_avg, float* hp_exp_avg_sq, int64_t step, float lr,
+                          float beta1, float beta2, float adam_eps, float weight_decay, int decoupled, mmvae_exec* ex, void* stream) {
+    const char* who = "zinb_train_step";
+    Ctx c;
+    if (int rc = make_ctx(c, d, h, ws, ws_bytes, ex, stream)) return rc;
+    if (!params || !heads_pr || !x || !grads || !head_grads || !loss_out) {
+        set_error("%s: null params / heads_pr / x / grads / head_grads / loss_out", who);
+        return MMVAE_E_BADARG;
+    }
+    if (x_arm_stride < 0) { set_error("%s: negative arm stride", who); return MMVAE_E_BADARG; }
+    if (int rc = check_noise(c, nz)) return rc;
+    if (!h->training) { set_error("%s requires training mode", who); return MMVAE_E_UNSUPPORTED; }
+    if (h->gemm_bf16 == 1) { set_error("%s: the bf16 engine is not offered (gemm_bf16 = 1)", who); return MMVAE_E_UNSUPPORTED; }
+    if (h->cat_mask[0] | h->cat_mask[1] | h->cat_mask[2] | h->cat_mask[3]) {
+        set_error("%s: a category mask (pruning) is not offered in training", who);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    ZinbWs z;
+    if (int rc = check_zinb_ws(who, d, zinb_eps, zws, zws_bytes, z)) return rc;
+    if (do_adam && (!exp_avg || !exp_avg_sq || !hp_exp_avg || !hp_exp_avg_sq || step < 1)) {
+        set_error("%s: adam state missing", who);
+        return MMVAE_E_BADARG;
+    }
+    // one stream: the ZINB kernels fill the chip, and nothing of the step is left to run beside the backward chain
+    c.ex.side_stream = nullptr;
+    c.ex.early_grad_event = nullptr;
+    make_plan(c, CALL_ZINB_STEP, params, x, x_arm_stride);
+    const int A = d->A, D = d->D, H = d->H;
+    const int64_t B = d->B;
+    char* zb = static_cast<char*>(zws);
+    double* cell = reinterpret_cast<double*>(zb + z.grads);
+    double* gene = cell + (int64_t)A * B;
+    double* zrec = gene + D;
+    int rc;
+    // 1. the MSE step's forward, fc11 included: its launch leaves the partials of sum (relu(a_rec) - x)^2 that ll[a] is made of
+    //    (its dZ11 and d(d10) slabs are not read)
+    if ((rc = do_forward(c, nz, params, bn_running, nbt, x, x_arm_stride, nullptr, 1, loss_out))) return rc;
+    // 2., 3. per arm, one pass over g: the heads' gradients into grads (fc11) and head_grads, d(d10) into slab 0
+    const double scale = (double)(A > 1 ? A - 1 : 1) / ((double)B * (double)D);
+    const int64_t hp_per_arm = 2 * ((int64_t)D * H + D);
+    for (int a = 0; a < A; ++a) {
+        const ZinbArm za = zinb_arm(c, a, params, heads_pr, x, x_arm_stride);
+        float* G = grads + (int64_t)a * c.po.per_arm;
+        float* HG = head_grads + (int64_t)a * hp_per_arm;
+        float* const dW[3] = {G + c.po.o[26], HG, HG + (int64_t)D * H + D};
+        float* const db[3] = {G + c.po.o[27], HG + (int64_t)D * H, HG + 2 * (int64_t)D * H + D};
+        if ((rc = launch_zinb_step_grads(za.d10, H, B, H, D, za.W, za.b, za.Wp, za.bp, za.Wr, za.br, za.X, D, zinb_eps, scale, 7, 0, zb, dW,
+                                         db, cell + (int64_t)a * B, gene, c.ws + c.lay.GD10_slab + (int64_t)a * B * H, H, c.stream)))
+            return rc;
+    }
+    if ((rc = launch_zinb_rec(cell, A, B, D, zrec, c.stream))) return rc;
+    if ((rc = launch_couple(c))) return rc;
+    if ((rc = launch_loss_finalize(c, loss_out, 0, zrec))) return rc;
+    // 4. the rest of the backward pass from slab 0
+    if ((rc = do_backward(c, nz, params, x, x_arm_stride, 1.f, grads, nullptr, loss_out))) return rc;
+    if (!do_adam) return 0;
+    // (the alignment gaps of the flat buffers hold zeros in the parameters, the gradients and the moments, and keep them)
+    if ((rc = launch_adam((int64_t)A * c.po.per_arm, params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, adam_eps, weight_decay,
+                          decoupled, c.stream)))
+        return rc;
+    return launch_adam((int64_t)A * hp_per_arm, heads_pr, head_grads, hp_exp_avg, hp_exp_avg_sq, step, lr, beta1, beta2, adam_eps,
+                       weight_decay, decoupled, c.stream);
+}
+
+int mmvae_zinb_objective(const mmvae_dims* d, const mmvae_hyper* h, const float* params, const float* heads_pr, const float* x,
+                         int64_t x_arm_stride, double zinb_eps, void* ws, size_t ws_bytes, void* zws, size_t zws_bytes,
+                         float* loss_out, mmvae_exec* ex, void* stream) {
+    const char* who = "zinb_objective";
+    Ctx c;
+    if (int rc = make_ctx(c, d, h, ws, ws_bytes, ex, stream)) return rc;
+    if (!params || !heads_pr || !x || !loss_out) { set_error("%s: null params / heads_pr / x / loss_out", who); return MMVAE_E_BADARG; }
+    if (x_arm_stride < 0) { set_error("%s: negative arm stride", who); return MMVAE_E_BADARG; }
+    ZinbWs z;
+    if (int rc = check_zinb_ws(who, d, zinb_eps, zws, zws_bytes, z)) return rc;
+    make_plan(c, CALL_LOSS, nullptr, nullptr, 0);
+    const int A = d->A, D = d->D, H = d->H;
+    const int64_t B = d->B;
+    char* zb = static_cast<char*>(zws);
+    double* cell = reinterpret_cast<double*>(zb + z.grads);
+    double* gene = cell + (int64_t)A * B;
+    double* zrec = gene + D;
+    int rc;
+    for (int a = 0; a < A; ++a) {
+        const ZinbArm za = zinb_arm(c, a, params, heads_pr, x, x_arm_stride);
+        if ((rc = launch_zinb_nll(za.d10, H, B, H, D, za.W, za.b, za.Wp, za.bp, za.Wr, za.br, za.X, D, zinb_eps, zb, cell + (int64_t)a * B,
+                                  gene, c.stream)))
+            return rc;
+    }
+    if ((rc = launch_zinb_rec(cell, A, B, D, zrec, c.stream))) return rc;
+    if ((rc = launch_couple(c))) return rc;
+    return launch_loss_finalize(c, loss_out, 0, zrec);
 }
 
 int mmvae_eval_classify(const mmvae_dims* d, const mmvae_hyper* h, const float* params, const float* bn_running,
@@ -937,9 +1088,9 @@ int mmvae_debug_plan(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_exec
     static_assert(MMVAE_CALL_STEP == CALL_STEP && MMVAE_CALL_STEP_ROWS == CALL_STEP_ROWS && MMVAE_CALL_FORWARD == CALL_FORWARD &&
                   MMVAE_CALL_BACKWARD == CALL_BACKWARD && MMVAE_CALL_LOSS == CALL_LOSS && MMVAE_CALL_CLASSIFY == CALL_CLASSIFY &&
                   MMVAE_CALL_REPLAY == CALL_REPLAY && MMVAE_CALL_DECODE == CALL_DECODE && MMVAE_CALL_TRAVERSE == CALL_TRAVERSE &&
-                  MMVAE_CALL_ENCODE == CALL_ENCODE,
+                  MMVAE_CALL_ENCODE == CALL_ENCODE && MMVAE_CALL_ZINB_STEP == CALL_ZINB_STEP,
                   "MMVAE_CALL_* (include/mmvae.h) are the values of CallKind");
-    if (call_kind < CALL_STEP || (call_kind > CALL_TRAVERSE && call_kind != CALL_ENCODE)) { set_error("unknown call kind %d", call_kind); return MMVAE_E_BADARG; }
+    if (call_kind < CALL_STEP || (call_kind > CALL_TRAVERSE && call_kind != CALL_ENCODE && call_kind != CALL_ZINB_STEP)) { set_error("unknown call kind %d", call_kind); return MMVAE_E_BADARG; }
     if (params_align < 0 || x_align < 0) { set_error("negative alignment"); return MMVAE_E_BADARG; }
     // what make_ctx gives make_plan to read -- dims, hyper, exec copy, layout -- without a workspace or a stream
     Ctx c{};
@@ -948,6 +1099,7 @@ int mmvae_debug_plan(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_exec
     // (as their entry points plan: decode and the traversal force eval mode, eval_classify accepts nothing else)
     if (call_kind == CALL_DECODE || call_kind == CALL_TRAVERSE || call_kind == CALL_CLASSIFY) c.h.training = 0;
     if (ex) c.ex = *ex; else memset(&c.ex, 0, sizeof(c.ex));
+    if (call_kind == CALL_ZINB_STEP) c.ex.side_stream = nullptr;   // (mmvae_zinb_train_step runs on the call's stream alone)
     c.lay = make_layout(*d, &c.ex);
     c.po = make_poff(*d);
     // pointers that are never dereferenced: a 16-byte boundary plus the stated alignment's offset

@@ -531,6 +531,47 @@ int mmvae_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, 
                                 reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- the heads' gradients and gd10 in one pass over g (zinb_grad.hip, k_zg_step) ----
+size_t mmvae_zinb_step_grads_workspace_bytes(int64_t N, int D, int H, int segments) {
+    if (mmvae_zinb_head_grads_workspace_bytes(N, D, H, segments) == 0) return 0;
+    return zs_ws_bytes(N, D, H, segments);
+}
+
+int mmvae_zinb_step_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                          const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                          int head_mask, int segments, void* ws, size_t ws_bytes, float* dW, float* db, float* dWp, float* dbp,
+                          float* dWr, float* dbr, double* cell_sum, double* gene_sum, float* gd10, int64_t ldg, void* stream) {
+    const char* who = "zinb_step_grads";
+    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !cell_sum || !gene_sum || !gd10) {
+        set_error("%s: null pointer", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = check_count(who, "head_mask", head_mask, 1, 7)) return rc;
+    float* const dWs[3] = {dW, dWp, dWr};
+    float* const dbs[3] = {db, dbp, dbr};
+    for (int j = 0; j < 3; ++j)
+        if ((head_mask >> j & 1) && (!dWs[j] || !dbs[j])) { set_error("%s: null pointer (a selected head's output)", who); return MMVAE_E_BADARG; }
+    if (int rc = zinb_extent(who, N, D)) return rc;
+    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "segments", segments, 0, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (int rc = check_pitch(who, "ldg", ldg, "H", H)) return rc;
+    if (int rc = zinb_eps(who, eps)) return rc;
+    if (int rc = zinb_scale(who, scale)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, N, D)) return rc;
+    const size_t need = mmvae_zinb_step_grads_workspace_bytes(N, D, H, segments);
+    if (need == 0) {
+        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)N, D, segments);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    return launch_zinb_step_grads(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, scale, head_mask, segments, ws, dWs, dbs, cell_sum,
+                                  gene_sum, gd10, ldg, reinterpret_cast<hipStream_t>(stream));
+}
+
 size_t mmvae_decoder_trunk_grads_workspace_bytes(int64_t N, int Z, int L, int H, int segments) {
     if (N < 1 || N > N_MAX || Z < 1 || L < 1 || L > TR_MAX_W || H < 1 || H > TR_MAX_W || segments < 0 || segments > TR_MAX_SEG) return 0;
     return tr_ws_bytes(N, Z, L, H, segments);

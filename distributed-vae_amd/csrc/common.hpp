@@ -760,7 +760,8 @@ inline bool fc11_slots_fit(const Layout& L, int B) { return (int64_t)cdiv(B, 128
 // builds it once per entry point; the launchers and drivers read it and decide nothing themselves.
 enum CallKind { CALL_STEP, CALL_STEP_ROWS, CALL_FORWARD, CALL_BACKWARD, CALL_LOSS, CALL_CLASSIFY, CALL_REPLAY /*debug stage*/,
                 CALL_DECODE /*mmvae_decode, and the decoder half of mmvae_state_changes*/, CALL_TRAVERSE /*its encoder half*/,
-                CALL_ENCODE = 10 /*9 stays unknown to mmvae_debug_plan; mmvae_encode: the encoder and the latent block, or its head alone*/ };
+                CALL_ENCODE = 10 /*9 stays unknown to mmvae_debug_plan; mmvae_encode: the encoder and the latent block, or its head alone*/,
+                CALL_ZINB_STEP = 11 /*mmvae_zinb_train_step: the step's forward and backward around the ZINB gradient kernels; no side stream*/ };
 // fc1, dW1, dW11: gemm_big.hip, fp32 matrix instruction (gemm_fast.hip), k_bf16_* / k_x3_* (gemm_bf16.hip)
 enum GemmFamily { GEMM_GENERAL, GEMM_FP32, GEMM_BF16, GEMM_X3 };
 // fc11 + d(d10): k_fc11_fused, k_fc11_zg (d(d10) folded in), k_fc11_zt + k_gd10_*, k_bf16_fc11* (+ k_bf16_gemm), k_x3_fc11g;
@@ -884,7 +885,9 @@ int launch_prune_apply(const mmvae_dims& d, const POff& po, const uint32_t cat_m
 int launch_chain_fwd_dec(const Ctx& c, const float* params);   // (with the coupling terms as a role: Plan::couple)
 int launch_fc11_fused(const Ctx& c, const float* params, const float* x, int64_t xs, float* x_rec, int need_grad);
 int launch_couple(const Ctx& c);
-int launch_loss_finalize(const Ctx& c, float* loss_out, int mode = 0 /*1: the T sums only, 2: the scalars only*/);
+// zrec != null (double [A], device): rec[a] is zrec[a], the ZINB loss of arm a, in place of the MSE expression
+int launch_loss_finalize(const Ctx& c, float* loss_out, int mode = 0 /*1: the T sums only, 2: the scalars only*/,
+                         const double* zrec = nullptr);
 int launch_chain_bwd_dec(const Ctx& c, const float* params);
 int launch_lat_bwd(const Ctx& c, const mmvae_noise* nz, const float* params);
 int launch_chain_bwd_enc(const Ctx& c, int layer /*5..2*/, const float* params);
@@ -1088,6 +1091,12 @@ int64_t zd_tiles(int64_t N, int D, int asked);                      // the workg
 int launch_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
                          const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
                          int mask, int segments, void* ws, float* gd10, int64_t ldg, hipStream_t st);
+// both in one pass over g (zinb_grad.hip, k_zg_step): the heads' gradients at `segments` cell segments, gd10 at a segment a gene tile
+size_t zs_ws_bytes(int64_t N, int D, int H, int asked);             // zg_ws_bytes, then the gene tiles' partials of gd10
+int launch_zinb_step_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                           int mask, int segments, void* ws, float* const* dW, float* const* db, double* cell_sum, double* gene_sum,
+                           float* gd10, int64_t ldg, hipStream_t st);
 // the decoder trunk's backward from gd10 (zinb_trunk.hip); act / ld: zin, d6 .. d10; W: fc6 .. fc10; grads: dW6, db6, .. db10
 constexpr int TR_MAX_W = 128;          // H and L at most: a row of dZ in LDS
 constexpr int TR_MAX_SEG = 1024;       // cell segments one call may ask for
@@ -1096,6 +1105,8 @@ size_t tr_ws_bytes(int64_t N, int Z, int L, int H, int asked);
 int launch_decoder_trunk_grads(int64_t N, int Z, int L, int H, const float* const* act, const int64_t* ld, const float* const* W,
                                const float* gd10, int64_t ldg, int segments, void* ws, float* const* grads, float* gzin, int64_t ldgz,
                                hipStream_t st);
+// zrec[a] = (the sum of cell_sum[a][0 .. N) in a fixed order) / (N D): zinb_loss of every arm (zinb_grad.hip)
+int launch_zinb_rec(const double* cell_sum, int A, int64_t N, int D, double* zrec, hipStream_t st);
 void host_zinb_grad(int64_t n, const float* X, const float* a_rec, const float* a_p, const float* a_r, double eps, double* g, double* term);
 void host_digamma(int64_t n, const double* x, double* out);
 // count distributions (countdist.hip); the host_ pair runs the element code on the host

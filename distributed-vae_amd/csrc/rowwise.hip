@@ -103,7 +103,8 @@ __global__ __launch_bounds__(256) void k_loss_finalize(int A, int B, int D, int 
                                                        const float* __restrict__ lat_part, int nlat, int nblk,
                                                        const float* __restrict__ couple_part,
                                                        const float* __restrict__ T_part, float* __restrict__ T,
-                                                       float* __restrict__ out, int mode) {
+                                                       float* __restrict__ out, int mode, const double* __restrict__ zrec) {
+    // zrec != null: rec[a] = zrec[a] (mmvae_zinb_train_step, mmvae_zinb_objective); ll keeps the reference's expression
     // mode 0: block 0 the scalars, blocks 1.. the T sums; 1: T sums only (every block; they need the coupling kernel's
     // output alone and the latent backward waits for them); 2: scalars only (one block; they need fc11's loss partials)
     __shared__ double sh[256];
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void k_loss_finalize(int A, int B, int D, int 
             en += lat_part[((int64_t)a * nlat + i) * 2 + 1];
         }
         se = block_sum_d(se, sh); mm = block_sum_d(mm, sh); kl = block_sum_d(kl, sh); en = block_sum_d(en, sh);
-        const double rec = 0.5 * se / B + 0.5 * (100.0 * mm / ((double)B * D));   // nn_model.py:544-546
+        const double rec = zrec ? zrec[a] : 0.5 * se / B + 0.5 * (100.0 * mm / ((double)B * D));   // nn_model.py:544-546
         const double ll = se / ((double)B * D) + B * log(PI2);                     // :542
         const double klv = -0.5 * kl / B;                                          // :43-44
         if (tid == 0) {
@@ -648,7 +649,7 @@ int launch_couple(const Ctx& c) {
     return 0;
 }
 
-int launch_loss_finalize(const Ctx& c, float* loss_out, int mode) {
+int launch_loss_finalize(const Ctx& c, float* loss_out, int mode, const double* zrec) {
     const mmvae_dims& d = c.d;
     const Layout& L = c.lay;
     if (c.h.training && c.use_acc()) {   // the coupling kernel has added the T sums to their accumulator set itself
@@ -658,7 +659,7 @@ int launch_loss_finalize(const Ctx& c, float* loss_out, int mode) {
     const int nT = cdiv(d.A * d.C, 32);
     hipLaunchKernelGGL(k_loss_finalize, dim3(mode == 0 ? 1 + nT : (mode == 1 ? nT : 1)), dim3(256), 0, c.stream, d.A, d.B, d.D, d.C,
                        c.h.beta, c.h.lam, c.ws + L.fc11_part, L.n11, c.ws + L.lat_part, L.nblkl, L.nblk32, c.ws + L.couple_part,
-                       c.ws + L.T_part, c.ws + L.T, loss_out, mode);
+                       c.ws + L.T_part, c.ws + L.T, loss_out, mode, zrec);
     HIP_LAUNCH_CHECK("k_loss_finalize");
     return 0;
 }

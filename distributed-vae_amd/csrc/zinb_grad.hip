@@ -1,9 +1,10 @@
 // Gradients of the ZINB term with respect to the three decoder heads and to their input d10 (include/mmvae.h, DESIGN.md
-// sections 9m, 9n).  Three entries:
+// sections 9m, 9n, 9o).  Four entries:
 //   mmvae_zinb_head_grads   dW_j [D, H], db_j [D] of fc11, fc11_p, fc11_r from d10 and X, and the per-cell / per-gene sums
 //                           of the term itself, the bits of mmvae_zinb_nll; no N x D array is written;
 //   mmvae_zinb_d10_grad     gd10 [N, H], the gradient with respect to d10 through the selected heads (k_zg_d10, below);
-//   mmvae_zinb_terms_grad   the elementwise gradient with respect to heads the caller gives.
+//   mmvae_zinb_terms_grad   the elementwise gradient with respect to heads the caller gives;
+//   mmvae_zinb_step_grads   the first two from one evaluation of g (k_zg_heads<true>, "k_zg_step"): what the ZINB train step runs.
 // k_zg_heads: a workgroup of four waves owns 64 genes and a segment of cell tiles (64 cells each) and walks them in order.
 // Per cell tile:
 //   1. the cells' d10 rows go to LDS whole ([64][PH], PH = H rounded up to even, plus 1: an odd pitch), the three heads'
@@ -71,10 +72,21 @@ __device__ __attribute__((noinline)) void zd_element(float X, float a_rec, float
     g2 = (float)(gz * zb_gate_slope(a_r, eps));
 }
 
+// STEP (k_zg_step, mmvae_zinb_step_grads): the same walk also leaves the tile's share of gd10.  After step 3, with g's image
+// still in LDS, wave w multiplies it the other way round (M = cell, K = gene) into the 32 columns h = 32 w .. of the 64 genes'
+// rows of W_j, read from global memory as k_zg_d10 reads them, both cell halves: two accumulators of 32 x 32 that live for
+// this tile only (the 48 of step 1 are dead by then: the kernel's peak stays at step 1's 96 + 48).  The chain of one
+// gd10[cell, h] of the tile is k_zg_d10's: gene pairs rising, within a pair the selected heads in the order rec, p, r.  The
+// 64 x H partial goes to part_d [gene tile][cell][H], which k_zd_finish adds in rising order of the gene tiles: what
+// mmvae_zinb_d10_grad computes with one segment a gene tile, bit for bit.  The image is read with the cell on the lane here,
+// 16 lanes to a bank (it is laid out for step 3, gene on the lane): the reads hide behind the matrix instructions of the
+// other waves, and the fp64 epilogue bounds the kernel either way (profiles/zinb_step_time.json).
+template <bool STEP>
 __global__ __launch_bounds__(ZB_THREADS, 2) void k_zg_heads(const float* __restrict__ d10, int64_t ldh, int64_t N, int H, int D, ZbHeads<3> hd,
                                                          const float* __restrict__ X, int64_t ldx, double eps, int mask,
                                                          double* __restrict__ ws_cell, double* __restrict__ ws_gene,
-                                                         float* __restrict__ part, int tiles_n, int tiles_per_seg) {
+                                                         float* __restrict__ part, int tiles_n, int tiles_per_seg,
+                                                         float* __restrict__ part_d) {
     extern __shared__ __attribute__((aligned(16))) float zg_lds[];
     const int PH = zg_pitch(H);
     float* tile = zg_lds;                              // [64][PH] the cell tile's d10, columns >= H zero
@@ -174,6 +186,41 @@ __global__ __launch_bounds__(ZB_THREADS, 2) void k_zg_heads(const float* __restr
         }
         if (threadIdx.x < 192 && (mask >> (threadIdx.x >> 6) & 1))
             for (int c = 0; c < kmax; ++c) db += (double)work[zg_slot(threadIdx.x >> 6, c, threadIdx.x & 63)];
+        if constexpr (STEP) {
+            // 3b. the tile's gd10 = g W over its genes, k_zg_d10's step 3 on this image
+            const int hcol = w * 32 + i;
+            const bool hok = hcol < H;
+            if (w < nhb) {
+                f32x16 gd[2];
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+                    for (int g = 0; g < 16; ++g) gd[ch][g] = 0.f;
+                const int gmax = (int)imin64(ZB_T, (D - gene0 + 1) & ~(int64_t)1);
+                for (int k = 0; k < gmax; k += 2) {
+                    const int64_t gk = gene0 + k + kh;
+                    const bool ok = hok && gk < D;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j)
+                        if (mask >> j & 1) {
+                            const float bv = ok ? hd.W[j][gk * H + hcol] : 0.f;
+#pragma unroll
+                            for (int ch = 0; ch < 2; ++ch)
+                                gd[ch] = __builtin_amdgcn_mfma_f32_32x32x2f32(work[zg_slot(j, ch * 32 + i, k + kh)], bv, gd[ch], 0, 0, 0);
+                        }
+                }
+                if (hok) {
+                    float* pd = part_d + (gene0 / ZB_T) * N * H;
+#pragma unroll
+                    for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+                        for (int g = 0; g < 16; ++g) {
+                            const int64_t cell = cell0 + ch * 32 + zb_row(g, kh);
+                            if (cell < N) pd[cell * H + hcol] = gd[ch][g];
+                        }
+                }
+            }
+        }
         __syncthreads();                               // the image and the tile are free again
     }
 
@@ -424,13 +471,45 @@ int launch_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int 
     const int tiles_n = (int)cdiv64(D, ZB_T);
     double* ws_cell = static_cast<double*>(ws);
     float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + zb_ws_bytes(N, D));
-    hipLaunchKernelGGL(k_zg_heads, dim3((unsigned)zg_tiles(N, D, segments)), dim3(ZB_THREADS), zg_lds_bytes(H), st, d10, ldh, N, H, D, hd, X,
-                       ldx, eps, mask, ws_cell, ws_cell + cdiv64(D, 32) * N, part, tiles_n, tps);
+    hipLaunchKernelGGL(k_zg_heads<false>, dim3((unsigned)zg_tiles(N, D, segments)), dim3(ZB_THREADS), zg_lds_bytes(H), st, d10, ldh, N, H, D,
+                       hd, X, ldx, eps, mask, ws_cell, ws_cell + cdiv64(D, 32) * N, part, tiles_n, tps, (float*)nullptr);
     HIP_LAUNCH_CHECK("k_zg_heads");
     ZgOut out{{dW[0], dW[1], dW[2]}, {db[0], db[1], db[2]}};
     const unsigned gx = (unsigned)imin64(cdiv64((int64_t)3 * D * (H + 1), 256), 1 << 20);
     hipLaunchKernelGGL(k_zg_finish, dim3(gx), dim3(256), 0, st, part, nseg, D, H, mask, scale, out);
     HIP_LAUNCH_CHECK("k_zg_finish");
+    return zb_finish(ws, N, D, cell_sum, gene_sum, st);
+}
+
+// mmvae_zinb_step_grads: zg_ws_bytes(N, D, H, asked), then the gene tiles' partials of gd10, [ceil(D / 64)][N][H] float32
+// (zd_ws_bytes with a segment a gene tile)
+size_t zs_ws_bytes(int64_t N, int D, int H, int asked) {
+    const size_t heads = zg_ws_bytes(N, D, H, asked);
+    const size_t d10 = zd_ws_bytes(N, D, H, (int)imin64(cdiv64(D, ZB_T), INT32_MAX));
+    return heads && d10 && heads + d10 > heads ? heads + d10 : 0;
+}
+
+int launch_zinb_step_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
+                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
+                           int mask, int segments, void* ws, float* const* dW, float* const* db, double* cell_sum, double* gene_sum,
+                           float* gd10, int64_t ldg, hipStream_t st) {
+    ZbHeads<3> hd{{W, Wp, Wr}, {b, bp, br}};
+    int tps = 1;
+    const int nseg = zg_segments(N, D, segments, &tps);
+    const int tiles_n = (int)cdiv64(D, ZB_T);
+    double* ws_cell = static_cast<double*>(ws);
+    float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + zb_ws_bytes(N, D));
+    float* part_d = reinterpret_cast<float*>(static_cast<char*>(ws) + zg_ws_bytes(N, D, H, segments));
+    hipLaunchKernelGGL(k_zg_heads<true>, dim3((unsigned)zg_tiles(N, D, segments)), dim3(ZB_THREADS), zg_lds_bytes(H), st, d10, ldh, N, H, D,
+                       hd, X, ldx, eps, mask, ws_cell, ws_cell + cdiv64(D, 32) * N, part, tiles_n, tps, part_d);
+    HIP_LAUNCH_CHECK("k_zg_step");
+    ZgOut out{{dW[0], dW[1], dW[2]}, {db[0], db[1], db[2]}};
+    unsigned gx = (unsigned)imin64(cdiv64((int64_t)3 * D * (H + 1), 256), 1 << 20);
+    hipLaunchKernelGGL(k_zg_finish, dim3(gx), dim3(256), 0, st, part, nseg, D, H, mask, scale, out);
+    HIP_LAUNCH_CHECK("k_zg_finish");
+    gx = (unsigned)imin64(cdiv64(N * H, 256), 1 << 20);
+    hipLaunchKernelGGL(k_zd_finish, dim3(gx), dim3(256), 0, st, part_d, tiles_n, N, H, scale, gd10, ldg);
+    HIP_LAUNCH_CHECK("k_zd_finish");
     return zb_finish(ws, N, D, cell_sum, gene_sum, st);
 }
 
@@ -478,6 +557,29 @@ int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p,
     hipLaunchKernelGGL(k_zg_terms, dim3((unsigned)zb_tiles(N, D)), dim3(ZB_THREADS), 0, st, x_rec, ld_rec, x_p, ld_p, x_r, ld_r, X, ldx, N, D,
                        eps, scale, g_rec, g_p, g_r, ld_g, (int)cdiv64(D, ZB_T));
     HIP_LAUNCH_CHECK("k_zg_terms");
+    return 0;
+}
+
+// zinb_loss of every arm from the per-cell sums (mmvae_zinb_train_step, mmvae_zinb_objective): one workgroup an arm; thread
+// t adds cells t, t + 256, .. in rising order, the 256 sums fold in halves (128, 64, ..): one fixed order in fp64, then one
+// division by N D.  The loss finalisation rounds it to float32.
+__global__ __launch_bounds__(256) void k_zinb_rec(const double* __restrict__ cell_sum, int64_t N, int D, double* __restrict__ zrec) {
+    __shared__ double sh[256];
+    const double* cs = cell_sum + (int64_t)blockIdx.x * N;
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < N; i += 256) s += cs[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) zrec[blockIdx.x] = sh[0] / ((double)N * (double)D);
+}
+
+int launch_zinb_rec(const double* cell_sum, int A, int64_t N, int D, double* zrec, hipStream_t st) {
+    hipLaunchKernelGGL(k_zinb_rec, dim3((unsigned)A), dim3(256), 0, st, cell_sum, N, D, zrec);
+    HIP_LAUNCH_CHECK("k_zinb_rec");
     return 0;
 }
 

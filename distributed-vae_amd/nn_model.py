@@ -739,6 +739,143 @@ class mixVAE_model(nn.Module):
         self._ctx = None
         return res
 
+    # ------------------------------------------------------------------ training under the ZINB objective
+    _ZINB_PR = (("fc11_p", "weight"), ("fc11_p", "bias"), ("fc11_r", "weight"), ("fc11_r", "bias"))
+
+    def _heads_packed(self) -> bool:
+        flat = getattr(self, "_heads_flat", None)
+        if flat is None:
+            return False
+        lay, A = self._heads_layout, self.n_arm
+        w0, bl = self.fc11_p[0].weight, self.fc11_r[A - 1].bias
+        return (w0.device == flat.device and w0.data_ptr() == flat.data_ptr()
+                and bl.data_ptr() == flat.data_ptr() + 4 * (int(lay.per_arm) * (A - 1) + int(lay.offset[3])))
+
+    def _pack_heads(self):
+        """The p and r heads in one flat buffer (mmvae_zinb_head_layout), as ``_pack`` keeps the 28 tensors: every
+        ``fc11_p`` / ``fc11_r`` parameter becomes a view of it, so the modules hold the step's result at every moment (the
+        write-back points of ``fit_zinb_heads`` -- before a ``score_zinb``, on exit -- are trivially met).  Values are kept."""
+        dev = self.fc1[0].weight.device
+        lay = N.zinb_head_layout(self._dims(2))
+        A, per_arm = self.n_arm, int(lay.per_arm)
+        flat = torch.zeros(A * per_arm, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for a in range(A):
+                for j, (name, kind) in enumerate(self._ZINB_PR):
+                    p = getattr(getattr(self, name)[a], kind)
+                    o = a * per_arm + int(lay.offset[j])
+                    v = flat[o: o + p.numel()].view(p.shape)
+                    v.copy_(p.data.to(torch.float32))
+                    p.data = v
+        self._heads_flat, self._heads_grad, self._heads_layout = flat, torch.zeros_like(flat), lay
+
+    def zinb_heads_flat(self):
+        """(the flat buffer of ``fc11_p`` / ``fc11_r``, its gradient buffer): [A, 2 (D H + D)] each, laid out per arm
+        ``fc11_p.weight | fc11_p.bias | fc11_r.weight | fc11_r.bias`` (mmvae_zinb_head_layout)."""
+        self._need_zinb("zinb_heads_flat()")
+        if not self._heads_packed():
+            self._pack_heads()
+        return self._heads_flat.view(self.n_arm, -1), self._heads_grad.view(self.n_arm, -1)
+
+    def zinb_step_state(self):
+        """A fresh optimiser state of ``zinb_train_step``: Adam's step count and the two moment pairs, all zero."""
+        self._need_zinb("zinb_step_state()")
+        flat = self.flat_parameters()
+        hp, _ = self.zinb_heads_flat()
+        z = torch.zeros_like
+        return {"kind": "zinb_step", "step": 0, "exp_avg": z(flat), "exp_avg_sq": z(flat), "hp_exp_avg": z(hp), "hp_exp_avg_sq": z(hp)}
+
+    def _check_zinb_step_state(self, what, state):
+        """ValueError for a state that is not ``zinb_step_state``'s of this model (``fit_zinb_heads`` / ``fit_zinb_decoder``
+        return another); reads shapes only."""
+        lay, A = N.param_layout(self._dims(2)), self.n_arm
+        n, hn = A * int(lay.per_arm), 2 * (self.input_dim * self.fc_dim + self.input_dim)
+        ok = (isinstance(state, dict) and state.get("kind") == "zinb_step"
+              and all(k in state for k in ("step", "exp_avg", "exp_avg_sq", "hp_exp_avg", "hp_exp_avg_sq"))
+              and all(int(state[k].numel()) == n for k in ("exp_avg", "exp_avg_sq"))
+              and all(tuple(state[k].shape) == (A, hn) for k in ("hp_exp_avg", "hp_exp_avg_sq")))
+        if not ok:
+            raise ValueError(f"{what}: state is not a ZINB training state of this model (zinb_step_state(): step and the moments "
+                             f"of the {n} flat parameters and of the [{A}, {hn}] p / r heads); the states of fit_zinb_heads / "
+                             "fit_zinb_decoder hold other moments")
+
+    @torch.no_grad()
+    def zinb_train_step(self, x, temp, state=None, do_adam=True, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """One training step under the ZINB objective in one C-ABI call (mmvae_zinb_train_step): the training-mode forward
+        (input and state dropout, batch-statistic BatchNorm, Gumbel noise, reparameterised ``s``), the reference's ``loss()``
+        with its reconstruction term replaced by ``zinb_loss`` (eps 1e-6), the backward through decoder, latent block and
+        encoder, and Adam (L2 ``weight_decay``, as ``torch.optim.Adam``) on all parameters, ``fc11_p`` and ``fc11_r`` included.
+        Consumes one noise draw and one ``_step_id``, as ``fused_train_step``.  Returns the device loss vector
+        (MMVAE_LOSS_*; ``rec[a]`` is the ZINB loss of arm a, ``ll[a]`` the reference's MSE-based expression); no host sync.
+
+        ``state``: ``zinb_step_state()``'s dict, updated in place (None: one the model keeps).  ``do_adam=False`` leaves the
+        gradients in ``flat_grad()`` and ``zinb_heads_flat()[1]`` and touches no state.  Needs ``model.train()`` and a model
+        built with ``loss_mode="ZINB"`` (RuntimeError otherwise); NotImplementedError for ``gemm_dtype="bf16"``.  Every
+        refusal comes before any device work, and consumes no noise."""
+        what = "zinb_train_step()"
+        self._need_zinb(what)
+        if not self.training:
+            raise RuntimeError(f"{what} needs model.train()")
+        if self.gemm_dtype == "bf16":
+            raise NotImplementedError(f"{what}: gemm_dtype='bf16' is not offered under the ZINB objective (bf16 heads are not built)")
+        if self.ref_prior:
+            raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
+        if do_adam:
+            if (not (0.0 <= lr < float("inf")) or not (0.0 <= weight_decay < float("inf")) or not eps >= 0.0 or len(betas) != 2
+                    or not all(0.0 <= b < 1.0 for b in betas)):
+                raise ValueError(f"{what}: lr = {lr}, betas = {betas}, eps = {eps}, weight_decay = {weight_decay}")
+            if state is not None:
+                self._check_zinb_step_state(what, state)
+        xt, xs = self._prep_x(x)
+        if xt.device.type != "cuda":
+            raise N.NativeError(f"{what} needs GPU tensors: the model runs only on the HIP engine")
+        assert xt.shape[-1] == self.input_dim
+        eng = self._ensure(xt.shape[-2])
+        hp, hg = self.zinb_heads_flat()
+        if do_adam and state is None:
+            if getattr(self, "_zinb_state", None) is None:
+                self._zinb_state = self.zinb_step_state()
+            state = self._zinb_state
+        hyper = self._hyper(temp, False)
+        noise = self._next_noise()
+        self._step_id += 1
+        self._ctx = None
+        if do_adam:
+            state["step"] = int(state["step"]) + 1
+            return eng.zinb_train_step(hyper, noise, self._flat, hp, self._bn_flat, self._nbt, xt, xs, self._flat_grad, hg, True,
+                                       state["exp_avg"], state["exp_avg_sq"], state["hp_exp_avg"], state["hp_exp_avg_sq"],
+                                       state["step"], float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                       False)
+        return eng.zinb_train_step(hyper, noise, self._flat, hp, self._bn_flat, self._nbt, xt, xs, self._flat_grad, hg, False,
+                                   None, None, None, None, 1, 0.0)
+
+    @torch.no_grad()
+    def zinb_objective(self, x, temp, mask=None):
+        """The training objective of ``zinb_train_step`` evaluated in eval mode: ``_forward(x, temp, True, mask, False)``, then
+        mmvae_zinb_objective on the workspace it left.  Returns the reference's 9-tuple as ``loss()`` does, with ``rec`` the
+        per-arm ZINB loss: ``(total, rec [A], loss_joint, c_entropy, c_distance, c_l2, [KL_a], [], [ll_a])``, 0-dim device
+        tensors.  ``loss()`` itself stays refused under ZINB.  Needs model.eval()."""
+        vals = self._zinb_objective_vec(x, temp, mask)
+        A = self.n_arm
+        if A == 1:
+            raise ZeroDivisionError("division by zero")          # the reference divides by len([]) here (nn_model.py:592-594)
+        rec = vals[N.LOSS_REC0: N.LOSS_REC0 + A]
+        kl = vals[N.LOSS_REC0 + A: N.LOSS_REC0 + 2 * A]
+        ll = vals[N.LOSS_REC0 + 2 * A: N.LOSS_REC0 + 3 * A]
+        return (vals[N.LOSS_TOTAL], rec.clone(), vals[N.LOSS_JOINT], vals[N.LOSS_CENT], vals[N.LOSS_CDIST], vals[N.LOSS_CL2],
+                list(kl.unbind(0)), [], list(ll.unbind(0)))
+
+    def _zinb_objective_vec(self, x, temp, mask):
+        """``zinb_objective``'s loss vector (MMVAE_LOSS_*), a fresh device tensor."""
+        self._need_zinb("zinb_objective()")
+        if self.training:
+            raise RuntimeError("zinb_objective() needs model.eval()")
+        self._forward(x, temp, True, mask, False)
+        hp, _ = self.zinb_heads_flat()
+        buf = self._engine.zinb_objective(self._ctx["hyper"], self._flat, hp, self._ctx["x"], self._ctx["x_arm_stride"])
+        self._ctx = None
+        return buf.clone()
+
     @torch.no_grad()
     def zinb_sample_batch(self, x, seed, temp=1.0, mask=None, offset=0, cell0=0, log1p=False, arms=None):
         """One ZINB draw per (arm, cell, gene) of the batch ``x`` (as ``forward`` takes it) at the model's own codes: an eval

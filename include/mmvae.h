@@ -705,6 +705,19 @@ int mmvae_zinb_d10_grad(const float *d10, int64_t ldh, int64_t N, int H, int D, 
                         const float *Wp, const float *bp, const float *Wr, const float *br, const float *X, int64_t ldx,
                         double eps, double scale, int head_mask, int segments, void *ws, size_t ws_bytes, float *gd10,
                         int64_t ldg, void *stream);
+/* mmvae_zinb_step_grads: mmvae_zinb_head_grads (at `segments` cell segments) and mmvae_zinb_d10_grad
+ *   (at one segment a gene tile, segments = ceil(D / 64)) from ONE evaluation of g: k_zg_heads' walk, in which a tile's image
+ *   of g, once multiplied (transposed) into d10 for dW, is also multiplied (M = cell, K = gene) into the 64 genes' rows of
+ *   W_j; the 64 x H partials, [gene tile][cell][H] float32 in ws, are added in rising order of the gene tiles in fp64, scaled
+ *   and rounded once.  The summation chains are the two entries': every output equals theirs bit for bit.
+ *   ws: mmvae_zinb_step_grads_workspace_bytes(N, D, H, segments) = mmvae_zinb_head_grads_workspace_bytes(N, D, H, segments)
+ *   + mmvae_zinb_d10_grad_workspace_bytes(N, D, H, ceil(D / 64)).  Refusals as the two entries'. */
+size_t mmvae_zinb_step_grads_workspace_bytes(int64_t N, int D, int H, int segments);
+int mmvae_zinb_step_grads(const float *d10, int64_t ldh, int64_t N, int H, int D, const float *W, const float *b,
+                          const float *Wp, const float *bp, const float *Wr, const float *br, const float *X, int64_t ldx,
+                          double eps, double scale, int head_mask, int segments, void *ws, size_t ws_bytes, float *dW,
+                          float *db, float *dWp, float *dbp, float *dWr, float *dbr, double *cell_sum, double *gene_sum,
+                          float *gd10, int64_t ldg, void *stream);
 size_t mmvae_decoder_trunk_grads_workspace_bytes(int64_t N, int Z, int L, int H, int segments);
 int mmvae_decoder_trunk_grads_segments(int64_t N, int segments);
 int mmvae_decoder_trunk_grads(int64_t N, int Z, int L, int H, const float *const *act, const int64_t *ld,
@@ -717,6 +730,59 @@ int mmvae_zinb_terms_grad(const float *x_rec, int64_t ld_rec, const float *x_p, 
 int mmvae_debug_zinb_grad_host(int64_t n, const float *X, const float *a_rec, const float *a_p, const float *a_r,
                                double eps, double *g, double *term /* NULL = not wanted */);
 int mmvae_debug_digamma_host(int64_t n, const double *x, double *out);
+
+/* ---- training under the ZINB likelihood ----
+ * The objective is the reference's loss() with the branch it left as `assert False` (mmidas/nn_model.py:547-549) taken
+ * literally:  total = max(A - 1, 1) sum_a (zinb_loss(x_rec_a, x_p_a, x_r_a, x_a) + beta KL_a) + loss_joint, zinb_loss the mean
+ * of the term over the B D elements of arm a as mmvae_zinb_nll evaluates it (zinb_eps: 1e-6 in the reference).  KL, entropy
+ * and coupling terms are those of mmvae_train_step.
+ *
+ * The p and r heads live outside the 28-tensor flat layout, in a second flat float buffer heads_pr:
+ *   [A][fc11_p.weight [D, H] | fc11_p.bias [D] | fc11_r.weight [D, H] | fc11_r.bias [D]], no padding;
+ * mmvae_zinb_head_layout gives per_arm = 2 (D H + D) and the four offsets 0, D H, D H + D, 2 D H + D.  head_grads and the two
+ * moment buffers hp_exp_avg, hp_exp_avg_sq have that shape.
+ *
+ * mmvae_zinb_train_step (call kind MMVAE_CALL_ZINB_STEP; needs h->training), on the call's stream alone (a side stream of
+ * ex is not used):
+ *   1. mmvae_train_step's forward pass, its fc11 launch included: the workspace's D10 and ZIN hold the step's activations,
+ *      the BatchNorm running statistics and nbt are updated exactly as mmvae_train_step updates them, and the fc11 launch
+ *      leaves the partial sums of (relu(a_rec) - x)^2 that ll[a] is made of (its dZ11 and d(d10) are not read);
+ *   2., 3. per arm mmvae_zinb_step_grads (below: head_mask 7, segments 0) on D10 and x with scale = max(A - 1, 1) / (B D): what
+ *      mmvae_zinb_head_grads gives for the three heads -- fc11's dW, db go to tensors 26 / 27 of grads, the other two heads'
+ *      to head_grads -- and what mmvae_zinb_d10_grad gives at one segment a gene tile, written as the first slab of
+ *      MMVAE_WS_GD10_SLAB, from one evaluation of g;
+ *   4. the loss vector, then mmvae_train_step's backward pass from that one slab, without the dW11 GEMM: the other 26
+ *      tensors of grads.
+ * The ZINB kernels run on the fp32 matrix instruction; everything else on the engine h->gemm_bf16 states (0 or 2).
+ * loss_out keeps the MMVAE_LOSS_* layout: rec[a] = zinb_loss of arm a (the fp64 per-cell sums added in a fixed order, divided
+ * by B D, rounded once), total uses it; ll[a] keeps the reference's MSE-based expression (:542).
+ * do_adam: mmvae_adam_step on params / grads / exp_avg / exp_avg_sq (A per_arm floats of mmvae_param_layout) and on heads_pr /
+ * head_grads / hp_exp_avg / hp_exp_avg_sq, the same step; the alignment gaps of params, grads and the moments must hold
+ * zeros (they then keep them).  do_adam == 0 leaves the gradients in grads / head_grads.
+ * No atomics beyond those of mmvae_train_step's chains (the exact fixed-point batch sums): bit-identical from run to run.
+ *   zws: mmvae_zinb_step_workspace_bytes(d, ex) = mmvae_zinb_step_grads_workspace_bytes(B, D, H, 0) + 8 (A B + D + A) bytes,
+ *        8-byte aligned; 0 for dims the step refuses.
+ * Refusals, all before the first launch: those of mmvae_train_step; MMVAE_E_UNSUPPORTED for eval mode, gemm_bf16 == 1 and a
+ * non-zero cat_mask; MMVAE_E_BADARG for a NULL buffer, zinb_eps outside [0, 1), a negative arm stride, missing Adam state;
+ * MMVAE_E_WORKSPACE for ws or zws below its size.
+ *
+ * mmvae_zinb_objective follows mmvae_forward on the same ws, in any mode, as mmvae_loss does: mmvae_zinb_nll per arm on D10,
+ * then mmvae_loss's scalars with rec[a] = zinb_loss of arm a.  A cat_mask is allowed (eval). */
+typedef struct {
+    int64_t per_arm;        /* floats per arm: 2 (D H + D) */
+    int64_t offset[4];      /* fc11_p.weight, fc11_p.bias, fc11_r.weight, fc11_r.bias */
+} mmvae_zinb_head_layout_t;
+int mmvae_zinb_head_layout(const mmvae_dims *d, mmvae_zinb_head_layout_t *out);
+size_t mmvae_zinb_step_workspace_bytes(const mmvae_dims *d, const mmvae_exec *ex);
+int mmvae_zinb_train_step(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noise *nz, float *params, float *heads_pr,
+                          float *bn_running, int64_t *nbt, const float *x, int64_t x_arm_stride, double zinb_eps, void *ws,
+                          size_t ws_bytes, void *zws, size_t zws_bytes, float *grads, float *head_grads, float *loss_out,
+                          int do_adam, float *exp_avg, float *exp_avg_sq, float *hp_exp_avg, float *hp_exp_avg_sq,
+                          int64_t step, float lr, float beta1, float beta2, float adam_eps, float weight_decay,
+                          int decoupled, mmvae_exec *ex, void *stream);
+int mmvae_zinb_objective(const mmvae_dims *d, const mmvae_hyper *h, const float *params, const float *heads_pr,
+                         const float *x, int64_t x_arm_stride, double zinb_eps, void *ws, size_t ws_bytes, void *zws,
+                         size_t zws_bytes, float *loss_out, mmvae_exec *ex, void *stream);
 
 /* ---- count distributions (mmidas/utils/distributions.py) ----
  * The scVI-parameterised likelihoods of count data and one draw per element of NB / ZINB.  All matrices are float32 [N, D],
@@ -1208,6 +1274,7 @@ int mmvae_debug_stage(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_noi
 #define MMVAE_CALL_DECODE 7
 #define MMVAE_CALL_TRAVERSE 8
 #define MMVAE_CALL_ENCODE 10   /* (9 is not a call kind: mmvae_debug_plan refuses it as unknown, as it always has) */
+#define MMVAE_CALL_ZINB_STEP 11   /* mmvae_zinb_train_step: planned without a side stream whatever ex states; gd10_slabs is 1 */
 int mmvae_debug_plan(const mmvae_dims *d, const mmvae_hyper *h, const mmvae_exec *ex, int call_kind,
                      int params_align, int x_align, int64_t x_arm_stride, int has_x16, int fc11_grad,
                      int32_t out[MMVAE_PLAN_FIELDS]);
