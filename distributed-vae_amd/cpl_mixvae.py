@@ -25,17 +25,43 @@ from .nn_model import VAEConfig, mixVAE_model  # noqa: F401
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam / AdamW semantics (cpl_mixvae.py:274, train.py:144-147) as ONE HIP kernel over
     the model's flat parameter buffer.  ``state_dict()`` is torch.optim.Adam-compatible so reference
-    checkpoints (``optimizer_state_dict``, cpl_mixvae.py:783-786) load and save unchanged."""
+    checkpoints (``optimizer_state_dict``, cpl_mixvae.py:783-786) load and save unchanged.
+
+    On a model built with ``mode="ZINB"`` it owns four moment buffers and one step count: ``exp_avg`` / ``exp_avg_sq`` over
+    the flat buffer of the 28 tensors per arm, ``hp_exp_avg`` / ``hp_exp_avg_sq`` over the [A, 2 (D H + D)] buffer of
+    ``fc11_p`` / ``fc11_r`` (``mixVAE_model.zinb_heads_flat``).  ``step()`` is then two mmvae_adam_step launches,
+    ``state_dict()`` covers all 32 parameters per arm, and ``zinb_state()`` hands the same buffers to
+    ``mixVAE_model.zinb_train_step(state=...)``.  ``decoupled=True`` (AdamW) is refused there: the fused ZINB step has not been
+    checked against ``torch.optim.AdamW``."""
 
     def __init__(self, model: mixVAE_model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  decoupled=False):
+        if decoupled and getattr(model, "loss_mode", "MSE") == "ZINB":
+            raise NotImplementedError("FusedAdam(decoupled=True) on a model built with loss_mode='ZINB' is not offered")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                         foreach=None, capturable=False, differentiable=False, fused=None)
+        # the one place the step count lives: the dict ``zinb_state()`` hands to ``zinb_train_step``, which counts in it
+        self._zstate = {"kind": "zinb_step", "step": 0}
         super().__init__(list(model.parameters()), defaults)
         self.model = model
         self.decoupled = bool(decoupled)
-        self.step_count = 0
         self.exp_avg = self.exp_avg_sq = None
+        self.hp_exp_avg = self.hp_exp_avg_sq = None
+
+    @property
+    def step_count(self) -> int:
+        return int(self._zstate["step"])
+
+    @step_count.setter
+    def step_count(self, n):
+        self._zstate["step"] = int(n)
+
+    def _zinb(self) -> bool:
+        return getattr(self.model, "loss_mode", "MSE") == "ZINB"
+
+    def _refuse_decoupled(self):
+        if self.decoupled and self._zinb():
+            raise NotImplementedError("FusedAdam(decoupled=True) on a model built with loss_mode='ZINB' is not offered")
 
     def _bind(self, model=None):
         flat = self.model.flat_parameters()
@@ -46,20 +72,45 @@ class FusedAdam(torch.optim.Optimizer):
             if old[0] is not None and old[0].numel() == flat.numel():
                 self.exp_avg.copy_(old[0])
                 self.exp_avg_sq.copy_(old[1])
+        if self._zinb():
+            hp, _ = self.model.zinb_heads_flat()
+            if self.hp_exp_avg is None or self.hp_exp_avg.device != hp.device or self.hp_exp_avg.shape != hp.shape:
+                old = (self.hp_exp_avg, self.hp_exp_avg_sq)
+                self.hp_exp_avg = torch.zeros_like(hp)
+                self.hp_exp_avg_sq = torch.zeros_like(hp)
+                if old[0] is not None and old[0].shape == hp.shape:
+                    self.hp_exp_avg.copy_(old[0])
+                    self.hp_exp_avg_sq.copy_(old[1])
+
+    def zinb_state(self):
+        """The state ``mixVAE_model.zinb_train_step(state=...)`` updates in place, made of this optimizer's own four moment
+        buffers and its step count (the same dict at every call): a fused ZINB step is this optimizer's step."""
+        self._refuse_decoupled()
+        self._bind()
+        self._zstate.update(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, hp_exp_avg=self.hp_exp_avg,
+                            hp_exp_avg_sq=self.hp_exp_avg_sq)
+        return self._zstate
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._refuse_decoupled()
         self._bind()
         self.step_count += 1
         g = self.param_groups[0]
         N.adam_step(self.model.flat_parameters(), self.model.flat_grad(), self.exp_avg, self.exp_avg_sq,
                     self.step_count, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
                     self.decoupled)
+        if self._zinb():
+            hp, hg = self.model.zinb_heads_flat()
+            N.adam_step(hp, hg, self.hp_exp_avg, self.hp_exp_avg_sq, self.step_count, g["lr"], g["betas"][0],
+                        g["betas"][1], g["eps"], g["weight_decay"], False)
 
     def zero_grad(self, set_to_none: bool = False):
         self.model.flat_grad().zero_()
+        if self._zinb():
+            self.model.zinb_heads_flat()[1].zero_()
 
-    def _views(self, buf):
+    def _views(self, buf, hbuf=None):
         lay, A = self.model._layout, self.model.n_arm
         out = {}
         for a in range(A):
@@ -67,11 +118,14 @@ class FusedAdam(torch.optim.Optimizer):
                 p = self.model._param_of(t, a)
                 o = a * int(lay.per_arm) + int(lay.offset[t])
                 out[id(p)] = buf[o: o + p.numel()].view(p.shape)
+        if hbuf is not None:
+            for a, _, p, o in self.model._zinb_head_params():
+                out[id(p)] = hbuf[a, o: o + p.numel()].view(p.shape)
         return [out[id(p)] for p in self.model.parameters()]
 
     def state_dict(self):
         self._bind()
-        m, v = self._views(self.exp_avg), self._views(self.exp_avg_sq)
+        m, v = self._views(self.exp_avg, self.hp_exp_avg), self._views(self.exp_avg_sq, self.hp_exp_avg_sq)
         n = len(m)
         state = {}
         if self.step_count > 0:
@@ -87,7 +141,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         self._bind()
-        m, v = self._views(self.exp_avg), self._views(self.exp_avg_sq)
+        m, v = self._views(self.exp_avg, self.hp_exp_avg), self._views(self.exp_avg_sq, self.hp_exp_avg_sq)
         for i, st in sd.get("state", {}).items():
             i = int(i)
             m[i].copy_(st["exp_avg"])
@@ -227,6 +281,46 @@ class cpl_mixVAE:
             self.model.prune_apply(mask, grads=False)            # weight_orig * mask behind a stock optimizer's step
         return buf
 
+    def _is_zinb(self) -> bool:
+        return getattr(getattr(self, "model", None), "loss_mode", "MSE") == "ZINB"
+
+    def _zinb_refusals(self, what):
+        """What ZINB training does not offer, refused before any device work and before noise is consumed: the bf16
+        configuration, a category mask (set by ``prune``, or implied by a model whose ``fcc`` bias has zeros), AdamW through
+        ``FusedAdam``."""
+        m = self.model
+        if m.gemm_dtype == "bf16":
+            raise NotImplementedError(f"{what}: gemm_dtype='bf16' is not offered under the ZINB objective (bf16 heads are not built)")
+        if (self._prune_mask is not None
+                or int(np.count_nonzero(m.fcc[0].bias.detach().cpu().numpy() != 0.0)) < self.n_categories):
+            raise NotImplementedError(f"{what}: the model has pruned categories; a category mask is not offered in ZINB training")
+        if isinstance(self.optimizer, FusedAdam):
+            self.optimizer._refuse_decoupled()
+
+    def _zinb_step(self, xs: torch.Tensor):
+        """``_step`` for a model built with ``mode="ZINB"`` (``_step`` itself refuses one): one
+        ``mixVAE_model.zinb_train_step`` on ``xs``.  With the trainer's own ``FusedAdam`` the update is the fused step's, on
+        the optimizer's own moment buffers and step count (``FusedAdam.zinb_state``) and with ``param_groups[0]``'s ``lr``,
+        ``betas``, ``eps`` and ``weight_decay``; any other optimizer assigned to ``self.optimizer`` gets the gradients through
+        each parameter's ``.grad`` (``bind_grads``: ``fc11_p`` / ``fc11_r`` included) and steps itself.  Under a process group:
+        ``dist.dp_zinb_train_step``.  Returns the device loss vector; no host synchronisation."""
+        m, opt = self.model, self.optimizer
+        m._need_zinb("_zinb_step()")
+        if m.gemm_dtype == "bf16":
+            raise NotImplementedError("_zinb_step(): gemm_dtype='bf16' is not offered under the ZINB objective (bf16 heads are not built)")
+        if self._prune_mask is not None:
+            raise NotImplementedError("_zinb_step(): the model has pruned categories; a category mask is not offered in ZINB training")
+        if D.is_dist():
+            return D.dp_zinb_train_step(m, xs, self.temp, opt)
+        if isinstance(opt, FusedAdam) and opt.model is m:
+            g = opt.param_groups[0]
+            return m.zinb_train_step(xs, self.temp, state=opt.zinb_state(), do_adam=True, lr=g["lr"], betas=g["betas"],
+                                     eps=g["eps"], weight_decay=g["weight_decay"])
+        buf = m.zinb_train_step(xs, self.temp, do_adam=False)
+        m.bind_grads()
+        opt.step()
+        return buf
+
     def _step_rows(self, data: torch.Tensor, rows: torch.Tensor, data16=None):
         """``_step`` on the batch ``data[rows]`` read in place (``mixVAE_model.fused_train_step_rows``); ``data16``: the
         matrix's bf16 copy for the bf16 configuration (bf16 storage)."""
@@ -250,7 +344,7 @@ class cpl_mixVAE:
         xs = x.expand(self.n_arm, -1, -1)
         if self.netA is not None:
             xs = self.netA(xs, True, 0.1)[1]                    # cpl_mixvae.py:422-423
-        return self._step(xs)
+        return (self._zinb_step if self._is_zinb() else self._step)(xs)
 
     def epoch_steps(self, loader):
         """Generator over the loss vectors of one pass over ``loader`` (the inner loop of cpl_mixvae.py:415-478).
@@ -260,8 +354,19 @@ class cpl_mixVAE:
         the frozen eval-mode augmenter -- on a high-priority side stream beside the train step of batch i.  The
         augmenter's GEMMs fill the matrix pipe while the step sits in its latency-bound chain kernels (measured at the
         benchmark shape: 2.93 ms per augmented batch against 3.21 ms back to back).  Same arithmetic and the same order
-        of random draws as the unpipelined loop (``pipeline = False`` / MMVAE_PIPELINE=0)."""
+        of random draws as the unpipelined loop (``pipeline = False`` / MMVAE_PIPELINE=0).
+
+        The step function is picked once per epoch: ``_step``, or ``_zinb_step`` for a model built with ``mode="ZINB"``, which
+        always runs this gathered-batch loop (with an augmenter, on each arm's own augmented batch) and never the
+        row-indexed steps below."""
         A = self.n_arm
+        # a model built with mode="ZINB": ``_zinb_step`` on gathered batches (there is no row-indexed ZINB step), after the
+        # refusals of ZINB training; chosen once per epoch
+        zinb = self._is_zinb()
+        if zinb:
+            self._zinb_refusals("epoch_steps()")
+            self.used_bf16_storage = False
+        step = self._zinb_step if zinb else self._step
 
         def first(b):
             return b[0] if isinstance(b, (tuple, list)) else b
@@ -271,7 +376,7 @@ class cpl_mixVAE:
         # row map), so a shuffled epoch costs what fixed batches do (the 100 MB row gather per step, and the hook that hid it
         # beside the encoder chain, are gone from this path).  Where the library does not offer it (other GEMM engines,
         # matrices beyond 4 GB) the first step says so and the epoch falls back to gathered batches.
-        if (self.netA is None and self.device.type == "cuda" and hasattr(loader, "iter_rows")
+        if (not zinb and self.netA is None and self.device.type == "cuda" and hasattr(loader, "iter_rows")
                 and getattr(loader, "data", None) is not None and os.environ.get("MMVAE_ROWS", "1") != "0"
                 and getattr(self, "_rows_ok", True)):
             it = loader.iter_rows()
@@ -372,7 +477,7 @@ class cpl_mixVAE:
                     nxt = produce()
             xs, x, ev = cur
             main.wait_event(ev)
-            buf = self._step(xs)
+            buf = step(xs)
             if late:
                 with torch.cuda.stream(side):
                     nxt = produce()
@@ -391,15 +496,26 @@ class cpl_mixVAE:
         validation block (:665-775), the 10-epoch checkpoint (:777-788) and the stop at ``good_enuf_consensus``
         (:851-927: checkpoint ``cns_cpl_mixVAE_model_before_pruning_A{A}_...pth``, then ``break``).  Pruning
         (:996-1444) is disabled upstream and not offered.  Returns the per-epoch history (the reference returns None and
-        hands the same numbers to its logger ``run``)."""
+        hands the same numbers to its logger ``run``).
+
+        A model built with ``mode="ZINB"`` trains through the same loop: ``epoch_steps`` runs ``_zinb_step`` (the fused step
+        under the ZINB objective) and ``validate`` takes its losses from ``zinb_objective``; everything else is the same
+        code.  ``loss_recs[a]`` keeps the reference's formula taken literally, ``rec[a] / D / steps`` (:475, :491), now
+        applied to the ZINB loss -- which is already a mean over the D genes, so the entry is that mean divided by D once
+        more.  Refused before any device work (NotImplementedError): ``gemm_dtype="bf16"``, a model with pruned
+        categories, AdamW through ``FusedAdam``."""
         A, Dm = self.n_arm, self.input_dim
         dev = self.device
         if not self.init:
             return {}
         if self.n_arm == 1:
             raise ZeroDivisionError("division by zero")   # nn_model.py:592-594
+        if self._is_zinb():
+            self._zinb_refusals("train()")
         if D.is_dist():
             D.broadcast_flat(self.model.flat_parameters())
+            if self._is_zinb():
+                D.broadcast_flat(self.model.zinb_heads_flat()[0])          # fc11_p / fc11_r live outside the 28 tensors
         hist = {"losses": [], "loss_joints": [], "loss_recs": [[] for _ in range(A)], "c_ents": [], "c_l2_dists": [],
                 "c_dists": [], "validation_loss": [], "validation_rec_loss": [], "consensus_train": [], "consensus_aug": [],
                 "consensus_val": [], "epoch_times": [], "stopped_at": None}
@@ -496,7 +612,11 @@ class cpl_mixVAE:
         of pruned entries are held at 0 where ``torch.nn.utils.prune`` leaves decaying remnants in the optimizer state;
         they never reach an effective weight.  No plots.  Returns the history: ``pruned`` (every pruned category in the
         order of the reference's ``ind``: those of the starting model first), ``kept``, ``agreement`` (one float64 [C] array
-        per assessment), ``rounds`` and the per-epoch lists of ``train`` (all retraining epochs in sequence)."""
+        per assessment), ``rounds`` and the per-epoch lists of ``train`` (all retraining epochs in sequence).  A model built with
+        ``mode="ZINB"`` is refused: the ZINB step takes no category mask."""
+        if self._is_zinb():
+            raise NotImplementedError("cpl_mixVAE.prune on a model built with loss_mode='ZINB': the ZINB train step takes no "
+                                      "category mask")
         if D.is_dist():
             raise NotImplementedError("cpl_mixVAE.prune under data parallelism: the category mask is not plumbed through "
                                       "dist.dp_train_step yet (issue 'Add the pruning phase: cpl_mixVAE.prune on a masked "
@@ -657,11 +777,14 @@ class cpl_mixVAE:
         rec loss, or the triple ``(validation_loss, validation_rec_loss, consensus_val)`` with ``full=True``.  With
         the reference's default test loader (batch_size 1) the whole set is one batch and ``len(loader)`` its row
         count, as in the reference.  ``mask``: the kept categories of a pruned model, as ``forward(mask=)`` takes them (the
-        pruning phase validates under its mask, :1317-1323, :1362-1369)."""
+        pruning phase validates under its mask, :1317-1323, :1362-1369).  On a model built with ``mode="ZINB"`` the
+        per-batch loss vector is the ZINB objective's (``mixVAE_model.zinb_objective``: ``loss_rec[a]`` the ZINB loss) on the
+        same eval forward; the formulas, the skipped one-cell batch and the consensus are the same."""
         from ._utils import confmat_counts, consensus_from_counts
         was_training = self.model.training
         self.model.eval()
         A = self.n_arm
+        zinb = self._is_zinb()
         counts = confmat_counts(A, self.n_categories, self.device)
         tot = torch.zeros((), dtype=torch.float64, device=self.device)
         rec = torch.zeros((), dtype=torch.float64, device=self.device)
@@ -671,11 +794,21 @@ class cpl_mixVAE:
             if x.shape[0] < 2:     # a one-cell batch has no batch variance: the reference's loss is NaN there (nn_model.py:75)
                 continue
             xs = x.expand(A, -1, -1)
-            out = self.model(xs, self.temp, 0.0, eval=True, mask=mask)
-            lt = self.model.loss(out[0], [], [], xs, out[7], out[8], out[4], out[6], 0.0)
-            tot += lt[0].double()                                             # :741 val_loss += loss.data.item()
-            rec += lt[1].double().sum() / self.input_dim                      # :742-743 sum_a loss_rec[a] / D
-            labels = torch.stack([N.classify(c) for c in out[4]])            # :744 / :752 classify(cs[a])
+            if zinb:
+                if A == 1:
+                    raise ZeroDivisionError("division by zero")              # nn_model.py:592-594, as loss() raises it
+                out = self.model._forward(xs, self.temp, True, mask, False)  # what _zinb_objective_vec runs, c kept
+                vec = self.model._zinb_objective_here()
+                self.model._ctx = None
+                tot += vec[N.LOSS_TOTAL].double()
+                rec += vec[N.LOSS_REC0: N.LOSS_REC0 + A].double().sum() / self.input_dim
+                labels = torch.stack([N.classify(c) for c in out[4]])
+            else:
+                out = self.model(xs, self.temp, 0.0, eval=True, mask=mask)
+                lt = self.model.loss(out[0], [], [], xs, out[7], out[8], out[4], out[6], 0.0)
+                tot += lt[0].double()                                             # :741 val_loss += loss.data.item()
+                rec += lt[1].double().sum() / self.input_dim                      # :742-743 sum_a loss_rec[a] / D
+                labels = torch.stack([N.classify(c) for c in out[4]])            # :744 / :752 classify(cs[a])
             N.confmat_accumulate(labels, self.n_categories, counts)
             seen += 1
         self.model.train(was_training)
@@ -696,10 +829,16 @@ class cpl_mixVAE:
         [A,N], ``data_indx`` [N], ``z_prob`` (c) and ``z_sample`` (c_smp) [A,N,C], ``x_low`` [A,N,L], ``recon_c``
         (x_rec) [A,N,D], ``prune_indx`` (categories whose fcc bias is zero) and ``cnss`` (between-arm consensus of the
         labels).  Forward, loss, labels, confusion counts and consensus run on the device; the per-batch outputs are
-        collected in device buffers and copied to the host once."""
+        collected in device buffers and copied to the host once.  On a model built with ``mode="ZINB"`` the loss is the ZINB
+        objective on the workspace of the same eval forward (one forward per batch, ``x_p`` / ``x_r`` never written):
+        ``total_loss_rec`` is the per-arm mean over batches of the ZINB loss, ``total_likelihood`` the reference's MSE-based
+        ``ll`` that the objective carries; every other key is what the MSE path gives."""
         if self.ref_prior:
             raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
         A, Cc, Dm, L, S = self.n_arm, self.n_categories, self.input_dim, self.lowD_dim, self.state_dim
+        zinb = self._is_zinb()
+        if zinb and A == 1:
+            raise ZeroDivisionError("division by zero")                   # nn_model.py:592-594, as loss() raises it
         n_rows = len(dl.dataset)
         B = dl.batch_size
         if B is None:
@@ -721,9 +860,15 @@ class cpl_mixVAE:
             n_fst, n_lst = i * B, min((i + 1) * B, n_rows)
             x = x.to(dev)
             xs = x.expand(A, -1, -1)                                      # xs = [x for _ in range(A)], :1519
-            out = self.model(xs, self.temp, prior_c=0.0, eval=True, mask=pruning_mask)
-            self.model.loss(out[0], out[1], out[2], xs, out[7], out[8], out[4], out[6], 0.0)
-            loss_vecs.append(self.model._engine.loss_buf.clone())         # the 9-tuple's scalars, still on the device
+            if zinb:
+                # no x_p / x_r are written: the ZINB objective forms the heads tile by tile from the workspace's d10
+                out = self.model._forward(xs, self.temp, True, pruning_mask, False)
+                loss_vecs.append(self.model._zinb_objective_here())
+                self.model._ctx = None
+            else:
+                out = self.model(xs, self.temp, prior_c=0.0, eval=True, mask=pruning_mask)
+                self.model.loss(out[0], out[1], out[2], xs, out[7], out[8], out[4], out[6], 0.0)
+                loss_vecs.append(self.model._engine.loss_buf.clone())     # the 9-tuple's scalars, still on the device
             for dst, k in ((s_means, 7), (s_logvars, 8), (cs, 4), (c_smps, 6), (x_lows, 3), (x_recs, 0)):
                 dst[:, n_fst:n_lst] = torch.stack(list(out[k]))
             data_indx[n_fst:n_lst] = torch.as_tensor(data_idx).to(dev).to(torch.int64).to(torch.float64)

@@ -191,6 +191,21 @@ def dp_train_step(model, xs, temp, optimizer, rehearse: bool = False, rows=None)
     return buf
 
 
+def dp_zinb_train_step(model, xs, temp, optimizer):
+    """``dp_train_step`` for a model built with ``loss_mode="ZINB"``: ``zinb_train_step(do_adam=False)``, then the average over
+    the ranks of both gradient buffers -- the flat buffer of the 28 tensors per arm and the [A, 2 (D H + D)] buffer of
+    ``fc11_p`` / ``fc11_r`` -- through ``allreduce_mean_``, one collective each, then the optimizer's step (a stock
+    ``torch.optim`` optimizer reads the gradients through ``p.grad``).  BatchNorm running statistics stay rank-local.
+    MMVAE_DP_OVERLAP and MMVAE_DP_DIRECT are not offered here and are ignored."""
+    buf = model.zinb_train_step(xs, temp, do_adam=False)
+    allreduce_mean_(model.flat_grad())
+    allreduce_mean_(model.zinb_heads_flat()[1])
+    if not hasattr(optimizer, "_bind"):
+        model.bind_grads()
+    optimizer.step()
+    return buf
+
+
 def allreduce_sum_(buf: torch.Tensor):
     """Per-epoch scalar reduction (cpl_mixvae.py:480-483), folded into one small tensor."""
     if is_dist():

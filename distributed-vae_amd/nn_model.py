@@ -240,6 +240,10 @@ class mixVAE_model(nn.Module):
             self._pack()
         for p, gv in zip(self.parameters(), self._grad_views):
             p.grad = gv
+        if self.loss_mode == "ZINB":      # the p and r heads: views of their own gradient buffer (``zinb_train_step`` fills it)
+            _, hg = self.zinb_heads_flat()
+            for a, _, p, o in self._zinb_head_params():
+                p.grad = hg[a, o: o + p.numel()].view(p.shape)
 
     # ------------------------------------------------------------------ noise control
     def set_explicit_noise(self, noise):
@@ -777,6 +781,14 @@ class mixVAE_model(nn.Module):
             self._pack_heads()
         return self._heads_flat.view(self.n_arm, -1), self._heads_grad.view(self.n_arm, -1)
 
+    def _zinb_head_params(self):
+        """(arm, index in the head layout, the ``nn.Parameter``, its offset in an arm's row of ``zinb_heads_flat``) for the
+        four head tensors of every arm."""
+        self.zinb_heads_flat()
+        lay = self._heads_layout
+        return [(a, j, getattr(getattr(self, name)[a], kind), int(lay.offset[j]))
+                for a in range(self.n_arm) for j, (name, kind) in enumerate(self._ZINB_PR)]
+
     def zinb_step_state(self):
         """A fresh optimiser state of ``zinb_train_step``: Adam's step count and the two moment pairs, all zero."""
         self._need_zinb("zinb_step_state()")
@@ -871,10 +883,15 @@ class mixVAE_model(nn.Module):
         if self.training:
             raise RuntimeError("zinb_objective() needs model.eval()")
         self._forward(x, temp, True, mask, False)
-        hp, _ = self.zinb_heads_flat()
-        buf = self._engine.zinb_objective(self._ctx["hyper"], self._flat, hp, self._ctx["x"], self._ctx["x_arm_stride"])
+        vec = self._zinb_objective_here()
         self._ctx = None
-        return buf.clone()
+        return vec
+
+    def _zinb_objective_here(self):
+        """mmvae_zinb_objective on the workspace the preceding eval ``_forward`` left (``cpl_mixVAE.eval_model`` keeps that
+        forward's outputs and so runs it once per batch): the loss vector, a fresh device tensor."""
+        hp, _ = self.zinb_heads_flat()
+        return self._engine.zinb_objective(self._ctx["hyper"], self._flat, hp, self._ctx["x"], self._ctx["x_arm_stride"]).clone()
 
     @torch.no_grad()
     def zinb_sample_batch(self, x, seed, temp=1.0, mask=None, offset=0, cell0=0, log1p=False, arms=None):

@@ -67,7 +67,8 @@ def parse_args(argv=None):
     p.add_argument("--pretrained_model", default=False, type=bool, help="train.py:229-231: start from --trained_model")
     p.add_argument("--trained_model", default="", type=str, help="checkpoint for --pretrained_model (mmidas.toml 'trained')")
     p.add_argument("--n_pr", default=0, type=int, help="train.py:232-237")
-    p.add_argument("--loss_mode", default="MSE", type=str, help="train.py:241-243 (ZINB is rejected by forward, nn_model.py:315)")
+    p.add_argument("--loss_mode", default="MSE", type=str, help="train.py:241-243: MSE, or ZINB (the fused step under the ZINB objective; fp32 only, no pruning, "
+                                                                     "with --optimizer adamw the stock torch.optim.AdamW steps)")
     p.add_argument("--hard", default=False, type=bool, help="train.py:245: straight-through one-hot samples")
     p.add_argument("--log-dir", dest="log_dir", default="", help="directory for the ranks' rank<r>.err files")
     p.add_argument("--gemm-dtype", default="fp32", choices=["fp32", "bf16", "fp32_mfma"])
