@@ -72,6 +72,19 @@ class AugTensors(C.Structure):
                 ("bnz_weight", C.c_void_p), ("bnz_bias", C.c_void_p), ("bnz_mean", C.c_void_p), ("bnz_var", C.c_void_p)]
 
 
+class AugTrainLayout(C.Structure):
+    """mmvae_aug_train_layout: Linear layers 0..13 = fc1..fc11, fc_mu, fc_sigma, noise; BatchNorms 0..11 = batch_fc1..batch_fc10,
+    batch_fc_mu, bnz."""
+    _fields_ = [("w_off", C.c_int64 * 14), ("b_off", C.c_int64 * 14), ("rows", C.c_int64 * 14), ("cols", C.c_int64 * 14),
+                ("bnz_w_off", C.c_int64), ("bnz_b_off", C.c_int64), ("total", C.c_int64),
+                ("rm_off", C.c_int64 * 12), ("rv_off", C.c_int64 * 12), ("bn_n", C.c_int64 * 12), ("run_total", C.c_int64),
+                ("act_off", C.c_int64 * 10)]
+
+
+AUG_LINEARS = [f"fc{i}" for i in range(1, 12)] + ["fc_mu", "fc_sigma", "noise"]
+AUG_BATCHNORMS = [f"batch_fc{i}" for i in range(1, 11)] + ["batch_fc_mu", "bnz"]
+
+
 class EncodeOut(C.Structure):
     """mmvae_encode_out: the arrays an encode is to write; each may be None."""
     _fields_ = [(n, C.c_void_p) for n in ("x_low", "c_prob", "c", "c_smp", "s_mean", "s_logvar", "labels", "counts")]
@@ -317,6 +330,12 @@ def lib():
     L.mmvae_aug_workspace_bytes.restype = C.c_size_t
     L.mmvae_aug_pack.argtypes = [C.POINTER(AugDims), C.POINTER(AugTensors), vp, vp]
     L.mmvae_augment.argtypes = [C.POINTER(AugDims), vp, vp, i64, vp, vp, f32, vp, C.c_size_t, vp, vp, i32, ex, vp]
+    L.mmvae_aug_param_layout.argtypes = [C.POINTER(AugDims), C.POINTER(AugTrainLayout)]
+    L.mmvae_aug_train_workspace_bytes.argtypes = [C.POINTER(AugDims)]
+    L.mmvae_aug_train_workspace_bytes.restype = C.c_size_t
+    L.mmvae_aug_train_forward.argtypes = [C.POINTER(AugDims), vp, vp, vp, vp, vp, f32, vp, vp, f32, vp, C.c_size_t, vp, vp, ex, vp]
+    L.mmvae_aug_train_step.argtypes = [C.POINTER(AugDims), vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, vp, C.c_size_t,
+                                       vp, vp, vp, vp, i32, vp, vp, i64, f32, f32, f32, f32, f32, ex, vp]
     L.mmvae_gather_rows.argtypes = [vp, i64, i64, vp, i64, i32, vp, vp]
     L.mmvae_tp_planes_bytes.argtypes = [i64, i32, i32]
     L.mmvae_tp_planes_bytes.restype = C.c_size_t

@@ -1117,6 +1117,39 @@ int mmvae_augment_rows(const mmvae_aug_dims *d, const float *packed, const uint1
                        void *ws, size_t ws_bytes, float *s_out, float *x_aug, int gemm_bf16,
                        const mmvae_exec *ex, void *stream);
 
+/* ---- augmenter training (mmidas/augmentation/train.py:10-157 in MSE mode) ----------------------
+ * The training-mode forward of Augmenter_smartseq (udagan.py:311-329: dropout, batch-statistic BatchNorm with running-statistic
+ * updates) and one step of the reference's train_augmenter, of which only weight * mse_loss(x_aug, x) has a gradient with
+ * respect to the augmenter.  One arm (d->A == 1: the non-batched forward), d->B >= 2.
+ * Linear layers l = 0..13: fc1..fc11, fc_mu, fc_sigma, noise (no bias: b_off = -1).  BatchNorms i = 0..11: batch_fc1..batch_fc10,
+ * batch_fc_mu, bnz.  params / grads / the Adam moments: flat fp32 buffers of `total` floats in the order of
+ * Augmenter_smartseq.parameters(), PyTorch layouts, alignment gaps that hold zeros; running: flat fp32 buffer of run_total floats
+ * (rm_off / rv_off); nbt: int64 [12] num_batches_tracked.  act_off[i]: where the workspace keeps y^_i = the normalised
+ * pre-activation of fc(i+1) ([B, rows] contiguous; h_i = relu(y^_i)) after a forward or a step. */
+typedef struct mmvae_aug_train_layout {
+    int64_t w_off[14], b_off[14], rows[14], cols[14];
+    int64_t bnz_w_off, bnz_b_off, total;
+    int64_t rm_off[12], rv_off[12], bn_n[12], run_total;
+    int64_t act_off[10];
+} mmvae_aug_train_layout;
+int mmvae_aug_param_layout(const mmvae_aug_dims *d, mmvae_aug_train_layout *out);
+size_t mmvae_aug_train_workspace_bytes(const mmvae_aug_dims *d);
+/* x [B,D]; mask: uint8 [B,D] dropout keep-mask (kept entries are scaled by 1 / (1 - p_drop)); z0 [B,NZ], eps [B,Z] standard
+ * normal draws.  Writes s_out [B,Z], x_aug [B,D]; updates running (unbiased variance; momentum 0.01, bnz 0.1) and nbt. */
+int mmvae_aug_train_forward(const mmvae_aug_dims *d, float *params, float *running, int64_t *nbt, const float *x,
+                            const uint8_t *mask, float p_drop, const float *z0, const float *eps, float scale, void *ws,
+                            size_t ws_bytes, float *s_out, float *x_aug, const mmvae_exec *ex, void *stream);
+/* [statistics pass: a forward with stat_mask / stat_z0 / stat_eps when stat_mask != NULL], forward, the gradient of
+ * weight * mean((x_aug - x)^2) with respect to all 29 tensors into grads, Adam (mmvae_adam_step on the flat buffers) when
+ * do_adam.  loss_out: 3 doubles on the device: mse, the count of elements with (x_aug > 1e-3) != (x > 1e-4), and
+ * (mse + 100 count / (B D)) / 2.  No atomics: bit-identical from run to run. */
+int mmvae_aug_train_step(const mmvae_aug_dims *d, float *params, float *running, int64_t *nbt, const float *x,
+                         const uint8_t *mask, float p_drop, const float *z0, const float *eps, const uint8_t *stat_mask,
+                         const float *stat_z0, const float *stat_eps, float scale, float weight, void *ws, size_t ws_bytes,
+                         float *grads, float *s_out, float *x_aug, double *loss_out, int do_adam, float *exp_avg,
+                         float *exp_avg_sq, int64_t step, float lr, float beta1, float beta2, float adam_eps,
+                         float weight_decay, const mmvae_exec *ex, void *stream);
+
 /* ---- device-resident data path ------------------------------------
  * out[i, :] = data[idx[i], :], i < n: the batch assembly of the reference's DataLoader
  * (mmidas/utils/dataloader.py:114-132: shuffled index batches collated from a host TensorDataset, pinned, copied to
