@@ -275,6 +275,20 @@ __global__ __launch_bounds__(RF_THREADS) void k_rf_fit(const uint8_t* __restrict
     if (tid == 0) count[blockIdx.x] = n_nodes;
 }
 
+// The node tables of a chunk's trees to the caller's arrays, one workgroup a tree: the count and the count's nodes.  The rows
+// of the workspace table past the count were never written by k_rf_fit and stay where they are: entries past the count are
+// not written (include/mmvae.h).
+__global__ __launch_bounds__(RF_THREADS) void k_rf_copy_trees(const int4* __restrict__ nodes_all, const int* __restrict__ count, int cap,
+                                                              int* __restrict__ out_count, int* __restrict__ out_nodes) {
+    const int g = blockIdx.x;
+    const int c = count[g];
+    if (threadIdx.x == 0) out_count[g] = c;
+    const int m = rf_clampi(c, 0, cap);
+    const int* src = reinterpret_cast<const int*>(nodes_all + (int64_t)g * cap);
+    int* dst = out_nodes + (int64_t)g * cap * 4;       // (int by int: the caller's array need not be 16-byte aligned)
+    for (int j = threadIdx.x; j < 4 * m; j += RF_THREADS) dst[j] = src[j];
+}
+
 // One wave a held-out row, one tree a lane: the trees g0 .. g0 + gc - 1 of the workspace that belong to the row's fold vote,
 // the votes add to votes [n][K] (first: they start at zero) and, with last, the arg-max (the lowest code on ties), its count
 // and the largest count among the other classes are written.  fold values are clamped to [0, F - 1], a walk takes at most
@@ -383,11 +397,9 @@ int launch_forest(const uint8_t* bins, int64_t ld, int64_t n, int d, const int* 
                            (uint32_t)seed, (uint32_t)(seed >> 32), g0, train, nf, nodes, stack, lists, count);
         HIP_LAUNCH_CHECK("k_rf_fit");
         if (tree_count) {
-            hipError_t e = hipMemcpyAsync(tree_count + g0, count, sizeof(int) * (size_t)gc, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(tree_nodes + (int64_t)g0 * 2 * n * 4, nodes, sizeof(int4) * (size_t)gc * 2 * (size_t)n,
-                                   hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) { set_error("forest: copying the node tables: %s", hipGetErrorString(e)); return MMVAE_E_LAUNCH; }
+            hipLaunchKernelGGL(k_rf_copy_trees, dim3((unsigned)gc), dim3(RF_THREADS), 0, st, nodes, count, (int)(2 * n), tree_count + g0,
+                               tree_nodes + (int64_t)g0 * 2 * n * 4);
+            HIP_LAUNCH_CHECK("k_rf_copy_trees");
         }
         hipLaunchKernelGGL(k_rf_predict, dim3((unsigned)cdiv64(n, RF_THREADS / 64)), dim3(RF_THREADS), 0, st, bins, ld, (int)n, d,
                            fold, F, K, T, g0, gc, nodes, count, g0 == 0 ? 1 : 0, g0 + gc == G ? 1 : 0, v, label, best, second);
