@@ -1261,6 +1261,45 @@ class cpl_mixVAE:
         return {"corr": r.cpu().numpy(), "n": cnt.cpu().numpy(), "categories": cats}
 
     @torch.no_grad()
+    def category_markers(self, dl, arm: int = 0, n_top: int = 20, eps: float = 0.0):
+        """Which genes mark category k: the Wilcoxon rank-sum test of every gene, the cells of each category of arm ``arm``
+        against all the others (``utils.marker_analysis.rank_sum_test``; scipy's ``mannwhitneyu`` without continuity
+        correction, scanpy's tie-corrected ``wilcoxon`` score).  ``dl`` is encoded through the device encode path as for
+        ``state_gene_corr``, the arm's eval labels are the groups, and ``mmvae_rank_sum`` reads the expression where it lies:
+        a ``DeviceLoader``'s resident matrix through the batches' row indices, or, for a plain loader, the concatenation of
+        its batches on the device.  Returns the ``rank_sum_test`` dict (all ``n_categories`` groups; a category with no cell
+        has n = 0, z = 0 and p = 1) plus ``"categories"`` (the 0-based categories, int64 [G]) and ``"markers"``
+        (``marker_genes(result, n_top)``: per category the ``n_top`` genes by z).  ``eps``: a cell expresses a gene where
+        x > eps.  At most 32768 cells; the loader must serve every row once (no ``drop_last``)."""
+        if D.is_dist():
+            raise NotImplementedError("category_markers is not data-parallel: run it on one rank, outside the process group")
+        if self.ref_prior:
+            raise NotImplementedError("ref_prior is rejected by the reference loss (nn_model.py:578)")
+        if not 0 <= int(arm) < self.n_arm:
+            raise ValueError(f"arm = {arm} outside [0, {self.n_arm})")
+        from .utils import marker_analysis as MA
+        from .utils.dataloader import DeviceLoader
+        resident = isinstance(dl, DeviceLoader)
+        drops = bool(getattr(dl, "drop_last", False)) and dl.batch_size and len(dl.dataset) % dl.batch_size
+        if (resident and dl.world_size > 1) or drops:
+            raise ValueError("category_markers needs a loader that serves every row once (no drop_last, no sharding)")
+        if len(dl.dataset) > MA.MAX_CELLS:
+            raise NotImplementedError(f"category_markers: {len(dl.dataset)} cells above the cap of {MA.MAX_CELLS} cells of one "
+                                      "rank-sum call (run it on a subset of the cells)")
+        if not resident:
+            dl = _Replay(dl, self.device)                                 # one walk of the loader: the same batches twice
+        out, inds = self._encode_all(dl)
+        if resident:
+            data, rows = dl.data, inds.to(torch.int64)                     # the batches' indices are rows of the matrix
+        else:
+            data, rows = dl.matrix(), None
+        cats = np.arange(self.n_categories, dtype=np.int64)
+        res = MA.rank_sum_test(data, out["labels"][int(arm)].to(torch.int64), groups=cats, rows=rows, eps=eps)
+        res["categories"] = cats
+        res["markers"] = MA.marker_genes(res, n_top=n_top)
+        return res
+
+    @torch.no_grad()
     def classify_latents(self, dl, labels, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", kind: str = "qda"):
         """How well a Gaussian classifier recovers ``labels`` from arm ``arm``'s latents under k-fold cross-validation: the
         reference's ``QDA_classifier`` / ``LDA_classifier`` (mmidas/utils/cluster_analysis.py:38-83; ``kind`` "qda" or

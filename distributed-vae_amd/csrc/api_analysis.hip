@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the Gaussian classifiers, the leaf merge, ZINB scoring and the ZINB heads' gradients, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the rank sums of the marker genes, the Gaussian classifiers, the leaf merge, ZINB scoring and the ZINB heads' gradients, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -254,6 +254,34 @@ int mmvae_debug_state_corr(const float* data, int64_t ld, int64_t n_total, int D
                            int64_t lds, int64_t n, int S, const int64_t* offsets, int G, void* ws, size_t ws_bytes, double* r,
                            int64_t* count, int path, void* stream) {
     return state_corr_checked(data, ld, n_total, D, rows, state, lds, n, S, offsets, G, ws, ws_bytes, r, count, path, stream);
+}
+
+// ---- rank sums of every gene (ranksum.hip) ----
+size_t mmvae_rank_sum_workspace_bytes(int64_t n, int D, int G) {
+    if (n < 1 || n > RS_MAX_N || D < 1 || G < 1 || G > RS_MAX_G) return 0;
+    return ((size_t)(D < RS_CHUNK ? D : RS_CHUNK) * (size_t)n * sizeof(float) + 7) / 8 * 8;
+}
+
+int mmvae_rank_sum(const float* x, int64_t ldx, int64_t n_total, int D, const int64_t* rows, int64_t n, const int64_t* offsets, int G,
+                   float eps, void* ws, size_t ws_bytes, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum,
+                   void* stream) {
+    const char* who = "rank_sum";
+    if (!x || !offsets || !ws || !rank_sum2 || !tie_term || !n_pos || !sum) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
+    if (n > RS_MAX_N) {
+        set_error("%s: n = %lld cells above the %d whose keys one workgroup's LDS holds", who, (long long)n, RS_MAX_N);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
+    if (G > RS_MAX_G) { set_error("%s: G = %d above %d", who, G, RS_MAX_G); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (eps != eps) { set_error("%s: eps is a NaN", who); return MMVAE_E_BADARG; }
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (int rc = check_ws(who, ws_bytes, mmvae_rank_sum_workspace_bytes(n, D, G))) return rc;
+    return launch_rank_sum(x, ldx, n_total, D, rows, (int)n, offsets, G, eps, ws, rank_sum2, tie_term, n_pos, sum,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- Gaussian classifiers (gaussclf.hip) ----

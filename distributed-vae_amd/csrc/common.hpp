@@ -1032,6 +1032,22 @@ constexpr int SC_MAX_S = 32;           // the model's limit on state_dim; more p
 constexpr int64_t SC_MAX_BLOCKS = ((int64_t)1 << 31) - 1;              // segments x gene tiles, and groups x gene tiles, one grid each
 int launch_state_corr(const float* data, int64_t ld, int64_t n_total, int D, const int64_t* rows, const float* state, int64_t lds,
                       int64_t n, int S, const int64_t* offsets, int G, void* ws, double* r, int64_t* count, bool wide, hipStream_t st);
+// rank sums of every gene, each group against the rest (ranksum.hip)
+constexpr int RS_MAX_N = MMVAE_RANKSUM_MAX_N;   // cells of one call: their 4-byte keys, padded to a power of two, are 128 KiB of LDS
+constexpr int RS_MAX_G = 4096;         // groups of one call: their offsets lie in LDS beside the keys (16 KiB)
+constexpr int RS_THREADS = 1024;       // threads of k_rs_rank at most (half the padded keys where those are fewer)
+constexpr int RS_BIG = 1024;           // a group of more cells is reduced by the whole workgroup, a smaller one by one wave
+constexpr int RS_CHUNK = 512;          // genes staged gene-major at a time: two workgroups for each of the 256 CUs
+// the order-preserving key of a float: a < b exactly where key(a) < key(b); -0.0 and +0.0 share a key; -inf lowest, +inf highest
+__host__ __device__ inline uint32_t rs_key(float v) {
+    uint32_t b = __builtin_bit_cast(uint32_t, v);
+    if ((b << 1) == 0) b = 0;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+int rs_pow2(int64_t n);                // the padded number of keys: the power of two from 128 up that holds n
+inline size_t rs_lds_bytes(int64_t n, int G) { return 4 * ((size_t)rs_pow2(n) + (size_t)G + 1); }
+int launch_rank_sum(const float* x, int64_t ld, int64_t n_total, int D, const int64_t* rows, int n, const int64_t* offsets, int G,
+                    float eps, void* ws, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum, hipStream_t st);
 // Gaussian classifiers: group moments and class scores (gaussclf.hip)
 constexpr int GC_SEG_ROWS = 256;       // rows per segment at most: a longer group is cut into pieces of this many
 constexpr int GC_ROW_CHUNK = 32;       // rows of a segment staged in LDS at a time by k_gc_partial

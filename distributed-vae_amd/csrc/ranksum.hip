@@ -1,0 +1,190 @@
+// Wilcoxon rank sums of every gene, each group of cells against the rest.
+//
+// For every gene the n selected cells' values are ranked among themselves (ties: the average rank) and the ranks of each
+// group's cells are added.  Twice a mid-rank is the integer lo + hi + 1 (lo values below, hi values not above), so the rank
+// sums, the tie term and the counts are integers and exact; only the groups' value sums are floating point, added in a fixed
+// order.  Two kernels per chunk of RS_CHUNK genes:
+//   k_rs_stage  transposes the chunk through LDS into a gene-major staging copy [genes of the chunk][n] (the row map is
+//               applied here, once), so that a gene's column is contiguous for the two passes that follow;
+//   k_rs_rank   one workgroup a gene: the n values become order-preserving 32-bit keys (rs_key), padded to a power of two P
+//               with keys above every value, and are sorted in LDS (bitonic network).  Every cell then searches its own key in
+//               the sorted array for lo and hi.  A group of at most RS_BIG cells is reduced by one wave, a larger one by the
+//               whole workgroup (wave partials added in wave order): lanes in a fixed butterfly, so the sums are the same
+//               bits on every run.  A cell tied with t - 1 others adds t^2 - 1 to the tie term: a run of t equal values
+//               adds t (t^2 - 1) = t^3 - t.
+// No floating-point atomics, no communication between workgroups; integer LDS atomics collect the tie term and the list of
+// large groups.  NaN is not checked for: a NaN's key is ordered somewhere and the gene's results are then unspecified (never an
+// access outside the buffers: every search stays inside [0, n]).  Offsets that do not ascend from 0 to n are the caller's
+// contract (include/mmvae.h): the tie term adds up the cells that lie in some group, and more than RS_MAX_N / RS_BIG groups
+// above RS_BIG cells, which ascending offsets cannot hold, leave the groups past that number unwritten.
+#include "common.hpp"
+
+namespace mmvae {
+
+// grid ceil(n / 64) x ceil(gc / 64), 256 threads: a tile of 64 cells x 64 genes, read along the rows (64 consecutive genes of
+// a row: 256 contiguous bytes), written along the cells.  stage [gc][n].
+__global__ __launch_bounds__(256) void k_rs_stage(const float* __restrict__ x, int64_t ld, int64_t n_total,
+                                                  const int64_t* __restrict__ rows, int n, int g0, int gc,
+                                                  float* __restrict__ stage) {
+    __shared__ float tile[64][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int c0 = blockIdx.x * 64, q0 = blockIdx.y * 64;
+    for (int r = ty; r < 64; r += 4) {
+        float v = 0.f;
+        if (c0 + r < n && q0 + tx < gc) v = x[src_row(rows, c0 + r, n_total) * ld + g0 + q0 + tx];
+        tile[r][tx] = v;
+    }
+    __syncthreads();
+    for (int q = ty; q < 64; q += 4)
+        if (q0 + q < gc && c0 + tx < n) stage[(int64_t)(q0 + q) * n + c0 + tx] = tile[tx][q];
+}
+
+struct RsAcc { long long r2, tie; int np; double s; };
+
+__device__ inline void rs_wave_sum(RsAcc& a) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        a.r2 += __shfl_xor(a.r2, m);
+        a.np += __shfl_xor(a.np, m);
+        a.s += __shfl_xor(a.s, m);
+    }
+}
+
+// the cells c0 + first, c0 + first + step, ... below c1 of one gene: twice the mid-rank, x > eps, the value and the tie count
+__device__ inline void rs_cells(const float* __restrict__ col, const uint32_t* keys, int n, int c0, int c1, int first, int step,
+                                uint32_t eps_key, RsAcc& a) {
+    for (int i = c0 + first; i < c1; i += step) {
+        const float v = col[i];
+        const uint32_t k = rs_key(v);
+        int lo = 0, len = n;
+        while (len > 0) {
+            const int half = len >> 1;
+            if (keys[lo + half] < k) { lo += half + 1; len -= half + 1; } else len = half;
+        }
+        int hi = lo;
+        len = n - lo;
+        while (len > 0) {
+            const int half = len >> 1;
+            if (keys[hi + half] <= k) { hi += half + 1; len -= half + 1; } else len = half;
+        }
+        const long long t = hi - lo;
+        a.r2 += lo + hi + 1;
+        a.tie += t * t - 1;
+        a.np += k > eps_key ? 1 : 0;
+        a.s += (double)v;
+    }
+}
+
+// grid gc workgroups of T = min(RS_THREADS, P / 2) threads; dynamic LDS: keys uint32 [P], then the group offsets int32 [G + 1]
+// (each clamped to [0, n]; a range that runs backwards is empty).  col = stage + blockIdx.x * n; the outputs of gene g0 + blockIdx.x.
+__global__ __launch_bounds__(RS_THREADS) void k_rs_rank(const float* __restrict__ stage, int n, int P,
+                                                        const int64_t* __restrict__ offsets, int G, uint32_t eps_key, int g0, int D,
+                                                        int64_t* __restrict__ rank_sum2, int64_t* __restrict__ tie_term,
+                                                        int64_t* __restrict__ n_pos, double* __restrict__ sum) {
+    extern __shared__ uint32_t rs_lds[];
+    uint32_t* keys = rs_lds;
+    int* off = reinterpret_cast<int*>(rs_lds + P);
+    __shared__ long long w_r2[RS_THREADS / 64];
+    __shared__ double w_s[RS_THREADS / 64];
+    __shared__ int w_np[RS_THREADS / 64];
+    __shared__ unsigned long long tie_all;
+    __shared__ int big[RS_MAX_N / RS_BIG], n_big;
+    const int T = blockDim.x, t = threadIdx.x, lane = t & 63, w = t >> 6, W = T >> 6;
+    const int gene = g0 + blockIdx.x;
+    const float* col = stage + (int64_t)blockIdx.x * n;
+    if (t == 0) { tie_all = 0; n_big = 0; }
+    for (int i = t; i < P; i += T) keys[i] = i < n ? rs_key(col[i]) : 0xFFFFFFFFu;
+    for (int g = t; g <= G; g += T) off[g] = (int)clamp64(offsets[g], 0, n);
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int idx = t; idx < (P >> 1); idx += T) {
+                const int i = ((idx & ~(j - 1)) << 1) | (idx & (j - 1)), l = i | j;
+                const uint32_t a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[l] = a; }
+            }
+            __syncthreads();
+        }
+    // the groups above RS_BIG cells, in any order: each is reduced on its own
+    for (int g = t; g < G; g += T)
+        if (off[g + 1] - off[g] > RS_BIG) {                               // at most n / RS_BIG of them where the offsets ascend
+            const int slot = atomicAdd(&n_big, 1);
+            if (slot < RS_MAX_N / RS_BIG) big[slot] = g;
+        }
+    __syncthreads();
+    long long tie = 0;
+    for (int g = w; g < G; g += W) {                                      // wave w: the groups w, w + W, ...
+        const int c0 = off[g], c1 = off[g + 1];
+        if (c1 - c0 > RS_BIG) continue;
+        RsAcc a{0, 0, 0, 0.0};
+        rs_cells(col, keys, n, c0, c1, lane, 64, eps_key, a);
+        tie += a.tie;
+        rs_wave_sum(a);
+        if (lane == 0) {
+            const int64_t o = (int64_t)g * D + gene;
+            rank_sum2[o] = a.r2;
+            n_pos[o] = a.np;
+            sum[o] = a.s;
+        }
+    }
+    const int nb = n_big < RS_MAX_N / RS_BIG ? n_big : RS_MAX_N / RS_BIG;
+    for (int b = 0; b < nb; ++b) {                                        // (nb is the same in every thread)
+        const int g = big[b];
+        RsAcc a{0, 0, 0, 0.0};
+        rs_cells(col, keys, n, off[g], off[g + 1], t, T, eps_key, a);
+        tie += a.tie;
+        rs_wave_sum(a);
+        if (lane == 0) { w_r2[w] = a.r2; w_np[w] = a.np; w_s[w] = a.s; }
+        __syncthreads();
+        if (t == 0) {
+            long long r2 = 0;
+            int np = 0;
+            double s = 0.0;
+            for (int v = 0; v < W; ++v) { r2 += w_r2[v]; np += w_np[v]; s += w_s[v]; }
+            const int64_t o = (int64_t)g * D + gene;
+            rank_sum2[o] = r2;
+            n_pos[o] = np;
+            sum[o] = s;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) tie += __shfl_xor(tie, m);
+    if (lane == 0) atomicAdd(&tie_all, (unsigned long long)tie);
+    __syncthreads();
+    if (t == 0) tie_term[gene] = (int64_t)tie_all;
+}
+
+int rs_pow2(int64_t n) {
+    int P = 128;
+    while (P < n) P <<= 1;
+    return P;
+}
+
+// ws: the staging copy float [min(D, RS_CHUNK)][n] (mmvae_rank_sum_workspace_bytes)
+int launch_rank_sum(const float* x, int64_t ld, int64_t n_total, int D, const int64_t* rows, int n, const int64_t* offsets, int G,
+                    float eps, void* ws, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum, hipStream_t st) {
+    const int P = rs_pow2(n), T = P / 2 < RS_THREADS ? P / 2 : RS_THREADS;
+    const size_t shm = rs_lds_bytes(n, G);
+    if (shm > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_rank), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        if (e != hipSuccess) {
+            set_error("rank_sum: %zu bytes of dynamic LDS refused: %s", shm, hipGetErrorString(e));
+            return MMVAE_E_LAUNCH;
+        }
+    }
+    float* stage = static_cast<float*>(ws);
+    const uint32_t eps_key = rs_key(eps);
+    for (int64_t g0 = 0; g0 < D; g0 += RS_CHUNK) {
+        const int gc = D - g0 < RS_CHUNK ? (int)(D - g0) : RS_CHUNK;
+        hipLaunchKernelGGL(k_rs_stage, dim3((unsigned)cdiv(n, 64), (unsigned)cdiv(gc, 64)), dim3(256), 0, st, x, ld, n_total, rows, n,
+                           (int)g0, gc, stage);
+        HIP_LAUNCH_CHECK("k_rs_stage");
+        hipLaunchKernelGGL(k_rs_rank, dim3((unsigned)gc), dim3((unsigned)T), shm, st, stage, n, P, offsets, G, eps_key, (int)g0, D,
+                           rank_sum2, tie_term, n_pos, sum);
+        HIP_LAUNCH_CHECK("k_rs_rank");
+    }
+    return 0;
+}
+
+}  // namespace mmvae

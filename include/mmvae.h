@@ -461,6 +461,46 @@ int mmvae_debug_state_corr(const float *data, int64_t ld, int64_t n_total, int D
                            const float *state, int64_t lds, int64_t n, int S, const int64_t *offsets, int G, void *ws,
                            size_t ws_bytes, double *r, int64_t *count, int path, void *stream);
 
+/* ---- marker genes: the Wilcoxon rank-sum (Mann-Whitney) test of every gene, each group of cells against the rest
+ * ---- (scipy.stats.mannwhitneyu, scanpy's rank_genes_groups(method="wilcoxon", tie_correct=True)) ----
+ * For gene d the n selected cells' values are ranked among themselves, ties sharing the average rank.  With lo the number of
+ * values < v and hi the number <= v, twice the mid-rank of a cell with value v is the integer lo + hi + 1, so
+ *   rank_sum2[g, d] = sum over the cells of group g of (lo + hi + 1)          (twice the group's rank sum)
+ *   tie_term[d]     = sum over the runs of equal values of t^3 - t            (t the length of a run)
+ *   n_pos[g, d]     = the number of the group's cells with x > eps
+ * are integers and EXACT; -0.0 and +0.0 are one value, -inf and +inf rank below and above every finite value.
+ *   sum[g, d]       = the sum of the group's values in fp64, the terms exact, added in a fixed order
+ * From these the caller forms U = rank_sum2 / 2 - n_g (n_g + 1) / 2 and the tie-corrected z (utils/marker_analysis.py).
+ *
+ * mmvae_rank_sum: x float32 row-major [n_total, ldx], columns 0..D-1 used, read where it lies; rows int64 [n] on the device,
+ *   the row of x of cell r, or NULL for the rows 0..n-1 (then n <= n_total); offsets int64 [G + 1] on the device, group g the
+ *   cells offsets[g] .. offsets[g + 1] - 1 (the cells ORDERED BY GROUP; an empty group is allowed and gives zeros).
+ *   rank_sum2, n_pos int64 [G, D], tie_term int64 [D], sum double [G, D], on the device; every element is written
+ *   (for offsets that keep the contract below).
+ *   Offsets that are not non-decreasing from offsets[0] = 0 to offsets[G] = n and row indices outside [0, n_total) are the
+ *   CALLER'S CONTRACT, as for mmvae_state_corr: every index derived from them is clamped, so they give wrong values and no
+ *   access outside the arrays.  Under broken offsets the values are not only wrong: tie_term adds up the cells that lie in
+ *   some group, so it is the gene's tie term only where the groups cover the cells 0..n-1 once; and where more than
+ *   n / 1024 = 32 groups claim more than 1024 cells each (non-decreasing offsets cannot), the groups past the 32nd -- which
+ *   ones is not determined -- get NO rank_sum2, n_pos and sum written and their cells are missing from tie_term.  NaN IS NOT CHECKED FOR: a gene that holds a NaN gets unspecified results (the other genes are
+ *   not affected).  eps must not be a NaN.
+ *   One workgroup owns one gene: its values become order-preserving 32-bit keys, are sorted in LDS, and every cell finds lo
+ *   and hi by binary search.  The keys, padded to a power of two, are the LDS budget: 128 KiB of the 160 KiB a workgroup may
+ *   declare hold MMVAE_RANKSUM_MAX_N = 32768 of them, and the G + 1 <= 4097 offsets lie beside them.  No floating-point
+ *   atomics and no communication between workgroups: bit-identical from run to run, and a gene's results do not depend on
+ *   which other genes the call holds.
+ *   ws: mmvae_rank_sum_workspace_bytes(n, D, G) bytes of device memory, 8-byte aligned: the gene-major staging copy of a
+ *   chunk of genes, min(D, 512) n floats (rounded up to whole 8 bytes); 0 for arguments that mmvae_rank_sum refuses.
+ *   MMVAE_E_BADARG, before any device work, for a null x / offsets / ws / rank_sum2 / tie_term / n_pos / sum, n < 1,
+ *   n_total < 1, rows NULL with n > n_total, D < 1, G < 1, ldx < D, a NaN eps, a misaligned ws; MMVAE_E_UNSUPPORTED for
+ *   n > MMVAE_RANKSUM_MAX_N or G > 4096; MMVAE_E_WORKSPACE for a ws below the size. */
+#define MMVAE_RANKSUM_KEY_LDS_BYTES (128 * 1024)                 /* of the 160 KiB of LDS one workgroup may declare */
+#define MMVAE_RANKSUM_MAX_N (MMVAE_RANKSUM_KEY_LDS_BYTES / 4)    /* 32768 four-byte keys */
+size_t mmvae_rank_sum_workspace_bytes(int64_t n, int D, int G);
+int mmvae_rank_sum(const float *x, int64_t ldx, int64_t n_total, int D, const int64_t *rows /* NULL = 0..n-1 */, int64_t n,
+                   const int64_t *offsets, int G, float eps, void *ws, size_t ws_bytes, int64_t *rank_sum2,
+                   int64_t *tie_term, int64_t *n_pos, double *sum, void *stream);
+
 /* ---- Gaussian classifiers (mmidas/utils/cluster_analysis.py: QDA_classifier, LDA_classifier) ----
  * A Gaussian classifier under k-fold cross-validation scores a held-out cell x under class k of the model m fitted to the
  * other folds as
