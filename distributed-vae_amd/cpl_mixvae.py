@@ -1261,7 +1261,7 @@ class cpl_mixVAE:
         return {"corr": r.cpu().numpy(), "n": cnt.cpu().numpy(), "categories": cats}
 
     @torch.no_grad()
-    def category_markers(self, dl, arm: int = 0, n_top: int = 20, eps: float = 0.0):
+    def category_markers(self, dl, arm: int = 0, n_top: int = 20, eps: float = 0.0, block_cells=None):
         """Which genes mark category k: the Wilcoxon rank-sum test of every gene, the cells of each category of arm ``arm``
         against all the others (``utils.marker_analysis.rank_sum_test``; scipy's ``mannwhitneyu`` without continuity
         correction, scanpy's tie-corrected ``wilcoxon`` score).  ``dl`` is encoded through the device encode path as for
@@ -1270,7 +1270,8 @@ class cpl_mixVAE:
         its batches on the device.  Returns the ``rank_sum_test`` dict (all ``n_categories`` groups; a category with no cell
         has n = 0, z = 0 and p = 1) plus ``"categories"`` (the 0-based categories, int64 [G]) and ``"markers"``
         (``marker_genes(result, n_top)``: per category the ``n_top`` genes by z).  ``eps``: a cell expresses a gene where
-        x > eps.  At most 32768 cells; the loader must serve every row once (no ``drop_last``)."""
+        x > eps.  At most 32768 cells; with ``block_cells`` = "auto" or a block size (``rank_sum_test``'s keyword: the blocked
+        rank sums, the same integers) at most 1048576.  The loader must serve every row once (no ``drop_last``)."""
         if D.is_dist():
             raise NotImplementedError("category_markers is not data-parallel: run it on one rank, outside the process group")
         if self.ref_prior:
@@ -1283,9 +1284,10 @@ class cpl_mixVAE:
         drops = bool(getattr(dl, "drop_last", False)) and dl.batch_size and len(dl.dataset) % dl.batch_size
         if (resident and dl.world_size > 1) or drops:
             raise ValueError("category_markers needs a loader that serves every row once (no drop_last, no sharding)")
-        if len(dl.dataset) > MA.MAX_CELLS:
+        if block_cells is None and len(dl.dataset) > MA.MAX_CELLS:
             raise NotImplementedError(f"category_markers: {len(dl.dataset)} cells above the cap of {MA.MAX_CELLS} cells of one "
-                                      "rank-sum call (run it on a subset of the cells)")
+                                      "rank-sum call (run it on a subset of the cells, or pass block_cells=\"auto\")")
+        MA._block_of(block_cells, len(dl.dataset), "category_markers")     # (a bad block and the blocked cap, before the encode)
         if not resident:
             dl = _Replay(dl, self.device)                                 # one walk of the loader: the same batches twice
         out, inds = self._encode_all(dl)
@@ -1294,7 +1296,8 @@ class cpl_mixVAE:
         else:
             data, rows = dl.matrix(), None
         cats = np.arange(self.n_categories, dtype=np.int64)
-        res = MA.rank_sum_test(data, out["labels"][int(arm)].to(torch.int64), groups=cats, rows=rows, eps=eps)
+        res = MA.rank_sum_test(data, out["labels"][int(arm)].to(torch.int64), groups=cats, rows=rows, eps=eps,
+                               block_cells=block_cells)
         res["categories"] = cats
         res["markers"] = MA.marker_genes(res, n_top=n_top)
         return res

@@ -284,6 +284,62 @@ int mmvae_rank_sum(const float* x, int64_t ldx, int64_t n_total, int D, const in
                            reinterpret_cast<hipStream_t>(stream));
 }
 
+// block: 0 the default RS_MAX_N, else a power of two in [RSB_MIN_BLOCK, RS_MAX_N]; 0 for anything else
+static int rsb_block(int block) {
+    if (block == 0) return RS_MAX_N;
+    return block >= RSB_MIN_BLOCK && block <= RS_MAX_N && (block & (block - 1)) == 0 ? block : 0;
+}
+
+size_t mmvae_rank_sum_blocked_workspace_bytes(int64_t n, int D, int G, int block) {
+    if (n < 1 || n > RSB_MAX_N || D < 1 || G < 1 || G > RS_MAX_G || !rsb_block(block)) return 0;
+    return ((size_t)rsb_chunk(n, D) * rsb_gene_bytes(n) + 7) / 8 * 8;
+}
+
+static int rank_sum_blocked_checked(const float* x, int64_t ldx, int64_t n_total, int D, const int64_t* rows, int64_t n,
+                                    const int64_t* offsets, int G, float eps, int block, void* ws, size_t ws_bytes, int64_t* rank_sum2,
+                                    int64_t* tie_term, int64_t* n_pos, double* sum, int form, int phases, void* stream) {
+    const char* who = "rank_sum_blocked";
+    if (!x || !offsets || !ws || !rank_sum2 || !tie_term || !n_pos || !sum) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
+    if (n > RSB_MAX_N) {
+        set_error("%s: n = %lld cells above the %d whose tie term an int64 holds", who, (long long)n, RSB_MAX_N);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
+    if (G > RS_MAX_G) { set_error("%s: G = %d above %d", who, G, RS_MAX_G); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (eps != eps) { set_error("%s: eps is a NaN", who); return MMVAE_E_BADARG; }
+    const int L = rsb_block(block);
+    if (!L) {
+        set_error("%s: block = %d is neither 0 nor a power of two in [%d, %d]", who, block, RSB_MIN_BLOCK, RS_MAX_N);
+        return MMVAE_E_BADARG;
+    }
+    if (form < RSB_FORM_AUTO || form > RSB_FORM_IN_PLACE || phases < 0 || phases > 3) {
+        set_error("%s: form = %d outside [-1, 1] or phases = %d outside [0, 3]", who, form, phases);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (int rc = check_ws(who, ws_bytes, mmvae_rank_sum_blocked_workspace_bytes(n, D, G, block))) return rc;
+    return launch_rank_sum_blocked(x, ldx, n_total, D, rows, (int)n, offsets, G, eps, L, ws, rank_sum2, tie_term, n_pos, sum, form, phases,
+                                   reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_rank_sum_blocked(const float* x, int64_t ldx, int64_t n_total, int D, const int64_t* rows, int64_t n, const int64_t* offsets,
+                           int G, float eps, int block, void* ws, size_t ws_bytes, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos,
+                           double* sum, void* stream) {
+    return rank_sum_blocked_checked(x, ldx, n_total, D, rows, n, offsets, G, eps, block, ws, ws_bytes, rank_sum2, tie_term, n_pos, sum,
+                                    RSB_FORM_AUTO, 0, stream);
+}
+
+int mmvae_debug_rank_sum_blocked(const float* x, int64_t ldx, int64_t n_total, int D, const int64_t* rows, int64_t n,
+                                 const int64_t* offsets, int G, float eps, int block, void* ws, size_t ws_bytes, int64_t* rank_sum2,
+                                 int64_t* tie_term, int64_t* n_pos, double* sum, int form, int phases, void* stream) {
+    return rank_sum_blocked_checked(x, ldx, n_total, D, rows, n, offsets, G, eps, block, ws, ws_bytes, rank_sum2, tie_term, n_pos, sum,
+                                    form, phases, stream);
+}
+
 // ---- Gaussian classifiers (gaussclf.hip) ----
 size_t mmvae_group_moments_workspace_bytes(int64_t n, int d, int G) {
     if (n < 1 || n > N_MAX || d < 1 || d > GC_MAX_D || G < 1 || G > GC_MAX_G) return 0;

@@ -1048,6 +1048,26 @@ int rs_pow2(int64_t n);                // the padded number of keys: the power o
 inline size_t rs_lds_bytes(int64_t n, int G) { return 4 * ((size_t)rs_pow2(n) + (size_t)G + 1); }
 int launch_rank_sum(const float* x, int64_t ld, int64_t n_total, int D, const int64_t* rows, int n, const int64_t* offsets, int G,
                     float eps, void* ws, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum, hipStream_t st);
+// The blocked path.  Its cap of 2^20 cells is what the outputs' formats hold, not a buffer's size: a gene with every value tied
+// has the tie term n^3 - n < 2^60, which an int64 holds; lo + hi + 1 <= 2 n + 1 < 2^22 fits the uint32 kept per cell; and a
+// group's sum of them stays below 2^42, so that U minus its mean is exact in fp64 on the host, as z_and_p assumes.
+constexpr int RSB_MAX_N = MMVAE_RANKSUM_BLOCKED_MAX_N;
+constexpr int RSB_MIN_BLOCK = 128;     // the smallest block of cells: the smallest number of padded keys of the sort
+constexpr int RSB_THREADS = 1024;      // threads of k_rsb_rank
+constexpr int RSB_CELLS = 4;           // cells a thread of k_rsb_rank carries: key, lo and hi in registers
+constexpr int RSB_TILE = RSB_THREADS * RSB_CELLS;   // cells per workgroup of k_rsb_rank; one partial of the tie term each
+constexpr size_t RSB_WS_BYTES = (size_t)4 << 30;    // the workspace at most: the gene chunk shrinks with n to stay below it
+enum { RSB_FORM_AUTO = -1, RSB_FORM_STAGED = 0, RSB_FORM_IN_PLACE = 1 };
+// a gene's share of the workspace: the staged values, the sorted keys and lo + hi + 1 (4 bytes a cell each), the tile partials
+inline size_t rsb_gene_bytes(int64_t n) { return 12 * (size_t)n + 8 * (size_t)((n + RSB_TILE - 1) / RSB_TILE); }
+inline int rsb_chunk(int64_t n, int D) {
+    size_t c = RSB_WS_BYTES / rsb_gene_bytes(n);                        // (at least 341: n <= RSB_MAX_N)
+    if (c > (size_t)RS_CHUNK) c = RS_CHUNK;
+    return (size_t)D < c ? D : (int)c;
+}
+int launch_rank_sum_blocked(const float* x, int64_t ld, int64_t n_total, int D, const int64_t* rows, int n, const int64_t* offsets,
+                            int G, float eps, int L, void* ws, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum,
+                            int form, int phases, hipStream_t st);
 // Gaussian classifiers: group moments and class scores (gaussclf.hip)
 constexpr int GC_SEG_ROWS = 256;       // rows per segment at most: a longer group is cut into pieces of this many
 constexpr int GC_ROW_CHUNK = 32;       // rows of a segment staged in LDS at a time by k_gc_partial

@@ -7,8 +7,10 @@ rest, on the device, without scipy.
 the rank sums, the tie term and the counts as exact integers; the statistic, its p-value and the Benjamini-Hochberg
 adjustment are then formed in numpy float64 on the host from those integers.  At most ``MAX_CELLS`` = 32768 cells a call and
 ``MAX_GROUPS`` = 4096 groups; NaN is refused in host input and not checked for in a device tensor (a gene that holds one gets
-unspecified results).  Not offered: more cells per call, data-parallel use, other tests, the continuity correction, and
-group-against-group tests."""
+unspecified results).  With ``block_cells`` (``"auto"`` or a block size) ``mmvae_rank_sum_blocked`` takes
+up to ``MAX_CELLS_BLOCKED`` = 1048576 cells: the cells are cut into blocks that are sorted one by one, and a cell's rank is
+added up over the blocks -- the same integers.  Not offered: more cells than that, a default that changes paths by itself,
+data-parallel use, other tests, the continuity correction, and group-against-group tests."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +23,8 @@ from .. import _native as N
 from .. import dist as D
 
 MAX_CELLS = 32768      # MMVAE_RANKSUM_MAX_N (include/mmvae.h): the keys of one gene fill 128 KiB of a workgroup's LDS
+MAX_CELLS_BLOCKED = 1 << 20   # MMVAE_RANKSUM_BLOCKED_MAX_N: n^3 - n, the tie term of an all-tied gene, stays below 2^60
+MIN_BLOCK = 128        # RSB_MIN_BLOCK: the smallest block of the blocked path; the largest is MAX_CELLS
 MAX_GROUPS = 4096      # RS_MAX_G (csrc/common.hpp)
 CHUNK = 512            # RS_CHUNK: genes of the gene-major staging copy, which is the workspace
 
@@ -28,15 +32,42 @@ _bound = [False]
 
 
 def _lib():
-    """The library with the two entries' signatures declared (here, as augmentation.py declares its own)."""
+    """The library with the rank-sum entries' signatures declared (here, as augmentation.py declares its own)."""
     L = N.lib()
     if not _bound[0]:
         vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
         L.mmvae_rank_sum_workspace_bytes.argtypes = [i64, i32, i32]
         L.mmvae_rank_sum_workspace_bytes.restype = C.c_size_t
         L.mmvae_rank_sum.argtypes = [vp, i64, i64, i32, vp, i64, vp, i32, C.c_float, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        L.mmvae_rank_sum_blocked_workspace_bytes.argtypes = [i64, i32, i32, i32]
+        L.mmvae_rank_sum_blocked_workspace_bytes.restype = C.c_size_t
+        L.mmvae_rank_sum_blocked.argtypes = [vp, i64, i64, i32, vp, i64, vp, i32, C.c_float, i32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        L.mmvae_debug_rank_sum_blocked.argtypes = [vp, i64, i64, i32, vp, i64, vp, i32, C.c_float, i32, vp, C.c_size_t, vp, vp, vp, vp,
+                                                   i32, i32, vp]
         _bound[0] = True
     return L
+
+
+def _block_of(block_cells, n: int, who: str):
+    """None for the one-call path, else the ``block`` argument of mmvae_rank_sum_blocked (0: its default); the refusals of
+    ``block_cells`` and of ``n`` cells, which come before any device work."""
+    if block_cells is None or (isinstance(block_cells, str) and block_cells == "auto" and n <= MAX_CELLS):
+        if n > MAX_CELLS:
+            why = " (the keys of one gene must fit one workgroup's LDS)" if who == "rank_sum_test" else ""
+            raise NotImplementedError(f"{who}: {n} cells above the {MAX_CELLS} of one call{why}; block_cells=\"auto\" takes up to "
+                                      f"{MAX_CELLS_BLOCKED}")
+        return None
+    if isinstance(block_cells, str) and block_cells == "auto":
+        block = 0
+    else:
+        if isinstance(block_cells, (str, bool)) or not isinstance(block_cells, (int, np.integer)):
+            raise ValueError(f"{who}: block_cells = {block_cells!r} is not None, \"auto\" or an int")
+        block = int(block_cells)
+        if not (MIN_BLOCK <= block <= MAX_CELLS and block & (block - 1) == 0):
+            raise ValueError(f"{who}: block_cells = {block} is not a power of two in [{MIN_BLOCK}, {MAX_CELLS}]")
+    if n > MAX_CELLS_BLOCKED:
+        raise NotImplementedError(f"{who}: {n} cells above the {MAX_CELLS_BLOCKED} of the blocked path")
+    return block
 
 
 def _buffer(shape, dtype, device) -> torch.Tensor:
@@ -45,11 +76,14 @@ def _buffer(shape, dtype, device) -> torch.Tensor:
     return N._workspace(8 * numel, device)[:numel].view(dtype).view(*shape)
 
 
-def rank_sums(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.Tensor, eps: float = 0.0):
+def rank_sums(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.Tensor, eps: float = 0.0, block_cells=None):
     """mmvae_rank_sum on device tensors: float32 ``x`` [n_total, D] (rows may be strided, columns not; read where it lies),
     the int64 row map ``rows`` [n] ordered by group (None: the rows 0..n-1, n = offsets[-1]) and int64 ``offsets`` [G + 1] ->
     (rank_sum2 int64 [G, D], tie_term int64 [D], n_pos int64 [G, D], sum float64 [G, D]) on the device.  ``offsets`` is read
-    on the host only for its last entry when ``rows`` is None."""
+    on the host only for its last entry when ``rows`` is None.  ``block_cells``: None the one-call path (at most 32768 cells);
+    "auto" that path up to 32768 cells and mmvae_rank_sum_blocked with its default block above, up to 1048576 cells; an int
+    (a power of two in [128, 32768]) mmvae_rank_sum_blocked with blocks of that many cells, at any n up to 1048576 -- the
+    same integers, and up to 32768 cells the same bits."""
     N._need_cuda("rank_sum", x, rows, offsets)
     if x.dtype != torch.float32 or x.dim() != 2:
         raise TypeError("rank_sum: x must be float32 [n_total, D]")
@@ -66,14 +100,20 @@ def rank_sums(x: torch.Tensor, rows: Optional[torch.Tensor], offsets: torch.Tens
         n = int(offsets[-1])
     offsets = offsets.contiguous()
     G = int(offsets.numel()) - 1
-    if n > MAX_CELLS:
-        raise NotImplementedError(f"rank_sum: {n} cells above the {MAX_CELLS} of one call")
+    block = _block_of(block_cells, n, "rank_sum")
     L = _lib()
     dev = xm.device
     rank_sum2 = _buffer((G, Dm), torch.int64, dev)
     n_pos = _buffer((G, Dm), torch.int64, dev)
     tie_term = _buffer((Dm,), torch.int64, dev)
     total = _buffer((G, Dm), torch.float64, dev)
+    if block is not None:
+        ws_bytes = int(L.mmvae_rank_sum_blocked_workspace_bytes(n, Dm, G, block))
+        ws = N._workspace(ws_bytes, dev)
+        N.check(L.mmvae_rank_sum_blocked(N._ptr(xm), int(xm.stride(0)), n_total, Dm, N._ptr(rows), n, N._ptr(offsets), G, float(eps),
+                                         block, N._ptr(ws), ws_bytes, N._ptr(rank_sum2), N._ptr(tie_term), N._ptr(n_pos),
+                                         N._ptr(total), N._stream(dev)), "mmvae_rank_sum_blocked")
+        return rank_sum2, tie_term, n_pos, total
     ws_bytes = int(L.mmvae_rank_sum_workspace_bytes(n, Dm, G))
     ws = N._workspace(ws_bytes, dev)
     N.check(L.mmvae_rank_sum(N._ptr(xm), int(xm.stride(0)), n_total, Dm, N._ptr(rows), n, N._ptr(offsets), G, float(eps), N._ptr(ws),
@@ -133,7 +173,7 @@ def _float32_device(x, device) -> torch.Tensor:
     return torch.from_numpy(h if h.flags.writeable else h.copy()).to(get_device(device))
 
 
-def rank_sum_test(x, labels, groups=None, rows=None, eps: float = 0.0, device=None) -> dict:
+def rank_sum_test(x, labels, groups=None, rows=None, eps: float = 0.0, device=None, block_cells=None) -> dict:
     """The rank-sum test of every gene (column of ``x``), each group of cells against all the others.
 
     ``x`` [n_total, D]: a float32 tensor on the GPU is used where it lies, with its row stride (a ``DeviceLoader``'s resident
@@ -141,7 +181,8 @@ def rank_sum_test(x, labels, groups=None, rows=None, eps: float = 0.0, device=No
     codes or any hashable labels.  ``groups``: the labels to test, in this order (default: ``np.unique(labels)``); cells with
     another label belong to every group's rest, and a label that no cell carries is an empty group.  ``rows``: int indices
     [n] into ``x``: ``labels[r]`` belongs to ``x[rows[r]]``; without it n must equal n_total.  ``eps``: a cell expresses a gene
-    where x > eps.  At most 32768 cells and 4096 groups.
+    where x > eps.  At most 32768 cells and 4096 groups; with ``block_cells`` = "auto" (the blocked path above 32768 cells) or
+    a block size (a power of two in [128, 32768]: the blocked path at any n) at most 1048576 cells, the same integers.
 
     The cells are sorted by group on the host (stable), ``mmvae_rank_sum`` returns the exact integers, and the rest is numpy
     float64: with N the number of cells, n_g the group's size and T the tie term,
@@ -160,9 +201,7 @@ def rank_sum_test(x, labels, groups=None, rows=None, eps: float = 0.0, device=No
     n_total = int(x.shape[0])
     if n < 1:
         raise ValueError("rank_sum_test needs at least one cell")
-    if n > MAX_CELLS:
-        raise NotImplementedError(f"rank_sum_test: {n} cells above the {MAX_CELLS} of one call (the keys of one gene must fit "
-                                  "one workgroup's LDS)")
+    _block_of(block_cells, n, "rank_sum_test")
     if not np.isfinite(float(eps)):
         raise ValueError(f"eps = {eps} is not finite")
     rows_h = None
@@ -197,7 +236,8 @@ def rank_sum_test(x, labels, groups=None, rows=None, eps: float = 0.0, device=No
     rows_sorted = order.astype(np.int64) if rows_h is None else rows_h[order]
     xd = _float32_device(x, device)
     dev = xd.device
-    r2_d, tie_d, pos_d, sum_d = rank_sums(xd, torch.from_numpy(rows_sorted).to(dev), torch.from_numpy(offsets).to(dev), eps)
+    r2_d, tie_d, pos_d, sum_d = rank_sums(xd, torch.from_numpy(rows_sorted).to(dev), torch.from_numpy(offsets).to(dev), eps,
+                                         block_cells)
     r2, tie, pos, tot = (t.cpu().numpy() for t in (r2_d, tie_d, pos_d, sum_d))
     U, z, p = z_and_p(r2[:G], tie, sizes[:G], n)
     n1 = sizes[:G].astype(np.float64)[:, None]

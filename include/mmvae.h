@@ -501,6 +501,45 @@ int mmvae_rank_sum(const float *x, int64_t ldx, int64_t n_total, int D, const in
                    const int64_t *offsets, int G, float eps, void *ws, size_t ws_bytes, int64_t *rank_sum2,
                    int64_t *tie_term, int64_t *n_pos, double *sum, void *stream);
 
+/* ---- rank sums past 32768 cells: sorted blocks, cross-block ranks ----
+ * mmvae_rank_sum_blocked: the arguments, the four outputs and their meaning are mmvae_rank_sum's; n may reach
+ *   MMVAE_RANKSUM_BLOCKED_MAX_N = 2^20 = 1048576.  The n cells of a gene, in the call's order, are cut into ceil(n / L) blocks
+ *   of L cells (the last one shorter, down to one cell), and every block's keys are sorted on their own.  For a cell with key k
+ *     lo = the sum over the blocks b of #{keys of block b < k},   hi = the sum over the blocks b of #{keys of block b <= k}
+ *   are the lo and hi of the whole column, so twice the mid-rank is again lo + hi + 1 and the cell adds t^2 - 1, t = hi - lo,
+ *   to the tie term: every integer is mmvae_rank_sum's, whatever L is.  The groups' cells are then added in mmvae_rank_sum's
+ *   order (a group of at most 1024 cells by one wave, a larger one by the workgroup of min(1024, P / 2) threads, P the power
+ *   of two from 128 up that holds n), so for n <= MMVAE_RANKSUM_MAX_N all four outputs, the fp64 sum included, are
+ *   bit-identical to mmvae_rank_sum's.  No floating-point atomics: bit-identical from run to run, and a gene's results do not
+ *   depend on the other genes of the call.
+ *   block: L; 0 = the default, MMVAE_RANKSUM_MAX_N; otherwise a power of two in [128, MMVAE_RANKSUM_MAX_N].
+ *   The cap is what the number formats hold: a gene with every value tied has tie_term = n^3 - n < 2^60, an int64;
+ *   lo + hi + 1 <= 2 n + 1 < 2^22 fits the uint32 kept per cell; a group's rank_sum2 stays below 2^42, so that U minus its mean
+ *   is exact in fp64 on the host.
+ *   Offsets that are not non-decreasing from 0 to n and row indices outside [0, n_total) are the CALLER'S CONTRACT as above:
+ *   every index derived from them is clamped, so they give wrong values (tie_term is here that of all n cells) and no access
+ *   outside the arrays; every output element is written.  NaN IS NOT CHECKED FOR: a gene that holds a NaN gets unspecified
+ *   results, and every search stays inside its block.
+ *   ws: mmvae_rank_sum_blocked_workspace_bytes(n, D, G, block) bytes of device memory, 8-byte aligned:
+ *     gc (12 n + 8 ceil(n / 4096)) bytes rounded up to whole 8,   gc = min(D, 512, floor(2^32 / (12 n + 8 ceil(n / 4096))))
+ *   -- for gc genes at a time the staged values, the sorted keys and lo + hi + 1 of every cell (4 bytes each) and one int64
+ *   partial of the tie term per 4096 cells; at most 4 GiB at any allowed shape (gc = 341 at n = 2^20); 0 for arguments that
+ *   mmvae_rank_sum_blocked refuses.
+ *   The refusals are mmvae_rank_sum's, in its order, with MMVAE_E_UNSUPPORTED for n > MMVAE_RANKSUM_BLOCKED_MAX_N, and
+ *   MMVAE_E_BADARG for a block that is neither 0 nor a power of two in [128, 32768].
+ * mmvae_debug_rank_sum_blocked (tools/time_ranksum.py): form -1 the entry's choice, 0 every block's keys copied to LDS and
+ *   searched there, 1 searched where they lie; the same bits.  phases 0 the whole call, 1 .. 3 only the staging copy / and the
+ *   block sort / and the ranks of every chunk: a timing split that LEAVES THE OUTPUTS UNWRITTEN. */
+#define MMVAE_RANKSUM_BLOCKED_MAX_N (1 << 20)
+size_t mmvae_rank_sum_blocked_workspace_bytes(int64_t n, int D, int G, int block);
+int mmvae_rank_sum_blocked(const float *x, int64_t ldx, int64_t n_total, int D, const int64_t *rows /* NULL = 0..n-1 */,
+                           int64_t n, const int64_t *offsets, int G, float eps, int block, void *ws, size_t ws_bytes,
+                           int64_t *rank_sum2, int64_t *tie_term, int64_t *n_pos, double *sum, void *stream);
+int mmvae_debug_rank_sum_blocked(const float *x, int64_t ldx, int64_t n_total, int D, const int64_t *rows, int64_t n,
+                                 const int64_t *offsets, int G, float eps, int block, void *ws, size_t ws_bytes,
+                                 int64_t *rank_sum2, int64_t *tie_term, int64_t *n_pos, double *sum, int form, int phases,
+                                 void *stream);
+
 /* ---- Gaussian classifiers (mmidas/utils/cluster_analysis.py: QDA_classifier, LDA_classifier) ----
  * A Gaussian classifier under k-fold cross-validation scores a held-out cell x under class k of the model m fitted to the
  * other folds as

@@ -9,7 +9,9 @@
          categories are the planted ones (no model), and the run fails unless every planted gene tops its category
 --model  a checkpoint, or a glob pattern of which the one with the highest ``_epoch_<n>`` is taken; the categories are arm
          --arm's labels on the cells of --data (a .npz, or a .npy holding a pickled dictionary, the cells [N, D] under
-         --x-key, default ``log1p``); at most 32768 cells
+         --x-key, default ``log1p``); at most 32768 cells, with --block-cells 1048576
+--block-cells  ``auto`` (the blocked rank sums above 32768 cells) or a block size, a power of two in [128, 32768] (the
+         blocked rank sums at any size); without it the one-call path and its cap
 --out    where to ``np.savez`` the result: every array of the ``rank_sum_test`` dictionary, and ``top_genes`` [G, top]
 """
 import argparse
@@ -65,13 +67,14 @@ def main():
     ap.add_argument("--eps", type=float, default=0.0)
     ap.add_argument("--top", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--block-cells", default=None, type=lambda v: v if v == "auto" else int(v))
     args = ap.parse_args()
     if args.synthetic:
         n, D, K = args.synthetic
         if not (K >= 2 and D >= K and 3 + (D // K) * (K - 1) < D and n >= 4 * K):
             ap.error("--synthetic needs K >= 2, D >= K, N >= 4 K and room for the last planted gene: 3 + (D // K) (K - 1) < D")
         x, labels, genes = planted(n, D, K)
-        res = MA.rank_sum_test(x, labels, eps=args.eps, device="cuda")
+        res = MA.rank_sum_test(x, labels, eps=args.eps, device="cuda", block_cells=args.block_cells)
         top = report(res, args.top)
         found = top[:, 0]
         print(f"planted genes {genes.tolist()}; top genes {found.tolist()}")
@@ -100,7 +103,7 @@ def main():
         cpl.load_model(model_file)
         dl = DataLoader(TensorDataset(torch.from_numpy(x), torch.arange(len(x), dtype=torch.float32)), batch_size=args.batch_size,
                         shuffle=False)
-        res = cpl.category_markers(dl, arm=args.arm, n_top=args.top, eps=args.eps)
+        res = cpl.category_markers(dl, arm=args.arm, n_top=args.top, eps=args.eps, block_cells=args.block_cells)
         if names is not None:
             res["markers"] = MA.marker_genes(res, n_top=args.top, gene_names=names)
         top = report(res, args.top, names)
