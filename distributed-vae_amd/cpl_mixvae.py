@@ -1321,6 +1321,40 @@ class cpl_mixVAE:
         return self._cv_result(CA.classify_points(points, y, kfold, seed, kind), data_indx)
 
     @torch.no_grad()
+    def latent_neighbors(self, dl, k: int = 15, arm: int = 0, on: str = "x_low"):
+        """The k-nearest-neighbour graph of the cells of ``dl`` in arm ``arm``'s latent space: what UMAP, Leiden and scanpy's
+        ``pp.neighbors`` start from.  ``on`` = "x_low", "state_mu" or "z_prob", ``dl`` and the loaders refused as for
+        ``classify_latents``; the latents never leave the device (``utils.neighbors.knn`` on them: Euclidean, a cell is not
+        its own neighbour, ties by index, the same bits on every run).  Returns ``{"indices": int32 [n, k], "distances":
+        float32 [n, k], "data_indx"}``: the cells in the order the loader serves them, ``indices`` positions in that order
+        (``data_indx[indices]`` the data set's rows; -1 and +inf where n <= k).  ``utils.neighbors.csr_from_neighbors`` makes
+        the CSR graph of them."""
+        if D.is_dist():
+            raise NotImplementedError("latent_neighbors is not data-parallel: run it on one rank, outside the process group")
+        from .utils import neighbors as NB
+        points, _, data_indx = self._latents_to_classify(dl, None, arm, on, "latent_neighbors")
+        idx, dist = NB.knn(points, k)
+        return {"indices": idx.cpu().numpy(), "distances": dist.cpu().numpy(), "data_indx": data_indx}
+
+    @torch.no_grad()
+    def classify_neighbors(self, dl, labels, k: int = 15, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low"):
+        """How well the ``k`` nearest training cells recover ``labels`` from arm ``arm``'s latents under k-fold
+        cross-validation: ``utils.neighbors.KNN_classifier``, the member of the ``classify_latents`` family that assumes no
+        cluster shape.  ``dl``, ``labels``, ``arm``, ``on``, the folds and the loaders refused are ``classify_latents``'s; the
+        latents never leave the device.  Returns its dict -- ``"acc"``, ``"ref_labels"``, ``"pred_labels"``, ``"fold"``,
+        ``"data_indx"`` and ``"margin"`` float64 [n], here (the prediction's votes minus the most votes of another label) /
+        k -- and ``"purity"`` float64 [n] (the share of a cell's k training neighbours with its own label) and
+        ``"kth_distance"`` float32 [n], in the loader's order."""
+        if D.is_dist():
+            raise NotImplementedError("classify_neighbors is not data-parallel: run it on one rank, outside the process group")
+        from .utils import neighbors as NB
+        points, y, data_indx = self._latents_to_classify(dl, labels, arm, on, "classify_neighbors")
+        classified = NB.classify_points(points, y, kfold, seed, k)
+        res = self._cv_result(classified, data_indx, per=float(int(k)))
+        res["purity"], res["kth_distance"] = classified[3]["purity"], classified[3]["kth_distance"]
+        return res
+
+    @torch.no_grad()
     def classify_tree(self, dl, labels, list_changes, leaves, kfold: int = 10, seed=0, arm: int = 0, on: str = "x_low", levels=None):
         """How well the cell types are recovered from arm ``arm``'s latents at EVERY resolution of the taxonomy: the
         reference's ``predict_leaf_gmm`` (mmidas/utils/analysis_tree_helpers.py) under k-fold cross-validation and at all
@@ -1357,7 +1391,8 @@ class cpl_mixVAE:
             raise ValueError(f"{who} needs a loader that serves every row once (no drop_last, no sharding)")
         out, inds = self._encode_all(dl if resident else _Replay(dl, self.device))
         data_indx = inds.cpu().numpy()
-        return out[names[on]][int(arm)], np.asarray(labels)[data_indx.astype(np.int64)], data_indx
+        y = None if labels is None else np.asarray(labels)[data_indx.astype(np.int64)]     # (latent_neighbors has no labels)
+        return out[names[on]][int(arm)], y, data_indx
 
     def _expression_to_classify(self, dl, labels, who):
         """What ``classify_pcs`` and ``classify_forest(on="pcs")`` share: the loaders they refuse and the expression of the cells

@@ -1,5 +1,5 @@
 // C ABI (include/mmvae.h) of the evaluation and analysis routines: labels and consensus, mutual information, silhouette,
-// state-gene correlation, the rank sums of the marker genes, the Gaussian classifiers, the leaf merge, ZINB scoring and the ZINB heads' gradients, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
+// state-gene correlation, the rank sums of the marker genes, k nearest neighbours, the Gaussian classifiers, the leaf merge, ZINB scoring and the ZINB heads' gradients, the count distributions, the random forest, PCA and data preparation.  Every argument is checked here, on the host,
 // before any device work; the training step's entry points, the plan and set_error live in api.hip.
 #include "common.hpp"
 
@@ -338,6 +338,78 @@ int mmvae_debug_rank_sum_blocked(const float* x, int64_t ldx, int64_t n_total, i
                                  int64_t* tie_term, int64_t* n_pos, double* sum, int form, int phases, void* stream) {
     return rank_sum_blocked_checked(x, ldx, n_total, D, rows, n, offsets, G, eps, block, ws, ws_bytes, rank_sum2, tie_term, n_pos, sum,
                                     form, phases, stream);
+}
+
+// ---- k nearest neighbours (knn.hip) ----
+size_t mmvae_knn_workspace_bytes(int64_t nq, int64_t nr, int d, int k) {
+    if (nq < 1 || nq > KNN_MAX_N || nr < 1 || nr > KNN_MAX_N || d < 1 || d > KNN_MAX_D || k < 1 || k > KNN_MAX_K) return 0;
+    return knn_ws_bytes(nq, nr, k, knn_seg_cols(nq, nr, k));
+}
+
+static int knn_checked(const float* q, int64_t ldq, int64_t nq, const float* r, int64_t ldr, int64_t nr, int d, int k,
+                       const int32_t* qgroup, const int32_t* rgroup, void* ws, size_t ws_bytes, int32_t* idx, float* dist2,
+                       int64_t seg_cols, int phases, void* stream) {
+    const char* who = "knn";
+    if (!q || !r || !ws || !idx || !dist2) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if ((qgroup == nullptr) != (rgroup == nullptr)) {
+        set_error("%s: qgroup and rgroup come together or not at all", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = check_count(who, "k", k, 1, INT32_MAX)) return rc;
+    if (k > KNN_MAX_K) { set_error("%s: k = %d above %d", who, k, KNN_MAX_K); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_count(who, "d", d, 1, INT32_MAX)) return rc;
+    if (d > KNN_MAX_D) { set_error("%s: d = %d above %d", who, d, KNN_MAX_D); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_count(who, "nq", nq, 1, INT64_MAX)) return rc;
+    if (int rc = check_count(who, "nr", nr, 1, INT64_MAX)) return rc;
+    if (nq > KNN_MAX_N || nr > KNN_MAX_N) {
+        set_error("%s: nq = %lld, nr = %lld above %d", who, (long long)nq, (long long)nr, KNN_MAX_N);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_pitch(who, "ldq", ldq, "d", d)) return rc;
+    if (int rc = check_pitch(who, "ldr", ldr, "d", d)) return rc;
+    if (seg_cols < 0 || phases < KNN_PHASE_ALL || phases > KNN_PHASE_MERGE) {
+        set_error("%s: seg_cols = %lld below 0 or phases = %d outside [0, 2]", who, (long long)seg_cols, phases);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (seg_cols == 0) seg_cols = knn_seg_cols(nq, nr, k);
+    const size_t need = knn_ws_bytes(nq, nr, k, seg_cols);
+    if (need == 0 || need > KNN_WS_BYTES) {
+        set_error("%s: segments of %lld columns need a workspace above %zu bytes", who, (long long)seg_cols, KNN_WS_BYTES);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    if (int rc = check_ws(who, ws_bytes, need)) return rc;
+    return launch_knn(q, ldq, nq, r, ldr, nr, d, k, qgroup, rgroup, seg_cols, ws, idx, dist2, phases,
+                      reinterpret_cast<hipStream_t>(stream));
+}
+
+int mmvae_knn(const float* q, int64_t ldq, int64_t nq, const float* r, int64_t ldr, int64_t nr, int d, int k, const int32_t* qgroup,
+              const int32_t* rgroup, void* ws, size_t ws_bytes, int32_t* idx, float* dist2, void* stream) {
+    return knn_checked(q, ldq, nq, r, ldr, nr, d, k, qgroup, rgroup, ws, ws_bytes, idx, dist2, 0, KNN_PHASE_ALL, stream);
+}
+
+int mmvae_debug_knn(const float* q, int64_t ldq, int64_t nq, const float* r, int64_t ldr, int64_t nr, int d, int k,
+                    const int32_t* qgroup, const int32_t* rgroup, void* ws, size_t ws_bytes, int32_t* idx, float* dist2,
+                    int64_t seg_cols, int phases, void* stream) {
+    return knn_checked(q, ldq, nq, r, ldr, nr, d, k, qgroup, rgroup, ws, ws_bytes, idx, dist2, seg_cols, phases, stream);
+}
+
+int mmvae_knn_votes(const int32_t* idx, int64_t nq, int k, const int32_t* rlabel, int64_t nr, int n_classes, const int32_t* qlabel,
+                    int32_t* pred, double* purity, int32_t* top2, void* stream) {
+    const char* who = "knn_votes";
+    if (!idx || !rlabel || !pred) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (purity && !qlabel) { set_error("%s: purity needs qlabel", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "k", k, 1, INT32_MAX)) return rc;
+    if (k > KNN_MAX_K) { set_error("%s: k = %d above %d", who, k, KNN_MAX_K); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_count(who, "n_classes", n_classes, 1, INT32_MAX)) return rc;
+    if (n_classes > KNN_MAX_CLASSES) { set_error("%s: n_classes = %d above %d", who, n_classes, KNN_MAX_CLASSES); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_count(who, "nq", nq, 1, INT64_MAX)) return rc;
+    if (int rc = check_count(who, "nr", nr, 1, INT64_MAX)) return rc;
+    if (nq > KNN_MAX_N || nr > KNN_MAX_N) {
+        set_error("%s: nq = %lld, nr = %lld above %d", who, (long long)nq, (long long)nr, KNN_MAX_N);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return launch_knn_votes(idx, nq, k, rlabel, nr, n_classes, qlabel, pred, purity, top2, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- Gaussian classifiers (gaussclf.hip) ----

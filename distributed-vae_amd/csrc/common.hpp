@@ -1068,6 +1068,39 @@ inline int rsb_chunk(int64_t n, int D) {
 int launch_rank_sum_blocked(const float* x, int64_t ld, int64_t n_total, int D, const int64_t* rows, int n, const int64_t* offsets,
                             int G, float eps, int L, void* ws, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum,
                             int form, int phases, hipStream_t st);
+// k nearest neighbours, their votes and purity (knn.hip)
+constexpr int KNN_MAX_K = MMVAE_KNN_MAX_K;
+constexpr int KNN_MAX_D = SIL_MAX_D;   // k_knn_partial is built for the float4 pieces of SIL_DV
+constexpr int KNN_MAX_N = MMVAE_KNN_MAX_N;      // queries, and references: an index and a list's slot stay far inside 32 bits
+constexpr int KNN_MAX_CLASSES = 4096;
+constexpr int KNN_LDS_FLOATS = 2048;   // floats of staged reference columns per pass (8 KiB: with the lists of k = 15, nine workgroups a CU)
+constexpr int KNN_TILE = 64;           // queries per workgroup of k_knn_partial and k_knn_merge: one wave, one thread a query
+constexpr int KNN_VOTE_TILE = 64;      // queries per workgroup of k_knn_votes, one thread each
+constexpr int KNN_MIN_SEG = 256;       // reference columns per segment at least, where the entry chooses
+constexpr int KNN_TARGET_WGS = 1024;   // workgroups of k_knn_partial aimed at: four one-wave workgroups for each of the 256 CUs
+constexpr size_t KNN_WS_BYTES = (size_t)2 << 30;    // the workspace at most
+enum { KNN_PHASE_ALL = 0, KNN_PHASE_PARTIAL = 1, KNN_PHASE_MERGE = 2 };
+// the segment length the entry chooses: as FEW segments as fill the chip -- every segment starts its lists empty, and while a
+// list fills nearly every candidate enters it -- so KNN_TARGET_WGS workgroups over the query tiles
+// (the count does not depend on k, so that the workspace grows with k), no more than the workspace's cap allows, none
+// shorter than KNN_MIN_SEG
+inline int64_t knn_seg_cols(int64_t nq, int64_t nr, int k) {
+    int64_t nseg = KNN_TARGET_WGS / cdiv64(nq, KNN_TILE);
+    const int64_t cap = (int64_t)(KNN_WS_BYTES / (8 * (size_t)nq * (size_t)k));     // (at least 4: nq <= 2^20, k <= 64)
+    nseg = nseg > cap ? cap : nseg;
+    nseg = nseg < 1 ? 1 : nseg;
+    const int64_t len = cdiv64(nr, nseg);
+    return len < KNN_MIN_SEG ? KNN_MIN_SEG : len;
+}
+// part uint64 [nseg][k][nq] for nseg = ceil(nr / seg_cols) > 1 segments; 8 bytes (unused) for one
+inline size_t knn_ws_bytes(int64_t nq, int64_t nr, int k, int64_t seg_cols) {
+    const int64_t nseg = cdiv64(nr, seg_cols);
+    return nseg <= 1 ? 8 : bytes_or_0((unsigned __int128)8 * (unsigned __int128)nseg * (unsigned __int128)nq * (unsigned __int128)k);
+}
+int launch_knn(const float* q, int64_t ldq, int64_t nq, const float* r, int64_t ldr, int64_t nr, int d, int k, const int* qgroup,
+               const int* rgroup, int64_t seg_cols, void* ws, int* idx, float* dist2, int phases, hipStream_t st);
+int launch_knn_votes(const int* idx, int64_t nq, int k, const int* rlabel, int64_t nr, int n_classes, const int* qlabel, int* pred,
+                     double* purity, int* top2, hipStream_t st);
 // Gaussian classifiers: group moments and class scores (gaussclf.hip)
 constexpr int GC_SEG_ROWS = 256;       // rows per segment at most: a longer group is cut into pieces of this many
 constexpr int GC_ROW_CHUNK = 32;       // rows of a segment staged in LDS at a time by k_gc_partial

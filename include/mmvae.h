@@ -540,6 +540,51 @@ int mmvae_debug_rank_sum_blocked(const float *x, int64_t ldx, int64_t n_total, i
                                  int64_t *rank_sum2, int64_t *tie_term, int64_t *n_pos, double *sum, int form, int phases,
                                  void *stream);
 
+/* ---- k nearest neighbours, their votes and purity ----
+ * For every query point q_i the k admitted reference points with the smallest squared Euclidean distance.
+ *   q float32 row-major [nq, ldq] and r float32 row-major [nr, ldr], columns 0..d-1 used, both read where they lie;
+ *   qgroup int32 [nq] and rgroup int32 [nr] on the device, both or neither: reference j is ADMITTED for query i iff no
+ *   groups are given or rgroup[j] != qgroup[i] (no groups: a plain query; both = 0..n-1 on one set: the k-NN graph
+ *   without the point itself; both = the fold of each cell: a test cell sees training cells only).
+ *   The squared distance is fp32 in difference form: t = q_ic - r_jc rounded, acc = fma(t, t, acc) for c = 0 .. d-1 from
+ *   +0.  Candidates are ordered by (the 32 bits of that float, then j), ascending -- a total order -- and
+ *   idx int32 [nq, k], dist2 float32 [nq, k] hold the k smallest admitted candidates of every query in that order; where
+ *   fewer than k are admitted the tail is idx = -1, dist2 = +inf.  Every element is written.  The result is a pure function
+ *   of the inputs: bit-identical from run to run, independent of how the work is cut (seg_cols below) and, row by row, of the
+ *   other queries of the call.  No atomics.  NaN IS NOT CHECKED FOR: a query or reference that holds one gets unspecified
+ *   neighbours (indices stay inside [-1, nr)).
+ *   ws: mmvae_knn_workspace_bytes(nq, nr, d, k) bytes of device memory, 8-byte aligned: the reference columns are cut into
+ *   segments so that the chip is filled, and every (segment, query) keeps a sorted list of k 8-byte keys there, which a
+ *   second launch merges; at most 2 GiB, 8 bytes where one segment is enough, 0 for arguments that mmvae_knn refuses.
+ *   MMVAE_E_BADARG, before any device work, for a null q / r / ws / idx / dist2, one group array without the other, k, d,
+ *   nq or nr below 1, ldq or ldr below d, a misaligned ws; MMVAE_E_UNSUPPORTED for k > 64, d > 128, nq or nr > 2^20;
+ *   MMVAE_E_WORKSPACE for a ws below the size.
+ * mmvae_debug_knn (tests, tools/time_knn.py): the same call with segments of seg_cols reference columns (0: the entry's own
+ *   choice); ws then holds 8 ceil(nr / seg_cols) nq k bytes where that is more than one segment, and MMVAE_E_UNSUPPORTED
+ *   where those exceed 2 GiB.  phases 0 the whole call, 1 the segment launch alone, 2 the merge alone (on the lists that an
+ *   earlier call left in ws): a timing split; with more than one segment phase 1 LEAVES THE OUTPUTS UNWRITTEN.  The same bits
+ *   for every seg_cols.
+ * mmvae_knn_votes: idx int32 [nq, k] as above (entries outside [0, nr) are no neighbours), rlabel int32 [nr] with the
+ *   reference points' labels in [0, n_classes) (a neighbour with another label is no neighbour) ->
+ *   pred int32 [nq]: the label most of the row's valid neighbours carry, the SMALLEST such label on ties, -1 without a valid one;
+ *   purity double [nq] (optional, needs qlabel int32 [nq]): valid neighbours with rlabel == qlabel[i] / valid neighbours,
+ *   one fp64 division of two small integers, NaN without a valid neighbour;
+ *   top2 int32 [nq, 2] (optional): the votes of pred and the most votes of any other label.
+ *   Integer work only; deterministic.  MMVAE_E_BADARG for a null idx / rlabel / pred, purity without qlabel, nq, nr, k or
+ *   n_classes below 1; MMVAE_E_UNSUPPORTED for k > 64, n_classes > 4096, nq or nr > 2^20. */
+#define MMVAE_KNN_MAX_K 64
+#define MMVAE_KNN_MAX_N (1 << 20)
+size_t mmvae_knn_workspace_bytes(int64_t nq, int64_t nr, int d, int k);
+int mmvae_knn(const float *q, int64_t ldq, int64_t nq, const float *r, int64_t ldr, int64_t nr, int d, int k,
+              const int32_t *qgroup /* NULL with rgroup */, const int32_t *rgroup, void *ws, size_t ws_bytes, int32_t *idx,
+              float *dist2, void *stream);
+int mmvae_debug_knn(const float *q, int64_t ldq, int64_t nq, const float *r, int64_t ldr, int64_t nr, int d, int k,
+                    const int32_t *qgroup, const int32_t *rgroup, void *ws, size_t ws_bytes, int32_t *idx, float *dist2,
+                    int64_t seg_cols, int phases, void *stream);
+int mmvae_knn_votes(const int32_t *idx, int64_t nq, int k, const int32_t *rlabel, int64_t nr, int n_classes,
+                    const int32_t *qlabel /* or NULL */, int32_t *pred, double *purity /* or NULL */,
+                    int32_t *top2 /* or NULL */, void *stream);
+
 /* ---- Gaussian classifiers (mmidas/utils/cluster_analysis.py: QDA_classifier, LDA_classifier) ----
  * A Gaussian classifier under k-fold cross-validation scores a held-out cell x under class k of the model m fitted to the
  * other folds as
