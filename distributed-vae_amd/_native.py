@@ -262,25 +262,24 @@ def lib():
     L.mmvae_zinb_heads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
     L.mmvae_zinb_nll_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_zinb_nll_workspace_bytes.restype = C.c_size_t
-    L.mmvae_zinb_nll.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, vp, C.c_size_t, vp, vp, vp]
+    zinb_in = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double]     # d10, ldh, N, H, D, three layers, X, ldx, eps
+    zinb_grad_in = zinb_in + [C.c_double, i32, i32, vp, C.c_size_t]                   # scale, head mask, segments, workspace
+    L.mmvae_zinb_nll.argtypes = zinb_in + [vp, C.c_size_t, vp, vp, vp]
     L.mmvae_zinb_terms_workspace_bytes.argtypes = [i64, i32]
     L.mmvae_zinb_terms_workspace_bytes.restype = C.c_size_t
     L.mmvae_zinb_terms.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, vp, C.c_size_t, vp, vp, vp, i64, vp]
     L.mmvae_zinb_head_grads_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_zinb_head_grads_workspace_bytes.restype = C.c_size_t
     L.mmvae_zinb_head_grads_segments.argtypes = [i64, i32, i32]
-    L.mmvae_zinb_head_grads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
-                                        C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mmvae_zinb_head_grads.argtypes = zinb_grad_in + [vp] * 9
     L.mmvae_zinb_terms_grad.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.c_double, C.c_double, vp, vp, vp, i64, vp]
     L.mmvae_zinb_d10_grad_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_zinb_d10_grad_workspace_bytes.restype = C.c_size_t
     L.mmvae_zinb_d10_grad_segments.argtypes = [i64, i32, i32]
-    L.mmvae_zinb_d10_grad.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
-                                      C.c_size_t, vp, i64, vp]
+    L.mmvae_zinb_d10_grad.argtypes = zinb_grad_in + [vp, i64, vp]
     L.mmvae_zinb_step_grads_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.mmvae_zinb_step_grads_workspace_bytes.restype = C.c_size_t
-    L.mmvae_zinb_step_grads.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_double, C.c_double, i32, i32, vp,
-                                        C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.mmvae_zinb_step_grads.argtypes = zinb_grad_in + [vp] * 9 + [i64, vp]
     L.mmvae_decoder_trunk_grads_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     L.mmvae_decoder_trunk_grads_workspace_bytes.restype = C.c_size_t
     L.mmvae_decoder_trunk_grads_segments.argtypes = [i64, i32]
@@ -1130,6 +1129,45 @@ def _zinb_layer(what: str, name: str, W: torch.Tensor, b: torch.Tensor, D: int, 
     return W.contiguous(), b.contiguous()
 
 
+def _zinb_inputs(what: str, d10, W, b, Wp, bp, Wr, br, X, eps, scale=None, heads=None, segments: int = 0):
+    """What the entries on d10 [N, H], the three layers and X [N, D] check and pass alike -> (keep, n, H, D, dev, mask, args).
+    ``args`` are the leading ctypes arguments: mmvae_zinb_nll's 14, through eps, with ``heads=None``; else the gradient
+    entries' 17, through ``scale`` (None: 1 / (N D)), the head mask and ``segments``.  ``keep`` holds the tensors the
+    pointers belong to: the caller keeps it until the call has been made."""
+    mask = zinb_head_mask(heads) if heads is not None else None
+    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
+    d10 = _zinb_mat(what, "d10", d10)
+    n, H = (int(v) for v in d10.shape)
+    D = int(W.shape[0])
+    X = _zinb_mat(what, "X", X, D)
+    if X.shape[0] != n:
+        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
+    if segments < 0:
+        raise ValueError(f"{what}: segments = {segments} below 0")
+    layers = [t for nm, Wj, bj in (("fc11", W, b), ("fc11_p", Wp, bp), ("fc11_r", Wr, br)) for t in _zinb_layer(what, nm, Wj, bj, D, H)]
+    args = [_ptr(d10), _zinb_pitch(d10), n, H, D, *(_ptr(t) for t in layers), _ptr(X), _zinb_pitch(X), float(eps)]
+    if heads is not None:
+        args += [1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments)]
+    return (d10, X, layers), n, H, D, d10.device, mask, args
+
+
+def _zinb_given_heads(what: str, x_rec, x_p, x_r, X, eps):
+    """What mmvae_zinb_terms and mmvae_zinb_terms_grad check and pass alike: four float32 [N, D] matrices
+    -> (keep, n, D, dev, args), ``args`` the leading ctypes arguments through eps."""
+    _need_cuda(what, x_rec, x_p, x_r, X)
+    X = _zinb_mat(what, "X", X)
+    n, D = (int(v) for v in X.shape)
+    x_rec, x_p, x_r = (_zinb_mat(what, nm, t, D) for nm, t in (("rec_x", x_rec), ("x_p", x_p), ("x_r", x_r)))
+    if not (x_rec.shape[0] == x_p.shape[0] == x_r.shape[0] == n):
+        raise ValueError(f"{what}: the four matrices must have the same number of rows")
+    keep = (x_rec, x_p, x_r, X)
+    return keep, n, D, X.device, [v for t in keep for v in (_ptr(t), _zinb_pitch(t))] + [n, D, float(eps)]
+
+
+def _zinb_sums(n: int, D: int, dev):
+    return torch.empty(n, dtype=torch.float64, device=dev), torch.empty(D, dtype=torch.float64, device=dev)
+
+
 def zinb_head_layout(dims: Dims) -> ZinbHeadLayout:
     """mmvae_zinb_head_layout: the offsets of the p and r heads in their flat buffer (host only)."""
     out = ZinbHeadLayout()
@@ -1163,24 +1201,12 @@ def zinb_nll(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: floa
     """mmvae_zinb_nll: the ZINB term of every element of X [N, D] under the three heads of d10 [N, H] (fc11: W, b; fc11_p: Wp,
     bp; fc11_r: Wr, br), summed -> (cell_sum float64 [N], gene_sum float64 [D]) on the device; no head is written."""
     what = "zinb_nll"
-    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
-    d10 = _zinb_mat(what, "d10", d10)
-    n, H = (int(v) for v in d10.shape)
-    D = int(W.shape[0])
-    X = _zinb_mat(what, "X", X, D)
-    if X.shape[0] != n:
-        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
-    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
-                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
-    dev = d10.device
+    keep, n, H, D, dev, _, args = _zinb_inputs(what, d10, W, b, Wp, bp, Wr, br, X, eps)
     with torch.cuda.device(dev):
         nbytes = int(lib().mmvae_zinb_nll_workspace_bytes(n, D))
         ws = _workspace(nbytes, dev)
-        cell = torch.empty(n, dtype=torch.float64, device=dev)
-        gene = torch.empty(D, dtype=torch.float64, device=dev)
-        check(lib().mmvae_zinb_nll(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr), _ptr(br),
-                                   _ptr(X), _zinb_pitch(X), float(eps), _ptr(ws), nbytes, _ptr(cell), _ptr(gene), _stream(dev)),
-              "mmvae_zinb_nll")
+        cell, gene = _zinb_sums(n, D, dev)
+        check(lib().mmvae_zinb_nll(*args, _ptr(ws), nbytes, _ptr(cell), _ptr(gene), _stream(dev)), "mmvae_zinb_nll")
     return cell, gene
 
 
@@ -1189,22 +1215,13 @@ def zinb_terms(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X: tor
     """mmvae_zinb_terms: the ZINB term of every element from given heads (float32 [N, D] on the GPU, rows may be strided)
     -> (cell_sum float64 [N], gene_sum float64 [D], terms float32 [N, D] or None) on the device."""
     what = "zinb_terms"
-    _need_cuda(what, x_rec, x_p, x_r, X)
-    X = _zinb_mat(what, "X", X)
-    n, D = (int(v) for v in X.shape)
-    x_rec, x_p, x_r = (_zinb_mat(what, nm, t, D) for nm, t in (("rec_x", x_rec), ("x_p", x_p), ("x_r", x_r)))
-    if not (x_rec.shape[0] == x_p.shape[0] == x_r.shape[0] == n):
-        raise ValueError(f"{what}: the four matrices must have the same number of rows")
-    dev = X.device
+    keep, n, D, dev, args = _zinb_given_heads(what, x_rec, x_p, x_r, X, eps)
     with torch.cuda.device(dev):
         nbytes = int(lib().mmvae_zinb_terms_workspace_bytes(n, D))
         ws = _workspace(nbytes, dev)
-        cell = torch.empty(n, dtype=torch.float64, device=dev)
-        gene = torch.empty(D, dtype=torch.float64, device=dev)
+        cell, gene = _zinb_sums(n, D, dev)
         terms = torch.empty(n, D, dtype=torch.float32, device=dev) if return_terms else None
-        check(lib().mmvae_zinb_terms(_ptr(x_rec), _zinb_pitch(x_rec), _ptr(x_p), _zinb_pitch(x_p), _ptr(x_r), _zinb_pitch(x_r),
-                                     _ptr(X), _zinb_pitch(X), n, D, float(eps), _ptr(ws), nbytes, _ptr(cell), _ptr(gene),
-                                     _ptr(terms), D, _stream(dev)), "mmvae_zinb_terms")
+        check(lib().mmvae_zinb_terms(*args, _ptr(ws), nbytes, _ptr(cell), _ptr(gene), _ptr(terms), D, _stream(dev)), "mmvae_zinb_terms")
     return cell, gene, terms
 
 
@@ -1222,34 +1239,9 @@ def zinb_head_mask(heads) -> int:
     return sum(1 << ZINB_HEADS.index(h) for h in set(heads))
 
 
-def zinb_head_grads_segments(n: int, D: int, segments: int = 0) -> int:
-    """The number of cell segments mmvae_zinb_head_grads uses for n cells and D genes when ``segments`` are asked for
-    (0: the library's rule)."""
-    return int(lib().mmvae_zinb_head_grads_segments(int(n), int(D), int(segments)))
-
-
-def zinb_head_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: float = 1e-6, scale: Optional[float] = None,
-                    heads=ZINB_HEADS, segments: int = 0, out=None):
-    """mmvae_zinb_head_grads: the gradient of ``scale`` x the sum of the ZINB terms of X [N, D] under the three heads of d10
-    [N, H] with respect to the weights and biases of the heads in ``heads`` ("rec": fc11, "p": fc11_p, "r": fc11_r).
-    ``scale=None`` is 1 / (N D), the mean that ``zinb_loss`` returns.  ``segments``: the number of cell segments, 0 the
-    library's rule.  ``out``: ``{head: (dW float32 [D, H], db float32 [D])}`` to write into (contiguous, on the device;
-    views of one flat buffer will do), by default new tensors.  Returns ``(grads, cell_sum, gene_sum)``: ``grads`` as ``out``
-    with the selected heads only; the float64 sums are mmvae_zinb_nll's bit for bit."""
-    what = "zinb_head_grads"
-    mask = zinb_head_mask(heads)
-    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
-    d10 = _zinb_mat(what, "d10", d10)
-    n, H = (int(v) for v in d10.shape)
-    D = int(W.shape[0])
-    X = _zinb_mat(what, "X", X, D)
-    if X.shape[0] != n:
-        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
-    if segments < 0:
-        raise ValueError(f"{what}: segments = {segments} below 0")
-    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
-                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
-    dev = d10.device
+def _zinb_head_outputs(what: str, mask: int, out, D: int, H: int, dev):
+    """The per-head outputs of a gradient entry -> (grads, ptrs): ``grads`` ``{head: (dW [D, H], db [D])}`` of the selected
+    heads, taken from ``out`` (checked) or new; ``ptrs`` the six tensors or None in the order of the C arguments."""
     grads, ptrs = {}, []
     for j, h in enumerate(ZINB_HEADS):
         if not mask >> j & 1:
@@ -1265,15 +1257,31 @@ def zinb_head_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, ep
             db = torch.empty(D, dtype=torch.float32, device=dev)
         grads[h] = (dW, db)
         ptrs += [dW, db]
+    return grads, ptrs
+
+
+def zinb_head_grads_segments(n: int, D: int, segments: int = 0) -> int:
+    """The number of cell segments mmvae_zinb_head_grads uses for n cells and D genes when ``segments`` are asked for
+    (0: the library's rule)."""
+    return int(lib().mmvae_zinb_head_grads_segments(int(n), int(D), int(segments)))
+
+
+def zinb_head_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps: float = 1e-6, scale: Optional[float] = None,
+                    heads=ZINB_HEADS, segments: int = 0, out=None):
+    """mmvae_zinb_head_grads: the gradient of ``scale`` x the sum of the ZINB terms of X [N, D] under the three heads of d10
+    [N, H] with respect to the weights and biases of the heads in ``heads`` ("rec": fc11, "p": fc11_p, "r": fc11_r).
+    ``scale=None`` is 1 / (N D), the mean that ``zinb_loss`` returns.  ``segments``: the number of cell segments, 0 the
+    library's rule.  ``out``: ``{head: (dW float32 [D, H], db float32 [D])}`` to write into (contiguous, on the device;
+    views of one flat buffer will do), by default new tensors.  Returns ``(grads, cell_sum, gene_sum)``: ``grads`` as ``out``
+    with the selected heads only; the float64 sums are mmvae_zinb_nll's bit for bit."""
+    what = "zinb_head_grads"
+    keep, n, H, D, dev, mask, args = _zinb_inputs(what, d10, W, b, Wp, bp, Wr, br, X, eps, scale, heads, segments)
+    grads, ptrs = _zinb_head_outputs(what, mask, out, D, H, dev)
     with torch.cuda.device(dev):
         nbytes = int(lib().mmvae_zinb_head_grads_workspace_bytes(n, D, H, int(segments)))
         ws = _workspace(nbytes, dev)
-        cell = torch.empty(n, dtype=torch.float64, device=dev)
-        gene = torch.empty(D, dtype=torch.float64, device=dev)
-        check(lib().mmvae_zinb_head_grads(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr),
-                                          _ptr(br), _ptr(X), _zinb_pitch(X), float(eps),
-                                          1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments),
-                                          _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _stream(dev)),
+        cell, gene = _zinb_sums(n, D, dev)
+        check(lib().mmvae_zinb_head_grads(*args, _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _stream(dev)),
               "mmvae_zinb_head_grads")
     return grads, cell, gene
 
@@ -1291,19 +1299,7 @@ def zinb_d10_grad(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps:
     is 1 / (N D); ``segments``: the number of gene segments, 0 the library's rule; ``out``: float32 [N, H] on the device to
     write into (rows may be strided).  Returns gd10 float32 [N, H]."""
     what = "zinb_d10_grad"
-    mask = zinb_head_mask(heads)
-    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
-    d10 = _zinb_mat(what, "d10", d10)
-    n, H = (int(v) for v in d10.shape)
-    D = int(W.shape[0])
-    X = _zinb_mat(what, "X", X, D)
-    if X.shape[0] != n:
-        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
-    if segments < 0:
-        raise ValueError(f"{what}: segments = {segments} below 0")
-    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
-                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
-    dev = d10.device
+    keep, n, H, D, dev, _, args = _zinb_inputs(what, d10, W, b, Wp, bp, Wr, br, X, eps, scale, heads, segments)
     if out is None:
         out = torch.empty(n, H, dtype=torch.float32, device=dev)
     elif (out.dtype != torch.float32 or tuple(out.shape) != (n, H) or out.device != dev or out.stride(1) != 1
@@ -1312,10 +1308,7 @@ def zinb_d10_grad(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, eps:
     with torch.cuda.device(dev):
         nbytes = int(lib().mmvae_zinb_d10_grad_workspace_bytes(n, D, H, int(segments)))
         ws = _workspace(nbytes, dev)
-        check(lib().mmvae_zinb_d10_grad(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr), _ptr(br),
-                                        _ptr(X), _zinb_pitch(X), float(eps),
-                                        1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments),
-                                        _ptr(ws), nbytes, _ptr(out), _zinb_pitch(out), _stream(dev)), "mmvae_zinb_d10_grad")
+        check(lib().mmvae_zinb_d10_grad(*args, _ptr(ws), nbytes, _ptr(out), _zinb_pitch(out), _stream(dev)), "mmvae_zinb_d10_grad")
     return out
 
 
@@ -1327,36 +1320,14 @@ def zinb_step_grads(d10: torch.Tensor, W, b, Wp, bp, Wr, br, X: torch.Tensor, ep
     """mmvae_zinb_step_grads: ``zinb_head_grads`` (at ``segments`` cell segments) and ``zinb_d10_grad`` (at a segment a gene
     tile) from one evaluation of g.  Returns ``(grads, cell_sum, gene_sum, gd10)``, each bit for bit what the two give."""
     what = "zinb_step_grads"
-    mask = zinb_head_mask(heads)
-    _need_cuda(what, d10, W, b, Wp, bp, Wr, br, X)
-    d10 = _zinb_mat(what, "d10", d10)
-    n, H = (int(v) for v in d10.shape)
-    D = int(W.shape[0])
-    X = _zinb_mat(what, "X", X, D)
-    if X.shape[0] != n:
-        raise ValueError(f"{what}: X has {X.shape[0]} rows, d10 has {n}")
-    if segments < 0:
-        raise ValueError(f"{what}: segments = {segments} below 0")
-    (W, b), (Wp, bp), (Wr, br) = (_zinb_layer(what, "fc11", W, b, D, H), _zinb_layer(what, "fc11_p", Wp, bp, D, H),
-                                  _zinb_layer(what, "fc11_r", Wr, br, D, H))
-    dev = d10.device
-    grads, ptrs = {}, []
-    for j, h in enumerate(ZINB_HEADS):
-        if mask >> j & 1:
-            grads[h] = (torch.empty(D, H, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev))
-            ptrs += list(grads[h])
-        else:
-            ptrs += [None, None]
+    keep, n, H, D, dev, mask, args = _zinb_inputs(what, d10, W, b, Wp, bp, Wr, br, X, eps, scale, heads, segments)
+    grads, ptrs = _zinb_head_outputs(what, mask, None, D, H, dev)
     with torch.cuda.device(dev):
         nbytes = int(lib().mmvae_zinb_step_grads_workspace_bytes(n, D, H, int(segments)))
         ws = _workspace(nbytes, dev)
-        cell = torch.empty(n, dtype=torch.float64, device=dev)
-        gene = torch.empty(D, dtype=torch.float64, device=dev)
+        cell, gene = _zinb_sums(n, D, dev)
         gd10 = torch.empty(n, H, dtype=torch.float32, device=dev)
-        check(lib().mmvae_zinb_step_grads(_ptr(d10), _zinb_pitch(d10), n, H, D, _ptr(W), _ptr(b), _ptr(Wp), _ptr(bp), _ptr(Wr),
-                                          _ptr(br), _ptr(X), _zinb_pitch(X), float(eps),
-                                          1.0 / (float(n) * float(D)) if scale is None else float(scale), mask, int(segments),
-                                          _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _ptr(gd10), H,
+        check(lib().mmvae_zinb_step_grads(*args, _ptr(ws), nbytes, *(_ptr(t) for t in ptrs), _ptr(cell), _ptr(gene), _ptr(gd10), H,
                                           _stream(dev)), "mmvae_zinb_step_grads")
     return grads, cell, gene, gd10
 
@@ -1420,18 +1391,11 @@ def zinb_terms_grad(x_rec: torch.Tensor, x_p: torch.Tensor, x_r: torch.Tensor, X
     """mmvae_zinb_terms_grad: ``scale`` x the gradient of every element's ZINB term with respect to the given heads (float32
     [N, D] on the GPU, rows may be strided) -> (g_rec, g_p, g_r) float32 [N, D] on the device."""
     what = "zinb_terms_grad"
-    _need_cuda(what, x_rec, x_p, x_r, X)
-    X = _zinb_mat(what, "X", X)
-    n, D = (int(v) for v in X.shape)
-    x_rec, x_p, x_r = (_zinb_mat(what, nm, t, D) for nm, t in (("rec_x", x_rec), ("x_p", x_p), ("x_r", x_r)))
-    if not (x_rec.shape[0] == x_p.shape[0] == x_r.shape[0] == n):
-        raise ValueError(f"{what}: the four matrices must have the same number of rows")
-    dev = X.device
+    keep, n, D, dev, args = _zinb_given_heads(what, x_rec, x_p, x_r, X, eps)
     with torch.cuda.device(dev):
         g = [torch.empty(n, D, dtype=torch.float32, device=dev) for _ in range(3)]
-        check(lib().mmvae_zinb_terms_grad(_ptr(x_rec), _zinb_pitch(x_rec), _ptr(x_p), _zinb_pitch(x_p), _ptr(x_r), _zinb_pitch(x_r),
-                                          _ptr(X), _zinb_pitch(X), n, D, float(eps), float(scale), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
-                                          D, _stream(dev)), "mmvae_zinb_terms_grad")
+        check(lib().mmvae_zinb_terms_grad(*args, float(scale), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), D, _stream(dev)),
+              "mmvae_zinb_terms_grad")
     return tuple(g)
 
 

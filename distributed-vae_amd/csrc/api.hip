@@ -759,15 +759,14 @@ static int check_zinb_ws(const char* who, const mmvae_dims* d, double zinb_eps, 
     return 0;
 }
 
-struct ZinbArm {
-    const float *d10, *X, *W, *b, *Wp, *bp, *Wr, *br;
-};
-static ZinbArm zinb_arm(const Ctx& c, int a, const float* params, const float* heads_pr, const float* x, int64_t xs) {
+// one arm's inputs of the ZINB kernels: D10 of the workspace, the arm's rows of x, fc11 of params and the two heads of heads_pr
+static ZinbIn zinb_arm(const Ctx& c, int a, const float* params, const float* heads_pr, const float* x, int64_t xs, double eps, double scale) {
     const int64_t D = c.d.D, H = c.d.H;
     const float* P = params + (int64_t)a * c.po.per_arm;
     const float* Q = heads_pr + (int64_t)a * 2 * (D * H + D);
-    return ZinbArm{c.ws + c.lay.Dk[4] + (int64_t)a * c.d.B * H, x + (int64_t)a * xs, P + c.po.o[26], P + c.po.o[27],
-                   Q, Q + D * H, Q + D * H + D, Q + 2 * D * H + D};
+    return ZinbIn{c.ws + c.lay.Dk[4] + (int64_t)a * c.d.B * H, H, c.d.B, c.d.H, c.d.D,
+                  {{P + c.po.o[26], Q, Q + D * H + D}, {P + c.po.o[27], Q + D * H, Q + 2 * D * H + D}},
+                  x + (int64_t)a * xs, D, eps, scale, 7, 0};
 }
 
 int mmvae_zinb_train_step(const mmvae_dims* d, const mmvae_hyper* h, const mmvae_noise* nz, float* params, float* heads_pr,
@@ -814,14 +813,11 @@ int mmvae_zinb_train_step(const mmvae_dims* d, const mmvae_hyper* h, const mmvae
     const double scale = (double)(A > 1 ? A - 1 : 1) / ((double)B * (double)D);
     const int64_t hp_per_arm = 2 * ((int64_t)D * H + D);
     for (int a = 0; a < A; ++a) {
-        const ZinbArm za = zinb_arm(c, a, params, heads_pr, x, x_arm_stride);
         float* G = grads + (int64_t)a * c.po.per_arm;
         float* HG = head_grads + (int64_t)a * hp_per_arm;
-        float* const dW[3] = {G + c.po.o[26], HG, HG + (int64_t)D * H + D};
-        float* const db[3] = {G + c.po.o[27], HG + (int64_t)D * H, HG + 2 * (int64_t)D * H + D};
-        if ((rc = launch_zinb_step_grads(za.d10, H, B, H, D, za.W, za.b, za.Wp, za.bp, za.Wr, za.br, za.X, D, zinb_eps, scale, 7, 0, zb, dW,
-                                         db, cell + (int64_t)a * B, gene, c.ws + c.lay.GD10_slab + (int64_t)a * B * H, H, c.stream)))
-            return rc;
+        const ZinbGradOut out{{G + c.po.o[26], HG, HG + (int64_t)D * H + D}, {G + c.po.o[27], HG + (int64_t)D * H, HG + 2 * (int64_t)D * H + D},
+                              cell + (int64_t)a * B, gene, c.ws + c.lay.GD10_slab + (int64_t)a * B * H, H};
+        if ((rc = launch_zinb_head_grads(zinb_arm(c, a, params, heads_pr, x, x_arm_stride, zinb_eps, scale), zb, out, c.stream))) return rc;
     }
     if ((rc = launch_zinb_rec(cell, A, B, D, zrec, c.stream))) return rc;
     if ((rc = launch_couple(c))) return rc;
@@ -848,7 +844,7 @@ int mmvae_zinb_objective(const mmvae_dims* d, const mmvae_hyper* h, const float*
     ZinbWs z;
     if (int rc = check_zinb_ws(who, d, zinb_eps, zws, zws_bytes, z)) return rc;
     make_plan(c, CALL_LOSS, nullptr, nullptr, 0);
-    const int A = d->A, D = d->D, H = d->H;
+    const int A = d->A, D = d->D;
     const int64_t B = d->B;
     char* zb = static_cast<char*>(zws);
     double* cell = reinterpret_cast<double*>(zb + z.grads);
@@ -856,9 +852,7 @@ int mmvae_zinb_objective(const mmvae_dims* d, const mmvae_hyper* h, const float*
     double* zrec = gene + D;
     int rc;
     for (int a = 0; a < A; ++a) {
-        const ZinbArm za = zinb_arm(c, a, params, heads_pr, x, x_arm_stride);
-        if ((rc = launch_zinb_nll(za.d10, H, B, H, D, za.W, za.b, za.Wp, za.bp, za.Wr, za.br, za.X, D, zinb_eps, zb, cell + (int64_t)a * B,
-                                  gene, c.stream)))
+        if ((rc = launch_zinb_nll(zinb_arm(c, a, params, heads_pr, x, x_arm_stride, zinb_eps, 0.0), zb, cell + (int64_t)a * B, gene, c.stream)))
             return rc;
     }
     if ((rc = launch_zinb_rec(cell, A, B, D, zrec, c.stream))) return rc;

@@ -574,8 +574,8 @@ int mmvae_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, const
     if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
     if (int rc = zinb_grid(who, N, D)) return rc;
     if (int rc = check_ws(who, ws_bytes, mmvae_zinb_nll_workspace_bytes(N, D))) return rc;
-    return launch_zinb_nll(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, ws, cell_sum, gene_sum,
-                           reinterpret_cast<hipStream_t>(stream));
+    const ZinbIn in{d10, ldh, N, H, D, {{W, Wp, Wr}, {b, bp, br}}, X, ldx, eps, 0.0, 7, 0};
+    return launch_zinb_nll(in, ws, cell_sum, gene_sum, reinterpret_cast<hipStream_t>(stream));
 }
 
 int mmvae_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,
@@ -615,38 +615,47 @@ int mmvae_zinb_head_grads_segments(int64_t N, int D, int segments) {
     return zg_segments(N, D, segments, nullptr);
 }
 
+// What the three gradient entries check, in one order: `heads` for an entry that writes dW, db and the term's sums, `d10` for
+// one that writes gd10; ws_fn is the entry's own workspace function.
+static int zinb_grad_checks(const char* who, bool heads, bool d10, const ZinbIn& in, const void* ws, size_t ws_bytes,
+                            size_t (*ws_fn)(int64_t, int, int, int), const ZinbGradOut& out) {
+    const ZbHeads<3>& hd = in.hd;
+    if (!in.d10 || !hd.W[0] || !hd.b[0] || !hd.W[1] || !hd.b[1] || !hd.W[2] || !hd.b[2] || !in.X || !ws ||
+        (heads && (!out.cell_sum || !out.gene_sum)) || (d10 && !out.gd10)) {
+        set_error("%s: null pointer", who);
+        return MMVAE_E_BADARG;
+    }
+    if (int rc = check_count(who, "head_mask", in.mask, 1, 7)) return rc;
+    for (int j = 0; heads && j < 3; ++j)
+        if ((in.mask >> j & 1) && (!out.dW[j] || !out.db[j])) { set_error("%s: null pointer (a selected head's output)", who); return MMVAE_E_BADARG; }
+    if (int rc = zinb_extent(who, in.N, in.D)) return rc;
+    if (int rc = check_count(who, "H", in.H, 1, INT32_MAX)) return rc;
+    if (int rc = check_count(who, "segments", in.segments, 0, INT32_MAX)) return rc;
+    if (int rc = check_pitch(who, "ldh", in.ldh, "H", in.H)) return rc;
+    if (int rc = check_pitch(who, "ldx", in.ldx, "D", in.D)) return rc;
+    if (d10)
+        if (int rc = check_pitch(who, "ldg", out.ldg, "H", in.H)) return rc;
+    if (int rc = zinb_eps(who, in.eps)) return rc;
+    if (int rc = zinb_scale(who, in.scale)) return rc;
+    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
+    if (in.H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, in.H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = zinb_grid(who, in.N, in.D)) return rc;
+    const size_t need = ws_fn(in.N, in.D, in.H, in.segments);
+    if (need == 0) {
+        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)in.N, in.D, in.segments);
+        return MMVAE_E_UNSUPPORTED;
+    }
+    return check_ws(who, ws_bytes, need);
+}
+
 int mmvae_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
                           int head_mask, int segments, void* ws, size_t ws_bytes, float* dW, float* db, float* dWp, float* dbp,
                           float* dWr, float* dbr, double* cell_sum, double* gene_sum, void* stream) {
-    const char* who = "zinb_head_grads";
-    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !cell_sum || !gene_sum) {
-        set_error("%s: null pointer", who);
-        return MMVAE_E_BADARG;
-    }
-    if (int rc = check_count(who, "head_mask", head_mask, 1, 7)) return rc;
-    float* const dWs[3] = {dW, dWp, dWr};
-    float* const dbs[3] = {db, dbp, dbr};
-    for (int j = 0; j < 3; ++j)
-        if ((head_mask >> j & 1) && (!dWs[j] || !dbs[j])) { set_error("%s: null pointer (a selected head's output)", who); return MMVAE_E_BADARG; }
-    if (int rc = zinb_extent(who, N, D)) return rc;
-    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
-    if (int rc = check_count(who, "segments", segments, 0, INT32_MAX)) return rc;
-    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
-    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
-    if (int rc = zinb_eps(who, eps)) return rc;
-    if (int rc = zinb_scale(who, scale)) return rc;
-    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
-    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = zinb_grid(who, N, D)) return rc;
-    const size_t need = mmvae_zinb_head_grads_workspace_bytes(N, D, H, segments);
-    if (need == 0) {
-        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)N, D, segments);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (int rc = check_ws(who, ws_bytes, need)) return rc;
-    return launch_zinb_head_grads(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, scale, head_mask, segments, ws, dWs, dbs, cell_sum,
-                                  gene_sum, reinterpret_cast<hipStream_t>(stream));
+    const ZinbIn in{d10, ldh, N, H, D, {{W, Wp, Wr}, {b, bp, br}}, X, ldx, eps, scale, head_mask, segments};
+    const ZinbGradOut out{{dW, dWp, dWr}, {db, dbp, dbr}, cell_sum, gene_sum, nullptr, 0};
+    if (int rc = zinb_grad_checks("zinb_head_grads", true, false, in, ws, ws_bytes, mmvae_zinb_head_grads_workspace_bytes, out)) return rc;
+    return launch_zinb_head_grads(in, ws, out, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- the gradient with respect to d10, and the decoder trunk's backward (zinb_grad.hip, zinb_trunk.hip) ----
@@ -663,28 +672,10 @@ int mmvae_zinb_d10_grad_segments(int64_t N, int D, int segments) {
 int mmvae_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
                         const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
                         int head_mask, int segments, void* ws, size_t ws_bytes, float* gd10, int64_t ldg, void* stream) {
-    const char* who = "zinb_d10_grad";
-    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !gd10) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
-    if (int rc = check_count(who, "head_mask", head_mask, 1, 7)) return rc;
-    if (int rc = zinb_extent(who, N, D)) return rc;
-    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
-    if (int rc = check_count(who, "segments", segments, 0, INT32_MAX)) return rc;
-    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
-    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
-    if (int rc = check_pitch(who, "ldg", ldg, "H", H)) return rc;
-    if (int rc = zinb_eps(who, eps)) return rc;
-    if (int rc = zinb_scale(who, scale)) return rc;
-    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
-    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = zinb_grid(who, N, D)) return rc;
-    const size_t need = mmvae_zinb_d10_grad_workspace_bytes(N, D, H, segments);
-    if (need == 0) {
-        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)N, D, segments);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (int rc = check_ws(who, ws_bytes, need)) return rc;
-    return launch_zinb_d10_grad(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, scale, head_mask, segments, ws, gd10, ldg,
-                                reinterpret_cast<hipStream_t>(stream));
+    const ZinbIn in{d10, ldh, N, H, D, {{W, Wp, Wr}, {b, bp, br}}, X, ldx, eps, scale, head_mask, segments};
+    const ZinbGradOut out{{}, {}, nullptr, nullptr, gd10, ldg};
+    if (int rc = zinb_grad_checks("zinb_d10_grad", false, true, in, ws, ws_bytes, mmvae_zinb_d10_grad_workspace_bytes, out)) return rc;
+    return launch_zinb_d10_grad(in, ws, gd10, ldg, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- the heads' gradients and gd10 in one pass over g (zinb_grad.hip, k_zg_step) ----
@@ -697,35 +688,10 @@ int mmvae_zinb_step_grads(const float* d10, int64_t ldh, int64_t N, int H, int D
                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
                           int head_mask, int segments, void* ws, size_t ws_bytes, float* dW, float* db, float* dWp, float* dbp,
                           float* dWr, float* dbr, double* cell_sum, double* gene_sum, float* gd10, int64_t ldg, void* stream) {
-    const char* who = "zinb_step_grads";
-    if (!d10 || !W || !b || !Wp || !bp || !Wr || !br || !X || !ws || !cell_sum || !gene_sum || !gd10) {
-        set_error("%s: null pointer", who);
-        return MMVAE_E_BADARG;
-    }
-    if (int rc = check_count(who, "head_mask", head_mask, 1, 7)) return rc;
-    float* const dWs[3] = {dW, dWp, dWr};
-    float* const dbs[3] = {db, dbp, dbr};
-    for (int j = 0; j < 3; ++j)
-        if ((head_mask >> j & 1) && (!dWs[j] || !dbs[j])) { set_error("%s: null pointer (a selected head's output)", who); return MMVAE_E_BADARG; }
-    if (int rc = zinb_extent(who, N, D)) return rc;
-    if (int rc = check_count(who, "H", H, 1, INT32_MAX)) return rc;
-    if (int rc = check_count(who, "segments", segments, 0, INT32_MAX)) return rc;
-    if (int rc = check_pitch(who, "ldh", ldh, "H", H)) return rc;
-    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
-    if (int rc = check_pitch(who, "ldg", ldg, "H", H)) return rc;
-    if (int rc = zinb_eps(who, eps)) return rc;
-    if (int rc = zinb_scale(who, scale)) return rc;
-    if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
-    if (H > ZB_MAX_H) { set_error("%s: H = %d above %d", who, H, ZB_MAX_H); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = zinb_grid(who, N, D)) return rc;
-    const size_t need = mmvae_zinb_step_grads_workspace_bytes(N, D, H, segments);
-    if (need == 0) {
-        set_error("%s: N = %lld, D = %d with %d segments need more than 2^31 - 1 workgroups", who, (long long)N, D, segments);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (int rc = check_ws(who, ws_bytes, need)) return rc;
-    return launch_zinb_step_grads(d10, ldh, N, H, D, W, b, Wp, bp, Wr, br, X, ldx, eps, scale, head_mask, segments, ws, dWs, dbs, cell_sum,
-                                  gene_sum, gd10, ldg, reinterpret_cast<hipStream_t>(stream));
+    const ZinbIn in{d10, ldh, N, H, D, {{W, Wp, Wr}, {b, bp, br}}, X, ldx, eps, scale, head_mask, segments};
+    const ZinbGradOut out{{dW, dWp, dWr}, {db, dbp, dbr}, cell_sum, gene_sum, gd10, ldg};
+    if (int rc = zinb_grad_checks("zinb_step_grads", true, true, in, ws, ws_bytes, mmvae_zinb_step_grads_workspace_bytes, out)) return rc;
+    return launch_zinb_head_grads(in, ws, out, reinterpret_cast<hipStream_t>(stream));
 }
 
 size_t mmvae_decoder_trunk_grads_workspace_bytes(int64_t N, int Z, int L, int H, int segments) {

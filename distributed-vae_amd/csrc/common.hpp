@@ -1130,13 +1130,37 @@ int launch_leaf_merge(double* p, int64_t ldp, int64_t n, int L, const int* level
                       hipStream_t st);
 // zero-inflated negative binomial heads, terms and sums (zinb.hip)
 constexpr int ZB_MAX_H = 128;          // the K extent one LDS tile holds
+template <int NH>
+struct ZbHeads {
+    const float* W[NH];      // [D, H] each, nn.Linear's layout
+    const float* b[NH];      // [D]
+};
+// what the entries on d10 and X share: d10 [N, H] at pitch ldh, the heads fc11, fc11_p, fc11_r, X [N, D] at pitch ldx; the
+// gradient entries read scale, mask (the selected heads, bits 1, 2, 4) and segments (0 = the launcher's rule) as well
+struct ZinbIn {
+    const float* d10;
+    int64_t ldh, N;
+    int H, D;
+    ZbHeads<3> hd;
+    const float* X;
+    int64_t ldx;
+    double eps, scale;
+    int mask, segments;
+};
+// the outputs of the gradient entries: dW_j [D, H], db_j [D] of the selected heads and the term's sums (mmvae_zinb_head_grads),
+// gd10 [N, H] at pitch ldg (mmvae_zinb_d10_grad); mmvae_zinb_step_grads has both
+struct ZinbGradOut {
+    float* dW[3];
+    float* db[3];
+    double *cell_sum, *gene_sum;
+    float* gd10;
+    int64_t ldg;
+};
 size_t zb_ws_bytes(int64_t N, int D);  // the partial sums of the 32 x 32 sub-tiles; 0 for a size no size_t holds
 int64_t zb_tiles(int64_t N, int D);    // the workgroups of one grid; 0 where a grid cannot hold them
 int launch_zinb_heads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* Wp, const float* bp, const float* Wr,
                       const float* br, float* x_p, float* x_r, int64_t ldo, hipStream_t st);
-int launch_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
-                    const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, void* ws,
-                    double* cell_sum, double* gene_sum, hipStream_t st);
+int launch_zinb_nll(const ZinbIn& in, void* ws, double* cell_sum, double* gene_sum, hipStream_t st);
 int launch_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,
                       int64_t ldx, int64_t N, int D, double eps, void* ws, double* cell_sum, double* gene_sum, float* terms,
                       int64_t ld_t, hipStream_t st);
@@ -1146,10 +1170,8 @@ int zb_finish(void* ws, int64_t N, int D, double* cell_sum, double* gene_sum, hi
 int zg_segments(int64_t N, int D, int asked, int* tiles_per_seg);   // the cell segments of a call (and the cell tiles of one)
 size_t zg_ws_bytes(int64_t N, int D, int H, int asked);             // zb_ws_bytes, then the segments' partials; 0 as zb_ws_bytes
 int64_t zg_tiles(int64_t N, int D, int asked);                      // the workgroups of one grid; 0 where a grid cannot hold them
-int launch_zinb_head_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
-                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
-                           int mask, int segments, void* ws, float* const* dW, float* const* db, double* cell_sum, double* gene_sum,
-                           hipStream_t st);
+// with out.gd10 the same pass leaves gd10 too (k_zg_step), at a segment a gene tile: ws is zs_ws_bytes then, zg_ws_bytes without
+int launch_zinb_head_grads(const ZinbIn& in, void* ws, const ZinbGradOut& out, hipStream_t st);
 int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r,
                            const float* X, int64_t ldx, int64_t N, int D, double eps, double scale, float* g_rec, float* g_p, float* g_r,
                            int64_t ld_g, hipStream_t st);
@@ -1157,15 +1179,8 @@ int launch_zinb_terms_grad(const float* x_rec, int64_t ld_rec, const float* x_p,
 int zd_segments(int64_t N, int D, int asked, int* tiles_per_seg);
 size_t zd_ws_bytes(int64_t N, int D, int H, int asked);             // the segments' partials; 0 for a size no size_t holds
 int64_t zd_tiles(int64_t N, int D, int asked);                      // the workgroups of one grid; 0 where a grid cannot hold them
-int launch_zinb_d10_grad(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
-                         const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
-                         int mask, int segments, void* ws, float* gd10, int64_t ldg, hipStream_t st);
-// both in one pass over g (zinb_grad.hip, k_zg_step): the heads' gradients at `segments` cell segments, gd10 at a segment a gene tile
+int launch_zinb_d10_grad(const ZinbIn& in, void* ws, float* gd10, int64_t ldg, hipStream_t st);
 size_t zs_ws_bytes(int64_t N, int D, int H, int asked);             // zg_ws_bytes, then the gene tiles' partials of gd10
-int launch_zinb_step_grads(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
-                           const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, double scale,
-                           int mask, int segments, void* ws, float* const* dW, float* const* db, double* cell_sum, double* gene_sum,
-                           float* gd10, int64_t ldg, hipStream_t st);
 // the decoder trunk's backward from gd10 (zinb_trunk.hip); act / ld: zin, d6 .. d10; W: fc6 .. fc10; grads: dW6, db6, .. db10
 constexpr int TR_MAX_W = 128;          // H and L at most: a row of dZ in LDS
 constexpr int TR_MAX_SEG = 1024;       // cell segments one call may ask for

@@ -14,8 +14,9 @@
 // over its 32 genes (a butterfly over the lanes: the pairwise tree on the gene index), and for each of its genes the sum over
 // its 32 cells (a lane's 16 cells in register order, then the two lane halves); k_zb_finish adds the sub-tiles' partials
 // in tile order.  No atomics: bit-identical from run to run, and a cell's sum depends on that cell's row alone.
-// The tile's products and sums (zb_products, zb_reduce) live in zb_tile.hpp, which countdist.hip shares; the element's term and
-// its gates (zinb_term, zb_gate) in zinb_core.hpp, which zinb_grad.hip shares.
+// The tile's products and sums (zb_run under zb_products, zb_reduce) live in zb_tile.hpp, which countdist.hip and zinb_grad.hip
+// share; the element's term, its gates and what they read from the pre-activations (zinb_term, zb_gate, zb_operands) in
+// zinb_core.hpp, which zinb_grad.hip and the host's restatement share.
 #include "zb_tile.hpp"
 #include "zinb_core.hpp"
 
@@ -63,10 +64,7 @@ __global__ __launch_bounds__(ZB_THREADS) void k_zb_nll(const float* __restrict__
     zb_reduce(
         [&](int g, int64_t cell, int64_t gene) {
             const float a_rec = mine[g * 64], a_p = mine[(16 + g) * 64], a_r = mine[(32 + g) * 64];
-            double p, q, z, y;
-            zb_gate(a_p, eps, p, q);
-            zb_gate(a_r, eps, z, y);
-            return zinb_term((double)X[cell * ldx + gene], (double)fmaxf(a_rec, 0.f) + eps, p, q, z, y);
+            return zinb_term(zb_operands(X[cell * ldx + gene], a_rec, a_p, a_r, eps));
         },
         lane, wc0, wg0, N, D, ws_cell, ws_gene);
 }
@@ -134,15 +132,12 @@ int launch_zinb_heads(const float* d10, int64_t ldh, int64_t N, int H, int D, co
     return 0;
 }
 
-int launch_zinb_nll(const float* d10, int64_t ldh, int64_t N, int H, int D, const float* W, const float* b, const float* Wp,
-                    const float* bp, const float* Wr, const float* br, const float* X, int64_t ldx, double eps, void* ws,
-                    double* cell_sum, double* gene_sum, hipStream_t st) {
-    ZbHeads<3> hd{{W, Wp, Wr}, {b, bp, br}};
+int launch_zinb_nll(const ZinbIn& in, void* ws, double* cell_sum, double* gene_sum, hipStream_t st) {
     double* ws_cell = static_cast<double*>(ws);
-    hipLaunchKernelGGL(k_zb_nll, dim3((unsigned)zb_tiles(N, D)), dim3(ZB_THREADS), 0, st, d10, ldh, N, H, D, hd, X, ldx, eps, ws_cell,
-                       ws_cell + cdiv64(D, 32) * N, (int)cdiv64(D, ZB_T));
+    hipLaunchKernelGGL(k_zb_nll, dim3((unsigned)zb_tiles(in.N, in.D)), dim3(ZB_THREADS), 0, st, in.d10, in.ldh, in.N, in.H, in.D, in.hd, in.X,
+                       in.ldx, in.eps, ws_cell, ws_cell + cdiv64(in.D, 32) * in.N, (int)cdiv64(in.D, ZB_T));
     HIP_LAUNCH_CHECK("k_zb_nll");
-    return zb_finish(ws, N, D, cell_sum, gene_sum, st);
+    return zb_finish(ws, in.N, in.D, cell_sum, gene_sum, st);
 }
 
 int launch_zinb_terms(const float* x_rec, int64_t ld_rec, const float* x_p, int64_t ld_p, const float* x_r, int64_t ld_r, const float* X,

@@ -77,4 +77,32 @@ ZB_HD void zinb_term_grad(double X, double r, double p, double q, double z, doub
     gz = expm1(r * lq) / u;
 }
 
+// One element of the kernels on d10: what zinb_term reads, from X and the float32 pre-activations of the three heads.
+// r = relu(a_rec) + eps; the gates of a_p and a_r.
+struct ZbOperands {
+    double x, r, p, q, z, y;
+};
+ZB_HD ZbOperands zb_operands(float X, float a_rec, float a_p, float a_r, double eps) {
+    ZbOperands o;
+    zb_gate(a_p, eps, o.p, o.q);
+    zb_gate(a_r, eps, o.z, o.y);
+    o.x = (double)X;
+    o.r = (double)fmaxf(a_rec, 0.f) + eps;
+    return o;
+}
+ZB_HD double zinb_term(const ZbOperands& o) { return zinb_term(o.x, o.r, o.p, o.q, o.z, o.y); }
+
+// g = d term / d (a_rec, a_p, a_r) of that element in fp64, before any rounding: zinb_term_grad through the relu's and the
+// gates' slopes.  Returns the operands, from which zinb_term gives the element's term (two lgamma: the caller asks for it or
+// not).  The one body of the gradient kernels (zinb_grad.hip: zg_element) and of the host's restatement (host_zinb_grad).
+ZB_HD ZbOperands zinb_element_grad(float X, float a_rec, float a_p, float a_r, double eps, double (&g)[3]) {
+    const ZbOperands o = zb_operands(X, a_rec, a_p, a_r, eps);
+    double gr, gp, gz;
+    zinb_term_grad(o.x, o.r, o.p, o.q, o.z, o.y, gr, gp, gz);
+    g[0] = a_rec > 0.f ? gr : 0.0;
+    g[1] = gp * zb_gate_slope(a_p, eps);
+    g[2] = gz * zb_gate_slope(a_r, eps);
+    return o;
+}
+
 }  // namespace mmvae

@@ -175,6 +175,38 @@ def test_zinb_head_grads_rejects_bad_arguments(kw, rc):
     assert "zinb_head_grads" in N.lib().mmvae_last_error_string().decode()
 
 
+def _step_grads(**kw):
+    a = dict(d10=PTR, ldh=100, N=64, H=100, D=70, W=PTR, b=PTR, Wp=PTR, bp=PTR, Wr=PTR, br=PTR, X=PTR, ldx=70, eps=1e-6, scale=1.0,
+             mask=7, segments=0, ws=PTR, ws_bytes=1 << 40, dW=PTR, db=PTR, dWp=PTR, dbp=PTR, dWr=PTR, dbr=PTR, cell=PTR, gene=PTR,
+             gd10=PTR, ldg=100)
+    a.update(kw)
+    return N.lib().mmvae_zinb_step_grads(a["d10"], a["ldh"], a["N"], a["H"], a["D"], a["W"], a["b"], a["Wp"], a["bp"], a["Wr"],
+                                         a["br"], a["X"], a["ldx"], a["eps"], a["scale"], a["mask"], a["segments"], a["ws"],
+                                         a["ws_bytes"], a["dW"], a["db"], a["dWp"], a["dbp"], a["dWr"], a["dbr"], a["cell"],
+                                         a["gene"], a["gd10"], a["ldg"], None)
+
+
+# the union of the tables of mmvae_zinb_head_grads (above) and mmvae_zinb_d10_grad (test_zinb_decoder_cpu.py), gd10 = None and a
+# short ldg; the workspace is the head gradients' (one cell segment) and then gd10's at a segment a gene tile (two)
+STEP_WS = 8 * (3 * 64 + 2 * 70) + 4 * 3 * 70 * 101 + 4 * 2 * 64 * 100
+
+
+@pytest.mark.parametrize("kw,rc", [
+    (dict(d10=None), BAD), (dict(W=None), BAD), (dict(b=None), BAD), (dict(Wp=None), BAD), (dict(bp=None), BAD), (dict(Wr=None), BAD),
+    (dict(br=None), BAD), (dict(X=None), BAD), (dict(ws=None), BAD), (dict(cell=None), BAD), (dict(gene=None), BAD),
+    (dict(gd10=None), BAD), (dict(dW=None), BAD), (dict(dbp=None), BAD), (dict(dWr=None), BAD), (dict(mask=0), BAD),
+    (dict(mask=8), BAD), (dict(mask=6, dWp=None), BAD), (dict(N=0), BAD), (dict(D=0), BAD), (dict(H=0), BAD), (dict(ldh=99), BAD),
+    (dict(ldx=69), BAD), (dict(ldg=99), BAD), (dict(eps=-1e-6), BAD), (dict(eps=1.0), BAD), (dict(scale=float("inf")), BAD),
+    (dict(scale=float("nan")), BAD), (dict(segments=-1), BAD), (dict(ws=PTR + 4), BAD),
+    (dict(H=129, ldh=129), BAD),                       # doubly bad: the short ldg is met before H above 128
+    (dict(H=129, ldh=129, ldg=129), UNSUPPORTED), (dict(N=1 << 31, D=1 << 20, ldx=1 << 20), UNSUPPORTED),
+    (dict(ws_bytes=8 * (3 * 64 + 2 * 70) + 4 * 3 * 70 * 101 - 1), WORKSPACE), (dict(ws_bytes=4 * 2 * 64 * 100 - 1), WORKSPACE),
+    (dict(ws_bytes=STEP_WS - 1), WORKSPACE)])
+def test_zinb_step_grads_rejects_bad_arguments(kw, rc):
+    assert _step_grads(**kw) == rc
+    assert "zinb_step_grads" in N.lib().mmvae_last_error_string().decode()
+
+
 def test_an_unselected_heads_outputs_may_be_null():
     assert _head_grads(mask=6, dW=None, db=None, ws_bytes=8) == WORKSPACE          # past the pointer checks
     assert "workspace" in N.lib().mmvae_last_error_string().decode()
