@@ -15,6 +15,14 @@ static int check_count(const char* who, const char* name, int64_t v, int64_t lo,
     return MMVAE_E_BADARG;
 }
 
+// a count from 1 up (else a bad argument) that the kernels take up to cap (above: unsupported)
+static int check_extent(const char* who, const char* name, int v, int cap) {
+    if (int rc = check_count(who, name, v, 1, INT32_MAX)) return rc;
+    if (v <= cap) return 0;
+    set_error("%s: %s = %d above %d", who, name, v, cap);
+    return MMVAE_E_UNSUPPORTED;
+}
+
 // n selected rows of a matrix of n_total: without a row map they are its first n
 static int check_rowmap(const char* who, const int64_t* rows, int64_t n, int64_t n_total) {
     if (n_total < 1) { set_error("%s: n_total = %lld below 1", who, (long long)n_total); return MMVAE_E_BADARG; }
@@ -262,22 +270,28 @@ size_t mmvae_rank_sum_workspace_bytes(int64_t n, int D, int G) {
     return ((size_t)(D < RS_CHUNK ? D : RS_CHUNK) * (size_t)n * sizeof(float) + 7) / 8 * 8;
 }
 
+// the checks both rank-sum entries begin with, up to eps.  cap: the entry's most cells; why: what those cells are the most of
+static int rank_sum_args(const char* who, int cap, const char* why, const float* x, int64_t ldx, int64_t n_total, int D,
+                         const int64_t* rows, int64_t n, const int64_t* offsets, int G, float eps, const void* ws,
+                         const int64_t* rank_sum2, const int64_t* tie_term, const int64_t* n_pos, const double* sum) {
+    if (!x || !offsets || !ws || !rank_sum2 || !tie_term || !n_pos || !sum) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
+    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
+    if (n > cap) { set_error("%s: n = %lld cells above the %d %s", who, (long long)n, cap, why); return MMVAE_E_UNSUPPORTED; }
+    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
+    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
+    if (int rc = check_extent(who, "G", G, RS_MAX_G)) return rc;
+    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
+    if (eps != eps) { set_error("%s: eps is a NaN", who); return MMVAE_E_BADARG; }
+    return 0;
+}
+
 int mmvae_rank_sum(const float* x, int64_t ldx, int64_t n_total, int D, const int64_t* rows, int64_t n, const int64_t* offsets, int G,
                    float eps, void* ws, size_t ws_bytes, int64_t* rank_sum2, int64_t* tie_term, int64_t* n_pos, double* sum,
                    void* stream) {
     const char* who = "rank_sum";
-    if (!x || !offsets || !ws || !rank_sum2 || !tie_term || !n_pos || !sum) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
-    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
-    if (n > RS_MAX_N) {
-        set_error("%s: n = %lld cells above the %d whose keys one workgroup's LDS holds", who, (long long)n, RS_MAX_N);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
-    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
-    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
-    if (G > RS_MAX_G) { set_error("%s: G = %d above %d", who, G, RS_MAX_G); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
-    if (eps != eps) { set_error("%s: eps is a NaN", who); return MMVAE_E_BADARG; }
+    if (int rc = rank_sum_args(who, RS_MAX_N, "whose keys one workgroup's LDS holds", x, ldx, n_total, D, rows, n, offsets, G, eps, ws,
+                               rank_sum2, tie_term, n_pos, sum))
+        return rc;
     if (int rc = check_aligned(who, "workspace", ws, sizeof(double))) return rc;
     if (int rc = check_ws(who, ws_bytes, mmvae_rank_sum_workspace_bytes(n, D, G))) return rc;
     return launch_rank_sum(x, ldx, n_total, D, rows, (int)n, offsets, G, eps, ws, rank_sum2, tie_term, n_pos, sum,
@@ -299,18 +313,9 @@ static int rank_sum_blocked_checked(const float* x, int64_t ldx, int64_t n_total
                                     const int64_t* offsets, int G, float eps, int block, void* ws, size_t ws_bytes, int64_t* rank_sum2,
                                     int64_t* tie_term, int64_t* n_pos, double* sum, int form, int phases, void* stream) {
     const char* who = "rank_sum_blocked";
-    if (!x || !offsets || !ws || !rank_sum2 || !tie_term || !n_pos || !sum) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
-    if (int rc = check_count(who, "n", n, 1, INT64_MAX)) return rc;
-    if (n > RSB_MAX_N) {
-        set_error("%s: n = %lld cells above the %d whose tie term an int64 holds", who, (long long)n, RSB_MAX_N);
-        return MMVAE_E_UNSUPPORTED;
-    }
-    if (int rc = check_rowmap(who, rows, n, n_total)) return rc;
-    if (int rc = check_count(who, "D", D, 1, INT32_MAX)) return rc;
-    if (int rc = check_count(who, "G", G, 1, INT32_MAX)) return rc;
-    if (G > RS_MAX_G) { set_error("%s: G = %d above %d", who, G, RS_MAX_G); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = check_pitch(who, "ldx", ldx, "D", D)) return rc;
-    if (eps != eps) { set_error("%s: eps is a NaN", who); return MMVAE_E_BADARG; }
+    if (int rc = rank_sum_args(who, RSB_MAX_N, "whose tie term an int64 holds", x, ldx, n_total, D, rows, n, offsets, G, eps, ws,
+                               rank_sum2, tie_term, n_pos, sum))
+        return rc;
     const int L = rsb_block(block);
     if (!L) {
         set_error("%s: block = %d is neither 0 nor a power of two in [%d, %d]", who, block, RSB_MIN_BLOCK, RS_MAX_N);
@@ -346,6 +351,17 @@ size_t mmvae_knn_workspace_bytes(int64_t nq, int64_t nr, int d, int k) {
     return knn_ws_bytes(nq, nr, k, knn_seg_cols(nq, nr, k));
 }
 
+// what mmvae_knn and mmvae_knn_votes check alike, in their order: k, then `name` (d, n_classes), then nq and nr
+static int knn_extents(const char* who, int k, const char* name, int v, int cap, int64_t nq, int64_t nr) {
+    if (int rc = check_extent(who, "k", k, KNN_MAX_K)) return rc;
+    if (int rc = check_extent(who, name, v, cap)) return rc;
+    if (int rc = check_count(who, "nq", nq, 1, INT64_MAX)) return rc;
+    if (int rc = check_count(who, "nr", nr, 1, INT64_MAX)) return rc;
+    if (nq <= KNN_MAX_N && nr <= KNN_MAX_N) return 0;
+    set_error("%s: nq = %lld, nr = %lld above %d", who, (long long)nq, (long long)nr, KNN_MAX_N);
+    return MMVAE_E_UNSUPPORTED;
+}
+
 static int knn_checked(const float* q, int64_t ldq, int64_t nq, const float* r, int64_t ldr, int64_t nr, int d, int k,
                        const int32_t* qgroup, const int32_t* rgroup, void* ws, size_t ws_bytes, int32_t* idx, float* dist2,
                        int64_t seg_cols, int phases, void* stream) {
@@ -355,16 +371,7 @@ static int knn_checked(const float* q, int64_t ldq, int64_t nq, const float* r, 
         set_error("%s: qgroup and rgroup come together or not at all", who);
         return MMVAE_E_BADARG;
     }
-    if (int rc = check_count(who, "k", k, 1, INT32_MAX)) return rc;
-    if (k > KNN_MAX_K) { set_error("%s: k = %d above %d", who, k, KNN_MAX_K); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = check_count(who, "d", d, 1, INT32_MAX)) return rc;
-    if (d > KNN_MAX_D) { set_error("%s: d = %d above %d", who, d, KNN_MAX_D); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = check_count(who, "nq", nq, 1, INT64_MAX)) return rc;
-    if (int rc = check_count(who, "nr", nr, 1, INT64_MAX)) return rc;
-    if (nq > KNN_MAX_N || nr > KNN_MAX_N) {
-        set_error("%s: nq = %lld, nr = %lld above %d", who, (long long)nq, (long long)nr, KNN_MAX_N);
-        return MMVAE_E_UNSUPPORTED;
-    }
+    if (int rc = knn_extents(who, k, "d", d, KNN_MAX_D, nq, nr)) return rc;
     if (int rc = check_pitch(who, "ldq", ldq, "d", d)) return rc;
     if (int rc = check_pitch(who, "ldr", ldr, "d", d)) return rc;
     if (seg_cols < 0 || phases < KNN_PHASE_ALL || phases > KNN_PHASE_MERGE) {
@@ -399,16 +406,7 @@ int mmvae_knn_votes(const int32_t* idx, int64_t nq, int k, const int32_t* rlabel
     const char* who = "knn_votes";
     if (!idx || !rlabel || !pred) { set_error("%s: null pointer", who); return MMVAE_E_BADARG; }
     if (purity && !qlabel) { set_error("%s: purity needs qlabel", who); return MMVAE_E_BADARG; }
-    if (int rc = check_count(who, "k", k, 1, INT32_MAX)) return rc;
-    if (k > KNN_MAX_K) { set_error("%s: k = %d above %d", who, k, KNN_MAX_K); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = check_count(who, "n_classes", n_classes, 1, INT32_MAX)) return rc;
-    if (n_classes > KNN_MAX_CLASSES) { set_error("%s: n_classes = %d above %d", who, n_classes, KNN_MAX_CLASSES); return MMVAE_E_UNSUPPORTED; }
-    if (int rc = check_count(who, "nq", nq, 1, INT64_MAX)) return rc;
-    if (int rc = check_count(who, "nr", nr, 1, INT64_MAX)) return rc;
-    if (nq > KNN_MAX_N || nr > KNN_MAX_N) {
-        set_error("%s: nq = %lld, nr = %lld above %d", who, (long long)nq, (long long)nr, KNN_MAX_N);
-        return MMVAE_E_UNSUPPORTED;
-    }
+    if (int rc = knn_extents(who, k, "n_classes", n_classes, KNN_MAX_CLASSES, nq, nr)) return rc;
     return launch_knn_votes(idx, nq, k, rlabel, nr, n_classes, qlabel, pred, purity, top2, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -3,12 +3,10 @@
 // For every query point q_i the k admitted reference points r_j with the smallest squared distance, where reference j is
 // admitted for query i iff no groups are given or rgroup[j] != qgroup[i] (no groups: a plain query; groups = arange on one
 // set: the k-NN graph without the cell itself; groups = the fold of each cell: a test cell sees training cells only).  The
-// squared distance is fp32 in difference form, as k_sil_partial's: subtract, fma the squares in rising coordinate order from
-// +0; coordinates padded to a float4 are zeros on both sides and fma(0, 0, acc) = acc exactly, so a pair's bits do not
-// depend on the padding.  Candidates are ordered by the 64-bit key (bits of the squared distance) << 32 | j: a sum of
-// squares is never -0, so its bits order as unsigned integers, and j breaks ties.  The order is total, hence the k smallest
-// keys of a query are a pure function of the inputs: the same bits on every run, whatever the cut of the work, whatever the
-// other queries of the call.  No atomics.
+// squared distance is fp32 in difference form, k_sil_partial's own (pairdist.hpp states its order and its padding rule).
+// Candidates are ordered by the 64-bit key (bits of the squared distance) << 32 | j: a sum of squares is never -0, so its
+// bits order as unsigned integers, and j breaks ties.  The order is total, hence the k smallest keys of a query are a pure
+// function of the inputs: the same bits on every run, whatever the cut of the work, whatever the other queries.  No atomics.
 //
 // Partition.  The reference columns are cut into segments of seg_cols; one workgroup of one wave owns (segment, tile of
 // T = KNN_TILE = 64 queries), one thread per query (k_knn_partial).  A thread keeps its query in registers and its sorted list of k keys in
@@ -22,7 +20,7 @@
 //
 // k_knn_votes: one thread per query, the labels of its valid neighbours in LDS, counted pair by pair (k^2 integer
 // compares; no table of n_classes counters per thread).
-#include "common.hpp"
+#include "pairdist.hpp"
 
 namespace mmvae {
 
@@ -68,8 +66,7 @@ __global__ __launch_bounds__(KNN_TILE) void k_knn_partial(const float* __restric
                                                      const int* __restrict__ qgroup, const int* __restrict__ rgroup,
                                                      int64_t seg_cols, int64_t nseg, uint64_t* __restrict__ part,
                                                      int* __restrict__ idx, float* __restrict__ dist2) {
-    constexpr int W = 4 * DV;                       // floats per staged column
-    constexpr int CT = KNN_LDS_FLOATS / W;          // columns per pass (at most KNN_LDS_FLOATS / 4)
+    constexpr int CT = KNN_LDS_FLOATS / (4 * DV);   // columns per pass (at most KNN_LDS_FLOATS / 4)
     __shared__ float4 cols[KNN_LDS_FLOATS / 4];
     __shared__ int grp[KNN_LDS_FLOATS / 4];
     extern __shared__ uint64_t lst[];               // k T keys (launch_knn)
@@ -82,41 +79,19 @@ __global__ __launch_bounds__(KNN_TILE) void k_knn_partial(const float* __restric
     const bool grouped = qgroup != nullptr;
     const int qg = valid && grouped ? qgroup[row] : 0;
     float4 xi[DV];
-#pragma unroll
-    for (int v = 0; v < DV; ++v) {
-        float t[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[e] = valid && 4 * v + e < d ? q[row * ldq + 4 * v + e] : 0.f;
-        xi[v] = make_float4(t[0], t[1], t[2], t[3]);
-    }
+    pd_load<DV>(q, ldq, row, d, valid, xi);
     uint64_t* mine = lst + tid;
     for (int s = 0; s < k; ++s) mine[s * T] = KNN_NONE;
     uint64_t worst = KNN_NONE;
-    float* cf = reinterpret_cast<float*>(cols);
     for (int64_t cb = c0; cb < c1; cb += CT) {
         const int m = (int)imin64(CT, c1 - cb);
         __syncthreads();                            // the pass before has been read
-        for (int e = tid; e < m * W; e += T) {
-            const int c = e / W, x = e - c * W;
-            cf[e] = x < d ? r[(cb + c) * ldr + x] : 0.f;
-        }
+        pd_stage<DV, T>(r, ldr, cb, m, d, cols, tid);
         if (grouped)
             for (int c = tid; c < m; c += T) grp[c] = rgroup[cb + c];
         __syncthreads();
         if (!valid) continue;                       // (the barriers above are reached by every thread of every pass)
-        auto dist = [&](int j) {
-            float a = 0.f;
-#pragma unroll
-            for (int v = 0; v < DV; ++v) {
-                const float4 y = cols[j * DV + v];
-                const float d0 = xi[v].x - y.x, d1 = xi[v].y - y.y, d2 = xi[v].z - y.z, d3 = xi[v].w - y.w;
-                a = __builtin_fmaf(d0, d0, a);
-                a = __builtin_fmaf(d1, d1, a);
-                a = __builtin_fmaf(d2, d2, a);
-                a = __builtin_fmaf(d3, d3, a);
-            }
-            return a;
-        };
+        auto dist = [&](int j) { return pd_dist2<DV>(xi, cols, j); };
         auto offer = [&](int j, float a) {
             const uint64_t key = ((uint64_t)__builtin_bit_cast(uint32_t, a) << 32) | (uint64_t)(uint32_t)(cb + j);
             if (key < worst && (!grouped || grp[j] != qg)) knn_insert(mine, k, key, worst);
@@ -225,19 +200,14 @@ int launch_knn(const float* q, int64_t ldq, int64_t nq, const float* r, int64_t 
     const int64_t nseg = cdiv64(nr, seg_cols);
     uint64_t* part = static_cast<uint64_t*>(ws);
     const dim3 grid((unsigned)nseg, (unsigned)cdiv64(nq, T)), block(T);
-#define KNN_CASE(V)                                                                                              \
-    case V:                                                                                                      \
-        hipLaunchKernelGGL(k_knn_partial<V>, grid, block, lds, st, q, ldq, nq, r, ldr, nr, d, k, qgroup, rgroup,   \
-                           seg_cols, nseg, part, idx, dist2);                                                    \
-        break;
     if (phases != KNN_PHASE_MERGE) {
-        switch (sil_dv(d)) {
-            KNN_CASE(1) KNN_CASE(2) KNN_CASE(3) KNN_CASE(4) KNN_CASE(6) KNN_CASE(8) KNN_CASE(12) KNN_CASE(16) KNN_CASE(24) KNN_CASE(32)
-            default: set_error("knn: no kernel for d = %d", d); return MMVAE_E_UNSUPPORTED;
-        }
+        if (int rc = pd_dispatch("knn", d, [&](auto dv) {
+                hipLaunchKernelGGL(k_knn_partial<decltype(dv)::value>, grid, block, lds, st, q, ldq, nq, r, ldr, nr, d, k, qgroup,
+                                   rgroup, seg_cols, nseg, part, idx, dist2);
+            }))
+            return rc;
         HIP_LAUNCH_CHECK("k_knn_partial");
     }
-#undef KNN_CASE
     if (nseg > 1 && phases != KNN_PHASE_PARTIAL) {
         hipLaunchKernelGGL(k_knn_merge, dim3((unsigned)cdiv64(nq, T)), block, lds, st, part, nseg, nq, k, idx, dist2);
         HIP_LAUNCH_CHECK("k_knn_merge");

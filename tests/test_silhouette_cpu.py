@@ -157,8 +157,14 @@ def test_launch_constants_are_those_of_the_source():
     assert const("SIL_MAX_D") == N.SILHOUETTE_MAX_D == 128
     dv = re.search(r"SIL_DV\[SIL_N_DV\] = \{([^}]*)\}", hpp).group(1)
     assert tuple(int(v) for v in dv.split(",")) == N.SILHOUETTE_DV and const("SIL_N_DV") == len(N.SILHOUETTE_DV)
-    hip = open(os.path.join(ROOT, "distributed-vae_amd", "csrc", "silhouette.hip")).read()
-    assert [int(v) for v in re.findall(r"SIL_CASE\((\d+)\)", hip)] == list(N.SILHOUETTE_DV)   # every table entry is built
+    # every table entry is built: the launchers instantiate through pd_dispatch, which spans all SIL_N_DV entries of SIL_DV
+    csrc = os.path.join(ROOT, "distributed-vae_amd", "csrc")
+    pd = open(os.path.join(csrc, "pairdist.hpp")).read()
+    body = pd[pd.index("pd_dispatch("):]
+    assert re.search(r"I\s*<\s*SIL_N_DV", body) and re.search(r"SIL_DV\[I\]", body) and re.search(r"pd_dispatch<I\s*\+\s*1>", body)
+    for src, kernel in (("silhouette.hip", "k_sil_partial"), ("knn.hip", "k_knn_partial")):
+        hip = open(os.path.join(csrc, src)).read()
+        assert len(re.findall(r"pd_dispatch\(", hip)) == 1 and len(re.findall(kernel + "<", hip)) == 1   # no instance outside the table
     # the d dispatch at its switch points: the last d of one instance and the first of the next
     assert [N.silhouette_dv(d) for d in (1, 4, 5, 8, 9, 12, 13, 16, 17, 24, 25, 32, 33, 48, 49, 64, 65, 96, 97, 128)] == \
         [1, 1, 2, 2, 3, 3, 4, 4, 6, 6, 8, 8, 12, 12, 16, 16, 24, 24, 32, 32]

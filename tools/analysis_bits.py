@@ -1,8 +1,10 @@
 """Bit identity of the device analysis routines across builds: silhouette, state-gene correlation, the Gaussian classifiers'
-group moments and scores, the Gram matrix, the PCA projection and data preparation (csrc/silhouette.hip, statecorr.hip,
-gaussclf.hip, pca.hip, dataprep.hip and the segment table they share, csrc/segments.hip).
+group moments and scores, the Gram matrix, the PCA projection, data preparation, the rank sums and k nearest neighbours
+(csrc/silhouette.hip, statecorr.hip, gaussclf.hip, pca.hip, dataprep.hip, ranksum.hip, knn.hip, the segment table,
+csrc/segments.hip, and the distance, csrc/pairdist.hpp, that some of them share).
 
-Every case calls the wrappers of distributed_vae_amd._native on inputs drawn from a seeded numpy.random.Generator(PCG64) and
+Every case calls the wrappers of distributed_vae_amd._native (the rank sums and k-NN: those of utils.marker_analysis and
+utils.neighbors) on inputs drawn from a seeded numpy.random.Generator(PCG64) and
 takes the SHA-256 of the raw bytes of every output tensor.  The kernels use no atomics and add in a fixed order, so equal
 digests are the gate of a change that must not alter what they compute.
 
@@ -15,7 +17,8 @@ Without --write the tool prints each case's verdict.
 The cases are the smallest shapes at which the shared pieces can go wrong:
   * silhouette: clusters of 1, 511, 512, 513, 0 and 1025 cells -- a singleton, both sides of SIL_SEG_COLS, an empty cluster
     and one of three segments -- at d = 3 and 5 (one and two float4 pieces a point), with and without the permutation, on
-    strided rows; and 300 clusters of 1-3 cells, where every thread of the table kernel owns two groups;
+    strided rows; d = 50 (sixteen pieces); and 300 clusters of 1-3 cells, where every thread of the table kernel owns two
+    groups;
   * state_corr: groups of 0, 1, 255, 256, 257 and 513 cells, D = 5 (a lane's quad reaches past D) and 257 (a second tile of
     one gene), S = 3 (a 2-state and a 1-state pass), with and without a row map, without offsets, narrow (a pitch that is
     no multiple of 4) and wide loads; and G = 300;
@@ -23,7 +26,19 @@ The cases are the smallest shapes at which the shared pieces can go wrong:
     every instance that admits them; and G = 300;
   * gauss_scores, gram (n = 257, D = 65, sums and covariance), pca_project, cpm_dense and cpm_csr (int32 and float32, with and
     without log1p, a gene subset) and gene_stats: one case each on a shuffled row map with repeats, narrow on a pitch that
-    is no multiple of 4 and wide on an aligned copy.
+    is no multiple of 4 and wide on an aligned copy;
+  * rank sums (rank_sum2, tie_term, n_pos and sum at eps = 0.0 and 0.1), on values rounded to one decimal with three zeros in
+    ten, so that ties are the rule, read through a shuffled row map with repeats from a strided view: the one-call path and
+    the blocked one with blocks of 128 and 32768 cells, on 65 cells in groups of 0, 64 and 1 (128 padded keys, a workgroup of
+    one wave), on 130 cells and 513 genes (a second gene chunk, a ninth gene tile of the staging copy), on groups of 1, 1024,
+    0, 1025 and 65 cells (both sides of RS_BIG) and on 300 groups of 1-3 cells (every wave walks several); the blocked path
+    alone on 4097 cells in blocks of 128 and 4096 (two tiles of k_rsb_rank, a last block of one cell);
+  * knn (idx and dist2), 130 queries (a partial third tile) against 700 references, on such values too, so that equal
+    distances are common: d = 3, 5 and 50 (1, 2 and 16 float4 pieces; 16 is the path without the four-wide unroll) by k = 1,
+    15 and 64 (15 is no multiple of the insert's chunk of 8), each without groups and with fold groups of 5, with the entry's
+    own segmentation, with seg_cols = 256 (three segments and the merge -- which the entry also chooses at this size) and
+    with seg_cols = 1024 (one segment: two staging passes at d = 3, no merge); once on strided rows; and knn_votes on a k = 15
+    result with 7 classes, qlabel and top2.
 """
 import argparse
 import hashlib
@@ -224,11 +239,75 @@ def _gene_stats(N, dev):
     return out
 
 
+def _quantised(rng, shape):
+    """Values on a grid of tenths, three in ten exactly zero: ties in value and in distance are common."""
+    a = np.round(rng.standard_normal(shape), 1).astype(np.float32)
+    a[rng.random(shape) < 0.3] = 0.0
+    return a
+
+
+def _rs(sizes, D, block, seed):
+    def run(N, dev):
+        from distributed_vae_amd.utils import marker_analysis as MA
+        rng = _rng(seed)
+        n = int(np.sum(sizes))
+        n_total = n + 37
+        x = _pitched(_quantised(rng, (n_total, D)), _narrow_ld(D), dev)
+        rows = _row_map(rng, n_total, n, dev)
+        out = {}
+        for eps in (0.0, 0.1):
+            res = MA.rank_sums(x, rows, _offsets(sizes, dev), eps, block_cells=block)
+            for key, t in zip(_RS_OUT, res):
+                out[f"eps{eps}/{key}"] = t
+        return out
+    return run
+
+
+def _knn_inputs(d, seed, dev, strided=False):
+    rng = _rng(seed)
+    nq, nr = 130, 700
+    q, r = _quantised(rng, (nq, d)), _quantised(rng, (nr, d))
+    qg = torch.as_tensor(rng.integers(0, 5, size=nq).astype(np.int32)).to(dev)
+    rg = torch.as_tensor(rng.integers(0, 5, size=nr).astype(np.int32)).to(dev)
+    if strided:
+        return _pitched(q, d + 2, dev), _pitched(r, d + 3, dev), qg, rg
+    return torch.as_tensor(q).to(dev), torch.as_tensor(r).to(dev), qg, rg
+
+
+def _knn(d, k, strided, seed):
+    def run(N, dev):
+        from distributed_vae_amd.utils import neighbors as NB
+        q, r, qg, rg = _knn_inputs(d, seed, dev, strided)
+        out = {}
+        for gname, groups in (("plain", (None, None)), ("fold", (qg, rg))):
+            for sname, seg in _KNN_SEGS[:1] if strided else _KNN_SEGS:
+                out[f"{gname}/{sname}/idx"], out[f"{gname}/{sname}/dist2"] = NB.knn_device(q, r, k, *groups, seg_cols=seg)
+        return out
+    return run
+
+
+def _knn_votes(N, dev):
+    from distributed_vae_amd.utils import neighbors as NB
+    q, r, _, _ = _knn_inputs(3, 103, dev)
+    rng = _rng(199)
+    rlabel = torch.as_tensor(rng.integers(0, 7, size=int(r.shape[0])).astype(np.int32)).to(dev)
+    qlabel = torch.as_tensor(rng.integers(0, 7, size=int(q.shape[0])).astype(np.int32)).to(dev)
+    idx, _ = NB.knn_device(q, r, 15)
+    pred, purity, top2 = NB.knn_votes_device(idx, rlabel, 7, qlabel, top2=True)
+    return {"pred": pred, "purity": purity, "top2": top2}
+
+
+_RS_OUT = ("rank_sum2", "tie_term", "n_pos", "sum")
+_RS_SHAPES = {"n65": ((0, 64, 1), 3), "n130_D513": ((65, 65), 513), "big_small": ((1, 1024, 0, 1025, 65), 17),
+              "g300": (tuple(int(v) for v in _small_groups(_rng(4), 300)), 5)}
+_KNN_SEGS = (("own", None), ("seg256", 256), ("seg1024", 1024))
+
 CASES = {}
 for _d in (3, 5):
     CASES[f"sil_d{_d}"] = _sil(SIL_SIZES, _d, False, 0, 10 + _d)
     CASES[f"sil_d{_d}_perm"] = _sil(SIL_SIZES, _d, True, 0, 10 + _d)
     CASES[f"sil_d{_d}_perm_strided"] = _sil(SIL_SIZES, _d, True, _d + 2, 10 + _d)
+CASES["sil_d50"] = _sil(SIL_SIZES, 50, False, 0, 60)
 CASES["sil_k300"] = _sil(tuple(int(v) for v in _small_groups(_rng(1), 300)), 3, True, 0, 19)
 for _D in (5, 257):
     CASES[f"sc_D{_D}_narrow_rows"] = _sc(SC_SIZES, _D, 3, True, True, "narrow", 20 + _D)
@@ -246,6 +325,16 @@ CASES["pca_project"] = _pca_project
 CASES["cpm_dense"] = _cpm_dense
 CASES["cpm_csr"] = _cpm_csr
 CASES["gene_stats"] = _gene_stats
+for _i, (_name, (_sizes, _D)) in enumerate(_RS_SHAPES.items()):
+    for _b in (None, 128, 32768):
+        CASES[f"rs_{_name}_{'one_call' if _b is None else 'b%d' % _b}"] = _rs(_sizes, _D, _b, 110 + _i)
+for _b in (128, 4096):
+    CASES[f"rs_n4097_b{_b}"] = _rs((1025, 3000, 72), 5, _b, 119)
+for _d in (3, 5, 50):
+    for _k in (1, 15, 64):
+        CASES[f"knn_d{_d}_k{_k}"] = _knn(_d, _k, False, 100 + _d)
+CASES["knn_d5_k15_strided"] = _knn(5, 15, True, 105)
+CASES["knnvotes"] = _knn_votes
 
 _PATHS2 = ("narrow", "wide")
 _KEYS = {
@@ -255,6 +344,10 @@ _KEYS = {
     "cpm_dense": tuple(f"{t}/{p}/log{g}/{a}" for t in ("int32", "float32") for p in _PATHS2 for g in (0, 1) for a in ("out", "norms")),
     "cpm_csr": tuple(f"{t}/log{g}/{a}" for t in ("int32", "float32") for g in (0, 1) for a in ("out", "norms")),
     "gene_stats": tuple(f"{p}/{a}" for p in _PATHS2 for a in ("n_above", "mean", "std")),
+    "rs": tuple(f"eps{e}/{a}" for e in (0.0, 0.1) for a in _RS_OUT),
+    "knn": tuple(f"{g}/{s}/{a}" for g in ("plain", "fold") for s, _ in _KNN_SEGS for a in ("idx", "dist2")),
+    "knn_d5_k15_strided": tuple(f"{g}/own/{a}" for g in ("plain", "fold") for a in ("idx", "dist2")),
+    "knnvotes": ("pred", "purity", "top2"),
 }
 
 

@@ -12,7 +12,9 @@ sizes, on synthetic-10x-style data (bench.py's ``synthetic_rows``: 20 % of the e
   * on the host of the same run, where scipy is importable, ``scipy.stats.mannwhitneyu`` per (gene, group) on a SAMPLE of
     genes, extrapolated to all D (labelled ``extrapolated``);
   * the kernel at the cap, n = 32 768, on the same kind of data and on data without a single tie (the worst case: every search
-    runs its full depth and nothing in the sort is already in place).
+    runs its full depth and nothing in the sort is already in place);
+  * both entries (the blocked one with blocks of 32 768 cells) at the most groups a call takes: n = 8192, D = 512, G = 4096
+    groups of two cells.
 
     python tools/time_ranksum.py [--repeats R] [--sample GENES] [--out profiles/ranksum_time.json]
 
@@ -328,6 +330,14 @@ def main():
     r2_d, tie_d, _, _ = MA.rank_sums(distinct, order_c, offsets_c)
     res["cap_n32768"]["no_ties_kernel_ms"] = _median_ms(_entry_call(distinct, order_c, offsets_c), few)
     res["cap_n32768"]["no_ties_tie_term_is_zero"] = bool((tie_d == 0).all())
+    del distinct, perm
+    # the most groups a call takes: every wave of the group walk owns 256 groups of two cells, none is a large one
+    n_g, D_g, G_g = 8192, 512, MA.MAX_GROUPS
+    many = synthetic_rows(n_g, D_g, 550, dev)
+    order_g, offsets_g = _device_groups(np.repeat(np.arange(G_g), 2), np.full(G_g, 2), dev)
+    res["g4096_n8192_D512"] = {"ms": _alternating_ms({"mmvae_rank_sum": _entry_call(many, order_g, offsets_g),
+                                                      "blocked_block_32768": _blocked_call(many, order_g, offsets_g, 32768)[0]},
+                                                     args.repeats)}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=1)
